@@ -8,6 +8,7 @@ step of the whole box (fused kick/drift pass + LJ force pass, rebuilds included)
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--cells n] [--precision f64|f32]
                   [--rc 2.5] [--mixture] [--rebuild-every 0] [--no-cpu-baseline] [--scaling strong|weak]
+                  [--dump-outputs DIR]
 
 N = 1: fcc 136^3 x 4 = 10,061,824 atoms (the 10^7-atom config the metric is quoted on) on one GPU.
 N > 1: one rank per GPU, spatial domain decomposition with ghost-atom halo exchange over RCCL.  Either the
@@ -44,6 +45,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+DUMP_MAX_ATOMS = 500_000      # --dump-outputs: 3 (N, 3) float64 arrays + the ids of 5e5 atoms = 40 MB, under 64 MB
+DUMP_SEED = 20240901
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); 6.29 TB/s measured copy ceiling
 RHO = 0.8
 
@@ -112,6 +115,10 @@ def parse_args():
                          "N > 1 runs of the default 136-cell box; 0 = skip")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: strong = the same --cells^3x4 box on N GPUs (default); weak = one such brick per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they ended in (positions, velocities, forces of a fixed, "
+                         "seeded sample of at most %d atoms, in atom order, and the energy totals) as DIR/<name>.npy, "
+                         "so that two builds can be compared output for output" % DUMP_MAX_ATOMS)
     return ap.parse_args()
 
 
@@ -393,6 +400,48 @@ def cache_path(args):
     key = "c%d_%s_rc%g_skin%g_dt%g%s%s" % (args.cells, args.precision, args.rc, args.skin, args.dt,
                                           "_mix" if args.mixture else "", "_re%d" % args.rebuild_every if args.rebuild_every else "")
     return os.path.join(ROOT, ".bench_cache", "onegpu_%s.json" % key)
+
+
+def dump_sample_ids(n_total):
+    """Global atom ids --dump-outputs writes: all of them up to DUMP_MAX_ATOMS, else a fixed, seeded sample (sorted)."""
+    if n_total <= DUMP_MAX_ATOMS:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_total, DUMP_MAX_ATOMS, replace=False))
+
+
+def dump_outputs(outdir, parts, totals, n_total, dist=None, world=1, rank=0):
+    """--dump-outputs: `parts` holds (gid, positions, velocities, forces) device tensors of the atoms this process owns after
+    the timed steps; the sampled rows of every part (of every rank) are written by rank 0 in ascending global id, in the
+    precision of the run, with the ids (atom_index, float64) and the energy totals (potential, kinetic, virial)."""
+    import torch
+    ids = dump_sample_ids(n_total)
+    mine = []
+    for gid, x, v, f in parts:
+        if ids is not None:
+            keep = torch.isin(gid, torch.as_tensor(ids, dtype=gid.dtype, device=gid.device))
+            gid, x, v, f = gid[keep], x[keep], v[keep], f[keep]
+        mine.append(tuple(t.detach().cpu().numpy() for t in (gid, x, v, f)))
+    if dist is not None:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, mine)
+        mine = [p for g in gathered for p in g]
+    if rank != 0:
+        return
+    gid = np.concatenate([p[0] for p in mine]).astype(np.int64)
+    order = np.argsort(gid, kind="stable")
+    want = np.arange(n_total) if ids is None else ids
+    if not np.array_equal(gid[order], want):
+        raise SystemExit("--dump-outputs: the owned atoms of the domains do not add up to the box (%d rows for %d ids)"
+                         % (gid.size, want.size))
+    arrays = {"atom_index": gid[order].astype(np.float64),
+              "positions": np.concatenate([p[1] for p in mine])[order],
+              "velocities": np.concatenate([p[2] for p in mine])[order],
+              "forces": np.concatenate([p[3] for p in mine])[order],
+              "energy_totals": np.asarray(totals, dtype=np.float64)}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+    print("bench.py: wrote %s (%d of %d atoms) to %s" % (", ".join(sorted(arrays)), want.size, n_total, outdir), file=sys.stderr)
 
 
 def main():
@@ -739,6 +788,17 @@ def main():
                                  "profiled_clock_ghz": t.get("profiled_clock_ghz"),
                                  "frac_at_profiled_clock": t.get("frac_at_profiled_clock"),
                                  "valu_busy_fraction": t.get("valu_busy_fraction")}
+    if args.dump_outputs:
+        if domain is None:
+            st = md.state()
+            parts = [(torch.arange(N_total, dtype=torch.int64, device=dev), st["positions"][:N_total], st["velocities"],
+                      st["forces"])]
+        elif native_dd:
+            parts = [domain.state(l) for l in (range(args.domains) if world == 1 else [0])]
+        else:
+            parts = [domain.gather_state()]
+        dump_outputs(args.dump_outputs, parts, (ep, ek, vir), N_total, dist, world, rank)
+        del parts
     # ---- the north-star target box (>= 10^8 atoms) on the same ranks: a second, smaller measurement riding on the N > 1
     # runs, so that the driver's 1/2/4/8-GPU sweep also yields the strong-scaling curve of the target size.  `value` above
     # stays the BASELINE metric (the 10^7-atom box); a failure here is reported inside the object and changes nothing else.

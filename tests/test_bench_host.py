@@ -249,3 +249,42 @@ def test_a_line_only_carries_the_issue_floor_of_its_own_kernel():
     only_head = [dict(head)]
     assert bench.pick_valu(only_head, N, "f64", 3.5, True) is None and bench.pick_valu(only_head, N, "f32", 2.5, False) is None
     assert bench.pick_valu([dict(head, issue_floor_ms=None)], N, "f64", 2.5, False) is None
+
+
+def test_dump_outputs_writes_the_box_in_atom_order(bench, tmp_path):
+    """--dump-outputs: the owned atoms of several domains, in whatever order the domains hold them, come out as ONE set of
+    arrays in ascending global id, in the precision of the run, with the ids and the energy totals."""
+    import torch
+    n = 50
+    gid = torch.randperm(n, generator=torch.Generator().manual_seed(3))
+    x = torch.arange(3 * n, dtype=torch.float64).reshape(n, 3)[gid]          # row i of the box holds 3i, 3i+1, 3i+2
+    v, f = -x, 2.0 * x
+    parts = [(gid[:20], x[:20], v[:20], f[:20]), (gid[20:], x[20:], v[20:], f[20:])]
+    bench.dump_outputs(str(tmp_path), parts, (-1.5, 2.5, 0.25), n)
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(got) == {"atom_index", "positions", "velocities", "forces", "energy_totals"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["atom_index"], np.arange(n, dtype=np.float64))
+    assert np.array_equal(got["positions"], np.arange(3 * n, dtype=np.float64).reshape(n, 3))
+    assert np.array_equal(got["velocities"], -got["positions"]) and np.array_equal(got["forces"], 2.0 * got["positions"])
+    assert np.array_equal(got["energy_totals"], [-1.5, 2.5, 0.25])
+    with pytest.raises(SystemExit):                                         # a domain missing: refused, not written short
+        bench.dump_outputs(str(tmp_path / "short"), parts[:1], (0.0, 0.0, 0.0), n)
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(bench, tmp_path, monkeypatch):
+    """A box larger than DUMP_MAX_ATOMS is written as the same seeded sample every time, within 64 MB at the largest."""
+    import torch
+    big = 4 * 136 ** 3
+    ids = bench.dump_sample_ids(big)
+    assert np.array_equal(ids, bench.dump_sample_ids(big)) and ids.size == bench.DUMP_MAX_ATOMS
+    assert np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < big
+    assert bench.DUMP_MAX_ATOMS * (3 * 3 * 8 + 8) + 3 * 8 <= 64 * 2 ** 20
+    monkeypatch.setattr(bench, "DUMP_MAX_ATOMS", 40)
+    n = 1000
+    gid = torch.arange(n - 1, -1, -1)
+    x = gid.to(torch.float32)[:, None].repeat(1, 3)
+    bench.dump_outputs(str(tmp_path), [(gid, x, x, x)], (0.0, 0.0, 0.0), n)
+    idx, pos = np.load(tmp_path / "atom_index.npy"), np.load(tmp_path / "positions.npy")
+    assert np.array_equal(idx, bench.dump_sample_ids(n).astype(np.float64)) and idx.size == 40
+    assert pos.dtype == np.float32 and np.array_equal(pos[:, 0], idx.astype(np.float32))

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from .conftest import ROOT
@@ -129,3 +130,45 @@ def test_worked_examples_run(tmp_path):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", script)] + args, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, script + ": " + r.stdout[-600:] + r.stderr[-1200:]
         assert "relative energy change" in r.stdout or "energy" in r.stdout, r.stdout[-600:]
+
+
+def test_dump_outputs_hold_the_state_after_the_timed_steps(tmp_path, oracle):
+    """--dump-outputs writes the state the timed steps ended in: warm-up + --steps velocity-Verlet steps of the benchmark
+    box, which the CPU oracle reproduces from the same seeded inputs (so --steps really sets the number of steps)."""
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    d = _bench("--cells", "12", "--steps", "10", "--warmup", "4", "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
+    got = {name: np.load(tmp_path / (name + ".npy")) for name in ("atom_index", "positions", "velocities", "forces", "energy_totals")}
+    n = 4 * 12 ** 3
+    assert d["config"]["atoms"] == n and np.array_equal(got["atom_index"], np.arange(n, dtype=np.float64))
+    p0, L = pkg.synthetic.fcc_positions(12)
+    v0 = pkg.synthetic.velocities(n)
+    ref = oracle.verlet(p0, v0, L, oracle.model(2.5, 2.0), pkg.lennard_jones_atoms(1.0, 1.0, n), 0.005, 14)
+    dx = got["positions"] - ref["x"]
+    dx -= L * np.round(dx / L)                                     # either side may have wrapped an atom into the box
+    assert np.abs(dx).max() < 1e-8
+    assert np.abs(got["velocities"] - ref["v"]).max() < 1e-8
+    assert np.abs(got["forces"] - ref["f"]).max() < 1e-7 * np.abs(ref["f"]).max()
+    ep, ek, _ = got["energy_totals"]
+    assert ep == pytest.approx(ref["epot"][-1], rel=1e-9) and ek == pytest.approx(ref["ekin"][-1], rel=1e-9)
+    assert ep / n == pytest.approx(d["energy_per_atom"]["potential"], rel=1e-12)
+
+
+def test_dump_outputs_of_the_decomposed_box_match_the_single_gpu_box(tmp_path):
+    """The native decomposition (all domains in this process) dumps the same box, gathered from its domains into atom
+    order: the same atoms, and the same state as the undivided run to rounding."""
+    one, two = tmp_path / "one", tmp_path / "two"
+    _bench("--cells", "12", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--dump-outputs", str(one))
+    _bench("--domains", "2", "--cells", "12", "--target-cells", "0", "--steps", "8", "--warmup", "4", "--no-cpu-baseline",
+           "--dump-outputs", str(two))
+    a = {p.stem: np.load(p) for p in one.glob("*.npy")}
+    b = {p.stem: np.load(p) for p in two.glob("*.npy")}
+    assert set(a) == set(b) == {"atom_index", "positions", "velocities", "forces", "energy_totals"}
+    assert np.array_equal(a["atom_index"], b["atom_index"]) and a["atom_index"].size == 4 * 12 ** 3
+    L = (4 * 12 ** 3 / 0.8) ** (1.0 / 3.0)
+    dx = a["positions"] - b["positions"]
+    dx -= L * np.round(dx / L)
+    assert np.abs(dx).max() < 1e-9
+    assert np.abs(a["velocities"] - b["velocities"]).max() < 1e-9
+    assert np.abs(a["forces"] - b["forces"]).max() < 1e-8 * np.abs(a["forces"]).max()
+    assert b["energy_totals"][:2] == pytest.approx(a["energy_totals"][:2], rel=1e-9)
