@@ -41,11 +41,7 @@ namespace emdee {
 enum BrickMode { BRICK_FORCE = 1, BRICK_STATS = 2, BRICK_STEP = 3 };
 
 // a loop the compiler must leave as written (no unrolling, no interleaving of trips behind run-time alias checks)
-#ifndef EMDEE_NO_PLAIN_LOOPS
 #define EMDEE_PLAIN_LOOP _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
-#else
-#define EMDEE_PLAIN_LOOP
-#endif
 
 constexpr int EPL = 8;   // neighbour entries per lane per 16-byte load
 // entries the force kernels read of every row without looking at its length: the NPF prefetched blocks of 8 G entries
@@ -113,9 +109,6 @@ struct BrickArgs {
     int *flags;                // [0] row overflow (max count), [2] tile overflow
     real rlist2;
     float margin;              // build: half-width of the fp32 rounding band around rlist2
-    // near/far build (ALG 23): tile coordinates are scaled by nf_scale = k so that k^2 (r_near^2 - r_list^2) = -2.0 exactly --
-    // the class of a candidate is then the top two bits of the float k^2 (d^2 - r_list^2): sign = listed, sign and |.| >= 2 = near
-    float nf_scale, nf_scale2;
     LJModel<real> model;
     size_t pitch;
     real *frc, *en, *vir;
@@ -156,17 +149,10 @@ struct BrickArgs {
     int nsub, sub_k;
     const int *fstart;
     int *bsub;
-    // near/far rows with the far class skipped outright (round 5 experiment, EMDEE_FAR_SKIP=1 on top of EMDEE_BUILD_NEARFAR=1):
-    // cnt[p] = total | near << 8, and while NO atom has moved delta / 2 since the build (*far_word == 0: raised like the
-    // rebuild trigger, by the launch that produced the positions, read by the next one) a row ends at its near entries -- an
-    // entry beyond r_c + delta at the build cannot be inside r_c before two atoms have moved delta / 2 each: the same sums
     // cell-relative records (kernels.hpp RelGrid; fp32 integrators): a record is relative to the origin of its cell, and a tile
     // coordinate is record + (tile cell - brick origin) cell widths -- no image shift, no box-sized number anywhere
     int rel;
     double rcw[3], rlo[3];
-    int far_skip;
-    int *far_word;
-    real thr2_near;
     const real *user_pos;      // ... read from the CALLER's array (3 x N, caller order): the engine's records hold positions wrapped
                                // into the box, and x - L rounded to fp32 is not the number the reference divides by L
 };
@@ -226,11 +212,8 @@ constexpr int SOA_SLOTS = 2048;                      // records a coordinate-pla
 // Plane pitch in records.  fp64: one record more than a power of two, so that the x and y reads of a neighbour cannot be
 // merged into one ds_read2st64_b64 (8 LDS-array cycles per wavefront, MI355X_MICROARCH.md LDS table) and stay two
 // ds_read_b64 (2 cycles each) off one address register with immediate offsets.
-#ifndef EMDEE_SOA_PAD
-#define EMDEE_SOA_PAD 1
-#endif
 template <typename real>
-constexpr int soa_pitch() { return SOA_SLOTS + ((sizeof(real) == 8 && EMDEE_SOA_PAD) ? 1 : 0); }
+constexpr int soa_pitch() { return SOA_SLOTS + (sizeof(real) == 8 ? 1 : 0); }
 template <typename real, class Shape, int THREADS>
 static inline size_t brick_force_lds_bytes_soa(int own_cap) {
     return (((size_t)3 * soa_pitch<real>() * sizeof(real) + 15) & ~(size_t)15) + BrickTables<Shape, THREADS>::bytes(own_cap);
@@ -508,11 +491,11 @@ constexpr int OWN_REGS = 2;   // own atoms per thread whose table entry is fetch
 // ------------------------------------------------------------------------------------ build
 // ALG 1: candidates are dealt round-robin to the lanes of a group and every pass of the test loop
 // compacts its hits with a ballot (count, prefix, scattered 2-byte LDS store: more VALU work than the
-// distance test itself).  ALG 2 (default when no 3-cell tile row holds more than BUILD2_MAX_SPAN atoms):
-// each lane tests a CONTIGUOUS chunk of every tile row and only records one bit per candidate; the hits
-// are compacted once per atom, from the bit fields, after a prefix sum over the lanes of the group.  Rows
+// distance test itself).  ALG 3 / 5, the two-phase build (chosen when no 3-cell tile row is too long for the bit
+// fields of its lanes): each lane tests a CONTIGUOUS chunk of every tile row and only records one bit per candidate;
+// the hits are compacted once per atom, from the bit fields, after a prefix sum over the lanes of the group.  Rows
 // come out ordered lane by lane, i.e. still along the tile rows, so neighbouring entries keep pointing at
-// neighbouring tile slots.
+// neighbouring tile slots.  ALG 13 / 15 deal the candidates to the lanes round-robin instead.
 constexpr int BUILD2_FIELD = 16;                      // bits per tile row in a lane's bit field
 
 // G = lanes that share one atom HERE; GL = lanes per atom of the force kernels, which fixes the lane-major row
@@ -529,7 +512,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
     if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     // x sub-bins (the two-phase builds that take their candidate rows from the row table): rows per own cell AND sub-bin
-    constexpr bool SUBOK = ALG == 3 || ALG == 5 || ALG == 13 || ALG == 15 || ALG == 23;
+    constexpr bool SUBOK = ALG == 3 || ALG == 5 || ALG == 13 || ALG == 15;
     const int NSUB = (SUBOK && a.nsub == 4 && a.bsub != nullptr) ? 4 : 1;
     // (one word per row: first slot | slots << 16 -- a tile holds < 2^16 slots; the build's LDS decides whether a CU takes
     // three workgroups.  The sub-bin boundaries of the tile cells are only needed until the row table is written: they
@@ -579,12 +562,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
         const int sh = T.shift[tc];
         const Rec<real> r = a.rec[gp];
         float4 q;
-        if constexpr (ALG == 23) {   // (scaled in the box's own precision, one rounding to fp32 as before)
-            const real ks = (real)a.nf_scale;
-            q.x = (float)(((r.x + (real)((sh & 3) - 1) * a.g.len[0]) - org[0]) * ks);
-            q.y = (float)(((r.y + (real)(((sh >> 2) & 3) - 1) * a.g.len[1]) - org[1]) * ks);
-            q.z = (float)(((r.z + (real)(((sh >> 4) & 3) - 1) * a.g.len[2]) - org[2]) * ks);
-        } else if (sizeof(real) == 4 && a.rel) {              // cell-relative records: the tile coordinates the force kernels see, to the bit
+        if (sizeof(real) == 4 && a.rel) {              // cell-relative records: the tile coordinates the force kernels see, to the bit
             q.x = (float)rel_tile(r.x, s_relc[tx]);
             q.y = (float)rel_tile(r.y, s_relc[TX + ty]);
             q.z = (float)rel_tile(r.z, s_relc[TX + TY + tz]);
@@ -665,210 +643,8 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
         return pass;
     };
     auto in_range = [&](const float4 &qi, int p, int c, int tcr) -> bool { return in_range_q(qi, tile[c], p, c, tcr); };
-    if constexpr (ALG == 23) {
-        // ---- ALG 13 with NEAR entries first --------------------------------------------------------------------------
-        // The force kernels run their 31-instruction pair body whenever ANY of the 64 lanes of a wavefront is inside the
-        // cutoff, and 29 % of a row are skin entries (r_c <= d < r_list when the list is built).  Rows are therefore
-        // written near entries first (d < r_near = r_c + delta), far entries behind them: the lanes of a wavefront walk
-        // their rows in step, so its last pair steps see far entries in every lane -- pairs that only come inside the
-        // cutoff if both atoms use up most of the skin -- fail the cutoff test wave-wide and skip the body.  The force
-        // kernels need no change (the cutoff test decides, as ever); only the ORDER of a row differs.
-        // The class of a candidate costs nothing: with the tile scaled by k, k^2 (r_near^2 - r_list^2) = -2.0, the top two
-        // bits of the float t = k^2 (d^2 - r_list^2) are {t < 0 : listed, |t| >= 2 : near}, and ONE v_alignbit_b32 shifts
-        // both into the lane's digit string (the two-instruction compare + add-with-carry of ALG 13 did one bit).
-        static_assert(G == 8 && sizeof(unsigned) == 4, "near/far build: 8 lanes per atom");
-        constexpr int NROWS = 9, LOG2G = 3;
-        constexpr bool BAND = sizeof(real) == 8;
-        float nrl2 = -rl2 * a.nf_scale2, margin_v = a.margin * a.nf_scale2;
-        asm volatile("" : "+v"(nrl2), "+v"(margin_v));
-        const int kshift = a.idx_shift + LOG2G;                  // digit j of a row is tile slot cb + (trips - 1 - j) G
-        for (int ob = 0; ob < n_own; ob += NGROUPS) {            // wave-uniform trip count
-            const int o = ob + gid;
-            const bool have = o < n_own;
-            const int2 info = have ? T.oinfo[o] : make_int2(0, 0);
-            const int ti = info.y & 0xffff, p = info.x, oc = info.y >> 20;
-            const bool act = have && ((info.y >> 16) & 1) != 0;   // ghosts own no row
-            const float4 qi = tile[ti];
-            unsigned short *row = a.nbr + (size_t)p * a.stride;
-            for (int c = gl * EPL; c < a.stride; c += G * EPL) *reinterpret_cast<uint4 *>(rowbuf + c) = fill;
-            const unsigned *rt = rtab + (act ? oc * NSUB + ((info.y >> 17) & 3) : Shape::NOC * NSUB) * 9;   // (x sub-bins: as ALG 13)
-            int trips_of[NROWS];
-            {   // wave-uniform trip counts of the nine rows from one reduction (as ALG 13)
-                int cv = (int)((unsigned)(rt_get(rt, min(gl, NROWS - 1)).y + G - 1) / (unsigned)G);
-                int c8 = (int)((unsigned)(rt_get(rt, NROWS - 1).y + G - 1) / (unsigned)G);
-                cv = max(cv, __builtin_amdgcn_update_dpp(0, cv, 0x128 /* row_ror:8 */, 0xf, 0xf, true));
-                c8 = max(c8, __builtin_amdgcn_update_dpp(0, c8, 0x128, 0xf, 0xf, true));
-                auto rows_max = [](int v) {
-                    auto q = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-                    v = max((int)q[0], (int)q[1]);
-                    q = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-                    return max((int)q[0], (int)q[1]);
-                };
-                cv = rows_max(cv);
-                c8 = rows_max(c8);
-#pragma unroll
-                for (int r = 0; r < NROWS; r++)
-                    trips_of[r] = (r == NROWS - 1) ? __builtin_amdgcn_readlane(c8, 0) : __builtin_amdgcn_readlane(cv, r);
-            }
-            unsigned D[NROWS];                                   // two bits per candidate of my share of each tile row
-            int2 rv_next = rt_get(rt, 0);
-#pragma unroll
-            for (int r = 0; r < NROWS; r++) {
-                const int c0 = rv_next.x, span = rv_next.y;
-                if (r + 1 < NROWS) rv_next = rt_get(rt, r + 1);
-                const int lim = (int)((unsigned)(span - gl + G - 1) >> LOG2G);   // my candidates: slots cb + k G, k < lim (may be <= 0)
-                const int cb = c0 + gl;
-                const int trips = trips_of[r];                    // <= 16 (host check: a tile row holds <= 16 G atoms)
-                unsigned bits = 0;
-                const float4 *cand = tile + cb;
-                auto dist = [&](const float4 &q) {
-                    const float dx = qi.x - q.x, dyy = qi.y - q.y, dzz = qi.z - q.z;
-                    float t = __builtin_fmaf(dx, dx, nrl2);
-                    t = __builtin_fmaf(dyy, dyy, t);
-                    return __builtin_fmaf(dzz, dzz, t);
-                };
-                // rounding band (fp64 boxes): decided with the exact fp64 records (a far entry if listed)
-                auto exact = [&](float &t, int gpj, int k) {
-                    if (__builtin_fabsf(t) <= margin_v && k < lim) {
-                        int kq = k;
-                        asm volatile("" : "+s"(kq));
-                        const int c = cb + kq * G;
-                        int occ = oc;
-                        asm volatile("" : "+v"(occ));
-                        const int tcr = occ % BX + TX * (((occ / BX) % BY + r % 3) + TY * (occ / (BX * BY) + r / 3));
-                        const int tc = tcr + (c >= T.off[tcr + 1] ? 1 : 0) + (c >= T.off[tcr + 2] ? 1 : 0);
-                        const int sh = T.shift[tc];
-                        const Rec<real> ri = a.rec[p], rj = a.rec[gpj];
-                        const real ex = ri.x - (rj.x + (real)((sh & 3) - 1) * a.g.len[0]);
-                        const real ey = ri.y - (rj.y + (real)(((sh >> 2) & 3) - 1) * a.g.len[1]);
-                        const real ez = ri.z - (rj.z + (real)(((sh >> 4) & 3) - 1) * a.g.len[2]);
-                        t = (ex * ex + ey * ey + ez * ez < a.rlist2) ? -1.f : 1.f;
-                    }
-                };
-                auto shift_in = [&](float t) { bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(t), 30); };   // bits = bits << 2 | t >> 30
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (int k = 0; k + 1 < trips; k += 2) {             // (reads past my share / the tile: harmless)
-                    float4 q[2];
-                    float t[2];
-                    q[0] = cand[k * G]; q[1] = cand[(k + 1) * G];
-                    if constexpr (!BAND) { asm volatile("" : : "v"(q[0].w)); asm volatile("" : : "v"(q[1].w)); }
-                    t[0] = dist(q[0]); t[1] = dist(q[1]);
-                    if constexpr (BAND) {
-                        const float tm = __builtin_fminf(__builtin_fabsf(t[0]), __builtin_fabsf(t[1]));
-                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(tm <= margin_v) != 0, 0)) {
-                            exact(t[0], __float_as_int(q[0].w), k);
-                            exact(t[1], __float_as_int(q[1].w), k + 1);
-                        }
-                    }
-                    shift_in(t[0]); shift_in(t[1]);
-                }
-                if (trips & 1) {
-                    const float4 q = cand[(trips - 1) * G];
-                    if constexpr (!BAND) asm volatile("" : : "v"(q.w));
-                    float t = dist(q);
-                    if constexpr (BAND) {
-                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(__builtin_fabsf(t) <= margin_v) != 0, 0))
-                            exact(t, __float_as_int(q.w), trips - 1);
-                    }
-                    shift_in(t);
-                }
-                // candidate k sits at digit trips - 1 - k: what lies past my share (k >= lim) is the low trips - lim digits
-                const int drop = 2 * (trips - max(lim, 0));
-                bits = drop >= 32 ? 0u : ((bits >> drop) << drop);
-                if (r == 4) {                                         // the atom itself (its cell is the middle one of row 4)
-                    const int d = ti - c0;
-                    if ((d & (G - 1)) == gl) bits &= ~(3u << (2 * (trips - 1 - (d >> LOG2G))));
-                }
-                D[r] = bits;
-            }
-            // ---- phase 2: near entries of all lanes first, far entries behind them --------------------------------------
-            int mineN = 0, mineH = 0;
-#pragma unroll
-            for (int r = 0; r < NROWS; r++) {
-                const unsigned H = (D[r] >> 1) & 0x55555555u;         // listed: the sign bit of t
-                mineH += __popc(H);
-                mineN += __popc(H & D[r]);                            // ... and |t| >= 2
-            }
-            const int mineF = mineH - mineN;
-            auto group_prefix = [&](int v) {
-                int t = __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR1, 0xf, 0xf, true);
-                v += gl >= 1 ? t : 0;
-                t = __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR2, 0xf, 0xf, true);
-                v += gl >= 2 ? t : 0;
-                t = __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR4, 0xf, 0xf, true);
-                v += gl >= 4 ? t : 0;
-                return v;
-            };
-            const int inclN = group_prefix(mineN), inclF = group_prefix(mineF);
-            const int totalN = __shfl(inclN, lane | (G - 1));
-            unsigned short *epN = rowbuf + (unsigned)(inclN - mineN), *epF = rowbuf + (unsigned)(totalN + inclF - mineF);
-            unsigned short *const ep_last = rowbuf + (ustride - 1u);
-            // Round 4: TEN emission loops instead of eighteen.  The listed / near masks of a row have their digits at the EVEN bit
-            // positions (digit j at bit 2 j), so the masks of two rows fit one word, the second shifted to the odd positions;
-            // the pairs are OPPOSITE rows, (dy, dz) with (-dy, -dz) -- their hits add up to nearly the same number for every atom,
-            // and a loop runs as long as the busiest of 64 lanes -- and row 4 stays alone.  Bit b of a word: row A (b even) or B
-            // (b odd), digit b >> 1 = tile slot c0 + gl + (trips - 1 - j) G.
-#pragma unroll
-            for (int w = 0; w < 5; w++) {
-                const int rA = w, rB = 8 - w;
-                const unsigned HA = (D[rA] >> 1) & 0x55555555u;
-                unsigned WN = HA & D[rA], WF = HA & ~D[rA];
-                int baseA = (rt_get(rt, rA).x + gl + (trips_of[rA] - 1) * G) << a.idx_shift, dBA = 0;
-                if (w < 4) {
-                    const unsigned HB = (D[rB] >> 1) & 0x55555555u;
-                    WN |= (HB & D[rB]) << 1;
-                    WF |= (HB & ~D[rB]) << 1;
-                    dBA = ((rt_get(rt, rB).x + gl + (trips_of[rB] - 1) * G) << a.idx_shift) - baseA;
-                }
-                asm volatile("" : "+v"(baseA), "+v"(dBA));
-#ifdef EMDEE_BUILD_ABLATE      // timing experiments only (the lists are wrong): 2 no emission
-                if (EMDEE_BUILD_ABLATE & 2) { WN = 0; WF = 0; }
-                if (EMDEE_BUILD_ABLATE & 32) { WN |= WF; WF = 0; }     // 32: one class (all hits through the near loops)
-#endif
-                auto entry = [&](int b) {                              // base of the row the bit belongs to, minus the digit's step
-                    // (a shift, not a multiply: v_mul_lo_u32 is a quarter-rate instruction, and the compiler picks it for a product)
-                    return baseA + ((b & 1) ? dBA : 0) - ((b >> 1) << kshift);
-                };
-                while (WN) {
-                    const int b = __ffs((int)WN) - 1;
-                    WN &= WN - 1;
-                    asm volatile("" : "+v"(WN));
-                    *(epN < ep_last ? epN : ep_last) = (unsigned short)entry(b);
-                    epN++;
-                }
-                while (WF) {
-                    const int b = __ffs((int)WF) - 1;
-                    WF &= WF - 1;
-                    asm volatile("" : "+v"(WF));
-                    *(epF < ep_last ? epF : ep_last) = (unsigned short)entry(b);
-                    epF++;
-                }
-            }
-            if (have && EMDEE_BOUND(BS_BUILD_ROW, p, a.n)) {
-                constexpr int BLKL = EPL * GL;                // entries per lane-major block of the force kernels' rows
-                // (left to itself the compiler interleaves two trips of this loop behind a run-time alias check and splits each
-                // 16-byte store into four: 130 instructions per atom where 40 do -- the flush was 0.32 ms of the build for that)
-                EMDEE_PLAIN_LOOP
-                for (int c = gl * EPL; c < a.stride; c += G * EPL) {
-                    const unsigned short *src = rowbuf + (c / BLKL) * BLKL + (c % BLKL) / EPL;   // entries src[GL t], t = 0..7
-                    uint4 q;
-                    q.x = (unsigned)src[0 * GL] | ((unsigned)src[1 * GL] << 16);
-                    q.y = (unsigned)src[2 * GL] | ((unsigned)src[3 * GL] << 16);
-                    q.z = (unsigned)src[4 * GL] | ((unsigned)src[5 * GL] << 16);
-                    q.w = (unsigned)src[6 * GL] | ((unsigned)src[7 * GL] << 16);
-                    *reinterpret_cast<uint4 *>(row + c) = q;
-                }
-                if (gl == G - 1) {                            // the last lane's inclusive prefixes add up to the row length
-                    const unsigned total = (unsigned)(inclN + inclF);
-                    a.cnt[p] = act ? (int)(min(total, ustride) | (a.far_skip ? (min((unsigned)inclN, ustride) << 8) : 0u)) : 0;
-                    if (total > ustride) atomicMax(&a.flags[0], (int)total);
-                }
-            }
-        }
-        return;
-    }
     if constexpr (ALG % 10 == 3 || ALG % 10 == 5) {   // ALG 13 / 15: the same with candidates dealt round-robin (below)
-        // ALG 2 with a leaner candidate loop (the build is VALU-issue bound: 2.7 G wave-instructions per rebuild at
+        // The candidate loop is lean (the build is VALU-issue bound: 2.7 G wave-instructions per rebuild at
         // 10^7 atoms, profiles/r02): the trip count of a tile row is made WAVE-uniform (the longest chunk in the
         // wavefront; a lane whose chunk is shorter tests slots past its chunk and drops those bits afterwards), so
         // the loop needs no per-lane exit bookkeeping on the execution mask; the hit bit is shifted in by the carry
@@ -880,26 +656,16 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
         constexpr int FIELD = ALG % 10 == 3 ? BUILD2_FIELD : 32, PER = 32 / FIELD;
         constexpr int NROWS = 9, NWORDS = (NROWS + PER - 1) / PER;
         constexpr bool BAND = sizeof(real) == 8;              // fp32 boxes: the fp32 test is the definition of the set
-#ifndef EMDEE_BUILD_UNROLL
-#define EMDEE_BUILD_UNROLL 2
-#endif
-        constexpr int UNR = EMDEE_BUILD_UNROLL;
+        constexpr int UNR = 2;
         float nrl2 = -rl2, nmargin_v = BAND ? -a.margin : 0.f, margin_v = a.margin;
+        // (nmargin_v is no longer read: it stays pinned because the fp32 kernels' register allocation, and so their code, moves without it)
         asm volatile("" : "+v"(nrl2), "+v"(nmargin_v), "+v"(margin_v));   // loop-invariant operands stay in VGPRs
-#ifndef EMDEE_BUILD_ROWTAB
-#define EMDEE_BUILD_ROWTAB 1
-#endif
         // The build is bound by VALU issue, and a third of its instructions were per-row bookkeeping (profiles/r02): the
         // candidate rows of an atom come from the brick's row table (one ds_read_b64 each, immediate offsets), and the
         // wave-uniform trip counts of all 9 rows are found at once -- lane gl of every group holds the chunk length of
         // row gl, three max steps combine the groups of the wavefront, 9 v_readlane move the result to scalars.
-        constexpr bool RT = EMDEE_BUILD_ROWTAB != 0;
-        // an odd trip count ends with a single-candidate step instead of being rounded up (row spans of ~53 slots over 8
-        // lanes give 7 trips: rounding to 8 tested 14 % more slots than there are)
-        constexpr bool TAIL = RT && UNR == 2;
-#ifndef EMDEE_BUILD_STRIDED
-#define EMDEE_BUILD_STRIDED 1
-#endif
+        // An odd trip count ends with a single-candidate step instead of being rounded up (row spans of ~53 slots over 8
+        // lanes give 7 trips: rounding to 8 tested 14 % more slots than there are).
         // Candidates are dealt to the lanes of a group round-robin (lane gl tests slots c0 + gl, c0 + gl + G, ...), not in
         // contiguous chunks: in-range candidates come in runs along a tile row, so contiguous chunks gave some lanes all of
         // a row's hits and others none -- and the emission loops below run as long as the busiest lane of the wavefront
@@ -908,15 +674,12 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
         // The rows then list slots G apart in consecutive entries: fine for the force kernels that read 8-byte plane values
         // or 16-byte records with 4 lanes per atom, an 8-way LDS bank conflict for 32-byte records read by 8 lanes (measured
         // on the rc = 3.5 mixture: build 8.1 -> 6.6 ms, force 4.1 -> 6.0 ms) -- the host picks ALG 13/15 only for the former.
-        constexpr bool STRIDED = RT && EMDEE_BUILD_STRIDED != 0 && ALG >= 10;
-#ifndef EMDEE_BUILD_PAIR_OPPOSITE
-#define EMDEE_BUILD_PAIR_OPPOSITE 1
-#endif
+        constexpr bool STRIDED = ALG >= 10;
         // Which two tile rows share a 32-bit word of hit bits (16-bit fields).  The emission loop of a word runs as long as
         // the busiest of the 64 lanes has hits in it, and an atom near a face of its cell has many hits in the row beyond
         // that face and few in the opposite one: rows (dy, dz) and (-dy, -dz) in one word -- (0,8) (1,7) (2,6) (3,5) (4) --
         // have a nearly constant sum where neighbouring rows (0,1) (2,3) ... do not.
-        constexpr bool OPP = EMDEE_BUILD_PAIR_OPPOSITE != 0 && PER == 2;
+        constexpr bool OPP = PER == 2;
         auto row_word = [](int r) constexpr { return OPP ? (r <= 4 ? r : 8 - r) : r / PER; };
         auto row_half = [](int r) constexpr { return OPP ? (r > 4 ? 1 : 0) : r % PER; };
         constexpr int LOG2G = G == 4 ? 2 : (G == 8 ? 3 : 4), KSTEP = STRIDED ? G : 1;
@@ -938,58 +701,47 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
             unsigned word[NWORDS];
             int cbase[NROWS];
             const unsigned *rt = rtab + (act ? oc * NSUB + ((info.y >> 17) & 3) : Shape::NOC * NSUB) * 9;
-            int2 rv_next = make_int2(0, 0);
+            int2 rv_next = rt_get(rt, 0);
             int trips_of[NROWS];
-            if constexpr (RT) {
-                rv_next = rt_get(rt, 0);
-                // chunk length of row gl (G = 8: rows 0..7 in the lanes, row 8 apart; G = 16: lanes 0..8 hold all nine; G = 4: rows
-                // 0..3 in cv, 4..7 in cw, row 8 apart)
-                auto chunk_of = [&](int r) { return (int)((unsigned)(rt_get(rt, r).y + G - 1) / (unsigned)G); };
-                int cv = chunk_of(min(gl, NROWS - 1));
-                int cw = G == 4 ? chunk_of(4 + gl) : 0;
-                int c8 = chunk_of(NROWS - 1);
-                // across the groups of a 16-lane row with row rotations, across the four rows with the gfx950 row / half swaps
-                // (no LDS, no address registers)
-                auto ror4 = [](int v) { return max(v, __builtin_amdgcn_update_dpp(0, v, 0x124 /* row_ror:4 */, 0xf, 0xf, true)); };
-                auto ror8 = [](int v) { return max(v, __builtin_amdgcn_update_dpp(0, v, 0x128 /* row_ror:8 */, 0xf, 0xf, true)); };
-                if constexpr (G == 4) { cv = ror4(cv); cw = ror4(cw); c8 = ror4(c8); }
-                if constexpr (G <= 8) {
-                    cv = ror8(cv); c8 = ror8(c8);
-                    if constexpr (G == 4) cw = ror8(cw);
-                }
-                auto rows_max = [](int v) {
-                    auto q = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-                    v = max((int)q[0], (int)q[1]);
-                    q = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-                    return max((int)q[0], (int)q[1]);
-                };
-                cv = rows_max(cv);
-                if constexpr (G <= 8) c8 = rows_max(c8);
-                if constexpr (G == 4) cw = rows_max(cw);
+            // chunk length of row gl (G = 8: rows 0..7 in the lanes, row 8 apart; G = 16: lanes 0..8 hold all nine; G = 4: rows
+            // 0..3 in cv, 4..7 in cw, row 8 apart)
+            auto chunk_of = [&](int r) { return (int)((unsigned)(rt_get(rt, r).y + G - 1) / (unsigned)G); };
+            int cv = chunk_of(min(gl, NROWS - 1));
+            int cw = G == 4 ? chunk_of(4 + gl) : 0;
+            int c8 = chunk_of(NROWS - 1);
+            // across the groups of a 16-lane row with row rotations, across the four rows with the gfx950 row / half swaps
+            // (no LDS, no address registers)
+            auto ror4 = [](int v) { return max(v, __builtin_amdgcn_update_dpp(0, v, 0x124 /* row_ror:4 */, 0xf, 0xf, true)); };
+            auto ror8 = [](int v) { return max(v, __builtin_amdgcn_update_dpp(0, v, 0x128 /* row_ror:8 */, 0xf, 0xf, true)); };
+            if constexpr (G == 4) { cv = ror4(cv); cw = ror4(cw); c8 = ror4(c8); }
+            if constexpr (G <= 8) {
+                cv = ror8(cv); c8 = ror8(c8);
+                if constexpr (G == 4) cw = ror8(cw);
+            }
+            auto rows_max = [](int v) {
+                auto q = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+                v = max((int)q[0], (int)q[1]);
+                q = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+                return max((int)q[0], (int)q[1]);
+            };
+            cv = rows_max(cv);
+            if constexpr (G <= 8) c8 = rows_max(c8);
+            if constexpr (G == 4) cw = rows_max(cw);
 #pragma unroll
-                for (int r = 0; r < NROWS; r++) {
-                    int m;
-                    if (G <= 8 && r == NROWS - 1) m = __builtin_amdgcn_readlane(c8, 0);
-                    else if (G == 4 && r >= 4) m = __builtin_amdgcn_readlane(cw, r - 4);
-                    else m = __builtin_amdgcn_readlane(cv, r);
-                    trips_of[r] = TAIL ? m : ((m + UNR - 1) & ~(UNR - 1));
-                    // (a lane's share of a tile row must fit its bit field: the host picked the field from the widest 3-cell run,
-                    // which the x sub-bins undercut -- and with 4 lanes per atom only THEY keep a row within 16 x 4 slots)
-                    if (FIELD < 32 && m > FIELD && lane == 0) atomicMax(&a.flags[4], m);
-                }
+            for (int r = 0; r < NROWS; r++) {
+                int m;
+                if (G <= 8 && r == NROWS - 1) m = __builtin_amdgcn_readlane(c8, 0);
+                else if (G == 4 && r >= 4) m = __builtin_amdgcn_readlane(cw, r - 4);
+                else m = __builtin_amdgcn_readlane(cv, r);
+                trips_of[r] = m;
+                // (a lane's share of a tile row must fit its bit field: the host picked the field from the widest 3-cell run,
+                // which the x sub-bins undercut -- and with 4 lanes per atom only THEY keep a row within 16 x 4 slots)
+                if (FIELD < 32 && m > FIELD && lane == 0) atomicMax(&a.flags[4], m);
             }
 #pragma unroll
             for (int r = 0; r < NROWS; r++) {
-                int tcr = 0, c0, span;
-                if constexpr (RT) {
-                    c0 = rv_next.x; span = rv_next.y;
-                    if (r + 1 < NROWS) rv_next = rt_get(rt, r + 1);                        // one row ahead of its use
-                } else {
-                    const int ox = oc % BX, oy = (oc / BX) % BY, oz = oc / (BX * BY);
-                    tcr = ox + TX * ((oy + r % 3) + TY * (oz + r / 3));           // cell x-1 of tile row (dy, dz) = (r%3-1, r/3-1)
-                    c0 = T.off[tcr];
-                    span = act ? T.off[tcr + 3] - c0 : 0;                           // cells x-1, x, x+1: contiguous
-                }
+                const int c0 = rv_next.x, span = rv_next.y;
+                if (r + 1 < NROWS) rv_next = rt_get(rt, r + 1);                            // one row ahead of its use
                 const int chunk = (int)((unsigned)(span + G - 1) / (unsigned)G);    // <= BUILD2_FIELD (host check)
                 const int first = STRIDED ? gl : (int)__umul24((unsigned)gl, (unsigned)chunk);
                 // my candidates (may be <= 0 in the chunked form): slots cb + k KSTEP, k < lim
@@ -997,11 +749,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                 const int cb = c0 + first;
                 cbase[r] = cb - row_half(r) * FIELD * KSTEP;
                 // scalar (chunk is the same in all lanes of a group); unrolled UNR times
-#ifdef EMDEE_BUILD_ABLATE      // timing experiments only (the lists are wrong): 1 no candidate loop, 2 no emission, 4 no flush
-                const int trips = (EMDEE_BUILD_ABLATE & 1) ? 0 : (RT ? trips_of[r] : ((wave_group_max<G>(chunk) + UNR - 1) & ~(UNR - 1)));
-#else
-                const int trips = RT ? trips_of[r] : ((wave_group_max<G>(chunk) + UNR - 1) & ~(UNR - 1));
-#endif
+                const int trips = trips_of[r];
                 unsigned bits = 0;
                 const float4 *cand = tile + cb;
                 // d^2 - r_list^2 of candidate q, accumulated from -r_list^2
@@ -1018,11 +766,9 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                         int kq = k;
                         asm volatile("" : "+s"(kq));                         // (worked out here, not carried through the loop)
                         const int c = cb + kq * KSTEP;
-                        if constexpr (RT) {                                  // rare path: the tile row is worked out here, not per row
-                            int occ = oc;
-                            asm volatile("" : "+v"(occ));
-                            tcr = occ % BX + TX * (((occ / BX) % BY + r % 3) + TY * (occ / (BX * BY) + r / 3));
-                        }
+                        int occ = oc;                                        // rare path: the tile row is worked out here, not per row
+                        asm volatile("" : "+v"(occ));
+                        const int tcr = occ % BX + TX * (((occ / BX) % BY + r % 3) + TY * (occ / (BX * BY) + r / 3));
                         const int tc = tcr + (c >= T.off[tcr + 1] ? 1 : 0) + (c >= T.off[tcr + 2] ? 1 : 0);
                         const int sh = T.shift[tc];
                         const Rec<real> ri = a.rec[p], rj = a.rec[gpj];
@@ -1038,32 +784,16 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                 // leaves t = -1 or +1; for every other candidate t < -margin is t < 0; and t = d^2 - r_list^2 is never -0.
                 // So "listed" is the sign bit of t, and v_alignbit_b32 {bits, t} >> 31 is bits = 2 bits + sign(t) --
                 // what the compare + add-with-carry pair did in two: -6 % instructions in the candidate loop.)
-                auto shift_in = [&](float t) {
-#ifdef EMDEE_BUILD_CMP_ADDC
-                    asm volatile("v_cmp_lt_f32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc"
-                                 : "+v"(bits) : "v"(t), "v"(nmargin_v) : "vcc");
-#else
-                    bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(t), 31);
-#endif
-                };
+                auto shift_in = [&](float t) { bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(t), 31); };
                 // UNR candidates per trip, loaded at its top: with six wavefronts per SIMD the LDS latency hides behind the
                 // other waves' arithmetic, and nothing is carried from trip to trip (no register rotation).  The band test
                 // of the group is one compare of the smallest |t| with the margin.
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (int k = 0; k + (TAIL ? 1 : 0) < trips; k += UNR) {             // (reads past the chunk / the tile: harmless)
+                for (int k = 0; k + 1 < trips; k += UNR) {                   // (reads past the chunk / the tile: harmless)
                     float4 q[UNR];
                     float t[UNR];
 #pragma unroll
                     for (int u = 0; u < UNR; u++) q[u] = cand[(k + u) * KSTEP];
-#ifdef EMDEE_BUILD_ABLATE      // 8: half the candidate reads (the second candidate of a trip is the first again); 16: every read twice
-                    if (EMDEE_BUILD_ABLATE & 8) { q[1] = q[0]; asm volatile("" : "+v"(q[1].x)); }
-                    if (EMDEE_BUILD_ABLATE & 16) {
-                        float4 extra = cand[(k + 1) * KSTEP + 1];
-                        asm volatile("" : : "v"(extra.x), "v"(extra.y), "v"(extra.z), "v"(extra.w));
-                        extra = cand[k * KSTEP + 1];
-                        asm volatile("" : : "v"(extra.x), "v"(extra.y), "v"(extra.z), "v"(extra.w));
-                    }
-#endif
                     // (keeps the whole 16-byte records alive: a ds_read_b96 costs 8 LDS cycles per wavefront, a ds_read_b128 4)
                     if constexpr (!BAND) {
 #pragma unroll
@@ -1083,7 +813,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
 #pragma unroll
                     for (int u = 0; u < UNR; u++) shift_in(t[u]);
                 }
-                if (TAIL && (trips & 1)) {
+                if (trips & 1) {
                     const float4 q = cand[(trips - 1) * KSTEP];
                     asm volatile("" : : "v"(q.w));          // (the whole record: a ds_read_b96 costs twice the LDS cycles of a ds_read_b128)
                     float t = dist(q);
@@ -1094,7 +824,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                     shift_in(t);
                 }
                 // candidate k sits at bit trips-1-k: reverse, drop what lies past my chunk
-                if constexpr (RT && FIELD < 32)                                     // one v_bfe_u32: bits [32-trips, 32-trips+lim)
+                if constexpr (FIELD < 32)                                           // one v_bfe_u32: bits [32-trips, 32-trips+lim)
                     bits = __builtin_amdgcn_ubfe(__builtin_bitreverse32(bits), (unsigned)(32 - trips), (unsigned)max(lim, 0));
                 else
                     bits = lim > 0 ? ((__builtin_bitreverse32(bits) >> (32 - trips)) & (lim >= 32 ? ~0u : ((1u << lim) - 1u))) : 0u;
@@ -1110,7 +840,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                 if (row_half(r)) word[row_word(r)] |= bits << (row_half(r) * FIELD);
                 else word[row_word(r)] = bits;
             }
-            // ---- phase 2 (as ALG 2): prefix over the lanes of the group, then every lane emits its hits --------
+            // ---- phase 2: prefix over the lanes of the group, then every lane emits its hits --------
             int mine = 0;
 #pragma unroll
             for (int w = 0; w < NWORDS; w++) mine += __popc(word[w]);
@@ -1139,9 +869,6 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
 #pragma unroll
             for (int w = 0; w < NWORDS; w++) {
                 unsigned W = word[w];
-#ifdef EMDEE_BUILD_ABLATE
-                if (EMDEE_BUILD_ABLATE & 2) W = 0;
-#endif
                 int cA = cbase[OPP ? w : PER * w] << a.idx_shift,
                     cB = (OPP ? (w < 4 ? cbase[8 - w] : 0) : ((PER == 2 && 2 * w + 1 < NROWS) ? cbase[2 * w + 1] : 0)) << a.idx_shift;
                 asm volatile("" : "+v"(cA), "+v"(cB));                             // shifted once, here
@@ -1154,11 +881,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                     ep++;
                 }
             }
-#ifdef EMDEE_BUILD_ABLATE
-            if (have && !(EMDEE_BUILD_ABLATE & 4)) {
-#else
             if (have && EMDEE_BOUND(BS_BUILD_ROW, p, a.n)) {
-#endif
                 constexpr int BLKL = EPL * GL;                // entries per lane-major block of the force kernels' rows
                 EMDEE_PLAIN_LOOP
                 for (int c = gl * EPL; c < a.stride; c += G * EPL) {
@@ -1170,89 +893,6 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
                     q.w = (unsigned)src[6 * GL] | ((unsigned)src[7 * GL] << 16);
                     *reinterpret_cast<uint4 *>(row + c) = q;
                 }
-                if (gl == G - 1) {                            // the last lane's inclusive prefix is the row length
-                    a.cnt[p] = act ? (int)min((unsigned)incl, ustride) : 0;
-                    if ((unsigned)incl > ustride) atomicMax(&a.flags[0], incl);
-                }
-            }
-        }
-        return;
-    }
-    if constexpr (ALG == 2) {
-        static_assert(G == 8 || G == 16, "two-phase build: 8 or 16 lanes per atom");
-        constexpr int NROWS = 9, NWORDS = (NROWS + 1) / 2;
-        for (int ob = 0; ob < n_own; ob += NGROUPS) {         // wave-uniform trip count
-            const int o = ob + gid;
-            const bool have = o < n_own;
-            int ti = 0, p = 0, oc = 0;
-            if (have) oc = brick_locate(T, o, ti, p);
-            const bool act = have && ((T.oinfo[o].y >> 16) & 1) != 0;   // ghosts own no row
-            const int ox = oc % BX, oy = (oc / BX) % BY, oz = oc / (BX * BY);
-            const float4 qi = tile[ti];
-            unsigned short *row = a.nbr + (size_t)p * a.stride;
-            for (int c = gl * EPL; c < a.stride; c += G * EPL) *reinterpret_cast<uint4 *>(rowbuf + c) = fill;
-            // ---- phase 1: one bit per candidate of my chunk of each of the 9 tile rows -------------
-            unsigned word[NWORDS];
-            int cbase[NROWS];
-#pragma unroll
-            for (int r = 0; r < NROWS; r++) {
-                const int dy = r % 3 - 1, dz = r / 3 - 1;
-                const int tcr = ox + TX * ((oy + 1 + dy) + TY * (oz + 1 + dz));   // cell x-1 of that tile row
-                const int c0 = T.off[tcr];
-                const int span = act ? T.off[tcr + 3] - c0 : 0;                    // cells x-1, x, x+1: contiguous
-                const int chunk = (span + G - 1) / G;                               // <= BUILD2_FIELD (host check)
-                const int first = gl * chunk;
-                const int lim = min(chunk, span - first);                           // my candidates; may be <= 0
-                const int cb = c0 + first;
-                cbase[r] = (r & 1) ? cb - BUILD2_FIELD : cb;
-                unsigned bits = 0;
-                float4 qc = tile[cb];                                               // one candidate ahead
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (int k = 0; k < lim; k++) {                                     // divergent trip count
-                    const float4 qn = tile[cb + k + 1];                             // (past the chunk: harmless)
-                    bits |= (in_range_q(qi, qc, p, cb + k, tcr) ? 1u : 0u) << k;
-                    qc = qn;
-                }
-                if (r == 4) {                                                       // the atom itself
-                    const int ks = ti - cb;
-                    if (ks >= 0 && ks < lim) bits &= ~(1u << ks);
-                }
-                if (r & 1) word[r / 2] |= bits << BUILD2_FIELD;
-                else word[r / 2] = bits;
-            }
-            // ---- phase 2: prefix over the lanes of the group, then every lane emits its hits --------
-            int mine = 0;
-#pragma unroll
-            for (int w = 0; w < NWORDS; w++) mine += __popc(word[w]);
-            int incl = mine;
-            {
-                int t = __builtin_amdgcn_update_dpp(0, incl, DPP_ROW_SHR1, 0xf, 0xf, true);
-                incl += gl >= 1 ? t : 0;
-                t = __builtin_amdgcn_update_dpp(0, incl, DPP_ROW_SHR2, 0xf, 0xf, true);
-                incl += gl >= 2 ? t : 0;
-                t = __builtin_amdgcn_update_dpp(0, incl, DPP_ROW_SHR4, 0xf, 0xf, true);
-                incl += gl >= 4 ? t : 0;
-                if (G == 16) {
-                    t = __builtin_amdgcn_update_dpp(0, incl, DPP_ROW_SHR8, 0xf, 0xf, true);
-                    incl += gl >= 8 ? t : 0;
-                }
-            }
-            unsigned e = (unsigned)(incl - mine);
-#pragma unroll
-            for (int w = 0; w < NWORDS; w++) {
-                unsigned W = word[w];
-                const int cA = cbase[2 * w], cB = (2 * w + 1 < NROWS) ? cbase[2 * w + 1] : 0;
-                while (W) {
-                    const int k = __ffs((int)W) - 1;
-                    W &= W - 1;
-                    const int c = k + (k >= BUILD2_FIELD ? cB : cA);
-                    if (e < ustride && EMDEE_BOUND(BS_BUILD_ROWBUF, row_position<GL>(e), ustride)) rowbuf[row_position<GL>(e)] = (unsigned short)(c << a.idx_shift);
-                    e++;
-                }
-            }
-            if (have && EMDEE_BOUND(BS_BUILD_ROW, p, a.n)) {
-                for (int c = gl * EPL; c < a.stride; c += G * EPL)
-                    *reinterpret_cast<uint4 *>(row + c) = *reinterpret_cast<const uint4 *>(rowbuf + c);
                 if (gl == G - 1) {                            // the last lane's inclusive prefix is the row length
                     a.cnt[p] = act ? (int)min((unsigned)incl, ustride) : 0;
                     if ((unsigned)incl > ustride) atomicMax(&a.flags[0], incl);
@@ -1336,15 +976,6 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
     int bxi, byi, bzi, tile_n, n_own;
     if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-    // (far class skipped: rows end at their near entries while nobody has moved delta / 2; the statistics always see whole rows)
-#ifdef EMDEE_EXPERIMENTS
-    const bool far_skip = a.far_skip != 0;
-#else
-    constexpr bool far_skip = false;                          // (the product library has plain rows only)
-#endif
-    const bool near_only = far_skip && MODE != BRICK_STATS && *a.far_word == 0;
-    auto row_len = [&](int c) { return far_skip ? (near_only ? (c >> 8) : (c & 255)) : c; };
-
     // ---- own-atom table entries first: their global loads fly while the tile is being staged --------
     // row length = cnt[p]; the build kernel wrote 0 for ghosts (they own no row and receive no force)
     int own_p[OWN_REGS], own_ti[OWN_REGS], own_m[OWN_REGS];
@@ -1354,7 +985,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         own_p[k] = own_ti[k] = own_m[k] = 0;
         if (o < n_own) {
             brick_locate(T, o, own_ti[k], own_p[k]);
-            own_m[k] = row_len(a.cnt[own_p[k]]);
+            own_m[k] = a.cnt[own_p[k]];
         }
     }
     // ---- stage the tile: HBM -> LDS, unit stride inside each tile row, image shift applied -----------
@@ -1418,7 +1049,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
     for (int o = tid + OWN_REGS * THREADS; o < n_own; o += THREADS) {   // very dense bricks only
         int ti, p;
         brick_locate(T, o, ti, p);
-        if (EMDEE_BOUND(BS_FORCE_OWN, o, a.own_cap)) T.oinfo[o] = make_int2(p, (row_len(a.cnt[p]) << 16) | ti);
+        if (EMDEE_BOUND(BS_FORCE_OWN, o, a.own_cap)) T.oinfo[o] = make_int2(p, (a.cnt[p] << 16) | ti);
     }
     __syncthreads();
 
@@ -1531,15 +1162,12 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                 block2(q, b0);
                 return;
             }
-#ifndef EMDEE_PREFETCH_XJ
-#define EMDEE_PREFETCH_XJ 1
-#endif
-            // (EMDEE_PREFETCH_XJ, on: the coordinates of entry t + 1 are requested before the arithmetic of entry t, as in the typed
-            // kernels -- round 5, same-box A/B of the build: fused launch 1.290 -> 1.280 ms, 600 -> 603.6 steps/s; =0 is the A/B baseline)
+            // (the coordinates of entry t + 1 are requested before the arithmetic of entry t, as in the typed
+            // kernels -- round 5, same-box A/B of the build: fused launch 1.290 -> 1.280 ms, 600 -> 603.6 steps/s)
             // Force-only launches (the integrator's): with energies or virials as well the six registers of the read-ahead take the fp64
             // kernel from 76 to 82 VGPRs and a third workgroup off the CU -- the operator's F+E+W call went 1.49 -> 1.53 ms for it
             // (found by running round 4's tree beside this one, profiles/r05/r04_vs_r05_same_box.txt)
-            constexpr bool AHEAD = SOA && EMDEE_PREFETCH_XJ != 0 && BITMASK == EMDEE_FORCES;
+            constexpr bool AHEAD = SOA && BITMASK == EMDEE_FORCES;
             real xn = 0, yn = 0, zn = 0;
             if (AHEAD) {
                 const unsigned char *pn = plane_b + pick16(q, 0);
@@ -1654,7 +1282,6 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                     a.rec_next[p] = r;
                     const real ex = r.x - bx, ey = r.y - by, ez = r.z - bz;
                     if (ex * ex + ey * ey + ez * ez > a.thr2) *a.trigger = 1;
-                    if (far_skip && ex * ex + ey * ey + ez * ez > a.thr2_near) *a.far_word = 1;
                 }
             } else if (have && gl == G - 1) {
                 if (a.user_f != nullptr || a.user_e != nullptr || a.user_w != nullptr) {
@@ -1712,7 +1339,7 @@ __global__ __launch_bounds__(THREADS) void k_brick_export(BrickArgs<real> a, int
         brick_locate(T, o, ti, p);
         if (a.perm[p] >= a.n_owned) continue;
         const int i = cmap ? cmap[a.perm[p]] : a.perm[p];
-        const int m = a.far_skip ? (a.cnt[p] & 255) : a.cnt[p];
+        const int m = a.cnt[p];
         counts[i] = m;
         const unsigned short *row = a.nbr + (size_t)p * a.stride;
         for (int e = 0; e < m && e < capacity; e++) {

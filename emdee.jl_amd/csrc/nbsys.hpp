@@ -9,33 +9,25 @@
 #include <type_traits>
 
 #include "brick.hpp"
-#ifdef EMDEE_EXPERIMENTS
-#include "brick_tbuild.hpp"
-#endif
 #include "kernels.hpp"
 #include "typed.hpp"
 
 namespace emdee {
 
-// The laboratory of rounds 1-5 -- measured alternatives that lost and the ablation switches that measured them -- compiles
-// only under `make EXPERIMENTS=1` (-> libemdee_hip_exp.so).  The product library carries none of it: no experiment kernel is
-// instantiated, and an experiment switch found in the environment is REFUSED with a message when an engine is created, not
-// ignored (a run that believes it is measuring a variant must not silently measure the default).
-#ifdef EMDEE_EXPERIMENTS
-static inline const char *exp_env(const char *name) { return std::getenv(name); }
-static inline void refuse_experiment_switches() {}
-#else
-static inline const char *exp_env(const char *) { return nullptr; }
+// The laboratory of rounds 1-5 -- measured alternatives that lost and the ablation switches that measured them -- has been
+// retired from the tree ("Product and laboratory", keeps the measurements).  A retired switch found in the
+// environment is REFUSED with a message when an engine is created, not ignored (a run that believes it is measuring a
+// variant must not silently measure the default).
 static inline void refuse_experiment_switches() {
     static const char *const gone[] = {"EMDEE_DEBUG_RC2_SCALE", "EMDEE_TBUILD", "EMDEE_BUILD4", "EMDEE_BUILD_ALG", "EMDEE_BUILD_CHUNKED",
         "EMDEE_BUILD_STRIDED", "EMDEE_NO_BRICK_TABLES", "EMDEE_NO_PREMUL", "EMDEE_BUILD_NEARFAR", "EMDEE_NEAR_DELTA", "EMDEE_FAR_SKIP",
         "EMDEE_PLAN_MAXIMA", "EMDEE_PLAN_SYNC", "EMDEE_STRIDE", "EMDEE_BRICK_VARIANT"};
     for (const char *name : gone)
         EMDEE_REQUIRE(std::getenv(name) == nullptr, EMDEE_ERR_INVALID,
-                      "%s is an experiment switch: this libemdee_hip.so was built without them (make -C emdee.jl_amd/csrc EXPERIMENTS=1 builds "
-                      "libemdee_hip_exp.so, selected with EMDEE_HIP_LIB)", name);
+                      "%s is an experiment switch that has been retired with the laboratory (make EXPERIMENTS=1 no longer "
+                      "exists): the variant it selected is not built; its measurement is recorded in DESIGN.md, "
+                      "\"Product and laboratory\"", name);
 }
-#endif
 
 // T_STEP: every fused step launch but the boundary-brick halves of a decomposed step, which go to T_STEP_BOUNDARY (emdee_md_kernel_time(4)
 // reports the two together, 5 and 6 one each); T_HALO: pack -> exchange -> unpack of a decomposed step, on the stream they run on
@@ -74,19 +66,12 @@ struct Scanner {
 };
 
 // ---- brick kernel variants (shape, workgroup size, lanes per atom); variant 0 is the default ----
-constexpr int BRICK_VARIANTS = 10;
 constexpr size_t LDS_LIMIT = 160 * 1024;
 
 template <int V>
 struct BrickVariant;
 // G = lanes per atom in the force kernels (and the row layout), GB = lanes per atom in the build kernel
 template <> struct BrickVariant<0> { using Shape = BrickShape<4, 2, 2>; static constexpr int THREADS = 512, G = 4, GB = 8; };
-template <> struct BrickVariant<1> { using Shape = BrickShape<3, 2, 2>; static constexpr int THREADS = 512, G = 8, GB = G; };
-template <> struct BrickVariant<2> { using Shape = BrickShape<5, 2, 2>; static constexpr int THREADS = 512, G = 8, GB = G; };
-template <> struct BrickVariant<3> { using Shape = BrickShape<4, 2, 2>; static constexpr int THREADS = 512, G = 16, GB = G; };
-template <> struct BrickVariant<4> { using Shape = BrickShape<6, 2, 2>; static constexpr int THREADS = 512, G = 8, GB = G; };
-template <> struct BrickVariant<5> { using Shape = BrickShape<2, 2, 2>; static constexpr int THREADS = 256, G = 8, GB = G; };
-template <> struct BrickVariant<6> { using Shape = BrickShape<3, 3, 2>; static constexpr int THREADS = 512, G = 8, GB = G; };
 // (7: the 1024-thread workgroup of variant 8 with FOUR lanes per atom: long rows, e.g. the rc = 3.5 sigma mixture -- 184 entries
 // are 46 pair steps per lane -- amortise a round's fixed work over 16 atoms per wavefront instead of 8)
 template <> struct BrickVariant<7> { using Shape = BrickShape<4, 2, 2>; static constexpr int THREADS = 1024, G = 4, GB = 8; };
@@ -99,14 +84,6 @@ template <> struct BrickVariant<9> { using Shape = BrickShape<2, 2, 2>; static c
 template <class F>
 static inline void with_brick_variant(int v, F &&f) {
     switch (v) {
-#ifdef EMDEE_EXPERIMENTS                                   // (brick shapes / lanes per atom of the tuning sweeps, EMDEE_BRICK_VARIANT)
-        case 1: f(BrickVariant<1>{}); break;
-        case 2: f(BrickVariant<2>{}); break;
-        case 3: f(BrickVariant<3>{}); break;
-        case 4: f(BrickVariant<4>{}); break;
-        case 5: f(BrickVariant<5>{}); break;
-        case 6: f(BrickVariant<6>{}); break;
-#endif
         case 7: f(BrickVariant<7>{}); break;
         case 8: f(BrickVariant<8>{}); break;
         case 9: f(BrickVariant<9>{}); break;
@@ -143,40 +120,10 @@ struct NbSystem {
     // path selection
     int path = PATH_BRICK;
     int variant = 0;
-    bool variant_forced = false;          // EMDEE_BRICK_VARIANT given: no automatic choice
     BrickGrid bgrid{};
     int tile_cap = 0, own_cap = 0, row_block = 1;
-    int build_alg = 1;                    // k_brick_build ALG (2 = two-phase; 1 when a tile row is too crowded for it)
-    bool force_build1 = false;            // EMDEE_BUILD_ALG=1: A/B switch
-    int build_alg_pref = 3;               // EMDEE_BUILD_ALG=2: the two-phase build with the per-lane candidate loop
-    // the transposed build (brick_tbuild.hpp: candidates in the lanes, own atoms in the loop) for the default variant of untyped
-    // boxes.  Measured in round 4 and left OFF (EMDEE_TBUILD=1 switches it on): same neighbour set, 2.63 ms per build at 10^7
-    // atoms against k_brick_build's 1.90 (profiles/r04/tbuild_*.txt).  tbuild_blocked: a cell of this state has more candidates
-    // than the kernel's registers hold (it raised flags[3]) -- until the next load
-    bool tbuild_enabled = exp_env("EMDEE_TBUILD") != nullptr && std::atoi(exp_env("EMDEE_TBUILD")) != 0 &&
-                          exp_env("EMDEE_BUILD_ALG") == nullptr && exp_env("EMDEE_BUILD_NEARFAR") == nullptr;
-    bool tbuild_blocked = false;
-    // Four lanes per atom in the round-robin build (round 4; EMDEE_BUILD4=1 switches it on): 16 atoms per wavefront share what
-    // is paid once per atom and wavefront-round (row bookkeeping, trip counts, prefix: 400 of ~960 instructions per atom and lane
-    // at 8 lanes), the emission loops run on twice the hits per lane (less imbalance), and twice the row buffers fit because the
-    // workgroup is 768 threads, two per CU: still six waves per SIMD.  Measured: 1.927 ms per launch against 1.90-1.93 with 8
-    // lanes and 512 threads -- 11 % fewer vector instructions (SQ counters) and no gain: in both forms the waves sit at
-    // s_waitcnt for 42-48 % of their lifetime, and doubling the candidate LDS reads costs only 12 % (profiles/r04/
-    // tbuild_transposed_build.txt): dependent-chain latency, which the dealing does not change.  Off by default.  A lane's share of a tile row must fit a 16-bit field (64 slots per row): the x sub-bins
-    // see to that in a fluid; the kernel reports a wider row in flags[4] and the state goes on with 8 lanes.
-    bool build4_enabled = exp_env("EMDEE_BUILD4") != nullptr && std::atoi(exp_env("EMDEE_BUILD4")) != 0;
-    bool build4_blocked = false;
+    int build_alg = 1;                    // k_brick_build ALG (3 / 5 = two-phase, 16- / 32-bit hit fields; 1 when a tile row is too crowded for both)
     bool field16_blocked = false;         // a 16-bit hit field overflowed under a plan that should have ruled it out: 32-bit fields until the next load
-    static constexpr int B4_THREADS = 768, B4_G = 4;
-    static constexpr int TB_NPAIR = 5;    // 640 candidates per own cell (27 cells of 17.6 atoms at rho* = 0.8, r_list = 2.8: 475)
-    template <class V>
-    bool tbuild_active() const {
-#ifdef EMDEE_EXPERIMENTS
-        return tbuild_enabled && !tbuild_blocked && !typed_active && std::is_same<V, BrickVariant<0>>::value;
-#else
-        return false;
-#endif
-    }
     size_t lds_bytes = 0, lds_build_bytes = 0;
     float build_margin = 0.f;
 
@@ -206,7 +153,7 @@ struct NbSystem {
     int nt = 1;
     // untyped boxes on the brick path: a cell's atoms ordered by quarter along x (kernels.hpp XSubBin), digit = cell * nsub + quarter
     int nsub = 1;
-    bool subbins_enabled = std::getenv("EMDEE_NO_SUBBINS") == nullptr && exp_env("EMDEE_NO_BRICK_TABLES") == nullptr;
+    bool subbins_enabled = std::getenv("EMDEE_NO_SUBBINS") == nullptr;
     // two-species boxes on the brick path (round 5): the typed build takes the same quarters, digit = (cell * 2 + species) * 4 + quarter
     // (EMDEE_TYPED_SUBBINS=0: the (cell, species) order of rounds 3-4, the A/B baseline)
     int tsub = 1;
@@ -226,11 +173,6 @@ struct NbSystem {
     NbSystem() {
         refuse_experiment_switches();
         if (const char *e = std::getenv("EMDEE_PATH")) path = (std::string(e) == "direct") ? PATH_DIRECT : PATH_BRICK;
-        if (const char *e = exp_env("EMDEE_BRICK_VARIANT")) {
-            variant = std::max(0, std::min(BRICK_VARIANTS - 1, std::atoi(e)));
-            variant_forced = true;
-        }
-        if (const char *e = exp_env("EMDEE_BUILD_ALG")) { force_build1 = std::atoi(e) == 1; if (std::atoi(e) == 2) build_alg_pref = 2; }
         if (const char *e = std::getenv("EMDEE_RUN_AHEAD")) run_ahead = std::max(1, std::min(RUN_AHEAD, std::atoi(e)));
     }
 
@@ -244,8 +186,8 @@ struct NbSystem {
     double rel_lo[3] = {0, 0, 0}, rel_cw[3] = {1, 1, 1};
     int rel_M[3] = {1, 1, 1};
     bool rel_wanted() const {
-        return sizeof(real) == 4 && with_vel && !with_mass && !use_tags && !has_ghosts && path == PATH_BRICK && !tbuild_enabled &&
-               near_far_scale() <= 0.0 && std::getenv("EMDEE_F32_ABS") == nullptr;
+        return sizeof(real) == 4 && with_vel && !with_mass && !use_tags && !has_ghosts && path == PATH_BRICK &&
+               std::getenv("EMDEE_F32_ABS") == nullptr;
     }
     RelGrid rel_grid(bool on, const int *cells) const {
         RelGrid r{};
@@ -563,12 +505,6 @@ struct NbSystem {
         a.g = grid; a.bg = bgrid; a.tile_cap = tile_cap; a.own_cap = own_cap;
         a.nbr = nbr16.ptr; a.stride = stride; a.cnt = cnt.ptr; a.flags = flags.ptr;
         a.rlist2 = (real)(rlist * rlist); a.margin = build_margin; a.model = model; a.pitch = pitch;
-        {
-            const double k = near_far_scale();
-            a.nf_scale = k > 0.0 ? (float)k : 1.f;
-            a.nf_scale2 = a.nf_scale * a.nf_scale;     // (the square of the fp32 scale the tile really gets)
-        }
-        if (const char *dbg = exp_env("EMDEE_DEBUG_RC2_SCALE")) a.model.rc2 = (real)(std::atof(dbg) * (double)model.rc2);   // ablation only (EXPERIMENTS builds)
         a.frc = frc.ptr; a.en = en.ptr; a.vir = vir.ptr; a.stats = stats.ptr;
         a.phase = phase;   // only force launches are phased; build and stats always cover every brick
         a.vel = vel.ptr; a.vel_next = vel2.ptr; a.xb = xb.ptr; a.inv_mass = with_mass ? im.ptr : nullptr; a.rec_next = rec2.ptr;
@@ -593,9 +529,6 @@ struct NbSystem {
         }
         a.rel = rel_now ? 1 : 0;
         for (int d = 0; d < 3; d++) { a.rcw[d] = rel_cw[d]; a.rlo[d] = rel_lo[d]; }
-        a.far_skip = far_skip_active() ? 1 : 0;
-        a.far_word = flags.ptr + 16;
-        a.thr2_near = (real)(0.25 * near_delta() * near_delta());
         a.refmath = (sizeof(real) == 4 && refmath && ref_pos != nullptr) ? 1 : 0;
         a.user_pos = ref_pos;
         a.thr2 = (real)(0.25 * skin * skin);
@@ -742,11 +675,7 @@ struct NbSystem {
                 // (a CU holds three workgroups only up to ~50,000 B each, not 160 KB / 3: measured in round 2 by padding the launch)
                 constexpr size_t USABLE = 150000;
                 auto per_cu = [&](int tc) {
-                    size_t b = brick_build_lds_bytes<S, V::THREADS>(tc, own_cap, st, V::GB, nsub);
-#ifdef EMDEE_EXPERIMENTS
-                    if (tbuild_active<V>()) b = brick_tbuild_lds_bytes<S, V::THREADS, TB_NPAIR>(tc, own_cap, st);
-#endif
-                    const size_t
+                    const size_t b = brick_build_lds_bytes<S, V::THREADS>(tc, own_cap, st, V::GB, nsub),
                                  f = brick_force_lds_bytes<real, S, V::THREADS>(tc, own_cap);
                     return (int)(USABLE / std::max<size_t>(b, 1)) * 16 + (int)(USABLE / std::max<size_t>(f, 1));
                 };
@@ -756,12 +685,11 @@ struct NbSystem {
             if (std::getenv("EMDEE_DEBUG_PLAN"))
                 std::fprintf(stderr, "emdee plan: bricks %d x %d x %d, tile_cap %d (max %d), own_cap %d (max %d), max 3-cell span %d, x sub-bins %d K %d\n", bgrid.nb[0],
                              bgrid.nb[1], bgrid.nb[2], tile_cap, max_tile, own_cap, max_own, max_span3, nsub, sub_k());
-            build_alg = (!force_build1 && !field16_blocked && (V::GB == 8 || V::GB == 16) && plan_span3 <= BUILD2_FIELD * V::GB) ? build_alg_pref : 1;
+            build_alg = (!field16_blocked && (V::GB == 8 || V::GB == 16) && plan_span3 <= BUILD2_FIELD * V::GB) ? 3 : 1;
             // crowded tile rows (long cutoffs): the same build with one 32-bit hit field per row
-            if (build_alg == 1 && !force_build1 && build_alg_pref == 3 && (V::GB == 8 || V::GB == 16) && plan_span3 <= 32 * V::GB) build_alg = 5;
+            if (build_alg == 1 && (V::GB == 8 || V::GB == 16) && plan_span3 <= 32 * V::GB) build_alg = 5;
             if (build_alg == 1) plan_span3 = 1 << 30;               // the ballot build has no limit
             else plan_span3 = (build_alg == 5 ? 32 : BUILD2_FIELD) * V::GB;   // what the chosen build can take
-            if (tbuild_active<V>()) plan_span3 = 1 << 30;           // the transposed build reports a crowded cell itself (flags[3])
             lds_bytes = brick_force_lds_bytes<real, S, V::THREADS>(tile_cap, own_cap);
             ok = lds_bytes <= LDS_LIMIT && tile_cap < 65536;
             // fp32 pre-test of the build kernel (fp64 boxes): brick-relative coordinates are below
@@ -796,40 +724,11 @@ struct NbSystem {
     // ---------------------------------------------------------------- neighbour list
     bool brick_active = false;
 
-    // near/far rows (EMDEE_BUILD_NEARFAR=1; measured in round 3 and left OFF: the force launch gains 6 %, 1.280 -> 1.199 ms,
-    // the build loses 0.6 ms, 2.92 -> 3.52, because nine rows x two classes make 18 short emission loops that each run as
-    // long as the busiest lane of the wavefront -- 585 vs 584 steps/s; profiles/README.md):
-    // r_near = r_c + delta (EMDEE_NEAR_DELTA, default 0.04 length units); returns the scale k of the build tile with
-    // k^2 (r_list^2 - r_near^2) = 2, or 0 when switched off or the skin is too thin
-    double near_delta() const {
-        double delta = 0.04;
-        if (const char *e = exp_env("EMDEE_NEAR_DELTA")) delta = std::atof(e);
-        return delta;
-    }
-    // the far class skipped outright while no atom has moved delta / 2 (BrickArgs::far_skip): untyped boxes without ghosts on
-    // the near/far build, rows short enough for the two counts to share cnt[p]
-    bool far_skip_active() const {
-        const char *on = exp_env("EMDEE_FAR_SKIP");
-        return on != nullptr && std::atoi(on) != 0 && nearfar_built && brick_active && !typed_active && !has_ghosts && stride < 256;
-    }
-    bool nearfar_built = false;           // the list in use was written by the near/far build (ALG 23)
-    double near_far_scale() const {
-        const char *on = exp_env("EMDEE_BUILD_NEARFAR");
-        if (on == nullptr || std::atoi(on) == 0) return 0.0;
-        const double delta = near_delta();
-        const double rc = std::sqrt((double)model_d.rc2), rn = rc + delta;
-        if (!(delta >= 0.0) || rn >= rlist - 0.05 * skin) return 0.0;
-        return std::sqrt(2.0 / (rlist * rlist - rn * rn));
-    }
-
     bool build_fits_lds() {
         bool ok = true;
         with_brick_variant(variant, [&](auto v) {
             using V = decltype(v);
             ok = brick_build_lds_bytes<typename V::Shape, V::THREADS>(tile_cap, own_cap, stride, V::GB, nsub) <= LDS_LIMIT;
-#ifdef EMDEE_EXPERIMENTS
-            if (tbuild_active<V>()) ok = brick_tbuild_lds_bytes<typename V::Shape, V::THREADS, TB_NPAIR>(tile_cap, own_cap, stride) <= LDS_LIMIT;
-#endif
             if (typed_active) ok = typed_build_lds_bytes<typename V::Shape, V::THREADS>(tile_cap, own_cap, stride, V::GB, V::G) <= LDS_LIMIT;
         });
         return ok;
@@ -840,12 +739,12 @@ struct NbSystem {
     int plan_M[3] = {0, 0, 0}, plan_n = 0;
     void make_plan() {
         const int n = n_total;
-        if (!variant_forced) variant = 0;
+        variant = 0;
         brick_active = (path == PATH_BRICK) && n > 0 && plan_bricks();
         // A tile too large for two workgroups of the default variant per CU (long cutoffs, dense boxes: rc = 3.5
         // sigma needs 135 KB) would leave 2 waves per SIMD: take the same bricks with 1024-thread workgroups
         // (measured on the rc = 3.5 mixture: 116 -> 154 steps/s).
-        if (brick_active && !variant_forced && lds_bytes > LDS_LIMIT / 2) {
+        if (brick_active && lds_bytes > LDS_LIMIT / 2) {
             variant = 8;
             if (!plan_bricks()) { variant = 0; plan_bricks(); }
         }
@@ -856,7 +755,7 @@ struct NbSystem {
         // the build kernel's LDS (fp32 tile + tables + one row buffer per lane group) must fit as well: very dense or
         // very inhomogeneous boxes with a long cutoff fall back to the direct (global-gather) kernels
         if (brick_active && !build_fits_lds()) brick_active = false;
-        idx_shift = (brick_active && variant == 0 && uniform_atoms && tile_cap <= SOA_SLOTS && !exp_env("EMDEE_NO_PREMUL")) ? PLANE_SHIFT : 0;
+        idx_shift = (brick_active && variant == 0 && uniform_atoms && tile_cap <= SOA_SLOTS) ? PLANE_SHIFT : 0;
         // two species: the typed kernels (typed.hpp), if the tile fits their coordinate planes, no three cells of a tile row hold
         // more atoms of one species than the 16-bit hit fields of their build take, and both kernels fit LDS
         typed_active = false;
@@ -871,7 +770,7 @@ struct NbSystem {
             // A/B baseline).  Short rows: variant 0, on request only.
             const int keep = variant;
             int cands[2] = {-1, -1};
-            if (variant == 8 && !variant_forced) {
+            if (variant == 8) {
                 const char *tb = std::getenv("EMDEE_TYPED_BRICKS");
                 const bool only7 = tb != nullptr && std::atoi(tb) == 7;
                 cands[0] = only7 ? 7 : 9;
@@ -944,7 +843,6 @@ struct NbSystem {
     int plan_nt = 1;
     bool typed_blocked = false;           // this state's rows outgrew the typed build (until the next load)
     bool typed_stride = false;            // the stride already includes the typed rows' segment padding
-    bool maxima_from_tables = exp_env("EMDEE_PLAN_MAXIMA") != nullptr && std::string(exp_env("EMDEE_PLAN_MAXIMA")) == "tables";
 
     void build_list() {
         const int n = n_total;
@@ -955,7 +853,6 @@ struct NbSystem {
             // melt 91): rounded up to whole lane-major blocks below, 96 entries there.  A longer row grows the stride and
             // builds again.  (128 instead of 96 costs 2 % of the step: 33 % more bytes flushed per build, rows 256 B apart)
             stride = (int)((expect * 1.15 + 8.0) / 16.0 + 1.0) * 16;
-            if (const char *e = exp_env("EMDEE_STRIDE")) stride = std::max(16, std::atoi(e));   // tuning: first guess of the row stride
             typed_stride = false;
         }
         btab_valid = false;
@@ -964,7 +861,7 @@ struct NbSystem {
         // populations come back with the build's overflow words -- ONE blocking read-back per rebuild instead of two.
         // (inside resort_edit n is an upper bound: the plan is compared with the number of atoms before the edit)
         const int np = in_edit ? edit_n_plan : n;
-        bool kept = plan_valid && !exp_env("EMDEE_PLAN_SYNC") && !exp_env("EMDEE_NO_BRICK_TABLES") && path == PATH_BRICK && n > 0 && plan_M[0] == grid.M[0] &&
+        bool kept = plan_valid && path == PATH_BRICK && n > 0 && plan_M[0] == grid.M[0] &&
                     plan_M[1] == grid.M[1] && plan_M[2] == grid.M[2] && plan_n <= np + np / 8 && np <= plan_n + plan_n / 8 &&
                     plan_uniform == uniform_atoms && plan_nt == nt;
         if (kept) {
@@ -972,9 +869,8 @@ struct NbSystem {
             // (taking the maxima from k_brick_tables instead, which has every brick's tables in LDS anyway, was measured and
             // lost: one workgroup per brick means one look at -- or atomic on -- three hot words per brick, 2.84 -> 2.95 ms per
             // rebuild even with a device-scope look before the atomic, 4.50 ms without; k_brick_tile_max reduces 64 bricks per
-            // wavefront first.  EMDEE_PLAN_MAXIMA=tables switches it on)
-            if (maxima_from_tables) Zeros().add(flags.ptr, 9).run(stream());
-            else launch_tile_max(true);
+            // wavefront first)
+            launch_tile_max(true);
             brick_active = true;
         } else {
             make_plan();
@@ -984,10 +880,7 @@ struct NbSystem {
         for (int attempt = 0; attempt < 6; attempt++) {
             EMDEE_REQUIRE((double)n * stride < 1.7e10, EMDEE_ERR_OVERFLOW, "neighbour list would exceed 64 GiB");
             if (in_edit && !brick_active) { edit_abort = true; return; }   // (the direct kernels count atoms on the host: the caller reloads)
-            bool launched4 = false;
-            nearfar_built = false;
             if (!(kept && attempt == 0)) Zeros().add(flags.ptr, 5).run(stream());   // (a kept plan cleared them with the maxima)
-            if (exp_env("EMDEE_FAR_SKIP")) Zeros().add(flags.ptr + 16, 1).run(stream());   // (experiment: the near word starts afresh)
             if (brick_active) {
                 nbr16.ensure(rows * stride);
                 with_brick_variant(variant, [&](auto v) {
@@ -1016,7 +909,7 @@ struct NbSystem {
                             return;
                         }
                     }
-                    if (!btab_valid && !exp_env("EMDEE_NO_BRICK_TABLES")) {
+                    if (!btab_valid) {
                         // tables of every brick, once per rebuild; the build and every force launch copy them in
                         // (the image depends on the brick shape only: a small workgroup writes it)
                         constexpr int TT = V::Shape::NTC <= 128 ? 128 : 256;
@@ -1026,60 +919,20 @@ struct NbSystem {
                         btab_valid = false;
                         BrickArgs<real> ta = brick_args();
                         ta.btab = btab.ptr;
-                        ta.stats = (kept && maxima_from_tables) ? reinterpret_cast<unsigned long long *>(flags.ptr + 6) : nullptr;
+                        ta.stats = nullptr;
                         if (nsub > 1) { bsub.ensure((size_t)bgrid.nbricks * V::Shape::NTC + 4); ta.bsub = bsub.ptr; }
                         hipLaunchKernelGGL((k_brick_tables<real, typename V::Shape, TT>), dim3(bgrid.per_xcd * NXCD), dim3(TT),
                                            BT::bytes(0), stream(), ta);
                         btab_valid = true;
                     }
-#ifdef EMDEE_EXPERIMENTS
-                    if constexpr (std::is_same<V, BrickVariant<0>>::value) {
-                        if (tbuild_active<V>()) {
-                            auto tk = k_brick_build_t<real, typename V::Shape, V::THREADS, V::G, TB_NPAIR>;
-                            lds_build_bytes = brick_tbuild_lds_bytes<typename V::Shape, V::THREADS, TB_NPAIR>(tile_cap, own_cap, stride);
-                            allow_big_lds(tk, lds_build_bytes);
-                            hipLaunchKernelGGL(tk, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), lds_build_bytes, stream(), brick_args());
-                            return;
-                        }
-                    }
-#endif
                     auto kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 1, V::G>;
                     if constexpr (V::GB == 8 || V::GB == 16) {
-#ifdef EMDEE_EXPERIMENTS
-                        if (build_alg == 2) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 2, V::G>;
-#endif
                         if (build_alg == 3) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 3, V::G>;
                         if (build_alg == 5) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 5, V::G>;
                         // round-robin candidates (brick.hpp): when the force kernels read plane values or 16-byte records with 4 lanes per atom
-#ifdef EMDEE_EXPERIMENTS
-                        constexpr bool STRIDED_G8 = sizeof(real) == 4;   // (8 lanes per atom on 16-byte records: EMDEE_BUILD_STRIDED=1 only)
-#else
-                        constexpr bool STRIDED_G8 = false;
-#endif
-                        if constexpr (V::G == 4 || (V::G == 8 && STRIDED_G8)) {
-                            const bool strided_ok = (sizeof(real) == 4 || idx_shift != 0) && !exp_env("EMDEE_BUILD_CHUNKED") &&
-                                                    (V::G == 4 || exp_env("EMDEE_BUILD_STRIDED") != nullptr);
+                        if constexpr (V::G == 4) {
+                            const bool strided_ok = sizeof(real) == 4 || idx_shift != 0;
                             if (build_alg == 3 && strided_ok) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 13, V::G>;
-#ifdef EMDEE_EXPERIMENTS
-                            if constexpr (std::is_same<V, BrickVariant<0>>::value) {
-                                if (build_alg == 3 && strided_ok && nsub == 4 && build4_enabled && !build4_blocked && near_far_scale() <= 0.0) {
-                                    auto k4 = k_brick_build<real, typename V::Shape, B4_THREADS, B4_G, 13, V::G>;
-                                    const size_t lds4 = brick_build_lds_bytes<typename V::Shape, B4_THREADS>(tile_cap, own_cap, stride, B4_G, nsub);
-                                    if (lds4 <= LDS_LIMIT) {
-                                        lds_build_bytes = lds4;
-                                        allow_big_lds(k4, lds4);
-                                        launched4 = true;
-                                        hipLaunchKernelGGL(k4, dim3(bgrid.per_xcd * NXCD), dim3(B4_THREADS), lds4, stream(), brick_args());
-                                        return;
-                                    }
-                                }
-                            }
-                            // ... and near entries first (brick.hpp ALG 23), when the skin leaves room for a near radius
-                            if (build_alg == 3 && strided_ok && near_far_scale() > 0.0) {
-                                kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 23, V::G>;
-                                nearfar_built = true;
-                            }
-#endif
                             if (build_alg == 5 && strided_ok) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 15, V::G>;
                         }
                     }
@@ -1112,27 +965,11 @@ struct NbSystem {
                 continue;
             }
             if (brick_active && ctx->host_flags[4] != 0) {
-                // A lane's share of a tile row did not fit its 16-bit hit field.  The 4-lane build (an experiment) sees that
-                // when the x sub-bins do not keep a row within 64 slots: this state goes on with 8 lanes per atom.  The default
-                // builds cannot (the plan's widest 3-cell run is what picked the field): should they ever, the list is NOT
-                // taken -- this state goes on with 32-bit fields.
-                if (launched4) {
-                    build4_blocked = true;
-                    if (std::getenv("EMDEE_DEBUG_PLAN")) std::fprintf(stderr, "emdee plan: a tile row needs %d trips of 4 lanes (> 16): the build goes on with 8 lanes per atom\n", ctx->host_flags[4]);
-                    continue;
-                }
+                // A lane's share of a tile row did not fit its 16-bit hit field.  The builds cannot overflow it (the plan's widest
+                // 3-cell run is what picked the field): should they ever, the list is NOT taken -- this state goes on with 32-bit fields.
                 EMDEE_REQUIRE(!field16_blocked, EMDEE_ERR_OVERFLOW, "neighbour build: a lane's share of a tile row (%d) overflows its hit field", ctx->host_flags[4]);
                 field16_blocked = true;
                 kept = false; plan_valid = false; btab_valid = false;
-                make_plan();
-                continue;
-            }
-            if (brick_active && ctx->host_flags[3] != 0 && !tbuild_blocked) {
-                // a cell with more candidates than the transposed build holds in registers: this state goes on with k_brick_build
-                tbuild_blocked = true;
-                kept = false;
-                plan_valid = false;
-                btab_valid = false;
                 make_plan();
                 continue;
             }
@@ -1275,8 +1112,6 @@ struct NbSystem {
         nt = 1;
         species.n = 1;
         typed_blocked = false;
-        tbuild_blocked = false;
-        build4_blocked = false;
         field16_blocked = false;
         if (uniform_known >= 0 && n_total > 0) {
             uniform_atoms = uniform_known == 1;
@@ -1463,8 +1298,7 @@ struct NbSystem {
         real thr = (real)(0.5 * skin);
         hipLaunchKernelGGL((k_kick_drift<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned,
                            pitch, perm.ptr, rec.ptr, vel.ptr, frc.ptr, with_mass ? im.ptr : nullptr, (real)c, (real)dt,
-                           xb.ptr, thr * thr, trigger ? trigger : flags.ptr + 1, lgv_on ? noise.ptr : nullptr, (real)lgv_c1, guard,
-                           far_skip_active() ? flags.ptr + 16 : (int *)nullptr, (real)(0.25 * near_delta() * near_delta()));
+                           xb.ptr, thr * thr, trigger ? trigger : flags.ptr + 1, lgv_on ? noise.ptr : nullptr, (real)lgv_c1, guard);
         if (lgv_on) lgv_step++;
     }
 

@@ -36,7 +36,7 @@ constexpr int TNT = 2;   // species of a typed box
 template <class Shape, int THREADS>
 constexpr int typed_slots() { return THREADS >= 1024 ? 4608 : (Shape::NOC == 8 ? 3104 : SOA_SLOTS); }
 template <typename real, class Shape, int THREADS>
-constexpr int typed_pitch() { return typed_slots<Shape, THREADS>() + ((sizeof(real) == 8 && EMDEE_SOA_PAD) ? 1 : 0); }
+constexpr int typed_pitch() { return typed_slots<Shape, THREADS>() + (sizeof(real) == 8 ? 1 : 0); }
 // index blocks of a row (= of its species-0 segment) fetched one atom ahead: two of 32 entries where rows are short, four where
 // the workgroup is a long-row one (rc = 3.5 sigma: ~92 neighbours per species; NOC = own cells of the brick shape)
 constexpr int typed_prefetch_blocks(int G, int THREADS, int NOC = 16) { return (EPL * G) >= 128 ? 1 : ((G == 4 && (THREADS >= 1024 || NOC == 8)) ? 4 : 2); }
@@ -670,11 +670,7 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
     LJModel<real> mdl = a.model;
     // fp64: 4 eps_ij folded into the segment's switch constants (lj_pair.hpp LJSeg: 3.077 -> 3.042 ms per launch, same box twice;
     // fp32 loses with it, 2.12 -> 2.21 ms: ten more live registers per lane; profiles/r05/call_v.sh)
-#ifdef EMDEE_TYPED_NO_FOLD
-    constexpr bool FOLD = false;
-#else
     constexpr bool FOLD = sizeof(real) == 8;
-#endif
     if (BITMASK == EMDEE_FORCES && FOLD) asm volatile("" : "+v"(mdl.nx0), "+v"(mdl.idl2));    // (the Horner constants are the segment's)
     else if (BITMASK == EMDEE_FORCES) asm volatile("" : "+v"(mdl.nx0), "+v"(mdl.idl2), "+v"(mdl.h4), "+v"(mdl.h3), "+v"(mdl.k6));
     else asm volatile("" : "+v"(mdl.x0), "+v"(mdl.k3));
@@ -738,7 +734,6 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
                 } else if (r2 < a.model.rc2) {                // strict test (Q2)
                     const real inv_r2 = fast_rcp(r2);
                     if (BITMASK == EMDEE_FORCES) {
-                        // (A/B: profiles/build_variant.sh nofold -DEMDEE_TYPED_NO_FOLD=1)
                         const real wr2 = FOLD ? lj_force_over_r2_seg(r2, inv_r2, mdl, c.seg) : lj_force_over_r2(r2, inv_r2, mdl, c.sig2, c.e4);
                         fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
                     } else {

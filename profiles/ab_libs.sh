@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of library variants built by profiles/build_variant.sh on the same box, same process conditions:
-#   bash profiles/ab_libs.sh OUTDIR "base opp abl1 ..." [bench.py arguments]      ("base" = the in-tree library)
+#   bash profiles/ab_libs.sh OUTDIR "base nofence ..." [bench.py arguments]      ("base" = the in-tree library)
 O=$1; NAMES=$2; shift 2; ARGS=${@:---steps 40 --warmup 10}
 mkdir -p $O
 for V in $NAMES; do

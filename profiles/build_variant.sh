@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B builds of the library: profiles/build_variant.sh NAME "-DFLAG=1 ..." [f64|f32|both]
+# A/B builds of the library: profiles/build_variant.sh NAME "-DFLAG=1 ..." [f64|f32|both], e.g. nofence "-DEMDEE_NO_FENCE=1"
+# (the library's one compile-time A/B switch: csrc/common.hpp; the build kernel's ablation macros were retired with the laboratory)
 # -> emdee.jl_amd/variants/libemdee_hip_NAME.so (selected at run time with EMDEE_HIP_LIB=...), only the kernel
 # translation unit(s) recompiled with the extra flags.  Run in the container (hipcc cross-compiles); *.so travels with gpurun.
 set -e

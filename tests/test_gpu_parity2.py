@@ -121,6 +121,43 @@ def test_neighbour_set_with_x_sub_bins(emdee, oracle, dev, case, monkeypatch, ca
 
 
 
+def test_neighbour_set_of_the_ballot_build(emdee, oracle, dev, monkeypatch, capfd):
+    """A tile row too crowded for the two-phase builds -- more than 32 GB atoms in three consecutive cells, GB = 8 lanes per atom
+    in the build -- takes the ballot build (k_brick_build ALG 1): a dilute gas with one dense column of cells along x.  Its rows
+    are the oracle's, entry for entry, and its forces the oracle's."""
+    E = emdee
+    rng = np.random.default_rng(41)
+    rc, rs, skin = 3.5, 3.0, 0.4
+    L = 6.05 * (rc + skin)                                             # 6 cells of 3.93 per side
+    cw = L / 6
+    a = 0.72                                                           # column: a 5 x 5 lattice per layer, layers a apart
+    g = np.arange(5) * a + 2 * cw + 0.25
+    layers = np.arange(int(L / a)) * a
+    col = np.array([(x, y, z) for x in layers for y in g for z in g]) + rng.normal(0.0, 0.04, size=(len(layers) * 25, 3))
+    m = np.arange(11) * (L / 11)                                       # the gas: a jittered lattice 2.1 apart
+    gas = np.array([(x, y, z) for x in m for y in m for z in m]) + rng.normal(0.0, 0.2, size=(11 ** 3, 3))
+    lo, hi = 2 * cw - 0.6, 2 * cw + 0.25 + 4 * a + 0.6                  # keep the gas out of the column's reach
+    gas = gas[~(np.all((gas[:, 1:] > lo) & (gas[:, 1:] < hi), axis=1))]
+    x = np.concatenate([col, gas])
+    N = x.shape[0]
+    atoms = E.lennard_jones_atoms(1.0, 1.0, N)
+    monkeypatch.setenv("EMDEE_DEBUG_PLAN", "1")
+    tiles = E.nonbonded_computation_tiles(N, skin=skin)
+    f = torch.zeros((N, 3), dtype=torch.float64, device=dev)
+    E.compute_nonbonded_(f, None, None, E.cu(x, dev), L, tiles, E.LennardJonesModel(rc, rs), E.cu(atoms, dev), E.Val(E.FORCES))
+    got = _rows(*tiles.neighbor_lists())
+    plans = [l for l in capfd.readouterr().err.splitlines() if l.startswith("emdee plan")]
+    assert plans, "the tiled path must be in use"
+    span = int(plans[-1].split("max 3-cell span ")[1].split(",")[0])
+    assert span > 32 * 8, plans[-1]
+    want = _oracle_rows(oracle, x, L, rc + skin)
+    assert sum(len(r) for r in got) == sum(len(r) for r in want) == tiles.stats()["listed"]
+    for i in range(N):
+        assert np.array_equal(got[i], want[i]), "row %d differs from the oracle" % i
+    f0, _, _ = oracle.nonbonded_cells(x, L, oracle.model(rc, rs), atoms)
+    assert np.abs(f.cpu().numpy() - f0).max() <= 1e-9 * np.abs(f0).max()
+
+
 def test_posted_read_backs_and_copies_give_the_same_run(emdee, dev, monkeypatch):
     """The small blocking read-backs (rebuild requests of a batch of queued steps, the build's overflow words) are posted by a
     kernel into pinned host memory while the host spins on a stamp; EMDEE_READBACK=copy takes hipMemcpyAsync +
