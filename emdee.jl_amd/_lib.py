@@ -105,6 +105,8 @@ SIGNATURES = {
     "emdee_dd_rebuild_stats": [_p, C.POINTER(_i64)],
     "emdee_dd_phase_times": [_p, C.POINTER(_dbl)],
     "emdee_dd_set_overlap": [_p, _i32],
+    "emdee_dd_set_exclusions": [_p, _p, _i64],
+    "emdee_dd_set_pairs14": [_p, _p, _i64, _dbl],
     "emdee_last_error": [],
 }
 _RESTYPES = {"emdee_last_error": C.c_char_p}

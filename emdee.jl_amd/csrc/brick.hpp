@@ -1359,9 +1359,10 @@ __global__ __launch_bounds__(THREADS) void k_brick_export(BrickArgs<real> a, int
 // named pairs to leave out.  One thread per own atom that has exclusions: its entries are decoded as k_brick_export does
 // (tile slot -> cell-order slot -> caller id), looked up in the atom's sorted exclusion list, and the row is compacted in
 // place, the vacated tail refilled with the sentinel.  Untyped rows only (a box with exclusions keeps the general kernels).
+// keys: caller ids or, in a decomposed engine, global ids (tags) -- and the 1-4 partners' slots (kernels.hpp PairKeys).
 template <typename real, class Shape, int THREADS, int G>
 __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, const int *__restrict__ ex_start,
-                                                          const int *__restrict__ ex_idx) {
+                                                          const int *__restrict__ ex_idx, PairKeys keys) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     BrickTables<Shape, THREADS> T;
     T.carve(s_dyn);
@@ -1370,10 +1371,13 @@ __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, con
     for (int o = threadIdx.x; o < n_own; o += THREADS) {
         int ti, p;
         brick_locate(T, o, ti, p);
-        const int i = a.perm[p];
-        if (i >= a.n_owned) continue;
-        const int lo_x = ex_start[i], hi_x = ex_start[i + 1];
+        if (a.perm[p] >= a.n_owned) continue;
+        const long long gi = pair_key(keys, a.perm, p);
+        if (gi < 0 || gi >= keys.n_tab) continue;
+        const int lo_x = ex_start[gi], hi_x = ex_start[gi + 1];
         if (lo_x == hi_x) continue;
+        const int lo14 = keys.s14 ? keys.start14[gi] : 0, hi14 = keys.s14 ? keys.start14[gi + 1] : 0;
+        for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
         const int m = min(a.cnt[p], a.stride);
         unsigned short *row = a.nbr + (size_t)p * a.stride;
         int w = 0;
@@ -1385,10 +1389,14 @@ __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, con
                 const int mid = (lo + hi) >> 1;
                 if (T.off[mid] <= sl) lo = mid; else hi = mid;
             }
-            const int j = a.perm[T.gbeg[lo] + (sl - T.off[lo])];
-            if (!csr_holds(ex_idx, lo_x, hi_x, j)) {
+            const int q = T.gbeg[lo] + (sl - T.off[lo]);
+            const long long gj = pair_key(keys, a.perm, q);
+            if (!csr_holds(ex_idx, lo_x, hi_x, (int)min(gj, (long long)keys.n_tab))) {
                 if (w != e) row[row_position<G>((unsigned)w)] = ent;
                 w++;
+            } else if (lo14 < hi14) {
+                const int k = csr_find(keys.idx14, lo14, hi14, gj);
+                if (k >= 0) keys.s14[k] = q;
             }
         }
         for (int e = w; e < m; e++) row[row_position<G>((unsigned)e)] = 0;   // the sentinel slot

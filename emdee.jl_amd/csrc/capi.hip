@@ -522,6 +522,12 @@ int32_t emdee_dd_phase_times(emdee_dd *dd, double out[8]) {
 int32_t emdee_dd_set_overlap(emdee_dd *dd, int32_t overlap) {
     return guarded([&] { REQUIRE_PTR(dd, "dd"); dd->impl->set_overlap(overlap != 0); });
 }
+int32_t emdee_dd_set_exclusions(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs) {
+    return guarded([&] { REQUIRE_PTR(dd, "dd"); dd->impl->set_pair_table(pairs_dev, n_pairs, false, 1.0); });
+}
+int32_t emdee_dd_set_pairs14(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs, double lj14scale) {
+    return guarded([&] { REQUIRE_PTR(dd, "dd"); dd->impl->set_pair_table(pairs_dev, n_pairs, true, lj14scale); });
+}
 
 }  // extern "C"
 

@@ -68,6 +68,7 @@ struct IDd {
     virtual void rebuild_stats(int64_t out[4]) = 0;
     virtual void phase_times(double out[8]) = 0;
     virtual void set_overlap(bool on) = 0;
+    virtual void set_pair_table(const int64_t *pairs, int64_t n_pairs, bool one_four, double lj14scale) = 0;
 };
 
 void dd_rccl_selftest(emdee_ctx *ctx, int n_bytes);

@@ -178,6 +178,8 @@ struct MdImpl : IMd {
     }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
+    // an engine of a decomposition (emdee_dd_engine): its pair tables are the decomposition's, keyed by global id
+    bool lent = false;
     // decomposed domains: the global ids of the atoms handed to set_state (caller order, owned atoms and ghosts); they travel
     // with the atoms from then on (NbSystem::tag) and order the atoms of a cell
     const long long *tags_user = nullptr;
@@ -342,6 +344,7 @@ struct MdImpl : IMd {
     void set_langevin_ids(const int64_t *ids) override { sys.lgv_ids = reinterpret_cast<const long long *>(ids); }
     void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) override {
         use_device(sys.ctx);
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "exclusions / 1-4 pairs of a decomposed run: emdee_dd_set_exclusions / emdee_dd_set_pairs14 (this integrator is a domain's, lent by emdee_dd_engine)");
         EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "exclusions / 1-4 pairs: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
         sys.set_pair_tables(sys.n_owned, one_four ? nullptr : pairs, one_four ? 0 : n_pairs, !one_four, one_four ? pairs : nullptr, one_four ? n_pairs : 0, one_four, lj14scale);
         sys.resort();                                        // the list without the named pairs (a two-species box leaves the typed kernels)

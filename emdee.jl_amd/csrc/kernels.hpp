@@ -1119,22 +1119,57 @@ __device__ __forceinline__ bool csr_holds(const int *__restrict__ idx, int lo, i
     }
     return false;
 }
+// position of j in idx[lo, hi), or -1
+__device__ __forceinline__ int csr_find(const int *__restrict__ idx, int lo, int hi, long long j) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int v = idx[mid];
+        if (v == j) return mid;
+        if (v < j) lo = mid + 1; else hi = mid;
+    }
+    return -1;
+}
+
+// Decomposed engines (dd.hpp) key the tables by GLOBAL id: the tag of the row's owner and of each entry, not the caller index
+// (perm).  tag == NULL: caller indices.  n_tab: ids 0 .. n_tab - 1 have rows (an id beyond names no pair).  With a 1-4 table
+// (s14 != NULL, tag mode) the filter also records, for every 1-4 partner of an owned atom, the cell-order slot of the entry it
+// strikes, in the table's order: s14[k] for idx14[k], -1 when the partner is not in the row (beyond the list radius at the
+// build, so beyond rc until the next one).  k_pairs14_slots sums those slots.
+struct PairKeys {
+    const long long *tag;
+    int n_tab;
+    const int *start14, *idx14;
+    int *s14;
+};
+__device__ __forceinline__ long long pair_key(const PairKeys &k, const int *__restrict__ perm, int slot) {
+    return k.tag ? k.tag[slot] : (long long)perm[slot];
+}
 
 // rows of the direct (int32, cell-order slot) list without their excluded entries
 static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__ perm, int *__restrict__ nbr, int stride,
-                                     int *__restrict__ cnt, const int *__restrict__ ex_start, const int *__restrict__ ex_idx) {
+                                     int *__restrict__ cnt, const int *__restrict__ ex_start, const int *__restrict__ ex_idx,
+                                     PairKeys keys) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const int i = perm[p];
-    if (i >= n_owned) return;
-    const int lo = ex_start[i], hi = ex_start[i + 1];
+    if (perm[p] >= n_owned) return;
+    const long long gi = pair_key(keys, perm, p);
+    if (gi < 0 || gi >= keys.n_tab) return;
+    const int lo = ex_start[gi], hi = ex_start[gi + 1];
     if (lo == hi) return;
+    const int lo14 = keys.s14 ? keys.start14[gi] : 0, hi14 = keys.s14 ? keys.start14[gi + 1] : 0;
+    for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
     int *row = nbr + (size_t)p * stride;
     const int m = min(cnt[p], stride);
     int w = 0;
     for (int e = 0; e < m; e++) {
         const int q = row[e];
-        if (!csr_holds(ex_idx, lo, hi, perm[q])) row[w++] = q;
+        const long long gj = pair_key(keys, perm, q);
+        if (!csr_holds(ex_idx, lo, hi, (int)min(gj, (long long)keys.n_tab))) {
+            row[w++] = q;
+        } else if (lo14 < hi14) {
+            const int k = csr_find(keys.idx14, lo14, hi14, gj);
+            if (k >= 0) keys.s14[k] = q;
+        }
     }
     cnt[p] = w;
 }
@@ -1184,6 +1219,50 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
         if (bitmask & EMDEE_ENERGIES) en[p] += e;
         if (bitmask & EMDEE_VIRIALS) vir[p] += w;
     }
+}
+
+// 1-4 pairs of a decomposed engine: as k_pairs14 -- owner-computes, the table's order, half of E and W to the owner -- over the
+// slots the row filter recorded at the last build (k_filter_rows / k_brick_filter, tag mode) instead of a look-up by id: the
+// partner may be an owned atom or a ghost image (the records hold its shifted coordinates).  With global ids equal to caller
+// indices the order of summation is k_pairs14's.
+template <typename real>
+__global__ void k_pairs14_slots(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm,
+                                const long long *__restrict__ tag, int n_tab, GridP<real> g, LJModel<real> model,
+                                const int *__restrict__ start14, const int *__restrict__ s14, real scale, int bitmask,
+                                real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (perm[p] >= n_owned) return;
+    const long long gi = tag[p];
+    if (gi < 0 || gi >= n_tab) return;
+    const int lo = start14[gi], hi = start14[gi + 1];
+    if (lo == hi) return;
+    real xi, yi, zi, hs_i, te_i;
+    load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
+    real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+    for (int k = lo; k < hi; k++) {
+        const int q = s14[k];
+        if (q < 0) continue;
+        real xj, yj, zj, hs_j, te_j;
+        load_atom(atoms, q, xj, yj, zj, hs_j, te_j);
+        const real dx = min_image(xi - xj, g.plen[0], g.pinv[0]);
+        const real dy = min_image(yi - yj, g.plen[1], g.pinv[1]);
+        const real dz = min_image(zi - zj, g.plen[2], g.pinv[2]);
+        const real r2 = dx * dx + dy * dy + dz * dz;
+        if (r2 < model.rc2) {
+            const real inv_r2 = (real)1 / r2;
+            real E, W;
+            lj_interaction(r2, inv_r2, model, hs_i, te_i, hs_j, te_j, E, W);
+            const real wr2 = W * inv_r2;
+            fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
+            e += E; w += W;
+        }
+    }
+    fx *= scale; fy *= scale; fz *= scale;
+    e *= (real)0.5 * scale; w *= (real)0.5 * scale;
+    if (bitmask & EMDEE_FORCES) { frc[p] += fx; frc[pitch + p] += fy; frc[2 * pitch + p] += fz; }
+    if (bitmask & EMDEE_ENERGIES) en[p] += e;
+    if (bitmask & EMDEE_VIRIALS) vir[p] += w;
 }
 
 // ------------------------------------------------------------------------------------ reductions

@@ -1002,8 +1002,8 @@ struct NbSystem {
     // Pairs the caller names (caller ids; bonded neighbours of a molecular model) are struck from the rows right after every
     // build; the 1-4 pairs among them come back scaled (lj14scale of the reference's force-field file, src/modelling.jl:198)
     // through k_pairs14 after every force pass.  Symmetric CSR tables over caller ids, built on the host once per call
-    // (topology does not change during a run).  Undivided engines only; two-species boxes with exclusions keep the
-    // general-species kernels (a typed row is two block-aligned segments: compacting one would move the other).
+    // (topology does not change during a run); decomposed engines take tables over global ids instead (use_gid_tables).
+    // Two-species boxes with exclusions keep the general-species kernels (a typed row is two block-aligned segments: compacting one would move the other).
     DevBuf<int> ex_start, ex_idx, p14_start, p14_idx;
     bool has_excl = false, has_14 = false;
     double scale14 = 1.0;
@@ -1055,26 +1055,52 @@ struct NbSystem {
         table_atoms = n_atoms;
         has_list = false; plan_valid = false;                // (the rows in use were filtered with the old tables; typed rows are not filtered)
     }
+    // Decomposed engines (dd.hpp DdImpl::set_pair_table): tables over GLOBAL ids, one copy per process shared by its engines; the
+    // rows are keyed by the tags that travel with the atoms, owned atoms and ghosts alike, and the 1-4 partners are found by the
+    // row filter (slots14) instead of by id at every step.
+    bool tab_by_tag = false;
+    const int *gx_start = nullptr, *gx_idx = nullptr, *g14_start = nullptr, *g14_idx = nullptr;
+    int gtab_rows = 0;                                       // global ids 0 .. gtab_rows - 1 have rows
+    DevBuf<int> slots14;                                     // per 1-4 entry of an owned atom's row of g14: the partner's cell-order slot
+    void use_gid_tables(const int *xs, const int *xi, bool excl, const int *ps, const int *pi, size_t n14, double scale, int rows) {
+        if (n14 > 0) slots14.ensure(n14 + 1);
+        tab_by_tag = true;
+        gx_start = xs; gx_idx = xi; g14_start = ps; g14_idx = pi;
+        gtab_rows = rows;
+        has_excl = excl; has_14 = n14 > 0; scale14 = scale;
+    }
+    PairKeys pair_keys() const {
+        if (!tab_by_tag) return PairKeys{nullptr, table_atoms, nullptr, nullptr, nullptr};
+        return PairKeys{tag.ptr, gtab_rows, g14_start, g14_idx, has_14 ? slots14.ptr : nullptr};
+    }
     // right after a build: the rows without their excluded entries
     void apply_exclusions() {
         if (!has_excl || n_total == 0) return;
-        EMDEE_REQUIRE(table_atoms == n_owned && !id_gaps, EMDEE_ERR_STATE, "exclusion tables were set for %d atoms, the state holds %d", table_atoms, n_owned);
+        if (tab_by_tag) EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "exclusion tables over global ids: the state carries no tags");
+        else EMDEE_REQUIRE(table_atoms == n_owned && !id_gaps, EMDEE_ERR_STATE, "exclusion tables were set for %d atoms, the state holds %d", table_atoms, n_owned);
+        const int *xs = tab_by_tag ? gx_start : ex_start.ptr, *xi = tab_by_tag ? gx_idx : ex_idx.ptr;
         if (brick_active) {
             EMDEE_REQUIRE(!typed_active, EMDEE_ERR_STATE, "exclusions: typed rows are not filtered");
             with_brick_variant(variant, [&](auto v) {
                 using V = decltype(v);
                 auto kernel = k_brick_filter<real, typename V::Shape, V::THREADS, V::G>;
                 using BT = BrickTables<typename V::Shape, V::THREADS>;
-                hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(), ex_start.ptr, ex_idx.ptr);
+                hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(), xs, xi, pair_keys());
             });
         } else {
             hipLaunchKernelGGL(k_filter_rows, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, perm.ptr, nbr.ptr, stride,
-                               cnt.ptr, ex_start.ptr, ex_idx.ptr);
+                               cnt.ptr, xs, xi, pair_keys());
         }
     }
     // after a force pass: the scaled 1-4 terms on top
     void add_pairs14(int bitmask) {
         if (!has_14 || n_total == 0) return;
+        if (tab_by_tag) {
+            EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "1-4 table over global ids: the state carries no tags");
+            hipLaunchKernelGGL((k_pairs14_slots<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(),
+                               perm.ptr, tag.ptr, gtab_rows, grid, model, g14_start, slots14.ptr, (real)scale14, bitmask, frc.ptr, en.ptr, vir.ptr);
+            return;
+        }
         EMDEE_REQUIRE(table_atoms == n_owned && !id_gaps, EMDEE_ERR_STATE, "1-4 table was set for %d atoms, the state holds %d", table_atoms, n_owned);
         const bool user = brick_active && (out_f || out_e || out_w);
         hipLaunchKernelGGL((k_pairs14<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
@@ -1274,7 +1300,7 @@ struct NbSystem {
         force_phase = brick_active ? phase : 0;
         if (brick_active) {
             with_brick_variant(variant, [&](auto v) { launch_brick_force<decltype(v)>(bitmask); });
-            add_pairs14(bitmask);
+            if (phase != 1) add_pairs14(bitmask);            // (once per force pass: behind its last half)
             return;
         }
         switch (bitmask) {
@@ -1305,10 +1331,12 @@ struct NbSystem {
     // One inner step of a domain whose tiles do not fit LDS (the direct kernels), obeying the same device words as
     // fused_step: nothing happens if *guard is set (and *trigger is raised, passing the request on), otherwise force pass,
     // full kick and drift in place, *trigger raised if an atom is now skin/2 away from its position at the last build.
-    // Keeps a decomposed run's message sequence independent of which kernels a domain uses (emdee_dd_step).
+    // Keeps a decomposed run's message sequence independent of which kernels a domain uses (emdee_dd_step).  Also the form of a
+    // tiled domain with a 1-4 table (force pass, 1-4 terms, kick + drift): its force pass ignores the guard and leaves forces
+    // at unmoved positions -- the rebuild the raised word brings evaluates them afresh.
     void guarded_split_step(double c, double dt, const int *guard, int *trigger) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
-        EMDEE_REQUIRE(!brick_active, EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
+        EMDEE_REQUIRE(!brick_active || has_14, EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
         if (n_total == 0) return;
         direct_guard = guard;
         compute_forces(EMDEE_FORCES, 0);

@@ -73,6 +73,17 @@ set_langevin!(dd::DomainDecomposition, gamma, temperature; seed=0, first_step=0)
     check(ccall((:emdee_dd_set_langevin, libemdee_hip), Int32, (Ptr{Cvoid}, Float64, Float64, UInt64, UInt64),
                 dd.handle, gamma, temperature, seed, first_step))
 
+# int32_t emdee_dd_set_exclusions(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs);
+# int32_t emdee_dd_set_pairs14(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs, double lj14scale);
+# pairs: 2 x n device matrix of 0-based GLOBAL ids (the gids of set_atoms!); collective, every rank passes the same whole
+# table; before load! or between step! calls; `nothing` clears the table.
+set_exclusions!(dd::DomainDecomposition, pairs::Union{Nothing,HipArray{Int64,2}}) =
+    check(ccall((:emdee_dd_set_exclusions, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), dd.handle,
+                pairs === nothing ? C_NULL : pairs.ptr, pairs === nothing ? 0 : size(pairs, 2)))
+set_pairs14!(dd::DomainDecomposition, pairs::Union{Nothing,HipArray{Int64,2}}, lj14scale) =
+    check(ccall((:emdee_dd_set_pairs14, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64), dd.handle,
+                pairs === nothing ? C_NULL : pairs.ptr, pairs === nothing ? 0 : size(pairs, 2), Float64(lj14scale)))
+
 # int32_t emdee_dd_set_overlap(emdee_dd *dd, int32_t overlap);
 # true (default): interior bricks overlap the halo exchange; false: exchange and one launch over all bricks in order
 set_overlap!(dd::DomainDecomposition, on::Bool) =

@@ -160,7 +160,8 @@ int32_t emdee_md_nbr_list(emdee_md *md, int32_t *counts_dev, int32_t *neighbors_
  * carries no mask -- and the 1-4 pairs are evaluated by a kernel of their own behind every force pass (an integrator with
  * 1-4 pairs steps with the split kernels: force pass, 1-4 terms, kick + drift).  Each call replaces its table; n_pairs = 0
  * clears it.  Undivided boxes (emdee_nbr, emdee_md without ghosts); emdee_md: after emdee_md_set_state.  Two-species boxes with
- * exclusions keep the general-species kernels. */
+ * exclusions keep the general-species kernels.  Decomposed runs: emdee_dd_set_exclusions / emdee_dd_set_pairs14 (tables over
+ * global ids); an integrator lent by emdee_dd_engine refuses these calls with EMDEE_ERR_STATE. */
 int32_t emdee_nbr_set_exclusions(emdee_nbr *nbr, const int32_t *pairs_dev, int32_t n_pairs);
 int32_t emdee_nbr_set_pairs14(emdee_nbr *nbr, const int32_t *pairs_dev, int32_t n_pairs, double lj14scale);
 int32_t emdee_md_set_exclusions(emdee_md *md, const int32_t *pairs_dev, int32_t n_pairs);
@@ -348,6 +349,20 @@ int32_t emdee_dd_phase_times(emdee_dd *dd, double out[8]);
  * cross-stream bookkeeping (small domains).  Same results either way; collective (all ranks must choose alike only for
  * speed, not for correctness).  Call between emdee_dd_step calls. */
 int32_t emdee_dd_set_overlap(emdee_dd *dd, int32_t overlap);
+/* Exclusions and 1-4 pairs of a decomposed run.  pairs_dev: n_pairs pairs {g, h} of GLOBAL ids (the gids of
+ * emdee_dd_set_atoms), 2 n_pairs int64, device; copied.  Semantics as emdee_md_set_exclusions / emdee_md_set_pairs14: an
+ * excluded pair contributes nothing, a 1-4 pair contributes lj14scale times its pair terms (forces, energy and virial halves),
+ * CUTOFF semantics as the list kernels.  Each call replaces its own table; n_pairs = 0 clears it.
+ *   - Collective: every process passes the whole table, all the same one; the domains of a process share one copy.
+ *   - Before emdee_dd_load, or between emdee_dd_step calls: after a load the call rebuilds every domain (rows, 1-4 slots,
+ *     forces), and on return the forces are current and follow the new tables.
+ *   - All or nothing: each pair needs g != h and 0 <= g, h < 2^31, else EMDEE_ERR_INVALID and the previous tables stay in
+ *     force.  A pair naming a gid no domain holds is legal and contributes nothing.
+ * A domain with a 1-4 table steps in the split form (force pass behind the halo, 1-4 terms, kick + drift) under the same guard
+ * words as the fused step; one with exclusions only keeps the fused, overlapped step.  Boxes with a table keep the
+ * general-species kernels.  emdee_md_set_exclusions / _set_pairs14 on an integrator of emdee_dd_engine return EMDEE_ERR_STATE. */
+int32_t emdee_dd_set_exclusions(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs);
+int32_t emdee_dd_set_pairs14(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs, double lj14scale);
 
 #ifdef __cplusplus
 }
