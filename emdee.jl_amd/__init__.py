@@ -18,8 +18,8 @@ from .device import Context, context_for, cu, gpu_available, to_host           #
 from .lennard_jones import (LJAtom, LennardJonesAtom, LennardJonesModel,        # noqa: E402
                             interaction, lennard_jones_atoms)
 from .nonbonded import (ENERGIES, FORCES, VIRIALS, WAVESIZE, AllPairsTiles,     # noqa: E402
-                        NeighborTiles, Val, compute_nonbonded_, naively_compute_nonbonded_,
-                        nonbonded_computation_tiles)
+                        NeighborTiles, Val, compute_nonbonded_, compute_virial_tensor_,
+                        naively_compute_nonbonded_, nonbonded_computation_tiles)
 from .verlet import VelocityVerlet                                              # noqa: E402
 from . import synthetic                                                         # noqa: E402
 from . import domain                                                            # noqa: E402
@@ -29,6 +29,7 @@ from .dd import DomainDecomposition                                             
 
 __all__ = ["LennardJonesModel", "LennardJonesAtom", "LJAtom", "lennard_jones_atoms", "interaction",
            "FORCES", "ENERGIES", "VIRIALS", "Val", "nonbonded_computation_tiles", "compute_nonbonded_",
+           "compute_virial_tensor_",
            "naively_compute_nonbonded_", "NeighborTiles", "AllPairsTiles", "Cells", "update_cells_",
            "VelocityVerlet", "cu", "to_host", "context_for", "Context", "gpu_available", "synthetic",
            "EmDeeError", "LITERAL", "CUTOFF", "WAVESIZE", "domain", "ingest", "dd", "DomainDecomposition"]

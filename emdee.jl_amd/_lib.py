@@ -65,6 +65,7 @@ SIGNATURES = {
     "emdee_nbr_list": [_p, _p, _p, _i32],
     "emdee_md_nbr_list": [_p, _p, _p, _i32],
     "emdee_compute_nonbonded": [_p, _p, _p, _p, _p, _dbl, _p, LJModelC, _p, _i32, _i32],
+    "emdee_compute_virial_tensor": [_p, _p, _p, _dbl, _p, LJModelC, _p, _i32],
     "emdee_compute_nonbonded_tiles": [_p, _p, _p, _p, _p, _dbl, _i32, LJModelC, _p, _i32, _i32, _i32],
     "emdee_compute_nonbonded_naive": [_p, _p, _p, _p, _p, _dbl, _i32, LJModelC, _p, _i32, _i32],
     "emdee_md_create": [_p, _d3, _d3, _i3, LJModelC, _dbl, _i32, _pp],
@@ -81,6 +82,8 @@ SIGNATURES = {
     "emdee_md_pack_positions": [_p, _p, _p, _i32, _d3, _i32, _p],
     "emdee_md_unpack_ghosts": [_p, _p, _i32, _i32],
     "emdee_md_energies": [_p, _d3],
+    "emdee_md_virial_tensor": [_p, _p],
+    "emdee_md_pressure_tensor": [_p, _d3],
     "emdee_md_nbr_stats": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)],
     "emdee_md_count_pairs": [_p, C.POINTER(_i64)],
     "emdee_md_profile": [_p, _i32],
@@ -97,6 +100,7 @@ SIGNATURES = {
     "emdee_dd_load": [_p],
     "emdee_dd_step": [_p, _i32, _dbl, _i32],
     "emdee_dd_energies": [_p, _d3],
+    "emdee_dd_pressure_tensor": [_p, _d3],
     "emdee_dd_counts": [_p, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)],
     "emdee_dd_get_state": [_p, _i32, _p, _p, _p, _p],
     "emdee_dd_engine": [_p, _i32, _pp],

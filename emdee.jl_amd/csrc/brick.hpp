@@ -155,6 +155,8 @@ struct BrickArgs {
     double rcw[3], rlo[3];
     const real *user_pos;      // ... read from the CALLER's array (3 x N, caller order): the engine's records hold positions wrapped
                                // into the box, and x - L rounded to fp32 is not the number the reference divides by L
+    // tensor pass (BITMASK & EMDEE_TENSOR): six pitch-strided planes (xx, yy, zz, xy, xz, yz), or the caller's 6 x N array
+    real *vt, *user_vt;
 };
 
 // ---- cell-relative records: tile coordinates (kernels.hpp RelGrid) ---------------------------------
@@ -1099,6 +1101,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         if (SOA) { xi = plane[ti]; yi = plane[PITCH + ti]; zi = plane[2 * PITCH + ti]; hs_i = te_i = 0; }
         else tile_load<real>(tile, tile_te, ti, xi, yi, zi, hs_i, te_i);
         real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+        real txx = 0, tyy = 0, tzz = 0, txy = 0, txz = 0, tyz = 0;   // (tensor pass only)
         real vx = 0, vy = 0, vz = 0, bx = 0, by = 0, bz = 0, imv = 1, nx = 0, ny = 0, nz = 0;
         // (the SOA kernels fetch these after the pair loop instead: 14 registers less = three workgroups per CU)
         if (MODE == BRICK_STEP && !SOA && have && gl == G - 1) {   // owner lane: its loads fly during the pair loop
@@ -1112,6 +1115,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         // way past one fp32 operation per lane and instruction); the coordinate planes deliver (x_a, x_b) pairs
         // straight into adjacent registers
         f32x2 pfx = {0.f, 0.f}, pfy = {0.f, 0.f}, pfz = {0.f, 0.f}, pe = {0.f, 0.f}, pw = {0.f, 0.f};
+        f32x2 ptxx = {0.f, 0.f}, ptyy = {0.f, 0.f}, ptzz = {0.f, 0.f}, ptxy = {0.f, 0.f}, ptxz = {0.f, 0.f}, ptyz = {0.f, 0.f};
         constexpr bool PACKED = SOA && sizeof(real) == 4;
         auto block2 = [&](const uint4 &q, int b0) {
             if constexpr (PACKED) {
@@ -1152,6 +1156,11 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                             }
                             if (BITMASK & EMDEE_ENERGIES) pe += E;
                             if (BITMASK & EMDEE_VIRIALS) pw += W;
+                            if (BITMASK & EMDEE_TENSOR) {     // W / r2 d^a d^b: three products and six fmas per pair
+                                const f32x2 wr2 = W * inv, hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+                                ptxx += hx * dx; ptyy += hy * dy; ptzz += hz * dz;
+                                ptxy += hx * dy; ptxz += hx * dz; ptyz += hy * dz;
+                            }
                         }
                     }
                 }
@@ -1233,6 +1242,11 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                             }
                             if (BITMASK & EMDEE_ENERGIES) e += E;
                             if (BITMASK & EMDEE_VIRIALS) w += W;
+                            if (BITMASK & EMDEE_TENSOR) {     // W / r2 d^a d^b, d the real-space pair vector (refmath: L times the scaled one)
+                                const real wr2 = W * inv_r2, hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+                                txx += hx * dx; tyy += hy * dy; tzz += hz * dz;
+                                txy += hx * dy; txz += hx * dz; tyz += hy * dz;
+                            }
                         }
                     }
                 }
@@ -1250,6 +1264,8 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         if (PACKED) {
             fx = (real)(pfx.x + pfx.y); fy = (real)(pfy.x + pfy.y); fz = (real)(pfz.x + pfz.y);
             e = (real)(pe.x + pe.y); w = (real)(pw.x + pw.y);
+            txx = (real)(ptxx.x + ptxx.y); tyy = (real)(ptyy.x + ptyy.y); tzz = (real)(ptzz.x + ptzz.y);
+            txy = (real)(ptxy.x + ptxy.y); txz = (real)(ptxz.x + ptxz.y); tyz = (real)(ptyz.x + ptyz.y);
         }
         if (MODE == BRICK_STATS) {
             if (gl == 0) { st_entries += (unsigned long long)m; st_max = max(st_max, m); }
@@ -1261,6 +1277,10 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
             }
             if (BITMASK & EMDEE_ENERGIES) e = group_sum_to_last<G>(e);
             if (BITMASK & EMDEE_VIRIALS) w = group_sum_to_last<G>(w);
+            if (BITMASK & EMDEE_TENSOR) {
+                txx = group_sum_to_last<G>(txx); tyy = group_sum_to_last<G>(tyy); tzz = group_sum_to_last<G>(tzz);
+                txy = group_sum_to_last<G>(txy); txz = group_sum_to_last<G>(txz); tyz = group_sum_to_last<G>(tyz);
+            }
             if (MODE == BRICK_STEP) {
                 if (have && gl == G - 1) {
                     if (SOA) {
@@ -1284,18 +1304,27 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                     if (ex * ex + ey * ey + ez * ez > a.thr2) *a.trigger = 1;
                 }
             } else if (have && gl == G - 1) {
-                if (a.user_f != nullptr || a.user_e != nullptr || a.user_w != nullptr) {
+                if (a.user_f != nullptr || a.user_e != nullptr || a.user_w != nullptr || ((BITMASK & EMDEE_TENSOR) && a.user_vt != nullptr)) {
                     const size_t i = (size_t)a.perm[p];                     // caller index of this atom
                     // (a tuning variant may run the all-outputs kernel for a narrower request: unselected arrays are NULL)
                     if ((BITMASK & EMDEE_FORCES) && a.user_f) { a.user_f[3 * i] = fx; a.user_f[3 * i + 1] = fy; a.user_f[3 * i + 2] = fz; }
                     if ((BITMASK & EMDEE_ENERGIES) && a.user_e) a.user_e[i] = (real)0.5 * e;
                     if ((BITMASK & EMDEE_VIRIALS) && a.user_w) a.user_w[i] = (real)0.5 * w;
+                    if ((BITMASK & EMDEE_TENSOR) && a.user_vt) {
+                        real *t = a.user_vt + 6 * i;
+                        t[0] = (real)0.5 * txx; t[1] = (real)0.5 * tyy; t[2] = (real)0.5 * tzz;
+                        t[3] = (real)0.5 * txy; t[4] = (real)0.5 * txz; t[5] = (real)0.5 * tyz;
+                    }
                 } else {
                     if (BITMASK & EMDEE_FORCES) {
                         a.frc[p] = fx; a.frc[a.pitch + p] = fy; a.frc[2 * a.pitch + p] = fz;
                     }
                     if (BITMASK & EMDEE_ENERGIES) a.en[p] = (real)0.5 * e;   // src/nonbonded.jl:142-145
                     if (BITMASK & EMDEE_VIRIALS) a.vir[p] = (real)0.5 * w;
+                    if (BITMASK & EMDEE_TENSOR) {
+                        a.vt[p] = (real)0.5 * txx; a.vt[a.pitch + p] = (real)0.5 * tyy; a.vt[2 * a.pitch + p] = (real)0.5 * tzz;
+                        a.vt[3 * a.pitch + p] = (real)0.5 * txy; a.vt[4 * a.pitch + p] = (real)0.5 * txz; a.vt[5 * a.pitch + p] = (real)0.5 * tyz;
+                    }
                 }
             }
         }

@@ -278,6 +278,18 @@ int32_t emdee_compute_nonbonded(emdee_ctx *ctx, void *forces_dev, void *energies
     });
 }
 
+int32_t emdee_compute_virial_tensor(emdee_ctx *ctx, void *tensor_dev, const void *positions_dev, double L, emdee_nbr *nbr,
+                                    emdee_lj_model model, const emdee_lj_atom *atoms_dev, int32_t precision) {
+    return guarded([&] {
+        REQUIRE_PTR(ctx, "ctx");
+        REQUIRE_PTR(nbr, "nbr (tiles)");
+        REQUIRE_PTR(tensor_dev, "tensor_dev");
+        REQUIRE_PRECISION(precision);
+        EMDEE_REQUIRE(nbr->ctx == ctx, EMDEE_ERR_INVALID, "neighbour handle belongs to another context");
+        nbr->impl->compute_tensor(tensor_dev, positions_dev, L, model, atoms_dev);
+    });
+}
+
 int32_t emdee_compute_nonbonded_tiles(emdee_ctx *ctx, void *forces_dev, void *energies_dev, void *virials_dev,
                                       const void *positions_dev, double L, int32_t N, emdee_lj_model model,
                                       const emdee_lj_atom *atoms_dev, int32_t bitmask, int32_t mode, int32_t precision) {
@@ -348,6 +360,7 @@ int32_t emdee_md_forces(emdee_md *md, int32_t bitmask, int32_t phase) {
     return guarded([&] {
         REQUIRE_PTR(md, "md");
         EMDEE_REQUIRE(phase >= 0 && phase <= 2, EMDEE_ERR_INVALID, "phase must be 0, 1 or 2");
+        EMDEE_REQUIRE(bitmask >= 0 && bitmask <= 7, EMDEE_ERR_INVALID, "bitmask must be a combination of 1|2|4");   // (the tensor pass is internal)
         md->impl->forces(bitmask, phase);
     });
 }
@@ -387,6 +400,12 @@ int32_t emdee_md_unpack_ghosts(emdee_md *md, const void *buf_dev, int32_t first,
 }
 int32_t emdee_md_energies(emdee_md *md, double out[3]) {
     return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "out"); md->impl->energies(out); });
+}
+int32_t emdee_md_virial_tensor(emdee_md *md, void *tensor_dev) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(tensor_dev, "tensor_dev"); md->impl->virial_tensor(tensor_dev); });
+}
+int32_t emdee_md_pressure_tensor(emdee_md *md, double out[12]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "out"); md->impl->pressure_tensor(out); });
 }
 int32_t emdee_md_nbr_stats(emdee_md *md, int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->stats(builds, listed, max_count, capacity); });
@@ -486,6 +505,9 @@ int32_t emdee_dd_step(emdee_dd *dd, int32_t nsteps, double dt, int32_t rebuild_e
 }
 int32_t emdee_dd_energies(emdee_dd *dd, double out[3]) {
     return guarded([&] { REQUIRE_PTR(dd, "dd"); REQUIRE_PTR(out, "out"); dd->impl->energies(out); });
+}
+int32_t emdee_dd_pressure_tensor(emdee_dd *dd, double out[12]) {
+    return guarded([&] { REQUIRE_PTR(dd, "dd"); REQUIRE_PTR(out, "out"); dd->impl->pressure_tensor(out); });
 }
 int32_t emdee_dd_counts(emdee_dd *dd, int32_t local, int64_t *n_global, int32_t *n_owned, int32_t *n_ghost) {
     return guarded([&] {

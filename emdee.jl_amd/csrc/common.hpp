@@ -17,6 +17,13 @@
 
 namespace emdee {
 
+// ---- internal output bit: the per-atom virial tensor W_i^ab = 1/2 sum_j (-E'r / r^2) d^a d^b, six components per atom in the
+// order (xx, yy, zz, xy, xz, yz).  Never part of the public bitmask (emdee_md_forces(md, 8, ...) is refused).  The tensor pass
+// (emdee_compute_virial_tensor, emdee_md_virial_tensor / _pressure_tensor) writes energies, virials and the tensor and leaves
+// the forces alone: the integrator keeps the bits of its own force-only kernels, so a sample does not move a trajectory.
+constexpr int EMDEE_TENSOR = 8;
+constexpr int TENSOR_PASS = EMDEE_ENERGIES | EMDEE_VIRIALS | EMDEE_TENSOR;
+
 // ---- error plumbing: no exception crosses the C ABI -------------------------------------------
 void set_error(const char *fmt, ...);
 const char *get_error();

@@ -359,7 +359,7 @@ struct DdImpl : IDd {
             if (d->owns_ctx) d->md->caller_ctx = c;        // queries of this engine order their results on the caller's stream
             d->words.ensure(DD_WORDS);
             d->small.ensure(96);
-            d->red.ensure(8);
+            d->red.ensure(12);
             EMDEE_HIP_CHECK(hipMemsetAsync(d->words.ptr, 0, DD_WORDS * sizeof(int), d->stream()));
         }
         if (use_rccl) {
@@ -500,7 +500,7 @@ struct DdImpl : IDd {
             for (int k = 0; k < n; k++) out[k] *= (double)world;   // (every rank of the rehearsed grid holds the same)
         if (!use_rccl) return;
         Domain<real> &d = *dom[0];
-        EMDEE_REQUIRE(n <= 8, EMDEE_ERR_INVALID, "allreduce_sum: at most 8 values");
+        EMDEE_REQUIRE(n <= 12, EMDEE_ERR_INVALID, "allreduce_sum: at most 12 values");
         EMDEE_HIP_CHECK(hipMemcpyAsync(d.red.ptr, out, n * sizeof(double), hipMemcpyHostToDevice, d.stream()));
         EMDEE_RCCL_CHECK(RcclApi::get().AllReduce(d.red.ptr, d.red.ptr, (size_t)n, RcclApi::kFloat64, RcclApi::kSum, comm, d.stream()));
         EMDEE_HIP_CHECK(hipMemcpyAsync(out, d.red.ptr, n * sizeof(double), hipMemcpyDeviceToHost, d.stream()));
@@ -1515,6 +1515,19 @@ struct DdImpl : IDd {
             vals.push_back({e[0], e[1], e[2]});
         }
         allreduce_sum(vals, 3, out);
+    }
+    void pressure_tensor(double out[12]) override {
+        use_device(user_ctx);
+        EMDEE_REQUIRE(loaded, EMDEE_ERR_STATE, "emdee_dd_pressure_tensor: call emdee_dd_load first");
+        join_halo();
+        std::vector<std::vector<double>> vals;
+        for (auto &pd : dom) {
+            // (ghosts are current whenever the forces are, as for energies)
+            double t[12];
+            pd->md->pressure_tensor(t);
+            vals.push_back(std::vector<double>(t, t + 12));
+        }
+        allreduce_sum(vals, 12, out);
     }
     int64_t n_atoms_global() override { return n_global; }
     int n_owned(int l) override { return local(l).n_owned; }

@@ -22,6 +22,7 @@ struct INbr {
     virtual void count_pairs(int64_t *pairs) = 0;
     virtual void export_list(int32_t *counts, int32_t *neighbors, int32_t capacity) = 0;
     virtual void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) = 0;
+    virtual void compute_tensor(void *tensor, const void *positions, double L, const emdee_lj_model &model, const emdee_lj_atom *atoms) = 0;
 };
 
 struct IMd {
@@ -40,6 +41,8 @@ struct IMd {
                                 void *buf) = 0;
     virtual void unpack_ghosts(const void *buf, int first, int n) = 0;
     virtual void energies(double out[3]) = 0;
+    virtual void virial_tensor(void *out) = 0;
+    virtual void pressure_tensor(double out[12]) = 0;
     virtual void stats(int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) = 0;
     virtual void count_pairs(int64_t *pairs) = 0;
     virtual void export_list(int32_t *counts, int32_t *neighbors, int32_t capacity) = 0;
@@ -58,6 +61,7 @@ struct IDd {
     virtual void load() = 0;
     virtual void step(int nsteps, double dt, int rebuild_every) = 0;
     virtual void energies(double out[3]) = 0;
+    virtual void pressure_tensor(double out[12]) = 0;
     virtual int64_t n_atoms_global() = 0;
     virtual int n_owned(int local) = 0;
     virtual int n_ghost(int local) = 0;

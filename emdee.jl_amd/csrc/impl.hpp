@@ -88,6 +88,45 @@ struct NbrImpl : INbr {
         if (N == 0 || bitmask == 0) return;
         EMDEE_REQUIRE(positions && atoms, EMDEE_ERR_INVALID, "positions/atoms are NULL");
         const real *pos = (const real *)positions;
+        prepare(pos, L, model, atoms);
+        real *uf = (bitmask & EMDEE_FORCES) ? (real *)forces : nullptr, *ue = (bitmask & EMDEE_ENERGIES) ? (real *)energies : nullptr,
+             *uw = (bitmask & EMDEE_VIRIALS) ? (real *)virials : nullptr;
+        if (sys.brick_active) {
+            // the tiled kernels write the caller's arrays themselves (owner lane, caller index from perm)
+            sys.out_f = uf; sys.out_e = ue; sys.out_w = uw;
+            sys.ref_pos = pos;
+            sys.compute_forces(bitmask);
+            sys.ref_pos = nullptr;
+            sys.out_f = sys.out_e = sys.out_w = nullptr;
+        } else {
+            sys.compute_forces(bitmask);
+            sys.unsort(nullptr, nullptr, uf, ue, uw);
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    // emdee_compute_virial_tensor: the per-atom virial tensors (6 x N, caller order) of the same pairs compute() sums
+    void compute_tensor(void *tensor, const void *positions, double L, const emdee_lj_model &model, const emdee_lj_atom *atoms) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(tensor || N == 0, EMDEE_ERR_INVALID, "tensor is NULL");
+        EMDEE_REQUIRE(L > 0, EMDEE_ERR_INVALID, "L must be positive");
+        if (N == 0) return;
+        EMDEE_REQUIRE(positions && atoms, EMDEE_ERR_INVALID, "positions/atoms are NULL");
+        const real *pos = (const real *)positions;
+        prepare(pos, L, model, atoms);
+        if (sys.brick_active) {
+            sys.out_vt = (real *)tensor;
+            sys.ref_pos = pos;
+            sys.compute_forces(TENSOR_PASS);
+            sys.ref_pos = nullptr;
+            sys.out_vt = nullptr;
+        } else {
+            sys.compute_forces(TENSOR_PASS);
+            sys.unsort_tensor((real *)tensor);
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    // the list for these positions: kept if it still covers them, else re-sorted or rebuilt
+    void prepare(const real *pos, double L, const emdee_lj_model &model, const emdee_lj_atom *atoms) {
         const double lo[3] = {0, 0, 0}, len[3] = {L, L, L};
         const int per[3] = {1, 1, 1};   // cubic periodic box, the reference's only geometry (Q9)
         sys.set_box(lo, len, per);
@@ -110,20 +149,6 @@ struct NbrImpl : INbr {
             }
         }
         if (rebuild && !resorted) sys.load_user(N, 0, pos, nullptr, atoms, nullptr);
-        real *uf = (bitmask & EMDEE_FORCES) ? (real *)forces : nullptr, *ue = (bitmask & EMDEE_ENERGIES) ? (real *)energies : nullptr,
-             *uw = (bitmask & EMDEE_VIRIALS) ? (real *)virials : nullptr;
-        if (sys.brick_active) {
-            // the tiled kernels write the caller's arrays themselves (owner lane, caller index from perm)
-            sys.out_f = uf; sys.out_e = ue; sys.out_w = uw;
-            sys.ref_pos = pos;
-            sys.compute_forces(bitmask);
-            sys.ref_pos = nullptr;
-            sys.out_f = sys.out_e = sys.out_w = nullptr;
-        } else {
-            sys.compute_forces(bitmask);
-            sys.unsort(nullptr, nullptr, uf, ue, uw);
-        }
-        EMDEE_HIP_CHECK(hipGetLastError());
     }
     void stats(int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) override {
         use_device(sys.ctx);
@@ -298,6 +323,29 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
         if ((current_mask & 7) != 7) forces(7, 0);
         sys.energy_sums(0.0, out);
+    }
+    // the tensor pass, unless the tensors are current: energies, virials and tensors; the forces stay as they are
+    void tensor_pass() {
+        if (current_mask & EMDEE_TENSOR) return;
+        sys.compute_forces(TENSOR_PASS, 0);
+        current_mask |= TENSOR_PASS;
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    void virial_tensor(void *out) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
+        EMDEE_REQUIRE(out || sys.n_owned == 0, EMDEE_ERR_INVALID, "tensor is NULL");
+        tensor_pass();
+        sys.ids_map();                                       // (scratch of the engine's own: before the fence)
+        FenceOut fence(caller_ctx, sys.stream());
+        sys.unsort_tensor((real *)out);
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    void pressure_tensor(double out[12]) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
+        tensor_pass();
+        sys.tensor_sums(out);
     }
     void stats(int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) override {
         use_device(sys.ctx);

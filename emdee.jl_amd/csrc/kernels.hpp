@@ -824,8 +824,10 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
                                                               const int *__restrict__ cnt, GridP<real> g,
                                                               LJModel<real> model, size_t pitch,
                                                               real *__restrict__ frc, real *__restrict__ en,
-                                                              real *__restrict__ vir, const int *__restrict__ guard = nullptr) {
-    __shared__ real s_out[5][FORCE_ATOMS];
+                                                              real *__restrict__ vir, const int *__restrict__ guard = nullptr,
+                                                              real *__restrict__ vt = nullptr) {
+    constexpr int NOUT = (BITMASK & EMDEE_TENSOR) ? 11 : 5;   // f, e, w (+ the six tensor components)
+    __shared__ real s_out[NOUT][FORCE_ATOMS];
     if (guard != nullptr && *guard != 0) return;   // a step queued behind a rebuild request (emdee_dd_step): leave no trace
     const int lane = threadIdx.x & (WAVE - 1);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
@@ -840,6 +842,7 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
         const int p = first + slot;
         if (p >= n) break;
         real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+        real tv[6] = {0, 0, 0, 0, 0, 0};   // (tensor pass only: xx, yy, zz, xy, xz, yz)
         if (perm[p] < n_owned) {
             real xi, yi, zi, hs_i, te_i;
             load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
@@ -863,6 +866,11 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
                     }
                     if (BITMASK & EMDEE_ENERGIES) e += E;
                     if (BITMASK & EMDEE_VIRIALS) w += W;
+                    if (BITMASK & EMDEE_TENSOR) {   // W / r2 d^a d^b
+                        const real wr2 = W * inv_r2, hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+                        tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
+                        tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
+                    }
                 }
             }
             if (BITMASK & EMDEE_FORCES) {
@@ -870,11 +878,15 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
             }
             if (BITMASK & EMDEE_ENERGIES) e = wave_sum_to_lane63(e);
             if (BITMASK & EMDEE_VIRIALS) w = wave_sum_to_lane63(w);
+            if (BITMASK & EMDEE_TENSOR)
+                for (int c = 0; c < 6; c++) tv[c] = wave_sum_to_lane63(tv[c]);
         }
         if (lane == WAVE - 1) {
             s_out[0][slot] = fx; s_out[1][slot] = fy; s_out[2][slot] = fz;
             s_out[3][slot] = (real)0.5 * e;   // half of each pair term per atom, src/nonbonded.jl:142-145
             s_out[4][slot] = (real)0.5 * w;
+            if (BITMASK & EMDEE_TENSOR)
+                for (int c = 0; c < 6; c++) s_out[(NOUT - 6) + c][slot] = (real)0.5 * tv[c];
         }
     }
     __syncthreads();
@@ -885,6 +897,8 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
             if (BITMASK & EMDEE_ENERGIES) en[first + col] = s_out[3][col];
             if (BITMASK & EMDEE_VIRIALS) vir[first + col] = s_out[4][col];
         }
+        if (BITMASK & EMDEE_TENSOR)
+            for (int c = plane; c < 6; c += FORCE_BLOCK / FORCE_ATOMS) vt[c * pitch + first + col] = s_out[(NOUT - 6) + c][col];
     }
 }
 
@@ -1177,11 +1191,13 @@ static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__
 // 1-4 pairs: owner-computes over the symmetric table (no atomics, a fixed order of summation); the scaled pair terms are
 // ADDED to what the list kernels have left -- in the cell-ordered arrays, or in the caller's arrays when the operator
 // path had its results written there (user_*: caller order).
-template <typename real>
+// (TENSOR: the tensor pass's instance; the force and observable passes keep the instance without the six sums)
+template <typename real, bool TENSOR = false>
 __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm,
                           const int *__restrict__ inv_perm, GridP<real> g, LJModel<real> model, const int *__restrict__ start14,
                           const int *__restrict__ idx14, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
-                          real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w) {
+                          real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
+                          real *__restrict__ vt = nullptr, real *__restrict__ user_vt = nullptr) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const int i = perm[p];
@@ -1191,6 +1207,7 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
     real xi, yi, zi, hs_i, te_i;
     load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
     real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+    real tv[6] = {0, 0, 0, 0, 0, 0};                           // (tensor pass: the scaled terms of the tensor, as of w)
     for (int k = lo; k < hi; k++) {
         const int q = inv_perm[idx14[k]];
         real xj, yj, zj, hs_j, te_j;
@@ -1206,18 +1223,28 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
             const real wr2 = W * inv_r2;                      // src/nonbonded.jl:139
             fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
             e += E; w += W;
+            if (TENSOR) {
+                const real hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+                tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
+                tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
+            }
         }
     }
     fx *= scale; fy *= scale; fz *= scale;
     e *= (real)0.5 * scale; w *= (real)0.5 * scale;           // src/nonbonded.jl:142-145: half of a pair's E and W to either atom
-    if (user_f != nullptr || user_e != nullptr || user_w != nullptr) {
+    for (int c = 0; c < 6; c++) tv[c] *= (real)0.5 * scale;
+    if (user_f != nullptr || user_e != nullptr || user_w != nullptr || (TENSOR && user_vt != nullptr)) {
         if ((bitmask & EMDEE_FORCES) && user_f) { user_f[3 * (size_t)i] += fx; user_f[3 * (size_t)i + 1] += fy; user_f[3 * (size_t)i + 2] += fz; }
         if ((bitmask & EMDEE_ENERGIES) && user_e) user_e[i] += e;
         if ((bitmask & EMDEE_VIRIALS) && user_w) user_w[i] += w;
+        if (TENSOR && user_vt)
+            for (int c = 0; c < 6; c++) user_vt[6 * (size_t)i + c] += tv[c];
     } else {
         if (bitmask & EMDEE_FORCES) { frc[p] += fx; frc[pitch + p] += fy; frc[2 * pitch + p] += fz; }
         if (bitmask & EMDEE_ENERGIES) en[p] += e;
         if (bitmask & EMDEE_VIRIALS) vir[p] += w;
+        if (TENSOR)
+            for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
     }
 }
 
@@ -1225,11 +1252,11 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
 // slots the row filter recorded at the last build (k_filter_rows / k_brick_filter, tag mode) instead of a look-up by id: the
 // partner may be an owned atom or a ghost image (the records hold its shifted coordinates).  With global ids equal to caller
 // indices the order of summation is k_pairs14's.
-template <typename real>
+template <typename real, bool TENSOR = false>
 __global__ void k_pairs14_slots(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm,
                                 const long long *__restrict__ tag, int n_tab, GridP<real> g, LJModel<real> model,
                                 const int *__restrict__ start14, const int *__restrict__ s14, real scale, int bitmask,
-                                real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir) {
+                                real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir, real *__restrict__ vt = nullptr) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     if (perm[p] >= n_owned) return;
@@ -1240,6 +1267,7 @@ __global__ void k_pairs14_slots(int n, int n_owned, size_t pitch, AtomView<real>
     real xi, yi, zi, hs_i, te_i;
     load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
     real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+    real tv[6] = {0, 0, 0, 0, 0, 0};                           // (tensor pass: the scaled terms of the tensor, as of w)
     for (int k = lo; k < hi; k++) {
         const int q = s14[k];
         if (q < 0) continue;
@@ -1256,13 +1284,21 @@ __global__ void k_pairs14_slots(int n, int n_owned, size_t pitch, AtomView<real>
             const real wr2 = W * inv_r2;
             fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
             e += E; w += W;
+            if (TENSOR) {
+                const real hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+                tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
+                tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
+            }
         }
     }
     fx *= scale; fy *= scale; fz *= scale;
     e *= (real)0.5 * scale; w *= (real)0.5 * scale;
+    for (int c = 0; c < 6; c++) tv[c] *= (real)0.5 * scale;
     if (bitmask & EMDEE_FORCES) { frc[p] += fx; frc[pitch + p] += fy; frc[2 * pitch + p] += fz; }
     if (bitmask & EMDEE_ENERGIES) en[p] += e;
     if (bitmask & EMDEE_VIRIALS) vir[p] += w;
+    if (TENSOR)
+        for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
 }
 
 // ------------------------------------------------------------------------------------ reductions
@@ -1320,6 +1356,57 @@ static __global__ __launch_bounds__(RED_BLOCK) void k_final_sum3(int nblocks, co
         double t = block_sum(s, sh);
         if (threadIdx.x == 0) out[q] = t;
     }
+}
+
+// Pressure tensor sums: partial[b][0..5] = sum of the owned atoms' virial tensors W_i, [6..11] = kinetic tensor
+// sum m_i v_i^a v_i^b (with the velocities k_energy_partials takes for its kinetic energy, no pending kick), both in the order
+// (xx, yy, zz, xy, xz, yz); fp64, fixed order, no atomics (k_final_sums completes them)
+constexpr int TENSOR_SUMS = 12;
+template <typename real>
+__global__ __launch_bounds__(RED_BLOCK) void k_tensor_partials(int n, int n_owned, size_t pitch, const int *__restrict__ perm,
+                                                                const real *__restrict__ vt, const real *__restrict__ vel,
+                                                                const real *__restrict__ inv_mass, double *__restrict__ partial) {
+    __shared__ double sh[RED_BLOCK / WAVE];
+    double s[TENSOR_SUMS];
+    for (int q = 0; q < TENSOR_SUMS; q++) s[q] = 0.0;
+    for (int p = blockIdx.x * RED_BLOCK + threadIdx.x; p < n; p += gridDim.x * RED_BLOCK) {
+        if (perm[p] >= n_owned) continue;
+        for (int c = 0; c < 6; c++) s[c] += (double)vt[c * pitch + p];
+        if (vel) {
+            const double m = 1.0 / (double)(inv_mass ? inv_mass[p] : (real)1);
+            const double vx = (double)vel[p], vy = (double)vel[pitch + p], vz = (double)vel[2 * pitch + p];
+            s[6] += m * vx * vx; s[7] += m * vy * vy; s[8] += m * vz * vz;
+            s[9] += m * vx * vy; s[10] += m * vx * vz; s[11] += m * vy * vz;
+        }
+    }
+    for (int q = 0; q < TENSOR_SUMS; q++) {
+        const double t = block_sum(s[q], sh);
+        if (threadIdx.x == 0) partial[TENSOR_SUMS * blockIdx.x + q] = t;
+    }
+}
+
+// out[q] = sum over b of partial[b][q], q < nq (k_final_sum3 for any number of sums)
+static __global__ __launch_bounds__(RED_BLOCK) void k_final_sums(int nblocks, int nq, const double *__restrict__ partial,
+                                                                 double *__restrict__ out) {
+    __shared__ double sh[RED_BLOCK / WAVE];
+    for (int q = 0; q < nq; q++) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < nblocks; b += RED_BLOCK) s += partial[(size_t)nq * b + q];
+        double t = block_sum(s, sh);
+        if (threadIdx.x == 0) out[q] = t;
+    }
+}
+
+// per-atom tensors in caller order, owned atoms only: out[6 i + c] = vt[c][p] (i: k_unsort's caller index)
+template <typename real>
+__global__ void k_unsort_tensor(int n_owned, int n_total, size_t pitch, const int *__restrict__ perm, const int *__restrict__ cmap,
+                                const real *__restrict__ vt, real *__restrict__ out) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_total) return;
+    const int id = perm[p];
+    const int i = cmap ? cmap[id] : id;
+    if (i >= n_owned) return;
+    for (int c = 0; c < 6; c++) out[6 * (size_t)i + c] = vt[c * pitch + p];
 }
 
 // list statistics: out[0] = entries, out[1] = max row, out[2] = entries with r2 < rc2

@@ -536,6 +536,7 @@ struct NbSystem {
         a.guard = step_guard;
         a.btab = btab_valid ? btab.ptr : nullptr;
         a.user_f = out_f; a.user_e = out_e; a.user_w = out_w;
+        a.vt = vt.ptr; a.user_vt = out_vt;
         a.noise = lgv_on ? noise.ptr : nullptr; a.lgv_c1 = lgv_on ? (real)lgv_c1 : (real)1;
         return a;
     }
@@ -556,7 +557,7 @@ struct NbSystem {
     template <class V, int MODE, int BM>
     void launch_typed_kernel() {
         if constexpr (typed_variant<V>()) {
-            constexpr int M = (MODE == BRICK_STATS) ? 0 : ((MODE == BRICK_STEP || BM == 1) ? 1 : 7);
+            constexpr int M = (MODE == BRICK_STATS) ? 0 : ((MODE == BRICK_STEP || BM == 1) ? 1 : BM == TENSOR_PASS ? TENSOR_PASS : 7);
             auto kernel = k_typed<real, typename V::Shape, V::THREADS, V::G, MODE, M>;
             const size_t lds = typed_force_lds_bytes<real, typename V::Shape, V::THREADS>(own_cap);
             allow_big_lds(kernel, lds);
@@ -571,7 +572,7 @@ struct NbSystem {
     void launch_brick_kernel() {
         if (typed_active) { launch_typed_kernel<V, MODE, BM>(); return; }
         // single-species fast path for the kernels of the MD loop (default variant only)
-        if constexpr (std::is_same<V, BrickVariant<0>>::value && (MODE == BRICK_STEP || (MODE == BRICK_FORCE && (BM == 1 || BM == 7)))) {
+        if constexpr (std::is_same<V, BrickVariant<0>>::value && (MODE == BRICK_STEP || (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)))) {
             // (the fp64 variant keeps coordinate planes only in LDS and needs the tile to fit their fixed pitch)
             if (uniform_atoms && tile_cap <= SOA_SLOTS && idx_shift == PLANE_SHIFT && !(MODE == BRICK_FORCE && sizeof(real) == 4 && refmath && ref_pos != nullptr)) {
                 launch_brick_kernel_impl<V, MODE, BM, true>();
@@ -603,11 +604,13 @@ struct NbSystem {
                 case 4: launch_brick_kernel<V, BRICK_FORCE, 4>(); return;
                 case 5: launch_brick_kernel<V, BRICK_FORCE, 5>(); return;
                 case 6: launch_brick_kernel<V, BRICK_FORCE, 6>(); return;
+                case TENSOR_PASS: launch_brick_kernel<V, BRICK_FORCE, TENSOR_PASS>(); return;
                 default: launch_brick_kernel<V, BRICK_FORCE, 7>(); return;
             }
         }
-        // tuning variants carry only the two masks the MD loop uses
+        // tuning variants carry only the two masks the MD loop uses, and the tensor pass
         if (bitmask == 1) launch_brick_kernel<V, BRICK_FORCE, 1>();
+        else if (bitmask == TENSOR_PASS) launch_brick_kernel<V, BRICK_FORCE, TENSOR_PASS>();
         else launch_brick_kernel<V, BRICK_FORCE, 7>();
     }
 
@@ -1097,15 +1100,19 @@ struct NbSystem {
         if (!has_14 || n_total == 0) return;
         if (tab_by_tag) {
             EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "1-4 table over global ids: the state carries no tags");
-            hipLaunchKernelGGL((k_pairs14_slots<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(),
-                               perm.ptr, tag.ptr, gtab_rows, grid, model, g14_start, slots14.ptr, (real)scale14, bitmask, frc.ptr, en.ptr, vir.ptr);
+            auto kernel = (bitmask & EMDEE_TENSOR) ? k_pairs14_slots<real, true> : k_pairs14_slots<real, false>;
+            hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(),
+                               perm.ptr, tag.ptr, gtab_rows, grid, model, g14_start, slots14.ptr, (real)scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
+                               vt.ptr);
             return;
         }
         EMDEE_REQUIRE(table_atoms == n_owned && !id_gaps, EMDEE_ERR_STATE, "1-4 table was set for %d atoms, the state holds %d", table_atoms, n_owned);
-        const bool user = brick_active && (out_f || out_e || out_w);
-        hipLaunchKernelGGL((k_pairs14<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
+        const bool user = brick_active && (out_f || out_e || out_w || out_vt);
+        auto kernel = (bitmask & EMDEE_TENSOR) ? k_pairs14<real, true> : k_pairs14<real, false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
                            inv_perm.ptr, grid, model, p14_start.ptr, p14_idx.ptr, (real)scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
-                           user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr);
+                           user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
+                           user ? out_vt : (real *)nullptr);
     }
 
     // ---------------------------------------------------------------- forces
@@ -1117,7 +1124,7 @@ struct NbSystem {
         int per_xcd = (nblocks + NXCD - 1) / NXCD;
         hipLaunchKernelGGL((k_lj_force_nbr<real, BM>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
                            per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
-                           vir.ptr, direct_guard);
+                           vir.ptr, direct_guard, vt.ptr);
     }
 
     int force_phase = 0;
@@ -1286,6 +1293,9 @@ struct NbSystem {
 
     // operator path: outputs of the next compute_forces go straight to these caller-order arrays (tiled kernels only)
     real *out_f = nullptr, *out_e = nullptr, *out_w = nullptr;
+    real *out_vt = nullptr;               // ... and the tensor pass's 6 x N array
+    // per-atom virial tensors of the last tensor pass (TENSOR_PASS): six planes of pitch slots, allocated on first use
+    DevBuf<real> vt;
     // fp32 operator path: pair geometry in the reference's own Float32 arithmetic (scaled positions, minimum image per
     // pair; brick.hpp BrickArgs::refmath) -- what keeps compute_nonbonded! within the reference's 1e-4 of its CPU loop
     bool refmath = false;
@@ -1293,8 +1303,9 @@ struct NbSystem {
 
     void compute_forces(int bitmask, int phase = 0) {
         EMDEE_REQUIRE(has_list, EMDEE_ERR_STATE, "no neighbour list");
-        EMDEE_REQUIRE(bitmask >= 0 && bitmask <= 7, EMDEE_ERR_INVALID, "bitmask must be a combination of 1|2|4");
+        EMDEE_REQUIRE((bitmask >= 0 && bitmask <= 7) || bitmask == TENSOR_PASS, EMDEE_ERR_INVALID, "bitmask must be a combination of 1|2|4");
         if (n_total == 0 || bitmask == 0) return;
+        if (bitmask & EMDEE_TENSOR) vt.ensure(6 * pitch);
         if (!brick_active && phase == 1) return;   // the direct kernels have no brick phases: all work in phase 2
         Timed t(this, T_FORCE);
         force_phase = brick_active ? phase : 0;
@@ -1310,6 +1321,7 @@ struct NbSystem {
             case 4: launch_direct_force<4>(); break;
             case 5: launch_direct_force<5>(); break;
             case 6: launch_direct_force<6>(); break;
+            case TENSOR_PASS: launch_direct_force<TENSOR_PASS>(); break;
             default: launch_direct_force<7>(); break;
         }
         add_pairs14(bitmask);
@@ -1370,6 +1382,28 @@ struct NbSystem {
         hipLaunchKernelGGL(k_final_sum3, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, partial.ptr, sums.ptr);
         EMDEE_HIP_CHECK(hipMemcpyAsync(out, sums.ptr, 3 * sizeof(double), hipMemcpyDeviceToHost, stream()));
         EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+    }
+
+    // out[0..5] = sum of the owned atoms' virial tensors (the last tensor pass), out[6..11] = kinetic tensor sum m v^a v^b;
+    // (xx, yy, zz, xy, xz, yz), fp64, blocking
+    DevBuf<double> tpartial;
+    void tensor_sums(double out[TENSOR_SUMS]) {
+        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
+        if (n_total == 0) return;
+        int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+        tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + TENSOR_SUMS);
+        double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
+        hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                           vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
+        hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot);
+        EMDEE_HIP_CHECK(hipMemcpyAsync(out, tot, TENSOR_SUMS * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+    }
+    // caller-order copy of the last tensor pass's per-atom tensors (owned atoms, 6 x n_owned)
+    void unsort_tensor(real *out) {
+        if (n_total == 0) return;
+        hipLaunchKernelGGL((k_unsort_tensor<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_owned, n_total, pitch,
+                           perm.ptr, ids_map(), vt.ptr, out);
     }
 
     void list_stats(bool count_pairs, int64_t *listed, int32_t *max_count, int64_t *inside) {

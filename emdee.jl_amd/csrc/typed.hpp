@@ -707,6 +707,7 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
         const real xi = plane[ti], yi = plane[PITCH + ti], zi = plane[2 * PITCH + ti];
         const PairC c0 = ptab[t_i * TNT], c1 = ptab[t_i * TNT + 1];
         real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+        real txx = 0, tyy = 0, tzz = 0, txy = 0, txz = 0, tyz = 0;   // (tensor pass only)
         // one block of 8 G neighbours of one species: lane gl holds entries b0 + gl + t G, t = 0..7, in q
         auto block = [&](const uint4 &q, int b0, int wm, int m, const PairC &c) {
             // The coordinates of entry t + 1 are requested BEFORE the arithmetic of entry t (round 5): this kernel runs four
@@ -745,6 +746,11 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
                         }
                         if (BITMASK & EMDEE_ENERGIES) e += E;
                         if (BITMASK & EMDEE_VIRIALS) w += W;
+                        if (BITMASK & EMDEE_TENSOR) {         // W / r2 d^a d^b (brick.hpp k_brick)
+                            const real wr2 = W * inv_r2, hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+                            txx += hx * dx; tyy += hy * dy; tzz += hz * dz;
+                            txy += hx * dy; txz += hx * dz; tyz += hy * dz;
+                        }
                     }
                 }
             }
@@ -777,6 +783,10 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
             if (BITMASK & EMDEE_FORCES) { fx = group_sum_to_last<G>(fx); fy = group_sum_to_last<G>(fy); fz = group_sum_to_last<G>(fz); }
             if (BITMASK & EMDEE_ENERGIES) e = group_sum_to_last<G>(e);
             if (BITMASK & EMDEE_VIRIALS) w = group_sum_to_last<G>(w);
+            if (BITMASK & EMDEE_TENSOR) {
+                txx = group_sum_to_last<G>(txx); tyy = group_sum_to_last<G>(tyy); tzz = group_sum_to_last<G>(tzz);
+                txy = group_sum_to_last<G>(txy); txz = group_sum_to_last<G>(txz); tyz = group_sum_to_last<G>(tyz);
+            }
             if (MODE == BRICK_STEP) {
                 if (have && gl == G - 1) {
                     real vx = a.vel[p], vy = a.vel[a.pitch + p], vz = a.vel[2 * a.pitch + p];
@@ -795,15 +805,24 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
                     if (ex * ex + ey * ey + ez * ez > a.thr2) *a.trigger = 1;
                 }
             } else if (have && gl == G - 1) {
-                if (a.user_f != nullptr || a.user_e != nullptr || a.user_w != nullptr) {
+                if (a.user_f != nullptr || a.user_e != nullptr || a.user_w != nullptr || ((BITMASK & EMDEE_TENSOR) && a.user_vt != nullptr)) {
                     const size_t i = (size_t)a.perm[p];                     // caller index of this atom
                     if ((BITMASK & EMDEE_FORCES) && a.user_f) { a.user_f[3 * i] = fx; a.user_f[3 * i + 1] = fy; a.user_f[3 * i + 2] = fz; }
                     if ((BITMASK & EMDEE_ENERGIES) && a.user_e) a.user_e[i] = (real)0.5 * e;
                     if ((BITMASK & EMDEE_VIRIALS) && a.user_w) a.user_w[i] = (real)0.5 * w;
+                    if ((BITMASK & EMDEE_TENSOR) && a.user_vt) {
+                        real *t = a.user_vt + 6 * i;
+                        t[0] = (real)0.5 * txx; t[1] = (real)0.5 * tyy; t[2] = (real)0.5 * tzz;
+                        t[3] = (real)0.5 * txy; t[4] = (real)0.5 * txz; t[5] = (real)0.5 * tyz;
+                    }
                 } else {
                     if (BITMASK & EMDEE_FORCES) { a.frc[p] = fx; a.frc[a.pitch + p] = fy; a.frc[2 * a.pitch + p] = fz; }
                     if (BITMASK & EMDEE_ENERGIES) a.en[p] = (real)0.5 * e;   // src/nonbonded.jl:142-145
                     if (BITMASK & EMDEE_VIRIALS) a.vir[p] = (real)0.5 * w;
+                    if (BITMASK & EMDEE_TENSOR) {
+                        a.vt[p] = (real)0.5 * txx; a.vt[a.pitch + p] = (real)0.5 * tyy; a.vt[2 * a.pitch + p] = (real)0.5 * tzz;
+                        a.vt[3 * a.pitch + p] = (real)0.5 * txy; a.vt[4 * a.pitch + p] = (real)0.5 * txz; a.vt[5 * a.pitch + p] = (real)0.5 * tyz;
+                    }
                 }
             }
         }

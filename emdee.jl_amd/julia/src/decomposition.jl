@@ -2,7 +2,7 @@
 # include/emdee_hip.h.  Build-defined: the reference is single-GPU (SURVEY.md 8(b) table, 8(e)).  One Julia process
 # per GPU (Distributed.jl / MPI.jl workers); rank 0 generates the communicator id and the caller hands it to the
 # other ranks by its own means, e.g.   id = rank == 0 ? dd_unique_id() : nothing;  id = MPI.bcast(id, 0, comm).
-export DomainDecomposition, dd_unique_id, set_atoms!, load!, owned_state!, set_overlap!
+export DomainDecomposition, dd_unique_id, set_atoms!, load!, owned_state!, set_overlap!, pressure_tensor
 
 mutable struct DomainDecomposition{T}
     handle::Ptr{Cvoid}
@@ -53,6 +53,14 @@ function energies(dd::DomainDecomposition)
     out = zeros(Float64, 3)
     check(ccall((:emdee_dd_energies, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), dd.handle, out))
     return (potential=out[1], kinetic=out[2], virial=out[3])
+end
+
+# int32_t emdee_dd_pressure_tensor(emdee_dd *dd, double out[12]);    global sums, collective (verlet.jl pressure_tensor)
+function pressure_tensor(dd::DomainDecomposition, volume)
+    out = zeros(Float64, 12)
+    check(ccall((:emdee_dd_pressure_tensor, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), dd.handle, out))
+    W, K = tensor3(out[1:6]), tensor3(out[7:12])
+    return (virial=W, kinetic=K, pressure=(K + W) / volume)
 end
 
 # int32_t emdee_dd_counts(emdee_dd *dd, int32_t local, int64_t *n_global, int32_t *n_owned, int32_t *n_ghost);

@@ -4,6 +4,7 @@ export FORCES,
        VIRIALS,
        nonbonded_computation_tiles,
        compute_nonbonded!,
+       compute_virial_tensor!,
        naively_compute_nonbonded!
 
 const FORCES = 1 << 0          # src/nonbonded.jl:12-14
@@ -73,6 +74,21 @@ function compute_nonbonded!(forces, energies, virials, positions::HipArray{T,2},
                  Ptr{Cvoid}, Int32, Int32),
                 context().handle, forces.ptr, energies.ptr, virials.ptr, positions.ptr, Float64(L),
                 handle!(tiles, precision_of(T)), model, atoms.ptr, bitmask, precision_of(T)))
+    return nothing
+end
+
+# Per-atom virial tensors of the same pairs (O(N) list path): tensor is a 6xN device matrix, rows (xx, yy, zz, xy, xz, yz),
+# overwritten; the trace of a column is that atom's VIRIALS output.  Asynchronous.
+# int32_t emdee_compute_virial_tensor(emdee_ctx*, void *tensor, const void *positions, double L, emdee_nbr *nbr,
+#                                     emdee_lj_model model, const emdee_lj_atom *atoms, int32_t precision);
+function compute_virial_tensor!(tensor::HipArray{T,2}, positions::HipArray{T,2}, L, tiles::NeighborTiles,
+                                model::LennardJonesModel, atoms::HipArray{LJAtom,1}) where {T}
+    size(positions, 2) == tiles.N || throw(DimensionMismatch("tiles were built for N = $(tiles.N)"))
+    size(tensor) == (6, tiles.N) || throw(DimensionMismatch("tensor must be 6 x $(tiles.N)"))
+    check(ccall((:emdee_compute_virial_tensor, libemdee_hip), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, LennardJonesModel, Ptr{Cvoid}, Int32),
+                context().handle, tensor.ptr, positions.ptr, Float64(L), handle!(tiles, precision_of(T)), model, atoms.ptr,
+                precision_of(T)))
     return nothing
 end
 

@@ -1,6 +1,6 @@
 # verlet.jl -- velocity-Verlet on the device.  Build-defined: the reference has no integrator
 # (SURVEY.md 8a row a16).  API in EmDee's style: a constructor and `!` mutators.
-export VelocityVerlet, step!, energies, set_langevin!, set_langevin_ids!
+export VelocityVerlet, step!, energies, set_langevin!, set_langevin_ids!, virial_tensor!, pressure_tensor
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -59,6 +59,24 @@ function energies(md::VelocityVerlet)
     out = zeros(Float64, 3)
     check(ccall((:emdee_md_energies, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, out))
     return (potential=out[1], kinetic=out[2], virial=out[3])
+end
+
+# int32_t emdee_md_virial_tensor(emdee_md *md, void *tensor);   per-atom virial tensors, 6 x N, rows (xx, yy, zz, xy, xz, yz)
+function virial_tensor!(tensor::HipArray{T,2}, md::VelocityVerlet{T}) where {T}
+    size(tensor) == (6, md.N) || throw(DimensionMismatch("tensor must be 6 x $(md.N)"))
+    check(ccall((:emdee_md_virial_tensor, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), md.handle, tensor.ptr))
+    return tensor
+end
+
+# the twelve sums (xx, yy, zz, xy, xz, yz of W, then of K) -> symmetric 3x3 matrices
+tensor3(s) = [s[1] s[4] s[5]; s[4] s[2] s[6]; s[5] s[6] s[3]]
+
+# int32_t emdee_md_pressure_tensor(emdee_md *md, double out[12]);   -> (virial = sum W_i, kinetic = sum m v v, pressure = (K + W) / V)
+function pressure_tensor(md::VelocityVerlet, volume)
+    out = zeros(Float64, 12)
+    check(ccall((:emdee_md_pressure_tensor, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, out))
+    W, K = tensor3(out[1:6]), tensor3(out[7:12])
+    return (virial=W, kinetic=K, pressure=(K + W) / volume)
 end
 
 # int32_t emdee_md_get_state(emdee_md*, void *positions, void *velocities, void *forces, void *energies, void *virials);

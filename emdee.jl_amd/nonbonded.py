@@ -197,6 +197,53 @@ def compute_nonbonded_(forces, energies, virials, positions, L, tiles, model, at
     return None
 
 
+def check_tensor_out(tensor, rows, dtype):
+    """A per-atom tensor output: (rows, 6), `dtype`, contiguous, on a GPU (shape and dtype are checked first)."""
+    if not isinstance(tensor, torch.Tensor):
+        raise TypeError("tensor must be a torch tensor")
+    if tuple(tensor.shape) != (rows, 6):
+        raise ValueError("tensor has shape %s, expected %s" % (tuple(tensor.shape), (rows, 6)))
+    if tensor.dtype != dtype:
+        raise TypeError("tensor has dtype %s, expected %s" % (tensor.dtype, dtype))
+    if not tensor.is_contiguous():
+        raise ValueError("tensor must be contiguous")
+    if not tensor.is_cuda:
+        raise TypeError("tensor must be a GPU tensor")
+    return tensor
+
+
+def compute_virial_tensor_(tensor, positions, L, tiles, model, atoms):
+    """Per-atom virial tensors W_i = 1/2 sum_j (-E'r / r^2) d (x) d of the pairs compute_nonbonded_ sums (O(N) list path,
+    CUTOFF semantics): tensor (N, 6) in the positions' dtype, columns (xx, yy, zz, xy, xz, yz), overwritten; its row sums
+    over xx, yy, zz are the VIRIALS output.  Enqueued on the current stream, not synchronised."""
+    if isinstance(tiles, AllPairsTiles):
+        raise ValueError("compute_virial_tensor_ takes the O(N) list handle (nonbonded_computation_tiles(N)); all-pairs tiles have no tensor")
+    if not isinstance(tiles, NeighborTiles):
+        raise TypeError("tiles must come from nonbonded_computation_tiles(N)")
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
+        raise ValueError("positions must be an (N, 3) tensor")
+    if positions.dtype not in (torch.float32, torch.float64):
+        raise TypeError("positions must be float32 or float64, got %s" % positions.dtype)
+    N = positions.shape[0]
+    if N != tiles.N:
+        raise ValueError("tiles were built for N = %d, positions hold %d atoms" % (tiles.N, N))
+    check_tensor_out(tensor, N, positions.dtype)
+    check_array(positions, "positions", N, 3, None, tensor.device)
+    check_array(atoms, "atoms", N, 2, torch.float32, tensor.device)
+    ctx = context_for(positions.device)
+    prec = precision_of(positions)
+    _lib.call("emdee_compute_virial_tensor", ctx.handle, _ptr(tensor), _ptr(positions), float(L), tiles._get(ctx, prec),
+              _lib.model_c(model), _ptr(atoms), prec)
+    return None
+
+
+def tensor_matrix(six):
+    """(xx, yy, zz, xy, xz, yz) -> the symmetric 3 x 3 numpy array"""
+    import numpy as np
+    xx, yy, zz, xy, xz, yz = (float(v) for v in six)
+    return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+
+
 def naively_compute_nonbonded_(forces, energies, virials, positions, L, model, atoms, mode=_lib.LITERAL):
     """naively_compute_nonbonded!(forces, energies, virials, positions, L, model, atoms)
     -- src/nonbonded.jl:122-155: the plain all-pairs double loop.  The reference runs it on the host;

@@ -6,7 +6,7 @@ import torch
 
 from . import _lib
 from .device import check_array, context_for, precision_of
-from .nonbonded import ENERGIES, FORCES, VIRIALS
+from .nonbonded import ENERGIES, FORCES, VIRIALS, check_tensor_out, tensor_matrix
 
 KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick": 3, "lj_force_nbr_fused_step": 4,
            # decomposed steps: the fused launches over interior bricks (or all bricks, in-order form), over boundary bricks, and the
@@ -129,6 +129,28 @@ class VelocityVerlet:
         return dict(potential=ep, kinetic=ek, virial=vir, temperature=2.0 * ek / max(3 * n - 3, 1),
                     pressure=(2.0 * ek + vir) / (3.0 * v), density=n / v)
 
+    def virial_tensor(self, out=None):
+        """Per-atom virial tensors of the owned atoms, (n_owned, 6) in caller order, columns (xx, yy, zz, xy, xz, yz)
+        (compute_virial_tensor_'s convention).  One extra pass over the list if they are not current; the forces and the
+        trajectory are left as they are."""
+        if out is None:
+            out = torch.empty((self.n_owned, 6), dtype=self.dtype, device=self.device)
+        check_tensor_out(out, self.n_owned, self.dtype)
+        _lib.call("emdee_md_virial_tensor", self._handle, C.c_void_p(out.data_ptr()))
+        return out
+
+    def tensor_sums(self):
+        """The twelve fp64 sums of emdee_md_pressure_tensor: sum of W_i (6), kinetic tensor sum m v v (6) (blocking)."""
+        out = (C.c_double * 12)()
+        _lib.call("emdee_md_pressure_tensor", self._handle, out)
+        return list(out)
+
+    def pressure_tensor(self, volume=None):
+        """dict(virial=W, kinetic=K, pressure=(K + W) / V) as 3 x 3 numpy arrays: W the sum of the per-atom virial tensors,
+        K = sum m v (x) v over owned atoms, so that trace(pressure) / 3 is observables()["pressure"]."""
+        v = self.lengths[0] * self.lengths[1] * self.lengths[2] if volume is None else volume
+        return pressure_tensor_dict(self.tensor_sums(), v)
+
     def nbr_stats(self):
         b, l, m, c = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
         _lib.call("emdee_md_nbr_stats", self._handle, C.byref(b), C.byref(l), C.byref(m), C.byref(c))
@@ -199,3 +221,9 @@ class VelocityVerlet:
             self.close()
         except Exception:
             pass
+
+
+def pressure_tensor_dict(sums, volume):
+    """twelve sums (W, K, each xx, yy, zz, xy, xz, yz) -> dict of 3 x 3 arrays virial, kinetic and pressure = (K + W) / V"""
+    w, k = tensor_matrix(sums[:6]), tensor_matrix(sums[6:12])
+    return dict(virial=w, kinetic=k, pressure=(k + w) / float(volume))

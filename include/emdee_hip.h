@@ -175,6 +175,13 @@ int32_t emdee_compute_nonbonded(emdee_ctx *ctx, void *forces_dev, void *energies
                                 const void *positions_dev, double L, emdee_nbr *nbr,
                                 emdee_lj_model model, const emdee_lj_atom *atoms_dev,
                                 int32_t bitmask, int32_t precision);
+/* Per-atom virial tensors of the same pairs, O(N) list path: W_i^ab = 1/2 sum_j (-E'r / r^2) d^a d^b with d = r_i - r_j the
+ * minimum image, so that its trace is the VIRIALS output w_i.  tensor_dev: 6 x N reals, caller order, the six components
+ * of an atom adjacent in the order (xx, yy, zz, xy, xz, yz); overwritten.  1-4 pairs add their scaled terms, excluded pairs
+ * none.  The handle's list is kept or rebuilt as by emdee_compute_nonbonded.  EMDEE_ERR_INVALID: NULL tensor_dev. */
+int32_t emdee_compute_virial_tensor(emdee_ctx *ctx, void *tensor_dev, const void *positions_dev, double L,
+                                    emdee_nbr *nbr, emdee_lj_model model, const emdee_lj_atom *atoms_dev,
+                                    int32_t precision);
 
 /* compute_tile! semantics (src/nonbonded.jl:44-107) for any N: all-pairs 64x64 tiles,
  * one wavefront per tile pair, lane rotation through DPP/bpermute instead of shfl_sync.
@@ -249,6 +256,15 @@ int32_t emdee_md_unpack_ghosts(emdee_md *md, const void *buf_dev, int32_t first,
 /* totals over owned atoms: out[0] = potential energy (sum of per-atom halves), out[1] =
  * kinetic energy, out[2] = virial sum.  Evaluates energies/virials if needed. Blocking. */
 int32_t emdee_md_energies(emdee_md *md, double out[3]);
+/* per-atom virial tensors of the owned atoms (emdee_compute_virial_tensor's convention): tensor_dev 6 x n_owned reals, caller
+ * order.  Evaluates them if they are not current (one extra pass over the list; the forces are left as they are, so a query
+ * does not change the trajectory).  Ordered against the caller's stream.  EMDEE_ERR_STATE before emdee_md_set_state,
+ * EMDEE_ERR_INVALID for a NULL tensor_dev. */
+int32_t emdee_md_virial_tensor(emdee_md *md, void *tensor_dev);
+/* box totals over owned atoms, fp64, deterministic: out[0..5] = sum_i W_i, out[6..11] = kinetic tensor K^ab = sum_i m_i v^a v^b
+ * (the velocities emdee_md_energies takes: tr K = 2 x its kinetic energy), both (xx, yy, zz, xy, xz, yz).  The pressure
+ * tensor is (K + W) / V.  Evaluates the tensors if needed.  Blocking. */
+int32_t emdee_md_pressure_tensor(emdee_md *md, double out[12]);
 int32_t emdee_md_nbr_stats(emdee_md *md, int64_t *builds, int64_t *listed, int32_t *max_count,
                            int32_t *capacity);
 int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
@@ -315,6 +331,9 @@ int32_t emdee_dd_load(emdee_dd *dd);
 int32_t emdee_dd_step(emdee_dd *dd, int32_t nsteps, double dt, int32_t rebuild_every);
 /* global {potential, kinetic, virial} sums (collective, blocking) */
 int32_t emdee_dd_energies(emdee_dd *dd, double out[3]);
+/* global emdee_md_pressure_tensor sums over all domains and ranks (collective like emdee_dd_energies, blocking);
+ * EMDEE_ERR_STATE before emdee_dd_load */
+int32_t emdee_dd_pressure_tensor(emdee_dd *dd, double out[12]);
 /* atoms in the whole box / owned and ghost atoms of a local domain */
 int32_t emdee_dd_counts(emdee_dd *dd, int32_t local, int64_t *n_global, int32_t *n_owned, int32_t *n_ghost);
 /* owned atoms of a local domain: global ids and positions (wrapped into the global box at the last rebuild),
