@@ -1388,7 +1388,7 @@ __global__ __launch_bounds__(THREADS) void k_brick_export(BrickArgs<real> a, int
 // named pairs to leave out.  One thread per own atom that has exclusions: its entries are decoded as k_brick_export does
 // (tile slot -> cell-order slot -> caller id), looked up in the atom's sorted exclusion list, and the row is compacted in
 // place, the vacated tail refilled with the sentinel.  Untyped rows only (a box with exclusions keeps the general kernels).
-// keys: caller ids or, in a decomposed engine, global ids (tags) -- and the 1-4 partners' slots (kernels.hpp PairKeys).
+// The loop is kernels.hpp strike_row (keys, the 1-4 partners' slots: PairKeys); this kernel decodes the entries and refills.
 template <typename real, class Shape, int THREADS, int G>
 __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, const int *__restrict__ ex_start,
                                                           const int *__restrict__ ex_idx, PairKeys keys) {
@@ -1397,37 +1397,24 @@ __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, con
     T.carve(s_dyn);
     int bxi, byi, bzi, tile_n, n_own;
     if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
+    auto slot = [&](unsigned short ent) {                // tile slot -> cell-order slot
+        const int sl = (int)ent >> a.idx_shift;
+        int lo = 0, hi = Shape::NTC;                      // tile cell with off[tc] <= sl < off[tc + 1]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (T.off[mid] <= sl) lo = mid; else hi = mid;
+        }
+        return T.gbeg[lo] + (sl - T.off[lo]);
+    };
     for (int o = threadIdx.x; o < n_own; o += THREADS) {
         int ti, p;
         brick_locate(T, o, ti, p);
         if (a.perm[p] >= a.n_owned) continue;
-        const long long gi = pair_key(keys, a.perm, p);
-        if (gi < 0 || gi >= keys.n_tab) continue;
-        const int lo_x = ex_start[gi], hi_x = ex_start[gi + 1];
-        if (lo_x == hi_x) continue;
-        const int lo14 = keys.s14 ? keys.start14[gi] : 0, hi14 = keys.s14 ? keys.start14[gi + 1] : 0;
-        for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
         const int m = min(a.cnt[p], a.stride);
         unsigned short *row = a.nbr + (size_t)p * a.stride;
-        int w = 0;
-        for (int e = 0; e < m; e++) {
-            const unsigned short ent = row[row_position<G>((unsigned)e)];
-            const int sl = (int)ent >> a.idx_shift;
-            int lo = 0, hi = Shape::NTC;                  // tile cell with off[tc] <= sl < off[tc + 1]
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (T.off[mid] <= sl) lo = mid; else hi = mid;
-            }
-            const int q = T.gbeg[lo] + (sl - T.off[lo]);
-            const long long gj = pair_key(keys, a.perm, q);
-            if (!csr_holds(ex_idx, lo_x, hi_x, (int)min(gj, (long long)keys.n_tab))) {
-                if (w != e) row[row_position<G>((unsigned)w)] = ent;
-                w++;
-            } else if (lo14 < hi14) {
-                const int k = csr_find(keys.idx14, lo14, hi14, gj);
-                if (k >= 0) keys.s14[k] = q;
-            }
-        }
+        const int w = strike_row(keys, a.perm, ex_start, ex_idx, p, m,
+                                 [&](int e) -> unsigned short & { return row[row_position<G>((unsigned)e)]; }, slot);
+        if (w < 0) continue;
         for (int e = w; e < m; e++) row[row_position<G>((unsigned)e)] = 0;   // the sentinel slot
         a.cnt[p] = w;
     }

@@ -354,6 +354,7 @@ struct DdImpl : IDd {
             EMDEE_HIP_CHECK(hipEventCreateWithFlags(&d->ev_bnd, hipEventDisableTiming));
             const int32_t per[3] = {d->geo.periodic[0], d->geo.periodic[1], d->geo.periodic[2]};
             d->md = std::make_unique<MdImpl<real>>(d->ctx, d->geo.local_lo, d->geo.local_len, per, model, skin);
+            d->md->sys.tables = &tables;
             d->md->sys.lgv_by_tag = true;                  // the thermostat's noise is keyed by the global ids that travel with the atoms
             d->md->lent = true;                            // (its pair tables are the decomposition's: emdee_dd_set_*)
             if (d->owns_ctx) d->md->caller_ctx = c;        // queries of this engine order their results on the caller's stream
@@ -1230,83 +1231,18 @@ struct DdImpl : IDd {
     }
 
     // ---------------------------------------------------------------- exclusions and 1-4 pairs (emdee_dd_set_exclusions / _set_pairs14)
-    // The topology does not change during a run: one symmetric, sorted, duplicate-free CSR per table over GLOBAL ids, built on the
-    // host at every call and uploaded once per process; every local engine points at it and keys its rows by the tags that travel
-    // with the atoms (NbSystem::use_gid_tables).  Replicating the tables is simpler than carrying each atom's partners through
-    // migration: 4 (max gid + 2) + 4 (directed pairs) bytes per table and process.
-    DevBuf<int> tx_start, tx_idx, t14_start, t14_idx;        // struck from the rows (exclusions and 1-4 pairs together) | the 1-4 pairs
-    std::vector<int32_t> tab_excl, tab_14;                   // the pairs of the tables in use, as given: {g, h, g, h, ...}
-    double tab_scale = 1.0;
-    bool has_tables() const { return !tab_excl.empty() || !tab_14.empty(); }
-    // pairs of the lists a and b -> rows 0 .. rows - 1: start[rows + 1], partners ascending, no duplicates
-    static void gid_csr(const std::vector<int32_t> &a, const std::vector<int32_t> &b, int rows, std::vector<int32_t> &st,
-                        std::vector<int32_t> &ix) {
-        st.assign((size_t)rows + 1, 0);
-        for (const std::vector<int32_t> *h : {&a, &b})
-            for (size_t k = 0; k < h->size(); k++) st[(size_t)(*h)[k] + 1]++;
-        for (int r = 0; r < rows; r++) st[(size_t)r + 1] += st[r];
-        ix.assign(st[rows], 0);
-        std::vector<int32_t> at(st.begin(), st.end() - 1);
-        for (const std::vector<int32_t> *h : {&a, &b})
-            for (size_t k = 0; k + 1 < h->size(); k += 2) {
-                const int32_t g = (*h)[k], q = (*h)[k + 1];
-                ix[at[g]++] = q;
-                ix[at[q]++] = g;
-            }
-        size_t w = 0;
-        for (int r = 0; r < rows; r++) {
-            const size_t lo = st[r], hi = st[(size_t)r + 1];
-            std::sort(ix.begin() + lo, ix.begin() + hi);
-            st[r] = (int32_t)w;
-            for (size_t k = lo; k < hi; k++)
-                if (k == lo || ix[k] != ix[k - 1]) ix[w++] = ix[k];
-        }
-        st[rows] = (int32_t)w;
-        ix.resize(w);
-    }
-    static void upload(DevBuf<int> &b, const std::vector<int32_t> &h, hipStream_t s) {
-        b.ensure(h.size() + 1);
-        if (!h.empty()) EMDEE_HIP_CHECK(hipMemcpyAsync(b.ptr, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
+    // One copy of the tables per process, over GLOBAL ids (nbsys.hpp PairTables): every local engine points at it and keys its
+    // rows by the tags that travel with the atoms.
+    PairTables tables;
+    bool has_tables() const { return tables.has_excl; }
     // Collective.  one_four: the 1-4 table (scaled by lj14scale), else the exclusions; n = 0 clears it.  All or nothing: an invalid
     // pair throws before anything changes.  After a load the engines are loaded again from their own states (same atoms, same
     // owners, same ghosts: nothing travels), so the rows, the 1-4 slots and the forces follow the new tables on return.
     void set_pair_table(const int64_t *pairs, int64_t n, bool one_four, double scale) override {
         use_device(user_ctx);
-        const char *what = one_four ? "emdee_dd_set_pairs14" : "emdee_dd_set_exclusions";
-        EMDEE_REQUIRE(n >= 0 && (n == 0 || pairs), EMDEE_ERR_INVALID, "%s: negative count or NULL array", what);
-        EMDEE_REQUIRE(!one_four || std::isfinite(scale), EMDEE_ERR_INVALID, "%s: lj14scale must be finite", what);
-        hipStream_t s = user_ctx->stream;
-        std::vector<int64_t> raw((size_t)2 * n);
-        if (n > 0) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(raw.data(), pairs, raw.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        }
-        std::vector<int32_t> h(raw.size());
-        for (int64_t k = 0; k < n; k++) {
-            const int64_t g = raw[2 * k], q = raw[2 * k + 1];
-            EMDEE_REQUIRE(g != q && g >= 0 && q >= 0 && g < ((int64_t)1 << 31) && q < ((int64_t)1 << 31), EMDEE_ERR_INVALID,
-                          "%s: pair %lld = (%lld, %lld) is not a pair of two different global ids in [0, 2^31)", what, (long long)k,
-                          (long long)g, (long long)q);
-            h[2 * k] = (int32_t)g; h[2 * k + 1] = (int32_t)q;
-        }
-        const std::vector<int32_t> &ex = one_four ? tab_excl : h, &p14 = one_four ? h : tab_14;
-        int rows = 0;
-        for (const std::vector<int32_t> *t : {&ex, &p14})
-            for (int32_t g : *t) rows = std::max(rows, g + 1);
-        std::vector<int32_t> xs, xi, ps, pi;
-        gid_csr(ex, p14, rows, xs, xi);
-        gid_csr(p14, std::vector<int32_t>{}, rows, ps, pi);
-        DevBuf<int> nxs, nxi, nps, npi;
-        upload(nxs, xs, s); upload(nxi, xi, s); upload(nps, ps, s); upload(npi, pi, s);
-        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        // ---- commit: nothing in flight reads the old tables any more
-        join_halo();
+        join_halo();                                         // nothing in flight reads the old tables any more
         for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
-        tx_start.swap(nxs); tx_idx.swap(nxi); t14_start.swap(nps); t14_idx.swap(npi);
-        if (one_four) { tab_14 = h; tab_scale = scale; } else { tab_excl = h; }
-        for (auto &pd : dom)
-            pd->sys().use_gid_tables(tx_start.ptr, tx_idx.ptr, !xi.empty(), t14_start.ptr, t14_idx.ptr, pi.size(), tab_scale, rows);
+        tables.set(pairs, n, one_four, scale, (int64_t)1 << 31, user_ctx->stream);
         if (!loaded) return;
         for (auto &pd : dom) {
             Domain<real> &d = *pd;
@@ -1347,7 +1283,7 @@ struct DdImpl : IDd {
         for (auto &pd : dom) hipLaunchKernelGGL(k_dd_batch_begin, dim3(1), dim3(64), 0, pd->stream(), pd->words.ptr, DD_WORDS, carry);
         with_halo(0, 0, [&](Domain<real> &d, int phase) {
             // (a domain with 1-4 pairs adds them behind a whole force pass: all bricks behind the halo, as its steps do)
-            if (d.sys().has_14) { if (phase == 1) return; phase = 0; }
+            if (d.sys().has_14()) { if (phase == 1) return; phase = 0; }
             d.md->forces(bitmask, phase);
         });
         join_halo();
@@ -1429,10 +1365,10 @@ struct DdImpl : IDd {
             for (int j = 0; j < B; j++) {
                 if (lgv_on) join_halo();   // (the boundary half of the previous step still reads the previous noise)
                 for (auto &pd : dom)
-                    if (pd->sys().brick_active && !pd->sys().has_14) pd->sys().prepare_noise(dt);   // (thermostat only) before the pack: both halves read it
+                    if (pd->sys().brick_active && !pd->sys().has_14()) pd->sys().prepare_noise(dt);   // (thermostat only) before the pack: both halves read it
                 with_halo(j, j, [&](Domain<real> &d, int phase) {
                     if (d.sys().n_total == 0) return;                     // nothing to move; its words stay clear
-                    if (d.sys().brick_active && !d.sys().has_14) {
+                    if (d.sys().brick_active && !d.sys().has_14()) {
                         // interior bricks look at my own request only (their neighbours are all mine); boundary bricks
                         // at the OR of everybody's
                         const int *guard = (phase == 1) ? d.V(j) : d.G(j);
@@ -1456,7 +1392,7 @@ struct DdImpl : IDd {
             }
             for (auto &pd : dom) {
                 Domain<real> &d = *pd;
-                const bool tiled = d.sys().brick_active && !d.sys().has_14 && d.sys().n_total > 0;
+                const bool tiled = d.sys().brick_active && !d.sys().has_14() && d.sys().n_total > 0;
                 if (tiled && ((B - ran) & 1)) d.sys().swap_step_buffers();   // the cancelled launches did not advance the ping-pong
                 if (d.sys().lgv_on && d.sys().n_total > 0) d.sys().lgv_step -= (unsigned long long)(B - ran);
                 if (tiled && d.sys().profiling) {

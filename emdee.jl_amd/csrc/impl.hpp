@@ -166,7 +166,7 @@ struct NbrImpl : INbr {
     }
     void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) override {
         use_device(sys.ctx);
-        sys.set_pair_tables(N, one_four ? nullptr : pairs, one_four ? 0 : n_pairs, !one_four, one_four ? pairs : nullptr, one_four ? n_pairs : 0, one_four, lj14scale);
+        sys.set_pair_tables(N, pairs, n_pairs, one_four, lj14scale);
     }
 };
 
@@ -394,7 +394,7 @@ struct MdImpl : IMd {
         use_device(sys.ctx);
         EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "exclusions / 1-4 pairs of a decomposed run: emdee_dd_set_exclusions / emdee_dd_set_pairs14 (this integrator is a domain's, lent by emdee_dd_engine)");
         EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "exclusions / 1-4 pairs: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
-        sys.set_pair_tables(sys.n_owned, one_four ? nullptr : pairs, one_four ? 0 : n_pairs, !one_four, one_four ? pairs : nullptr, one_four ? n_pairs : 0, one_four, lj14scale);
+        sys.set_pair_tables(sys.n_owned, pairs, n_pairs, one_four, lj14scale);
         sys.resort();                                        // the list without the named pairs (a two-species box leaves the typed kernels)
         since_build = 0;
         sys.compute_forces(EMDEE_FORCES);

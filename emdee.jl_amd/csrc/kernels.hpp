@@ -1123,7 +1123,7 @@ static __global__ void k_export_rows(int n, int n_owned, const int *__restrict__
 // (the hooks of src/modelling.jl:197-200.  The reference parses lj14scale and nothing consumes it --
 // its hot path sums every pair, src/nonbonded.jl:129-150 -- so these are build-defined: pairs named by the caller are struck
 // from the neighbour rows right after every build (the pair loop gets no mask), and the 1-4 pairs among them are
-// evaluated on their own, scaled.)  Both tables are symmetric CSR lists over caller ids, partners ascending.
+// evaluated on their own, scaled.)  Both tables are symmetric CSR lists over ids (PairKeys), partners ascending.
 __device__ __forceinline__ bool csr_holds(const int *__restrict__ idx, int lo, int hi, int j) {
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -1144,11 +1144,11 @@ __device__ __forceinline__ int csr_find(const int *__restrict__ idx, int lo, int
     return -1;
 }
 
-// Decomposed engines (dd.hpp) key the tables by GLOBAL id: the tag of the row's owner and of each entry, not the caller index
-// (perm).  tag == NULL: caller indices.  n_tab: ids 0 .. n_tab - 1 have rows (an id beyond names no pair).  With a 1-4 table
-// (s14 != NULL, tag mode) the filter also records, for every 1-4 partner of an owned atom, the cell-order slot of the entry it
-// strikes, in the table's order: s14[k] for idx14[k], -1 when the partner is not in the row (beyond the list radius at the
-// build, so beyond rc until the next one).  k_pairs14_slots sums those slots.
+// How a row filter and k_pairs14 name an atom: by its tag (the global id that travels with it) when the engine carries tags
+// -- a decomposed engine (dd.hpp), owned atoms and ghosts alike -- else by its caller index (perm).  n_tab: ids 0 .. n_tab - 1
+// have rows (an id beyond names no pair).  With a 1-4 table (s14 != NULL) the filter also records, for every 1-4 partner of an
+// owned atom, the cell-order slot of the entry it strikes, in the table's order: s14[k] for idx14[k], -1 when the partner is
+// not in the row (beyond the list radius at the build, so beyond rc until the next one).  k_pairs14 sums those slots.
 struct PairKeys {
     const long long *tag;
     int n_tab;
@@ -1159,6 +1159,35 @@ __device__ __forceinline__ long long pair_key(const PairKeys &k, const int *__re
     return k.tag ? k.tag[slot] : (long long)perm[slot];
 }
 
+// The loop both row filters share (k_filter_rows, brick.hpp k_brick_filter): owned atom p's row of m entries without its struck
+// entries (ex_start / ex_idx: exclusions and 1-4 pairs together), compacted in place, the 1-4 partners' slots recorded.
+// at(e): the row's e-th entry (a reference); slot(entry): its cell-order slot.  Returns the new length, or -1 if p has nothing
+// struck (its row is left as it is).
+template <class At, class Slot>
+__device__ __forceinline__ int strike_row(const PairKeys &keys, const int *__restrict__ perm, const int *__restrict__ ex_start,
+                                          const int *__restrict__ ex_idx, int p, int m, At at, Slot slot) {
+    const long long gi = pair_key(keys, perm, p);
+    if (gi < 0 || gi >= keys.n_tab) return -1;
+    const int lo = ex_start[gi], hi = ex_start[gi + 1];
+    if (lo == hi) return -1;
+    const int lo14 = keys.s14 ? keys.start14[gi] : 0, hi14 = keys.s14 ? keys.start14[gi + 1] : 0;
+    for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
+    int w = 0;
+    for (int e = 0; e < m; e++) {
+        const auto ent = at(e);
+        const int q = slot(ent);
+        const long long gj = pair_key(keys, perm, q);
+        if (!csr_holds(ex_idx, lo, hi, (int)min(gj, (long long)keys.n_tab))) {
+            if (w != e) at(w) = ent;
+            w++;
+        } else if (lo14 < hi14) {
+            const int k = csr_find(keys.idx14, lo14, hi14, gj);
+            if (k >= 0) keys.s14[k] = q;
+        }
+    }
+    return w;
+}
+
 // rows of the direct (int32, cell-order slot) list without their excluded entries
 static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__ perm, int *__restrict__ nbr, int stride,
                                      int *__restrict__ cnt, const int *__restrict__ ex_start, const int *__restrict__ ex_idx,
@@ -1166,50 +1195,38 @@ static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     if (perm[p] >= n_owned) return;
-    const long long gi = pair_key(keys, perm, p);
-    if (gi < 0 || gi >= keys.n_tab) return;
-    const int lo = ex_start[gi], hi = ex_start[gi + 1];
-    if (lo == hi) return;
-    const int lo14 = keys.s14 ? keys.start14[gi] : 0, hi14 = keys.s14 ? keys.start14[gi + 1] : 0;
-    for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
     int *row = nbr + (size_t)p * stride;
-    const int m = min(cnt[p], stride);
-    int w = 0;
-    for (int e = 0; e < m; e++) {
-        const int q = row[e];
-        const long long gj = pair_key(keys, perm, q);
-        if (!csr_holds(ex_idx, lo, hi, (int)min(gj, (long long)keys.n_tab))) {
-            row[w++] = q;
-        } else if (lo14 < hi14) {
-            const int k = csr_find(keys.idx14, lo14, hi14, gj);
-            if (k >= 0) keys.s14[k] = q;
-        }
-    }
-    cnt[p] = w;
+    const int w = strike_row(keys, perm, ex_start, ex_idx, p, min(cnt[p], stride), [&](int e) -> int & { return row[e]; },
+                             [](int q) { return q; });
+    if (w >= 0) cnt[p] = w;
 }
 
-// 1-4 pairs: owner-computes over the symmetric table (no atomics, a fixed order of summation); the scaled pair terms are
-// ADDED to what the list kernels have left -- in the cell-ordered arrays, or in the caller's arrays when the operator
-// path had its results written there (user_*: caller order).
+// 1-4 pairs: owner-computes over the slots the row filter recorded at the last build (k_filter_rows / k_brick_filter) -- no
+// atomics, the table's order of summation, half of a pair's E and W to the owner.  The partner may be an owned atom or a ghost
+// image (the records hold its shifted coordinates).  The scaled pair terms are ADDED to what the list kernels have left -- in
+// the cell-ordered arrays, or in the caller's arrays when the operator path had its results written there (user_*: caller
+// order).  A pair missing from the rows is beyond rc + skin at the build, so beyond rc while the list is valid.
 // (TENSOR: the tensor pass's instance; the force and observable passes keep the instance without the six sums)
 template <typename real, bool TENSOR = false>
-__global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm,
-                          const int *__restrict__ inv_perm, GridP<real> g, LJModel<real> model, const int *__restrict__ start14,
-                          const int *__restrict__ idx14, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
+__global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
+                          GridP<real> g, LJModel<real> model, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
                           real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
                           real *__restrict__ vt = nullptr, real *__restrict__ user_vt = nullptr) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const int i = perm[p];
     if (i >= n_owned) return;
-    const int lo = start14[i], hi = start14[i + 1];
+    const long long gi = pair_key(keys, perm, p);
+    if (gi < 0 || gi >= keys.n_tab) return;
+    const int lo = keys.start14[gi], hi = keys.start14[gi + 1];
     if (lo == hi) return;
     real xi, yi, zi, hs_i, te_i;
     load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
     real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
     real tv[6] = {0, 0, 0, 0, 0, 0};                           // (tensor pass: the scaled terms of the tensor, as of w)
     for (int k = lo; k < hi; k++) {
-        const int q = inv_perm[idx14[k]];
+        const int q = keys.s14[k];
+        if (q < 0) continue;
         real xj, yj, zj, hs_j, te_j;
         load_atom(atoms, q, xj, yj, zj, hs_j, te_j);
         const real dx = min_image(xi - xj, g.plen[0], g.pinv[0]);
@@ -1246,59 +1263,6 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
         if (TENSOR)
             for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
     }
-}
-
-// 1-4 pairs of a decomposed engine: as k_pairs14 -- owner-computes, the table's order, half of E and W to the owner -- over the
-// slots the row filter recorded at the last build (k_filter_rows / k_brick_filter, tag mode) instead of a look-up by id: the
-// partner may be an owned atom or a ghost image (the records hold its shifted coordinates).  With global ids equal to caller
-// indices the order of summation is k_pairs14's.
-template <typename real, bool TENSOR = false>
-__global__ void k_pairs14_slots(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm,
-                                const long long *__restrict__ tag, int n_tab, GridP<real> g, LJModel<real> model,
-                                const int *__restrict__ start14, const int *__restrict__ s14, real scale, int bitmask,
-                                real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir, real *__restrict__ vt = nullptr) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    if (perm[p] >= n_owned) return;
-    const long long gi = tag[p];
-    if (gi < 0 || gi >= n_tab) return;
-    const int lo = start14[gi], hi = start14[gi + 1];
-    if (lo == hi) return;
-    real xi, yi, zi, hs_i, te_i;
-    load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
-    real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
-    real tv[6] = {0, 0, 0, 0, 0, 0};                           // (tensor pass: the scaled terms of the tensor, as of w)
-    for (int k = lo; k < hi; k++) {
-        const int q = s14[k];
-        if (q < 0) continue;
-        real xj, yj, zj, hs_j, te_j;
-        load_atom(atoms, q, xj, yj, zj, hs_j, te_j);
-        const real dx = min_image(xi - xj, g.plen[0], g.pinv[0]);
-        const real dy = min_image(yi - yj, g.plen[1], g.pinv[1]);
-        const real dz = min_image(zi - zj, g.plen[2], g.pinv[2]);
-        const real r2 = dx * dx + dy * dy + dz * dz;
-        if (r2 < model.rc2) {
-            const real inv_r2 = (real)1 / r2;
-            real E, W;
-            lj_interaction(r2, inv_r2, model, hs_i, te_i, hs_j, te_j, E, W);
-            const real wr2 = W * inv_r2;
-            fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
-            e += E; w += W;
-            if (TENSOR) {
-                const real hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
-                tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
-                tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
-            }
-        }
-    }
-    fx *= scale; fy *= scale; fz *= scale;
-    e *= (real)0.5 * scale; w *= (real)0.5 * scale;
-    for (int c = 0; c < 6; c++) tv[c] *= (real)0.5 * scale;
-    if (bitmask & EMDEE_FORCES) { frc[p] += fx; frc[pitch + p] += fy; frc[2 * pitch + p] += fz; }
-    if (bitmask & EMDEE_ENERGIES) en[p] += e;
-    if (bitmask & EMDEE_VIRIALS) vir[p] += w;
-    if (TENSOR)
-        for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
 }
 
 // ------------------------------------------------------------------------------------ reductions

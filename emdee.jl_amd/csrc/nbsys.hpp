@@ -98,6 +98,91 @@ static inline void allow_big_lds(K kernel, size_t bytes) {
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
+// Exclusions and scaled 1-4 pairs (kernels.hpp, "exclusions and 1-4 pairs"; the hooks of src/modelling.jl:197-200): pairs the
+// caller names are struck from the rows right after every build, and the 1-4 pairs among them come back scaled by lj14scale
+// after every force pass.  The topology does not change during a run: both tables are symmetric, sorted, duplicate-free CSRs
+// built on the host once per call.  An undivided engine owns one over caller ids (NbSystem::own_tables); a decomposition owns
+// one over global ids that all its engines point at (dd.hpp), which is simpler than carrying each atom's partners through
+// migration: 4 (max id + 2) + 4 (directed pairs) bytes per table.
+struct PairTables {
+    DevBuf<int> x_start, x_idx;                              // struck from the rows: the exclusions and the 1-4 pairs together
+    DevBuf<int> p_start, p_idx;                              // the 1-4 pairs
+    std::vector<int32_t> excl, p14;                          // the pairs as given: {i, j, i, j, ...}
+    double scale14 = 1.0;
+    int rows = 0;                                            // ids 0 .. rows - 1 have rows (max id + 1)
+    int64_t limit = 0;                                       // ids of the last call lay in [0, limit): the atom count, or 2^31 (global ids)
+    size_t n14 = 0;                                          // entries of the 1-4 CSR
+    bool has_excl = false, has_14 = false;
+
+    // pairs of the lists a and b -> rows 0 .. rows - 1: start[rows + 1], partners ascending, no duplicates
+    static void csr(const std::vector<int32_t> &a, const std::vector<int32_t> &b, int rows, std::vector<int32_t> &st,
+                    std::vector<int32_t> &ix) {
+        st.assign((size_t)rows + 1, 0);
+        for (const std::vector<int32_t> *h : {&a, &b})
+            for (size_t k = 0; k < h->size(); k++) st[(size_t)(*h)[k] + 1]++;
+        for (int r = 0; r < rows; r++) st[(size_t)r + 1] += st[r];
+        ix.assign(st[rows], 0);
+        std::vector<int32_t> at(st.begin(), st.end() - 1);
+        for (const std::vector<int32_t> *h : {&a, &b})
+            for (size_t k = 0; k + 1 < h->size(); k += 2) {
+                const int32_t g = (*h)[k], q = (*h)[k + 1];
+                ix[at[g]++] = q;
+                ix[at[q]++] = g;
+            }
+        size_t w = 0;
+        for (int r = 0; r < rows; r++) {
+            const size_t lo = st[r], hi = st[(size_t)r + 1];
+            std::sort(ix.begin() + lo, ix.begin() + hi);
+            st[r] = (int32_t)w;
+            for (size_t k = lo; k < hi; k++)
+                if (k == lo || ix[k] != ix[k - 1]) ix[w++] = ix[k];
+        }
+        st[rows] = (int32_t)w;
+        ix.resize(w);
+    }
+    static void upload(DevBuf<int> &b, const std::vector<int32_t> &h, hipStream_t s) {
+        b.ensure(h.size() + 1);
+        if (!h.empty()) EMDEE_HIP_CHECK(hipMemcpyAsync(b.ptr, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    // Replaces one table by the n pairs at pairs_dev (device, {i, j, ...}): one_four, the 1-4 pairs scaled by `scale`, else the
+    // exclusions; n = 0 clears it.  All or nothing: every pair given is checked against [0, lim) and both CSRs are uploaded
+    // into buffers of their own before anything changes, so an invalid call throws and leaves both tables in force.
+    // The caller makes sure nothing in flight reads the old tables.
+    template <typename T>
+    void set(const T *pairs_dev, int64_t n, bool one_four, double scale, int64_t lim, hipStream_t s) {
+        const char *what = one_four ? "set_pairs14" : "set_exclusions";
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || pairs_dev), EMDEE_ERR_INVALID, "%s: negative count or NULL array", what);
+        EMDEE_REQUIRE(!one_four || std::isfinite(scale), EMDEE_ERR_INVALID, "%s: lj14scale must be finite", what);
+        std::vector<T> raw((size_t)2 * n);
+        if (n > 0) {
+            EMDEE_HIP_CHECK(hipMemcpyAsync(raw.data(), pairs_dev, raw.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        }
+        for (int64_t k = 0; k < n; k++) {
+            const int64_t i = raw[2 * k], j = raw[2 * k + 1];
+            EMDEE_REQUIRE(i != j && i >= 0 && j >= 0 && i < lim && j < lim, EMDEE_ERR_INVALID,
+                          "%s: pair %lld = (%lld, %lld) is not a pair of two different ids in [0, %lld)", what, (long long)k,
+                          (long long)i, (long long)j, (long long)lim);
+        }
+        const std::vector<int32_t> h(raw.begin(), raw.end());
+        const std::vector<int32_t> &ex = one_four ? excl : h, &pp = one_four ? h : p14;
+        int r = 0;
+        for (const std::vector<int32_t> *t : {&ex, &pp})
+            for (int32_t g : *t) r = std::max(r, g + 1);
+        std::vector<int32_t> xs, xi, ps, pi;
+        csr(ex, pp, r, xs, xi);
+        csr(pp, std::vector<int32_t>{}, r, ps, pi);
+        DevBuf<int> nxs, nxi, nps, npi;
+        upload(nxs, xs, s); upload(nxi, xi, s); upload(nps, ps, s); upload(npi, pi, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        x_start.swap(nxs); x_idx.swap(nxi); p_start.swap(nps); p_idx.swap(npi);
+        if (one_four) { p14 = h; scale14 = scale; } else { excl = h; }
+        rows = r; limit = lim; n14 = pi.size();
+        has_excl = !xi.empty(); has_14 = !pi.empty();
+    }
+};
+
 template <typename real>
 struct NbSystem {
     emdee_ctx *ctx = nullptr;
@@ -762,7 +847,7 @@ struct NbSystem {
         // two species: the typed kernels (typed.hpp), if the tile fits their coordinate planes, no three cells of a tile row hold
         // more atoms of one species than the 16-bit hit fields of their build take, and both kernels fit LDS
         typed_active = false;
-        if (brick_active && nt == 2 && !typed_blocked && !has_excl) {
+        if (brick_active && nt == 2 && !typed_blocked && !has_excl()) {
             // (where the general-species kernels take 1024 threads with 8 lanes per atom -- long cutoffs -- the typed ones take
             // 1024 threads with 4: rows are two block-aligned segments, and blocks of 32 entries pad them half as much as blocks of 64)
             // Measured (profiles/README.md, round 3): at rc = 3.5 sigma 190.7 -> 218.0 steps/s in fp64 and 233.8 -> 324.2 in fp32; at
@@ -1001,116 +1086,57 @@ struct NbSystem {
         EMDEE_REQUIRE(false, EMDEE_ERR_OVERFLOW, "neighbour capacity kept overflowing");
     }
 
-    // ---------------------------------------------------------------- exclusions and 1-4 pairs (kernels.hpp)
-    // Pairs the caller names (caller ids; bonded neighbours of a molecular model) are struck from the rows right after every
-    // build; the 1-4 pairs among them come back scaled (lj14scale of the reference's force-field file, src/modelling.jl:198)
-    // through k_pairs14 after every force pass.  Symmetric CSR tables over caller ids, built on the host once per call
-    // (topology does not change during a run); decomposed engines take tables over global ids instead (use_gid_tables).
-    // Two-species boxes with exclusions keep the general-species kernels (a typed row is two block-aligned segments: compacting one would move the other).
-    DevBuf<int> ex_start, ex_idx, p14_start, p14_idx;
-    bool has_excl = false, has_14 = false;
-    double scale14 = 1.0;
-    int table_atoms = 0;
-    std::vector<int32_t> excl_host, p14_host;          // the caller's pairs as given: {i, j, i, j, ...}
-    std::vector<int32_t> fetch_pairs(const int32_t *pairs_dev, int n_pairs) {
-        std::vector<int32_t> h((size_t)2 * n_pairs);
-        if (n_pairs > 0) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(h.data(), pairs_dev, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream()));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
-        }
-        return h;
-    }
-    // pairs {i, j} of caller ids -> symmetric, sorted, duplicate-free CSR (start[n_atoms + 1], idx) on the device
-    void upload_csr(const std::vector<int32_t> &h, int n_atoms, DevBuf<int> &start_out, DevBuf<int> &idx_out) {
-        const size_t np = h.size() / 2;
-        std::vector<std::pair<int32_t, int32_t>> both;
-        both.reserve(2 * np);
-        for (size_t k = 0; k < np; k++) {
-            const int32_t i = h[2 * k], j = h[2 * k + 1];
-            EMDEE_REQUIRE(i >= 0 && j >= 0 && i < n_atoms && j < n_atoms && i != j, EMDEE_ERR_INVALID,
-                          "pair table: pair %zu = (%d, %d) is not a pair of two different atoms of %d", k, i, j, n_atoms);
-            both.emplace_back(i, j);
-            both.emplace_back(j, i);
-        }
-        std::sort(both.begin(), both.end());
-        both.erase(std::unique(both.begin(), both.end()), both.end());
-        std::vector<int32_t> st((size_t)n_atoms + 1, 0), ix(both.size());
-        for (size_t k = 0; k < both.size(); k++) { st[(size_t)both[k].first + 1]++; ix[k] = both[k].second; }
-        for (int a = 0; a < n_atoms; a++) st[(size_t)a + 1] += st[a];
-        start_out.ensure(st.size() + 1); idx_out.ensure(ix.size() + 1);
-        EMDEE_HIP_CHECK(hipMemcpyAsync(start_out.ptr, st.data(), st.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream()));
-        if (!ix.empty()) EMDEE_HIP_CHECK(hipMemcpyAsync(idx_out.ptr, ix.data(), ix.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream()));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
-    }
-    // set_excl / set_14: which of the two tables this call replaces (n = 0 clears it); scale: lj14scale
-    void set_pair_tables(int n_atoms, const int32_t *excl_dev, int n_excl, bool set_excl, const int32_t *p14_dev, int n_14, bool set_14, double scale) {
-        EMDEE_REQUIRE(n_atoms >= 0 && n_excl >= 0 && n_14 >= 0, EMDEE_ERR_INVALID, "pair table: negative count");
-        EMDEE_REQUIRE((n_excl == 0 || excl_dev) && (n_14 == 0 || p14_dev), EMDEE_ERR_INVALID, "pair table: NULL array");
-        EMDEE_REQUIRE(!set_14 || std::isfinite(scale), EMDEE_ERR_INVALID, "pair table: lj14scale must be finite");
-        if (set_excl) excl_host = fetch_pairs(excl_dev, n_excl);
-        if (set_14) { p14_host = fetch_pairs(p14_dev, n_14); scale14 = scale; }
-        upload_csr(p14_host, n_atoms, p14_start, p14_idx);
-        has_14 = !p14_host.empty();
-        std::vector<int32_t> all = excl_host;                // what is struck from the rows: the exclusions and the 1-4 pairs together
-        all.insert(all.end(), p14_host.begin(), p14_host.end());
-        upload_csr(all, n_atoms, ex_start, ex_idx);
-        has_excl = !all.empty();
-        table_atoms = n_atoms;
+    // ---------------------------------------------------------------- exclusions and 1-4 pairs (PairTables)
+    // Every engine keys the rows of its tables the same way (kernels.hpp PairKeys): by tag when it carries tags (a decomposed
+    // engine), else by caller id.  The row filter records where each 1-4 partner sits in the rows (slots14) and k_pairs14 sums
+    // those slots after every force pass: no look-up by id during steps, and a pair beyond rc + skin at the build is beyond rc
+    // while the list is valid.  Two-species boxes with tables keep the general-species kernels (a typed row is two
+    // block-aligned segments: compacting one would move the other).
+    PairTables own_tables;                                   // an undivided engine's, over caller ids
+    PairTables *tables = &own_tables;                        // a decomposed engine's point at the decomposition's, over global ids
+    DevBuf<int> slots14;                                     // per 1-4 entry of an owned atom's row: the partner's cell-order slot
+    bool has_excl() const { return tables->has_excl; }
+    bool has_14() const { return tables->has_14; }
+    // emdee_nbr_* / emdee_md_set_exclusions, _set_pairs14: replaces one of the engine's own tables (n = 0 clears it), all or nothing
+    void set_pair_tables(int n_atoms, const int32_t *pairs_dev, int n_pairs, bool one_four, double scale) {
+        own_tables.set(pairs_dev, n_pairs, one_four, scale, n_atoms, stream());
         has_list = false; plan_valid = false;                // (the rows in use were filtered with the old tables; typed rows are not filtered)
     }
-    // Decomposed engines (dd.hpp DdImpl::set_pair_table): tables over GLOBAL ids, one copy per process shared by its engines; the
-    // rows are keyed by the tags that travel with the atoms, owned atoms and ghosts alike, and the 1-4 partners are found by the
-    // row filter (slots14) instead of by id at every step.
-    bool tab_by_tag = false;
-    const int *gx_start = nullptr, *gx_idx = nullptr, *g14_start = nullptr, *g14_idx = nullptr;
-    int gtab_rows = 0;                                       // global ids 0 .. gtab_rows - 1 have rows
-    DevBuf<int> slots14;                                     // per 1-4 entry of an owned atom's row of g14: the partner's cell-order slot
-    void use_gid_tables(const int *xs, const int *xi, bool excl, const int *ps, const int *pi, size_t n14, double scale, int rows) {
-        if (n14 > 0) slots14.ensure(n14 + 1);
-        tab_by_tag = true;
-        gx_start = xs; gx_idx = xi; g14_start = ps; g14_idx = pi;
-        gtab_rows = rows;
-        has_excl = excl; has_14 = n14 > 0; scale14 = scale;
-    }
     PairKeys pair_keys() const {
-        if (!tab_by_tag) return PairKeys{nullptr, table_atoms, nullptr, nullptr, nullptr};
-        return PairKeys{tag.ptr, gtab_rows, g14_start, g14_idx, has_14 ? slots14.ptr : nullptr};
+        return PairKeys{use_tags ? tag.ptr : nullptr, tables->rows, tables->p_start.ptr, tables->p_idx.ptr, has_14() ? slots14.ptr : nullptr};
     }
-    // right after a build: the rows without their excluded entries
+    void check_tables(const char *what) const {
+        if (tables != &own_tables) EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "%s over global ids: the state carries no tags", what);
+        else EMDEE_REQUIRE(tables->limit == n_owned && !id_gaps, EMDEE_ERR_STATE, "%s set for %lld atoms, the state holds %d", what,
+                           (long long)tables->limit, n_owned);
+    }
+    // right after a build: the rows without their excluded entries, and the 1-4 partners' slots
     void apply_exclusions() {
-        if (!has_excl || n_total == 0) return;
-        if (tab_by_tag) EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "exclusion tables over global ids: the state carries no tags");
-        else EMDEE_REQUIRE(table_atoms == n_owned && !id_gaps, EMDEE_ERR_STATE, "exclusion tables were set for %d atoms, the state holds %d", table_atoms, n_owned);
-        const int *xs = tab_by_tag ? gx_start : ex_start.ptr, *xi = tab_by_tag ? gx_idx : ex_idx.ptr;
+        if (!has_excl() || n_total == 0) return;
+        check_tables("exclusion tables");
+        if (has_14()) slots14.ensure(tables->n14 + 1);
         if (brick_active) {
             EMDEE_REQUIRE(!typed_active, EMDEE_ERR_STATE, "exclusions: typed rows are not filtered");
             with_brick_variant(variant, [&](auto v) {
                 using V = decltype(v);
                 auto kernel = k_brick_filter<real, typename V::Shape, V::THREADS, V::G>;
                 using BT = BrickTables<typename V::Shape, V::THREADS>;
-                hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(), xs, xi, pair_keys());
+                hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(),
+                                   tables->x_start.ptr, tables->x_idx.ptr, pair_keys());
             });
         } else {
             hipLaunchKernelGGL(k_filter_rows, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, perm.ptr, nbr.ptr, stride,
-                               cnt.ptr, xs, xi, pair_keys());
+                               cnt.ptr, tables->x_start.ptr, tables->x_idx.ptr, pair_keys());
         }
     }
     // after a force pass: the scaled 1-4 terms on top
     void add_pairs14(int bitmask) {
-        if (!has_14 || n_total == 0) return;
-        if (tab_by_tag) {
-            EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "1-4 table over global ids: the state carries no tags");
-            auto kernel = (bitmask & EMDEE_TENSOR) ? k_pairs14_slots<real, true> : k_pairs14_slots<real, false>;
-            hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(),
-                               perm.ptr, tag.ptr, gtab_rows, grid, model, g14_start, slots14.ptr, (real)scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
-                               vt.ptr);
-            return;
-        }
-        EMDEE_REQUIRE(table_atoms == n_owned && !id_gaps, EMDEE_ERR_STATE, "1-4 table was set for %d atoms, the state holds %d", table_atoms, n_owned);
+        if (!has_14() || n_total == 0) return;
+        check_tables("1-4 table");
         const bool user = brick_active && (out_f || out_e || out_w || out_vt);
         auto kernel = (bitmask & EMDEE_TENSOR) ? k_pairs14<real, true> : k_pairs14<real, false>;
         hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
-                           inv_perm.ptr, grid, model, p14_start.ptr, p14_idx.ptr, (real)scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
+                           pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
                            user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
                            user ? out_vt : (real *)nullptr);
     }
@@ -1233,7 +1259,7 @@ struct NbSystem {
                     bool carry_ghosts = true, bool noise_ready = false) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         if (!brick_active || n_total == 0) return false;
-        if (has_14) return false;                            // (the scaled 1-4 terms are added behind a force pass: the split kernels)
+        if (has_14()) return false;                            // (the scaled 1-4 terms are added behind a force pass: the split kernels)
         if (phase != 2 && !noise_ready) prepare_noise(dt);   // phases 1 and 2 are the two halves of one step
         {
             Timed t(this, phase == 2 ? T_STEP_BOUNDARY : T_STEP);
@@ -1266,7 +1292,7 @@ struct NbSystem {
     int fused_steps_run_ahead(double c, double dt, int want, bool *stale) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         *stale = false;
-        if (!brick_active || n_total == 0 || has_ghosts || has_14) return 0;
+        if (!brick_active || n_total == 0 || has_ghosts || has_14()) return 0;
         const int B = std::max(1, std::min(want, run_ahead));
         int *words = flags.ptr + 9;                          // flags[9 .. 9 + RUN_AHEAD)
         EMDEE_HIP_CHECK(hipMemsetAsync(words, 0, B * sizeof(int), stream()));
@@ -1348,7 +1374,7 @@ struct NbSystem {
     // at unmoved positions -- the rebuild the raised word brings evaluates them afresh.
     void guarded_split_step(double c, double dt, const int *guard, int *trigger) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
-        EMDEE_REQUIRE(!brick_active || has_14, EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
+        EMDEE_REQUIRE(!brick_active || has_14(), EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
         if (n_total == 0) return;
         direct_guard = guard;
         compute_forces(EMDEE_FORCES, 0);

@@ -159,9 +159,14 @@ int32_t emdee_md_nbr_list(emdee_md *md, int32_t *counts_dev, int32_t *neighbors_
  * (forces, energy and virial halves).  Both are struck from the neighbour rows right after every list build -- the pair loop
  * carries no mask -- and the 1-4 pairs are evaluated by a kernel of their own behind every force pass (an integrator with
  * 1-4 pairs steps with the split kernels: force pass, 1-4 terms, kick + drift).  Each call replaces its table; n_pairs = 0
- * clears it.  Undivided boxes (emdee_nbr, emdee_md without ghosts); emdee_md: after emdee_md_set_state.  Two-species boxes with
+ * clears it.  All or nothing: each pair needs i != j and 0 <= i, j < N, else EMDEE_ERR_INVALID and both previous tables stay in
+ * force.  Undivided boxes (emdee_nbr, emdee_md without ghosts); emdee_md: after emdee_md_set_state.  Two-species boxes with
  * exclusions keep the general-species kernels.  Decomposed runs: emdee_dd_set_exclusions / emdee_dd_set_pairs14 (tables over
- * global ids); an integrator lent by emdee_dd_engine refuses these calls with EMDEE_ERR_STATE. */
+ * global ids); an integrator lent by emdee_dd_engine refuses these calls with EMDEE_ERR_STATE.
+ * A 1-4 partner is found through the neighbour rows (the list build records where it sits), in undivided and decomposed runs
+ * alike.  That is the same as a look-up by index whenever the list is valid -- automatic rebuilds (rebuild_every = 0) and the
+ * emdee_nbr calls: a pair beyond rc + skin at a build cannot come within rc before the next one.  With a fixed rebuild_every > 0
+ * that lets atoms outrun the skin, a 1-4 pair is treated like any listed pair: the list's own contract. */
 int32_t emdee_nbr_set_exclusions(emdee_nbr *nbr, const int32_t *pairs_dev, int32_t n_pairs);
 int32_t emdee_nbr_set_pairs14(emdee_nbr *nbr, const int32_t *pairs_dev, int32_t n_pairs, double lj14scale);
 int32_t emdee_md_set_exclusions(emdee_md *md, const int32_t *pairs_dev, int32_t n_pairs);

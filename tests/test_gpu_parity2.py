@@ -6,6 +6,7 @@
     the reference's own force-field fixture (src/modelling.jl:71-73,197-200) -> compute_nonbonded_ vs the oracle;
   * the fp32 configuration (BASELINE configs[3]) at the size it is quoted on: 10^7 atoms, conserved quantities.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -623,6 +624,84 @@ def test_exclusions_and_scaled_14_pairs(emdee, oracle, dev, lj_sample, monkeypat
     half.step_(40, 0.002)
     eph, ekh, _ = half.totals()
     assert abs((eph + ekh) - (ep0 + ek0)) > 2.5 * abs((ep1 + ek1) - (ep0 + ek0))          # ... and it shrinks with dt^2
+
+
+@pytest.mark.parametrize("path", ["tiled", "direct"])
+def test_invalid_pair_tables_leave_the_previous_ones_in_force(emdee, dev, lj_sample, monkeypatch, path):
+    """The undivided counterpart of test_gpu_dd_pairs.py::test_refusals: every emdee_md_set_* / emdee_nbr_set_* is all or
+    nothing.  A pair of one atom, a negative index or an index equal to N in either table returns EMDEE_ERR_INVALID, and the
+    engine then steps / computes bit for bit like a twin that never saw the bad calls; a call that clears only one table
+    afterwards succeeds (the bad pairs were not kept)."""
+    E = emdee
+    if path == "direct":
+        monkeypatch.setenv("EMDEE_PATH", "direct")
+    x = lj_sample.astype(np.float64)
+    N, L, rc, rs = x.shape[0], 10.0, 3.0, 2.5
+    atoms = E.lennard_jones_atoms(np.array([1.0, 0.8, 1.1, 0.9])[np.arange(N) % 4], np.array([1.0, 0.9, 1.05, 0.95])[np.arange(N) % 4])
+    mol = np.arange(N).reshape(-1, 4)
+    excl = np.concatenate([mol[:, [0, 1]], mol[:, [1, 2]], mol[:, [2, 3]], mol[:, [0, 2]], mol[:, [1, 3]]])
+    p14, s14 = mol[:, [0, 3]], 0.5
+    bads = ([[3, 3]], [[-1, 5]], [[0, N]])
+    ERR_INVALID = -1
+
+    def dev_pairs(p):
+        return torch.as_tensor(np.asarray(p)).to(device=dev, dtype=torch.int32).contiguous()
+
+    # emdee_md
+    v0 = 0.3 * E.synthetic.velocities(N)
+    a, b = (E.VelocityVerlet(E.cu(x, dev), E.cu(v0, dev), L, E.LennardJonesModel(rc, rs), E.cu(atoms, dev), skin=0.3) for _ in range(2))
+    for md in (a, b):
+        md.set_exclusions_(excl)
+        md.set_pairs14_(p14, s14)
+    for bad in bads:
+        with pytest.raises(E.EmDeeError) as err:
+            a.set_exclusions_(np.concatenate([excl[:7], np.array(bad)]))
+        assert err.value.code == ERR_INVALID
+        with pytest.raises(E.EmDeeError) as err:
+            a.set_pairs14_(np.array(bad), s14)
+        assert err.value.code == ERR_INVALID
+
+    def same(ma, mb):
+        sa, sb = ma.state(energies=True, virials=True), mb.state(energies=True, virials=True)
+        for k in sa:
+            assert torch.equal(sa[k], sb[k]), k
+
+    for md in (a, b):
+        md.step_(30, 0.001)
+    same(a, b)
+    for md in (a, b):
+        md.set_pairs14_(None, 1.0)                                   # clears the 1-4 table only
+        md.step_(10, 0.001)
+    same(a, b)
+    a.close(); b.close()
+
+    # emdee_nbr (the C calls on the handle: the Python wrapper re-sends both tables it holds at every call)
+    ta, tb = (E.nonbonded_computation_tiles(N, skin=0.3) for _ in range(2))
+    outs = []
+    for tiles in (ta, tb):
+        tiles.set_exclusions_(excl)
+        tiles.set_pairs14_(p14, s14)
+        out = tuple(torch.zeros(s, dtype=torch.float64, device=dev) for s in ((N, 3), (N,), (N,)))
+        E.compute_nonbonded_(*out, E.cu(x, dev), L, tiles, E.LennardJonesModel(rc, rs), E.cu(atoms, dev), E.Val(7))
+        outs.append(out)
+    h = ta._handle
+    for bad in bads:
+        for name, t, extra in (("emdee_nbr_set_exclusions", dev_pairs(np.concatenate([excl[:7], bad])), ()),
+                               ("emdee_nbr_set_pairs14", dev_pairs(bad), (s14,))):
+            with pytest.raises(E.EmDeeError) as err:
+                E._lib.call(name, h, ctypes.c_void_p(t.data_ptr()), int(t.shape[0]), *extra)
+            assert err.value.code == ERR_INVALID
+    x2 = x + 0.25 * np.sin(x[:, [1, 2, 0]])                           # past skin / 2: the rows are built and filtered again
+    for step in ("same positions", "moved", "1-4 cleared"):
+        if step == "1-4 cleared":
+            for tiles in (ta, tb):
+                E._lib.call("emdee_nbr_set_pairs14", tiles._handle, None, 0, 1.0)
+        for tiles, out in zip((ta, tb), outs):
+            E.compute_nonbonded_(*out, E.cu(x if step == "same positions" else x2, dev), L, tiles, E.LennardJonesModel(rc, rs),
+                                 E.cu(atoms, dev), E.Val(7))
+        for qa, qb in zip(*outs):
+            assert torch.equal(qa, qb), step
+    ta.close(); tb.close()
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
