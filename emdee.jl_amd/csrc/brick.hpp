@@ -1388,10 +1388,11 @@ __global__ __launch_bounds__(THREADS) void k_brick_export(BrickArgs<real> a, int
 // named pairs to leave out.  One thread per own atom that has exclusions: its entries are decoded as k_brick_export does
 // (tile slot -> cell-order slot -> caller id), looked up in the atom's sorted exclusion list, and the row is compacted in
 // place, the vacated tail refilled with the sentinel.  Untyped rows only (a box with exclusions keeps the general kernels).
-// The loop is kernels.hpp strike_row (keys, the 1-4 partners' slots: PairKeys); this kernel decodes the entries and refills.
+// The loop is kernels.hpp strike_row (keys, the 1-4 and bonded partners' slots: PairKeys, BondedKeys); this kernel decodes the
+// entries and refills.
 template <typename real, class Shape, int THREADS, int G>
 __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, const int *__restrict__ ex_start,
-                                                          const int *__restrict__ ex_idx, PairKeys keys) {
+                                                          const int *__restrict__ ex_idx, PairKeys keys, BondedKeys bk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     BrickTables<Shape, THREADS> T;
     T.carve(s_dyn);
@@ -1412,7 +1413,7 @@ __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, con
         if (a.perm[p] >= a.n_owned) continue;
         const int m = min(a.cnt[p], a.stride);
         unsigned short *row = a.nbr + (size_t)p * a.stride;
-        const int w = strike_row(keys, a.perm, ex_start, ex_idx, p, m,
+        const int w = strike_row(keys, bk, a.perm, ex_start, ex_idx, p, m,
                                  [&](int e) -> unsigned short & { return row[row_position<G>((unsigned)e)]; }, slot);
         if (w < 0) continue;
         for (int e = w; e < m; e++) row[row_position<G>((unsigned)e)] = 0;   // the sentinel slot

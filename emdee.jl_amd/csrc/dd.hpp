@@ -531,6 +531,7 @@ struct DdImpl : IDd {
     void load() override {
         use_device(user_ctx);
         for (auto &d : dom) d->sys().uniform_known = -1;
+        for (auto &d : dom) d->sys().reset_bonded_error();   // (a new state: the bonded terms get another chance)
         redistribute(false);
         agree_on_species();
         if (n_global == 0) {
@@ -1252,6 +1253,45 @@ struct DdImpl : IDd {
         EMDEE_HIP_CHECK(hipGetLastError());
     }
 
+    // Collective.  The bonded table of one kind over global ids (nbsys.hpp PairTables::set_bonded), as set_pair_table: all or
+    // nothing, and after a load every domain is loaded again, so the partners' slots and the forces are current on return.
+    void set_bonded(int32_t kind, const int64_t *atoms, const double *params, int64_t n) override {
+        use_device(user_ctx);
+        join_halo();
+        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+        tables.set_bonded(kind, atoms, params, n, (int64_t)1 << 31, user_ctx->stream);
+        if (!loaded) return;
+        for (auto &pd : dom) {
+            Domain<real> &d = *pd;
+            d.sys().reset_bonded_error();
+            export_caller_arrays(d, d.ids.ptr, d.n_send);
+            load_engine(d, true);
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+        check_bonded();
+    }
+    // Collective and blocking: EMDEE_ERR_STATE on every rank if a domain's bonded term has lost a partner (NbSystem::check_bonded;
+    // the message names the term on the rank that holds it)
+    void check_bonded() {
+        if (!tables.has_bonded) return;
+        join_halo();
+        std::vector<std::vector<double>> bad;
+        bool mine = false;
+        for (auto &pd : dom) {
+            double b = 0.0;
+            try { pd->sys().check_bonded(); } catch (const Failure &) { b = 1.0; mine = true; }
+            bad.push_back({b});
+        }
+        double total = 0.0;
+        allreduce_sum(bad, 1, &total);
+        if (total > 0.0) {
+            // every domain of every rank refuses to step from now on, so that no rank enters a step's collectives alone
+            for (auto &pd : dom) pd->sys().bonded_broken = true;
+            if (!mine) set_error("a bonded term of another domain has lost a partner: replace the tables or the state");
+            throw Failure{EMDEE_ERR_STATE};
+        }
+    }
+
     // ---------------------------------------------------------------- stepping
     void set_langevin(double gamma, double temperature, uint64_t seed, uint64_t first_step) override {
         lgv_on = gamma > 0.0;
@@ -1282,8 +1322,8 @@ struct DdImpl : IDd {
     void forces_with_halo(int bitmask, int carry, bool check_displacement = true) {
         for (auto &pd : dom) hipLaunchKernelGGL(k_dd_batch_begin, dim3(1), dim3(64), 0, pd->stream(), pd->words.ptr, DD_WORDS, carry);
         with_halo(0, 0, [&](Domain<real> &d, int phase) {
-            // (a domain with 1-4 pairs adds them behind a whole force pass: all bricks behind the halo, as its steps do)
-            if (d.sys().has_14()) { if (phase == 1) return; phase = 0; }
+            // (a domain with 1-4 pairs or bonded terms adds them behind a whole force pass: all bricks behind the halo, as its steps do)
+            if (d.sys().has_post()) { if (phase == 1) return; phase = 0; }
             d.md->forces(bitmask, phase);
         });
         join_halo();
@@ -1321,6 +1361,8 @@ struct DdImpl : IDd {
         use_device(user_ctx);
         EMDEE_REQUIRE(loaded, EMDEE_ERR_STATE, "emdee_dd_step: call emdee_dd_load first");
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0 && rebuild_every >= 0, EMDEE_ERR_INVALID, "emdee_dd_step: negative argument");
+        for (auto &pd : dom)
+            EMDEE_REQUIRE(!pd->sys().bonded_broken, EMDEE_ERR_STATE, "emdee_dd_step: a bonded term has lost a partner; replace the tables or the state");
         if (nsteps == 0) return;
         // Which kernels a domain steps with is ITS business and may change at any rebuild (brick_active: the densest tile of
         // this domain fits LDS or not; an empty domain launches nothing): the batches, their exchanges and the guard words
@@ -1365,10 +1407,10 @@ struct DdImpl : IDd {
             for (int j = 0; j < B; j++) {
                 if (lgv_on) join_halo();   // (the boundary half of the previous step still reads the previous noise)
                 for (auto &pd : dom)
-                    if (pd->sys().brick_active && !pd->sys().has_14()) pd->sys().prepare_noise(dt);   // (thermostat only) before the pack: both halves read it
+                    if (pd->sys().brick_active && !pd->sys().has_post()) pd->sys().prepare_noise(dt);   // (thermostat only) before the pack: both halves read it
                 with_halo(j, j, [&](Domain<real> &d, int phase) {
                     if (d.sys().n_total == 0) return;                     // nothing to move; its words stay clear
-                    if (d.sys().brick_active && !d.sys().has_14()) {
+                    if (d.sys().brick_active && !d.sys().has_post()) {
                         // interior bricks look at my own request only (their neighbours are all mine); boundary bricks
                         // at the OR of everybody's
                         const int *guard = (phase == 1) ? d.V(j) : d.G(j);
@@ -1392,7 +1434,7 @@ struct DdImpl : IDd {
             }
             for (auto &pd : dom) {
                 Domain<real> &d = *pd;
-                const bool tiled = d.sys().brick_active && !d.sys().has_14() && d.sys().n_total > 0;
+                const bool tiled = d.sys().brick_active && !d.sys().has_post() && d.sys().n_total > 0;
                 if (tiled && ((B - ran) & 1)) d.sys().swap_step_buffers();   // the cancelled launches did not advance the ping-pong
                 if (d.sys().lgv_on && d.sys().n_total > 0) d.sys().lgv_step -= (unsigned long long)(B - ran);
                 if (tiled && d.sys().profiling) {
@@ -1436,6 +1478,7 @@ struct DdImpl : IDd {
             EMDEE_HIP_CHECK(hipMemsetAsync(pd->words.ptr, 0, DD_WORDS * sizeof(int), pd->stream()));
         }
         EMDEE_HIP_CHECK(hipGetLastError());
+        check_bonded();                                      // (one read-back per call, with bonded tables only)
     }
 
     // ---------------------------------------------------------------- state out
@@ -1443,6 +1486,7 @@ struct DdImpl : IDd {
         use_device(user_ctx);
         EMDEE_REQUIRE(loaded, EMDEE_ERR_STATE, "emdee_dd_energies: call emdee_dd_load first");
         join_halo();
+        check_bonded();
         std::vector<std::vector<double>> vals;
         for (auto &pd : dom) {
             // ghosts are current whenever the forces are (every force pass follows a halo unpack or a rebuild)
@@ -1456,6 +1500,7 @@ struct DdImpl : IDd {
         use_device(user_ctx);
         EMDEE_REQUIRE(loaded, EMDEE_ERR_STATE, "emdee_dd_pressure_tensor: call emdee_dd_load first");
         join_halo();
+        check_bonded();
         std::vector<std::vector<double>> vals;
         for (auto &pd : dom) {
             // (ghosts are current whenever the forces are, as for energies)

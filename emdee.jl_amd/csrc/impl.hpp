@@ -193,6 +193,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(vel || n_owned == 0, EMDEE_ERR_INVALID, "velocities are NULL");
         n_ghost = ng;
         sys.load_user(n_owned, ng, (const real *)pos, (const real *)vel, atoms, (const real *)inv_mass, tags_user);
+        if (!lent) sys.reset_bonded_error();                 // (a new state: the bonded terms get another chance; a decomposition resets its own)
         since_build = 0;
         current_mask = 0;
         if (!defer_forces) {
@@ -225,6 +226,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
         EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "md_step needs n_ghost == 0; decomposed runs drive kick_drift/forces/kick");
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
+        EMDEE_REQUIRE(!sys.bonded_broken, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
         if (nsteps == 0) return;
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
@@ -263,6 +265,7 @@ struct MdImpl : IMd {
         sys.kick(0.5 * dt);
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
+        if (!lent) sys.check_bonded();                       // (one read-back per call, with bonded tables only)
     }
     void kick_drift(double dt, double kick) override {
         use_device(sys.ctx);
@@ -322,6 +325,7 @@ struct MdImpl : IMd {
         use_device(sys.ctx);
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
         if ((current_mask & 7) != 7) forces(7, 0);
+        if (!lent) sys.check_bonded();                       // (a decomposition checks its domains together)
         sys.energy_sums(0.0, out);
     }
     // the tensor pass, unless the tensors are current: energies, virials and tensors; the forces stay as they are
@@ -345,6 +349,7 @@ struct MdImpl : IMd {
         use_device(sys.ctx);
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
         tensor_pass();
+        if (!lent) sys.check_bonded();
         sys.tensor_sums(out);
     }
     void stats(int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) override {
@@ -400,6 +405,20 @@ struct MdImpl : IMd {
         sys.compute_forces(EMDEE_FORCES);
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    void set_bonded(int32_t kind, const int32_t *atoms, const double *params, int32_t n_terms) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "bonded terms of a decomposed run: emdee_dd_set_bonded (this integrator is a domain's, lent by emdee_dd_engine)");
+        EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "bonded terms: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
+        sys.own_tables.set_bonded(kind, atoms, params, n_terms, sys.n_owned, sys.stream());
+        sys.has_list = false; sys.plan_valid = false;
+        sys.reset_bonded_error();
+        sys.resort();                                        // the rows and slots for the new partners (a two-species box leaves the typed kernels)
+        since_build = 0;
+        sys.compute_forces(EMDEE_FORCES);
+        current_mask = EMDEE_FORCES;
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.check_bonded();
     }
     void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) override {
         use_device(sys.ctx);

@@ -1159,24 +1159,45 @@ __device__ __forceinline__ long long pair_key(const PairKeys &k, const int *__re
     return k.tag ? k.tag[slot] : (long long)perm[slot];
 }
 
+// Bonded terms (emdee_*_set_bonded; nbsys.hpp PairTables): a CSR per atom key, keyed as PairKeys.  Row gi lists the atom's
+// bonded partners (pidx[pstart[gi] .. pstart[gi + 1]), ascending) and its terms (terms[tstart[gi] .. tstart[gi + 1])): x = kind
+// | role << 2 (role: the atom's position in the term), y, z, w = the other atoms of the term, in term order, as positions in
+// the atom's partner list.  The row filter records each partner's cell-order slot in slots[] (-1: not in the row at the build).
+struct BondedKeys {
+    int n_tab;
+    const int *pstart, *pidx;
+    int *slots;                                              // NULL: no bonded table
+    const int *tstart;
+    const int4 *terms;
+    const int *tid;                                          // per term entry: the term's number over all kinds (error reports)
+};
+
 // The loop both row filters share (k_filter_rows, brick.hpp k_brick_filter): owned atom p's row of m entries without its struck
-// entries (ex_start / ex_idx: exclusions and 1-4 pairs together), compacted in place, the 1-4 partners' slots recorded.
+// entries (ex_start / ex_idx: exclusions and 1-4 pairs together), compacted in place, the 1-4 and bonded partners' slots recorded.
 // at(e): the row's e-th entry (a reference); slot(entry): its cell-order slot.  Returns the new length, or -1 if p has nothing
 // struck (its row is left as it is).
 template <class At, class Slot>
-__device__ __forceinline__ int strike_row(const PairKeys &keys, const int *__restrict__ perm, const int *__restrict__ ex_start,
-                                          const int *__restrict__ ex_idx, int p, int m, At at, Slot slot) {
+__device__ __forceinline__ int strike_row(const PairKeys &keys, const BondedKeys &bk, const int *__restrict__ perm,
+                                          const int *__restrict__ ex_start, const int *__restrict__ ex_idx, int p, int m, At at,
+                                          Slot slot) {
     const long long gi = pair_key(keys, perm, p);
-    if (gi < 0 || gi >= keys.n_tab) return -1;
-    const int lo = ex_start[gi], hi = ex_start[gi + 1];
-    if (lo == hi) return -1;
-    const int lo14 = keys.s14 ? keys.start14[gi] : 0, hi14 = keys.s14 ? keys.start14[gi + 1] : 0;
+    const bool ex = gi >= 0 && gi < keys.n_tab && ex_start[gi] < ex_start[gi + 1];
+    const bool bd = bk.slots != nullptr && gi >= 0 && gi < bk.n_tab && bk.pstart[gi] < bk.pstart[gi + 1];
+    if (!ex && !bd) return -1;
+    const int lo = ex ? ex_start[gi] : 0, hi = ex ? ex_start[gi + 1] : 0;
+    const int lo14 = (ex && keys.s14) ? keys.start14[gi] : 0, hi14 = (ex && keys.s14) ? keys.start14[gi + 1] : 0;
     for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
+    const int lob = bd ? bk.pstart[gi] : 0, hib = bd ? bk.pstart[gi + 1] : 0;
+    for (int k = lob; k < hib; k++) bk.slots[k] = -1;
     int w = 0;
     for (int e = 0; e < m; e++) {
         const auto ent = at(e);
         const int q = slot(ent);
         const long long gj = pair_key(keys, perm, q);
+        if (lob < hib) {
+            const int k = csr_find(bk.pidx, lob, hib, gj);
+            if (k >= 0) bk.slots[k] = q;
+        }
         if (!csr_holds(ex_idx, lo, hi, (int)min(gj, (long long)keys.n_tab))) {
             if (w != e) at(w) = ent;
             w++;
@@ -1185,18 +1206,18 @@ __device__ __forceinline__ int strike_row(const PairKeys &keys, const int *__res
             if (k >= 0) keys.s14[k] = q;
         }
     }
-    return w;
+    return ex ? w : -1;
 }
 
 // rows of the direct (int32, cell-order slot) list without their excluded entries
 static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__ perm, int *__restrict__ nbr, int stride,
                                      int *__restrict__ cnt, const int *__restrict__ ex_start, const int *__restrict__ ex_idx,
-                                     PairKeys keys) {
+                                     PairKeys keys, BondedKeys bk) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     if (perm[p] >= n_owned) return;
     int *row = nbr + (size_t)p * stride;
-    const int w = strike_row(keys, perm, ex_start, ex_idx, p, min(cnt[p], stride), [&](int e) -> int & { return row[e]; },
+    const int w = strike_row(keys, bk, perm, ex_start, ex_idx, p, min(cnt[p], stride), [&](int e) -> int & { return row[e]; },
                              [](int q) { return q; });
     if (w >= 0) cnt[p] = w;
 }
@@ -1263,6 +1284,147 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
         if (TENSOR)
             for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
     }
+}
+
+// Bonded terms: owner-computes over the slots the row filter recorded at the last build -- no atomics, the row's order of
+// summation.  Each owned atom evaluates every term it belongs to in full (chained minimum images along the term's bonds: the
+// term is unwrapped) and keeps its own force and a 1/2, 1/3, 1/4 share of the term's U, of W = sum_a x_a . F_a and of the
+// symmetrised tensor sum_a x_a (x) F_a.  A partner missing from the rows (farther than rc + skin at the build) leaves the term
+// out and writes its number + 1 to *err (read by the host: NbSystem::check_bonded).
+// prm: 3 values per term entry -- bond {k, r0, 0}, angle {k, theta0, 0}, torsion {k, n, phase}.
+template <typename real>
+__device__ __forceinline__ void cross3(const real a[3], const real b[3], real c[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+template <typename real>
+__device__ __forceinline__ real dot3(const real a[3], const real b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// U and the forces F[0 .. nat) of one term at unwrapped positions u[0 .. nat) (kind: 1 bond, 2 angle, 3 torsion)
+template <typename real>
+__device__ __forceinline__ real bonded_term(int kind, const real u[4][3], real p0, real p1, real p2, real F[4][3]) {
+    const real tiny = sizeof(real) == 8 ? (real)1e-300 : (real)1e-37;
+    real U;
+    if (kind == 1) {
+        real d[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) d[c] = u[1][c] - u[0][c];
+        const real r = sqrt(dot3(d, d));
+        const real g = p0 * (r - p1) / max(r, tiny);
+#pragma unroll
+        for (int c = 0; c < 3; c++) { F[1][c] = -g * d[c]; F[0][c] = g * d[c]; F[2][c] = 0; F[3][c] = 0; }
+        U = (real)0.5 * p0 * (r - p1) * (r - p1);
+    } else if (kind == 2) {
+        real a[3], b[3], cr[3], ac[3], bc[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) { a[c] = u[0][c] - u[1][c]; b[c] = u[2][c] - u[1][c]; }
+        cross3(a, b, cr);
+        const real cn = sqrt(dot3(cr, cr));
+        const real th = atan2(cn, dot3(a, b));               // finite at 0 and pi (no acos of a clamped cosine needed)
+        const real dU = p0 * (th - p1);
+        cross3(a, cr, ac);
+        cross3(b, cr, bc);
+        const real gi = -dU / (dot3(a, a) * max(cn, tiny)), gk = dU / (dot3(b, b) * max(cn, tiny));
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            F[0][c] = gi * ac[c]; F[2][c] = gk * bc[c]; F[1][c] = -F[0][c] - F[2][c]; F[3][c] = 0;
+        }
+        U = (real)0.5 * p0 * (th - p1) * (th - p1);
+    } else {
+        real b1[3], b2[3], b3[3], m[3], n[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) { b1[c] = u[1][c] - u[0][c]; b2[c] = u[2][c] - u[1][c]; b3[c] = u[3][c] - u[2][c]; }
+        cross3(b1, b2, m);
+        cross3(b2, b3, n);
+        const real b22 = dot3(b2, b2), b2n = sqrt(b22);
+        const real phi = atan2(b2n * dot3(b1, n), dot3(m, n));   // IUPAC: trans = pi
+        const real arg = p1 * phi - p2;
+        const real dU = -p0 * p1 * sin(arg);
+        const real ci = dU * b2n / max(dot3(m, m), tiny), cl = -dU * b2n / max(dot3(n, n), tiny);   // F_i = ci m, F_l = cl n
+        const real s1 = dot3(b1, b2) / max(b22, tiny), s3 = dot3(b3, b2) / max(b22, tiny);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            F[0][c] = ci * m[c];
+            F[3][c] = cl * n[c];
+            F[1][c] = -((real)1 + s1) * F[0][c] + s3 * F[3][c];
+            F[2][c] = -F[0][c] - F[3][c] - F[1][c];
+        }
+        U = p0 * ((real)1 + cos(arg));
+    }
+    return U;
+}
+
+template <typename real, bool TENSOR = false>
+__global__ __launch_bounds__(256) void k_bonded(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
+                         BondedKeys bk, const real *__restrict__ prm, GridP<real> g, int bitmask, real *__restrict__ frc,
+                         real *__restrict__ en, real *__restrict__ vir, real *__restrict__ vt, int *__restrict__ err) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int i = perm[p];
+    if (i >= n_owned) return;
+    const long long gi = pair_key(keys, perm, p);
+    if (gi < 0 || gi >= bk.n_tab) return;
+    const int lo = bk.tstart[gi], hi = bk.tstart[gi + 1];
+    if (lo == hi) return;
+    const int base = bk.pstart[gi];
+    real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+    real tv[6] = {0, 0, 0, 0, 0, 0};
+    for (int t = lo; t < hi; t++) {
+        const int4 d = bk.terms[t];
+        const int kind = d.x & 3, role = d.x >> 2, nat = kind + 1;
+        // the term's atoms in term order: this atom at `role`, the others from the recorded slots
+        int s[4];
+        bool ok = true;
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            const int k = a < role ? a : a - 1;              // position among the other atoms
+            const int loc = k == 0 ? d.y : (k == 1 ? d.z : d.w);
+            const int q = (a < nat && a != role) ? bk.slots[base + loc] : p;
+            ok = ok && q >= 0;
+            s[a] = q;
+        }
+        if (!ok) { *err = bk.tid[t] + 1; continue; }
+        real u[4][3], F[4][3];                                // u: unwrapped positions relative to the term's first atom
+        real px, py, pz;
+        {
+            real hs, te;
+            load_atom(atoms, s[0], px, py, pz, hs, te);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) u[0][c] = 0;
+#pragma unroll
+        for (int a = 1; a < 4; a++) {
+            real x, y, z, hs, te;
+            load_atom(atoms, s[a], x, y, z, hs, te);
+            u[a][0] = u[a - 1][0] + min_image(x - px, g.plen[0], g.pinv[0]);
+            u[a][1] = u[a - 1][1] + min_image(y - py, g.plen[1], g.pinv[1]);
+            u[a][2] = u[a - 1][2] + min_image(z - pz, g.plen[2], g.pinv[2]);
+            px = x; py = y; pz = z;
+        }
+        const real U = bonded_term<real>(kind, u, prm[3 * (size_t)t], prm[3 * (size_t)t + 1], prm[3 * (size_t)t + 2], F);
+        real T[6] = {0, 0, 0, 0, 0, 0};                       // sum_a u_a (x) F_a, symmetrised
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            T[0] += u[a][0] * F[a][0]; T[1] += u[a][1] * F[a][1]; T[2] += u[a][2] * F[a][2];
+            T[3] += (real)0.5 * (u[a][0] * F[a][1] + u[a][1] * F[a][0]);
+            T[4] += (real)0.5 * (u[a][0] * F[a][2] + u[a][2] * F[a][0]);
+            T[5] += (real)0.5 * (u[a][1] * F[a][2] + u[a][2] * F[a][1]);
+        }
+        const real share = (real)1 / (real)nat;
+        fx += role == 0 ? F[0][0] : role == 1 ? F[1][0] : role == 2 ? F[2][0] : F[3][0];
+        fy += role == 0 ? F[0][1] : role == 1 ? F[1][1] : role == 2 ? F[2][1] : F[3][1];
+        fz += role == 0 ? F[0][2] : role == 1 ? F[1][2] : role == 2 ? F[2][2] : F[3][2];
+        e += share * U;
+        w += share * (T[0] + T[1] + T[2]);
+        if (TENSOR)
+            for (int c = 0; c < 6; c++) tv[c] += share * T[c];
+    }
+    if (bitmask & EMDEE_FORCES) { frc[p] += fx; frc[pitch + p] += fy; frc[2 * pitch + p] += fz; }
+    if (bitmask & EMDEE_ENERGIES) en[p] += e;
+    if (bitmask & EMDEE_VIRIALS) vir[p] += w;
+    if (TENSOR)
+        for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
 }
 
 // ------------------------------------------------------------------------------------ reductions

@@ -181,6 +181,136 @@ struct PairTables {
         rows = r; limit = lim; n14 = pi.size();
         has_excl = !xi.empty(); has_14 = !pi.empty();
     }
+
+    // ---- bonded terms (emdee_*_set_bonded): kernels.hpp BondedKeys.  Rows 0 .. b_rows - 1 list each atom's bonded partners and
+    // its terms; the terms as given are kept per kind (b_atoms, b_prm) so that one kind can be replaced without the others.
+    static constexpr int KINDS = 4;                          // kinds 1 (bond), 2 (angle), 3 (torsion)
+    static int kind_atoms(int kind) { return kind + 1; }
+    static int kind_params(int kind) { return kind == 3 ? 3 : 2; }
+    std::vector<int32_t> b_atoms[KINDS];
+    std::vector<double> b_prm[KINDS];
+    DevBuf<int> b_pstart, b_pidx, b_tstart, b_tid;
+    DevBuf<int4> b_terms;
+    DevBuf<double> b_prm_d;
+    DevBuf<float> b_prm_f;
+    int b_rows = 0;
+    size_t nb = 0;                                           // entries of the partner CSR (slots of the row filter)
+    bool has_bonded = false;
+    template <typename real>
+    const real *bonded_params() const {
+        if constexpr (sizeof(real) == 8) return b_prm_d.ptr; else return b_prm_f.ptr;
+    }
+    // term number (over all kinds, in kind order) -> kind and index within it
+    void bonded_term_of(int64_t id, int &kind, int64_t &index) const {
+        for (kind = 1; kind < KINDS - 1 && id >= (int64_t)(b_atoms[kind].size() / kind_atoms(kind)); kind++)
+            id -= (int64_t)(b_atoms[kind].size() / kind_atoms(kind));
+        index = id;
+    }
+    // Replaces the table of one kind by the n terms at atoms_dev / params_dev (device; kind_atoms(kind) ids and
+    // kind_params(kind) doubles per term); n = 0 clears it.  All or nothing, as set().
+    template <typename T>
+    void set_bonded(int kind, const T *atoms_dev, const double *params_dev, int64_t n, int64_t lim, hipStream_t s) {
+        EMDEE_REQUIRE(kind >= 1 && kind <= 3, EMDEE_ERR_INVALID, "set_bonded: unknown kind %d (EMDEE_HARMONIC_BOND, "
+                      "EMDEE_HARMONIC_ANGLE or EMDEE_PERIODIC_TORSION)", kind);
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && params_dev)), EMDEE_ERR_INVALID, "set_bonded: negative count or NULL array");
+        const int na = kind_atoms(kind), np = kind_params(kind);
+        std::vector<T> raw((size_t)na * n);
+        std::vector<double> prm((size_t)np * n);
+        if (n > 0) {
+            EMDEE_HIP_CHECK(hipMemcpyAsync(raw.data(), atoms_dev, raw.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+            EMDEE_HIP_CHECK(hipMemcpyAsync(prm.data(), params_dev, prm.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        }
+        static const char *const names[KINDS] = {"", "bond", "angle", "torsion"};
+        for (int64_t k = 0; k < n; k++) {
+            for (int a = 0; a < na; a++) {
+                const int64_t g = raw[(size_t)na * k + a];
+                EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_bonded: %s %lld names id %lld, outside [0, %lld)", names[kind],
+                              (long long)k, (long long)g, (long long)lim);
+                for (int b = 0; b < a; b++)
+                    EMDEE_REQUIRE(raw[(size_t)na * k + b] != raw[(size_t)na * k + a], EMDEE_ERR_INVALID,
+                                  "set_bonded: %s %lld names atom %lld twice", names[kind], (long long)k, (long long)g);
+            }
+            const double *q = prm.data() + (size_t)np * k;
+            for (int c = 0; c < np; c++)
+                EMDEE_REQUIRE(std::isfinite(q[c]), EMDEE_ERR_INVALID, "set_bonded: %s %lld has a non-finite parameter", names[kind], (long long)k);
+            if (kind == 1) EMDEE_REQUIRE(q[1] >= 0.0, EMDEE_ERR_INVALID, "set_bonded: bond %lld has r0 < 0", (long long)k);
+            if (kind == 2) EMDEE_REQUIRE(q[1] >= 0.0 && q[1] <= M_PI, EMDEE_ERR_INVALID, "set_bonded: angle %lld has theta0 outside [0, pi]", (long long)k);
+            if (kind == 3) EMDEE_REQUIRE(q[1] >= 1.0 && q[1] == std::floor(q[1]), EMDEE_ERR_INVALID,
+                                         "set_bonded: torsion %lld has a periodicity that is not an integer >= 1", (long long)k);
+        }
+        int64_t total = n;
+        for (int kd = 1; kd < KINDS; kd++)
+            if (kd != kind) total += (int64_t)(b_atoms[kd].size() / kind_atoms(kd));
+        EMDEE_REQUIRE(total < INT32_MAX, EMDEE_ERR_INVALID, "set_bonded: %lld terms in all (at most 2^31 - 2)", (long long)total);
+        const std::vector<int32_t> h(raw.begin(), raw.end());
+        const std::vector<int32_t> *at[KINDS];
+        const std::vector<double> *pr[KINDS];
+        for (int kd = 1; kd < KINDS; kd++) { at[kd] = kd == kind ? &h : &b_atoms[kd]; pr[kd] = kd == kind ? &prm : &b_prm[kd]; }
+        // partners: (owner, partner) over every role of every term -> CSR, ascending, unique
+        int r = 0;
+        for (int kd = 1; kd < KINDS; kd++)
+            for (int32_t g : *at[kd]) r = std::max(r, g + 1);
+        std::vector<int32_t> half;                           // each partner pair once (csr() makes the rows symmetric)
+        for (int kd = 1; kd < KINDS; kd++) {
+            const int nk = kind_atoms(kd);
+            for (size_t t = 0; t + nk <= at[kd]->size(); t += nk)
+                for (int a = 0; a < nk; a++)
+                    for (int b = 0; b < nk; b++)
+                        if ((*at[kd])[t + a] < (*at[kd])[t + b]) { half.push_back((*at[kd])[t + a]); half.push_back((*at[kd])[t + b]); }
+        }
+        std::vector<int32_t> ps, pi;
+        csr(half, std::vector<int32_t>{}, r, ps, pi);
+        // term entries, in (kind, term, role) order within each row
+        std::vector<int32_t> ts((size_t)r + 1, 0);
+        for (int kd = 1; kd < KINDS; kd++)
+            for (int32_t g : *at[kd]) ts[(size_t)g + 1]++;
+        for (int q = 0; q < r; q++) ts[(size_t)q + 1] += ts[q];
+        std::vector<int4> terms(ts[r]);
+        std::vector<int32_t> tid(ts[r]);
+        std::vector<double> pd((size_t)3 * ts[r], 0.0);
+        std::vector<float> pf((size_t)3 * ts[r], 0.f);
+        std::vector<int32_t> fill(ts.begin(), ts.end() - 1);
+        int32_t number = 0;
+        for (int kd = 1; kd < KINDS; kd++) {
+            const int nk = kind_atoms(kd), npk = kind_params(kd);
+            for (size_t t = 0; t + nk <= at[kd]->size(); t += nk, number++) {
+                const int32_t *ids = at[kd]->data() + t;
+                const double *q = pr[kd]->data() + (t / nk) * npk;
+                for (int role = 0; role < nk; role++) {
+                    const int32_t g = ids[role];
+                    const int e = fill[g]++;
+                    int loc[3] = {0, 0, 0}, c = 0;
+                    for (int a = 0; a < nk; a++) {
+                        if (a == role) continue;
+                        const auto it = std::lower_bound(pi.begin() + ps[g], pi.begin() + ps[(size_t)g + 1], ids[a]);
+                        loc[c++] = (int)(it - (pi.begin() + ps[g]));
+                    }
+                    terms[e] = make_int4(kd | role << 2, loc[0], loc[1], loc[2]);
+                    tid[e] = number;
+                    for (int c2 = 0; c2 < npk; c2++) { pd[(size_t)3 * e + c2] = q[c2]; pf[(size_t)3 * e + c2] = (float)q[c2]; }
+                }
+            }
+        }
+        DevBuf<int> nps, npi, nts, ntid;
+        DevBuf<int4> nterms;
+        DevBuf<double> npd;
+        DevBuf<float> npf;
+        upload(nps, ps, s); upload(npi, pi, s); upload(nts, ts, s); upload(ntid, tid, s);
+        nterms.ensure(terms.size() + 1); npd.ensure(pd.size() + 1); npf.ensure(pf.size() + 1);
+        if (!terms.empty()) {
+            EMDEE_HIP_CHECK(hipMemcpyAsync(nterms.ptr, terms.data(), terms.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+            EMDEE_HIP_CHECK(hipMemcpyAsync(npd.ptr, pd.data(), pd.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            EMDEE_HIP_CHECK(hipMemcpyAsync(npf.ptr, pf.data(), pf.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        b_pstart.swap(nps); b_pidx.swap(npi); b_tstart.swap(nts); b_tid.swap(ntid); b_terms.swap(nterms);
+        b_prm_d.swap(npd); b_prm_f.swap(npf);
+        b_atoms[kind] = h; b_prm[kind] = prm;
+        b_rows = r; limit = lim; nb = pi.size();
+        has_bonded = !terms.empty();
+    }
 };
 
 template <typename real>
@@ -847,7 +977,7 @@ struct NbSystem {
         // two species: the typed kernels (typed.hpp), if the tile fits their coordinate planes, no three cells of a tile row hold
         // more atoms of one species than the 16-bit hit fields of their build take, and both kernels fit LDS
         typed_active = false;
-        if (brick_active && nt == 2 && !typed_blocked && !has_excl()) {
+        if (brick_active && nt == 2 && !typed_blocked && !filters_rows()) {
             // (where the general-species kernels take 1024 threads with 8 lanes per atom -- long cutoffs -- the typed ones take
             // 1024 threads with 4: rows are two block-aligned segments, and blocks of 32 entries pad them half as much as blocks of 64)
             // Measured (profiles/README.md, round 3): at rc = 3.5 sigma 190.7 -> 218.0 steps/s in fp64 and 233.8 -> 324.2 in fp32; at
@@ -1095,8 +1225,42 @@ struct NbSystem {
     PairTables own_tables;                                   // an undivided engine's, over caller ids
     PairTables *tables = &own_tables;                        // a decomposed engine's point at the decomposition's, over global ids
     DevBuf<int> slots14;                                     // per 1-4 entry of an owned atom's row: the partner's cell-order slot
+    DevBuf<int> slotsb;                                      // per bonded partner of an owned atom: its cell-order slot
     bool has_excl() const { return tables->has_excl; }
     bool has_14() const { return tables->has_14; }
+    bool has_bonded() const { return tables->has_bonded; }
+    // terms added behind a whole force pass (add_post_terms): such a box steps in the split form (force pass, these terms,
+    // kick + drift), not the fused one
+    bool has_post() const { return has_14() || has_bonded(); }
+    // rows the filter visits right after every build: excluded pairs are struck, 1-4 and bonded partners' slots recorded
+    bool filters_rows() const { return has_excl() || has_bonded(); }
+    // a bonded term whose partner was missing from the rows (flags[16], raised by k_bonded): the engine refuses to step until
+    // the tables or the state are replaced
+    bool bonded_broken = false;
+    void reset_bonded_error() {
+        bonded_broken = false;
+        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 16, 0, sizeof(int), stream()));
+    }
+    // blocking: EMDEE_ERR_STATE naming the term if k_bonded has met a missing partner since the last reset
+    void check_bonded() {
+        if (!has_bonded() || !flags.ptr) return;
+        int32_t word = 0;
+        if (!bonded_broken) read_back_words(ctx, stream(), flags.ptr + 16, 1, &word);
+        if (word != 0) {
+            bonded_broken = true;
+            int kind;
+            int64_t index;
+            tables->bonded_term_of((int64_t)word - 1, kind, index);
+            static const char *const names[4] = {"", "bond", "angle", "torsion"};
+            const int na = PairTables::kind_atoms(kind);
+            const int32_t *ids = tables->b_atoms[kind].data() + (size_t)na * index;
+            set_error("bonded %s %lld (atoms %d %d%s%s%s%s): a partner is farther than rc + skin from its owner at a neighbour-list "
+                      "build, so the term cannot be evaluated; replace the tables or the state", names[kind], (long long)index, ids[0], ids[1],
+                      na > 2 ? " " : "", na > 2 ? std::to_string(ids[2]).c_str() : "", na > 3 ? " " : "", na > 3 ? std::to_string(ids[3]).c_str() : "");
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        EMDEE_REQUIRE(!bonded_broken, EMDEE_ERR_STATE, "a bonded term has lost a partner (reported before): replace the tables or the state");
+    }
     // emdee_nbr_* / emdee_md_set_exclusions, _set_pairs14: replaces one of the engine's own tables (n = 0 clears it), all or nothing
     void set_pair_tables(int n_atoms, const int32_t *pairs_dev, int n_pairs, bool one_four, double scale) {
         own_tables.set(pairs_dev, n_pairs, one_four, scale, n_atoms, stream());
@@ -1105,6 +1269,10 @@ struct NbSystem {
     PairKeys pair_keys() const {
         return PairKeys{use_tags ? tag.ptr : nullptr, tables->rows, tables->p_start.ptr, tables->p_idx.ptr, has_14() ? slots14.ptr : nullptr};
     }
+    BondedKeys bonded_keys() const {
+        return BondedKeys{tables->b_rows, tables->b_pstart.ptr, tables->b_pidx.ptr, has_bonded() ? slotsb.ptr : nullptr,
+                          tables->b_tstart.ptr, tables->b_terms.ptr, tables->b_tid.ptr};
+    }
     void check_tables(const char *what) const {
         if (tables != &own_tables) EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "%s over global ids: the state carries no tags", what);
         else EMDEE_REQUIRE(tables->limit == n_owned && !id_gaps, EMDEE_ERR_STATE, "%s set for %lld atoms, the state holds %d", what,
@@ -1112,9 +1280,10 @@ struct NbSystem {
     }
     // right after a build: the rows without their excluded entries, and the 1-4 partners' slots
     void apply_exclusions() {
-        if (!has_excl() || n_total == 0) return;
-        check_tables("exclusion tables");
+        if (!filters_rows() || n_total == 0) return;
+        check_tables("exclusion / bonded tables");
         if (has_14()) slots14.ensure(tables->n14 + 1);
+        if (has_bonded()) slotsb.ensure(tables->nb + 1);
         if (brick_active) {
             EMDEE_REQUIRE(!typed_active, EMDEE_ERR_STATE, "exclusions: typed rows are not filtered");
             with_brick_variant(variant, [&](auto v) {
@@ -1122,11 +1291,11 @@ struct NbSystem {
                 auto kernel = k_brick_filter<real, typename V::Shape, V::THREADS, V::G>;
                 using BT = BrickTables<typename V::Shape, V::THREADS>;
                 hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(),
-                                   tables->x_start.ptr, tables->x_idx.ptr, pair_keys());
+                                   tables->x_start.ptr, tables->x_idx.ptr, pair_keys(), bonded_keys());
             });
         } else {
             hipLaunchKernelGGL(k_filter_rows, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, perm.ptr, nbr.ptr, stride,
-                               cnt.ptr, tables->x_start.ptr, tables->x_idx.ptr, pair_keys());
+                               cnt.ptr, tables->x_start.ptr, tables->x_idx.ptr, pair_keys(), bonded_keys());
         }
     }
     // after a force pass: the scaled 1-4 terms on top
@@ -1139,6 +1308,20 @@ struct NbSystem {
                            pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
                            user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
                            user ? out_vt : (real *)nullptr);
+    }
+
+    // after a force pass: the bonded terms on top (k_bonded; not on the operator path, which has no bonded tables)
+    void add_bonded(int bitmask) {
+        if (!has_bonded() || n_total == 0) return;
+        check_tables("bonded tables");
+        auto kernel = (bitmask & EMDEE_TENSOR) ? k_bonded<real, true> : k_bonded<real, false>;
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
+                           pair_keys(), bonded_keys(), tables->template bonded_params<real>(), grid, bitmask, frc.ptr, en.ptr,
+                           vir.ptr, vt.ptr, flags.ptr + 16);
+    }
+    void add_post_terms(int bitmask) {
+        add_pairs14(bitmask);
+        add_bonded(bitmask);
     }
 
     // ---------------------------------------------------------------- forces
@@ -1259,7 +1442,7 @@ struct NbSystem {
                     bool carry_ghosts = true, bool noise_ready = false) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         if (!brick_active || n_total == 0) return false;
-        if (has_14()) return false;                            // (the scaled 1-4 terms are added behind a force pass: the split kernels)
+        if (has_post()) return false;                          // (the scaled 1-4 and bonded terms are added behind a force pass: the split kernels)
         if (phase != 2 && !noise_ready) prepare_noise(dt);   // phases 1 and 2 are the two halves of one step
         {
             Timed t(this, phase == 2 ? T_STEP_BOUNDARY : T_STEP);
@@ -1292,7 +1475,7 @@ struct NbSystem {
     int fused_steps_run_ahead(double c, double dt, int want, bool *stale) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         *stale = false;
-        if (!brick_active || n_total == 0 || has_ghosts || has_14()) return 0;
+        if (!brick_active || n_total == 0 || has_ghosts || has_post()) return 0;
         const int B = std::max(1, std::min(want, run_ahead));
         int *words = flags.ptr + 9;                          // flags[9 .. 9 + RUN_AHEAD)
         EMDEE_HIP_CHECK(hipMemsetAsync(words, 0, B * sizeof(int), stream()));
@@ -1337,7 +1520,7 @@ struct NbSystem {
         force_phase = brick_active ? phase : 0;
         if (brick_active) {
             with_brick_variant(variant, [&](auto v) { launch_brick_force<decltype(v)>(bitmask); });
-            if (phase != 1) add_pairs14(bitmask);            // (once per force pass: behind its last half)
+            if (phase != 1) add_post_terms(bitmask);         // (once per force pass: behind its last half)
             return;
         }
         switch (bitmask) {
@@ -1350,7 +1533,7 @@ struct NbSystem {
             case TENSOR_PASS: launch_direct_force<TENSOR_PASS>(); break;
             default: launch_direct_force<7>(); break;
         }
-        add_pairs14(bitmask);
+        add_post_terms(bitmask);
     }
 
     // ---------------------------------------------------------------- integrator
@@ -1374,7 +1557,7 @@ struct NbSystem {
     // at unmoved positions -- the rebuild the raised word brings evaluates them afresh.
     void guarded_split_step(double c, double dt, const int *guard, int *trigger) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
-        EMDEE_REQUIRE(!brick_active || has_14(), EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
+        EMDEE_REQUIRE(!brick_active || has_post(), EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
         if (n_total == 0) return;
         direct_guard = guard;
         compute_forces(EMDEE_FORCES, 0);

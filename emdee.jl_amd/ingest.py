@@ -1,7 +1,10 @@
 """Inputs and outputs either side of the hot path: an XYZ reader/writer
 (stands in for the Chemfiles read of test/runtests.jl:20-23), the Lennard-Jones part of an OpenMM-style
 force-field file (the `NonbondedForce` table the reference parses at src/modelling.jl:71-73,197-200)
-turned into LJAtom arrays, and a checkpoint of (positions, velocities, step).  Host-side, numpy only."""
+turned into LJAtom arrays, its bonded terms (`HarmonicBondForce`, `HarmonicAngleForce`, `PeriodicTorsionForce` propers,
+src/modelling.jl:46-69) and residue templates turned into the tables of emdee_*_set_bonded, exclusions and 1-4 pairs, and a
+checkpoint of (positions, velocities, step).  Host-side, numpy only."""
+from collections import deque
 import xml.etree.ElementTree as ET
 
 import numpy as np
@@ -53,6 +56,133 @@ class NonbondedTable:
         sigma = np.array([self.types[t]["sigma"] for t in atom_types], dtype=np.float64) / length_unit
         eps = np.array([self.types[t]["epsilon"] for t in atom_types], dtype=np.float64) / energy_unit
         return lennard_jones_atoms(eps, sigma)
+
+
+class BondedTable:
+    """Bonded parameters by atom type: `<HarmonicBondForce><Bond type1= type2= length= k=/>`, `<HarmonicAngleForce><Angle
+    type1..3= angle= k=/>` and `<PeriodicTorsionForce><Proper type1..4= periodicity1..N= phase1..N= k1..N=/>` (impropers are
+    not read).  A pattern names types (`typeN`) or classes (`classN`, the class of each type from `<AtomTypes>`); "" is a
+    wildcard; a pattern matches forward or reversed.  Of the patterns that match, the one with the fewest wildcards wins, and
+    among those the first in the file (OpenMM's preference of a specific match over a wildcard one).  Units as OpenMM writes
+    them: nm, kJ/mol, radians."""
+
+    def __init__(self, xml_file):
+        root = ET.parse(xml_file).getroot()
+        self.classes = {t.attrib["name"]: t.attrib.get("class", t.attrib["name"]) for t in root.iter("Type")}
+        self.masses = {t.attrib["name"]: float(t.attrib["mass"]) for t in root.iter("Type") if "mass" in t.attrib}
+        self.bonds, self.angles, self.propers = [], [], []
+        for kind, tag, n, out in (("HarmonicBondForce", "Bond", 2, self.bonds), ("HarmonicAngleForce", "Angle", 3, self.angles),
+                                  ("PeriodicTorsionForce", "Proper", 4, self.propers)):
+            for force in root.findall(kind):
+                for el in force.findall(tag):
+                    a = el.attrib
+                    by = "class" if ("class1" in a and "type1" not in a) else "type"
+                    pattern = tuple(a.get("%s%d" % (by, k + 1), "") for k in range(n))
+                    if tag == "Bond":
+                        params = [(float(a["k"]), float(a["length"]))]
+                    elif tag == "Angle":
+                        params = [(float(a["k"]), float(a["angle"]))]
+                    else:
+                        params, m = [], 1
+                        while "k%d" % m in a:
+                            params.append((float(a["k%d" % m]), float(a["periodicity%d" % m]), float(a["phase%d" % m])))
+                            m += 1
+                    out.append((by, pattern, params))
+
+    def _find(self, table, atom_types):
+        best, fewest = None, None
+        for by, pattern, params in table:
+            names = atom_types if by == "type" else tuple(self.classes.get(t, t) for t in atom_types)
+            if any(all(p == "" or p == t for p, t in zip(pattern, seq)) for seq in (names, names[::-1])):
+                wild = pattern.count("")
+                if fewest is None or wild < fewest:
+                    best, fewest = params, wild
+        return best
+
+    def bond(self, t1, t2):
+        return self._find(self.bonds, (t1, t2))
+
+    def angle(self, t1, t2, t3):
+        return self._find(self.angles, (t1, t2, t3))
+
+    def proper(self, t1, t2, t3, t4):
+        return self._find(self.propers, (t1, t2, t3, t4))
+
+
+class ResidueTemplates:
+    """`<Residues><Residue name=><Atom name= type=/>...<Bond atomName1= atomName2=/>...` of a force-field file."""
+
+    def __init__(self, xml_file):
+        root = ET.parse(xml_file).getroot()
+        self.residues = {}
+        for res in root.iter("Residue"):
+            names = [a.attrib["name"] for a in res.findall("Atom")]
+            index = {nm: k for k, nm in enumerate(names)}
+            types = [a.attrib["type"] for a in res.findall("Atom")]
+            bonds = [(index[b.attrib["atomName1"]], index[b.attrib["atomName2"]]) for b in res.findall("Bond")]
+            self.residues[res.attrib["name"]] = dict(names=names, types=types, bonds=bonds)
+
+    def build(self, sequence):
+        """(types, bonds (n, 2) int64) of a sequence of residue names, the atoms of each residue in template order"""
+        types, bonds = [], []
+        for name in sequence:
+            r = self.residues[name]
+            bonds += [(len(types) + i, len(types) + j) for i, j in r["bonds"]]
+            types += r["types"]
+        return types, np.array(bonds, dtype=np.int64).reshape(-1, 2)
+
+
+def topology(types, bonds, table, length_unit=1.0, energy_unit=1.0):
+    """Bonded terms, exclusions and 1-4 pairs of atoms of the given types joined by the given bonds (emdee_*_set_bonded,
+    _set_exclusions, _set_pairs14):
+      bonds, angles, torsions: (n, 2 | 3 | 4) ids, every i-j-k and i-j-k-l path of distinct atoms once; a torsion with several
+        periodicities appears once per term;
+      bond_params {k, r0}, angle_params {k, theta0}, torsion_params {k, n, phase}: parameters in the caller's units (lengths
+        / length_unit, energies / energy_unit, as NonbondedTable.lj_atoms);
+      exclusions: the 1-2 and 1-3 pairs; pairs14: the pairs at bond distance exactly 3, each once.
+    Raises KeyError for a term the table has no parameters for."""
+    n = len(types)
+    nb = [set() for _ in range(n)]
+    for i, j in np.asarray(bonds, dtype=np.int64).reshape(-1, 2):
+        nb[i].add(int(j)); nb[j].add(int(i))
+    nb = [sorted(s) for s in nb]
+    bl = sorted({(min(i, j), max(i, j)) for i in range(n) for j in nb[i]})
+    angles = [(i, j, k) for j in range(n) for i in nb[j] for k in nb[j] if i < k]
+    tors = [(i, j, k, l) for j in range(n) for k in nb[j] if j < k for i in nb[j] if i != k for l in nb[k] if l != j and l != i]
+
+    def need(params, what, ids):
+        if params is None:
+            raise KeyError("no %s parameters for atoms %s (types %s)" % (what, ids, tuple(types[a] for a in ids)))
+        return params
+
+    kb, kt = energy_unit / length_unit ** 2, energy_unit
+    bp = [(k / kb, r0 / length_unit) for i, j in bl for k, r0 in need(table.bond(types[i], types[j]), "bond", (i, j))]
+    ap = [(k / kt, th) for i, j, k_ in angles for k, th in need(table.angle(types[i], types[j], types[k_]), "angle", (i, j, k_))]
+    ta, tp = [], []
+    for q in tors:
+        for k, per, ph in need(table.proper(*(types[a] for a in q)), "proper torsion", q):
+            ta.append(q); tp.append((k / kt, per, ph))
+    # bond distances up to 3 from every atom (ring atoms reached by two paths count once, at their shortest distance)
+    excl, p14 = set(), set()
+    for s in range(n):
+        dist = {s: 0}
+        todo = deque([s])
+        while todo:
+            a = todo.popleft()
+            if dist[a] == 3:
+                continue
+            for b in nb[a]:
+                if b not in dist:
+                    dist[b] = dist[a] + 1
+                    todo.append(b)
+        for t, d in dist.items():
+            if t > s and d in (1, 2):
+                excl.add((s, t))
+            elif t > s and d == 3:
+                p14.add((s, t))
+    arr = lambda v, m, dt=np.int64: np.array(sorted(v) if isinstance(v, set) else v, dtype=dt).reshape(-1, m)
+    return dict(bonds=arr(bl, 2), bond_params=arr(bp, 2, np.float64), angles=arr(angles, 3), angle_params=arr(ap, 2, np.float64),
+                torsions=arr(ta, 4), torsion_params=arr(tp, 3, np.float64), exclusions=arr(excl, 2), pairs14=arr(p14, 2))
 
 
 def save_checkpoint(path, positions, velocities, step, box_length):

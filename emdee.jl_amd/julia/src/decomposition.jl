@@ -92,6 +92,13 @@ set_pairs14!(dd::DomainDecomposition, pairs::Union{Nothing,HipArray{Int64,2}}, l
     check(ccall((:emdee_dd_set_pairs14, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64), dd.handle,
                 pairs === nothing ? C_NULL : pairs.ptr, pairs === nothing ? 0 : size(pairs, 2), Float64(lj14scale)))
 
+# int32_t emdee_dd_set_bonded(emdee_dd *dd, int32_t kind, const int64_t *atoms_dev, const double *params_dev, int64_t n_terms);
+# As set_bonded! of a VelocityVerlet, over 0-based GLOBAL ids (Int64); collective, before load! or between step! calls.
+set_bonded!(dd::DomainDecomposition, kind, atoms::Union{Nothing,HipArray{Int64,2}}, params::Union{Nothing,HipArray{Float64,2}}) =
+    check(ccall((:emdee_dd_set_bonded, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int64), dd.handle,
+                Int32(kind), atoms === nothing ? C_NULL : atoms.ptr, params === nothing ? C_NULL : params.ptr,
+                atoms === nothing ? 0 : size(atoms, 2)))
+
 # int32_t emdee_dd_set_overlap(emdee_dd *dd, int32_t overlap);
 # true (default): interior bricks overlap the halo exchange; false: exchange and one launch over all bricks in order
 set_overlap!(dd::DomainDecomposition, on::Bool) =

@@ -48,6 +48,16 @@ set_pairs14!(md::VelocityVerlet, pairs::Union{Nothing,HipArray{Int32,2}}, lj14sc
     check(ccall((:emdee_md_set_pairs14, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64), md.handle,
                 pairs === nothing ? C_NULL : pairs.ptr, pairs === nothing ? 0 : size(pairs, 2), Float64(lj14scale)))
 
+# int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev, const double *params_dev, int32_t n_terms);
+# kind: HARMONIC_BOND (1), HARMONIC_ANGLE (2) or PERIODIC_TORSION (3); atoms: 2|3|4 x n device matrix of 0-based atom
+# indices, params: 2|2|3 x n Float64 device matrix ({k, r0}, {k, theta0}, {k, n, phase}); after the state is loaded;
+# `nothing` clears the kind's table.
+const HARMONIC_BOND, HARMONIC_ANGLE, PERIODIC_TORSION = Int32(1), Int32(2), Int32(3)
+set_bonded!(md::VelocityVerlet, kind, atoms::Union{Nothing,HipArray{Int32,2}}, params::Union{Nothing,HipArray{Float64,2}}) =
+    check(ccall((:emdee_md_set_bonded, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
+                Int32(kind), atoms === nothing ? C_NULL : atoms.ptr, params === nothing ? C_NULL : params.ptr,
+                atoms === nothing ? 0 : size(atoms, 2)))
+
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);
 # Atom ids keying the thermostat's noise (device Int64 vector in caller order); `nothing` = the caller index.
 set_langevin_ids!(md::VelocityVerlet, ids::Union{Nothing,HipArray{Int64,1}}) =

@@ -124,3 +124,47 @@ def mixture_parameters(types, eps=(1.0, 0.5), sigma=(1.0, 0.88)):
     eps = np.asarray(eps, dtype=np.float64)[types]
     sigma = np.asarray(sigma, dtype=np.float64)[types]
     return eps, sigma
+
+
+WATER_SPACING = 0.3104       # nm: one molecule per cube of this side is liquid water's 33.4 molecules / nm^3
+
+
+def water_box(n, xml_file=None, seed=SEED):
+    """n^3 water molecules from the HOH template of a force-field file (default: the committed dibenzo-p-dioxin-in-water.xml)
+    on a simple cubic lattice of WATER_SPACING nm, each O at a site with its two H at the bond length and angle of the file's
+    tables, in a seeded random orientation per molecule.  nm, kJ/mol and real masses.  Returns a dict: positions (3 n^3, 3)
+    wrapped into [0, L), L, types, atoms (LJAtom array), inv_mass (per atom, mol / g), and topology(): bonds, bond_params,
+    angles, angle_params, exclusions (1-2 and 1-3)."""
+    import os
+
+    from . import ingest
+    if xml_file is None:
+        xml_file = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
+                                "dibenzo-p-dioxin-in-water.xml")
+    table, templates = ingest.BondedTable(xml_file), ingest.ResidueTemplates(xml_file)
+    hoh = templates.residues["HOH"]
+    o = hoh["types"].index("OW")
+    h = [k for k in range(3) if k != o]
+    r0 = table.bond("OW", "HW")[0][1]
+    theta0 = table.angle("HW", "OW", "HW")[0][1]
+    m = n ** 3
+    one = ingest.topology(hoh["types"], np.array(hoh["bonds"]), table)        # one molecule, repeated with an offset of 3
+    tile = lambda a: (a[None, :, :] + 3 * np.arange(m)[:, None, None]).reshape(-1, a.shape[1])
+    top = dict(bonds=tile(one["bonds"]), angles=tile(one["angles"]), exclusions=tile(one["exclusions"]),
+               bond_params=np.tile(one["bond_params"], (m, 1)), angle_params=np.tile(one["angle_params"], (m, 1)))
+    types = hoh["types"] * m
+    L = n * WATER_SPACING
+    g = np.arange(n) * WATER_SPACING + 0.5 * WATER_SPACING
+    sites = np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3)
+    # the molecule in its own frame (O at the origin, H in the xy plane), then a random rotation (QR of a normal matrix)
+    local = np.zeros((3, 3))
+    local[h[0]] = r0 * np.array([np.cos(theta0 / 2), np.sin(theta0 / 2), 0.0])
+    local[h[1]] = r0 * np.array([np.cos(theta0 / 2), -np.sin(theta0 / 2), 0.0])
+    q, r = np.linalg.qr(np.random.default_rng(seed).standard_normal((m, 3, 3)))
+    q *= np.sign(np.diagonal(r, axis1=1, axis2=2))[:, None, :]
+    pos = (sites[:, None, :] + np.einsum("ad,mcd->mac", local, q)).reshape(-1, 3)
+    nbt = ingest.NonbondedTable(xml_file)
+    inv_mass = 1.0 / np.array([table.masses[t] for t in types])
+    return dict(positions=np.mod(pos, L), L=L, types=types, atoms=nbt.lj_atoms(types), inv_mass=inv_mass,
+                bonds=top["bonds"], bond_params=top["bond_params"], angles=top["angles"], angle_params=top["angle_params"],
+                exclusions=top["exclusions"])

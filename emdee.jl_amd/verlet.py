@@ -8,6 +8,21 @@ from . import _lib
 from .device import check_array, context_for, precision_of
 from .nonbonded import ENERGIES, FORCES, VIRIALS, check_tensor_out, tensor_matrix
 
+HARMONIC_BOND, HARMONIC_ANGLE, PERIODIC_TORSION = 1, 2, 3
+_BONDED_SHAPE = {HARMONIC_BOND: (2, 2), HARMONIC_ANGLE: (3, 2), PERIODIC_TORSION: (4, 3)}
+
+
+def bonded_arrays(kind, atoms, params, device, id_dtype):
+    """(atoms, params) of one bonded kind as contiguous device tensors (ids of id_dtype, parameters float64).  An unknown kind
+    keeps 2 ids and 2 parameters per term, so that the library is the one to refuse it."""
+    na, npar = _BONDED_SHAPE.get(int(kind), (2, 2))
+    a = torch.as_tensor(atoms if atoms is not None else []).reshape(-1, na).to(device=device, dtype=id_dtype).contiguous()
+    p = torch.as_tensor(params if params is not None else [], dtype=torch.float64).reshape(-1, npar).to(device=device).contiguous()
+    if a.shape[0] != p.shape[0]:
+        raise ValueError("set_bonded_: %d terms but %d parameter rows" % (a.shape[0], p.shape[0]))
+    return a, p
+
+
 KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick": 3, "lj_force_nbr_fused_step": 4,
            # decomposed steps: the fused launches over interior bricks (or all bricks, in-order form), over boundary bricks, and the
            # halo (pack -> exchange -> unpack) on the stream it runs on
@@ -210,6 +225,13 @@ class VelocityVerlet:
     def set_pairs14_(self, pairs, lj14scale):
         t = torch.as_tensor(pairs if pairs is not None else []).reshape(-1, 2).to(device=self.device, dtype=torch.int32).contiguous()
         _lib.call("emdee_md_set_pairs14", self._handle, C.c_void_p(t.data_ptr()) if t.numel() else None, int(t.shape[0]), float(lj14scale))
+
+    def set_bonded_(self, kind, atoms, params):
+        """Bonded terms of one kind (HARMONIC_BOND, HARMONIC_ANGLE, PERIODIC_TORSION; include/emdee_hip.h emdee_md_set_bonded):
+        atoms (n, 2 | 3 | 4) caller ids, params (n, 2 | 2 | 3).  Replaces that kind's table; an empty one clears it."""
+        a, p = bonded_arrays(kind, atoms, params, self.device, torch.int32)
+        _lib.call("emdee_md_set_bonded", self._handle, int(kind), C.c_void_p(a.data_ptr()) if a.numel() else None,
+                  C.c_void_p(p.data_ptr()) if p.numel() else None, int(a.shape[0]))
 
     def close(self):
         if self._handle is not None:

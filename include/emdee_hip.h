@@ -172,6 +172,36 @@ int32_t emdee_nbr_set_pairs14(emdee_nbr *nbr, const int32_t *pairs_dev, int32_t 
 int32_t emdee_md_set_exclusions(emdee_md *md, const int32_t *pairs_dev, int32_t n_pairs);
 int32_t emdee_md_set_pairs14(emdee_md *md, const int32_t *pairs_dev, int32_t n_pairs, double lj14scale);
 
+/* Bonded terms (the HarmonicBondForce, HarmonicAngleForce and PeriodicTorsionForce of an OpenMM force-field file, as the
+ * reference's src/modelling.jl reads them).  kind, the ids of each term (atoms_dev, device, copied) and its fp64 parameters
+ * (params_dev, device, copied):
+ *   EMDEE_HARMONIC_BOND     i, j        {k, r0}            U = k/2 (r - r0)^2
+ *   EMDEE_HARMONIC_ANGLE    i, j, k     {k, theta0}        U = k/2 (theta - theta0)^2, j the vertex, theta0 in radians
+ *   EMDEE_PERIODIC_TORSION  i, j, k, l  {k, n, phase}      U = k (1 + cos(n phi - phase)), phi the IUPAC dihedral (trans = pi),
+ *                                                          n an integer >= 1; a quadruple may appear once per (k, n, phase)
+ * Vectors inside a term are chained minimum images along its bonds (r_j - r_i, then r_k - r_j, r_l - r_k): a term that crosses
+ * the periodic boundary is unwrapped.  Owner computes: every atom of a term receives -grad U with respect to itself and 1/2,
+ * 1/3 or 1/4 of the term's energy, of its virial W = sum_a x_a . F_a (x_a unwrapped; a bond gives -r dU/dr) and of its
+ * symmetrised tensor sum_a x_a (x) F_a; the energies, virials, tensors and sums of emdee_md_* / emdee_dd_* include them.
+ * Bonded terms do not change the pair set: exclusions and 1-4 pairs stay the caller's tables.
+ *   - emdee_md_set_bonded: caller ids in [0, N), after emdee_md_set_state, undivided boxes.  emdee_dd_set_bonded: global ids
+ *     in [0, 2^31), collective, before emdee_dd_load or between steps (after a load it rebuilds every domain).
+ *   - Each call replaces the table of its kind; n_terms = 0 clears it.  All or nothing: EMDEE_ERR_INVALID, the previous tables
+ *     in force, for an unknown kind, a NULL array with n_terms > 0, an atom named twice in a term, an id out of range, a
+ *     non-finite parameter, r0 < 0, theta0 outside [0, pi], or n not an integer >= 1.  An integrator lent by emdee_dd_engine
+ *     refuses emdee_md_set_bonded with EMDEE_ERR_STATE.
+ *   - The partners are found through the neighbour rows: the filter that runs right after every build records where each one
+ *     sits, so the terms are exact between builds whatever rebuild_every is.  A partner that is not in its owner's rows at a
+ *     build (the term spans more than rc + skin) is an error: EMDEE_ERR_STATE naming the term, from the set call or at the
+ *     latest from the next emdee_*_step / _energies / _pressure_tensor (no extra read-back inside a batch of steps), and the
+ *     engine refuses to step until the tables or the state are replaced.
+ *   - An engine with bonded terms steps in the split form (force pass, 1-4 and bonded terms, kick + drift) and keeps the
+ *     general-species kernels. */
+#define EMDEE_HARMONIC_BOND     1
+#define EMDEE_HARMONIC_ANGLE    2
+#define EMDEE_PERIODIC_TORSION  3
+int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev, const double *params_dev, int32_t n_terms);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -387,6 +417,10 @@ int32_t emdee_dd_set_overlap(emdee_dd *dd, int32_t overlap);
  * general-species kernels.  emdee_md_set_exclusions / _set_pairs14 on an integrator of emdee_dd_engine return EMDEE_ERR_STATE. */
 int32_t emdee_dd_set_exclusions(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs);
 int32_t emdee_dd_set_pairs14(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_pairs, double lj14scale);
+/* Bonded terms of a decomposed run over GLOBAL ids (int64, 2, 3 or 4 per term): see emdee_md_set_bonded.  Collective; the
+ * domains of a process share one copy; a missing partner is reported on every rank (EMDEE_ERR_STATE), and every rank then
+ * refuses emdee_dd_step until the tables or the state are replaced. */
+int32_t emdee_dd_set_bonded(emdee_dd *dd, int32_t kind, const int64_t *atoms_dev, const double *params_dev, int64_t n_terms);
 
 #ifdef __cplusplus
 }
