@@ -63,6 +63,7 @@ SIGNATURES = {
     "emdee_md_set_exclusions": [_p, _p, _i32],
     "emdee_md_set_pairs14": [_p, _p, _i32, _dbl],
     "emdee_md_set_bonded": [_p, _i32, _p, _p, _i32],
+    "emdee_md_set_coulomb": [_p, _p, _i32, _dbl, _dbl, _dbl],
     "emdee_nbr_list": [_p, _p, _p, _i32],
     "emdee_md_nbr_list": [_p, _p, _p, _i32],
     "emdee_compute_nonbonded": [_p, _p, _p, _p, _p, _dbl, _p, LJModelC, _p, _i32, _i32],
@@ -113,6 +114,7 @@ SIGNATURES = {
     "emdee_dd_set_exclusions": [_p, _p, _i64],
     "emdee_dd_set_pairs14": [_p, _p, _i64, _dbl],
     "emdee_dd_set_bonded": [_p, _i32, _p, _p, _i64],
+    "emdee_dd_set_coulomb": [_p, _p, _i64, _dbl, _dbl, _dbl],
     "emdee_last_error": [],
 }
 _RESTYPES = {"emdee_last_error": C.c_char_p}

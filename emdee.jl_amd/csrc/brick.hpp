@@ -157,6 +157,8 @@ struct BrickArgs {
                                // into the box, and x - L rounded to fp32 is not the number the reference divides by L
     // tensor pass (BITMASK & EMDEE_TENSOR): six pitch-strided planes (xx, yy, zz, xy, xz, yz), or the caller's 6 x N array
     real *vt, *user_vt;
+    // charged engines (BITMASK & EMDEE_CHARGED instances only): sqrt(K) q per cell-order slot and the reaction-field constants
+    Charges<real> chg;
 };
 
 // ---- cell-relative records: tile coordinates (kernels.hpp RelGrid) ---------------------------------
@@ -221,12 +223,14 @@ static inline size_t brick_force_lds_bytes_soa(int own_cap) {
     return (((size_t)3 * soa_pitch<real>() * sizeof(real) + 15) & ~(size_t)15) + BrickTables<Shape, THREADS>::bytes(own_cap);
 }
 
-// bytes of dynamic LDS: force tile = HBM records (+ te plane for fp32); build tile = float4
+// bytes of dynamic LDS: force tile = HBM records (+ te plane for fp32) (+ charge plane: charged instances); build tile = float4
+template <typename real>
+__host__ __device__ inline size_t brick_charge_lds_bytes(int tile_cap) { return ((size_t)tile_cap * sizeof(real) + 15) & ~(size_t)15; }
 template <typename real, class Shape, int THREADS>
-static inline size_t brick_force_lds_bytes(int tile_cap, int own_cap) {
+static inline size_t brick_force_lds_bytes(int tile_cap, int own_cap, bool charged = false) {
     size_t tile_bytes = (size_t)tile_cap * sizeof(Rec<real>);
     size_t te_bytes = sizeof(real) == 4 ? (((size_t)tile_cap * 4 + 15) & ~(size_t)15) : 0;
-    return tile_bytes + te_bytes + BrickTables<Shape, THREADS>::bytes(own_cap);
+    return tile_bytes + te_bytes + (charged ? brick_charge_lds_bytes<real>(tile_cap) : 0) + BrickTables<Shape, THREADS>::bytes(own_cap);
 }
 template <class Shape, int THREADS>
 static inline size_t brick_build_lds_bytes(int tile_cap, int own_cap, int stride, int G, int nsub = 1) {
@@ -949,8 +953,14 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
 }
 
 // ------------------------------------------------------------------------------------ force / stats
-template <typename real, class Shape, int THREADS, int G, int MODE, int BITMASK, bool UNI = false>
+// BITMASK_Q: the outputs (EMDEE_FORCES | ENERGIES | VIRIALS | TENSOR), plus EMDEE_CHARGED for the instances of charged engines
+// (general species, force launches only): the sqrt(K) q of every tile slot is staged next to the tile and each pair inside rc
+// adds the reaction-field terms (lj_pair.hpp rf_pair) to its LJ terms.
+template <typename real, class Shape, int THREADS, int G, int MODE, int BITMASK_Q, bool UNI = false>
 __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
+    constexpr int BITMASK = BITMASK_Q & ~EMDEE_CHARGED;
+    constexpr bool CHG = (BITMASK_Q & EMDEE_CHARGED) != 0;
+    static_assert(!CHG || (!UNI && MODE == BRICK_FORCE), "charged instances: general-species force launches only");
     constexpr int NGROUPS = (THREADS / WAVE) * (WAVE / G);
     constexpr int BLK = EPL * G;
 
@@ -966,8 +976,10 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
     const size_t tile_bytes = SOA ? (((size_t)3 * PITCH * sizeof(real) + 15) & ~(size_t)15) : (size_t)a.tile_cap * sizeof(Rec<real>);
     const size_t te_bytes = (sizeof(real) == 4 && !SOA) ? (((size_t)a.tile_cap * 4 + 15) & ~(size_t)15) : 0;
     float *tile_te = reinterpret_cast<float *>(s_dyn + tile_bytes);   // fp32 only
+    const size_t q_bytes = CHG ? brick_charge_lds_bytes<real>(a.tile_cap) : 0;
+    real *tile_q = reinterpret_cast<real *>(s_dyn + tile_bytes + te_bytes);   // charged instances only
     BrickTables<Shape, THREADS> T;
-    T.carve(s_dyn + tile_bytes + te_bytes);
+    T.carve(s_dyn + tile_bytes + te_bytes + q_bytes);
     if (MODE == BRICK_STEP && a.guard != nullptr && *a.guard != 0) {
         // The host queued this step before it could know that the previous one moved an atom past skin/2:
         // the list is stale, so this launch (and, through the propagated flag, every later one of the
@@ -1033,6 +1045,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         if (SOA) { plane[s] = r.x; plane[PITCH + s] = r.y; plane[2 * PITCH + s] = r.z; }
         else tile[s] = r;
         if (sizeof(real) == 4 && !SOA) tile_te[s] = a.te[gp];
+        if (CHG) tile_q[s] = a.chg.q[gp];
     });
     if (tid == 0) {   // the sentinel record every unused row entry points at: fails r2 < rc2, never NaN
         Rec<real> far;
@@ -1042,6 +1055,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         if (SOA) { plane[0] = big; plane[PITCH] = big; plane[2 * PITCH] = big; }
         else tile[0] = far;
         if (sizeof(real) == 4 && !SOA) tile_te[0] = 0.f;
+        if (CHG) tile_q[0] = (real)0;
     }
 #pragma unroll
     for (int k = 0; k < OWN_REGS; k++) {
@@ -1100,6 +1114,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
         real xi, yi, zi, hs_i, te_i;
         if (SOA) { xi = plane[ti]; yi = plane[PITCH + ti]; zi = plane[2 * PITCH + ti]; hs_i = te_i = 0; }
         else tile_load<real>(tile, tile_te, ti, xi, yi, zi, hs_i, te_i);
+        const real q_i = CHG ? tile_q[ti] : (real)0;
         real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
         real txx = 0, tyy = 0, tzz = 0, txy = 0, txz = 0, tyz = 0;   // (tensor pass only)
         real vx = 0, vy = 0, vz = 0, bx = 0, by = 0, bz = 0, imv = 1, nx = 0, ny = 0, nz = 0;
@@ -1228,6 +1243,7 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                                 const real sg = hs_i + hs_j;
                                 wr2 = lj_force_over_r2(r2, inv_r2, mdl, sg * sg, te_i * te_j);
                             }
+                            if (CHG) wr2 += rf_force_over_r2(r2, inv_r2, q_i * tile_q[sj], a.chg);
                             fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
                         } else {
                             real E, W;
@@ -1235,6 +1251,11 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                                 lj_interaction_pair(r2, inv_r2, mdl, a.uni_sigma2, a.uni_e4, E, W);
                             } else {
                                 lj_interaction(r2, inv_r2, mdl, hs_i, te_i, hs_j, te_j, E, W);
+                            }
+                            if (CHG) {
+                                real Ec, Wc;
+                                rf_pair(r2, q_i * tile_q[sj], a.chg, Ec, Wc);
+                                E += Ec; W += Wc;
                             }
                             if (BITMASK & EMDEE_FORCES) {
                                 const real wr2 = W * inv_r2;      // src/nonbonded.jl:139

@@ -266,6 +266,9 @@ int32_t emdee_md_set_pairs14(emdee_md *md, const int32_t *pairs_dev, int32_t n_p
 int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev, const double *params_dev, int32_t n_terms) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_bonded(kind, atoms_dev, params_dev, n_terms); });
 }
+int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_coulomb(charges_dev, n, coulomb_k, eps_rf, coulomb14scale); });
+}
 
 int32_t emdee_compute_nonbonded(emdee_ctx *ctx, void *forces_dev, void *energies_dev, void *virials_dev,
                                 const void *positions_dev, double L, emdee_nbr *nbr, emdee_lj_model model,
@@ -555,6 +558,10 @@ int32_t emdee_dd_set_pairs14(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_p
 }
 int32_t emdee_dd_set_bonded(emdee_dd *dd, int32_t kind, const int64_t *atoms_dev, const double *params_dev, int64_t n_terms) {
     return guarded([&] { REQUIRE_PTR(dd, "dd"); dd->impl->set_bonded(kind, atoms_dev, params_dev, n_terms); });
+}
+int32_t emdee_dd_set_coulomb(emdee_dd *dd, const double *charges_dev, int64_t n_ids, double coulomb_k, double eps_rf,
+                             double coulomb14scale) {
+    return guarded([&] { REQUIRE_PTR(dd, "dd"); dd->impl->set_coulomb(charges_dev, n_ids, coulomb_k, eps_rf, coulomb14scale); });
 }
 
 }  // extern "C"

@@ -23,6 +23,9 @@ namespace emdee {
 // the forces alone: the integrator keeps the bits of its own force-only kernels, so a sample does not move a trajectory.
 constexpr int EMDEE_TENSOR = 8;
 constexpr int TENSOR_PASS = EMDEE_ENERGIES | EMDEE_VIRIALS | EMDEE_TENSOR;
+// ---- internal template bit of the force kernels (brick.hpp k_brick): the instance adds the reaction-field Coulomb terms of a
+// charged engine (lj_pair.hpp Charges).  Never part of a public bitmask; instances without it are the uncharged kernels.
+constexpr int EMDEE_CHARGED = 64;
 
 // ---- error plumbing: no exception crosses the C ABI -------------------------------------------
 void set_error(const char *fmt, ...);

@@ -532,6 +532,7 @@ struct DdImpl : IDd {
         use_device(user_ctx);
         for (auto &d : dom) d->sys().uniform_known = -1;
         for (auto &d : dom) d->sys().reset_bonded_error();   // (a new state: the bonded terms get another chance)
+        for (auto &d : dom) d->sys().reset_charge_error();
         redistribute(false);
         agree_on_species();
         if (n_global == 0) {
@@ -542,6 +543,7 @@ struct DdImpl : IDd {
             n_global = (int64_t)(tot + 0.5);
         }
         loaded = true;
+        check_charges();                                     // (collective: an id without a charge is refused on every rank)
     }
 
     // stable partition of items 0..n-1 by mask bits into nbins bins: counts and scanned offsets (device), starts and
@@ -576,7 +578,7 @@ struct DdImpl : IDd {
             d->sys().species_known.n = 1;
             if (uni) d->sys().set_uniform_constants(emdee_lj_atom{unbits(sum[2] / voters), unbits(sum[3] / voters)});
         }
-        if (uni || voters == 0 || has_tables()) return;      // (typed rows are not filtered: a box with pair tables keeps the general kernels)
+        if (uni || voters == 0 || has_tables() || tables.has_charges) return;      // (typed rows are not filtered: a box with pair tables keeps the general kernels)
         // Two species everywhere?  Then every engine sorts by (cell, species) and takes the typed kernels where they pay
         // (typed.hpp).  Every domain with atoms must have found the same two LJAtom bit patterns (an empty one has no opinion).
         auto half = [](unsigned long long k, int h) { return (double)(unsigned)(h ? (k >> 32) : (k & 0xffffffffull)); };
@@ -1270,6 +1272,44 @@ struct DdImpl : IDd {
         EMDEE_HIP_CHECK(hipGetLastError());
         check_bonded();
     }
+    // Collective.  The charges over global ids (nbsys.hpp PairTables::set_charges), as set_pair_table: all or nothing, and after a
+    // load every domain is loaded again (its charge plane is filled by tag), so the forces include them on return.  A domain atom
+    // whose id has no charge is reported on every rank (check_charges).
+    void set_coulomb(const double *charges, int64_t n, double coulomb_k, double eps_rf, double coulomb14scale) override {
+        use_device(user_ctx);
+        join_halo();
+        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+        tables.set_charges(charges, n, coulomb_k, eps_rf, coulomb14scale, -1, user_ctx->stream);
+        for (auto &pd : dom) pd->sys().reset_charge_error();
+        if (!loaded) return;
+        for (auto &pd : dom) {
+            Domain<real> &d = *pd;
+            export_caller_arrays(d, d.ids.ptr, d.n_send);
+            load_engine(d, true);
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+        check_charges();
+    }
+    // Collective and blocking: EMDEE_ERR_STATE on every rank if an atom of a domain has an id outside the charge table
+    // (NbSystem::check_charges); every domain then refuses to step until the charges are set again
+    void check_charges() {
+        if (!tables.has_charges) return;
+        join_halo();
+        std::vector<std::vector<double>> bad;
+        bool mine = false;
+        for (auto &pd : dom) {
+            double b = 0.0;
+            try { pd->sys().ensure_charges(); pd->sys().check_charges(); } catch (const Failure &) { b = 1.0; mine = true; }
+            bad.push_back({b});
+        }
+        double total = 0.0;
+        allreduce_sum(bad, 1, &total);
+        if (total > 0.0) {
+            for (auto &pd : dom) pd->sys().charge_broken = true;
+            if (!mine) set_error("an atom of another domain has an id outside the charge table: set the charges again");
+            throw Failure{EMDEE_ERR_STATE};
+        }
+    }
     // Collective and blocking: EMDEE_ERR_STATE on every rank if a domain's bonded term has lost a partner (NbSystem::check_bonded;
     // the message names the term on the rank that holds it)
     void check_bonded() {
@@ -1363,6 +1403,8 @@ struct DdImpl : IDd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0 && rebuild_every >= 0, EMDEE_ERR_INVALID, "emdee_dd_step: negative argument");
         for (auto &pd : dom)
             EMDEE_REQUIRE(!pd->sys().bonded_broken, EMDEE_ERR_STATE, "emdee_dd_step: a bonded term has lost a partner; replace the tables or the state");
+        for (auto &pd : dom)
+            EMDEE_REQUIRE(!pd->sys().charge_broken, EMDEE_ERR_STATE, "emdee_dd_step: an atom has an id outside the charge table; set the charges again");
         if (nsteps == 0) return;
         // Which kernels a domain steps with is ITS business and may change at any rebuild (brick_active: the densest tile of
         // this domain fits LDS or not; an empty domain launches nothing): the batches, their exchanges and the guard words

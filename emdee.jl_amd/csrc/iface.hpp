@@ -53,6 +53,7 @@ struct IMd {
     virtual void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) = 0;
     virtual void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) = 0;
     virtual void set_bonded(int32_t kind, const int32_t *atoms, const double *params, int32_t n_terms) = 0;
+    virtual void set_coulomb(const double *charges, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) = 0;
 };
 
 // spatial domain decomposition (emdee_dd_*): the domains of the decomposition that live in this process
@@ -75,6 +76,7 @@ struct IDd {
     virtual void set_overlap(bool on) = 0;
     virtual void set_pair_table(const int64_t *pairs, int64_t n_pairs, bool one_four, double lj14scale) = 0;
     virtual void set_bonded(int32_t kind, const int64_t *atoms, const double *params, int64_t n_terms) = 0;
+    virtual void set_coulomb(const double *charges, int64_t n_ids, double coulomb_k, double eps_rf, double coulomb14scale) = 0;
 };
 
 void dd_rccl_selftest(emdee_ctx *ctx, int n_bytes);

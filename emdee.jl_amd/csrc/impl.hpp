@@ -196,7 +196,9 @@ struct MdImpl : IMd {
         if (!lent) sys.reset_bonded_error();                 // (a new state: the bonded terms get another chance; a decomposition resets its own)
         since_build = 0;
         current_mask = 0;
-        if (!defer_forces) {
+        // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
+        // cleared -- NbSystem::ensure_charges)
+        if (!defer_forces && !sys.charges_stale()) {
             sys.compute_forces(EMDEE_FORCES);
             current_mask = EMDEE_FORCES;
         }
@@ -215,6 +217,10 @@ struct MdImpl : IMd {
     void get_state(void *pos, void *vel, void *frc, void *en, void *vir) override {
         use_device(sys.ctx);
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
+        // (charges set for another atom count: the state's forces were never evaluated -- refused, as a step is)
+        EMDEE_REQUIRE(!((frc || en || vir) && sys.charges_stale()), EMDEE_ERR_STATE, "md: charges set for %lld atoms, the state "
+                      "holds %d: set them again or clear them (emdee_md_set_coulomb) before reading forces, energies or virials",
+                      (long long)sys.tables->q_n, sys.n_owned);
         if ((en || vir) && (current_mask & 6) != 6) forces(7, 0);
         sys.ids_map();                                       // (scratch of the engine's own: before the fence)
         FenceOut fence(caller_ctx, sys.stream());
@@ -419,6 +425,19 @@ struct MdImpl : IMd {
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.check_bonded();
+    }
+    void set_coulomb(const double *charges, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "charges of a decomposed run: emdee_dd_set_coulomb (this integrator is a domain's, lent by emdee_dd_engine)");
+        EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "charges: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
+        sys.own_tables.set_charges(charges, n, coulomb_k, eps_rf, coulomb14scale, sys.n_owned, sys.stream());
+        sys.reset_charge_error();
+        sys.has_list = false; sys.plan_valid = false;
+        sys.resort();                                        // (charged and uncharged engines take different kernels and LDS plans)
+        since_build = 0;
+        sys.compute_forces(EMDEE_FORCES);
+        current_mask = EMDEE_FORCES;
+        EMDEE_HIP_CHECK(hipGetLastError());
     }
     void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) override {
         use_device(sys.ctx);

@@ -817,15 +817,14 @@ constexpr int FORCE_BLOCK = 256;
 constexpr int FORCE_ATOMS = 64;
 constexpr int NXCD = 8;
 
-template <typename real, int BITMASK>
-__global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned, int nblocks_per_xcd,
-                                                              AtomView<real> atoms, const int *__restrict__ perm,
-                                                              const int *__restrict__ nbr, int stride,
-                                                              const int *__restrict__ cnt, GridP<real> g,
-                                                              LJModel<real> model, size_t pitch,
-                                                              real *__restrict__ frc, real *__restrict__ en,
-                                                              real *__restrict__ vir, const int *__restrict__ guard = nullptr,
-                                                              real *__restrict__ vt = nullptr) {
+// (the body of k_lj_force_nbr and of its charged twin k_lj_force_nbr_q: CHG adds the reaction-field terms, lj_pair.hpp rf_pair)
+template <typename real, int BITMASK, bool CHG>
+__device__ __forceinline__ void lj_force_nbr_body(int n, int n_owned, int nblocks_per_xcd, const AtomView<real> &atoms,
+                                                  const int *__restrict__ perm, const int *__restrict__ nbr, int stride,
+                                                  const int *__restrict__ cnt, const GridP<real> &g, const LJModel<real> &model,
+                                                  size_t pitch, real *__restrict__ frc, real *__restrict__ en,
+                                                  real *__restrict__ vir, const int *__restrict__ guard, real *__restrict__ vt,
+                                                  const Charges<real> &ch) {
     constexpr int NOUT = (BITMASK & EMDEE_TENSOR) ? 11 : 5;   // f, e, w (+ the six tensor components)
     __shared__ real s_out[NOUT][FORCE_ATOMS];
     if (guard != nullptr && *guard != 0) return;   // a step queued behind a rebuild request (emdee_dd_step): leave no trace
@@ -846,6 +845,7 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
         if (perm[p] < n_owned) {
             real xi, yi, zi, hs_i, te_i;
             load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
+            const real q_i = CHG ? ch.q[p] : (real)0;
             const int m = cnt[p];
             const int *row = nbr + (size_t)p * stride;
             for (int k = lane; k < m; k += WAVE) {
@@ -860,6 +860,11 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
                     const real inv_r2 = fast_rcp(r2);
                     real E, W;
                     lj_interaction(r2, inv_r2, model, hs_i, te_i, hs_j, te_j, E, W);
+                    if (CHG) {
+                        real Ec, Wc;
+                        rf_pair(r2, q_i * ch.q[j], ch, Ec, Wc);
+                        E += Ec; W += Wc;
+                    }
                     if (BITMASK & EMDEE_FORCES) {
                         const real wr2 = W * inv_r2;   // src/nonbonded.jl:139
                         fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
@@ -900,6 +905,32 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
         if (BITMASK & EMDEE_TENSOR)
             for (int c = plane; c < 6; c += FORCE_BLOCK / FORCE_ATOMS) vt[c * pitch + first + col] = s_out[(NOUT - 6) + c][col];
     }
+}
+template <typename real, int BITMASK>
+__global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned, int nblocks_per_xcd,
+                                                              AtomView<real> atoms, const int *__restrict__ perm,
+                                                              const int *__restrict__ nbr, int stride,
+                                                              const int *__restrict__ cnt, GridP<real> g,
+                                                              LJModel<real> model, size_t pitch,
+                                                              real *__restrict__ frc, real *__restrict__ en,
+                                                              real *__restrict__ vir, const int *__restrict__ guard = nullptr,
+                                                              real *__restrict__ vt = nullptr) {
+    lj_force_nbr_body<real, BITMASK, false>(n, n_owned, nblocks_per_xcd, atoms, perm, nbr, stride, cnt, g, model, pitch, frc, en,
+                                            vir, guard, vt, Charges<real>{});
+}
+// a charged engine's direct kernel: the same body with the reaction-field terms (its own name, so that the uncharged instances
+// keep their signatures and code)
+template <typename real, int BITMASK>
+__global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr_q(int n, int n_owned, int nblocks_per_xcd,
+                                                                AtomView<real> atoms, const int *__restrict__ perm,
+                                                                const int *__restrict__ nbr, int stride,
+                                                                const int *__restrict__ cnt, GridP<real> g,
+                                                                LJModel<real> model, size_t pitch,
+                                                                real *__restrict__ frc, real *__restrict__ en,
+                                                                real *__restrict__ vir, const int *__restrict__ guard,
+                                                                real *__restrict__ vt, Charges<real> ch) {
+    lj_force_nbr_body<real, BITMASK, true>(n, n_owned, nblocks_per_xcd, atoms, perm, nbr, stride, cnt, g, model, pitch, frc, en,
+                                           vir, guard, vt, ch);
 }
 
 // ------------------------------------------------------------------------------------ integrator
@@ -1228,11 +1259,13 @@ static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__
 // the cell-ordered arrays, or in the caller's arrays when the operator path had its results written there (user_*: caller
 // order).  A pair missing from the rows is beyond rc + skin at the build, so beyond rc while the list is valid.
 // (TENSOR: the tensor pass's instance; the force and observable passes keep the instance without the six sums)
-template <typename real, bool TENSOR = false>
-__global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
-                          GridP<real> g, LJModel<real> model, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
-                          real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
-                          real *__restrict__ vt = nullptr, real *__restrict__ user_vt = nullptr) {
+// (CHG: the body of k_pairs14_q, a charged engine's: the pair's reaction-field terms scaled by ch.scale14 on top)
+template <typename real, bool TENSOR, bool CHG>
+__device__ __forceinline__ void pairs14_body(int n, int n_owned, size_t pitch, const AtomView<real> &atoms, const int *__restrict__ perm,
+                                             const PairKeys &keys, const GridP<real> &g, const LJModel<real> &model, real scale,
+                                             int bitmask, real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir,
+                                             real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
+                                             real *__restrict__ vt, real *__restrict__ user_vt, const Charges<real> &ch) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const int i = perm[p];
@@ -1245,6 +1278,9 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
     load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
     real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
     real tv[6] = {0, 0, 0, 0, 0, 0};                           // (tensor pass: the scaled terms of the tensor, as of w)
+    const real q_i = CHG ? ch.q[p] : (real)0;
+    real cfx = 0, cfy = 0, cfz = 0, ce = 0, cw = 0;            // (charged: the reaction-field terms, scaled by ch.scale14)
+    real ctv[6] = {0, 0, 0, 0, 0, 0};
     for (int k = lo; k < hi; k++) {
         const int q = keys.s14[k];
         if (q < 0) continue;
@@ -1266,11 +1302,29 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
                 tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
                 tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
             }
+            if (CHG) {
+                real Ec, Wc;
+                rf_pair(r2, q_i * ch.q[q], ch, Ec, Wc);
+                const real cr2 = Wc * inv_r2;
+                cfx += cr2 * dx; cfy += cr2 * dy; cfz += cr2 * dz;
+                ce += Ec; cw += Wc;
+                if (TENSOR) {
+                    const real hx = cr2 * dx, hy = cr2 * dy, hz = cr2 * dz;
+                    ctv[0] += hx * dx; ctv[1] += hy * dy; ctv[2] += hz * dz;
+                    ctv[3] += hx * dy; ctv[4] += hx * dz; ctv[5] += hy * dz;
+                }
+            }
         }
     }
     fx *= scale; fy *= scale; fz *= scale;
     e *= (real)0.5 * scale; w *= (real)0.5 * scale;           // src/nonbonded.jl:142-145: half of a pair's E and W to either atom
     for (int c = 0; c < 6; c++) tv[c] *= (real)0.5 * scale;
+    if (CHG) {
+        const real sc = ch.scale14, hc = (real)0.5 * ch.scale14;
+        fx += sc * cfx; fy += sc * cfy; fz += sc * cfz;
+        e += hc * ce; w += hc * cw;
+        for (int c = 0; c < 6; c++) tv[c] += hc * ctv[c];
+    }
     if (user_f != nullptr || user_e != nullptr || user_w != nullptr || (TENSOR && user_vt != nullptr)) {
         if ((bitmask & EMDEE_FORCES) && user_f) { user_f[3 * (size_t)i] += fx; user_f[3 * (size_t)i + 1] += fy; user_f[3 * (size_t)i + 2] += fz; }
         if ((bitmask & EMDEE_ENERGIES) && user_e) user_e[i] += e;
@@ -1284,6 +1338,37 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
         if (TENSOR)
             for (int c = 0; c < 6; c++) vt[c * pitch + p] += tv[c];
     }
+}
+template <typename real, bool TENSOR = false>
+__global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
+                          GridP<real> g, LJModel<real> model, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
+                          real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
+                          real *__restrict__ vt = nullptr, real *__restrict__ user_vt = nullptr) {
+    pairs14_body<real, TENSOR, false>(n, n_owned, pitch, atoms, perm, keys, g, model, scale, bitmask, frc, en, vir, user_f, user_e,
+                                      user_w, vt, user_vt, Charges<real>{});
+}
+// a charged engine's 1-4 kernel (its own name: the uncharged instances keep their signatures and code)
+template <typename real, bool TENSOR>
+__global__ void k_pairs14_q(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
+                            GridP<real> g, LJModel<real> model, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
+                            real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
+                            real *__restrict__ vt, real *__restrict__ user_vt, Charges<real> ch) {
+    pairs14_body<real, TENSOR, true>(n, n_owned, pitch, atoms, perm, keys, g, model, scale, bitmask, frc, en, vir, user_f, user_e,
+                                     user_w, vt, user_vt, ch);
+}
+
+// The charge plane of a charged engine: sqrt(K) q of the atom in every cell-order slot, looked up by the key it carries (tag or
+// caller id, as PairKeys) in the table of n_tab keys.  A key outside the table leaves 0 in the slot and raises *err (the host
+// refuses to step: NbSystem::check_charges).
+template <typename real>
+__global__ void k_fill_charges(int n, const int *__restrict__ perm, const long long *__restrict__ tag, const double *__restrict__ tab,
+                               long long n_tab, real *__restrict__ q, int *__restrict__ err) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const long long key = tag ? tag[p] : (long long)perm[p];
+    const bool ok = key >= 0 && key < n_tab;
+    q[p] = ok ? (real)tab[key] : (real)0;
+    if (!ok) *err = 1;
 }
 
 // Bonded terms: owner-computes over the slots the row filter recorded at the last build -- no atomics, the row's order of

@@ -45,6 +45,40 @@ __device__ __forceinline__ double fast_rcp(double a) {
     return r;
 }
 
+// 1/sqrt(a) without the IEEE sqrt and division sequences.  fp32: v_rsq_f32 (1 ulp).  fp64: v_rsq_f64 seed + one Newton step
+// y (3 - a y^2) / 2 -> 4.0e-15 relative at most, 3.2e-16 rms (measured on gfx950 over 400,000 pair terms of the charged kernels,
+// profiles/coulomb_cost.py; fast_rcp: 2.2e-15)
+__device__ __forceinline__ float fast_rsq(float a) { return __builtin_amdgcn_rsqf(a); }
+__device__ __forceinline__ double fast_rsq(double a) {
+    double y = __builtin_amdgcn_rsq(a);
+    const double h = 0.5 * a * y;                                      // a y / 2
+    y = __builtin_fma(__builtin_fma(-h, y, 0.5), y, y);                // y + y (1/2 - a y^2 / 2)
+    return y;
+}
+
+// ---- reaction-field Coulomb (emdee_md_set_coulomb / emdee_dd_set_coulomb) ------------------------------------------------
+// The charged kernels read a plane of sqrt(K) q per cell-order slot (q), so that qq = K q_i q_j is one product.  Constants of
+// the reaction field: k = (eps_rf - 1) / ((2 eps_rf + 1) rc^3), k2 = 2 k, c = 1/rc + k rc^2; scale14 multiplies the 1-4 pairs.
+template <typename real>
+struct Charges {
+    const real *q;
+    real k, k2, c, scale14;
+};
+// U = qq (1/r + k r^2 - c),  W = -r dU/dr = qq (1/r - 2 k r^2).  CUTOFF semantics are the caller's test, as lj_interaction_pair.
+// The one formula of every charged path (force pass, direct kernels, 1-4 pairs).
+template <typename real>
+__device__ __forceinline__ void rf_pair(real r2, real qq, const Charges<real> &ch, real &E_out, real &W_out) {
+    const real inv_r = fast_rsq(r2);
+    E_out = qq * (inv_r + (ch.k * r2 - ch.c));
+    W_out = qq * (inv_r - ch.k2 * r2);
+}
+// force-only launches: W / r^2 = qq (1/r^3 - 2 k), from the caller's inv_r2
+template <typename real>
+__device__ __forceinline__ real rf_force_over_r2(real r2, real inv_r2, real qq, const Charges<real> &ch) {
+    const real inv_r = fast_rsq(r2);
+    return qq * (inv_r * inv_r2 - ch.k2);
+}
+
 // The reference clamp  x *= 0.5 (sign(x) - sign(x-1))  (src/lennard_jones.jl:37):
 // 0 < x < 1 -> x ;  x <= 0 -> 0 ;  x == 1 -> 0.5 (Q2) ;  x > 1 -> 0 (g = 1 beyond rc, Q1).
 // One max covers the common cases; x >= 1 is a rare, separately handled lane state.

@@ -311,6 +311,43 @@ struct PairTables {
         b_rows = r; limit = lim; nb = pi.size();
         has_bonded = !terms.empty();
     }
+
+    // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the
+    // reaction-field constants.  Every engine keeps a plane of them in its own cell order (NbSystem::qp).
+    DevBuf<double> q_tab;
+    int64_t q_n = 0;                                         // keys 0 .. q_n - 1 have a charge
+    double coulomb_k = 0.0, eps_rf = INFINITY, scale14c = 1.0;
+    bool has_charges = false;
+    // Replaces the charges by the n at charges_dev (device, fp64, one per key); n = 0 clears them.  want >= 0: the only
+    // non-zero n accepted (an undivided engine's atom count).  All or nothing, as set().
+    void set_charges(const double *charges_dev, int64_t n, double K, double eps, double s14, int64_t want, hipStream_t s) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || charges_dev), EMDEE_ERR_INVALID, "set_coulomb: negative count or NULL array");
+        if (n == 0) {                                        // (clearing needs no constants)
+            has_charges = false; q_n = 0;
+            return;
+        }
+        EMDEE_REQUIRE(want < 0 || n == want, EMDEE_ERR_INVALID, "set_coulomb: %lld charges for %lld atoms", (long long)n, (long long)want);
+        EMDEE_REQUIRE(n < ((int64_t)1 << 31), EMDEE_ERR_INVALID, "set_coulomb: %lld charges (at most 2^31 - 1)", (long long)n);
+        EMDEE_REQUIRE(std::isfinite(K) && K > 0.0, EMDEE_ERR_INVALID, "set_coulomb: the Coulomb constant must be finite and > 0");
+        EMDEE_REQUIRE(eps >= 1.0, EMDEE_ERR_INVALID, "set_coulomb: the reaction-field dielectric must be >= 1 (+inf allowed)");
+        EMDEE_REQUIRE(std::isfinite(s14) && s14 >= 0.0, EMDEE_ERR_INVALID, "set_coulomb: coulomb14scale must be finite and >= 0");
+        std::vector<double> h((size_t)n);
+        EMDEE_HIP_CHECK(hipMemcpyAsync(h.data(), charges_dev, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        const double sk = std::sqrt(K);
+        for (int64_t k = 0; k < n; k++) {
+            EMDEE_REQUIRE(std::isfinite(h[k]), EMDEE_ERR_INVALID, "set_coulomb: charge %lld is not finite", (long long)k);
+            h[k] *= sk;
+        }
+        DevBuf<double> nq;
+        nq.ensure(h.size() + 1);
+        EMDEE_HIP_CHECK(hipMemcpyAsync(nq.ptr, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        q_tab.swap(nq);
+        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14;
+        has_charges = true;
+    }
 };
 
 template <typename real>
@@ -593,6 +630,7 @@ struct NbSystem {
                                cell_sorted.ptr, img.ptr, digits(), use_tags ? tags_user : nullptr, use_tags ? tag.ptr : nullptr,
                                (int)ncell, digits() > 1 ? cstart.ptr : nullptr, count.ptr, rel_grid_next(rel_next, nullptr));
         rel_commit(rel_next);
+        q_valid = false;
         // ghosts are never written by the step kernel: both position buffers carry their records (LJAtom fields)
         // from the start; their coordinates are refreshed by every halo unpack
         if (has_ghosts)
@@ -627,6 +665,7 @@ struct NbSystem {
         build_list();
     }
     void swap_sorted_buffers() {
+        q_valid = false;                                     // (the charge plane is the previous order's)
         rec.swap(rec2); te.swap(te2); perm.swap(perm2); img.swap(img2); cell_sorted.swap(cell_sorted2);
         if (with_vel) vel.swap(vel2);
         if (with_mass) im.swap(im2);
@@ -753,6 +792,7 @@ struct NbSystem {
         a.user_f = out_f; a.user_e = out_e; a.user_w = out_w;
         a.vt = vt.ptr; a.user_vt = out_vt;
         a.noise = lgv_on ? noise.ptr : nullptr; a.lgv_c1 = lgv_on ? (real)lgv_c1 : (real)1;
+        a.chg = charge_args();
         return a;
     }
 
@@ -783,9 +823,20 @@ struct NbSystem {
         }
     }
 
+    // variants a general-species box reaches (0, and 8 for long rows) carry the charged force instances
+    template <class V>
+    static constexpr bool charged_variant() { return std::is_same<V, BrickVariant<0>>::value || std::is_same<V, BrickVariant<8>>::value; }
     template <class V, int MODE, int BM>
     void launch_brick_kernel() {
         if (typed_active) { launch_typed_kernel<V, MODE, BM>(); return; }
+        // charged engines: the general-species kernels with the reaction-field terms, whatever their LJ parameters
+        if constexpr (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)) {
+            if (has_charges()) {
+                if constexpr (charged_variant<V>()) launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED, false>();
+                else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "charged engine on brick variant %d", variant);
+                return;
+            }
+        }
         // single-species fast path for the kernels of the MD loop (default variant only)
         if constexpr (std::is_same<V, BrickVariant<0>>::value && (MODE == BRICK_STEP || (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)))) {
             // (the fp64 variant keeps coordinate planes only in LDS and needs the tile to fit their fixed pitch)
@@ -894,7 +945,7 @@ struct NbSystem {
                 constexpr size_t USABLE = 150000;
                 auto per_cu = [&](int tc) {
                     const size_t b = brick_build_lds_bytes<S, V::THREADS>(tc, own_cap, st, V::GB, nsub),
-                                 f = brick_force_lds_bytes<real, S, V::THREADS>(tc, own_cap);
+                                 f = brick_force_lds_bytes<real, S, V::THREADS>(tc, own_cap, has_charges());
                     return (int)(USABLE / std::max<size_t>(b, 1)) * 16 + (int)(USABLE / std::max<size_t>(f, 1));
                 };
                 while (tile_cap > exact && per_cu(tile_cap) < per_cu(exact)) tile_cap -= 16;
@@ -908,7 +959,7 @@ struct NbSystem {
             if (build_alg == 1 && (V::GB == 8 || V::GB == 16) && plan_span3 <= 32 * V::GB) build_alg = 5;
             if (build_alg == 1) plan_span3 = 1 << 30;               // the ballot build has no limit
             else plan_span3 = (build_alg == 5 ? 32 : BUILD2_FIELD) * V::GB;   // what the chosen build can take
-            lds_bytes = brick_force_lds_bytes<real, S, V::THREADS>(tile_cap, own_cap);
+            lds_bytes = brick_force_lds_bytes<real, S, V::THREADS>(tile_cap, own_cap, has_charges());
             ok = lds_bytes <= LDS_LIMIT && tile_cap < 65536;
             // fp32 pre-test of the build kernel (fp64 boxes): brick-relative coordinates are below
             // cmax, so each is off by <= cmax 2^-24 after rounding; with |d| <= r_list per component the
@@ -973,11 +1024,11 @@ struct NbSystem {
         // the build kernel's LDS (fp32 tile + tables + one row buffer per lane group) must fit as well: very dense or
         // very inhomogeneous boxes with a long cutoff fall back to the direct (global-gather) kernels
         if (brick_active && !build_fits_lds()) brick_active = false;
-        idx_shift = (brick_active && variant == 0 && uniform_atoms && tile_cap <= SOA_SLOTS) ? PLANE_SHIFT : 0;
+        idx_shift = (brick_active && variant == 0 && uniform_atoms && !has_charges() && tile_cap <= SOA_SLOTS) ? PLANE_SHIFT : 0;
         // two species: the typed kernels (typed.hpp), if the tile fits their coordinate planes, no three cells of a tile row hold
         // more atoms of one species than the 16-bit hit fields of their build take, and both kernels fit LDS
         typed_active = false;
-        if (brick_active && nt == 2 && !typed_blocked && !filters_rows()) {
+        if (brick_active && nt == 2 && !typed_blocked && !filters_rows() && !has_charges()) {
             // (where the general-species kernels take 1024 threads with 8 lanes per atom -- long cutoffs -- the typed ones take
             // 1024 threads with 4: rows are two block-aligned segments, and blocks of 32 entries pad them half as much as blocks of 64)
             // Measured (profiles/README.md, round 3): at rc = 3.5 sigma 190.7 -> 218.0 steps/s in fp64 and 233.8 -> 324.2 in fp32; at
@@ -1051,13 +1102,18 @@ struct NbSystem {
             }
         }
         if (!typed_active) typed_stride = false;
+        if (has_charges() && std::getenv("EMDEE_DEBUG_PLAN"))
+            std::fprintf(stderr, "emdee plan: charged engine, %s, variant %d, LDS force %zu\n", brick_active ? "brick kernels" : "direct kernels",
+                         variant, lds_bytes);
         plan_valid = brick_active;
         plan_uniform = uniform_atoms;
+        plan_charged = has_charges();
         plan_nt = nt;
         plan_n = in_edit ? edit_n_plan : n;
         for (int d = 0; d < 3; d++) plan_M[d] = grid.M[d];
     }
     bool plan_uniform = false;
+    bool plan_charged = false;
     int plan_nt = 1;
     bool typed_blocked = false;           // this state's rows outgrew the typed build (until the next load)
     bool typed_stride = false;            // the stride already includes the typed rows' segment padding
@@ -1081,7 +1137,7 @@ struct NbSystem {
         const int np = in_edit ? edit_n_plan : n;
         bool kept = plan_valid && path == PATH_BRICK && n > 0 && plan_M[0] == grid.M[0] &&
                     plan_M[1] == grid.M[1] && plan_M[2] == grid.M[2] && plan_n <= np + np / 8 && np <= plan_n + plan_n / 8 &&
-                    plan_uniform == uniform_atoms && plan_nt == nt;
+                    plan_uniform == uniform_atoms && plan_nt == nt && plan_charged == has_charges();
         if (kept) {
             plan_geometry();
             // (taking the maxima from k_brick_tables instead, which has every brick's tables in LDS anyway, was measured and
@@ -1231,7 +1287,7 @@ struct NbSystem {
     bool has_bonded() const { return tables->has_bonded; }
     // terms added behind a whole force pass (add_post_terms): such a box steps in the split form (force pass, these terms,
     // kick + drift), not the fused one
-    bool has_post() const { return has_14() || has_bonded(); }
+    bool has_post() const { return has_14() || has_bonded() || has_charges(); }
     // rows the filter visits right after every build: excluded pairs are struck, 1-4 and bonded partners' slots recorded
     bool filters_rows() const { return has_excl() || has_bonded(); }
     // a bonded term whose partner was missing from the rows (flags[16], raised by k_bonded): the engine refuses to step until
@@ -1298,11 +1354,66 @@ struct NbSystem {
                                cnt.ptr, tables->x_start.ptr, tables->x_idx.ptr, pair_keys(), bonded_keys());
         }
     }
+    // ---------------------------------------------------------------- charges (PairTables::set_charges)
+    // A charged engine keeps sqrt(K) q of every slot in its own cell order (qp), owned atoms and ghosts, looked up by the key the
+    // atom carries: filled before the first force pass after every sort or in-place edit (the messages of a decomposition carry
+    // no charges), unchanged in between (ghost identities are fixed between rebuilds).
+    DevBuf<real> qp;
+    bool q_valid = false;
+    bool charge_broken = false;                              // a key without a charge (flags[17]): the engine refuses to step
+    bool has_charges() const { return tables->has_charges; }
+    // an undivided engine whose state no longer has the atom count the charges were set for
+    bool charges_stale() const { return has_charges() && tables == &own_tables && (tables->q_n != n_owned || id_gaps); }
+    Charges<real> charge_args() const {
+        Charges<real> c{};
+        if (!has_charges()) return c;
+        const double rc = std::sqrt(model_d.rc2), rc3 = rc * rc * rc, eps = tables->eps_rf;
+        const double k = std::isinf(eps) ? 0.5 / rc3 : (eps - 1.0) / ((2.0 * eps + 1.0) * rc3);
+        c.q = qp.ptr;
+        c.k = (real)k; c.k2 = (real)(2.0 * k); c.c = (real)(1.0 / rc + k * rc * rc);
+        c.scale14 = (real)tables->scale14c;
+        return c;
+    }
+    void ensure_charges() {
+        if (!has_charges()) return;
+        EMDEE_REQUIRE(!charges_stale(), EMDEE_ERR_STATE, "charges set for %lld atoms, the state holds %d: set them again or clear them "
+                      "(emdee_md_set_coulomb)", (long long)tables->q_n, n_owned);
+        EMDEE_REQUIRE(!charge_broken, EMDEE_ERR_STATE, "an atom has an id outside the charge table: set the charges again");
+        if (q_valid || n_total == 0) return;
+        if (tables != &own_tables) EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "charges over global ids: the state carries no tags");
+        qp.ensure(std::max<size_t>((size_t)n_total, capacity) + 1);
+        hipLaunchKernelGGL((k_fill_charges<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, perm.ptr,
+                           use_tags ? tag.ptr : nullptr, tables->q_tab.ptr, (long long)tables->q_n, qp.ptr, flags.ptr + 17);
+        q_valid = true;
+    }
+    void reset_charge_error() {
+        charge_broken = false;
+        q_valid = false;
+        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 17, 0, sizeof(int), stream()));
+    }
+    // blocking: EMDEE_ERR_STATE if a fill has met a key outside the charge table since the last reset
+    void check_charges() {
+        if (!has_charges() || !flags.ptr) return;
+        int32_t word = 0;
+        if (!charge_broken) read_back_words(ctx, stream(), flags.ptr + 17, 1, &word);
+        if (word != 0) charge_broken = true;
+        EMDEE_REQUIRE(!charge_broken, EMDEE_ERR_STATE, "an atom has an id outside the charge table (emdee_dd_set_coulomb: n_ids too "
+                      "small); set the charges again");
+    }
+
     // after a force pass: the scaled 1-4 terms on top
     void add_pairs14(int bitmask) {
         if (!has_14() || n_total == 0) return;
         check_tables("1-4 table");
         const bool user = brick_active && (out_f || out_e || out_w || out_vt);
+        if (has_charges()) {
+            auto kq = (bitmask & EMDEE_TENSOR) ? k_pairs14_q<real, true> : k_pairs14_q<real, false>;
+            hipLaunchKernelGGL(kq, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
+                               pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
+                               user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
+                               user ? out_vt : (real *)nullptr, charge_args());
+            return;
+        }
         auto kernel = (bitmask & EMDEE_TENSOR) ? k_pairs14<real, true> : k_pairs14<real, false>;
         hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
                            pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
@@ -1331,6 +1442,14 @@ struct NbSystem {
         const int n = n_total;
         int nblocks = (n + FORCE_ATOMS - 1) / FORCE_ATOMS;
         int per_xcd = (nblocks + NXCD - 1) / NXCD;
+        if constexpr (BM == 1 || BM == 7 || BM == TENSOR_PASS) {
+          if (has_charges()) {
+            hipLaunchKernelGGL((k_lj_force_nbr_q<real, BM>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
+                               per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
+                               vir.ptr, direct_guard, vt.ptr, charge_args());
+            return;
+          }
+        }
         hipLaunchKernelGGL((k_lj_force_nbr<real, BM>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
                            per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
                            vir.ptr, direct_guard, vt.ptr);
@@ -1514,6 +1633,10 @@ struct NbSystem {
         EMDEE_REQUIRE(has_list, EMDEE_ERR_STATE, "no neighbour list");
         EMDEE_REQUIRE((bitmask >= 0 && bitmask <= 7) || bitmask == TENSOR_PASS, EMDEE_ERR_INVALID, "bitmask must be a combination of 1|2|4");
         if (n_total == 0 || bitmask == 0) return;
+        ensure_charges();
+        // charged engines have instances for forces, all outputs and the tensor pass: a narrower request runs all outputs (and the
+        // terms behind the force pass follow the kernel's outputs)
+        if (has_charges() && bitmask != EMDEE_FORCES && bitmask != TENSOR_PASS) bitmask = 7;
         if (bitmask & EMDEE_TENSOR) vt.ensure(6 * pitch);
         if (!brick_active && phase == 1) return;   // the direct kernels have no brick phases: all work in phase 2
         Timed t(this, T_FORCE);

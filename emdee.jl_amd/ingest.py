@@ -110,7 +110,8 @@ class BondedTable:
 
 
 class ResidueTemplates:
-    """`<Residues><Residue name=><Atom name= type=/>...<Bond atomName1= atomName2=/>...` of a force-field file."""
+    """`<Residues><Residue name=><Atom name= type= [charge=]/>...<Bond atomName1= atomName2=/>...` of a force-field file
+    (a template atom without a charge has charge 0)."""
 
     def __init__(self, xml_file):
         root = ET.parse(xml_file).getroot()
@@ -119,8 +120,9 @@ class ResidueTemplates:
             names = [a.attrib["name"] for a in res.findall("Atom")]
             index = {nm: k for k, nm in enumerate(names)}
             types = [a.attrib["type"] for a in res.findall("Atom")]
+            charges = [float(a.attrib.get("charge", 0.0)) for a in res.findall("Atom")]
             bonds = [(index[b.attrib["atomName1"]], index[b.attrib["atomName2"]]) for b in res.findall("Bond")]
-            self.residues[res.attrib["name"]] = dict(names=names, types=types, bonds=bonds)
+            self.residues[res.attrib["name"]] = dict(names=names, types=types, bonds=bonds, charges=charges)
 
     def build(self, sequence):
         """(types, bonds (n, 2) int64) of a sequence of residue names, the atoms of each residue in template order"""
@@ -130,6 +132,10 @@ class ResidueTemplates:
             bonds += [(len(types) + i, len(types) + j) for i, j in r["bonds"]]
             types += r["types"]
         return types, np.array(bonds, dtype=np.int64).reshape(-1, 2)
+
+    def charges(self, sequence):
+        """charges (elementary charges, float64) of a sequence of residue names, in the atom order of build(sequence)"""
+        return np.array([q for name in sequence for q in self.residues[name]["charges"]], dtype=np.float64)
 
 
 def topology(types, bonds, table, length_unit=1.0, energy_unit=1.0):

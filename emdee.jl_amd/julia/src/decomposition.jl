@@ -99,6 +99,14 @@ set_bonded!(dd::DomainDecomposition, kind, atoms::Union{Nothing,HipArray{Int64,2
                 Int32(kind), atoms === nothing ? C_NULL : atoms.ptr, params === nothing ? C_NULL : params.ptr,
                 atoms === nothing ? 0 : size(atoms, 2)))
 
+# int32_t emdee_dd_set_coulomb(emdee_dd *dd, const double *charges_dev, int64_t n_ids, double coulomb_k, double eps_rf,
+#                              double coulomb14scale);
+# As set_coulomb! of a VelocityVerlet, the table indexed by 0-based GLOBAL id; collective, before load! or between step! calls.
+set_coulomb!(dd::DomainDecomposition, charges::Union{Nothing,HipArray{Float64,1}}, coulomb_k, eps_rf=Inf, coulomb14scale=1.0) =
+    check(ccall((:emdee_dd_set_coulomb, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Float64), dd.handle,
+                charges === nothing ? C_NULL : charges.ptr, charges === nothing ? 0 : length(charges), Float64(coulomb_k),
+                Float64(eps_rf), Float64(coulomb14scale)))
+
 # int32_t emdee_dd_set_overlap(emdee_dd *dd, int32_t overlap);
 # true (default): interior bricks overlap the halo exchange; false: exchange and one launch over all bricks in order
 set_overlap!(dd::DomainDecomposition, on::Bool) =

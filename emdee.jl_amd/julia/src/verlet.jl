@@ -58,6 +58,15 @@ set_bonded!(md::VelocityVerlet, kind, atoms::Union{Nothing,HipArray{Int32,2}}, p
                 Int32(kind), atoms === nothing ? C_NULL : atoms.ptr, params === nothing ? C_NULL : params.ptr,
                 atoms === nothing ? 0 : size(atoms, 2)))
 
+# int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n, double coulomb_k, double eps_rf,
+#                              double coulomb14scale);
+# Reaction-field Coulomb forces: charges a device Float64 vector in caller order (n = the atom count), coulomb_k in the
+# caller's units (138.935457644 kJ mol^-1 nm e^-2), eps_rf >= 1 (Inf: conducting boundary); `nothing` clears them.
+set_coulomb!(md::VelocityVerlet, charges::Union{Nothing,HipArray{Float64,1}}, coulomb_k, eps_rf=Inf, coulomb14scale=1.0) =
+    check(ccall((:emdee_md_set_coulomb, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64, Float64), md.handle,
+                charges === nothing ? C_NULL : charges.ptr, charges === nothing ? 0 : length(charges), Float64(coulomb_k),
+                Float64(eps_rf), Float64(coulomb14scale)))
+
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);
 # Atom ids keying the thermostat's noise (device Int64 vector in caller order); `nothing` = the caller index.
 set_langevin_ids!(md::VelocityVerlet, ids::Union{Nothing,HipArray{Int64,1}}) =

@@ -133,8 +133,8 @@ def water_box(n, xml_file=None, seed=SEED):
     """n^3 water molecules from the HOH template of a force-field file (default: the committed dibenzo-p-dioxin-in-water.xml)
     on a simple cubic lattice of WATER_SPACING nm, each O at a site with its two H at the bond length and angle of the file's
     tables, in a seeded random orientation per molecule.  nm, kJ/mol and real masses.  Returns a dict: positions (3 n^3, 3)
-    wrapped into [0, L), L, types, atoms (LJAtom array), inv_mass (per atom, mol / g), and topology(): bonds, bond_params,
-    angles, angle_params, exclusions (1-2 and 1-3)."""
+    wrapped into [0, L), L, types, atoms (LJAtom array), inv_mass (per atom, mol / g), charges (per atom, e, from the HOH
+    template), and topology(): bonds, bond_params, angles, angle_params, exclusions (1-2 and 1-3)."""
     import os
 
     from . import ingest
@@ -167,4 +167,4 @@ def water_box(n, xml_file=None, seed=SEED):
     inv_mass = 1.0 / np.array([table.masses[t] for t in types])
     return dict(positions=np.mod(pos, L), L=L, types=types, atoms=nbt.lj_atoms(types), inv_mass=inv_mass,
                 bonds=top["bonds"], bond_params=top["bond_params"], angles=top["angles"], angle_params=top["angle_params"],
-                exclusions=top["exclusions"])
+                exclusions=top["exclusions"], charges=np.tile(templates.charges(["HOH"]), m))

@@ -11,6 +11,15 @@ from .nonbonded import ENERGIES, FORCES, VIRIALS, check_tensor_out, tensor_matri
 HARMONIC_BOND, HARMONIC_ANGLE, PERIODIC_TORSION = 1, 2, 3
 _BONDED_SHAPE = {HARMONIC_BOND: (2, 2), HARMONIC_ANGLE: (3, 2), PERIODIC_TORSION: (4, 3)}
 
+# Coulomb's constant 1 / (4 pi eps0) in kJ mol^-1 nm e^-2 (CODATA 2018 e, eps0 and N_A): the K of set_coulomb_ in the units of
+# the force-field files the library ingests
+COULOMB_K_KJ_NM = 138.935457644
+
+
+def charge_array(charges, device):
+    """charges as a contiguous float64 device vector (None: empty)."""
+    return torch.as_tensor(charges if charges is not None else [], dtype=torch.float64).reshape(-1).to(device=device).contiguous()
+
 
 def bonded_arrays(kind, atoms, params, device, id_dtype):
     """(atoms, params) of one bonded kind as contiguous device tensors (ids of id_dtype, parameters float64).  An unknown kind
@@ -232,6 +241,14 @@ class VelocityVerlet:
         a, p = bonded_arrays(kind, atoms, params, self.device, torch.int32)
         _lib.call("emdee_md_set_bonded", self._handle, int(kind), C.c_void_p(a.data_ptr()) if a.numel() else None,
                   C.c_void_p(p.data_ptr()) if p.numel() else None, int(a.shape[0]))
+
+    def set_coulomb_(self, charges, coulomb_k, eps_rf=float("inf"), coulomb14scale=1.0):
+        """Reaction-field Coulomb forces (include/emdee_hip.h emdee_md_set_coulomb): charges (n,) in caller order, n the atom
+        count; coulomb_k in the caller's units (COULOMB_K_KJ_NM for nm / kJ mol^-1 / e); eps_rf >= 1 (inf: the conducting
+        boundary); coulomb14scale scales the 1-4 pairs of set_pairs14_.  Empty or None clears them."""
+        q = charge_array(charges, self.device)
+        _lib.call("emdee_md_set_coulomb", self._handle, C.c_void_p(q.data_ptr()) if q.numel() else None, int(q.shape[0]),
+                  float(coulomb_k), float(eps_rf), float(coulomb14scale))
 
     def close(self):
         if self._handle is not None:

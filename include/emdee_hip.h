@@ -202,6 +202,38 @@ int32_t emdee_md_set_pairs14(emdee_md *md, const int32_t *pairs_dev, int32_t n_p
 #define EMDEE_PERIODIC_TORSION  3
 int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev, const double *params_dev, int32_t n_terms);
 
+/* Reaction-field Coulomb forces between charged atoms (a cutoff method: the neighbour rows of the LJ model, no new
+ * communication).  Each atom i carries a charge q_i; Coulomb's constant K is the caller's, in the caller's units (about
+ * 138.935 kJ mol^-1 nm e^-2); eps_rf is the reaction-field dielectric, 1 <= eps_rf <= +inf; rc is the LJ model's cutoff:
+ *   k_rf = (eps_rf - 1) / ((2 eps_rf + 1) rc^3)      (1 / (2 rc^3) at eps_rf = +inf, 0 at eps_rf = 1)
+ *   c_rf = 1/rc + k_rf rc^2
+ * For every listed pair with r^2 < rc^2 (the strict CUTOFF test of the LJ terms):
+ *   U_ij = K q_i q_j (1/r + k_rf r^2 - c_rf)          so that U(rc) = 0
+ *   W_ij = -r dU/dr = K q_i q_j (1/r - 2 k_rf r^2)
+ *   F_i  = (W_ij / r^2) d,  d = r_i - r_j the minimum image (the LJ convention)
+ * These terms are added to the LJ terms of the same pair in every output: forces, the per-atom energies and virials (half to
+ * each atom), the per-atom tensors (W / r^2) d (x) d (half to each atom; tr W_i = w_i still holds), emdee_*_energies and
+ * emdee_*_pressure_tensor.  An excluded pair contributes nothing; a 1-4 pair contributes coulomb14scale times its terms (same
+ * formula, same cutoff), next to its lj14scale-scaled LJ terms.  There is NO self term and NO reaction-field correction for
+ * excluded pairs.  Codes that add them (GROMACS' reaction field, for one) add K q_i q_j (k_rf r^2 - c_rf) for every excluded
+ * pair within rc, which changes energies and forces, and a self term -K q_i^2 c_rf / 2 per atom, a constant that changes
+ * energies only; energies from this library differ from theirs by those terms.  At eps_rf = +inf force and
+ * energy both go to zero at rc; at a finite eps_rf the force jumps at rc by K q_i q_j 3 / ((2 eps_rf + 1) rc^2).
+ *   - emdee_md_set_coulomb: charges in caller-id order, n = the owned atom count, after emdee_md_set_state; undivided engines
+ *     only (an integrator lent by emdee_dd_engine, or one with ghosts, returns EMDEE_ERR_STATE).  The charges stay in force
+ *     across a later set_state with the same atom count; after one with another count that set_state evaluates no forces,
+ *     and the engine refuses with EMDEE_ERR_STATE to step, to evaluate forces and to hand out forces, energies, virials or
+ *     tensors (emdee_md_get_state with any of them, _energies, _virial_tensor, _pressure_tensor) until the charges are set
+ *     again or cleared; positions and velocities can still be read.
+ *   - n = 0 clears the charges (the constants are then not looked at): the engine runs the uncharged kernels again.
+ *   - All or nothing: EMDEE_ERR_INVALID, the previous charges in force, for a NULL array with n > 0, the wrong n, a non-finite
+ *     charge, K not finite or <= 0, eps_rf < 1 or NaN, a non-finite or negative coulomb14scale.
+ *   - The 1-4 pairs themselves come from emdee_*_set_pairs14.
+ *   - A charged engine steps in the split form (force pass, 1-4 and bonded terms, kick + drift) and keeps the general-species
+ *     kernels, even where its LJ parameters are uniform.  Not on the operator path (emdee_compute_nonbonded, emdee_nbr_*). */
+int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n, double coulomb_k, double eps_rf,
+                             double coulomb14scale);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -268,7 +300,10 @@ int32_t emdee_md_step(emdee_md *md, int32_t nsteps, double dt, int32_t rebuild_e
  * carries the closing half kick of the previous step (same f), saving one pass over v and f. */
 int32_t emdee_md_kick_drift(emdee_md *md, double dt, double kick);
 /* f (and e, w) of owned atoms.  phase 0: all atoms; phase 1: only bricks whose LDS tile holds no
- * ghost cell (can run while the halo exchange is in flight); phase 2: the remaining bricks. */
+ * ghost cell (can run while the halo exchange is in flight); phase 2: the remaining bricks.
+ * A charged engine (emdee_md_set_coulomb) has kernels for EMDEE_FORCES and for all three outputs only: a narrower request
+ * (2 .. 6) evaluates all three, so the force plane is rewritten too, with the all-outputs kernel's rounding (an uncharged
+ * engine leaves it alone). */
 int32_t emdee_md_forces(emdee_md *md, int32_t bitmask, int32_t phase);
 int32_t emdee_md_kick(emdee_md *md, double dt);              /* v += (dt/2m) f */
 /* One inner step as a single kernel: f = F(x), v += kick (dt/m) f, x += dt v, with the new positions
@@ -421,6 +456,13 @@ int32_t emdee_dd_set_pairs14(emdee_dd *dd, const int64_t *pairs_dev, int64_t n_p
  * domains of a process share one copy; a missing partner is reported on every rank (EMDEE_ERR_STATE), and every rank then
  * refuses emdee_dd_step until the tables or the state are replaced. */
 int32_t emdee_dd_set_bonded(emdee_dd *dd, int32_t kind, const int64_t *atoms_dev, const double *params_dev, int64_t n_terms);
+/* Charges of a decomposed run (see emdee_md_set_coulomb): a table indexed by GLOBAL id, n_ids entries.  Collective, before
+ * emdee_dd_load or between steps (after a load it rebuilds every domain, as emdee_dd_set_bonded); the domains of a process share
+ * one device copy; n_ids = 0 clears it.  A domain atom whose gid is >= n_ids is an error, never a zero charge: EMDEE_ERR_STATE
+ * on every rank (from this call or from emdee_dd_load), and every rank then refuses emdee_dd_step until the charges are set
+ * again. */
+int32_t emdee_dd_set_coulomb(emdee_dd *dd, const double *charges_dev, int64_t n_ids, double coulomb_k, double eps_rf,
+                             double coulomb14scale);
 
 #ifdef __cplusplus
 }
