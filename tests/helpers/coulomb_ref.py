@@ -2,9 +2,19 @@
 charged engines:
   k_rf = (eps_rf - 1) / ((2 eps_rf + 1) rc^3)   (1 / (2 rc^3) at eps_rf = inf),   c_rf = 1/rc + k_rf rc^2
   U = K q_i q_j (1/r + k_rf r^2 - c_rf),  W = -r dU/dr = K q_i q_j (1/r - 2 k_rf r^2),  F_i = (W / r^2) d,  d = r_i - r_j
-for every pair with r^2 < rc^2 (minimum image in a cubic periodic box of side L); half of U, W and the tensor (W / r^2) d (x) d
-to either atom.  Excluded pairs contribute nothing, 1-4 pairs s14 times their terms."""
+for every pair with r^2 < rc^2 (minimum image in a periodic orthorhombic box); half of U, W and the tensor (W / r^2) d (x) d to
+either atom.  Excluded pairs contribute nothing, 1-4 pairs s14 times their terms.
+
+L is the box: one number for a cube, or the three per-axis lengths (Lx, Ly, Lz) -- every function here passes it through
+box_lengths, so that the minimum image of axis a uses L[a] and nothing else."""
 import numpy as np
+
+
+def box_lengths(L):
+    """L as the (3,) vector of per-axis lengths (a scalar is a cube)"""
+    L = np.asarray(L, dtype=np.float64)
+    assert L.shape in ((), (3,)), "L is one side or three per-axis lengths"
+    return np.broadcast_to(L, (3,))
 
 
 def rf_constants(rc, eps_rf):
@@ -23,6 +33,7 @@ def pair_energy_virial(r, qq, rc, eps_rf):
 def pairs_within(pos, L, rc, chunk=512):
     """every pair i < j with minimum-image distance below rc, as an (m, 2) int64 array"""
     n = pos.shape[0]
+    L = box_lengths(L)
     out = []
     for a in range(0, n, chunk):
         d = pos[a:a + chunk, None, :] - pos[None, :, :]
@@ -43,6 +54,7 @@ def pair_terms(pos, L, q, K, rc, eps_rf, pairs):
     if pairs.shape[0] == 0:
         return f, e, w, t
     i, j = pairs[:, 0], pairs[:, 1]
+    L = box_lengths(L)
     d = pos[i] - pos[j]
     d -= L * np.rint(d / L)
     r2 = (d * d).sum(axis=1)

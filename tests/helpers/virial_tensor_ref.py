@@ -40,12 +40,22 @@ def _minimum_image(d, lengths, periodic):
     return d
 
 
-def pairs_in_range(pos, lengths, periodic, rc, oracle=None):
-    """(i, j, d) of every pair i < j with |d| < rc + 0.1 (d = minimum image of r_i - r_j on the periodic axes)."""
+def pairs_in_range(pos, lengths, periodic, rc, oracle=None, rows=None, margin=0.1):
+    """(i, j, d) of every pair i < j with |d| < rc + margin (d = minimum image of r_i - r_j on the periodic axes).
+    rows: the sampled mode for boxes too large for the N^2 sum -- i runs over these atoms only and j over every other
+    atom, so that each listed row is whole (O(len(rows) N))."""
     pos = np.asarray(pos, dtype=np.float64)
     N = pos.shape[0]
     cubic = all(periodic) and lengths[0] == lengths[1] == lengths[2]
-    rl = rc + 0.1
+    rl = rc + margin
+    if rows is not None:
+        out = []
+        for r in np.asarray(rows, dtype=np.int64):
+            d = _minimum_image(pos[r] - pos, lengths, periodic)
+            j = np.nonzero(np.einsum("ij,ij->i", d, d) < rl * rl)[0]
+            j = j[j != r]
+            out.append((np.full(j.shape[0], r), j, d[j]))
+        return tuple(np.concatenate([o[k] for o in out]) for k in range(3))
     if cubic and oracle is not None and rl <= 0.5 * lengths[0]:
         off, nb = oracle.neighbor_list(pos, lengths[0], rl)
         i = np.repeat(np.arange(N), np.diff(off))

@@ -97,9 +97,10 @@ def _family_box(E, family):
         return pos, [L] * 3, [1, 1, 1], atoms, (2.5, 2.0), {}, "emdee plan: bricks", "two species"
     if family == "direct":
         return pos, [L] * 3, [1, 1, 1], atoms, (2.5, 2.0), {"EMDEE_PATH": "direct"}, None, "emdee plan: bricks"
-    # orthorhombic, z not periodic: stretch y and z so that every component differs, keep z inside the walls
-    lengths = [L, 1.1 * L, 1.3 * L]
-    pos = pos * np.array([1.0, 1.1, 1.3]) + np.array([0.0, 0.0, 0.0])
+    # orthorhombic, z not periodic: stretch y and z so that every component differs, and so do the three cell counts
+    # (sides 17.1, 20.5, 24.8 at rc + skin = 2.8: 6, 7 and 8 cells); keep z inside the walls
+    lengths = [L, 1.2 * L, 1.45 * L]
+    pos = pos * np.array([1.0, 1.2, 1.45]) + np.array([0.0, 0.0, 0.0])
     pos[:, 2] = np.clip(pos[:, 2], 0.05, lengths[2] - 0.05)
     return pos, lengths, [1, 1, 0], atoms, (2.5, 2.0), {}, "emdee plan: bricks", None
 
