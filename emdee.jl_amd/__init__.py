@@ -21,6 +21,8 @@ from .nonbonded import (ENERGIES, FORCES, VIRIALS, WAVESIZE, AllPairsTiles,     
                         NeighborTiles, Val, compute_nonbonded_, compute_virial_tensor_,
                         naively_compute_nonbonded_, nonbonded_computation_tiles)
 from .verlet import COULOMB_K_KJ_NM, HARMONIC_ANGLE, HARMONIC_BOND, PERIODIC_TORSION, VelocityVerlet  # noqa: E402
+from .verlet import (BAROSTAT_BERENDSEN, BAROSTAT_CRESCALE, BAROSTAT_OFF, COUPLE_ANISOTROPIC,     # noqa: E402
+                     COUPLE_ISOTROPIC, COUPLE_SEMIISOTROPIC)
 from . import synthetic                                                         # noqa: E402
 from . import domain                                                            # noqa: E402
 from . import ingest                                                            # noqa: E402
@@ -33,4 +35,6 @@ __all__ = ["LennardJonesModel", "LennardJonesAtom", "LJAtom", "lennard_jones_ato
            "naively_compute_nonbonded_", "NeighborTiles", "AllPairsTiles", "Cells", "update_cells_",
            "VelocityVerlet", "cu", "to_host", "context_for", "Context", "gpu_available", "synthetic",
            "EmDeeError", "LITERAL", "CUTOFF", "WAVESIZE", "domain", "ingest", "dd", "DomainDecomposition",
-           "HARMONIC_BOND", "HARMONIC_ANGLE", "PERIODIC_TORSION", "COULOMB_K_KJ_NM"]
+           "HARMONIC_BOND", "HARMONIC_ANGLE", "PERIODIC_TORSION", "COULOMB_K_KJ_NM",
+           "BAROSTAT_OFF", "BAROSTAT_BERENDSEN", "BAROSTAT_CRESCALE", "COUPLE_ISOTROPIC", "COUPLE_SEMIISOTROPIC",
+           "COUPLE_ANISOTROPIC"]

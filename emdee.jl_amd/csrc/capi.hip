@@ -439,6 +439,19 @@ int32_t emdee_md_langevin_normals(emdee_md *md, uint64_t seed, uint64_t step, co
         md->impl->langevin_normals(seed, step, ids_dev, n, out_dev);
     });
 }
+int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(lo, "lo"); REQUIRE_PTR(len, "len"); md->impl->get_box(lo, len); });
+}
+int32_t emdee_md_scale_box(emdee_md *md, const double mu[3], double velocity_scale) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(mu, "mu"); md->impl->scale_box(mu, velocity_scale); });
+}
+int32_t emdee_md_set_barostat(emdee_md *md, int32_t kind, int32_t coupling, const double p_ref[3], const double compressibility[3],
+                              double tau_p, int32_t every, double temperature, uint64_t seed, uint64_t first_step) {
+    return guarded([&] {
+        REQUIRE_PTR(md, "md");
+        md->impl->set_barostat(kind, coupling, p_ref, compressibility, tau_p, every, temperature, seed, first_step);
+    });
+}
 
 // ---------------------------------------------------------------- domain decomposition
 int32_t emdee_dd_unique_id(uint8_t out[128]) {

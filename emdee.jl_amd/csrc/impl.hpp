@@ -234,6 +234,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         EMDEE_REQUIRE(!sys.bonded_broken, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
         if (nsteps == 0) return;
+        if (baro.kind != EMDEE_BAROSTAT_OFF) { step_coupled(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
@@ -272,6 +273,134 @@ struct MdImpl : IMd {
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
         if (!lent) sys.check_bonded();                       // (one read-back per call, with bonded tables only)
+    }
+    // ---- pressure coupling (include/emdee_hip.h: emdee_md_scale_box, emdee_md_set_barostat)
+    struct Barostat {
+        int kind = EMDEE_BAROSTAT_OFF, coupling = EMDEE_COUPLE_ISOTROPIC, every = 1;
+        double p_ref[3] = {0, 0, 0}, beta[3] = {0, 0, 0}, tau_p = 1.0, temperature = 0.0;
+        unsigned long long seed = 0, step = 0;               // step: how many steps have been taken, counted from first_step
+    } baro;
+    DevBuf<long long> baro_id;                               // the id -1 of the coupling's random number (C-rescale)
+    DevBuf<double> baro_xi;
+    void get_box(double lo[3], double len[3]) override {
+        for (int d = 0; d < 3; d++) { lo[d] = sys.lo[d]; len[d] = sys.len[d]; }
+    }
+    void require_undivided(const char *what) const {
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s: this integrator is a domain's, lent by emdee_dd_engine (the geometry of a decomposition is fixed at create)", what);
+        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "%s: an integrator with ghosts (its box is a domain of a larger one)", what);
+    }
+    void scale_box(const double mu[3], double vscale) override {
+        use_device(sys.ctx);
+        require_undivided("scale_box");
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
+        sys.scale_box(mu, vscale);                           // (validates before it writes)
+        since_build = 0;
+        current_mask = 0;
+        if (!sys.charges_stale()) {
+            sys.compute_forces(EMDEE_FORCES);
+            current_mask = EMDEE_FORCES;
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.check_bonded();
+    }
+    void set_barostat(int32_t kind, int32_t coupling, const double *p_ref, const double *beta, double tau_p, int32_t every,
+                      double temperature, uint64_t seed, uint64_t first_step) override {
+        use_device(sys.ctx);
+        require_undivided("set_barostat");
+        if (kind == EMDEE_BAROSTAT_OFF) { baro.kind = EMDEE_BAROSTAT_OFF; return; }
+        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_BERENDSEN || kind == EMDEE_BAROSTAT_CRESCALE, EMDEE_ERR_INVALID, "set_barostat: unknown kind %d", kind);
+        EMDEE_REQUIRE(coupling >= EMDEE_COUPLE_ISOTROPIC && coupling <= EMDEE_COUPLE_ANISOTROPIC, EMDEE_ERR_INVALID, "set_barostat: unknown coupling %d", coupling);
+        EMDEE_REQUIRE(kind != EMDEE_BAROSTAT_CRESCALE || coupling == EMDEE_COUPLE_ISOTROPIC, EMDEE_ERR_INVALID,
+                      "set_barostat: stochastic cell rescaling is isotropic only");
+        EMDEE_REQUIRE(p_ref && beta, EMDEE_ERR_INVALID, "set_barostat: p_ref or compressibility is NULL");
+        EMDEE_REQUIRE(every >= 1, EMDEE_ERR_INVALID, "set_barostat: every = %d must be >= 1", every);
+        EMDEE_REQUIRE(std::isfinite(tau_p) && tau_p > 0.0, EMDEE_ERR_INVALID, "set_barostat: tau_p must be finite and > 0");
+        for (int d = 0; d < 3; d++) {
+            EMDEE_REQUIRE(std::isfinite(p_ref[d]), EMDEE_ERR_INVALID, "set_barostat: p_ref[%d] is not finite", d);
+            EMDEE_REQUIRE(std::isfinite(beta[d]) && beta[d] >= 0.0, EMDEE_ERR_INVALID, "set_barostat: compressibility[%d] must be finite and >= 0", d);
+        }
+        EMDEE_REQUIRE(kind != EMDEE_BAROSTAT_CRESCALE || (std::isfinite(temperature) && temperature > 0.0), EMDEE_ERR_INVALID,
+                      "set_barostat: stochastic cell rescaling needs a temperature > 0");
+        if (kind == EMDEE_BAROSTAT_CRESCALE) {
+            baro_xi.ensure(3);
+            if (baro_id.ensure(1)) EMDEE_HIP_CHECK(hipMemsetAsync(baro_id.ptr, 0xff, sizeof(long long), sys.stream()));
+        }
+        // ---- commit
+        baro.kind = kind; baro.coupling = coupling; baro.every = every; baro.tau_p = tau_p; baro.temperature = temperature;
+        baro.seed = seed; baro.step = first_step;
+        for (int d = 0; d < 3; d++) { baro.p_ref[d] = p_ref[d]; baro.beta[d] = beta[d]; }
+    }
+    // emdee_md_step with coupling on.  Every step closes its own half kick (kick + drift, force pass, kick): the state after s
+    // steps then does not depend on how the s steps were dealt to calls -- step(40), 8 x step(5) and 40 x step(1) are the same
+    // sequence of launches, bit for bit -- and no step is ever queued beyond an event on the box the event is about to change.
+    // (The merged kicks and the guarded run-ahead of the uncoupled loop would have to end at every call as well as at every
+    // event, and v + h + h is not v + 2 h in floating point.)  The step that completes an event's interval evaluates the
+    // energies and virials with its forces when the coupling is isotropic: no pass is added for the pressure.
+    void step_coupled(int nsteps, double dt, int rebuild_every) {
+        if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
+        for (int s = 0; s < nsteps; s++) {
+            const bool event = (baro.step + 1) % (unsigned long long)baro.every == 0;
+            sys.kick_drift(0.5 * dt, dt);
+            since_build++;
+            const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
+            if (rb) { sys.resort(); since_build = 0; }
+            const int mask = (event && baro.coupling == EMDEE_COUPLE_ISOTROPIC) ? 7 : EMDEE_FORCES;
+            sys.compute_forces(mask);
+            sys.kick(0.5 * dt);
+            current_mask = mask;
+            baro.step++;
+            if (event) couple(dt);
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
+    }
+    // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
+    // read-back), the factors on the host, emdee_md_scale_box
+    void couple(double dt) {
+        const double Dt = (double)baro.every * dt, V = sys.len[0] * sys.len[1] * sys.len[2];
+        double xi[3] = {0.0, 0.0, 0.0};
+        if (baro.kind == EMDEE_BAROSTAT_CRESCALE) {          // xi(seed, s, id = -1), queued ahead of the sums: it comes back with them
+            hipLaunchKernelGGL((k_langevin_normals_test<real>), dim3(1), dim3(64), 0, sys.stream(), 1, baro.seed, baro.step,
+                               (const long long *)baro_id.ptr, baro_xi.ptr);
+            EMDEE_HIP_CHECK(hipMemcpyAsync(xi, baro_xi.ptr, 3 * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        }
+        double P[3];
+        if (baro.coupling == EMDEE_COUPLE_ISOTROPIC) {
+            double e[3];
+            sys.energy_sums(0.0, e);
+            P[0] = P[1] = P[2] = (2.0 * e[1] + e[2]) / (3.0 * V);
+        } else {
+            tensor_pass();
+            double t[TENSOR_SUMS];
+            sys.tensor_sums(t);
+            for (int d = 0; d < 3; d++) P[d] = (t[6 + d] + t[d]) / V;
+            if (baro.coupling == EMDEE_COUPLE_SEMIISOTROPIC) P[0] = P[1] = 0.5 * (P[0] + P[1]);
+        }
+        // entries of p_ref and compressibility: 0 for the isotropic factor, 0 (x and y) and 2 (z) for the semi-isotropic ones
+        const int src[3][3] = {{0, 0, 0}, {0, 0, 2}, {0, 1, 2}};
+        double mu[3], vscale = 1.0;
+        if (baro.kind == EMDEE_BAROSTAT_BERENDSEN) {
+            for (int d = 0; d < 3; d++) {
+                const int k = src[baro.coupling][d];
+                mu[d] = 1.0 - (Dt / (3.0 * baro.tau_p)) * baro.beta[k] * (baro.p_ref[k] - P[d]);
+            }
+        } else {
+            const double beta = baro.beta[0];
+            const double de = -(beta / baro.tau_p) * (baro.p_ref[0] - P[0]) * Dt +
+                              std::sqrt(2.0 * baro.temperature * beta * Dt / (V * baro.tau_p)) * xi[0];
+            mu[0] = mu[1] = mu[2] = std::exp(de / 3.0);
+            vscale = 1.0 / mu[0];
+        }
+        try {
+            scale_box(mu, vscale);
+        } catch (const Failure &f) {
+            if (f.code != EMDEE_ERR_INVALID) throw;
+            // (the message of the refusal stays; the state is the completed step's)
+            std::string why = get_error();
+            set_error("md_step: pressure coupling at step %llu refused (P = %g %g %g, mu = %g %g %g): %s", baro.step, P[0], P[1], P[2],
+                      mu[0], mu[1], mu[2], why.c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
     }
     void kick_drift(double dt, double kick) override {
         use_device(sys.ctx);

@@ -1032,6 +1032,34 @@ __global__ void k_kick(int n, int n_owned, size_t pitch, const int *__restrict__
     vel[2 * pitch + p] += cm * frc[2 * pitch + p];
 }
 
+// ---- pressure coupling (emdee_md_scale_box; build-defined: the reference has no barostat) -----------------------------------
+// The cell-ordered state rescaled where it lives, one thread per slot: x_d <- lo_d + mu_d (x_d - lo_d) on the record, v <- s v on
+// the velocity planes (scale_vel = 0: the planes are not touched, bit for bit).  The arithmetic is fp64 in both precisions.
+// Cell-relative records (fp32 integrators, RelGrid) go through the ABSOLUTE position: origin of the record's cell + record,
+// scaled, and stored relative to the SAME origin again -- the cells of the old grid, which is what the re-sort that follows
+// reads them with (NbSystem::resort: rel_in); the offset leaves [0, cell width) by (mu - 1) x, as after a long drift, and the
+// re-sort brings it back.  Scaling the offset itself would move every atom towards its own cell's corner.
+// Wrapped records stay consistent with the image counts: lo + mu (x + k len - lo) = [lo + mu (x - lo)] + k (mu len).
+struct ScaleBox {
+    double lo[3], mu[3];
+};
+template <typename real>
+__global__ void k_cell_state_scale(int n, size_t pitch, Rec<real> *__restrict__ rec, real *__restrict__ vel, ScaleBox s,
+                                   real vscale, int scale_vel, RelGrid rel) {
+    int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    Rec<real> r = rec[p];
+    double ox = 0.0, oy = 0.0, oz = 0.0;
+    if (sizeof(real) == 4 && rel.on) rel.origin(rel.cell[p], ox, oy, oz);
+    r.x = (real)(s.lo[0] + s.mu[0] * ((double)r.x + ox - s.lo[0]) - ox);
+    r.y = (real)(s.lo[1] + s.mu[1] * ((double)r.y + oy - s.lo[1]) - oy);
+    r.z = (real)(s.lo[2] + s.mu[2] * ((double)r.z + oz - s.lo[2]) - oz);
+    rec[p] = r;
+    if (scale_vel) {
+        vel[p] *= vscale; vel[pitch + p] *= vscale; vel[2 * pitch + p] *= vscale;
+    }
+}
+
 // ------------------------------------------------------------------------------------ caller-order copies
 // One thread per cell-order slot p, written to the atom's id i = perm[p] -- or, when the ids have gaps (a decomposed domain
 // that re-sorted its own records: NbSystem::resort_edit), to the rank of that id among the ids in use, cmap[i]: owned atoms

@@ -664,6 +664,35 @@ struct NbSystem {
         rel_commit(rel_next);
         build_list();
     }
+    // emdee_md_scale_box: can the box take the factors mu?  (checked before anything is written)
+    void check_scaled_box(const double mu[3], double vscale) const {
+        for (int d = 0; d < 3; d++)
+            EMDEE_REQUIRE(std::isfinite(mu[d]) && mu[d] > 0.0, EMDEE_ERR_INVALID, "scale_box: mu[%d] = %g must be finite and > 0", d, mu[d]);
+        EMDEE_REQUIRE(std::isfinite(vscale) && vscale > 0.0, EMDEE_ERR_INVALID, "scale_box: velocity_scale = %g must be finite and > 0", vscale);
+        for (int d = 0; d < 3; d++) {
+            const double nl = mu[d] * len[d];
+            EMDEE_REQUIRE(std::isfinite(nl) && nl > 0.0, EMDEE_ERR_INVALID, "scale_box: the new box length %g along %d is not finite and > 0", nl, d);
+            EMDEE_REQUIRE(!per[d] || nl >= 2.0 * rlist, EMDEE_ERR_INVALID, "scale_box: the new periodic box length %g along dimension %d is below "
+                          "2 (cutoff + skin) = %g (minimum image)", nl, d, 2.0 * rlist);
+        }
+    }
+    // ... then: the sorted state rescaled in place (k_cell_state_scale), the box mu_d len_d, and the re-sort -- new cells, a new
+    // plan when the box changed (set_box), the list, the 1-4 and bonded slots, the charge plane at the next force pass.
+    // No read-back of its own: mu and vscale are the caller's host values.
+    void scale_box(const double mu[3], double vscale) {
+        EMDEE_REQUIRE(sorted && with_vel && !has_ghosts, EMDEE_ERR_STATE, "scale_box: needs a loaded state without ghosts");
+        check_scaled_box(mu, vscale);
+        if (n_total > 0) {
+            ScaleBox s{};
+            for (int d = 0; d < 3; d++) { s.lo[d] = lo[d]; s.mu[d] = mu[d]; }
+            hipLaunchKernelGGL((k_cell_state_scale<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, pitch, rec.ptr,
+                               vel.ptr, s, (real)vscale, vscale != 1.0 ? 1 : 0, rel_grid(rel_now, cell_sorted.ptr));
+        }
+        const double nl[3] = {mu[0] * len[0], mu[1] * len[1], mu[2] * len[2]};
+        set_box(lo, nl, per);                                // (a changed box invalidates the sort, the list and the plan ...)
+        sorted = true;                                       // ... but the records are this state's: the re-sort reads them
+        resort();
+    }
     void swap_sorted_buffers() {
         q_valid = false;                                     // (the charge plane is the previous order's)
         rec.swap(rec2); te.swap(te2); perm.swap(perm2); img.swap(img2); cell_sorted.swap(cell_sorted2);

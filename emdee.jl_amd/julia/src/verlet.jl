@@ -1,6 +1,7 @@
 # verlet.jl -- velocity-Verlet on the device.  Build-defined: the reference has no integrator
 # (SURVEY.md 8a row a16).  API in EmDee's style: a constructor and `!` mutators.
 export VelocityVerlet, step!, energies, set_langevin!, set_langevin_ids!, virial_tensor!, pressure_tensor
+export box, scale_box!, set_barostat!
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -66,6 +67,34 @@ set_coulomb!(md::VelocityVerlet, charges::Union{Nothing,HipArray{Float64,1}}, co
     check(ccall((:emdee_md_set_coulomb, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64, Float64), md.handle,
                 charges === nothing ? C_NULL : charges.ptr, charges === nothing ? 0 : length(charges), Float64(coulomb_k),
                 Float64(eps_rf), Float64(coulomb14scale)))
+
+# Pressure coupling (include/emdee_hip.h; undivided boxes).
+# int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);   -> (lo, len) of the engine's box
+function box(md::VelocityVerlet)
+    lo = zeros(Float64, 3); len = zeros(Float64, 3)
+    check(ccall((:emdee_md_get_box, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), md.handle, lo, len))
+    return (lo=lo, len=len)
+end
+
+# int32_t emdee_md_scale_box(emdee_md *md, const double mu[3], double velocity_scale);
+# x <- lo + mu (x - lo) per axis, len <- mu len, v <- velocity_scale v; then re-bin, re-plan, rebuild and a force pass.
+scale_box!(md::VelocityVerlet, mu, velocity_scale=1.0) =
+    check(ccall((:emdee_md_scale_box, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Float64), md.handle,
+                Float64[mu[1], mu[2], mu[3]], Float64(velocity_scale)))
+
+# int32_t emdee_md_set_barostat(emdee_md *md, int32_t kind, int32_t coupling, const double p_ref[3], const double compressibility[3],
+#                               double tau_p, int32_t every, double temperature, uint64_t seed, uint64_t first_step);
+# kind: BAROSTAT_OFF, BAROSTAT_BERENDSEN or BAROSTAT_CRESCALE (isotropic only; needs temperature > 0); p_ref and compressibility:
+# three entries (isotropic reads entry 1, semi-isotropic 1 for x and y and 3 for z); every: steps between coupling events.
+const BAROSTAT_OFF, BAROSTAT_BERENDSEN, BAROSTAT_CRESCALE = Int32(0), Int32(1), Int32(2)
+const COUPLE_ISOTROPIC, COUPLE_SEMIISOTROPIC, COUPLE_ANISOTROPIC = Int32(0), Int32(1), Int32(2)
+set_barostat!(md::VelocityVerlet, kind, p_ref, compressibility, tau_p, every; coupling=COUPLE_ISOTROPIC, temperature=0.0, seed=0,
+              first_step=0) =
+    check(ccall((:emdee_md_set_barostat, libemdee_hip), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Float64, Int32, Float64, UInt64, UInt64), md.handle,
+                Int32(kind), Int32(coupling), Float64[p_ref[1], p_ref[2], p_ref[3]],
+                Float64[compressibility[1], compressibility[2], compressibility[3]], Float64(tau_p), Int32(every),
+                Float64(temperature), UInt64(seed), UInt64(first_step)))
 
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);
 # Atom ids keying the thermostat's noise (device Int64 vector in caller order); `nothing` = the caller index.

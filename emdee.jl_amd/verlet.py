@@ -15,6 +15,23 @@ _BONDED_SHAPE = {HARMONIC_BOND: (2, 2), HARMONIC_ANGLE: (3, 2), PERIODIC_TORSION
 # the force-field files the library ingests
 COULOMB_K_KJ_NM = 138.935457644
 
+# pressure coupling (include/emdee_hip.h: emdee_md_set_barostat)
+BAROSTAT_OFF, BAROSTAT_BERENDSEN, BAROSTAT_CRESCALE = 0, 1, 2
+COUPLE_ISOTROPIC, COUPLE_SEMIISOTROPIC, COUPLE_ANISOTROPIC = 0, 1, 2
+_COUPLINGS = {"isotropic": COUPLE_ISOTROPIC, "semiisotropic": COUPLE_SEMIISOTROPIC, "anisotropic": COUPLE_ANISOTROPIC}
+_BAROSTATS = {"off": BAROSTAT_OFF, "berendsen": BAROSTAT_BERENDSEN, "c-rescale": BAROSTAT_CRESCALE, "crescale": BAROSTAT_CRESCALE}
+
+
+def _three(v):
+    """a scalar or three numbers as three floats"""
+    try:
+        out = [float(t) for t in v]
+    except TypeError:
+        out = [float(v)] * 3
+    if len(out) != 3:
+        raise ValueError("expected a scalar or three numbers, got %d" % len(out))
+    return out
+
 
 def charge_array(charges, device):
     """charges as a contiguous float64 device vector (None: empty)."""
@@ -45,6 +62,8 @@ class VelocityVerlet:
 
     Single-GPU, reference-shaped box: VelocityVerlet(x, v, L, model, atoms).
     Domain-decomposed: pass lo/lengths/periodic and n_ghost, and drive kick_drift_/forces_/kick_."""
+
+    _coupled = False                                       # set_barostat_ has switched pressure coupling on
 
     def __init__(self, positions, velocities, L, model, atoms, skin=0.3, inv_mass=None, lo=None, lengths=None,
                  periodic=None, n_ghost=0):
@@ -80,7 +99,11 @@ class VelocityVerlet:
 
     # -- whole steps (single domain)
     def step_(self, nsteps, dt, rebuild_every=0):
-        _lib.call("emdee_md_step", self._handle, int(nsteps), float(dt), int(rebuild_every))
+        try:
+            _lib.call("emdee_md_step", self._handle, int(nsteps), float(dt), int(rebuild_every))
+        finally:
+            if self._coupled:
+                self.box()                                  # (the coupling events of the call have changed the lengths)
 
     # -- split step (domain-decomposed driver: kick_drift_ -> halo exchange -> forces_ -> kick_)
     def kick_drift_(self, dt, kick=0.5):
@@ -225,6 +248,39 @@ class VelocityVerlet:
         _lib.call("emdee_md_langevin_normals", self._handle, int(seed) & (2 ** 64 - 1), int(step),
                   C.c_void_p(ids.data_ptr()), int(ids.shape[0]), C.c_void_p(out.data_ptr()))
         return out
+
+    # -- pressure coupling (include/emdee_hip.h: emdee_md_get_box, emdee_md_scale_box, emdee_md_set_barostat; undivided boxes)
+    def box(self):
+        """(lo, lengths) of the engine's box as two lists; also refreshes self.lengths, the volume observables() and
+        pressure_tensor() divide by."""
+        lo, ln = (C.c_double * 3)(), (C.c_double * 3)()
+        _lib.call("emdee_md_get_box", self._handle, lo, ln)
+        self.lo, self.lengths = list(lo), list(ln)
+        return list(lo), list(ln)
+
+    def scale_box_(self, mu, velocity_scale=1.0):
+        """x <- lo + mu (x - lo) per axis, lengths <- mu lengths, v <- velocity_scale v; then re-bin, re-plan, rebuild and a
+        force pass on the new box.  mu: a scalar or three factors.  All or nothing (EmDeeError code -1, nothing changed, for a
+        factor that is not finite and > 0 or a periodic length that would fall below 2 (rc + skin))."""
+        try:
+            _lib.call("emdee_md_scale_box", self._handle, (C.c_double * 3)(*_three(mu)), float(velocity_scale))
+        finally:
+            self.box()
+
+    def set_barostat_(self, kind, p_ref=0.0, compressibility=0.0, tau_p=1.0, every=1, coupling="isotropic", temperature=None,
+                      seed=0, first_step=0):
+        """Pressure coupling in every later step_: kind BAROSTAT_BERENDSEN / BAROSTAT_CRESCALE (or "berendsen" / "c-rescale"),
+        BAROSTAT_OFF (or None, "off") switches it off.  p_ref and compressibility: a scalar or three entries (isotropic reads
+        entry 0, semi-isotropic 0 for x, y and 2 for z); every: steps between events; coupling: "isotropic", "semiisotropic",
+        "anisotropic" or a COUPLE_* constant; temperature (energy units), seed, first_step: C-rescale's noise."""
+        if kind is None:
+            kind = BAROSTAT_OFF
+        k = _BAROSTATS[kind.lower()] if isinstance(kind, str) else int(kind)
+        c = _COUPLINGS[coupling.lower().replace("-", "").replace("_", "")] if isinstance(coupling, str) else int(coupling)
+        _lib.call("emdee_md_set_barostat", self._handle, k, c, (C.c_double * 3)(*_three(p_ref)),
+                  (C.c_double * 3)(*_three(compressibility)), float(tau_p), int(every),
+                  0.0 if temperature is None else float(temperature), int(seed) & (2 ** 64 - 1), int(first_step))
+        self._coupled = k != BAROSTAT_OFF
 
     # -- exclusions and 1-4 pairs (include/emdee_hip.h; set after the state is loaded, undivided boxes)
     def set_exclusions_(self, pairs):

@@ -3,6 +3,7 @@
 thermostat, switch it off, run NVE, write an XYZ frame and a checkpoint, and restart from the checkpoint.
 
     python examples/lj_fluid.py [cells]        # cells^3 x 4 atoms, default 20 (32,000 atoms)
+    python examples/lj_fluid.py [cells] --npt 1.0     # ... with an NPT phase at P* = 1.0 between the two (C-rescale barostat)
 
 Needs the built library (python -c "import __graft_entry__ as g; g.build()") and a gfx950 device."""
 import os
@@ -17,7 +18,13 @@ from __graft_entry__ import load_package  # noqa: E402
 
 E = load_package()
 dev = torch.device("cuda", 0)
-cells = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+args = [a for a in sys.argv[1:]]
+p_target = None
+if "--npt" in args:
+    k = args.index("--npt")
+    p_target = float(args[k + 1])
+    del args[k:k + 2]
+cells = int(args[0]) if args else 20
 
 pos, L = E.synthetic.fcc_positions(cells)                       # jittered fcc lattice at rho* = 0.8
 N = pos.shape[0]
@@ -32,6 +39,16 @@ md.set_langevin_(gamma=2.0, temperature=0.9, seed=2026)          # NVT: v = c1 v
 md.step_(2000, dt)
 obs = md.observables()
 print("after 2000 thermostatted steps: T* = %.4f  P* = %.4f  U/N = %.4f" % (obs["temperature"], obs["pressure"], obs["potential"] / N))
+
+if p_target is not None:
+    # NPT: the thermostat stays on, the box follows the pressure (stochastic cell rescaling every 10 steps; compressibility
+    # and tau_p in reduced units, the first of the order of the liquid's 1 / bulk modulus)
+    md.set_barostat_(E.BAROSTAT_CRESCALE, p_target, 0.05, tau_p=1.0, every=10, temperature=0.9, seed=2026)
+    md.step_(4000, dt)
+    md.set_barostat_(E.BAROSTAT_OFF)                             # the box stays as the last event left it
+    L = md.box()[1][0]                                           # (isotropic coupling keeps the box cubic)
+    obs = md.observables()
+    print("after 4000 NPT steps at P* = %.2f: L = %.4f  rho* = %.4f  T* = %.4f  P* = %.4f" % (p_target, L, obs["density"], obs["temperature"], obs["pressure"]))
 
 md.set_langevin_(0.0, 0.0)                                       # NVE from here
 e0 = sum(md.totals()[:2])

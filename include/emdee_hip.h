@@ -361,6 +361,67 @@ int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);
 int32_t emdee_md_langevin_normals(emdee_md *md, uint64_t seed, uint64_t step, const int64_t *ids_dev, int32_t n,
                                   double *out_dev);
 
+/* Pressure coupling (build-defined like the integrator and the thermostat: the reference has neither).  The box of an
+ * undivided integrator is no longer fixed at create: emdee_md_scale_box rescales box, positions and velocities, and
+ * emdee_md_set_barostat makes emdee_md_step do so every `every` steps from the pressure the engine measures itself.
+ *
+ * emdee_md_get_box: the current lo and len (len changes with every scale; lo never does).
+ *
+ * emdee_md_scale_box(mu, velocity_scale), the primitive (also for callers who drive the split calls):
+ *   x_d   <- lo_d + mu_d (x_d - lo_d)        every owned atom, in fp64 arithmetic in both precisions (the unwrapped coordinate
+ *                                            emdee_md_get_state returns scales the same way: image counts are kept)
+ *   len_d <- mu_d len_d ;  lo stays
+ *   v     <- velocity_scale v                (1.0 leaves the velocities bit for bit)
+ * then the engine re-bins on the new box, re-plans, rebuilds the list and evaluates the forces at the new positions, as
+ * emdee_md_rebuild followed by a force pass: on return forces, energies and virials belong to the new box.  Exclusion, 1-4,
+ * bonded and charge tables stay in force (their slots are re-recorded by the rebuild).  The scaling is atomic, not by molecule
+ * centres.  All or nothing:
+ *   - EMDEE_ERR_INVALID, with box, state and list untouched and the engine still able to step, for a non-finite or
+ *     non-positive mu_d or velocity_scale, and for a new periodic length below 2 (rc + skin);
+ *   - EMDEE_ERR_STATE before emdee_md_set_state, with ghosts, and on an integrator lent by emdee_dd_engine.
+ * emdee_md_step always returns with its last half kick closed, so a scale between two calls of it acts on full-step
+ * velocities and on forces of the unscaled positions; a caller of the split calls closes its own (emdee_md_kick) first.
+ *
+ * emdee_md_set_barostat switches coupling on for every later emdee_md_step of this integrator (kind = EMDEE_BAROSTAT_OFF:
+ * off; the other arguments are then not looked at).  Steps are numbered from first_step, as for the thermostat.  After the
+ * step that brings the count s to a multiple of `every`, with Dt = every dt, V the volume and the instantaneous pressure
+ * P^aa = (K^aa + W^aa) / V from the deterministic fp64 sums of emdee_md_pressure_tensor (isotropic: P = (2 KE + W) / (3 V)
+ * from the sums of emdee_md_energies, which the event's own force pass evaluates -- the event's one read-back):
+ *   Berendsen:   mu_d = 1 - (Dt / (3 tau_p)) beta_d (P_ref,d - P_d),  velocity_scale = 1
+ *     isotropic:       one factor from P = (Pxx + Pyy + Pzz) / 3, p_ref[0], compressibility[0]
+ *     semi-isotropic:  x and y share a factor from (Pxx + Pyy) / 2, p_ref[0], compressibility[0]; z its own from Pzz,
+ *                      p_ref[2], compressibility[2]
+ *     anisotropic:     three factors from Pxx, Pyy, Pzz and their own entries; the box stays orthorhombic
+ *   C-rescale (stochastic cell rescaling, Bernetti & Bussi, J. Chem. Phys. 153, 114107 (2020); isotropic only):
+ *     d_eps = -(beta / tau_p) (P_ref - P) Dt + sqrt(2 T beta Dt / (V tau_p)) xi
+ *     mu = exp(d_eps / 3) on all three sides, velocity_scale = 1 / mu
+ *     T = temperature in energy units (as emdee_md_set_langevin takes it); xi = component 0 of the thermostat's generator at
+ *     (seed, s, id = -1), i.e. out_dev[0] of emdee_md_langevin_normals(md, seed, s, {-1}, 1, out_dev): a run is reproducible.
+ * and then emdee_md_scale_box(mu, velocity_scale).  A coupling event always rebuilds; a fixed rebuild_every cadence restarts
+ * from the event.  A refusal from the scale (a box shrunk below 2 (rc + skin), a non-finite mu from a NaN pressure) comes
+ * back as EMDEE_ERR_STATE from emdee_md_step, the state being that of the completed step before the event.
+ * With coupling on, emdee_md_step closes the half kick of every step (kick + drift, force pass, kick; no merged kicks and no
+ * run-ahead): the states after s steps do not depend on how the steps were dealt to calls -- step(40), 8 x step(5) and
+ * 40 x step(1) agree bit for bit -- no step is queued beyond an event, and the run stays bitwise reproducible.  The split
+ * calls (emdee_md_kick_drift, _forces, _kick, _fused_step) never couple on their own.
+ *   - All or nothing: EMDEE_ERR_INVALID, the previous setting in force, for an unknown kind or coupling, every < 1, tau_p
+ *     not finite or <= 0, a non-finite p_ref, a negative or non-finite compressibility (all three entries are checked), a
+ *     NULL array, C-rescale with another coupling than isotropic or with temperature <= 0.
+ *   - EMDEE_ERR_STATE on an integrator lent by emdee_dd_engine and on one with ghosts.
+ * Scope: undivided orthorhombic boxes.  There is no emdee_dd_set_barostat -- the domain geometry of emdee_dd is fixed at
+ * create --, nothing on the operator path, no triclinic box, no long-range dispersion correction to the pressure. */
+#define EMDEE_BAROSTAT_OFF        0
+#define EMDEE_BAROSTAT_BERENDSEN  1
+#define EMDEE_BAROSTAT_CRESCALE   2     /* stochastic cell rescaling, Bernetti & Bussi 2020 */
+#define EMDEE_COUPLE_ISOTROPIC     0    /* one factor from P = (Pxx+Pyy+Pzz)/3 */
+#define EMDEE_COUPLE_SEMIISOTROPIC 1    /* x and y share a factor from (Pxx+Pyy)/2, z its own from Pzz */
+#define EMDEE_COUPLE_ANISOTROPIC   2    /* three factors from Pxx, Pyy, Pzz; the box stays orthorhombic */
+int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);
+int32_t emdee_md_scale_box(emdee_md *md, const double mu[3], double velocity_scale);
+int32_t emdee_md_set_barostat(emdee_md *md, int32_t kind, int32_t coupling, const double p_ref[3],
+                              const double compressibility[3], double tau_p, int32_t every, double temperature,
+                              uint64_t seed, uint64_t first_step);
+
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
  * The periodic box [0, len_d) is cut into grid[0] x grid[1] x grid[2] bricks (at most 3 per dimension), domain
