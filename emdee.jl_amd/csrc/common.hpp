@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/emdee_hip.h"
+#include "error.hpp"
 
 namespace emdee {
 
@@ -27,14 +28,7 @@ constexpr int TENSOR_PASS = EMDEE_ENERGIES | EMDEE_VIRIALS | EMDEE_TENSOR;
 // charged engine (lj_pair.hpp Charges).  Never part of a public bitmask; instances without it are the uncharged kernels.
 constexpr int EMDEE_CHARGED = 64;
 
-// ---- error plumbing: no exception crosses the C ABI -------------------------------------------
-void set_error(const char *fmt, ...);
-const char *get_error();
-
-struct Failure {
-    int32_t code;
-};
-
+// ---- error plumbing: error.hpp (set_error, get_error, Failure, EMDEE_REQUIRE), and the check of a HIP call
 #define EMDEE_HIP_CHECK(expr)                                                                    \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
@@ -42,14 +36,6 @@ struct Failure {
             ::emdee::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
             (void)hipGetLastError(); /* reported here: do not leave it for an unrelated later call */ \
             throw ::emdee::Failure{EMDEE_ERR_HIP};                                               \
-        }                                                                                        \
-    } while (0)
-
-#define EMDEE_REQUIRE(cond, code, ...)                                                           \
-    do {                                                                                         \
-        if (!(cond)) {                                                                           \
-            ::emdee::set_error(__VA_ARGS__);                                                     \
-            throw ::emdee::Failure{code};                                                        \
         }                                                                                        \
     } while (0)
 

@@ -1234,102 +1234,86 @@ struct DdImpl : IDd {
     }
 
     // ---------------------------------------------------------------- exclusions and 1-4 pairs (emdee_dd_set_exclusions / _set_pairs14)
-    // One copy of the tables per process, over GLOBAL ids (nbsys.hpp PairTables): every local engine points at it and keys its
+    // One copy of the tables per process, over GLOBAL ids (topology_dev.hpp Topology): every local engine points at it and keys its
     // rows by the tags that travel with the atoms.
-    PairTables tables;
+    Topology tables;
     bool has_tables() const { return tables.has_excl; }
     // Collective.  one_four: the 1-4 table (scaled by lj14scale), else the exclusions; n = 0 clears it.  All or nothing: an invalid
     // pair throws before anything changes.  After a load the engines are loaded again from their own states (same atoms, same
     // owners, same ghosts: nothing travels), so the rows, the 1-4 slots and the forces follow the new tables on return.
     void set_pair_table(const int64_t *pairs, int64_t n, bool one_four, double scale) override {
         use_device(user_ctx);
-        join_halo();                                         // nothing in flight reads the old tables any more
-        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+        quiesce();                                           // nothing in flight reads the old tables any more
         tables.set(pairs, n, one_four, scale, (int64_t)1 << 31, user_ctx->stream);
-        if (!loaded) return;
-        for (auto &pd : dom) {
-            Domain<real> &d = *pd;
-            export_caller_arrays(d, d.ids.ptr, d.n_send);
-            load_engine(d, true);
-        }
-        EMDEE_HIP_CHECK(hipGetLastError());
+        if (loaded) reload_engines();
     }
-
-    // Collective.  The bonded table of one kind over global ids (nbsys.hpp PairTables::set_bonded), as set_pair_table: all or
+    // Collective.  The bonded table of one kind over global ids (topology_dev.hpp Topology::set_bonded), as set_pair_table: all or
     // nothing, and after a load every domain is loaded again, so the partners' slots and the forces are current on return.
     void set_bonded(int32_t kind, const int64_t *atoms, const double *params, int64_t n) override {
         use_device(user_ctx);
-        join_halo();
-        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+        quiesce();
         tables.set_bonded(kind, atoms, params, n, (int64_t)1 << 31, user_ctx->stream);
-        if (!loaded) return;
-        for (auto &pd : dom) {
-            Domain<real> &d = *pd;
-            d.sys().reset_bonded_error();
-            export_caller_arrays(d, d.ids.ptr, d.n_send);
-            load_engine(d, true);
-        }
-        EMDEE_HIP_CHECK(hipGetLastError());
+        if (!loaded) return;                                 // (the bonded error is reset by load(), not here)
+        for (auto &pd : dom) pd->sys().reset_bonded_error();
+        reload_engines();
         check_bonded();
     }
-    // Collective.  The charges over global ids (nbsys.hpp PairTables::set_charges), as set_pair_table: all or nothing, and after a
+    // Collective.  The charges over global ids (topology_dev.hpp Topology::set_charges), as set_pair_table: all or nothing, and after a
     // load every domain is loaded again (its charge plane is filled by tag), so the forces include them on return.  A domain atom
     // whose id has no charge is reported on every rank (check_charges).
     void set_coulomb(const double *charges, int64_t n, double coulomb_k, double eps_rf, double coulomb14scale) override {
         use_device(user_ctx);
-        join_halo();
-        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+        quiesce();
         tables.set_charges(charges, n, coulomb_k, eps_rf, coulomb14scale, -1, user_ctx->stream);
-        for (auto &pd : dom) pd->sys().reset_charge_error();
+        for (auto &pd : dom) pd->sys().reset_charge_error();   // (before a load as well, where load() resets it again)
         if (!loaded) return;
-        for (auto &pd : dom) {
-            Domain<real> &d = *pd;
-            export_caller_arrays(d, d.ids.ptr, d.n_send);
-            load_engine(d, true);
-        }
-        EMDEE_HIP_CHECK(hipGetLastError());
+        reload_engines();
         check_charges();
     }
-    // Collective and blocking: EMDEE_ERR_STATE on every rank if an atom of a domain has an id outside the charge table
-    // (NbSystem::check_charges); every domain then refuses to step until the charges are set again
-    void check_charges() {
-        if (!tables.has_charges) return;
+    // join the halo and wait for every domain stream: nothing in flight reads what the caller is about to replace
+    void quiesce() {
+        join_halo();
+        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+    }
+    // every engine loaded again from its own state (same atoms, same owners, same ghosts: nothing travels)
+    void reload_engines() {
+        for (auto &pd : dom) {
+            export_caller_arrays(*pd, pd->ids.ptr, pd->n_send);
+            load_engine(*pd, true);
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    // Collective and blocking: every rank throws EMDEE_ERR_STATE if `probe` throws on a domain of any rank, and every domain of
+    // every rank then sets `broken` and refuses to step, so that no rank enters a step's collectives alone.  The message is the
+    // probe's on the rank that holds the domain, `elsewhere` on the others.
+    template <class Probe>
+    void agree_or_refuse(bool active, Probe &&probe, bool NbSystem<real>::*broken, const char *elsewhere) {
+        if (!active) return;
         join_halo();
         std::vector<std::vector<double>> bad;
         bool mine = false;
         for (auto &pd : dom) {
             double b = 0.0;
-            try { pd->sys().ensure_charges(); pd->sys().check_charges(); } catch (const Failure &) { b = 1.0; mine = true; }
+            try { probe(pd->sys()); } catch (const Failure &) { b = 1.0; mine = true; }
             bad.push_back({b});
         }
         double total = 0.0;
         allreduce_sum(bad, 1, &total);
         if (total > 0.0) {
-            for (auto &pd : dom) pd->sys().charge_broken = true;
-            if (!mine) set_error("an atom of another domain has an id outside the charge table: set the charges again");
+            for (auto &pd : dom) pd->sys().*broken = true;
+            if (!mine) set_error("%s", elsewhere);
             throw Failure{EMDEE_ERR_STATE};
         }
     }
-    // Collective and blocking: EMDEE_ERR_STATE on every rank if a domain's bonded term has lost a partner (NbSystem::check_bonded;
-    // the message names the term on the rank that holds it)
+    // an atom of a domain has an id outside the charge table (NbSystem::check_charges): the charges must be set again
+    void check_charges() {
+        agree_or_refuse(tables.has_charges, [](NbSystem<real> &s) { s.ensure_charges(); s.check_charges(); }, &NbSystem<real>::charge_broken,
+                        "an atom of another domain has an id outside the charge table: set the charges again");
+    }
+    // a domain's bonded term has lost a partner (NbSystem::check_bonded; the message names the term on the rank that holds it)
     void check_bonded() {
-        if (!tables.has_bonded) return;
-        join_halo();
-        std::vector<std::vector<double>> bad;
-        bool mine = false;
-        for (auto &pd : dom) {
-            double b = 0.0;
-            try { pd->sys().check_bonded(); } catch (const Failure &) { b = 1.0; mine = true; }
-            bad.push_back({b});
-        }
-        double total = 0.0;
-        allreduce_sum(bad, 1, &total);
-        if (total > 0.0) {
-            // every domain of every rank refuses to step from now on, so that no rank enters a step's collectives alone
-            for (auto &pd : dom) pd->sys().bonded_broken = true;
-            if (!mine) set_error("a bonded term of another domain has lost a partner: replace the tables or the state");
-            throw Failure{EMDEE_ERR_STATE};
-        }
+        agree_or_refuse(tables.has_bonded, [](NbSystem<real> &s) { s.check_bonded(); }, &NbSystem<real>::bonded_broken,
+                        "a bonded term of another domain has lost a partner: replace the tables or the state");
     }
 
     // ---------------------------------------------------------------- stepping
@@ -1601,8 +1585,7 @@ struct DdImpl : IDd {
         out[3] = dom.empty() ? 0 : dom[0]->gs_caps.start[dom[0]->geo.npeers];
     }
     void set_overlap(bool on) override {
-        join_halo();
-        for (auto &pd : dom) EMDEE_HIP_CHECK(hipStreamSynchronize(pd->stream()));
+        quiesce();
         overlap = on;
     }
 };

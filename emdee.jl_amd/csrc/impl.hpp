@@ -530,43 +530,38 @@ struct MdImpl : IMd {
         sys.set_langevin(gamma, temperature, seed, first_step, sys.lgv_ids);
     }
     void set_langevin_ids(const int64_t *ids) override { sys.lgv_ids = reinterpret_cast<const long long *>(ids); }
-    void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) override {
+    // The install path of the three table setters: refused on a domain's engine (`entry`: the decomposition's call for `what`)
+    // and without a loaded, ghost-free state; then `set` replaces the table and resets what it must, and the list, the plan and
+    // the forces follow the new tables on return.
+    template <class Set>
+    void install(const char *what, const char *entry, Set &&set) {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "exclusions / 1-4 pairs of a decomposed run: emdee_dd_set_exclusions / emdee_dd_set_pairs14 (this integrator is a domain's, lent by emdee_dd_engine)");
-        EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "exclusions / 1-4 pairs: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
-        sys.set_pair_tables(sys.n_owned, pairs, n_pairs, one_four, lj14scale);
-        sys.resort();                                        // the list without the named pairs (a two-species box leaves the typed kernels)
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s of a decomposed run: %s (this integrator is a domain's, lent by emdee_dd_engine)", what, entry);
+        EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "%s: set them on a loaded integrator without ghosts (call emdee_md_set_state first)", what);
+        set();
+        sys.has_list = false; sys.plan_valid = false;        // (the rows in use follow the old tables; charged and uncharged engines take different kernels and LDS plans)
+        sys.resort();                                        // the list, rows and slots for the new tables (a two-species box leaves the typed kernels)
         since_build = 0;
         sys.compute_forces(EMDEE_FORCES);
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) override {
+        install("exclusions / 1-4 pairs", "emdee_dd_set_exclusions / emdee_dd_set_pairs14",
+                [&] { sys.set_pair_tables(sys.n_owned, pairs, n_pairs, one_four, lj14scale); });
     }
     void set_bonded(int32_t kind, const int32_t *atoms, const double *params, int32_t n_terms) override {
-        use_device(sys.ctx);
-        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "bonded terms of a decomposed run: emdee_dd_set_bonded (this integrator is a domain's, lent by emdee_dd_engine)");
-        EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "bonded terms: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
-        sys.own_tables.set_bonded(kind, atoms, params, n_terms, sys.n_owned, sys.stream());
-        sys.has_list = false; sys.plan_valid = false;
-        sys.reset_bonded_error();
-        sys.resort();                                        // the rows and slots for the new partners (a two-species box leaves the typed kernels)
-        since_build = 0;
-        sys.compute_forces(EMDEE_FORCES);
-        current_mask = EMDEE_FORCES;
-        EMDEE_HIP_CHECK(hipGetLastError());
-        sys.check_bonded();
+        install("bonded terms", "emdee_dd_set_bonded", [&] {
+            sys.own_tables.set_bonded(kind, atoms, params, n_terms, sys.n_owned, sys.stream());
+            sys.reset_bonded_error();
+        });
+        sys.check_bonded();                                  // (blocking read-back; throws if a term spans more than the list radius)
     }
     void set_coulomb(const double *charges, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) override {
-        use_device(sys.ctx);
-        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "charges of a decomposed run: emdee_dd_set_coulomb (this integrator is a domain's, lent by emdee_dd_engine)");
-        EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "charges: set them on a loaded integrator without ghosts (call emdee_md_set_state first)");
-        sys.own_tables.set_charges(charges, n, coulomb_k, eps_rf, coulomb14scale, sys.n_owned, sys.stream());
-        sys.reset_charge_error();
-        sys.has_list = false; sys.plan_valid = false;
-        sys.resort();                                        // (charged and uncharged engines take different kernels and LDS plans)
-        since_build = 0;
-        sys.compute_forces(EMDEE_FORCES);
-        current_mask = EMDEE_FORCES;
-        EMDEE_HIP_CHECK(hipGetLastError());
+        install("charges", "emdee_dd_set_coulomb", [&] {
+            sys.own_tables.set_charges(charges, n, coulomb_k, eps_rf, coulomb14scale, sys.n_owned, sys.stream());
+            sys.reset_charge_error();
+        });
     }
     void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) override {
         use_device(sys.ctx);

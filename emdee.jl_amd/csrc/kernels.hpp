@@ -1218,7 +1218,7 @@ __device__ __forceinline__ long long pair_key(const PairKeys &k, const int *__re
     return k.tag ? k.tag[slot] : (long long)perm[slot];
 }
 
-// Bonded terms (emdee_*_set_bonded; nbsys.hpp PairTables): a CSR per atom key, keyed as PairKeys.  Row gi lists the atom's
+// Bonded terms (emdee_*_set_bonded; topology_dev.hpp Topology): a CSR per atom key, keyed as PairKeys.  Row gi lists the atom's
 // bonded partners (pidx[pstart[gi] .. pstart[gi + 1]), ascending) and its terms (terms[tstart[gi] .. tstart[gi + 1])): x = kind
 // | role << 2 (role: the atom's position in the term), y, z, w = the other atoms of the term, in term order, as positions in
 // the atom's partner list.  The row filter records each partner's cell-order slot in slots[] (-1: not in the row at the build).

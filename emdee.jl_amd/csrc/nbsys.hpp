@@ -10,6 +10,7 @@
 
 #include "brick.hpp"
 #include "kernels.hpp"
+#include "topology_dev.hpp"
 #include "typed.hpp"
 
 namespace emdee {
@@ -97,258 +98,6 @@ static inline void allow_big_lds(K kernel, size_t bytes) {
         EMDEE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
-
-// Exclusions and scaled 1-4 pairs (kernels.hpp, "exclusions and 1-4 pairs"; the hooks of src/modelling.jl:197-200): pairs the
-// caller names are struck from the rows right after every build, and the 1-4 pairs among them come back scaled by lj14scale
-// after every force pass.  The topology does not change during a run: both tables are symmetric, sorted, duplicate-free CSRs
-// built on the host once per call.  An undivided engine owns one over caller ids (NbSystem::own_tables); a decomposition owns
-// one over global ids that all its engines point at (dd.hpp), which is simpler than carrying each atom's partners through
-// migration: 4 (max id + 2) + 4 (directed pairs) bytes per table.
-struct PairTables {
-    DevBuf<int> x_start, x_idx;                              // struck from the rows: the exclusions and the 1-4 pairs together
-    DevBuf<int> p_start, p_idx;                              // the 1-4 pairs
-    std::vector<int32_t> excl, p14;                          // the pairs as given: {i, j, i, j, ...}
-    double scale14 = 1.0;
-    int rows = 0;                                            // ids 0 .. rows - 1 have rows (max id + 1)
-    int64_t limit = 0;                                       // ids of the last call lay in [0, limit): the atom count, or 2^31 (global ids)
-    size_t n14 = 0;                                          // entries of the 1-4 CSR
-    bool has_excl = false, has_14 = false;
-
-    // pairs of the lists a and b -> rows 0 .. rows - 1: start[rows + 1], partners ascending, no duplicates
-    static void csr(const std::vector<int32_t> &a, const std::vector<int32_t> &b, int rows, std::vector<int32_t> &st,
-                    std::vector<int32_t> &ix) {
-        st.assign((size_t)rows + 1, 0);
-        for (const std::vector<int32_t> *h : {&a, &b})
-            for (size_t k = 0; k < h->size(); k++) st[(size_t)(*h)[k] + 1]++;
-        for (int r = 0; r < rows; r++) st[(size_t)r + 1] += st[r];
-        ix.assign(st[rows], 0);
-        std::vector<int32_t> at(st.begin(), st.end() - 1);
-        for (const std::vector<int32_t> *h : {&a, &b})
-            for (size_t k = 0; k + 1 < h->size(); k += 2) {
-                const int32_t g = (*h)[k], q = (*h)[k + 1];
-                ix[at[g]++] = q;
-                ix[at[q]++] = g;
-            }
-        size_t w = 0;
-        for (int r = 0; r < rows; r++) {
-            const size_t lo = st[r], hi = st[(size_t)r + 1];
-            std::sort(ix.begin() + lo, ix.begin() + hi);
-            st[r] = (int32_t)w;
-            for (size_t k = lo; k < hi; k++)
-                if (k == lo || ix[k] != ix[k - 1]) ix[w++] = ix[k];
-        }
-        st[rows] = (int32_t)w;
-        ix.resize(w);
-    }
-    static void upload(DevBuf<int> &b, const std::vector<int32_t> &h, hipStream_t s) {
-        b.ensure(h.size() + 1);
-        if (!h.empty()) EMDEE_HIP_CHECK(hipMemcpyAsync(b.ptr, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
-    // Replaces one table by the n pairs at pairs_dev (device, {i, j, ...}): one_four, the 1-4 pairs scaled by `scale`, else the
-    // exclusions; n = 0 clears it.  All or nothing: every pair given is checked against [0, lim) and both CSRs are uploaded
-    // into buffers of their own before anything changes, so an invalid call throws and leaves both tables in force.
-    // The caller makes sure nothing in flight reads the old tables.
-    template <typename T>
-    void set(const T *pairs_dev, int64_t n, bool one_four, double scale, int64_t lim, hipStream_t s) {
-        const char *what = one_four ? "set_pairs14" : "set_exclusions";
-        EMDEE_REQUIRE(n >= 0 && (n == 0 || pairs_dev), EMDEE_ERR_INVALID, "%s: negative count or NULL array", what);
-        EMDEE_REQUIRE(!one_four || std::isfinite(scale), EMDEE_ERR_INVALID, "%s: lj14scale must be finite", what);
-        std::vector<T> raw((size_t)2 * n);
-        if (n > 0) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(raw.data(), pairs_dev, raw.size() * sizeof(T), hipMemcpyDeviceToHost, s));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        }
-        for (int64_t k = 0; k < n; k++) {
-            const int64_t i = raw[2 * k], j = raw[2 * k + 1];
-            EMDEE_REQUIRE(i != j && i >= 0 && j >= 0 && i < lim && j < lim, EMDEE_ERR_INVALID,
-                          "%s: pair %lld = (%lld, %lld) is not a pair of two different ids in [0, %lld)", what, (long long)k,
-                          (long long)i, (long long)j, (long long)lim);
-        }
-        const std::vector<int32_t> h(raw.begin(), raw.end());
-        const std::vector<int32_t> &ex = one_four ? excl : h, &pp = one_four ? h : p14;
-        int r = 0;
-        for (const std::vector<int32_t> *t : {&ex, &pp})
-            for (int32_t g : *t) r = std::max(r, g + 1);
-        std::vector<int32_t> xs, xi, ps, pi;
-        csr(ex, pp, r, xs, xi);
-        csr(pp, std::vector<int32_t>{}, r, ps, pi);
-        DevBuf<int> nxs, nxi, nps, npi;
-        upload(nxs, xs, s); upload(nxi, xi, s); upload(nps, ps, s); upload(npi, pi, s);
-        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        // ---- commit
-        x_start.swap(nxs); x_idx.swap(nxi); p_start.swap(nps); p_idx.swap(npi);
-        if (one_four) { p14 = h; scale14 = scale; } else { excl = h; }
-        rows = r; limit = lim; n14 = pi.size();
-        has_excl = !xi.empty(); has_14 = !pi.empty();
-    }
-
-    // ---- bonded terms (emdee_*_set_bonded): kernels.hpp BondedKeys.  Rows 0 .. b_rows - 1 list each atom's bonded partners and
-    // its terms; the terms as given are kept per kind (b_atoms, b_prm) so that one kind can be replaced without the others.
-    static constexpr int KINDS = 4;                          // kinds 1 (bond), 2 (angle), 3 (torsion)
-    static int kind_atoms(int kind) { return kind + 1; }
-    static int kind_params(int kind) { return kind == 3 ? 3 : 2; }
-    std::vector<int32_t> b_atoms[KINDS];
-    std::vector<double> b_prm[KINDS];
-    DevBuf<int> b_pstart, b_pidx, b_tstart, b_tid;
-    DevBuf<int4> b_terms;
-    DevBuf<double> b_prm_d;
-    DevBuf<float> b_prm_f;
-    int b_rows = 0;
-    size_t nb = 0;                                           // entries of the partner CSR (slots of the row filter)
-    bool has_bonded = false;
-    template <typename real>
-    const real *bonded_params() const {
-        if constexpr (sizeof(real) == 8) return b_prm_d.ptr; else return b_prm_f.ptr;
-    }
-    // term number (over all kinds, in kind order) -> kind and index within it
-    void bonded_term_of(int64_t id, int &kind, int64_t &index) const {
-        for (kind = 1; kind < KINDS - 1 && id >= (int64_t)(b_atoms[kind].size() / kind_atoms(kind)); kind++)
-            id -= (int64_t)(b_atoms[kind].size() / kind_atoms(kind));
-        index = id;
-    }
-    // Replaces the table of one kind by the n terms at atoms_dev / params_dev (device; kind_atoms(kind) ids and
-    // kind_params(kind) doubles per term); n = 0 clears it.  All or nothing, as set().
-    template <typename T>
-    void set_bonded(int kind, const T *atoms_dev, const double *params_dev, int64_t n, int64_t lim, hipStream_t s) {
-        EMDEE_REQUIRE(kind >= 1 && kind <= 3, EMDEE_ERR_INVALID, "set_bonded: unknown kind %d (EMDEE_HARMONIC_BOND, "
-                      "EMDEE_HARMONIC_ANGLE or EMDEE_PERIODIC_TORSION)", kind);
-        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && params_dev)), EMDEE_ERR_INVALID, "set_bonded: negative count or NULL array");
-        const int na = kind_atoms(kind), np = kind_params(kind);
-        std::vector<T> raw((size_t)na * n);
-        std::vector<double> prm((size_t)np * n);
-        if (n > 0) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(raw.data(), atoms_dev, raw.size() * sizeof(T), hipMemcpyDeviceToHost, s));
-            EMDEE_HIP_CHECK(hipMemcpyAsync(prm.data(), params_dev, prm.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        }
-        static const char *const names[KINDS] = {"", "bond", "angle", "torsion"};
-        for (int64_t k = 0; k < n; k++) {
-            for (int a = 0; a < na; a++) {
-                const int64_t g = raw[(size_t)na * k + a];
-                EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_bonded: %s %lld names id %lld, outside [0, %lld)", names[kind],
-                              (long long)k, (long long)g, (long long)lim);
-                for (int b = 0; b < a; b++)
-                    EMDEE_REQUIRE(raw[(size_t)na * k + b] != raw[(size_t)na * k + a], EMDEE_ERR_INVALID,
-                                  "set_bonded: %s %lld names atom %lld twice", names[kind], (long long)k, (long long)g);
-            }
-            const double *q = prm.data() + (size_t)np * k;
-            for (int c = 0; c < np; c++)
-                EMDEE_REQUIRE(std::isfinite(q[c]), EMDEE_ERR_INVALID, "set_bonded: %s %lld has a non-finite parameter", names[kind], (long long)k);
-            if (kind == 1) EMDEE_REQUIRE(q[1] >= 0.0, EMDEE_ERR_INVALID, "set_bonded: bond %lld has r0 < 0", (long long)k);
-            if (kind == 2) EMDEE_REQUIRE(q[1] >= 0.0 && q[1] <= M_PI, EMDEE_ERR_INVALID, "set_bonded: angle %lld has theta0 outside [0, pi]", (long long)k);
-            if (kind == 3) EMDEE_REQUIRE(q[1] >= 1.0 && q[1] == std::floor(q[1]), EMDEE_ERR_INVALID,
-                                         "set_bonded: torsion %lld has a periodicity that is not an integer >= 1", (long long)k);
-        }
-        int64_t total = n;
-        for (int kd = 1; kd < KINDS; kd++)
-            if (kd != kind) total += (int64_t)(b_atoms[kd].size() / kind_atoms(kd));
-        EMDEE_REQUIRE(total < INT32_MAX, EMDEE_ERR_INVALID, "set_bonded: %lld terms in all (at most 2^31 - 2)", (long long)total);
-        const std::vector<int32_t> h(raw.begin(), raw.end());
-        const std::vector<int32_t> *at[KINDS];
-        const std::vector<double> *pr[KINDS];
-        for (int kd = 1; kd < KINDS; kd++) { at[kd] = kd == kind ? &h : &b_atoms[kd]; pr[kd] = kd == kind ? &prm : &b_prm[kd]; }
-        // partners: (owner, partner) over every role of every term -> CSR, ascending, unique
-        int r = 0;
-        for (int kd = 1; kd < KINDS; kd++)
-            for (int32_t g : *at[kd]) r = std::max(r, g + 1);
-        std::vector<int32_t> half;                           // each partner pair once (csr() makes the rows symmetric)
-        for (int kd = 1; kd < KINDS; kd++) {
-            const int nk = kind_atoms(kd);
-            for (size_t t = 0; t + nk <= at[kd]->size(); t += nk)
-                for (int a = 0; a < nk; a++)
-                    for (int b = 0; b < nk; b++)
-                        if ((*at[kd])[t + a] < (*at[kd])[t + b]) { half.push_back((*at[kd])[t + a]); half.push_back((*at[kd])[t + b]); }
-        }
-        std::vector<int32_t> ps, pi;
-        csr(half, std::vector<int32_t>{}, r, ps, pi);
-        // term entries, in (kind, term, role) order within each row
-        std::vector<int32_t> ts((size_t)r + 1, 0);
-        for (int kd = 1; kd < KINDS; kd++)
-            for (int32_t g : *at[kd]) ts[(size_t)g + 1]++;
-        for (int q = 0; q < r; q++) ts[(size_t)q + 1] += ts[q];
-        std::vector<int4> terms(ts[r]);
-        std::vector<int32_t> tid(ts[r]);
-        std::vector<double> pd((size_t)3 * ts[r], 0.0);
-        std::vector<float> pf((size_t)3 * ts[r], 0.f);
-        std::vector<int32_t> fill(ts.begin(), ts.end() - 1);
-        int32_t number = 0;
-        for (int kd = 1; kd < KINDS; kd++) {
-            const int nk = kind_atoms(kd), npk = kind_params(kd);
-            for (size_t t = 0; t + nk <= at[kd]->size(); t += nk, number++) {
-                const int32_t *ids = at[kd]->data() + t;
-                const double *q = pr[kd]->data() + (t / nk) * npk;
-                for (int role = 0; role < nk; role++) {
-                    const int32_t g = ids[role];
-                    const int e = fill[g]++;
-                    int loc[3] = {0, 0, 0}, c = 0;
-                    for (int a = 0; a < nk; a++) {
-                        if (a == role) continue;
-                        const auto it = std::lower_bound(pi.begin() + ps[g], pi.begin() + ps[(size_t)g + 1], ids[a]);
-                        loc[c++] = (int)(it - (pi.begin() + ps[g]));
-                    }
-                    terms[e] = make_int4(kd | role << 2, loc[0], loc[1], loc[2]);
-                    tid[e] = number;
-                    for (int c2 = 0; c2 < npk; c2++) { pd[(size_t)3 * e + c2] = q[c2]; pf[(size_t)3 * e + c2] = (float)q[c2]; }
-                }
-            }
-        }
-        DevBuf<int> nps, npi, nts, ntid;
-        DevBuf<int4> nterms;
-        DevBuf<double> npd;
-        DevBuf<float> npf;
-        upload(nps, ps, s); upload(npi, pi, s); upload(nts, ts, s); upload(ntid, tid, s);
-        nterms.ensure(terms.size() + 1); npd.ensure(pd.size() + 1); npf.ensure(pf.size() + 1);
-        if (!terms.empty()) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(nterms.ptr, terms.data(), terms.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-            EMDEE_HIP_CHECK(hipMemcpyAsync(npd.ptr, pd.data(), pd.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            EMDEE_HIP_CHECK(hipMemcpyAsync(npf.ptr, pf.data(), pf.size() * sizeof(float), hipMemcpyHostToDevice, s));
-        }
-        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        // ---- commit
-        b_pstart.swap(nps); b_pidx.swap(npi); b_tstart.swap(nts); b_tid.swap(ntid); b_terms.swap(nterms);
-        b_prm_d.swap(npd); b_prm_f.swap(npf);
-        b_atoms[kind] = h; b_prm[kind] = prm;
-        b_rows = r; limit = lim; nb = pi.size();
-        has_bonded = !terms.empty();
-    }
-
-    // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the
-    // reaction-field constants.  Every engine keeps a plane of them in its own cell order (NbSystem::qp).
-    DevBuf<double> q_tab;
-    int64_t q_n = 0;                                         // keys 0 .. q_n - 1 have a charge
-    double coulomb_k = 0.0, eps_rf = INFINITY, scale14c = 1.0;
-    bool has_charges = false;
-    // Replaces the charges by the n at charges_dev (device, fp64, one per key); n = 0 clears them.  want >= 0: the only
-    // non-zero n accepted (an undivided engine's atom count).  All or nothing, as set().
-    void set_charges(const double *charges_dev, int64_t n, double K, double eps, double s14, int64_t want, hipStream_t s) {
-        EMDEE_REQUIRE(n >= 0 && (n == 0 || charges_dev), EMDEE_ERR_INVALID, "set_coulomb: negative count or NULL array");
-        if (n == 0) {                                        // (clearing needs no constants)
-            has_charges = false; q_n = 0;
-            return;
-        }
-        EMDEE_REQUIRE(want < 0 || n == want, EMDEE_ERR_INVALID, "set_coulomb: %lld charges for %lld atoms", (long long)n, (long long)want);
-        EMDEE_REQUIRE(n < ((int64_t)1 << 31), EMDEE_ERR_INVALID, "set_coulomb: %lld charges (at most 2^31 - 1)", (long long)n);
-        EMDEE_REQUIRE(std::isfinite(K) && K > 0.0, EMDEE_ERR_INVALID, "set_coulomb: the Coulomb constant must be finite and > 0");
-        EMDEE_REQUIRE(eps >= 1.0, EMDEE_ERR_INVALID, "set_coulomb: the reaction-field dielectric must be >= 1 (+inf allowed)");
-        EMDEE_REQUIRE(std::isfinite(s14) && s14 >= 0.0, EMDEE_ERR_INVALID, "set_coulomb: coulomb14scale must be finite and >= 0");
-        std::vector<double> h((size_t)n);
-        EMDEE_HIP_CHECK(hipMemcpyAsync(h.data(), charges_dev, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        const double sk = std::sqrt(K);
-        for (int64_t k = 0; k < n; k++) {
-            EMDEE_REQUIRE(std::isfinite(h[k]), EMDEE_ERR_INVALID, "set_coulomb: charge %lld is not finite", (long long)k);
-            h[k] *= sk;
-        }
-        DevBuf<double> nq;
-        nq.ensure(h.size() + 1);
-        EMDEE_HIP_CHECK(hipMemcpyAsync(nq.ptr, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        // ---- commit
-        q_tab.swap(nq);
-        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14;
-        has_charges = true;
-    }
-};
 
 template <typename real>
 struct NbSystem {
@@ -1301,14 +1050,14 @@ struct NbSystem {
         EMDEE_REQUIRE(false, EMDEE_ERR_OVERFLOW, "neighbour capacity kept overflowing");
     }
 
-    // ---------------------------------------------------------------- exclusions and 1-4 pairs (PairTables)
+    // ---------------------------------------------------------------- exclusions and 1-4 pairs (topology_dev.hpp Topology)
     // Every engine keys the rows of its tables the same way (kernels.hpp PairKeys): by tag when it carries tags (a decomposed
     // engine), else by caller id.  The row filter records where each 1-4 partner sits in the rows (slots14) and k_pairs14 sums
     // those slots after every force pass: no look-up by id during steps, and a pair beyond rc + skin at the build is beyond rc
     // while the list is valid.  Two-species boxes with tables keep the general-species kernels (a typed row is two
     // block-aligned segments: compacting one would move the other).
-    PairTables own_tables;                                   // an undivided engine's, over caller ids
-    PairTables *tables = &own_tables;                        // a decomposed engine's point at the decomposition's, over global ids
+    Topology own_tables;                                     // an undivided engine's, over caller ids
+    Topology *tables = &own_tables;                          // a decomposed engine's point at the decomposition's, over global ids
     DevBuf<int> slots14;                                     // per 1-4 entry of an owned atom's row: the partner's cell-order slot
     DevBuf<int> slotsb;                                      // per bonded partner of an owned atom: its cell-order slot
     bool has_excl() const { return tables->has_excl; }
@@ -1333,15 +1082,7 @@ struct NbSystem {
         if (!bonded_broken) read_back_words(ctx, stream(), flags.ptr + 16, 1, &word);
         if (word != 0) {
             bonded_broken = true;
-            int kind;
-            int64_t index;
-            tables->bonded_term_of((int64_t)word - 1, kind, index);
-            static const char *const names[4] = {"", "bond", "angle", "torsion"};
-            const int na = PairTables::kind_atoms(kind);
-            const int32_t *ids = tables->b_atoms[kind].data() + (size_t)na * index;
-            set_error("bonded %s %lld (atoms %d %d%s%s%s%s): a partner is farther than rc + skin from its owner at a neighbour-list "
-                      "build, so the term cannot be evaluated; replace the tables or the state", names[kind], (long long)index, ids[0], ids[1],
-                      na > 2 ? " " : "", na > 2 ? std::to_string(ids[2]).c_str() : "", na > 3 ? " " : "", na > 3 ? std::to_string(ids[3]).c_str() : "");
+            set_error("%s", topo::lost_partner_message(tables->b_atoms, (int64_t)word - 1).c_str());
             throw Failure{EMDEE_ERR_STATE};
         }
         EMDEE_REQUIRE(!bonded_broken, EMDEE_ERR_STATE, "a bonded term has lost a partner (reported before): replace the tables or the state");
@@ -1383,7 +1124,7 @@ struct NbSystem {
                                cnt.ptr, tables->x_start.ptr, tables->x_idx.ptr, pair_keys(), bonded_keys());
         }
     }
-    // ---------------------------------------------------------------- charges (PairTables::set_charges)
+    // ---------------------------------------------------------------- charges (Topology::set_charges)
     // A charged engine keeps sqrt(K) q of every slot in its own cell order (qp), owned atoms and ghosts, looked up by the key the
     // atom carries: filled before the first force pass after every sort or in-place edit (the messages of a decomposition carry
     // no charges), unchanged in between (ghost identities are fixed between rebuilds).

@@ -1,0 +1,219 @@
+// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, charges.  Plain C++17 on
+// std::vector, no HIP: every function here validates or builds and throws through EMDEE_REQUIRE before it returns anything, so
+// a stand-alone host program can test it (tests/c/topology_host.cpp).  topology_dev.hpp holds the device buffers.
+#pragma once
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "error.hpp"
+
+namespace emdee {
+namespace topo {
+
+// pairs of the lists a and b ({i, j, i, j, ...}) -> rows 0 .. rows - 1: start[rows + 1], partners ascending, no duplicates
+inline void csr(const std::vector<int32_t> &a, const std::vector<int32_t> &b, int rows, std::vector<int32_t> &st,
+                std::vector<int32_t> &ix) {
+    st.assign((size_t)rows + 1, 0);
+    for (const std::vector<int32_t> *h : {&a, &b})
+        for (size_t k = 0; k < h->size(); k++) st[(size_t)(*h)[k] + 1]++;
+    for (int r = 0; r < rows; r++) st[(size_t)r + 1] += st[r];
+    ix.assign(st[rows], 0);
+    std::vector<int32_t> at(st.begin(), st.end() - 1);
+    for (const std::vector<int32_t> *h : {&a, &b})
+        for (size_t k = 0; k + 1 < h->size(); k += 2) {
+            const int32_t g = (*h)[k], q = (*h)[k + 1];
+            ix[at[g]++] = q;
+            ix[at[q]++] = g;
+        }
+    size_t w = 0;
+    for (int r = 0; r < rows; r++) {
+        const size_t lo = st[r], hi = st[(size_t)r + 1];
+        std::sort(ix.begin() + lo, ix.begin() + hi);
+        st[r] = (int32_t)w;
+        for (size_t k = lo; k < hi; k++)
+            if (k == lo || ix[k] != ix[k - 1]) ix[w++] = ix[k];
+    }
+    st[rows] = (int32_t)w;
+    ix.resize(w);
+}
+
+// ---- exclusions and 1-4 pairs
+// the pairs as a caller gave them ({i, j, ...}, int32 or int64 ids): each two different ids in [0, lim), else refused
+template <typename T>
+std::vector<int32_t> checked_pairs(const char *what, const std::vector<T> &raw, int64_t lim) {
+    for (size_t k = 0; k + 1 < raw.size(); k += 2) {
+        const int64_t i = raw[k], j = raw[k + 1];
+        EMDEE_REQUIRE(i != j && i >= 0 && j >= 0 && i < lim && j < lim, EMDEE_ERR_INVALID,
+                      "%s: pair %lld = (%lld, %lld) is not a pair of two different ids in [0, %lld)", what, (long long)(k / 2),
+                      (long long)i, (long long)j, (long long)lim);
+    }
+    return std::vector<int32_t>(raw.begin(), raw.end());
+}
+// Both tables are symmetric, sorted, duplicate-free CSRs over ids 0 .. rows - 1 (max id + 1).
+struct PairCsrs {
+    std::vector<int32_t> xs, xi;                             // struck from the rows: the exclusions and the 1-4 pairs together
+    std::vector<int32_t> ps, pi;                             // the 1-4 pairs
+    int rows = 0;
+    size_t n14 = 0;                                          // entries of the 1-4 CSR
+    bool has_excl = false, has_14 = false;
+};
+inline PairCsrs build_pairs(const std::vector<int32_t> &excl, const std::vector<int32_t> &p14) {
+    PairCsrs t;
+    for (const std::vector<int32_t> *h : {&excl, &p14})
+        for (int32_t g : *h) t.rows = std::max(t.rows, g + 1);
+    csr(excl, p14, t.rows, t.xs, t.xi);
+    csr(p14, std::vector<int32_t>{}, t.rows, t.ps, t.pi);
+    t.n14 = t.pi.size();
+    t.has_excl = !t.xi.empty(); t.has_14 = !t.pi.empty();
+    return t;
+}
+
+// ---- bonded terms: kinds 1 (bond), 2 (angle), 3 (torsion); arrays over kinds have KINDS entries, entry 0 unused
+constexpr int KINDS = 4;
+inline int kind_atoms(int kind) { return kind + 1; }
+inline int kind_params(int kind) { return kind == 3 ? 3 : 2; }
+inline const char *kind_name(int kind) {
+    static const char *const names[KINDS] = {"", "bond", "angle", "torsion"};
+    return names[kind];
+}
+// term number (over all kinds, in kind order) -> kind and index within it
+inline void bonded_term_of(const std::vector<int32_t> (&atoms)[KINDS], int64_t id, int &kind, int64_t &index) {
+    for (kind = 1; kind < KINDS - 1 && id >= (int64_t)(atoms[kind].size() / kind_atoms(kind)); kind++)
+        id -= (int64_t)(atoms[kind].size() / kind_atoms(kind));
+    index = id;
+}
+// The terms of one kind as a caller gave them (kind_atoms(kind) ids and kind_params(kind) doubles per term), to replace that
+// kind of `atoms`: ids in [0, lim) and all different within a term, parameters finite and in range, fewer than 2^31 - 1 terms
+// over all kinds; else refused.
+template <typename T>
+std::vector<int32_t> checked_terms(int kind, const std::vector<T> &raw, const std::vector<double> &prm, int64_t lim,
+                                   const std::vector<int32_t> (&atoms)[KINDS]) {
+    const int na = kind_atoms(kind), np = kind_params(kind);
+    const int64_t n = (int64_t)(raw.size() / na);
+    for (int64_t k = 0; k < n; k++) {
+        for (int a = 0; a < na; a++) {
+            const int64_t g = raw[(size_t)na * k + a];
+            EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_bonded: %s %lld names id %lld, outside [0, %lld)", kind_name(kind),
+                          (long long)k, (long long)g, (long long)lim);
+            for (int b = 0; b < a; b++)
+                EMDEE_REQUIRE(raw[(size_t)na * k + b] != raw[(size_t)na * k + a], EMDEE_ERR_INVALID,
+                              "set_bonded: %s %lld names atom %lld twice", kind_name(kind), (long long)k, (long long)g);
+        }
+        const double *q = prm.data() + (size_t)np * k;
+        for (int c = 0; c < np; c++)
+            EMDEE_REQUIRE(std::isfinite(q[c]), EMDEE_ERR_INVALID, "set_bonded: %s %lld has a non-finite parameter", kind_name(kind), (long long)k);
+        if (kind == 1) EMDEE_REQUIRE(q[1] >= 0.0, EMDEE_ERR_INVALID, "set_bonded: bond %lld has r0 < 0", (long long)k);
+        if (kind == 2) EMDEE_REQUIRE(q[1] >= 0.0 && q[1] <= M_PI, EMDEE_ERR_INVALID, "set_bonded: angle %lld has theta0 outside [0, pi]", (long long)k);
+        if (kind == 3) EMDEE_REQUIRE(q[1] >= 1.0 && q[1] == std::floor(q[1]), EMDEE_ERR_INVALID,
+                                     "set_bonded: torsion %lld has a periodicity that is not an integer >= 1", (long long)k);
+    }
+    int64_t total = n;
+    for (int kd = 1; kd < KINDS; kd++)
+        if (kd != kind) total += (int64_t)(atoms[kd].size() / kind_atoms(kd));
+    EMDEE_REQUIRE(total < INT32_MAX, EMDEE_ERR_INVALID, "set_bonded: %lld terms in all (at most 2^31 - 2)", (long long)total);
+    return std::vector<int32_t>(raw.begin(), raw.end());
+}
+// One term entry of an atom's row (kernels.hpp BondedKeys; the device reads it as an int4): code = kind | role << 2 (role: the
+// atom's position in the term), loc = the other atoms of the term, in term order, as positions in the atom's partner row.
+struct TermEntry {
+    int32_t code, loc[3];
+};
+// Rows 0 .. rows - 1 list each atom's bonded partners (ps / pi: ascending, unique) and its term entries (ts / terms, in (kind,
+// term, role) order); per entry the term's number over all kinds (tid) and three parameters, zero padded (pd; pf the same in fp32).
+struct BondedRows {
+    std::vector<int32_t> ps, pi, ts, tid;
+    std::vector<TermEntry> terms;
+    std::vector<double> pd;
+    std::vector<float> pf;
+    int rows = 0;
+    size_t nb = 0;                                           // entries of the partner CSR (slots of the row filter)
+};
+inline BondedRows build_bonded(const std::vector<int32_t> *const (&at)[KINDS], const std::vector<double> *const (&pr)[KINDS]) {
+    BondedRows t;
+    // partners: (owner, partner) over every role of every term -> CSR, ascending, unique
+    for (int kd = 1; kd < KINDS; kd++)
+        for (int32_t g : *at[kd]) t.rows = std::max(t.rows, g + 1);
+    const int r = t.rows;
+    std::vector<int32_t> half;                               // each partner pair once (csr() makes the rows symmetric)
+    for (int kd = 1; kd < KINDS; kd++) {
+        const int nk = kind_atoms(kd);
+        for (size_t k = 0; k + nk <= at[kd]->size(); k += nk)
+            for (int a = 0; a < nk; a++)
+                for (int b = 0; b < nk; b++)
+                    if ((*at[kd])[k + a] < (*at[kd])[k + b]) { half.push_back((*at[kd])[k + a]); half.push_back((*at[kd])[k + b]); }
+    }
+    csr(half, std::vector<int32_t>{}, r, t.ps, t.pi);
+    t.nb = t.pi.size();
+    // term entries, in (kind, term, role) order within each row
+    t.ts.assign((size_t)r + 1, 0);
+    for (int kd = 1; kd < KINDS; kd++)
+        for (int32_t g : *at[kd]) t.ts[(size_t)g + 1]++;
+    for (int q = 0; q < r; q++) t.ts[(size_t)q + 1] += t.ts[q];
+    t.terms.resize(t.ts[r]);
+    t.tid.resize(t.ts[r]);
+    t.pd.assign((size_t)3 * t.ts[r], 0.0);
+    t.pf.assign((size_t)3 * t.ts[r], 0.f);
+    std::vector<int32_t> fill(t.ts.begin(), t.ts.end() - 1);
+    int32_t number = 0;
+    for (int kd = 1; kd < KINDS; kd++) {
+        const int nk = kind_atoms(kd), npk = kind_params(kd);
+        for (size_t k = 0; k + nk <= at[kd]->size(); k += nk, number++) {
+            const int32_t *ids = at[kd]->data() + k;
+            const double *q = pr[kd]->data() + (k / nk) * npk;
+            for (int role = 0; role < nk; role++) {
+                const int32_t g = ids[role];
+                const int e = fill[g]++;
+                int loc[3] = {0, 0, 0}, c = 0;
+                for (int a = 0; a < nk; a++) {
+                    if (a == role) continue;
+                    const auto it = std::lower_bound(t.pi.begin() + t.ps[g], t.pi.begin() + t.ps[(size_t)g + 1], ids[a]);
+                    loc[c++] = (int)(it - (t.pi.begin() + t.ps[g]));
+                }
+                t.terms[e] = TermEntry{kd | role << 2, {loc[0], loc[1], loc[2]}};
+                t.tid[e] = number;
+                for (int c2 = 0; c2 < npk; c2++) { t.pd[(size_t)3 * e + c2] = q[c2]; t.pf[(size_t)3 * e + c2] = (float)q[c2]; }
+            }
+        }
+    }
+    return t;
+}
+// the error text for term number `term` (as tid numbers them) whose owner did not find a partner in its rows
+inline std::string lost_partner_message(const std::vector<int32_t> (&atoms)[KINDS], int64_t term) {
+    int kind;
+    int64_t index;
+    bonded_term_of(atoms, term, kind, index);
+    const int na = kind_atoms(kind);
+    const int32_t *ids = atoms[kind].data() + (size_t)na * index;
+    char text[1024];
+    snprintf(text, sizeof(text), "bonded %s %lld (atoms %d %d%s%s%s%s): a partner is farther than rc + skin from its owner at a neighbour-list "
+             "build, so the term cannot be evaluated; replace the tables or the state", kind_name(kind), (long long)index, ids[0], ids[1],
+             na > 2 ? " " : "", na > 2 ? std::to_string(ids[2]).c_str() : "", na > 3 ? " " : "", na > 3 ? std::to_string(ids[3]).c_str() : "");
+    return text;
+}
+
+// ---- charges and the reaction-field constants
+// want >= 0: the only n accepted (an undivided engine's atom count)
+inline void check_coulomb(int64_t n, int64_t want, double K, double eps, double s14) {
+    EMDEE_REQUIRE(want < 0 || n == want, EMDEE_ERR_INVALID, "set_coulomb: %lld charges for %lld atoms", (long long)n, (long long)want);
+    EMDEE_REQUIRE(n < ((int64_t)1 << 31), EMDEE_ERR_INVALID, "set_coulomb: %lld charges (at most 2^31 - 1)", (long long)n);
+    EMDEE_REQUIRE(std::isfinite(K) && K > 0.0, EMDEE_ERR_INVALID, "set_coulomb: the Coulomb constant must be finite and > 0");
+    EMDEE_REQUIRE(eps >= 1.0, EMDEE_ERR_INVALID, "set_coulomb: the reaction-field dielectric must be >= 1 (+inf allowed)");
+    EMDEE_REQUIRE(std::isfinite(s14) && s14 >= 0.0, EMDEE_ERR_INVALID, "set_coulomb: coulomb14scale must be finite and >= 0");
+}
+// the charges as given -> sqrt(K) q, what the kernels multiply pairwise; a charge that is not finite is refused
+inline void scale_charges(std::vector<double> &q, double K) {
+    const double sk = std::sqrt(K);
+    for (size_t k = 0; k < q.size(); k++) {
+        EMDEE_REQUIRE(std::isfinite(q[k]), EMDEE_ERR_INVALID, "set_coulomb: charge %lld is not finite", (long long)k);
+        q[k] *= sk;
+    }
+}
+
+}  // namespace topo
+}  // namespace emdee

@@ -1,0 +1,141 @@
+// topology_dev.hpp -- the device side of the topology tables: what topology.hpp builds on the host, uploaded.
+#pragma once
+
+#include <cstddef>
+
+#include "common.hpp"
+#include "topology.hpp"
+
+namespace emdee {
+
+static_assert(sizeof(topo::TermEntry) == sizeof(int4) && offsetof(topo::TermEntry, code) == offsetof(int4, x) &&
+              offsetof(topo::TermEntry, loc) == offsetof(int4, y), "kernels.hpp BondedKeys reads the term entries as int4");
+
+// Exclusions and scaled 1-4 pairs (kernels.hpp, "exclusions and 1-4 pairs"; the hooks of src/modelling.jl:197-200): pairs the
+// caller names are struck from the rows right after every build, and the 1-4 pairs among them come back scaled by lj14scale
+// after every force pass.  With them the bonded terms and the charges.  The topology does not change during a run: every table
+// is built on the host once per call.  An undivided engine owns one over caller ids (NbSystem::own_tables); a decomposition owns
+// one over global ids that all its engines point at (dd.hpp), which is simpler than carrying each atom's partners through
+// migration: 4 (max id + 2) + 4 (directed pairs) bytes per pair table.
+// Every setter is all or nothing: fetch the caller's arrays, validate and build on the host (topology.hpp), put the result
+// into buffers of their own, synchronise, and only then swap and commit -- an invalid call throws and leaves the tables in
+// force.  The caller makes sure nothing in flight reads the old tables.
+struct Topology {
+    // n elements at dev (device) -> host; blocking
+    template <typename T>
+    static std::vector<T> fetch(const T *dev, size_t n, hipStream_t s) {
+        std::vector<T> h(n);
+        if (n > 0) {
+            EMDEE_HIP_CHECK(hipMemcpyAsync(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        }
+        return h;
+    }
+    // h -> a buffer that holds it (D: the device's type for H, of the same size)
+    template <typename D, typename H>
+    static void put(DevBuf<D> &b, const std::vector<H> &h, hipStream_t s) {
+        static_assert(sizeof(D) == sizeof(H), "put: element sizes differ");
+        b.ensure(h.size() + 1);
+        if (!h.empty()) EMDEE_HIP_CHECK(hipMemcpyAsync(b.ptr, h.data(), h.size() * sizeof(H), hipMemcpyHostToDevice, s));
+    }
+
+    // ---- exclusions and 1-4 pairs: two symmetric, sorted, duplicate-free CSRs (topo::PairCsrs)
+    DevBuf<int> x_start, x_idx;                              // struck from the rows: the exclusions and the 1-4 pairs together
+    DevBuf<int> p_start, p_idx;                              // the 1-4 pairs
+    std::vector<int32_t> excl, p14;                          // the pairs as given: {i, j, i, j, ...}
+    double scale14 = 1.0;
+    int rows = 0;                                            // ids 0 .. rows - 1 have rows (max id + 1)
+    int64_t limit = 0;                                       // ids of the last call lay in [0, limit): the atom count, or 2^31 (global ids)
+    size_t n14 = 0;                                          // entries of the 1-4 CSR
+    bool has_excl = false, has_14 = false;
+    // Replaces one table by the n pairs at pairs_dev (device, {i, j, ...}): one_four, the 1-4 pairs scaled by `scale`, else the
+    // exclusions; n = 0 clears it.
+    template <typename T>
+    void set(const T *pairs_dev, int64_t n, bool one_four, double scale, int64_t lim, hipStream_t s) {
+        const char *what = one_four ? "set_pairs14" : "set_exclusions";
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || pairs_dev), EMDEE_ERR_INVALID, "%s: negative count or NULL array", what);
+        EMDEE_REQUIRE(!one_four || std::isfinite(scale), EMDEE_ERR_INVALID, "%s: lj14scale must be finite", what);
+        const std::vector<int32_t> h = topo::checked_pairs(what, fetch(pairs_dev, (size_t)2 * n, s), lim);
+        const topo::PairCsrs t = topo::build_pairs(one_four ? excl : h, one_four ? h : p14);
+        DevBuf<int> nxs, nxi, nps, npi;
+        put(nxs, t.xs, s); put(nxi, t.xi, s); put(nps, t.ps, s); put(npi, t.pi, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        x_start.swap(nxs); x_idx.swap(nxi); p_start.swap(nps); p_idx.swap(npi);
+        if (one_four) { p14 = h; scale14 = scale; } else { excl = h; }
+        rows = t.rows; limit = lim; n14 = t.n14;
+        has_excl = t.has_excl; has_14 = t.has_14;
+    }
+
+    // ---- bonded terms (emdee_*_set_bonded): kernels.hpp BondedKeys, topo::BondedRows.  The terms as given are kept per kind
+    // (b_atoms, b_prm) so that one kind can be replaced without the others.
+    std::vector<int32_t> b_atoms[topo::KINDS];
+    std::vector<double> b_prm[topo::KINDS];
+    DevBuf<int> b_pstart, b_pidx, b_tstart, b_tid;
+    DevBuf<int4> b_terms;
+    DevBuf<double> b_prm_d;
+    DevBuf<float> b_prm_f;
+    int b_rows = 0;
+    size_t nb = 0;                                           // entries of the partner CSR (slots of the row filter)
+    bool has_bonded = false;
+    template <typename real>
+    const real *bonded_params() const {
+        if constexpr (sizeof(real) == 8) return b_prm_d.ptr; else return b_prm_f.ptr;
+    }
+    // Replaces the table of one kind by the n terms at atoms_dev / params_dev (device; kind_atoms(kind) ids and
+    // kind_params(kind) doubles per term); n = 0 clears it.
+    template <typename T>
+    void set_bonded(int kind, const T *atoms_dev, const double *params_dev, int64_t n, int64_t lim, hipStream_t s) {
+        EMDEE_REQUIRE(kind >= 1 && kind <= 3, EMDEE_ERR_INVALID, "set_bonded: unknown kind %d (EMDEE_HARMONIC_BOND, "
+                      "EMDEE_HARMONIC_ANGLE or EMDEE_PERIODIC_TORSION)", kind);
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && params_dev)), EMDEE_ERR_INVALID, "set_bonded: negative count or NULL array");
+        const std::vector<T> raw = fetch(atoms_dev, (size_t)topo::kind_atoms(kind) * n, s);
+        const std::vector<double> prm = fetch(params_dev, (size_t)topo::kind_params(kind) * n, s);
+        const std::vector<int32_t> h = topo::checked_terms(kind, raw, prm, lim, b_atoms);
+        const std::vector<int32_t> *at[topo::KINDS] = {};
+        const std::vector<double> *pr[topo::KINDS] = {};
+        for (int kd = 1; kd < topo::KINDS; kd++) { at[kd] = kd == kind ? &h : &b_atoms[kd]; pr[kd] = kd == kind ? &prm : &b_prm[kd]; }
+        const topo::BondedRows t = topo::build_bonded(at, pr);
+        DevBuf<int> nps, npi, nts, ntid;
+        DevBuf<int4> nterms;
+        DevBuf<double> npd;
+        DevBuf<float> npf;
+        put(nps, t.ps, s); put(npi, t.pi, s); put(nts, t.ts, s); put(ntid, t.tid, s);
+        put(nterms, t.terms, s); put(npd, t.pd, s); put(npf, t.pf, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        b_pstart.swap(nps); b_pidx.swap(npi); b_tstart.swap(nts); b_tid.swap(ntid); b_terms.swap(nterms);
+        b_prm_d.swap(npd); b_prm_f.swap(npf);
+        b_atoms[kind] = h; b_prm[kind] = prm;
+        b_rows = t.rows; limit = lim; nb = t.nb;
+        has_bonded = !t.terms.empty();
+    }
+
+    // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the
+    // reaction-field constants.  Every engine keeps a plane of them in its own cell order (NbSystem::qp).
+    DevBuf<double> q_tab;
+    int64_t q_n = 0;                                         // keys 0 .. q_n - 1 have a charge
+    double coulomb_k = 0.0, eps_rf = INFINITY, scale14c = 1.0;
+    bool has_charges = false;
+    // Replaces the charges by the n at charges_dev (device, fp64, one per key); n = 0 clears them.  want >= 0: the only
+    // non-zero n accepted (an undivided engine's atom count).
+    void set_charges(const double *charges_dev, int64_t n, double K, double eps, double s14, int64_t want, hipStream_t s) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || charges_dev), EMDEE_ERR_INVALID, "set_coulomb: negative count or NULL array");
+        if (n == 0) {                                        // (clearing needs no constants)
+            has_charges = false; q_n = 0;
+            return;
+        }
+        topo::check_coulomb(n, want, K, eps, s14);
+        std::vector<double> h = fetch(charges_dev, (size_t)n, s);
+        topo::scale_charges(h, K);
+        DevBuf<double> nq;
+        put(nq, h, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        q_tab.swap(nq);
+        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14;
+        has_charges = true;
+    }
+};
+
+}  // namespace emdee

@@ -3,14 +3,13 @@
 a charge table that misses the gid one rank holds refused on both ranks, by the set call and by the next step, without either
 rank waiting for the other."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from .conftest import ROOT
 from .helpers.coulomb_rank import CHARGES
+from .helpers.two_ranks import run_two_ranks
 from .test_gpu_bonded import DT, _box, _chains, _md
 from .test_gpu_dd_pairs import _lj14scale
 
@@ -24,25 +23,7 @@ ERR_STATE = -6
 def test_two_rccl_ranks_with_charges_match_the_undivided_run_and_refuse_an_unknown_gid_together(emdee, tmp_path):
     E = emdee
     script = os.path.join(ROOT, "tests", "helpers", "coulomb_rank.py")
-    env0 = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1", NCCL_NET_GDR_LEVEL="0")
-    kids = []
-    try:
-        for r in range(2):
-            env = dict(env0, NCCL_HOSTID="emdee-coulomb-rank-%d" % r)
-            k = subprocess.Popen([sys.executable, script, "--rank", str(r), "--out", str(tmp_path)], env=env, stdin=subprocess.PIPE,
-                                 stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
-            kids.append(k)
-            if r == 0:
-                uid = k.stdout.readline().strip()
-                assert uid.startswith("ID "), uid
-            else:
-                k.stdin.write(uid + "\n")
-                k.stdin.flush()
-        outs = [k.communicate(timeout=240) for k in kids]
-    finally:
-        for k in kids:
-            if k.poll() is None:
-                k.kill()
+    kids, outs = run_two_ranks(script, tmp_path, "emdee-coulomb-rank-")
     for k, (out, err) in zip(kids, outs):
         assert k.returncode == 0, err[-800:]
         assert "REFUSED %d %d" % (ERR_STATE, ERR_STATE) in out, out + err[-800:]
