@@ -955,12 +955,15 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 768 ? 6 : 4)) void k_brick_bui
 // ------------------------------------------------------------------------------------ force / stats
 // BITMASK_Q: the outputs (EMDEE_FORCES | ENERGIES | VIRIALS | TENSOR), plus EMDEE_CHARGED for the instances of charged engines
 // (general species, force launches only): the sqrt(K) q of every tile slot is staged next to the tile and each pair inside rc
-// adds the reaction-field terms (lj_pair.hpp rf_pair) to its LJ terms.
+// adds the reaction-field terms (lj_pair.hpp rf_pair) to its LJ terms -- or, with EMDEE_EWALD as well, the erfc-screened Ewald
+// terms (ewald_pair): a compile-time choice, the reaction-field instances are the code they were.
 template <typename real, class Shape, int THREADS, int G, int MODE, int BITMASK_Q, bool UNI = false>
 __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
-    constexpr int BITMASK = BITMASK_Q & ~EMDEE_CHARGED;
+    constexpr int BITMASK = BITMASK_Q & ~(EMDEE_CHARGED | EMDEE_EWALD);
     constexpr bool CHG = (BITMASK_Q & EMDEE_CHARGED) != 0;
+    constexpr bool EWD = (BITMASK_Q & EMDEE_EWALD) != 0;      // (Ewald engines: ewald_pair in place of rf_pair)
     static_assert(!CHG || (!UNI && MODE == BRICK_FORCE), "charged instances: general-species force launches only");
+    static_assert(!EWD || CHG, "Ewald instances are charged instances");
     constexpr int NGROUPS = (THREADS / WAVE) * (WAVE / G);
     constexpr int BLK = EPL * G;
 
@@ -1243,7 +1246,8 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                                 const real sg = hs_i + hs_j;
                                 wr2 = lj_force_over_r2(r2, inv_r2, mdl, sg * sg, te_i * te_j);
                             }
-                            if (CHG) wr2 += rf_force_over_r2(r2, inv_r2, q_i * tile_q[sj], a.chg);
+                            if (CHG) wr2 += EWD ? ewald_force_over_r2(r2, inv_r2, q_i * tile_q[sj], a.chg)
+                                                : rf_force_over_r2(r2, inv_r2, q_i * tile_q[sj], a.chg);
                             fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
                         } else {
                             real E, W;
@@ -1254,7 +1258,8 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
                             }
                             if (CHG) {
                                 real Ec, Wc;
-                                rf_pair(r2, q_i * tile_q[sj], a.chg, Ec, Wc);
+                                if (EWD) ewald_pair(r2, q_i * tile_q[sj], a.chg, Ec, Wc);
+                                else rf_pair(r2, q_i * tile_q[sj], a.chg, Ec, Wc);
                                 E += Ec; W += Wc;
                             }
                             if (BITMASK & EMDEE_FORCES) {

@@ -27,6 +27,9 @@ constexpr int TENSOR_PASS = EMDEE_ENERGIES | EMDEE_VIRIALS | EMDEE_TENSOR;
 // ---- internal template bit of the force kernels (brick.hpp k_brick): the instance adds the reaction-field Coulomb terms of a
 // charged engine (lj_pair.hpp Charges).  Never part of a public bitmask; instances without it are the uncharged kernels.
 constexpr int EMDEE_CHARGED = 64;
+// ---- internal template bit next to EMDEE_CHARGED: the charged instance takes the erfc-screened Ewald pair terms (lj_pair.hpp
+// ewald_pair) in place of the reaction-field ones (emdee_md_set_ewald).  Instances without it are the reaction-field kernels.
+constexpr int EMDEE_EWALD = 128;
 
 // ---- error plumbing: error.hpp (set_error, get_error, Failure, EMDEE_REQUIRE), and the check of a HIP call
 #define EMDEE_HIP_CHECK(expr)                                                                    \

@@ -193,7 +193,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(vel || n_owned == 0, EMDEE_ERR_INVALID, "velocities are NULL");
         n_ghost = ng;
         sys.load_user(n_owned, ng, (const real *)pos, (const real *)vel, atoms, (const real *)inv_mass, tags_user);
-        if (!lent) sys.reset_bonded_error();                 // (a new state: the bonded terms get another chance; a decomposition resets its own)
+        if (!lent) { sys.reset_bonded_error(); sys.reset_ewald_error(); }   // (a new state: the bonded terms and the struck pairs get another chance; a decomposition resets its own)
         since_build = 0;
         current_mask = 0;
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
@@ -233,6 +233,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "md_step needs n_ghost == 0; decomposed runs drive kick_drift/forces/kick");
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         EMDEE_REQUIRE(!sys.bonded_broken, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
+        EMDEE_REQUIRE(!sys.ewald_broken, EMDEE_ERR_STATE, "md_step: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
         if (nsteps == 0) return;
         if (baro.kind != EMDEE_BAROSTAT_OFF) { step_coupled(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
@@ -510,11 +511,11 @@ struct MdImpl : IMd {
     void kernel_time(int kernel, double *total_ms, int64_t *launches) override {
         // ids 0..3: the TimerIds; 4: every fused step launch (interior + boundary halves of a decomposed step together, as
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
-        // decomposed step (pack -> exchange -> unpack)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 7, EMDEE_ERR_INVALID, "kernel id out of range");
+        // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 8, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[8][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
-                               {T_STEP_BOUNDARY, -1}, {T_HALO, -1}};
+        const int ids[9][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+                               {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -547,8 +548,11 @@ struct MdImpl : IMd {
         EMDEE_HIP_CHECK(hipGetLastError());
     }
     void set_pairs(const int32_t *pairs, int32_t n_pairs, bool one_four, double lj14scale) override {
-        install("exclusions / 1-4 pairs", "emdee_dd_set_exclusions / emdee_dd_set_pairs14",
-                [&] { sys.set_pair_tables(sys.n_owned, pairs, n_pairs, one_four, lj14scale); });
+        install("exclusions / 1-4 pairs", "emdee_dd_set_exclusions / emdee_dd_set_pairs14", [&] {
+            sys.set_pair_tables(sys.n_owned, pairs, n_pairs, one_four, lj14scale);
+            sys.reset_ewald_error();
+        });
+        sys.check_ewald();                                   // (blocking read-back, Ewald engines with struck pairs only)
     }
     void set_bonded(int32_t kind, const int32_t *atoms, const double *params, int32_t n_terms) override {
         install("bonded terms", "emdee_dd_set_bonded", [&] {
@@ -561,7 +565,22 @@ struct MdImpl : IMd {
         install("charges", "emdee_dd_set_coulomb", [&] {
             sys.own_tables.set_charges(charges, n, coulomb_k, eps_rf, coulomb14scale, sys.n_owned, sys.stream());
             sys.reset_charge_error();
+            if (n == 0) sys.ewald.clear();                   // (no charges, no Ewald sum: the next set_coulomb starts with the reaction field)
         });
+    }
+    // emdee_md_set_ewald: all or nothing -- every refusal comes before the setting changes
+    void set_ewald(double alpha, const int32_t *kmax) override {
+        EMDEE_REQUIRE(alpha == 0.0 || (std::isfinite(alpha) && alpha > 0.0), EMDEE_ERR_INVALID, "set_ewald: alpha must be finite and >= 0");
+        if (alpha > 0.0) topo::check_ewald(alpha, kmax, std::sqrt(sys.model_d.rc2));
+        require_undivided("set_ewald");
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "set_ewald: no state loaded (call emdee_md_set_state first)");
+        EMDEE_REQUIRE(sys.has_charges() && !sys.charges_stale(), EMDEE_ERR_STATE, "set_ewald: the engine has no charges for its state (call emdee_md_set_coulomb first)");
+        EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "set_ewald: the box must be periodic in all three dimensions");
+        install("Ewald summation", "a decomposed run has none", [&] {
+            if (alpha > 0.0) sys.ewald.set(alpha, kmax); else sys.ewald.clear();
+            sys.reset_ewald_error();
+        });
+        sys.check_ewald();
     }
     void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) override {
         use_device(sys.ctx);

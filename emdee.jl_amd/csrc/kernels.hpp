@@ -818,7 +818,7 @@ constexpr int FORCE_ATOMS = 64;
 constexpr int NXCD = 8;
 
 // (the body of k_lj_force_nbr and of its charged twin k_lj_force_nbr_q: CHG adds the reaction-field terms, lj_pair.hpp rf_pair)
-template <typename real, int BITMASK, bool CHG>
+template <typename real, int BITMASK, bool CHG, bool EWD = false>
 __device__ __forceinline__ void lj_force_nbr_body(int n, int n_owned, int nblocks_per_xcd, const AtomView<real> &atoms,
                                                   const int *__restrict__ perm, const int *__restrict__ nbr, int stride,
                                                   const int *__restrict__ cnt, const GridP<real> &g, const LJModel<real> &model,
@@ -862,7 +862,8 @@ __device__ __forceinline__ void lj_force_nbr_body(int n, int n_owned, int nblock
                     lj_interaction(r2, inv_r2, model, hs_i, te_i, hs_j, te_j, E, W);
                     if (CHG) {
                         real Ec, Wc;
-                        rf_pair(r2, q_i * ch.q[j], ch, Ec, Wc);
+                        if (EWD) ewald_pair(r2, q_i * ch.q[j], ch, Ec, Wc);
+                        else rf_pair(r2, q_i * ch.q[j], ch, Ec, Wc);
                         E += Ec; W += Wc;
                     }
                     if (BITMASK & EMDEE_FORCES) {
@@ -919,7 +920,7 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr(int n, int n_owned
                                             vir, guard, vt, Charges<real>{});
 }
 // a charged engine's direct kernel: the same body with the reaction-field terms (its own name, so that the uncharged instances
-// keep their signatures and code)
+// keep their signatures and code); BITMASK | EMDEE_EWALD: the Ewald real-space terms in their place
 template <typename real, int BITMASK>
 __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr_q(int n, int n_owned, int nblocks_per_xcd,
                                                                 AtomView<real> atoms, const int *__restrict__ perm,
@@ -929,8 +930,8 @@ __global__ __launch_bounds__(FORCE_BLOCK) void k_lj_force_nbr_q(int n, int n_own
                                                                 real *__restrict__ frc, real *__restrict__ en,
                                                                 real *__restrict__ vir, const int *__restrict__ guard,
                                                                 real *__restrict__ vt, Charges<real> ch) {
-    lj_force_nbr_body<real, BITMASK, true>(n, n_owned, nblocks_per_xcd, atoms, perm, nbr, stride, cnt, g, model, pitch, frc, en,
-                                           vir, guard, vt, ch);
+    lj_force_nbr_body<real, BITMASK & ~EMDEE_EWALD, true, (BITMASK & EMDEE_EWALD) != 0>(n, n_owned, nblocks_per_xcd, atoms, perm, nbr, stride,
+                                                                                        cnt, g, model, pitch, frc, en, vir, guard, vt, ch);
 }
 
 // ------------------------------------------------------------------------------------ integrator
@@ -1183,15 +1184,6 @@ static __global__ void k_export_rows(int n, int n_owned, const int *__restrict__
 // its hot path sums every pair, src/nonbonded.jl:129-150 -- so these are build-defined: pairs named by the caller are struck
 // from the neighbour rows right after every build (the pair loop gets no mask), and the 1-4 pairs among them are
 // evaluated on their own, scaled.)  Both tables are symmetric CSR lists over ids (PairKeys), partners ascending.
-__device__ __forceinline__ bool csr_holds(const int *__restrict__ idx, int lo, int hi, int j) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int v = idx[mid];
-        if (v == j) return true;
-        if (v < j) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
 // position of j in idx[lo, hi), or -1
 __device__ __forceinline__ int csr_find(const int *__restrict__ idx, int lo, int hi, long long j) {
     while (lo < hi) {
@@ -1208,11 +1200,14 @@ __device__ __forceinline__ int csr_find(const int *__restrict__ idx, int lo, int
 // have rows (an id beyond names no pair).  With a 1-4 table (s14 != NULL) the filter also records, for every 1-4 partner of an
 // owned atom, the cell-order slot of the entry it strikes, in the table's order: s14[k] for idx14[k], -1 when the partner is
 // not in the row (beyond the list radius at the build, so beyond rc until the next one).  k_pairs14 sums those slots.
+// An Ewald engine (sx != NULL) has the slot of EVERY struck entry recorded the same way, in the order of the struck CSR
+// (ex_idx): k_ewald_struck takes the reciprocal sum's share of those pairs back.  Other engines pass NULL and record nothing.
 struct PairKeys {
     const long long *tag;
     int n_tab;
     const int *start14, *idx14;
     int *s14;
+    int *sx;
 };
 __device__ __forceinline__ long long pair_key(const PairKeys &k, const int *__restrict__ perm, int slot) {
     return k.tag ? k.tag[slot] : (long long)perm[slot];
@@ -1246,6 +1241,8 @@ __device__ __forceinline__ int strike_row(const PairKeys &keys, const BondedKeys
     const int lo = ex ? ex_start[gi] : 0, hi = ex ? ex_start[gi + 1] : 0;
     const int lo14 = (ex && keys.s14) ? keys.start14[gi] : 0, hi14 = (ex && keys.s14) ? keys.start14[gi + 1] : 0;
     for (int k = lo14; k < hi14; k++) keys.s14[k] = -1;
+    if (keys.sx)
+        for (int k = lo; k < hi; k++) keys.sx[k] = -1;
     const int lob = bd ? bk.pstart[gi] : 0, hib = bd ? bk.pstart[gi + 1] : 0;
     for (int k = lob; k < hib; k++) bk.slots[k] = -1;
     int w = 0;
@@ -1257,12 +1254,16 @@ __device__ __forceinline__ int strike_row(const PairKeys &keys, const BondedKeys
             const int k = csr_find(bk.pidx, lob, hib, gj);
             if (k >= 0) bk.slots[k] = q;
         }
-        if (!csr_holds(ex_idx, lo, hi, (int)min(gj, (long long)keys.n_tab))) {
+        const int kx = csr_find(ex_idx, lo, hi, min(gj, (long long)keys.n_tab));
+        if (kx < 0) {
             if (w != e) at(w) = ent;
             w++;
-        } else if (lo14 < hi14) {
-            const int k = csr_find(keys.idx14, lo14, hi14, gj);
-            if (k >= 0) keys.s14[k] = q;
+        } else {
+            if (keys.sx) keys.sx[kx] = q;
+            if (lo14 < hi14) {
+                const int k = csr_find(keys.idx14, lo14, hi14, gj);
+                if (k >= 0) keys.s14[k] = q;
+            }
         }
     }
     return ex ? w : -1;
@@ -1288,7 +1289,9 @@ static __global__ void k_filter_rows(int n, int n_owned, const int *__restrict__
 // order).  A pair missing from the rows is beyond rc + skin at the build, so beyond rc while the list is valid.
 // (TENSOR: the tensor pass's instance; the force and observable passes keep the instance without the six sums)
 // (CHG: the body of k_pairs14_q, a charged engine's: the pair's reaction-field terms scaled by ch.scale14 on top)
-template <typename real, bool TENSOR, bool CHG>
+// (EWD: an Ewald engine's: the pair's Coulomb part is ch.scale14 qq / r with NO cutoff test -- k_ewald_struck adds the
+// correction every struck pair gets -- and the LJ part keeps its cutoff test)
+template <typename real, bool TENSOR, bool CHG, bool EWD = false>
 __device__ __forceinline__ void pairs14_body(int n, int n_owned, size_t pitch, const AtomView<real> &atoms, const int *__restrict__ perm,
                                              const PairKeys &keys, const GridP<real> &g, const LJModel<real> &model, real scale,
                                              int bitmask, real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir,
@@ -1318,6 +1321,17 @@ __device__ __forceinline__ void pairs14_body(int n, int n_owned, size_t pitch, c
         const real dy = min_image(yi - yj, g.plen[1], g.pinv[1]);
         const real dz = min_image(zi - zj, g.plen[2], g.pinv[2]);
         const real r2 = dx * dx + dy * dy + dz * dz;
+        if (EWD) {                                             // bare Coulomb, whatever the distance
+            const real inv_r2 = (real)1 / r2;
+            const real Wc = q_i * ch.q[q] * sqrt(inv_r2), cr2 = Wc * inv_r2;
+            cfx += cr2 * dx; cfy += cr2 * dy; cfz += cr2 * dz;
+            ce += Wc; cw += Wc;
+            if (TENSOR) {
+                const real hx = cr2 * dx, hy = cr2 * dy, hz = cr2 * dz;
+                ctv[0] += hx * dx; ctv[1] += hy * dy; ctv[2] += hz * dz;
+                ctv[3] += hx * dy; ctv[4] += hx * dz; ctv[5] += hy * dz;
+            }
+        }
         if (r2 < model.rc2) {                                  // CUTOFF semantics, as the list kernels
             const real inv_r2 = (real)1 / r2;
             real E, W;
@@ -1330,7 +1344,7 @@ __device__ __forceinline__ void pairs14_body(int n, int n_owned, size_t pitch, c
                 tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
                 tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
             }
-            if (CHG) {
+            if (CHG && !EWD) {
                 real Ec, Wc;
                 rf_pair(r2, q_i * ch.q[q], ch, Ec, Wc);
                 const real cr2 = Wc * inv_r2;
@@ -1376,13 +1390,62 @@ __global__ void k_pairs14(int n, int n_owned, size_t pitch, AtomView<real> atoms
                                       user_w, vt, user_vt, Charges<real>{});
 }
 // a charged engine's 1-4 kernel (its own name: the uncharged instances keep their signatures and code)
-template <typename real, bool TENSOR>
+template <typename real, bool TENSOR, bool EWD = false>
 __global__ void k_pairs14_q(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
                             GridP<real> g, LJModel<real> model, real scale, int bitmask, real *__restrict__ frc, real *__restrict__ en,
                             real *__restrict__ vir, real *__restrict__ user_f, real *__restrict__ user_e, real *__restrict__ user_w,
                             real *__restrict__ vt, real *__restrict__ user_vt, Charges<real> ch) {
-    pairs14_body<real, TENSOR, true>(n, n_owned, pitch, atoms, perm, keys, g, model, scale, bitmask, frc, en, vir, user_f, user_e,
-                                     user_w, vt, user_vt, ch);
+    pairs14_body<real, TENSOR, true, EWD>(n, n_owned, pitch, atoms, perm, keys, g, model, scale, bitmask, frc, en, vir, user_f, user_e,
+                                          user_w, vt, user_vt, ch);
+}
+
+// Ewald engines: the correction of every pair struck from the rows (exclusions and 1-4 pairs; lj_pair.hpp ewald_struck_pair).
+// Owner-computes over the slots the row filter recorded for the struck CSR (PairKeys::sx) -- no atomics, the table's order of
+// summation, half of a pair's E and W to the owner, added to the cell-ordered arrays.  Minimum image, no cutoff test.  A
+// partner missing from the rows (farther than rc + skin at the build) leaves the pair out and writes its entry's number + 1 to
+// *err (read by the host: NbSystem::check_ewald).
+template <typename real, bool TENSOR>
+__global__ void k_ewald_struck(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
+                               const int *__restrict__ ex_start, GridP<real> g, int bitmask, real *__restrict__ frc,
+                               real *__restrict__ en, real *__restrict__ vir, real *__restrict__ vt, Charges<real> ch,
+                               int *__restrict__ err) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (perm[p] >= n_owned) return;
+    const long long gi = pair_key(keys, perm, p);
+    if (gi < 0 || gi >= keys.n_tab) return;
+    const int lo = ex_start[gi], hi = ex_start[gi + 1];
+    if (lo == hi) return;
+    real xi, yi, zi, hs_i, te_i;
+    load_atom(atoms, p, xi, yi, zi, hs_i, te_i);
+    const real q_i = ch.q[p];
+    real fx = 0, fy = 0, fz = 0, e = 0, w = 0;
+    real tv[6] = {0, 0, 0, 0, 0, 0};
+    for (int k = lo; k < hi; k++) {
+        const int q = keys.sx[k];
+        if (q < 0 || q >= n) { *err = k + 1; continue; }
+        real xj, yj, zj, hs_j, te_j;
+        load_atom(atoms, q, xj, yj, zj, hs_j, te_j);
+        const real dx = min_image(xi - xj, g.plen[0], g.pinv[0]);
+        const real dy = min_image(yi - yj, g.plen[1], g.pinv[1]);
+        const real dz = min_image(zi - zj, g.plen[2], g.pinv[2]);
+        const real r2 = dx * dx + dy * dy + dz * dz;
+        real E, W;
+        ewald_struck_pair(r2, q_i * ch.q[q], ch, E, W);
+        const real wr2 = W / r2;
+        fx += wr2 * dx; fy += wr2 * dy; fz += wr2 * dz;
+        e += E; w += W;
+        if (TENSOR) {
+            const real hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
+            tv[0] += hx * dx; tv[1] += hy * dy; tv[2] += hz * dz;
+            tv[3] += hx * dy; tv[4] += hx * dz; tv[5] += hy * dz;
+        }
+    }
+    if (bitmask & EMDEE_FORCES) { frc[p] += fx; frc[pitch + p] += fy; frc[2 * pitch + p] += fz; }
+    if (bitmask & EMDEE_ENERGIES) en[p] += (real)0.5 * e;
+    if (bitmask & EMDEE_VIRIALS) vir[p] += (real)0.5 * w;
+    if (TENSOR)
+        for (int c = 0; c < 6; c++) vt[c * pitch + p] += (real)0.5 * tv[c];
 }
 
 // The charge plane of a charged engine: sqrt(K) q of the atom in every cell-order slot, looked up by the key it carries (tag or

@@ -63,6 +63,7 @@ template <typename real>
 struct Charges {
     const real *q;
     real k, k2, c, scale14;
+    real alpha, a2spi;   // Ewald engines (emdee_md_set_ewald): the splitting parameter and 2 alpha / sqrt(pi); else 0
 };
 // U = qq (1/r + k r^2 - c),  W = -r dU/dr = qq (1/r - 2 k r^2).  CUTOFF semantics are the caller's test, as lj_interaction_pair.
 // The one formula of every charged path (force pass, direct kernels, 1-4 pairs).
@@ -77,6 +78,35 @@ template <typename real>
 __device__ __forceinline__ real rf_force_over_r2(real r2, real inv_r2, real qq, const Charges<real> &ch) {
     const real inv_r = fast_rsq(r2);
     return qq * (inv_r * inv_r2 - ch.k2);
+}
+
+// ---- Ewald real-space terms (emdee_md_set_ewald; the EMDEE_EWALD instances of the charged kernels) -----------------------
+// U = qq erfc(alpha r) / r,  W = -r dU/dr = qq (erfc(alpha r) / r + (2 alpha / sqrt(pi)) exp(-alpha^2 r^2)); the device erfc and
+// exp of the real type.  CUTOFF semantics are the caller's test, as rf_pair.
+template <typename real>
+__device__ __forceinline__ void ewald_pair(real r2, real qq, const Charges<real> &ch, real &E_out, real &W_out) {
+    const real inv_r = fast_rsq(r2);
+    const real ar = ch.alpha * (r2 * inv_r);
+    const real u = qq * (erfc(ar) * inv_r);
+    E_out = u;
+    W_out = u + qq * (ch.a2spi * exp(-ar * ar));
+}
+// force-only launches: W / r^2 from the caller's inv_r2
+template <typename real>
+__device__ __forceinline__ real ewald_force_over_r2(real r2, real inv_r2, real qq, const Charges<real> &ch) {
+    real E, W;
+    ewald_pair(r2, qq, ch, E, W);
+    return W * inv_r2;
+}
+// The correction of a pair struck from the rows (an exclusion or a 1-4 pair), which the reciprocal sum has counted in full:
+// U = -qq erf(alpha r) / r,  W = -qq (erf(alpha r) / r - (2 alpha / sqrt(pi)) exp(-alpha^2 r^2)); no cutoff test.
+template <typename real>
+__device__ __forceinline__ void ewald_struck_pair(real r2, real qq, const Charges<real> &ch, real &E_out, real &W_out) {
+    const real inv_r = (real)1 / sqrt(r2);
+    const real ar = ch.alpha * (r2 * inv_r);
+    const real u = -qq * (erf(ar) * inv_r);
+    E_out = u;
+    W_out = u + qq * (ch.a2spi * exp(-ar * ar));
 }
 
 // The reference clamp  x *= 0.5 (sign(x) - sign(x-1))  (src/lennard_jones.jl:37):

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "brick.hpp"
+#include "ewald.hpp"
 #include "kernels.hpp"
 #include "topology_dev.hpp"
 #include "typed.hpp"
@@ -32,7 +33,8 @@ static inline void refuse_experiment_switches() {
 
 // T_STEP: every fused step launch but the boundary-brick halves of a decomposed step, which go to T_STEP_BOUNDARY (emdee_md_kernel_time(4)
 // reports the two together, 5 and 6 one each); T_HALO: pack -> exchange -> unpack of a decomposed step, on the stream they run on
-enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_COUNT = 7 };
+// T_EWALD: the reciprocal-space pass of an Ewald engine (ewald.hpp), which runs inside T_FORCE's launches as well
+enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_COUNT = 8 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -610,8 +612,13 @@ struct NbSystem {
         // charged engines: the general-species kernels with the reaction-field terms, whatever their LJ parameters
         if constexpr (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)) {
             if (has_charges()) {
-                if constexpr (charged_variant<V>()) launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED, false>();
-                else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "charged engine on brick variant %d", variant);
+                if constexpr (charged_variant<V>()) {
+                    if (has_ewald()) {
+                        // (variant 0 only, see make_plan: the fp64 erfc does not fit the 128 registers of a 1024-thread workgroup)
+                        if constexpr (std::is_same<V, BrickVariant<0>>::value) launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED | EMDEE_EWALD, false>();
+                        else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "Ewald engine on brick variant %d", variant);
+                    } else launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED, false>();
+                } else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "charged engine on brick variant %d", variant);
                 return;
             }
         }
@@ -791,7 +798,9 @@ struct NbSystem {
         // A tile too large for two workgroups of the default variant per CU (long cutoffs, dense boxes: rc = 3.5
         // sigma needs 135 KB) would leave 2 waves per SIMD: take the same bricks with 1024-thread workgroups
         // (measured on the rc = 3.5 mixture: 116 -> 154 steps/s).
-        if (brick_active && lds_bytes > LDS_LIMIT / 2) {
+        // (Ewald engines stay on variant 0, one workgroup per CU if need be: under the 128-register budget of 1024 threads the
+        // erfc of their pair loop would spill to scratch memory)
+        if (brick_active && lds_bytes > LDS_LIMIT / 2 && !has_ewald()) {
             variant = 8;
             if (!plan_bricks()) { variant = 0; plan_bricks(); }
         }
@@ -1077,6 +1086,7 @@ struct NbSystem {
     }
     // blocking: EMDEE_ERR_STATE naming the term if k_bonded has met a missing partner since the last reset
     void check_bonded() {
+        check_ewald();                                       // (the other term that needs a partner in the rows)
         if (!has_bonded() || !flags.ptr) return;
         int32_t word = 0;
         if (!bonded_broken) read_back_words(ctx, stream(), flags.ptr + 16, 1, &word);
@@ -1093,7 +1103,8 @@ struct NbSystem {
         has_list = false; plan_valid = false;                // (the rows in use were filtered with the old tables; typed rows are not filtered)
     }
     PairKeys pair_keys() const {
-        return PairKeys{use_tags ? tag.ptr : nullptr, tables->rows, tables->p_start.ptr, tables->p_idx.ptr, has_14() ? slots14.ptr : nullptr};
+        return PairKeys{use_tags ? tag.ptr : nullptr, tables->rows, tables->p_start.ptr, tables->p_idx.ptr, has_14() ? slots14.ptr : nullptr,
+                        (has_ewald() && has_excl()) ? slotsx.ptr : nullptr};
     }
     BondedKeys bonded_keys() const {
         return BondedKeys{tables->b_rows, tables->b_pstart.ptr, tables->b_pidx.ptr, has_bonded() ? slotsb.ptr : nullptr,
@@ -1110,6 +1121,7 @@ struct NbSystem {
         check_tables("exclusion / bonded tables");
         if (has_14()) slots14.ensure(tables->n14 + 1);
         if (has_bonded()) slotsb.ensure(tables->nb + 1);
+        if (has_ewald() && has_excl()) slotsx.ensure(tables->nx + 1);
         if (brick_active) {
             EMDEE_REQUIRE(!typed_active, EMDEE_ERR_STATE, "exclusions: typed rows are not filtered");
             with_brick_variant(variant, [&](auto v) {
@@ -1142,6 +1154,7 @@ struct NbSystem {
         c.q = qp.ptr;
         c.k = (real)k; c.k2 = (real)(2.0 * k); c.c = (real)(1.0 / rc + k * rc * rc);
         c.scale14 = (real)tables->scale14c;
+        if (has_ewald()) { c.alpha = (real)ewald.alpha; c.a2spi = (real)(2.0 * ewald.alpha / std::sqrt(M_PI)); }
         return c;
     }
     void ensure_charges() {
@@ -1177,7 +1190,8 @@ struct NbSystem {
         check_tables("1-4 table");
         const bool user = brick_active && (out_f || out_e || out_w || out_vt);
         if (has_charges()) {
-            auto kq = (bitmask & EMDEE_TENSOR) ? k_pairs14_q<real, true> : k_pairs14_q<real, false>;
+            auto kq = has_ewald() ? ((bitmask & EMDEE_TENSOR) ? k_pairs14_q<real, true, true> : k_pairs14_q<real, false, true>)
+                                  : ((bitmask & EMDEE_TENSOR) ? k_pairs14_q<real, true> : k_pairs14_q<real, false>);
             hipLaunchKernelGGL(kq, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
                                pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
                                user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
@@ -1200,9 +1214,50 @@ struct NbSystem {
                            pair_keys(), bonded_keys(), tables->template bonded_params<real>(), grid, bitmask, frc.ptr, en.ptr,
                            vir.ptr, vt.ptr, flags.ptr + 16);
     }
+    // ---------------------------------------------------------------- Ewald summation (emdee_md_set_ewald)
+    // With ewald.alpha > 0 a charged engine's pair loops take the erfc-screened terms (the EMDEE_EWALD instances), the row filter
+    // records the slot of every struck entry (slotsx), and behind every force pass k_ewald_struck corrects the struck pairs and
+    // ewald.run adds the reciprocal-space terms, the self term and the background.  Undivided engines in a fully periodic box.
+    EwaldRecip<real> ewald;
+    DevBuf<int> slotsx;                                      // per entry of the struck CSR of an owned atom: the partner's cell-order slot
+    bool has_ewald() const { return ewald.on() && has_charges(); }
+    // a struck pair whose partner was missing from the rows (flags[18], raised by k_ewald_struck): as bonded_broken
+    bool ewald_broken = false;
+    void reset_ewald_error() {
+        ewald_broken = false;
+        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 18, 0, sizeof(int), stream()));
+    }
+    // blocking: EMDEE_ERR_STATE naming the pair if k_ewald_struck has met a missing partner since the last reset
+    void check_ewald() {
+        if (!has_ewald() || !has_excl() || !flags.ptr) return;
+        int32_t word = 0;
+        if (!ewald_broken) read_back_words(ctx, stream(), flags.ptr + 18, 1, &word);
+        if (word != 0) {
+            ewald_broken = true;
+            set_error("%s", topo::lost_pair_message(tables->excl, tables->p14, (int64_t)word - 1).c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        EMDEE_REQUIRE(!ewald_broken, EMDEE_ERR_STATE, "Ewald: an excluded or 1-4 pair spans more than rc + skin (reported before): replace the tables or the state");
+    }
+    void add_ewald(int bitmask) {
+        if (!has_ewald() || n_total == 0) return;
+        EMDEE_REQUIRE(!has_ghosts && n_total == n_owned && tables == &own_tables, EMDEE_ERR_STATE,
+                      "Ewald summation on an engine with ghosts or a domain's engine: switch it off (emdee_md_set_ewald) or load a state without ghosts");
+        EMDEE_REQUIRE(!(brick_active && (out_f || out_e || out_w || out_vt)), EMDEE_ERR_STATE, "Ewald summation is not on the operator path");
+        if (has_excl()) {
+            check_tables("exclusion table");
+            auto kernel = (bitmask & EMDEE_TENSOR) ? k_ewald_struck<real, true> : k_ewald_struck<real, false>;
+            hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
+                               pair_keys(), tables->x_start.ptr, grid, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr, charge_args(),
+                               flags.ptr + 18);
+        }
+        Timed t(this, T_EWALD);
+        ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
+    }
     void add_post_terms(int bitmask) {
         add_pairs14(bitmask);
         add_bonded(bitmask);
+        add_ewald(bitmask);
     }
 
     // ---------------------------------------------------------------- forces
@@ -1213,6 +1268,12 @@ struct NbSystem {
         int nblocks = (n + FORCE_ATOMS - 1) / FORCE_ATOMS;
         int per_xcd = (nblocks + NXCD - 1) / NXCD;
         if constexpr (BM == 1 || BM == 7 || BM == TENSOR_PASS) {
+          if (has_ewald()) {
+            hipLaunchKernelGGL((k_lj_force_nbr_q<real, BM | EMDEE_EWALD>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
+                               per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
+                               vir.ptr, direct_guard, vt.ptr, charge_args());
+            return;
+          }
           if (has_charges()) {
             hipLaunchKernelGGL((k_lj_force_nbr_q<real, BM>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
                                per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,

@@ -215,5 +215,56 @@ inline void scale_charges(std::vector<double> &q, double K) {
     }
 }
 
+
+// ---- Ewald summation (emdee_md_set_ewald): the argument checks, the wave vectors and their coefficients for a box
+// alpha > 0 (alpha == 0 switches back to the reaction field and is not checked here); rc: the LJ model's cutoff
+inline void check_ewald(double alpha, const int32_t *kmax, double rc) {
+    EMDEE_REQUIRE(std::isfinite(alpha) && alpha > 0.0, EMDEE_ERR_INVALID, "set_ewald: alpha must be finite and >= 0");
+    EMDEE_REQUIRE(kmax != nullptr, EMDEE_ERR_INVALID, "set_ewald: kmax is NULL");
+    for (int d = 0; d < 3; d++)
+        EMDEE_REQUIRE(kmax[d] >= 1 && kmax[d] <= 64, EMDEE_ERR_INVALID, "set_ewald: kmax[%d] = %d outside [1, 64]", d, kmax[d]);
+    EMDEE_REQUIRE(alpha * rc >= 1.0, EMDEE_ERR_INVALID, "set_ewald: alpha rc = %g < 1 splits nothing off (erfc(alpha rc) = %g at the cutoff)",
+                  alpha * rc, std::erfc(alpha * rc));
+}
+// The integer wave vectors n of the half space -- n_x > 0, or n_x = 0 and n_y > 0, or n_x = n_y = 0 and n_z > 0 -- with
+// |n_d| <= kmax[d], as {n_x, n_y, n_z, ...} in ascending (n_x, n_y, n_z) order: each stands for itself and for -n.
+inline std::vector<int32_t> ewald_vectors(const int32_t kmax[3]) {
+    std::vector<int32_t> n;
+    for (int32_t x = 0; x <= kmax[0]; x++)
+        for (int32_t y = (x == 0 ? 0 : -kmax[1]); y <= kmax[1]; y++)
+            for (int32_t z = ((x == 0 && y == 0) ? 1 : -kmax[2]); z <= kmax[2]; z++) { n.push_back(x); n.push_back(y); n.push_back(z); }
+    return n;
+}
+// One wave vector as the reciprocal-space kernels read it (ewald.hpp): k = 2 pi n / L per axis,
+// a = A(k) = (4 pi / V) exp(-k^2 / 4 alpha^2) / k^2,  b = 2 (1 / k^2 + 1 / (4 alpha^2)) (the tensor's factor).
+struct EwaldK {
+    double a, b, kx, ky, kz;
+    int32_t nx, ny, nz, pad;
+};
+inline std::vector<EwaldK> ewald_table(const std::vector<int32_t> &n, const double len[3], double alpha) {
+    std::vector<EwaldK> t(n.size() / 3);
+    const double V = len[0] * len[1] * len[2], q4 = 1.0 / (4.0 * alpha * alpha);
+    for (size_t v = 0; v < t.size(); v++) {
+        EwaldK &e = t[v];
+        e.nx = n[3 * v]; e.ny = n[3 * v + 1]; e.nz = n[3 * v + 2]; e.pad = 0;
+        e.kx = 2.0 * M_PI * e.nx / len[0]; e.ky = 2.0 * M_PI * e.ny / len[1]; e.kz = 2.0 * M_PI * e.nz / len[2];
+        const double k2 = e.kx * e.kx + e.ky * e.ky + e.kz * e.kz;
+        e.a = (4.0 * M_PI / V) * std::exp(-k2 * q4) / k2;
+        e.b = 2.0 * (1.0 / k2 + q4);
+    }
+    return t;
+}
+// the error text for entry `entry` of the struck CSR (xs / xi of build_pairs) whose owner did not find the partner in its rows
+inline std::string lost_pair_message(const std::vector<int32_t> &excl, const std::vector<int32_t> &p14, int64_t entry) {
+    const PairCsrs t = build_pairs(excl, p14);
+    int owner = 0;
+    while (owner + 1 < t.rows && t.xs[(size_t)owner + 1] <= entry) owner++;
+    const int partner = (entry >= 0 && entry < (int64_t)t.xi.size()) ? t.xi[(size_t)entry] : -1;
+    char text[512];
+    snprintf(text, sizeof(text), "Ewald: the excluded or 1-4 pair (%d, %d) is farther apart than rc + skin at a neighbour-list build, so its "
+             "correction cannot be evaluated; replace the tables or the state", owner, partner);
+    return text;
+}
+
 }  // namespace topo
 }  // namespace emdee

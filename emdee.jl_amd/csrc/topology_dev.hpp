@@ -47,6 +47,7 @@ struct Topology {
     int rows = 0;                                            // ids 0 .. rows - 1 have rows (max id + 1)
     int64_t limit = 0;                                       // ids of the last call lay in [0, limit): the atom count, or 2^31 (global ids)
     size_t n14 = 0;                                          // entries of the 1-4 CSR
+    size_t nx = 0;                                           // entries of the struck CSR (slots of an Ewald engine's row filter)
     bool has_excl = false, has_14 = false;
     // Replaces one table by the n pairs at pairs_dev (device, {i, j, ...}): one_four, the 1-4 pairs scaled by `scale`, else the
     // exclusions; n = 0 clears it.
@@ -63,7 +64,7 @@ struct Topology {
         // ---- commit
         x_start.swap(nxs); x_idx.swap(nxi); p_start.swap(nps); p_idx.swap(npi);
         if (one_four) { p14 = h; scale14 = scale; } else { excl = h; }
-        rows = t.rows; limit = lim; n14 = t.n14;
+        rows = t.rows; limit = lim; n14 = t.n14; nx = t.xi.size();
         has_excl = t.has_excl; has_14 = t.has_14;
     }
 
@@ -116,6 +117,7 @@ struct Topology {
     DevBuf<double> q_tab;
     int64_t q_n = 0;                                         // keys 0 .. q_n - 1 have a charge
     double coulomb_k = 0.0, eps_rf = INFINITY, scale14c = 1.0;
+    double q_sum = 0.0;                                      // sum of sqrt(K) q in key order (the Ewald background term)
     bool has_charges = false;
     // Replaces the charges by the n at charges_dev (device, fp64, one per key); n = 0 clears them.  want >= 0: the only
     // non-zero n accepted (an undivided engine's atom count).
@@ -128,12 +130,14 @@ struct Topology {
         topo::check_coulomb(n, want, K, eps, s14);
         std::vector<double> h = fetch(charges_dev, (size_t)n, s);
         topo::scale_charges(h, K);
+        double sum = 0.0;
+        for (double v : h) sum += v;
         DevBuf<double> nq;
         put(nq, h, s);
         EMDEE_HIP_CHECK(hipStreamSynchronize(s));
         // ---- commit
         q_tab.swap(nq);
-        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14;
+        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14; q_sum = sum;
         has_charges = true;
     }
 };

@@ -68,6 +68,13 @@ set_coulomb!(md::VelocityVerlet, charges::Union{Nothing,HipArray{Float64,1}}, co
                 charges === nothing ? C_NULL : charges.ptr, charges === nothing ? 0 : length(charges), Float64(coulomb_k),
                 Float64(eps_rf), Float64(coulomb14scale)))
 
+# int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]);
+# Ewald summation for a charged engine: alpha > 0 (an inverse length) switches its Coulomb terms from the reaction field to the
+# Ewald sum over the integer wave vectors |n_d| <= kmax[d]; alpha = 0 switches back (kmax may then be `nothing`).
+set_ewald!(md::VelocityVerlet, alpha, kmax::Union{Nothing,Vector{Int32}}=nothing) =
+    check(ccall((:emdee_md_set_ewald, libemdee_hip), Int32, (Ptr{Cvoid}, Float64, Ptr{Int32}), md.handle, Float64(alpha),
+                kmax === nothing ? C_NULL : kmax))
+
 # Pressure coupling (include/emdee_hip.h; undivided boxes).
 # int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);   -> (lo, len) of the engine's box
 function box(md::VelocityVerlet)

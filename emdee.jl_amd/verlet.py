@@ -52,7 +52,9 @@ def bonded_arrays(kind, atoms, params, device, id_dtype):
 KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick": 3, "lj_force_nbr_fused_step": 4,
            # decomposed steps: the fused launches over interior bricks (or all bricks, in-order form), over boundary bricks, and the
            # halo (pack -> exchange -> unpack) on the stream it runs on
-           "fused_step_interior": 5, "fused_step_boundary": 6, "halo": 7}
+           "fused_step_interior": 5, "fused_step_boundary": 6, "halo": 7,
+           # the reciprocal-space pass of an Ewald engine (set_ewald_); "lj_force_nbr" contains it as well
+           "ewald_reciprocal": 8}
 
 
 class VelocityVerlet:
@@ -305,6 +307,19 @@ class VelocityVerlet:
         q = charge_array(charges, self.device)
         _lib.call("emdee_md_set_coulomb", self._handle, C.c_void_p(q.data_ptr()) if q.numel() else None, int(q.shape[0]),
                   float(coulomb_k), float(eps_rf), float(coulomb14scale))
+
+    def set_ewald_(self, alpha, kmax=None):
+        """Ewald summation for a charged engine (include/emdee_hip.h emdee_md_set_ewald): alpha > 0, the splitting parameter (an
+        inverse length), switches the Coulomb terms from the reaction field to the Ewald sum over the integer wave vectors
+        |n_d| <= kmax[d] (one int for all three axes, or three); alpha = 0 switches back to the reaction field."""
+        if kmax is None:
+            arr = None
+        else:
+            k = [int(v) for v in kmax] if hasattr(kmax, "__len__") else [int(kmax)] * 3
+            if len(k) != 3:
+                raise ValueError("set_ewald_: kmax is one integer or three")
+            arr = (C.c_int32 * 3)(*k)
+        _lib.call("emdee_md_set_ewald", self._handle, float(alpha), arr)
 
     def close(self):
         if self._handle is not None:

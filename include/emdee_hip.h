@@ -234,6 +234,46 @@ int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev
 int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n, double coulomb_k, double eps_rf,
                              double coulomb14scale);
 
+/* Ewald summation for a charged engine (emdee_md_set_coulomb first): alpha > 0 switches the engine's Coulomb terms from the
+ * reaction field to the classical Ewald sum with splitting parameter alpha (an inverse length) and the integer wave vectors n,
+ * |n_d| <= kmax[d], n != 0.  While it is on eps_rf is not looked at; coulomb_k and coulomb14scale stay those of
+ * emdee_md_set_coulomb.  alpha == 0 switches back to the reaction field (kmax is then not looked at).  With qq = K q_i q_j,
+ * V the current volume, Q = sum q_i and N the atom count:
+ *   real space, every listed pair with r^2 < rc^2:
+ *     U = qq erfc(alpha r) / r
+ *     W = -r dU/dr = qq (erfc(alpha r) / r + (2 alpha / sqrt(pi)) exp(-alpha^2 r^2)),   F_i = (W / r^2) d
+ *     halves to each atom in energies, virials and tensors, as the reaction-field terms.
+ *   excluded pair (struck from the rows; minimum image, NO cutoff test):
+ *     U = -qq erf(alpha r) / r
+ *     W = -qq (erf(alpha r) / r - (2 alpha / sqrt(pi)) exp(-alpha^2 r^2))
+ *   1-4 pair: its Coulomb part is coulomb14scale qq / r plus the excluded-pair correction above, with no cutoff test; its LJ
+ *     part keeps lj14scale and the cutoff test.
+ *   reciprocal space, k = 2 pi (n_x / L_x, n_y / L_y, n_z / L_z) of the current box, A(k) = (4 pi / V) exp(-k^2 / 4 alpha^2) / k^2,
+ *   S(k) = sum_j q_j exp(i k.r_j):
+ *     E_k  = (K / 2) sum_k A |S|^2
+ *     F_i  = K q_i sum_k A k (sin(k.r_i) Re S - cos(k.r_i) Im S)
+ *     e_i  = (K / 2) q_i sum_k A (cos(k.r_i) Re S + sin(k.r_i) Im S)
+ *     W_i^ab = (K / 2) q_i sum_k A (cos(k.r_i) Re S + sin(k.r_i) Im S) (delta_ab - 2 k_a k_b (1 / k^2 + 1 / (4 alpha^2)))
+ *     and the per-atom virial is its trace.  A direct O(N K) sum in fp64 whatever the engine's precision, no floating-point
+ *     atomics: the same bits from run to run.
+ *   self term: -K (alpha / sqrt(pi)) q_i^2 in e_i; no force, no virial.
+ *   neutralising background: E_n = -pi K Q^2 / (2 V alpha^2); E_n / N in every e_i and in the xx, yy and zz components of every
+ *     atom's tensor (3 E_n / N in its virial).
+ * All of these are added to the LJ and bonded terms in every output of a charged engine: forces, per-atom energies, virials
+ * and tensors, emdee_md_energies and emdee_md_pressure_tensor; the barostats couple to the Ewald pressure.  emdee_md_scale_box
+ * keeps alpha and kmax and evaluates on the new box.  On return forces, energies and virials are current, as after
+ * emdee_md_set_coulomb.
+ *   - The setting survives a later emdee_md_set_coulomb with new charges and an emdee_md_set_state with the same atom count;
+ *     clearing the charges (n = 0) switches it off.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous setting in force: alpha negative or not finite, a NULL kmax, a kmax[d]
+ *     < 1 or > 64, alpha rc < 1 (nothing is split off).  EMDEE_ERR_STATE: before emdee_md_set_state, without charges, with
+ *     ghosts, on a box that is not periodic in all three dimensions, on an integrator lent by emdee_dd_engine.
+ *   - The row filter records the slot of every excluded and 1-4 partner at every build; a partner missing from its owner's rows
+ *     (the pair spans more than rc + skin) is EMDEE_ERR_STATE naming the pair, under the rules of a bonded partner.
+ *   - There is no emdee_dd_* counterpart (decomposed runs have the reaction field only) and nothing on the operator path.
+ *   - The reciprocal-space pass runs behind every force pass; its device time is emdee_md_kernel_time index 8. */
+int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -341,7 +381,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
 /* Per-kernel device time from HIP events recorded on the context's stream while
  * profiling is on.  kernel: 0 = lj_force_nbr (plain force launches), 1 = verlet_kick_drift, 2 = rebuild
  * (bin + sort + nbr_build), 3 = verlet_kick, 4 = lj_force_nbr with the velocity-Verlet update fused in
- * (emdee_md_step's inner steps, emdee_md_fused_step).  Blocking. */
+ * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald),
+ * which index 0 contains as well.  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
