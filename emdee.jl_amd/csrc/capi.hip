@@ -272,6 +272,9 @@ int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n,
 int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_ewald(alpha, kmax); });
 }
+int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int32_t order) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_pme(alpha, grid, order); });
+}
 
 int32_t emdee_compute_nonbonded(emdee_ctx *ctx, void *forces_dev, void *energies_dev, void *virials_dev,
                                 const void *positions_dev, double L, emdee_nbr *nbr, emdee_lj_model model,

@@ -13,10 +13,12 @@
 //      fills the device; k_ewald_add sums the ranges in order and adds the result, the self term and the neutralising
 //      background to the cell-ordered arrays.  The forces-only instance computes the three force sums alone.
 // The sums run over the half space of wave vectors; -k contributes the same to every one of them, hence the factors 2.
-// A particle-mesh version would replace kernels 2 and 3 behind EwaldRecip::run.
+// The particle-mesh version (emdee_md_set_pme, pme.hpp) replaces kernels 1 to 3 behind EwaldRecip::run and hands k_ewald_add one
+// range of the same layout.
 #pragma once
 
 #include "kernels.hpp"
+#include "pme.hpp"
 #include "topology.hpp"
 #include "wave_ops.hpp"
 
@@ -199,21 +201,41 @@ struct EwaldRecip {
     DevBuf<topo::EwaldK> ktab;
     DevBuf<double2> ph, S, partial;
     DevBuf<double> part;
+    PmeRecip<real> pme;                                      // on: the mesh takes the place of the direct sum (emdee_md_set_pme)
 
     bool on() const { return alpha > 0.0; }
     void set(double a, const int32_t k[3]) {
         alpha = a;
+        pme.clear();
         for (int d = 0; d < 3; d++) kmax[d] = k[d];
         nvec = topo::ewald_vectors(kmax);
         table_len[0] = -1.0;
     }
-    void clear() { alpha = 0.0; }
+    void set_pme(double a, const int32_t grid[3], int32_t order) {
+        alpha = a;
+        pme.set(grid, order);
+    }
+    void clear() { alpha = 0.0; pme.clear(); }
 
     // adds the reciprocal-space terms of the n atoms (all owned) to the outputs `bitmask` names; q: sqrt(K) q per slot, q_sum
-    // their sum
+    // their sum, q_abs the sum of their magnitudes
     void run(hipStream_t s, int n, size_t pitch, const AtomView<real> &atoms, const double lo[3], const double len[3], const real *q,
-             double q_sum, int bitmask, real *frc, real *en, real *vir, real *vt) {
+             double q_sum, double q_abs, int bitmask, real *frc, real *en, real *vir, real *vt) {
         if (!on() || n == 0) return;
+        if (pme.on()) {
+            const bool all = bitmask != EMDEE_FORCES;
+            part.ensure((size_t)(all ? 10 : 3) * pitch);
+            pme.run(s, n, pitch, atoms, lo, len, alpha, q, q_abs, all, part.ptr);
+            const double self_c = alpha / std::sqrt(M_PI);
+            const double V = len[0] * len[1] * len[2], e_bg = -M_PI * q_sum * q_sum / (2.0 * V * alpha * alpha) / (double)n;
+            if (all)
+                hipLaunchKernelGGL((k_ewald_add<real, true>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, 1, part.ptr, q, self_c, e_bg,
+                                   bitmask, frc, en, vir, vt);
+            else
+                hipLaunchKernelGGL((k_ewald_add<real, false>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, 1, part.ptr, q, self_c, e_bg,
+                                   bitmask, frc, en, vir, vt);
+            return;
+        }
         const int nk = (int)(nvec.size() / 3);
         if (table_len[0] != len[0] || table_len[1] != len[1] || table_len[2] != len[2] || table_alpha != alpha) {
             EMDEE_HIP_CHECK(hipStreamSynchronize(s));        // (nothing in flight reads the table it replaces)

@@ -55,6 +55,7 @@ struct IMd {
     virtual void set_bonded(int32_t kind, const int32_t *atoms, const double *params, int32_t n_terms) = 0;
     virtual void set_coulomb(const double *charges, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) = 0;
     virtual void set_ewald(double alpha, const int32_t *kmax) = 0;
+    virtual void set_pme(double alpha, const int32_t *grid, int32_t order) = 0;
     virtual void get_box(double lo[3], double len[3]) = 0;
     virtual void scale_box(const double mu[3], double velocity_scale) = 0;
     virtual void set_barostat(int32_t kind, int32_t coupling, const double *p_ref, const double *compressibility, double tau_p,

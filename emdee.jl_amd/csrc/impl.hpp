@@ -582,6 +582,20 @@ struct MdImpl : IMd {
         });
         sys.check_ewald();
     }
+    // emdee_md_set_pme: as set_ewald, with the mesh in the place of the direct sum
+    void set_pme(double alpha, const int32_t *grid, int32_t order) override {
+        EMDEE_REQUIRE(alpha == 0.0 || (std::isfinite(alpha) && alpha > 0.0), EMDEE_ERR_INVALID, "set_pme: alpha must be finite and >= 0");
+        if (alpha > 0.0) topo::check_pme(alpha, grid, order, std::sqrt(sys.model_d.rc2));
+        require_undivided("set_pme");
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "set_pme: no state loaded (call emdee_md_set_state first)");
+        EMDEE_REQUIRE(sys.has_charges() && !sys.charges_stale(), EMDEE_ERR_STATE, "set_pme: the engine has no charges for its state (call emdee_md_set_coulomb first)");
+        EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "set_pme: the box must be periodic in all three dimensions");
+        install("particle-mesh Ewald summation", "a decomposed run has none", [&] {
+            if (alpha > 0.0) sys.ewald.set_pme(alpha, grid, order); else sys.ewald.clear();
+            sys.reset_ewald_error();
+        });
+        sys.check_ewald();
+    }
     void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) override {
         use_device(sys.ctx);
         if (n <= 0) return;

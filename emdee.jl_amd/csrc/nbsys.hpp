@@ -1252,7 +1252,7 @@ struct NbSystem {
                                flags.ptr + 18);
         }
         Timed t(this, T_EWALD);
-        ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
+        ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, tables->q_abs, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
     }
     void add_post_terms(int bitmask) {
         add_pairs14(bitmask);

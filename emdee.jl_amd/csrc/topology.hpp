@@ -254,6 +254,89 @@ inline std::vector<EwaldK> ewald_table(const std::vector<int32_t> &n, const doub
     }
     return t;
 }
+// ---- smooth particle-mesh Ewald (emdee_md_set_pme; pme.hpp): the argument checks, the spline moduli, the index folding, the
+// FFT twiddles and the fixed-point scale of the charge mesh
+// alpha > 0 (alpha == 0 switches back to the reaction field and is not checked here); rc: the LJ model's cutoff
+inline void check_pme(double alpha, const int32_t *grid, int32_t order, double rc) {
+    EMDEE_REQUIRE(std::isfinite(alpha) && alpha > 0.0, EMDEE_ERR_INVALID, "set_pme: alpha must be finite and >= 0");
+    EMDEE_REQUIRE(grid != nullptr, EMDEE_ERR_INVALID, "set_pme: grid is NULL");
+    for (int d = 0; d < 3; d++)
+        EMDEE_REQUIRE(grid[d] >= 8 && grid[d] <= 256 && (grid[d] & (grid[d] - 1)) == 0, EMDEE_ERR_INVALID,
+                      "set_pme: grid[%d] = %d is not a power of two in [8, 256]", d, grid[d]);
+    EMDEE_REQUIRE(order == 4 || order == 6, EMDEE_ERR_INVALID, "set_pme: order = %d is neither 4 nor 6", order);
+    EMDEE_REQUIRE(alpha * rc >= 1.0, EMDEE_ERR_INVALID, "set_pme: alpha rc = %g < 1 splits nothing off (erfc(alpha rc) = %g at the cutoff)",
+                  alpha * rc, std::erfc(alpha * rc));
+}
+// the cardinal B-spline of order p at t + j, j = 0 .. p - 1, for 0 <= t < 1: w[j] = M_p(t + j); with dw, dw[j] = M_p'(t + j).
+// M_n(x) = (x M_{n-1}(x) + (n - x) M_{n-1}(x - 1)) / (n - 1), M_2(x) = 1 - |x - 1| on [0, 2]; M_n' (x) = M_{n-1}(x) - M_{n-1}(x - 1).
+// (pme.hpp pme_axis / pme_raise is this recursion on the device, on named scalars)
+inline void pme_bspline(double t, int p, double *w, double *dw) {
+    w[0] = t; w[1] = 1.0 - t;
+    for (int j = 2; j < p; j++) w[j] = 0.0;
+    for (int n = 3; n <= p; n++) {
+        if (n == p && dw != nullptr) {
+            dw[0] = w[0];
+            for (int j = 1; j < p; j++) dw[j] = w[j] - w[j - 1];
+        }
+        for (int j = n - 1; j >= 1; j--) w[j] = ((t + j) * w[j] + (n - t - j) * w[j - 1]) / (n - 1);
+        w[0] = t * w[0] / (n - 1);
+    }
+}
+// cos(pi x) and sin(pi x) of x = num / den, exact in the octant: the argument of the library call is at most pi / 4
+inline void pme_sincospi(int64_t num, int64_t den, double *s, double *c) {
+    num %= 2 * den;
+    if (num < 0) num += 2 * den;                             // x in [0, 2)
+    const bool neg = num >= den;                             // sin(pi (x + 1)) = -sin(pi x), and cos alike
+    if (neg) num -= den;
+    const bool mirror = 2 * num > den;                       // x in (1/2, 1): sin(pi (1 - x)) = sin(pi x), cos changes sign
+    if (mirror) num = den - num;
+    double sv, cv;
+    if (4 * num <= den) { sv = std::sin(M_PI * (double)num / (double)den); cv = std::cos(M_PI * (double)num / (double)den); }
+    else { sv = std::cos(M_PI * (double)(den - 2 * num) / (double)(2 * den)); cv = std::sin(M_PI * (double)(den - 2 * num) / (double)(2 * den)); }
+    if (mirror) cv = -cv;
+    *s = neg ? -sv : sv;
+    *c = neg ? -cv : cv;
+}
+// |b(m)|^2, m = 0 .. K - 1, of Essmann et al. eq. 4.4: 1 / |sum_{k=0}^{p-2} M_p(k + 1) exp(2 pi i m k / K)|^2.  Even orders have
+// no zero of the sum at m = K / 2.
+inline std::vector<double> pme_moduli(int K, int p) {
+    double w[8];
+    pme_bspline(0.0, p, w, nullptr);                         // w[j] = M_p(j): M_p(k + 1) = w[k + 1]
+    std::vector<double> b((size_t)K);
+    for (int m = 0; m < K; m++) {
+        double re = 0.0, im = 0.0;
+        for (int k = 0; k <= p - 2; k++) {
+            double s, c;
+            pme_sincospi(2 * (int64_t)m * k, K, &s, &c);
+            re += w[k + 1] * c; im += w[k + 1] * s;
+        }
+        b[(size_t)m] = 1.0 / (re * re + im * im);
+    }
+    return b;
+}
+// the mesh index m of an axis of K points as the integer of its wave vector, in (-K/2, K/2]
+inline int pme_fold(int m, int K) { return m <= K / 2 ? m : m - K; }
+// exp(-2 pi i j / K), j = 0 .. K/2 - 1, as {re, im, ...}: the twiddles of the forward transform (the inverse conjugates them)
+inline std::vector<double> pme_twiddles(int K) {
+    std::vector<double> t((size_t)K);
+    for (int j = 0; j < K / 2; j++) {
+        double s, c;
+        pme_sincospi(2 * (int64_t)j, K, &s, &c);
+        t[2 * (size_t)j] = c; t[2 * (size_t)j + 1] = -s;
+    }
+    return t;
+}
+// The charge mesh is summed in 64-bit fixed point: a contribution q w (|w| <= 1) becomes the integer nearest to q w 2^shift.
+// With sum |q_i| < 2^e (frexp) and shift = 61 - e no mesh point exceeds 2^61 + N / 2 < 2^63 in magnitude, whatever the
+// configuration; the quantum 2^-shift = 2^(e - 61) is at most 2^-60 sum |q_i|.
+inline int pme_fixed_shift(double sum_abs_q) {
+    EMDEE_REQUIRE(std::isfinite(sum_abs_q) && sum_abs_q >= 0.0, EMDEE_ERR_INVALID, "pme: the sum of |q| is not finite");
+    if (sum_abs_q == 0.0) return 0;
+    int e;
+    (void)std::frexp(sum_abs_q, &e);
+    return std::min(61 - e, 1000);
+}
+
 // the error text for entry `entry` of the struck CSR (xs / xi of build_pairs) whose owner did not find the partner in its rows
 inline std::string lost_pair_message(const std::vector<int32_t> &excl, const std::vector<int32_t> &p14, int64_t entry) {
     const PairCsrs t = build_pairs(excl, p14);

@@ -118,6 +118,7 @@ struct Topology {
     int64_t q_n = 0;                                         // keys 0 .. q_n - 1 have a charge
     double coulomb_k = 0.0, eps_rf = INFINITY, scale14c = 1.0;
     double q_sum = 0.0;                                      // sum of sqrt(K) q in key order (the Ewald background term)
+    double q_abs = 0.0;                                      // sum of sqrt(K) |q| (the fixed-point scale of the PME charge mesh)
     bool has_charges = false;
     // Replaces the charges by the n at charges_dev (device, fp64, one per key); n = 0 clears them.  want >= 0: the only
     // non-zero n accepted (an undivided engine's atom count).
@@ -130,14 +131,14 @@ struct Topology {
         topo::check_coulomb(n, want, K, eps, s14);
         std::vector<double> h = fetch(charges_dev, (size_t)n, s);
         topo::scale_charges(h, K);
-        double sum = 0.0;
-        for (double v : h) sum += v;
+        double sum = 0.0, sum_abs = 0.0;
+        for (double v : h) { sum += v; sum_abs += std::fabs(v); }
         DevBuf<double> nq;
         put(nq, h, s);
         EMDEE_HIP_CHECK(hipStreamSynchronize(s));
         // ---- commit
         q_tab.swap(nq);
-        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14; q_sum = sum;
+        q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14; q_sum = sum; q_abs = sum_abs;
         has_charges = true;
     }
 };

@@ -75,6 +75,14 @@ set_ewald!(md::VelocityVerlet, alpha, kmax::Union{Nothing,Vector{Int32}}=nothing
     check(ccall((:emdee_md_set_ewald, libemdee_hip), Int32, (Ptr{Cvoid}, Float64, Ptr{Int32}), md.handle, Float64(alpha),
                 kmax === nothing ? C_NULL : kmax))
 
+# int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int32_t order);
+# Smooth particle-mesh Ewald for a charged engine: alpha > 0 switches the reciprocal-space terms of the Ewald sum to a mesh of
+# grid[d] points per axis (powers of two in [8, 256]) with B-splines of order 4 or 6; alpha = 0 switches back to the reaction
+# field (grid may then be `nothing`).  Whichever of set_ewald! and set_pme! came last with alpha > 0 is in force.
+set_pme!(md::VelocityVerlet, alpha, grid::Union{Nothing,Vector{Int32}}=nothing, order=4) =
+    check(ccall((:emdee_md_set_pme, libemdee_hip), Int32, (Ptr{Cvoid}, Float64, Ptr{Int32}, Int32), md.handle, Float64(alpha),
+                grid === nothing ? C_NULL : grid, Int32(order)))
+
 # Pressure coupling (include/emdee_hip.h; undivided boxes).
 # int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);   -> (lo, len) of the engine's box
 function box(md::VelocityVerlet)

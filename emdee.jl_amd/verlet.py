@@ -53,7 +53,7 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # decomposed steps: the fused launches over interior bricks (or all bricks, in-order form), over boundary bricks, and the
            # halo (pack -> exchange -> unpack) on the stream it runs on
            "fused_step_interior": 5, "fused_step_boundary": 6, "halo": 7,
-           # the reciprocal-space pass of an Ewald engine (set_ewald_); "lj_force_nbr" contains it as well
+           # the reciprocal-space pass of an Ewald engine (set_ewald_, set_pme_); "lj_force_nbr" contains it as well
            "ewald_reciprocal": 8}
 
 
@@ -320,6 +320,20 @@ class VelocityVerlet:
                 raise ValueError("set_ewald_: kmax is one integer or three")
             arr = (C.c_int32 * 3)(*k)
         _lib.call("emdee_md_set_ewald", self._handle, float(alpha), arr)
+
+    def set_pme_(self, alpha, grid=None, order=4):
+        """Smooth particle-mesh Ewald for a charged engine (include/emdee_hip.h emdee_md_set_pme): alpha > 0 switches the
+        reciprocal-space terms of the Ewald sum to a mesh of grid[d] points per axis (one int for all three axes, or three; powers
+        of two in [8, 256]) with cardinal B-splines of the given order (4 or 6); the real-space terms are those of set_ewald_.
+        alpha = 0 switches back to the reaction field.  Whichever of set_ewald_ and set_pme_ came last with alpha > 0 is in force."""
+        if grid is None:
+            arr = None
+        else:
+            g = [int(v) for v in grid] if hasattr(grid, "__len__") else [int(grid)] * 3
+            if len(g) != 3:
+                raise ValueError("set_pme_: grid is one integer or three")
+            arr = (C.c_int32 * 3)(*g)
+        _lib.call("emdee_md_set_pme", self._handle, float(alpha), arr, int(order))
 
     def close(self):
         if self._handle is not None:

@@ -274,6 +274,39 @@ int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n,
  *   - The reciprocal-space pass runs behind every force pass; its device time is emdee_md_kernel_time index 8. */
 int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]);
 
+/* Smooth particle-mesh Ewald (Essmann et al., J. Chem. Phys. 103, 8577, 1995) for a charged engine: alpha > 0 switches the
+ * engine's reciprocal-space terms to a mesh of K_d = grid[d] points per axis and cardinal B-splines theta_p of order p = order.
+ * alpha == 0 switches back to the reaction field (grid and order are then not looked at).  It excludes emdee_md_set_ewald:
+ * whichever of the two was called last with alpha > 0 is in force, and alpha == 0 through either returns to the reaction field.
+ * The real-space side is that of emdee_md_set_ewald, term for term: erfc pair terms, the correction of excluded and 1-4 pairs,
+ * the coulomb14scale qq / r term, the self term, the neutralising background and the missing-partner error.  Only the
+ * reciprocal sum over k is replaced.  With u_d = K_d (x_d - lo_d) / L_d the scaled coordinates, m a mesh point,
+ *   Q(m) = sum_j q_j prod_d theta_p(u_jd - m_d) over periodic images          (the charge mesh),
+ *   |b_d(m)|^2 = 1 / |sum_{k=0}^{p-2} theta_p(k + 1) exp(2 pi i m k / K_d)|^2   (Essmann eq. 4.4),  |b|^2 = |b_x|^2 |b_y|^2 |b_z|^2,
+ *   k = 2 pi (n_x / L_x, n_y / L_y, n_z / L_z) with n_d the mesh index m_d folded to (-K_d / 2, K_d / 2], A(k) as above,
+ *   F the discrete Fourier transform over the mesh, F^-1 its unnormalised inverse:
+ *     E    = (K / 2) sum_{m != 0} A |b|^2 |F Q(m)|^2
+ *     phi  = F^-1[A |b|^2 F Q]                                               (the convolved mesh)
+ *     F_i  = -K q_i sum_m grad theta(u_i - m) phi(m)     (the analytic spline derivative: the exact gradient of E)
+ *     e_i  = (K / 2) q_i sum_m theta(u_i - m) phi(m)
+ *     W_i^ab = (K / 2) q_i sum_m theta(u_i - m) phi_ab(m),  phi_ab = F^-1[A |b|^2 (delta_ab - 2 k_a k_b (1 / k^2 + 1 / (4 alpha^2))) F Q]
+ *     and the per-atom virial is its trace.  Summed over the atoms the tensor is Essmann's eq. 2.7, the exact volume derivative
+ *     of E at a fixed mesh.  The mesh forces do not sum to zero exactly (the mesh breaks translation invariance).
+ * Mesh and transforms are fp64 whatever the engine's precision.  The charge mesh is summed in 64-bit fixed point with integer
+ * atomic adds, no floating-point atomics: the same bits from run to run.  The pass that writes every output costs one forward
+ * and seven inverse transforms, the forces-only pass one and one; two complex meshes of K_x K_y K_z points are held.
+ * emdee_md_scale_box and the barostats keep alpha, grid and order and evaluate on the new box.
+ *   - The setting survives a later emdee_md_set_coulomb with new charges and an emdee_md_set_state with the same atom count;
+ *     clearing the charges (n = 0) switches it off.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous setting in force: alpha negative or not finite, alpha rc < 1, a NULL
+ *     grid, a grid[d] that is not a power of two in [8, 256], an order other than 4 or 6 (even orders have no zero of the spline
+ *     modulus at the Nyquist index).  EMDEE_ERR_STATE: before emdee_md_set_state, without charges, with ghosts, on a box that
+ *     is not periodic in all three dimensions, on an integrator lent by emdee_dd_engine.
+ *   - Scope: undivided orthorhombic engines only; complex-to-complex transforms; no emdee_dd_* counterpart; nothing on the
+ *     operator path.
+ *   - The pass's device time is emdee_md_kernel_time index 8, as the direct sum's. */
+int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int32_t order);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -381,7 +414,7 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
 /* Per-kernel device time from HIP events recorded on the context's stream while
  * profiling is on.  kernel: 0 = lj_force_nbr (plain force launches), 1 = verlet_kick_drift, 2 = rebuild
  * (bin + sort + nbr_build), 3 = verlet_kick, 4 = lj_force_nbr with the velocity-Verlet update fused in
- * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald),
+ * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald, emdee_md_set_pme),
  * which index 0 contains as well.  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
