@@ -269,6 +269,9 @@ int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev
 int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_coulomb(charges_dev, n, coulomb_k, eps_rf, coulomb14scale); });
 }
+int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double *geom_dev, int32_t n_mol) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_rigid3(atoms_dev, geom_dev, n_mol); });
+}
 int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_ewald(alpha, kmax); });
 }

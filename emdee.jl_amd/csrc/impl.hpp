@@ -196,6 +196,17 @@ struct MdImpl : IMd {
         if (!lent) { sys.reset_bonded_error(); sys.reset_ewald_error(); }   // (a new state: the bonded terms and the struck pairs get another chance; a decomposition resets its own)
         since_build = 0;
         current_mask = 0;
+        // (rigid molecules set for another atom count stay in force, unused, as charges do; for the same count the table is
+        // checked against the new state and the velocities are projected again)
+        if (!lent && sys.has_rigid()) {
+            sys.reset_settle_error();
+            rigid_unchecked = true;
+            if (!sys.rigid_stale() && ng == 0) {
+                sys.settle_check_state(sys.tables->r_atoms.ptr, sys.tables->r_geom.ptr, sys.tables->r_atoms_h, sys.tables->r_n);
+                sys.settle_velocities();
+                rigid_unchecked = false;
+            }
+        }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
         // cleared -- NbSystem::ensure_charges)
         if (!defer_forces && !sys.charges_stale()) {
@@ -206,6 +217,8 @@ struct MdImpl : IMd {
     }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
+    // rigid molecules whose table has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
+    bool rigid_unchecked = false;
     // an engine of a decomposition (emdee_dd_engine): its pair tables are the decomposition's, keyed by global id
     bool lent = false;
     // decomposed domains: the global ids of the atoms handed to set_state (caller order, owned atoms and ghosts); they travel
@@ -234,8 +247,12 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         EMDEE_REQUIRE(!sys.bonded_broken, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
         EMDEE_REQUIRE(!sys.ewald_broken, EMDEE_ERR_STATE, "md_step: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
+        EMDEE_REQUIRE(!sys.settle_broken, EMDEE_ERR_STATE, "md_step: a rigid molecule had no solution; replace the table or the state");
+        EMDEE_REQUIRE(!sys.has_rigid() || !(sys.rigid_stale() || rigid_unchecked), EMDEE_ERR_STATE, "md_step: rigid molecules set for %lld atoms, "
+                      "the state holds %d (or does not fit them): set them again or clear them (emdee_md_set_rigid3)", (long long)sys.tables->r_limit, sys.n_owned);
         if (nsteps == 0) return;
         if (baro.kind != EMDEE_BAROSTAT_OFF) { step_coupled(nsteps, dt, rebuild_every); return; }
+        if (sys.has_rigid()) { step_rigid(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
@@ -293,6 +310,8 @@ struct MdImpl : IMd {
     void scale_box(const double mu[3], double vscale) override {
         use_device(sys.ctx);
         require_undivided("scale_box");
+        EMDEE_REQUIRE(!sys.has_rigid(), EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
+                      "would break their geometry, and its pressure lacks the constraint virial");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
         sys.scale_box(mu, vscale);                           // (validates before it writes)
         since_build = 0;
@@ -308,6 +327,8 @@ struct MdImpl : IMd {
                       double temperature, uint64_t seed, uint64_t first_step) override {
         use_device(sys.ctx);
         require_undivided("set_barostat");
+        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_rigid(), EMDEE_ERR_STATE, "set_barostat: the engine holds rigid molecules "
+                      "(emdee_md_set_rigid3): its pressure lacks the constraint virial, and scaling atom by atom would break their geometry");
         if (kind == EMDEE_BAROSTAT_OFF) { baro.kind = EMDEE_BAROSTAT_OFF; return; }
         EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_BERENDSEN || kind == EMDEE_BAROSTAT_CRESCALE, EMDEE_ERR_INVALID, "set_barostat: unknown kind %d", kind);
         EMDEE_REQUIRE(coupling >= EMDEE_COUPLE_ISOTROPIC && coupling <= EMDEE_COUPLE_ANISOTROPIC, EMDEE_ERR_INVALID, "set_barostat: unknown coupling %d", coupling);
@@ -354,6 +375,29 @@ struct MdImpl : IMd {
         }
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
+    }
+    // emdee_md_step with rigid molecules (emdee_md_set_rigid3): step_coupled's loop shape -- every step closes its own half kick, so
+    // the state after s steps does not depend on how they were dealt to calls -- with the three constraint stages around the
+    // unchanged kernels: (a) the constrained atoms' positions are remembered, (c) SETTLE on the drifted records, (e) the bond
+    // components of the relative velocities are removed.  Stage (c) re-tests its atoms against the rebuild threshold, so the
+    // displacement word is read after it; a re-sort between (c) and (e) is harmless (the stages find atoms through inv_perm).
+    void step_rigid(int nsteps, double dt, int rebuild_every) {
+        if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
+        for (int s = 0; s < nsteps; s++) {
+            sys.settle_gather();
+            sys.kick_drift(0.5 * dt, dt);
+            sys.settle_positions(dt);
+            since_build++;
+            const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
+            if (rb) { sys.resort(); since_build = 0; }
+            sys.compute_forces(EMDEE_FORCES);
+            sys.kick(0.5 * dt);
+            sys.settle_velocities();
+            current_mask = EMDEE_FORCES;
+        }
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
+        sys.check_settle();                                  // (one read-back per call)
     }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
@@ -511,11 +555,12 @@ struct MdImpl : IMd {
     void kernel_time(int kernel, double *total_ms, int64_t *launches) override {
         // ids 0..3: the TimerIds; 4: every fused step launch (interior + boundary halves of a decomposed step together, as
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
-        // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 8, EMDEE_ERR_INVALID, "kernel id out of range");
+        // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
+        // 9: the constraint stages of an engine with rigid molecules
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 9, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[9][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
-                               {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}};
+        const int ids[10][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+                                {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -533,13 +578,14 @@ struct MdImpl : IMd {
     void set_langevin_ids(const int64_t *ids) override { sys.lgv_ids = reinterpret_cast<const long long *>(ids); }
     // The install path of the three table setters: refused on a domain's engine (`entry`: the decomposition's call for `what`)
     // and without a loaded, ghost-free state; then `set` replaces the table and resets what it must, and the list, the plan and
-    // the forces follow the new tables on return.
+    // the forces follow the new tables on return (relist = false: a table the list and the forces do not depend on).
     template <class Set>
-    void install(const char *what, const char *entry, Set &&set) {
+    void install(const char *what, const char *entry, Set &&set, bool relist = true) {
         use_device(sys.ctx);
         EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s of a decomposed run: %s (this integrator is a domain's, lent by emdee_dd_engine)", what, entry);
         EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "%s: set them on a loaded integrator without ghosts (call emdee_md_set_state first)", what);
         set();
+        if (!relist) { EMDEE_HIP_CHECK(hipGetLastError()); return; }
         sys.has_list = false; sys.plan_valid = false;        // (the rows in use follow the old tables; charged and uncharged engines take different kernels and LDS plans)
         sys.resort();                                        // the list, rows and slots for the new tables (a two-species box leaves the typed kernels)
         since_build = 0;
@@ -567,6 +613,20 @@ struct MdImpl : IMd {
             sys.reset_charge_error();
             if (n == 0) sys.ewald.clear();                   // (no charges, no Ewald sum: the next set_coulomb starts with the reaction field)
         });
+    }
+    // emdee_md_set_rigid3: all or nothing -- the candidate table is checked on the host and then against the loaded state before it
+    // replaces the one in force; no atom moves, the velocities are projected once (stage (e)).  The neighbour list and the forces
+    // do not depend on the table: nothing is rebuilt.
+    void set_rigid3(const int32_t *atoms, const double *geom, int32_t n_mol) override {
+        EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF, EMDEE_ERR_STATE, "set_rigid3: pressure coupling is on (emdee_md_set_barostat): the pressure "
+                      "of an engine with rigid molecules lacks the constraint virial; switch the coupling off first");
+        install("rigid molecules", "a decomposed run has none", [&] {
+            sys.own_tables.set_rigid3(atoms, geom, n_mol, sys.n_owned, sys.stream(),
+                                      [&](const int *a, const double *g, const std::vector<int32_t> &h, int n) { sys.settle_check_state(a, g, h, n); });
+            sys.reset_settle_error();
+            rigid_unchecked = false;
+            if (sys.has_rigid()) sys.settle_velocities();
+        }, false);
     }
     // emdee_md_set_ewald: all or nothing -- every refusal comes before the setting changes
     void set_ewald(double alpha, const int32_t *kmax) override {

@@ -11,6 +11,7 @@
 #include "brick.hpp"
 #include "ewald.hpp"
 #include "kernels.hpp"
+#include "settle.hpp"
 #include "topology_dev.hpp"
 #include "typed.hpp"
 
@@ -34,7 +35,8 @@ static inline void refuse_experiment_switches() {
 // T_STEP: every fused step launch but the boundary-brick halves of a decomposed step, which go to T_STEP_BOUNDARY (emdee_md_kernel_time(4)
 // reports the two together, 5 and 6 one each); T_HALO: pack -> exchange -> unpack of a decomposed step, on the stream they run on
 // T_EWALD: the reciprocal-space pass of an Ewald engine (ewald.hpp), which runs inside T_FORCE's launches as well
-enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_COUNT = 8 };
+// T_SETTLE: the three constraint stages of an engine with rigid molecules (settle.hpp)
+enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8, T_COUNT = 9 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -1254,6 +1256,73 @@ struct NbSystem {
         Timed t(this, T_EWALD);
         ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, tables->q_abs, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
     }
+    // ---------------------------------------------------------------- rigid three-site molecules (Topology::set_rigid3, settle.hpp)
+    // The three stages MdImpl::step_rigid puts around the unchanged kick + drift, force pass and kick: one thread per molecule, no
+    // atomics on the state, fp64 on unwrapped differences in both precisions.  Undivided engines only.
+    DevBuf<double> settle_x0;                                // stage (a): 9 doubles per molecule, table order
+    bool has_rigid() const { return tables->has_rigid; }
+    // an engine whose state no longer has the atom count the table was set for: it refuses to step (as with charges)
+    bool rigid_stale() const { return has_rigid() && (tables->r_limit != n_owned || id_gaps); }
+    // a molecule that moved too far for a rigid solution (flags[20], raised by k_settle_positions): as bonded_broken
+    bool settle_broken = false;
+    void reset_settle_error() {
+        settle_broken = false;
+        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 20, 0, sizeof(int), stream()));
+    }
+    void check_settle() {
+        if (!has_rigid() || !flags.ptr) return;
+        int32_t word = 0;
+        if (!settle_broken) read_back_words(ctx, stream(), flags.ptr + 20, 1, &word);
+        if (word != 0) {
+            settle_broken = true;
+            set_error("%s", topo::rigid3_message(tables->r_atoms_h, (int64_t)word - 1, "the step moved its atoms too far for a rigid "
+                      "solution (a negative radicand in SETTLE); the molecule was left as it is: replace the table or the state").c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        EMDEE_REQUIRE(!settle_broken, EMDEE_ERR_STATE, "a rigid molecule had no solution (reported before): replace the table or the state");
+    }
+    SettleArgs<real> settle_args(const int *atoms, const double *geom, int n_mol) const {
+        SettleArgs<real> a{};
+        a.n_mol = n_mol; a.atoms = atoms; a.geom = geom; a.inv_perm = inv_perm.ptr; a.rec = rec.ptr; a.vel = vel.ptr;
+        a.inv_mass = with_mass ? im.ptr : nullptr; a.pitch = pitch;
+        a.rel = rel_grid(rel_now, cell_sorted.ptr);
+        for (int d = 0; d < 3; d++) { a.box.len[d] = len[d]; a.box.per[d] = per[d]; }
+        return a;
+    }
+    SettleArgs<real> settle_args() const { return settle_args(tables->r_atoms.ptr, tables->r_geom.ptr, tables->r_n); }
+    void settle_gather() {
+        Timed t(this, T_SETTLE);
+        settle_x0.ensure((size_t)9 * tables->r_n + 1);
+        hipLaunchKernelGGL((k_settle_gather<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args(), settle_x0.ptr);
+    }
+    void settle_positions(double dt) {
+        Timed t(this, T_SETTLE);
+        const real thr = (real)(0.5 * skin);                 // (kick_drift's threshold)
+        hipLaunchKernelGGL((k_settle_positions<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args(),
+                           (const double *)settle_x0.ptr, dt > 0.0 ? 1.0 / dt : 0.0, (const real *)xb.ptr, thr * thr, flags.ptr + 1, flags.ptr + 20);
+    }
+    void settle_velocities() {
+        Timed t(this, T_SETTLE);
+        hipLaunchKernelGGL((k_settle_velocities<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args());
+    }
+    // a table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the molecule whose
+    // legs have different masses or whose atoms miss a distance by more than 1e-3 relative; one launch, one read-back
+    void settle_check_state(const int *atoms, const double *geom, const std::vector<int32_t> &atoms_h, int n_mol) {
+        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 21, 0, 2 * sizeof(int), stream()));
+        hipLaunchKernelGGL((k_settle_check<real>), dim3(blocks_for(n_mol, 256)), dim3(256), 0, stream(), settle_args(atoms, geom, n_mol), flags.ptr + 21);
+        int32_t words[2] = {0, 0};
+        read_back_words(ctx, stream(), flags.ptr + 21, 2, words);
+        if (words[0] != 0) {
+            set_error("%s", topo::rigid3_message(atoms_h, (int64_t)words[0] - 1, "the two legs have different masses").c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        if (words[1] != 0) {
+            set_error("%s", topo::rigid3_message(atoms_h, (int64_t)words[1] - 1, "the loaded positions miss a distance of the table by more "
+                      "than 1e-3 (relative): a wrong topology, not rounding").c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+    }
+
     void add_post_terms(int bitmask) {
         add_pairs14(bitmask);
         add_bonded(bitmask);

@@ -1,4 +1,4 @@
-// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, charges.  Plain C++17 on
+// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, charges.  Plain C++17 on
 // std::vector, no HIP: every function here validates or builds and throws through EMDEE_REQUIRE before it returns anything, so
 // a stand-alone host program can test it (tests/c/topology_host.cpp).  topology_dev.hpp holds the device buffers.
 #pragma once
@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "error.hpp"
@@ -194,6 +195,44 @@ inline std::string lost_partner_message(const std::vector<int32_t> (&atoms)[KIND
     snprintf(text, sizeof(text), "bonded %s %lld (atoms %d %d%s%s%s%s): a partner is farther than rc + skin from its owner at a neighbour-list "
              "build, so the term cannot be evaluated; replace the tables or the state", kind_name(kind), (long long)index, ids[0], ids[1],
              na > 2 ? " " : "", na > 2 ? std::to_string(ids[2]).c_str() : "", na > 3 ? " " : "", na > 3 ? std::to_string(ids[3]).c_str() : "");
+    return text;
+}
+
+// ---- rigid three-site molecules (emdee_md_set_rigid3): {apex, a, b} ids and {d_leg, d_base} per molecule
+// The table as a caller gave it: ids in [0, lim), no atom named twice within or across molecules, distances finite and > 0 with
+// d_base < 2 d_leg (a triangle); else refused.
+template <typename T>
+std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector<double> &geom, int64_t lim) {
+    const int64_t n = (int64_t)(raw.size() / 3);
+    EMDEE_REQUIRE((int64_t)geom.size() == 2 * n, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules but %lld distances", (long long)n, (long long)geom.size());
+    EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules (at most (2^31 - 1) / 3)", (long long)n);
+    std::vector<std::pair<int64_t, int64_t>> named;           // (id, molecule)
+    named.reserve((size_t)3 * n);
+    for (int64_t k = 0; k < n; k++) {
+        for (int a = 0; a < 3; a++) {
+            const int64_t g = raw[(size_t)3 * k + a];
+            EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_rigid3: molecule %lld names id %lld, outside [0, %lld)", (long long)k,
+                          (long long)g, (long long)lim);
+            named.emplace_back(g, k);
+        }
+        const double d_leg = geom[(size_t)2 * k], d_base = geom[(size_t)2 * k + 1];
+        EMDEE_REQUIRE(std::isfinite(d_leg) && std::isfinite(d_base) && d_leg > 0.0 && d_base > 0.0, EMDEE_ERR_INVALID,
+                      "set_rigid3: molecule %lld has a distance that is not finite and > 0", (long long)k);
+        EMDEE_REQUIRE(d_base < 2.0 * d_leg, EMDEE_ERR_INVALID, "set_rigid3: molecule %lld has d_base = %g >= 2 d_leg = %g (no triangle)",
+                      (long long)k, d_base, 2.0 * d_leg);
+    }
+    std::sort(named.begin(), named.end());
+    for (size_t k = 1; k < named.size(); k++)
+        EMDEE_REQUIRE(named[k].first != named[k - 1].first, EMDEE_ERR_INVALID, "set_rigid3: atom %lld is named twice (molecules %lld and %lld)",
+                      (long long)named[k].first, (long long)named[k - 1].second, (long long)named[k].second);
+    return std::vector<int32_t>(raw.begin(), raw.end());
+}
+// the error texts of the device checks (molecule: the number the kernels report, from 0)
+inline std::string rigid3_message(const std::vector<int32_t> &atoms, int64_t molecule, const char *what) {
+    char text[512];
+    const bool in = molecule >= 0 && (size_t)(3 * molecule + 2) < atoms.size();
+    snprintf(text, sizeof(text), "rigid molecule %lld (atoms %d %d %d): %s", (long long)molecule, in ? atoms[(size_t)3 * molecule] : -1,
+             in ? atoms[(size_t)3 * molecule + 1] : -1, in ? atoms[(size_t)3 * molecule + 2] : -1, what);
     return text;
 }
 

@@ -112,6 +112,39 @@ struct Topology {
         has_bonded = !t.terms.empty();
     }
 
+    // ---- rigid three-site molecules (emdee_md_set_rigid3; settle.hpp): {apex, a, b} caller ids and {d_leg, d_base} per molecule,
+    // undivided engines only
+    DevBuf<int> r_atoms;
+    DevBuf<double> r_geom;
+    std::vector<int32_t> r_atoms_h;                          // the ids as given (the error texts name them)
+    int r_n = 0;                                             // molecules
+    int64_t r_limit = 0;                                     // the atom count the ids were checked against
+    bool has_rigid = false;
+    // Replaces the table by the n molecules at atoms_dev / geom_dev (device); n = 0 clears it.  check(atoms, geom, n): the
+    // engine's test of the uploaded candidate against its state; it throws to refuse, and the table in force stays.
+    template <class Check>
+    void set_rigid3(const int32_t *atoms_dev, const double *geom_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && geom_dev)), EMDEE_ERR_INVALID, "set_rigid3: negative count or NULL array");
+        if (n == 0) {
+            has_rigid = false; r_n = 0; r_atoms_h.clear();
+            return;
+        }
+        EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules (at most (2^31 - 1) / 3)", (long long)n);
+        const std::vector<int32_t> raw = fetch(atoms_dev, (size_t)3 * n, s);
+        const std::vector<double> geom = fetch(geom_dev, (size_t)2 * n, s);
+        const std::vector<int32_t> h = topo::checked_rigid3(raw, geom, lim);
+        DevBuf<int> na;
+        DevBuf<double> ng;
+        put(na, h, s); put(ng, geom, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        check(na.ptr, ng.ptr, h, (int)n);
+        // ---- commit
+        r_atoms.swap(na); r_geom.swap(ng);
+        r_atoms_h = h;
+        r_n = (int)n; r_limit = lim;
+        has_rigid = true;
+    }
+
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the
     // reaction-field constants.  Every engine keeps a plane of them in its own cell order (NbSystem::qp).
     DevBuf<double> q_tab;

@@ -191,6 +191,39 @@ def topology(types, bonds, table, length_unit=1.0, energy_unit=1.0):
                 torsions=arr(ta, 4), torsion_params=arr(tp, 3, np.float64), exclusions=arr(excl, 2), pairs14=arr(p14, 2))
 
 
+def rigid_triatomics(types, bonds, table, length_unit=1.0, with_dropped=False):
+    """The rigid three-site molecules (emdee_md_set_rigid3) among the molecules of a bond graph: those of exactly three atoms in
+    which a centre is bonded to two atoms of one type that are bonded to nothing else (water, H-O-H).  Returns (atoms, geom):
+      atoms (n, 3) int64 {centre, a, b}, centre first, a < b; geom (n, 2) float64 {d_leg, d_base} with d_leg the bond's r0 and
+        d_base = 2 r0 sin(theta0 / 2) from the angle entry, lengths / length_unit;
+    with_dropped: (atoms, geom, drop_bonds, drop_angles), the last two the (m, 2) and (m, 3) ids of the bonds and angles the
+    constraints replace, written as topology() writes them (i < j; i < k around the centre), for a caller who takes them out of
+    the harmonic tables.
+    Raises KeyError for a molecule the table has no bond or angle parameters for."""
+    n = len(types)
+    nb = [set() for _ in range(n)]
+    for i, j in np.asarray(bonds, dtype=np.int64).reshape(-1, 2):
+        nb[i].add(int(j)); nb[j].add(int(i))
+    atoms, geom, drop_b, drop_a = [], [], [], []
+    for c in range(n):
+        if len(nb[c]) != 2:
+            continue
+        a, b = sorted(nb[c])
+        if nb[a] != {c} or nb[b] != {c} or types[a] != types[b]:
+            continue
+        bond, angle = table.bond(types[c], types[a]), table.angle(types[a], types[c], types[b])
+        if bond is None or angle is None:
+            raise KeyError("no bond or angle parameters for the three-site molecule %s (types %s)"
+                           % ((c, a, b), tuple(types[t] for t in (c, a, b))))
+        r0, th = bond[0][1] / length_unit, angle[0][1]
+        atoms.append((c, a, b)); geom.append((r0, 2.0 * r0 * np.sin(0.5 * th)))
+        drop_b += [(min(c, a), max(c, a)), (min(c, b), max(c, b))]
+        drop_a.append((a, c, b))
+    arr = lambda v, m, dt=np.int64: np.array(v, dtype=dt).reshape(-1, m)
+    out = (arr(atoms, 3), arr(geom, 2, np.float64))
+    return out + (arr(drop_b, 2), arr(drop_a, 3)) if with_dropped else out
+
+
 def save_checkpoint(path, positions, velocities, step, box_length):
     """(x, v, step, L) as a compressed npz; accepts GPU tensors or numpy arrays."""
     to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)

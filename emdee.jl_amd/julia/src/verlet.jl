@@ -83,6 +83,14 @@ set_pme!(md::VelocityVerlet, alpha, grid::Union{Nothing,Vector{Int32}}=nothing, 
     check(ccall((:emdee_md_set_pme, libemdee_hip), Int32, (Ptr{Cvoid}, Float64, Ptr{Int32}, Int32), md.handle, Float64(alpha),
                 grid === nothing ? C_NULL : grid, Int32(order)))
 
+# int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double *geom_dev, int32_t n_mol);
+# Rigid three-site molecules: atoms a device Int32 matrix (3, n) of caller ids {apex, a, b} (0-based, as the library counts),
+# geom a device Float64 matrix (2, n) of {d_leg, d_base}; every later step! holds them rigid (SETTLE + RATTLE).  Moves no atom,
+# projects the velocities once; `nothing` clears the table.
+set_rigid3!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, geom::Union{Nothing,HipArray{Float64,2}}=nothing) =
+    check(ccall((:emdee_md_set_rigid3, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
+                atoms === nothing ? C_NULL : atoms.ptr, geom === nothing ? C_NULL : geom.ptr, atoms === nothing ? 0 : size(atoms, 2)))
+
 # Pressure coupling (include/emdee_hip.h; undivided boxes).
 # int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);   -> (lo, len) of the engine's box
 function box(md::VelocityVerlet)

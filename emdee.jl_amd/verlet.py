@@ -54,7 +54,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # halo (pack -> exchange -> unpack) on the stream it runs on
            "fused_step_interior": 5, "fused_step_boundary": 6, "halo": 7,
            # the reciprocal-space pass of an Ewald engine (set_ewald_, set_pme_); "lj_force_nbr" contains it as well
-           "ewald_reciprocal": 8}
+           "ewald_reciprocal": 8,
+           # the constraint stages of an engine with rigid molecules (set_rigid3_)
+           "settle": 9}
 
 
 class VelocityVerlet:
@@ -334,6 +336,17 @@ class VelocityVerlet:
                 raise ValueError("set_pme_: grid is one integer or three")
             arr = (C.c_int32 * 3)(*g)
         _lib.call("emdee_md_set_pme", self._handle, float(alpha), arr, int(order))
+
+    def set_rigid3_(self, atoms, geom):
+        """Rigid three-site molecules (include/emdee_hip.h emdee_md_set_rigid3): atoms (n, 3) caller ids {apex, a, b}, geom (n, 2)
+        {d_leg, d_base} with |apex - a| = |apex - b| = d_leg and |a - b| = d_base.  Every later step_ holds them rigid (SETTLE on
+        the positions, RATTLE on the velocities).  Moves no atom; projects the velocities once.  Empty or None clears the table."""
+        a = torch.as_tensor(atoms if atoms is not None else []).reshape(-1, 3).to(device=self.device, dtype=torch.int32).contiguous()
+        g = torch.as_tensor(geom if geom is not None else [], dtype=torch.float64).reshape(-1, 2).to(device=self.device).contiguous()
+        if a.shape[0] != g.shape[0]:
+            raise ValueError("set_rigid3_: %d molecules but %d geometry rows" % (a.shape[0], g.shape[0]))
+        _lib.call("emdee_md_set_rigid3", self._handle, C.c_void_p(a.data_ptr()) if a.numel() else None,
+                  C.c_void_p(g.data_ptr()) if g.numel() else None, int(a.shape[0]))
 
     def close(self):
         if self._handle is not None:

@@ -307,6 +307,49 @@ int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]);
  *   - The pass's device time is emdee_md_kernel_time index 8, as the direct sum's. */
 int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int32_t order);
 
+/* Rigid three-site molecules (SETTLE: Miyamoto & Kollman, J. Comput. Chem. 13, 952 (1992); build-defined like the integrator).
+ * n_mol rigid three-site molecules.  atoms_dev: 3 n_mol caller ids {apex, a, b}; geom_dev: 2 n_mol doubles {d_leg, d_base}:
+ * |apex - a| = |apex - b| = d_leg, |a - b| = d_base.  Device arrays, copied.  n_mol = 0 clears the table.
+ * While a table is in force emdee_md_step takes every step in the closed form of a coupled engine -- each step opens and closes
+ * its own half kick; no merged kicks, no run-ahead, no fused step -- with three stages around the unchanged kernels:
+ *   (a) the constrained atoms' positions x0 are remembered (they satisfy the constraints);
+ *   (b) v += (dt/2) f/m [; Langevin O step] ; x += dt v                                       (emdee_md_kick_drift's kernel)
+ *   (c) x <- the rigid triangle nearest x in the SHAKE sense with respect to x0: x + sum_k lambda_k (x0_i - x0_j) / m_i over the
+ *       three bonds, in closed form; v <- v + (x_constrained - x_unconstrained) / dt; the three atoms are tested against the
+ *       skin/2 displacement threshold again and raise the same rebuild word;
+ *   (d) the rebuild if due (rebuild_every, or the displacement word); f = F(x); v += (dt/2) f/m;
+ *   (e) the components of the relative velocities along the three bonds are removed (RATTLE for a triangle: one 3 x 3 linear
+ *       solve, no iteration).
+ * step(40), 8 x step(5) and 40 x step(1) are the same sequence of launches and agree bit for bit; a run is bitwise reproducible
+ * (one thread per molecule, no atomics on the state).  An engine without a table steps exactly as before.
+ * Stages (c) and (e) work in fp64 on unwrapped differences whatever the engine's precision: minimum images of a - apex and
+ * b - apex; a Float32 engine's cell-relative records get their cells' origins added in double before differencing; corrections
+ * are added to each record in its own frame.  Masses are the engine's (inv_mass_dev of emdee_md_set_state, or 1).
+ *   - Forces, energies, virials and tensors stay those of the force field: constraint forces are not added to any of them.  The
+ *     pressure of a constrained engine therefore LACKS THE CONSTRAINT VIRIAL, and for that reason (and because scaling atom by
+ *     atom would break the geometry) emdee_md_scale_box and emdee_md_set_barostat (other than OFF) return EMDEE_ERR_STATE on an
+ *     engine with a table, and this call returns EMDEE_ERR_STATE while a barostat is on.  The kinetic energy is that of the
+ *     constrained velocities.
+ *   - The call moves no atom.  It CHANGES VELOCITIES: stage (e) is applied once, so that the velocities it leaves are consistent
+ *     with the constraints.  The neighbour list and the forces are kept.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: a NULL array with n_mol > 0, n_mol < 0, an id outside
+ *     [0, n_owned), an atom named twice (within a molecule or across molecules), a distance that is not finite and > 0,
+ *     d_base >= 2 d_leg (no triangle).  EMDEE_ERR_STATE naming a molecule (one device check, one read-back), the previous table
+ *     in force: atoms a and b have different masses; the loaded positions miss a distance by more than 1e-3 relative (a wrong
+ *     topology, not rounding).  EMDEE_ERR_STATE also before emdee_md_set_state, with ghosts, and on an integrator lent by
+ *     emdee_dd_engine.
+ *   - The table survives an emdee_md_set_state with the same atom count: it is checked against the new state (EMDEE_ERR_STATE
+ *     from emdee_md_set_state if it does not fit) and the new velocities are projected.  After a state with another atom count,
+ *     or one that did not fit, emdee_md_step returns EMDEE_ERR_STATE until the table is set again or cleared, as with charges.
+ *   - A negative radicand in stage (c) means a molecule moved too far for a rigid solution: the molecule is left as it is and
+ *     emdee_md_step, which reads one error word per call, returns EMDEE_ERR_STATE naming it; the engine then refuses to step
+ *     until the table or the state is replaced.
+ *   - Scope: emdee_md_step of undivided engines only.  The split calls (emdee_md_kick_drift, _forces, _kick, _fused_step) never
+ *     constrain on their own; there is no emdee_dd_* counterpart.  Bonded terms that name a constrained pair stay legal: they
+ *     contribute a constant.  Scaling by molecular centres and the constraint virial are not provided.
+ *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 9. */
+int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double *geom_dev, int32_t n_mol);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -415,7 +458,7 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * profiling is on.  kernel: 0 = lj_force_nbr (plain force launches), 1 = verlet_kick_drift, 2 = rebuild
  * (bin + sort + nbr_build), 3 = verlet_kick, 4 = lj_force_nbr with the velocity-Verlet update fused in
  * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald, emdee_md_set_pme),
- * which index 0 contains as well.  Blocking. */
+ * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3).  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
