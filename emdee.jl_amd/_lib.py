@@ -89,6 +89,8 @@ SIGNATURES = {
     "emdee_md_energies": [_p, _d3],
     "emdee_md_virial_tensor": [_p, _p],
     "emdee_md_pressure_tensor": [_p, _d3],
+    "emdee_md_molecular_pressure_tensor": [_p, _d3],
+    "emdee_md_set_molecular_scaling": [_p, _i32],
     "emdee_md_nbr_stats": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)],
     "emdee_md_count_pairs": [_p, C.POINTER(_i64)],
     "emdee_md_profile": [_p, _i32],

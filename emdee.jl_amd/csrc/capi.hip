@@ -422,6 +422,12 @@ int32_t emdee_md_virial_tensor(emdee_md *md, void *tensor_dev) {
 int32_t emdee_md_pressure_tensor(emdee_md *md, double out[12]) {
     return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "out"); md->impl->pressure_tensor(out); });
 }
+int32_t emdee_md_molecular_pressure_tensor(emdee_md *md, double out[12]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "out"); md->impl->molecular_pressure_tensor(out); });
+}
+int32_t emdee_md_set_molecular_scaling(emdee_md *md, int32_t on) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_molecular_scaling(on); });
+}
 int32_t emdee_md_nbr_stats(emdee_md *md, int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->stats(builds, listed, max_count, capacity); });
 }

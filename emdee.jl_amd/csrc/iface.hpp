@@ -43,6 +43,8 @@ struct IMd {
     virtual void energies(double out[3]) = 0;
     virtual void virial_tensor(void *out) = 0;
     virtual void pressure_tensor(double out[12]) = 0;
+    virtual void molecular_pressure_tensor(double out[12]) = 0;
+    virtual void set_molecular_scaling(int32_t on) = 0;
     virtual void stats(int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) = 0;
     virtual void count_pairs(int64_t *pairs) = 0;
     virtual void export_list(int32_t *counts, int32_t *neighbors, int32_t capacity) = 0;

@@ -251,8 +251,8 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!sys.has_rigid() || !(sys.rigid_stale() || rigid_unchecked), EMDEE_ERR_STATE, "md_step: rigid molecules set for %lld atoms, "
                       "the state holds %d (or does not fit them): set them again or clear them (emdee_md_set_rigid3)", (long long)sys.tables->r_limit, sys.n_owned);
         if (nsteps == 0) return;
+        if (sys.has_rigid()) { step_rigid(nsteps, dt, rebuild_every); return; }   // (coupled or not)
         if (baro.kind != EMDEE_BAROSTAT_OFF) { step_coupled(nsteps, dt, rebuild_every); return; }
-        if (sys.has_rigid()) { step_rigid(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
@@ -307,13 +307,28 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s: this integrator is a domain's, lent by emdee_dd_engine (the geometry of a decomposition is fixed at create)", what);
         EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "%s: an integrator with ghosts (its box is a domain of a larger one)", what);
     }
+    // emdee_md_set_molecular_scaling: an engine with a rigid table scales by molecular centres and couples to the molecular pressure
+    bool molecular = false;
+    void set_molecular_scaling(int32_t on) override {
+        EMDEE_REQUIRE(on == 0 || on == 1, EMDEE_ERR_INVALID, "set_molecular_scaling: on = %d is neither 0 nor 1", on);
+        require_undivided("set_molecular_scaling");
+        EMDEE_REQUIRE(on == 1 || !(baro.kind != EMDEE_BAROSTAT_OFF && sys.has_rigid()), EMDEE_ERR_STATE, "set_molecular_scaling: pressure coupling is on "
+                      "and the engine holds rigid molecules: switch the coupling off (emdee_md_set_barostat) or clear the table (emdee_md_set_rigid3) first");
+        molecular = on == 1;
+    }
+    // the conditions emdee_md_step refuses a table on
+    void require_fitting_table(const char *what) const {
+        EMDEE_REQUIRE(!sys.has_rigid() || !(sys.rigid_stale() || rigid_unchecked), EMDEE_ERR_STATE, "%s: rigid molecules set for %lld atoms, the state "
+                      "holds %d (or does not fit them): set them again or clear them (emdee_md_set_rigid3)", what, (long long)sys.tables->r_limit, sys.n_owned);
+    }
     void scale_box(const double mu[3], double vscale) override {
         use_device(sys.ctx);
         require_undivided("scale_box");
-        EMDEE_REQUIRE(!sys.has_rigid(), EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
-                      "would break their geometry, and its pressure lacks the constraint virial");
+        EMDEE_REQUIRE(!sys.has_rigid() || molecular, EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
+                      "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
-        sys.scale_box(mu, vscale);                           // (validates before it writes)
+        require_fitting_table("scale_box");
+        sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes)
         since_build = 0;
         current_mask = 0;
         if (!sys.charges_stale()) {
@@ -327,8 +342,9 @@ struct MdImpl : IMd {
                       double temperature, uint64_t seed, uint64_t first_step) override {
         use_device(sys.ctx);
         require_undivided("set_barostat");
-        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_rigid(), EMDEE_ERR_STATE, "set_barostat: the engine holds rigid molecules "
-                      "(emdee_md_set_rigid3): its pressure lacks the constraint virial, and scaling atom by atom would break their geometry");
+        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_rigid() || molecular, EMDEE_ERR_STATE, "set_barostat: the engine holds rigid molecules "
+                      "(emdee_md_set_rigid3): its pressure lacks the constraint virial, and scaling atom by atom would break their geometry "
+                      "(emdee_md_set_molecular_scaling couples to the molecular pressure)");
         if (kind == EMDEE_BAROSTAT_OFF) { baro.kind = EMDEE_BAROSTAT_OFF; return; }
         EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_BERENDSEN || kind == EMDEE_BAROSTAT_CRESCALE, EMDEE_ERR_INVALID, "set_barostat: unknown kind %d", kind);
         EMDEE_REQUIRE(coupling >= EMDEE_COUPLE_ISOTROPIC && coupling <= EMDEE_COUPLE_ANISOTROPIC, EMDEE_ERR_INVALID, "set_barostat: unknown coupling %d", coupling);
@@ -381,9 +397,16 @@ struct MdImpl : IMd {
     // unchanged kernels: (a) the constrained atoms' positions are remembered, (c) SETTLE on the drifted records, (e) the bond
     // components of the relative velocities are removed.  Stage (c) re-tests its atoms against the rebuild threshold, so the
     // displacement word is read after it; a re-sort between (c) and (e) is harmless (the stages find atoms through inv_perm).
+    // The order of a step: (a) gather, (b) kick + drift, (c) SETTLE, [re-sort], (d) force pass and kick, (e) RATTLE; with pressure
+    // coupling on (emdee_md_set_molecular_scaling), after stage (e) of the step that completes an interval, (f) the event: the
+    // molecular pressure from that step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale,
+    // which rebuilds the list and evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.
     void step_rigid(int nsteps, double dt, int rebuild_every) {
+        const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF;
+        EMDEE_REQUIRE(!coupled || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
+            const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
             sys.settle_gather();
             sys.kick_drift(0.5 * dt, dt);
             sys.settle_positions(dt);
@@ -394,6 +417,8 @@ struct MdImpl : IMd {
             sys.kick(0.5 * dt);
             sys.settle_velocities();
             current_mask = EMDEE_FORCES;
+            if (coupled) baro.step++;
+            if (event) couple(dt);
         }
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
@@ -410,7 +435,14 @@ struct MdImpl : IMd {
             EMDEE_HIP_CHECK(hipMemcpyAsync(xi, baro_xi.ptr, 3 * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
         }
         double P[3];
-        if (baro.coupling == EMDEE_COUPLE_ISOTROPIC) {
+        if (sys.has_rigid()) {                               // the molecular pressure, always through the tensor path
+            tensor_pass();
+            double t[TENSOR_SUMS];
+            sys.molecular_tensor_sums(t);
+            for (int d = 0; d < 3; d++) P[d] = (t[6 + d] + t[d]) / V;
+            if (baro.coupling == EMDEE_COUPLE_ISOTROPIC) P[0] = P[1] = P[2] = (P[0] + P[1] + P[2]) / 3.0;
+            if (baro.coupling == EMDEE_COUPLE_SEMIISOTROPIC) P[0] = P[1] = 0.5 * (P[0] + P[1]);
+        } else if (baro.coupling == EMDEE_COUPLE_ISOTROPIC) {
             double e[3];
             sys.energy_sums(0.0, e);
             P[0] = P[1] = P[2] = (2.0 * e[1] + e[2]) / (3.0 * V);
@@ -532,6 +564,18 @@ struct MdImpl : IMd {
         if (!lent) sys.check_bonded();
         sys.tensor_sums(out);
     }
+    // emdee_md_molecular_pressure_tensor: without a table, pressure_tensor's kernels and nothing added
+    void molecular_pressure_tensor(double out[12]) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
+        if (!sys.has_rigid()) { pressure_tensor(out); return; }
+        EMDEE_REQUIRE(!lent && n_ghost == 0, EMDEE_ERR_STATE, "molecular_pressure_tensor: rigid molecules on an integrator with ghosts or a domain's");
+        require_fitting_table("molecular_pressure_tensor");
+        if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
+        tensor_pass();
+        sys.check_bonded();
+        sys.molecular_tensor_sums(out);
+    }
     void stats(int64_t *builds, int64_t *listed, int32_t *max_count, int32_t *capacity) override {
         use_device(sys.ctx);
         sys.list_stats(false, listed, max_count, nullptr);
@@ -556,11 +600,11 @@ struct MdImpl : IMd {
         // ids 0..3: the TimerIds; 4: every fused step launch (interior + boundary halves of a decomposed step together, as
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
-        // 9: the constraint stages of an engine with rigid molecules
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 9, EMDEE_ERR_INVALID, "kernel id out of range");
+        // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 10, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[10][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
-                                {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}};
+        const int ids[11][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+                                {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -618,8 +662,9 @@ struct MdImpl : IMd {
     // replaces the one in force; no atom moves, the velocities are projected once (stage (e)).  The neighbour list and the forces
     // do not depend on the table: nothing is rebuilt.
     void set_rigid3(const int32_t *atoms, const double *geom, int32_t n_mol) override {
-        EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF, EMDEE_ERR_STATE, "set_rigid3: pressure coupling is on (emdee_md_set_barostat): the pressure "
-                      "of an engine with rigid molecules lacks the constraint virial; switch the coupling off first");
+        EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF || molecular, EMDEE_ERR_STATE, "set_rigid3: pressure coupling is on (emdee_md_set_barostat): the pressure "
+                      "of an engine with rigid molecules lacks the constraint virial; switch the coupling off first (or couple to the molecular "
+                      "pressure: emdee_md_set_molecular_scaling)");
         install("rigid molecules", "a decomposed run has none", [&] {
             sys.own_tables.set_rigid3(atoms, geom, n_mol, sys.n_owned, sys.stream(),
                                       [&](const int *a, const double *g, const std::vector<int32_t> &h, int n) { sys.settle_check_state(a, g, h, n); });

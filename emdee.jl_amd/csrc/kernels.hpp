@@ -1041,14 +1041,18 @@ __global__ void k_kick(int n, int n_owned, size_t pitch, const int *__restrict__
 // reads them with (NbSystem::resort: rel_in); the offset leaves [0, cell width) by (mu - 1) x, as after a long drift, and the
 // re-sort brings it back.  Scaling the offset itself would move every atom towards its own cell's corner.
 // Wrapped records stay consistent with the image counts: lo + mu (x + k len - lo) = [lo + mu (x - lo)] + k (mu len).
+// member (with perm): one byte per caller id, non-zero for the atoms of rigid molecules, which the molecular scale moves by their
+// centres of mass (settle.hpp k_molecule_scale) and this kernel leaves alone; NULL: every slot is scaled.
 struct ScaleBox {
     double lo[3], mu[3];
 };
 template <typename real>
 __global__ void k_cell_state_scale(int n, size_t pitch, Rec<real> *__restrict__ rec, real *__restrict__ vel, ScaleBox s,
-                                   real vscale, int scale_vel, RelGrid rel) {
+                                   real vscale, int scale_vel, RelGrid rel, const unsigned char *__restrict__ member = nullptr,
+                                   const int *__restrict__ perm = nullptr) {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
+    if (member != nullptr && member[perm[p]]) return;
     Rec<real> r = rec[p];
     double ox = 0.0, oy = 0.0, oz = 0.0;
     if (sizeof(real) == 4 && rel.on) rel.origin(rel.cell[p], ox, oy, oz);

@@ -36,7 +36,9 @@ static inline void refuse_experiment_switches() {
 // reports the two together, 5 and 6 one each); T_HALO: pack -> exchange -> unpack of a decomposed step, on the stream they run on
 // T_EWALD: the reciprocal-space pass of an Ewald engine (ewald.hpp), which runs inside T_FORCE's launches as well
 // T_SETTLE: the three constraint stages of an engine with rigid molecules (settle.hpp)
-enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8, T_COUNT = 9 };
+// T_MOLECULAR: the molecular sums and the molecular scale of an engine with rigid molecules (settle.hpp)
+enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
+               T_MOLECULAR = 9, T_COUNT = 10 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -432,14 +434,25 @@ struct NbSystem {
     // ... then: the sorted state rescaled in place (k_cell_state_scale), the box mu_d len_d, and the re-sort -- new cells, a new
     // plan when the box changed (set_box), the list, the 1-4 and bonded slots, the charge plane at the next force pass.
     // No read-back of its own: mu and vscale are the caller's host values.
-    void scale_box(const double mu[3], double vscale) {
+    // molecular (emdee_md_set_molecular_scaling, an engine with a rigid table): the atoms of the table move with their molecules'
+    // centres of mass (k_molecule_scale) and k_cell_state_scale passes them over; every other atom scales as before.  Neither
+    // kernel reads what the other writes.
+    void scale_box(const double mu[3], double vscale, bool molecular = false) {
         EMDEE_REQUIRE(sorted && with_vel && !has_ghosts, EMDEE_ERR_STATE, "scale_box: needs a loaded state without ghosts");
         check_scaled_box(mu, vscale);
         if (n_total > 0) {
             ScaleBox s{};
             for (int d = 0; d < 3; d++) { s.lo[d] = lo[d]; s.mu[d] = mu[d]; }
+            const int scale_vel = vscale != 1.0 ? 1 : 0;
+            if (molecular && tables->r_n > 0) {
+                Timed t(this, T_MOLECULAR);
+                hipLaunchKernelGGL((k_molecule_scale<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args(), s,
+                                   vscale, scale_vel);
+            }
             hipLaunchKernelGGL((k_cell_state_scale<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, pitch, rec.ptr,
-                               vel.ptr, s, (real)vscale, vscale != 1.0 ? 1 : 0, rel_grid(rel_now, cell_sorted.ptr));
+                               vel.ptr, s, (real)vscale, scale_vel, rel_grid(rel_now, cell_sorted.ptr),
+                               molecular ? (const unsigned char *)tables->r_member.ptr : (const unsigned char *)nullptr,
+                               molecular ? (const int *)perm.ptr : (const int *)nullptr);
         }
         const double nl[3] = {mu[0] * len[0], mu[1] * len[1], mu[2] * len[2]};
         set_box(lo, nl, per);                                // (a changed box invalidates the sort, the list and the plan ...)
@@ -1623,13 +1636,40 @@ struct NbSystem {
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
         if (n_total == 0) return;
         int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-        tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + TENSOR_SUMS);
+        tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);
         double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
         hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
                            vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
         hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot);
         EMDEE_HIP_CHECK(hipMemcpyAsync(out, tot, TENSOR_SUMS * sizeof(double), hipMemcpyDeviceToHost, stream()));
         EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+    }
+    // out[0..5] = W_mol, out[6..11] = K_mol (include/emdee_hip.h: emdee_md_molecular_pressure_tensor): the atomic sums above minus
+    // what the atoms of the rigid molecules carry about their centres of mass (k_molecule_partials over the table, with the
+    // current force planes).  The partial sums of the two passes share their buffer (the stream orders them), the two totals lie
+    // side by side and come back in one copy; the subtraction is the host's.  Blocking.
+    void molecular_tensor_sums(double out[TENSOR_SUMS]) {
+        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
+        if (n_total == 0) return;
+        const int n_mol = has_rigid() ? tables->r_n : 0;
+        if (n_mol == 0) { tensor_sums(out); return; }
+        int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+        tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);
+        double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
+        hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                           vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
+        hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot);
+        {
+            Timed t(this, T_MOLECULAR);
+            nb = std::min((int)blocks_for(n_mol, RED_BLOCK), RED_MAX_BLOCKS);
+            hipLaunchKernelGGL((k_molecule_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), settle_args(), (const real *)frc.ptr,
+                               tpartial.ptr);
+        }
+        hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot + TENSOR_SUMS);
+        double both[2 * TENSOR_SUMS];
+        EMDEE_HIP_CHECK(hipMemcpyAsync(both, tot, 2 * TENSOR_SUMS * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = both[q] - both[TENSOR_SUMS + q];
     }
     // caller-order copy of the last tensor pass's per-atom tensors (owned atoms, 6 x n_owned)
     void unsort_tensor(real *out) {

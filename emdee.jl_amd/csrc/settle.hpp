@@ -123,6 +123,49 @@ EMDEE_HD void settle_velocities(const double (&x)[3][3], double (&v)[3][3], doub
     }
 }
 
+// ---- molecular pressure and centre-of-mass scaling (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling) ------
+// y: the three sites, unwrapped and in one frame, whichever; v: their velocities; f: the force-field forces on them (no constraint
+// forces).  out[0..5] = sum_k 1/2 (d_k^a f_k^b + d_k^b f_k^a) with d_k = y_k - Y, out[6..11] = sum_k m_k v_k^a v_k^b - M V^a V^b,
+// both in the order (xx, yy, zz, xy, xz, yz): what the molecule's atoms add to the atomic sums W and K beyond what its centre of
+// mass carries.  Y and V are formed from differences to the apex (as settle_positions forms its centre of mass), and the kinetic
+// term as sum_k m_k u_k^a u_k^b with u_k = v_k - V, which is the same number without the cancellation.
+EMDEE_HD void molecule_sums(const double (&y)[3][3], const double (&v)[3][3], const double (&f)[3][3], double m_apex, double m_leg,
+                            double (&out)[12]) {
+    const double mt = m_apex + 2.0 * m_leg, m[3] = {m_apex, m_leg, m_leg};
+    double d[3][3], u[3][3];
+    for (int c = 0; c < 3; c++) {
+        const double yb = y[1][c] - y[0][c], yc = y[2][c] - y[0][c], vb = v[1][c] - v[0][c], vc = v[2][c] - v[0][c];
+        const double com = m_leg * (yb + yc) / mt, vcm = m_leg * (vb + vc) / mt;
+        d[0][c] = -com; d[1][c] = yb - com; d[2][c] = yc - com;
+        u[0][c] = -vcm; u[1][c] = vb - vcm; u[2][c] = vc - vcm;
+    }
+    const int ca[6] = {0, 1, 2, 0, 0, 1}, cb[6] = {0, 1, 2, 1, 2, 2};
+    for (int q = 0; q < 6; q++) {
+        const int a = ca[q], b = cb[q];
+        double w = 0.0, k = 0.0;
+        for (int s = 0; s < 3; s++) {
+            w += 0.5 * (d[s][a] * f[s][b] + d[s][b] * f[s][a]);
+            k += m[s] * u[s][a] * u[s][b];
+        }
+        out[q] = w; out[6 + q] = k;
+    }
+}
+
+// The molecular scale of one molecule: y as above but in the frame of the box (lo is subtracted from its centre of mass), shift =
+// (mu - 1) (Y - lo), what every site of the molecule moves by (a site whose record is another periodic image of y_k adds (mu - 1)
+// times that whole number of box lengths itself), dv = (velocity_scale - 1) V, what every site's velocity gains: the centre of
+// mass scales, its momentum scales, geometry and rotation are untouched.
+EMDEE_HD void molecule_scale(const double (&y)[3][3], const double (&v)[3][3], double m_apex, double m_leg, const double (&mu)[3],
+                             const double (&lo)[3], double velocity_scale, double (&shift)[3], double (&dv)[3]) {
+    const double mt = m_apex + 2.0 * m_leg;
+    for (int c = 0; c < 3; c++) {
+        const double Y = y[0][c] + m_leg * ((y[1][c] - y[0][c]) + (y[2][c] - y[0][c])) / mt;
+        const double V = v[0][c] + m_leg * ((v[1][c] - v[0][c]) + (v[2][c] - v[0][c])) / mt;
+        shift[c] = (mu[c] - 1.0) * (Y - lo[c]);
+        dv[c] = (velocity_scale - 1.0) * V;
+    }
+}
+
 }  // namespace emdee
 
 #if defined(__HIPCC__)
@@ -293,6 +336,79 @@ __global__ __launch_bounds__(256) void k_settle_check(SettleArgs<real> a, int *_
     const double l3 = sqrt(bx * bx + by * by + bz * bz);
     if (!(fabs(l1 - d_leg) <= 1e-3 * d_leg) || !(fabs(l2 - d_leg) <= 1e-3 * d_leg) || !(fabs(l3 - d_base) <= 1e-3 * d_base))
         atomicMax(words + 1, m + 1);
+}
+
+// ---- molecular pressure and centre-of-mass scaling: the two kernels (timed under emdee_md_kernel_time index 10) ----------------
+// The sites of molecule m as the molecular definitions take them: s = the records in double (site()), y = the apex record and the
+// minimum images of the legs from it, v the velocities; p the slots.
+template <typename real>
+__device__ __forceinline__ void molecule_load(const SettleArgs<real> &a, int m, int (&p)[3], double (&s)[3][3], double (&y)[3][3],
+                                              double (&v)[3][3], double &m_apex, double &m_leg) {
+    double x[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        p[k] = a.inv_perm[a.atoms[3 * (size_t)m + k]];
+        settle_detail::site(a, p[k], s[k]);
+#pragma unroll
+        for (int d = 0; d < 3; d++) v[k][d] = (double)a.vel[d * a.pitch + p[k]];
+    }
+    settle_detail::unwrap(a.box, s, x);
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int d = 0; d < 3; d++) y[k][d] = s[0][d] + x[k][d];
+    settle_detail::masses(a, p[0], p[1], m_apex, m_leg);
+}
+
+// partial[b][0..11] = the sum of molecule_sums over the molecules of block b's stride, k_tensor_partials' shape: fp64, fixed order,
+// no atomics (k_final_sums completes them).  frc: the engine's force planes (the force-field forces of the last force pass).
+template <typename real>
+__global__ __launch_bounds__(RED_BLOCK) void k_molecule_partials(SettleArgs<real> a, const real *__restrict__ frc, double *__restrict__ partial) {
+    __shared__ double sh[RED_BLOCK / WAVE];
+    double sum[TENSOR_SUMS];
+    for (int q = 0; q < TENSOR_SUMS; q++) sum[q] = 0.0;
+    for (int m = blockIdx.x * RED_BLOCK + threadIdx.x; m < a.n_mol; m += gridDim.x * RED_BLOCK) {
+        int p[3];
+        double s[3][3], y[3][3], v[3][3], f[3][3], m_apex, m_leg, t[TENSOR_SUMS];
+        molecule_load(a, m, p, s, y, v, m_apex, m_leg);
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int d = 0; d < 3; d++) f[k][d] = (double)frc[d * a.pitch + p[k]];
+        molecule_sums(y, v, f, m_apex, m_leg, t);
+        for (int q = 0; q < TENSOR_SUMS; q++) sum[q] += t[q];
+    }
+    for (int q = 0; q < TENSOR_SUMS; q++) {
+        const double t = block_sum(sum[q], sh);
+        if (threadIdx.x == 0) partial[TENSOR_SUMS * blockIdx.x + q] = t;
+    }
+}
+
+// The molecular scale, one thread per molecule: every site's record moves by (mu - 1) (C_k - lo), C_k = Y + (r_k - y_k) the image
+// of the centre of mass that goes with the record (r_k - y_k: whole box lengths, so the stored image counts stay valid); the
+// shift is added to the record in its own frame in double and rounded once, as k_settle_positions adds its corrections.
+// scale_vel: v_k += (velocity_scale - 1) V; 0 leaves the velocity planes untouched, bit for bit.  k_cell_state_scale, given the
+// membership bytes, leaves these atoms alone.
+template <typename real>
+__global__ __launch_bounds__(256) void k_molecule_scale(SettleArgs<real> a, ScaleBox sb, double velocity_scale, int scale_vel) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n_mol) return;
+    int p[3];
+    double s[3][3], y[3][3], v[3][3], m_apex, m_leg, shift[3], dv[3];
+    molecule_load(a, m, p, s, y, v, m_apex, m_leg);
+    molecule_scale(y, v, m_apex, m_leg, sb.mu, sb.lo, velocity_scale, shift, dv);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        Rec<real> r = a.rec[p[k]];
+        r.x = (real)((double)r.x + (shift[0] + (sb.mu[0] - 1.0) * (s[k][0] - y[k][0])));
+        r.y = (real)((double)r.y + (shift[1] + (sb.mu[1] - 1.0) * (s[k][1] - y[k][1])));
+        r.z = (real)((double)r.z + (shift[2] + (sb.mu[2] - 1.0) * (s[k][2] - y[k][2])));
+        a.rec[p[k]] = r;
+        if (scale_vel) {
+#pragma unroll
+            for (int d = 0; d < 3; d++) a.vel[d * a.pitch + p[k]] = (real)(v[k][d] + dv[d]);
+        }
+    }
 }
 
 }  // namespace emdee

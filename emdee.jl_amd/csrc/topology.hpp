@@ -227,6 +227,14 @@ std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector
                       (long long)named[k].first, (long long)named[k - 1].second, (long long)named[k].second);
     return std::vector<int32_t>(raw.begin(), raw.end());
 }
+// one byte per id in [0, lim): 1 for the atoms a (checked) table names, 0 for the others -- the one-atom molecules of the
+// molecular scale (emdee_md_set_molecular_scaling), which the atom-by-atom scale kernel still moves
+inline std::vector<uint8_t> rigid3_members(const std::vector<int32_t> &atoms, int64_t lim) {
+    std::vector<uint8_t> member((size_t)std::max<int64_t>(lim, 0), 0);
+    for (int32_t g : atoms)
+        if (g >= 0 && g < lim) member[(size_t)g] = 1;
+    return member;
+}
 // the error texts of the device checks (molecule: the number the kernels report, from 0)
 inline std::string rigid3_message(const std::vector<int32_t> &atoms, int64_t molecule, const char *what) {
     char text[512];

@@ -116,6 +116,7 @@ struct Topology {
     // undivided engines only
     DevBuf<int> r_atoms;
     DevBuf<double> r_geom;
+    DevBuf<unsigned char> r_member;                          // one byte per id below r_limit: named by the table (topo::rigid3_members)
     std::vector<int32_t> r_atoms_h;                          // the ids as given (the error texts name them)
     int r_n = 0;                                             // molecules
     int64_t r_limit = 0;                                     // the atom count the ids were checked against
@@ -135,11 +136,13 @@ struct Topology {
         const std::vector<int32_t> h = topo::checked_rigid3(raw, geom, lim);
         DevBuf<int> na;
         DevBuf<double> ng;
-        put(na, h, s); put(ng, geom, s);
+        DevBuf<unsigned char> nm;
+        const std::vector<uint8_t> member = topo::rigid3_members(h, lim);
+        put(na, h, s); put(ng, geom, s); put(nm, member, s);
         EMDEE_HIP_CHECK(hipStreamSynchronize(s));
         check(na.ptr, ng.ptr, h, (int)n);
         // ---- commit
-        r_atoms.swap(na); r_geom.swap(ng);
+        r_atoms.swap(na); r_geom.swap(ng); r_member.swap(nm);
         r_atoms_h = h;
         r_n = (int)n; r_limit = lim;
         has_rigid = true;

@@ -150,6 +150,22 @@ function pressure_tensor(md::VelocityVerlet, volume)
     return (virial=W, kinetic=K, pressure=(K + W) / volume)
 end
 
+# int32_t emdee_md_molecular_pressure_tensor(emdee_md *md, double out[12]);   -> pressure_tensor from the molecular sums W_mol, K_mol:
+# the atomic sums minus what the atoms of the rigid molecules (set_rigid3!) carry about their centres of mass; without a table,
+# pressure_tensor itself
+function molecular_pressure_tensor(md::VelocityVerlet, volume)
+    out = zeros(Float64, 12)
+    check(ccall((:emdee_md_molecular_pressure_tensor, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, out))
+    W, K = tensor3(out[1:6]), tensor3(out[7:12])
+    return (virial=W, kinetic=K, pressure=(K + W) / volume)
+end
+
+# int32_t emdee_md_set_molecular_scaling(emdee_md *md, int32_t on);
+# on: an engine with rigid molecules accepts scale_box! and set_barostat! -- molecules are translated with their centres of mass,
+# and the coupling takes the molecular pressure; changes nothing for an engine without a table.
+set_molecular_scaling!(md::VelocityVerlet, on::Bool=true) =
+    check(ccall((:emdee_md_set_molecular_scaling, libemdee_hip), Int32, (Ptr{Cvoid}, Int32), md.handle, Int32(on)))
+
 # int32_t emdee_md_get_state(emdee_md*, void *positions, void *velocities, void *forces, void *energies, void *virials);
 function state!(md::VelocityVerlet{T}, positions::HipArray{T,2}, velocities::HipArray{T,2}, forces::HipArray{T,2}) where {T}
     check(ccall((:emdee_md_get_state, libemdee_hip), Int32,

@@ -56,7 +56,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the reciprocal-space pass of an Ewald engine (set_ewald_, set_pme_); "lj_force_nbr" contains it as well
            "ewald_reciprocal": 8,
            # the constraint stages of an engine with rigid molecules (set_rigid3_)
-           "settle": 9}
+           "settle": 9,
+           # the molecular sums and the molecular scale of an engine with rigid molecules (set_molecular_scaling_)
+           "molecular": 10}
 
 
 class VelocityVerlet:
@@ -202,6 +204,19 @@ class VelocityVerlet:
         v = self.lengths[0] * self.lengths[1] * self.lengths[2] if volume is None else volume
         return pressure_tensor_dict(self.tensor_sums(), v)
 
+    def molecular_tensor_sums(self):
+        """The twelve fp64 sums of emdee_md_molecular_pressure_tensor: W_mol (6), K_mol (6) -- tensor_sums() minus what the atoms
+        of the rigid molecules (set_rigid3_) carry about their centres of mass; without a table, tensor_sums() itself (blocking)."""
+        out = (C.c_double * 12)()
+        _lib.call("emdee_md_molecular_pressure_tensor", self._handle, out)
+        return list(out)
+
+    def molecular_pressure_tensor(self, volume=None):
+        """pressure_tensor() from the molecular sums: dict(virial=W_mol, kinetic=K_mol, pressure=(K_mol + W_mol) / V), the
+        pressure an engine with rigid molecules couples to under set_molecular_scaling_."""
+        v = self.lengths[0] * self.lengths[1] * self.lengths[2] if volume is None else volume
+        return pressure_tensor_dict(self.molecular_tensor_sums(), v)
+
     def nbr_stats(self):
         b, l, m, c = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
         _lib.call("emdee_md_nbr_stats", self._handle, C.byref(b), C.byref(l), C.byref(m), C.byref(c))
@@ -285,6 +300,12 @@ class VelocityVerlet:
                   (C.c_double * 3)(*_three(compressibility)), float(tau_p), int(every),
                   0.0 if temperature is None else float(temperature), int(seed) & (2 ** 64 - 1), int(first_step))
         self._coupled = k != BAROSTAT_OFF
+
+    def set_molecular_scaling_(self, on=True):
+        """Molecular scaling (include/emdee_hip.h emdee_md_set_molecular_scaling): with it on, an engine with rigid molecules
+        (set_rigid3_) accepts scale_box_ and set_barostat_ -- molecules are translated with their centres of mass, and the
+        coupling takes the molecular pressure.  Changes nothing for an engine without a table."""
+        _lib.call("emdee_md_set_molecular_scaling", self._handle, int(on))
 
     # -- exclusions and 1-4 pairs (include/emdee_hip.h; set after the state is loaded, undivided boxes)
     def set_exclusions_(self, pairs):

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """A small box of rigid three-site water on one MI355X: SPC/E geometry and charges, reaction-field electrostatics, the Langevin
 thermostat at 300 K and a time step of 2 fs, which the rigid molecules (emdee_md_set_rigid3: SETTLE + RATTLE) make possible.
-Prints the largest bond-length deviation and the temperature as it runs.
+Prints the largest bond-length deviation and the temperature as it runs.  An NPT leg follows: stochastic cell rescaling
+(C-rescale) at 1 bar with the Langevin thermostat, coupled to the molecular pressure and scaling the box by molecular centres of
+mass (emdee_md_set_molecular_scaling), which keeps the molecules rigid; it prints the box side and P_mol as well.
 
-    python examples/rigid_water.py [cells] [steps]     # cells^3 molecules (default 12: 1728), steps (default 2000)
+    python examples/rigid_water.py [cells] [steps] [npt_steps]   # cells^3 molecules (default 12: 1728), steps (default 2000),
+                                                                 # npt_steps (default 1000; 0 leaves the NPT leg out)
 
 Units: nm, ps, atomic mass units, kJ/mol, elementary charges.  Needs the built library
 (python -c "import __graft_entry__ as g; g.build()") and a gfx950 device."""
@@ -20,6 +23,7 @@ E = load_package()
 dev = torch.device("cuda", 0)
 cells = int(sys.argv[1]) if len(sys.argv) > 1 else 12
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
+npt_steps = int(sys.argv[3]) if len(sys.argv) > 3 else 1000
 
 # SPC/E: r(OH) = 0.1 nm, tetrahedral angle, q = -0.8476 / +0.4238, LJ on the oxygen only
 R_OH, THETA = 0.1, np.deg2rad(109.47)
@@ -28,6 +32,8 @@ SIGMA_O, EPS_O = 0.316557, 0.650194
 MASS = np.array([15.9994, 1.008, 1.008])
 KB = 0.0083144626                                                # kJ/mol/K
 T, DT, RC = 300.0, 0.002, 0.9
+BAR = 0.0602214076                                               # 1 bar in kJ/mol/nm^3
+P_REF, BETA, TAU_P, EVERY = 1.0 * BAR, 4.5e-5 / BAR, 1.0, 10     # water's compressibility 4.5e-5 / bar; tau_p in ps
 
 rng = np.random.default_rng(2026)
 n_mol = cells ** 3
@@ -60,17 +66,23 @@ md.set_rigid3_(mol, np.tile([R_OH, D_HH], (n_mol, 1)))
 md.set_langevin_(gamma=5.0, temperature=KB * T, seed=2026)       # 1/ps; the lattice start relaxes under it
 
 
-def report(step):
+def report(step, npt=False):
     x = md.state(velocities=False, forces=False)["positions"].cpu().numpy()
+    side = np.array(md.box()[1])
     dev_max = 0.0
     for i, j, want in ((0, 1, R_OH), (0, 2, R_OH), (1, 2, D_HH)):
         r = x[mol[:, i]] - x[mol[:, j]]
-        r -= L * np.rint(r / L)
+        r -= side * np.rint(r / side)
         dev_max = max(dev_max, np.abs(np.linalg.norm(r, axis=1) / want - 1.0).max())
     ep, ek, _ = md.totals()
     # 6 degrees of freedom per rigid molecule
-    print("step %6d  t = %7.3f ps  T = %6.1f K  E_pot = %10.1f kJ/mol  largest bond-length deviation %.2e"
-          % (step, step * DT, 2.0 * ek / (6 * n_mol * KB), ep, dev_max))
+    line = ("step %6d  t = %7.3f ps  T = %6.1f K  E_pot = %10.1f kJ/mol  largest bond-length deviation %.2e"
+            % (step, step * DT, 2.0 * ek / (6 * n_mol * KB), ep, dev_max))
+    if npt:
+        p_mol = np.trace(md.molecular_pressure_tensor()["pressure"]) / 3.0
+        line += "  box %.4f nm  P_mol = %8.1f bar  density %.1f / nm^3" % (side[0], p_mol / BAR, n_mol / np.prod(side))
+    print(line)
+    return dev_max
 
 
 print("%d rigid SPC/E molecules, box %.3f nm, dt = %g fs, reaction field (eps_rf = 78), Langevin at %g K" % (n_mol, L, 1e3 * DT, T))
@@ -81,4 +93,16 @@ while done < steps:
     md.step_(n, DT)
     done += n
     report(done)
+
+if npt_steps > 0:
+    md.set_molecular_scaling_()                                  # lets the engine with the rigid table take a barostat
+    md.set_barostat_("c-rescale", P_REF, BETA, TAU_P, EVERY, temperature=KB * T, seed=2027)
+    print("NPT: C-rescale at %g bar every %d steps (tau_p = %g ps), coupled to the molecular pressure" % (P_REF / BAR, EVERY, TAU_P))
+    worst, done = report(steps, npt=True), 0
+    while done < npt_steps:
+        n = min(200, npt_steps - done)
+        md.step_(n, DT)
+        done += n
+        worst = max(worst, report(steps + done, npt=True))
+    assert worst < 1e-10, "the molecules lost their geometry under the molecular scale"
 md.close()

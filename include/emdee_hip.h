@@ -328,8 +328,9 @@ int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int3
  *   - Forces, energies, virials and tensors stay those of the force field: constraint forces are not added to any of them.  The
  *     pressure of a constrained engine therefore LACKS THE CONSTRAINT VIRIAL, and for that reason (and because scaling atom by
  *     atom would break the geometry) emdee_md_scale_box and emdee_md_set_barostat (other than OFF) return EMDEE_ERR_STATE on an
- *     engine with a table, and this call returns EMDEE_ERR_STATE while a barostat is on.  The kinetic energy is that of the
- *     constrained velocities.
+ *     engine with a table, and this call returns EMDEE_ERR_STATE while a barostat is on -- unless emdee_md_set_molecular_scaling
+ *     (below) is on, which measures the pressure and scales by molecular centres of mass, where constraint forces drop out.
+ *     The kinetic energy is that of the constrained velocities.
  *   - The call moves no atom.  It CHANGES VELOCITIES: stage (e) is applied once, so that the velocities it leaves are consistent
  *     with the constraints.  The neighbour list and the forces are kept.
  *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: a NULL array with n_mol > 0, n_mol < 0, an id outside
@@ -346,7 +347,11 @@ int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int3
  *     until the table or the state is replaced.
  *   - Scope: emdee_md_step of undivided engines only.  The split calls (emdee_md_kick_drift, _forces, _kick, _fused_step) never
  *     constrain on their own; there is no emdee_dd_* counterpart.  Bonded terms that name a constrained pair stay legal: they
- *     contribute a constant.  Scaling by molecular centres and the constraint virial are not provided.
+ *     contribute a constant.  The constraint virial is not provided; scaling by molecular centres is
+ *     emdee_md_set_molecular_scaling.
+ *   - With pressure coupling on (emdee_md_set_molecular_scaling), the step that completes an interval is followed, after its
+ *     stage (e), by (f) the coupling event: the molecular pressure of that step's forces F(x) and stage-(e) velocities, then
+ *     the molecular scale (a rebuild and a force pass on the new box; a fixed rebuild_every cadence restarts from it).
  *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 9. */
 int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double *geom_dev, int32_t n_mol);
 
@@ -451,6 +456,57 @@ int32_t emdee_md_virial_tensor(emdee_md *md, void *tensor_dev);
  * (the velocities emdee_md_energies takes: tr K = 2 x its kinetic energy), both (xx, yy, zz, xy, xz, yz).  The pressure
  * tensor is (K + W) / V.  Evaluates the tensors if needed.  Blocking. */
 int32_t emdee_md_pressure_tensor(emdee_md *md, double out[12]);
+/* Molecular pressure and centre-of-mass scaling: constant pressure for rigid molecules (build-defined).
+ *
+ * Molecules.  The molecules are those of the rigid table in force (emdee_md_set_rigid3); every other owned atom is a molecule
+ * of one atom.  A rigid molecule with sites k = 0 (apex), 1, 2 is assembled exactly as the constraint stages assemble it: y_0 =
+ * the apex record in double (plus its cell's origin for the cell-relative records of a Float32 engine), y_1 and y_2 = y_0 + the
+ * minimum images of the legs from it.  For a caller: with x the unwrapped positions of emdee_md_get_state, y_0 = x_apex and
+ * y_k = x_apex + (x_k - x_apex) - len rint((x_k - x_apex) / len) on the periodic axes.  Then
+ *   M = sum_k m_k ;  Y = sum_k m_k y_k / M ;  V = sum_k m_k v_k / M ;  d_k = y_k - Y
+ * (Y and V are formed from differences to the apex, not from an average of far numbers).
+ *
+ * Molecular sums, fp64, deterministic, order (xx, yy, zz, xy, xz, yz):
+ *   W_mol^ab = W^ab - sum_mol sum_k 1/2 (d_k^a f_k^b + d_k^b f_k^a)
+ *   K_mol^ab = K^ab - sum_mol (sum_k m_k v_k^a v_k^b - M V^a V^b)
+ * W and K are the atomic sums of emdee_md_pressure_tensor; f_k are the engine's current force-field forces (the forces
+ * emdee_md_get_state returns: Lennard-Jones, Coulomb, reciprocal space, 1-4 and bonded terms, no constraint forces).  sum d (x) f
+ * is not symmetric -- molecules carry torques -- so its off-diagonals are symmetrised; the barostats use the diagonal.
+ *   P_mol = (K_mol + W_mol) / V.
+ * Constraint forces are internal to a molecule and sum to zero: they drop out of W_mol exactly, and tr W_mol is -dU/dln(mu) of
+ * the molecular scale below, the volume derivative under the scaling actually applied.
+ *
+ * emdee_md_molecular_pressure_tensor: out[0..5] = W_mol, out[6..11] = K_mol.  Evaluates the tensor pass as
+ * emdee_md_pressure_tensor does, and the forces if they are not current, as emdee_md_energies does.  Available whether or not
+ * the switch below is on.  Without a rigid table it returns emdee_md_pressure_tensor's twelve numbers: the same kernels, nothing
+ * added.  Blocking, one read-back (the atomic and the molecules' totals come back in one copy; the host subtracts).
+ * EMDEE_ERR_STATE before emdee_md_set_state, and with a table set for another atom count or one the state did not fit (the
+ * conditions emdee_md_step refuses on).
+ *
+ * Molecular scale by mu, velocity_scale: the box and every one-atom molecule scale exactly as emdee_md_scale_box scales them.
+ * Every site of a rigid molecule moves by (mu_d - 1) (C_k,d - lo_d), where C_k = Y + (r_k - y_k) is the image of the centre of
+ * mass that goes with that site's record r_k (r_k - y_k is a whole number of box lengths): the stored image counts stay valid,
+ * the unwrapped coordinates of emdee_md_get_state transform consistently, and the molecule's minimum-image geometry is a pure
+ * translation.  The shift is added to each record in its own frame in double and rounded once.  Velocities of the members:
+ * v_k <- v_k + (velocity_scale - 1) V -- the centre-of-mass momentum scales, the rotation is untouched; velocity_scale = 1 leaves
+ * the velocity planes bit for bit.  Then the re-bin, re-plan, rebuild and force pass of emdee_md_scale_box.  No re-projection
+ * follows: distances and bond-relative velocities are unchanged up to rounding.
+ *
+ * emdee_md_set_molecular_scaling(on): 0 (the default) -- everything behaves as without this call, the three refusals of
+ * emdee_md_set_rigid3's text included.  1 --
+ *   - emdee_md_scale_box on an engine with a rigid table performs the molecular scale (EMDEE_ERR_STATE with a table set for
+ *     another atom count or one the state did not fit; the all-or-nothing checks of mu and the 2 (rc + skin) limit are unchanged);
+ *   - emdee_md_set_barostat is accepted with a table in force, and emdee_md_set_rigid3 while a barostat is on;
+ *   - the coupling events of an engine with a table take P from the molecular sums, for all three couplings, always through
+ *     the tensor path (one tensor pass per event): P_d = (K_mol^dd + W_mol^dd) / V, isotropic P = tr(K_mol + W_mol) / (3 V);
+ *     mu and velocity_scale from the formulas of emdee_md_set_barostat, applied with the molecular scale.
+ * On an engine without a table the switch changes nothing, bit for bit.  emdee_md_energies and emdee_md_pressure_tensor return
+ * atomic values always.  EMDEE_ERR_INVALID for on outside {0, 1}; EMDEE_ERR_STATE on an integrator lent by emdee_dd_engine or
+ * with ghosts, and for switching off while a barostat is on and a table is in force (the setting stays).
+ * The device time of the molecular sums and the molecular scale is emdee_md_kernel_time index 10.
+ * Scope: undivided orthorhombic boxes, the molecules of the rigid table; no emdee_dd_* counterpart. */
+int32_t emdee_md_molecular_pressure_tensor(emdee_md *md, double out[12]);
+int32_t emdee_md_set_molecular_scaling(emdee_md *md, int32_t on);
 int32_t emdee_md_nbr_stats(emdee_md *md, int64_t *builds, int64_t *listed, int32_t *max_count,
                            int32_t *capacity);
 int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
@@ -458,7 +514,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * profiling is on.  kernel: 0 = lj_force_nbr (plain force launches), 1 = verlet_kick_drift, 2 = rebuild
  * (bin + sort + nbr_build), 3 = verlet_kick, 4 = lj_force_nbr with the velocity-Verlet update fused in
  * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald, emdee_md_set_pme),
- * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3).  Blocking. */
+ * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3);
+ * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling).  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
@@ -492,7 +549,7 @@ int32_t emdee_md_langevin_normals(emdee_md *md, uint64_t seed, uint64_t step, co
  * then the engine re-bins on the new box, re-plans, rebuilds the list and evaluates the forces at the new positions, as
  * emdee_md_rebuild followed by a force pass: on return forces, energies and virials belong to the new box.  Exclusion, 1-4,
  * bonded and charge tables stay in force (their slots are re-recorded by the rebuild).  The scaling is atomic, not by molecule
- * centres.  All or nothing:
+ * centres (for the molecules of a rigid table: emdee_md_set_molecular_scaling).  All or nothing:
  *   - EMDEE_ERR_INVALID, with box, state and list untouched and the engine still able to step, for a non-finite or
  *     non-positive mu_d or velocity_scale, and for a new periodic length below 2 (rc + skin);
  *   - EMDEE_ERR_STATE before emdee_md_set_state, with ghosts, and on an integrator lent by emdee_dd_engine.
