@@ -198,6 +198,7 @@ struct MdImpl : IMd {
         current_mask = 0;
         // (rigid molecules set for another atom count stay in force, unused, as charges do; for the same count the table is
         // checked against the new state and the velocities are projected again)
+        if (!lent && sys.has_hbonds()) hbonds_unchecked = true;   // (before either check can refuse)
         if (!lent && sys.has_rigid()) {
             sys.reset_settle_error();
             rigid_unchecked = true;
@@ -205,6 +206,16 @@ struct MdImpl : IMd {
                 sys.settle_check_state(sys.tables->r_atoms.ptr, sys.tables->r_geom.ptr, sys.tables->r_atoms_h, sys.tables->r_n);
                 sys.settle_velocities();
                 rigid_unchecked = false;
+            }
+        }
+        // (an hbonds table: the same rules)
+        if (!lent && sys.has_hbonds()) {
+            sys.reset_hbond_error();
+            hbonds_unchecked = true;
+            if (!sys.hbonds_stale() && ng == 0) {
+                sys.hbond_check_state(sys.tables->h_atoms.ptr, sys.tables->h_dist.ptr, sys.tables->h_atoms_h, sys.tables->h_n);
+                sys.hbond_velocities();
+                hbonds_unchecked = false;
             }
         }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
@@ -219,6 +230,8 @@ struct MdImpl : IMd {
     bool defer_forces = false;
     // rigid molecules whose table has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
     bool rigid_unchecked = false;
+    // the same for the clusters of an hbonds table
+    bool hbonds_unchecked = false;
     // an engine of a decomposition (emdee_dd_engine): its pair tables are the decomposition's, keyed by global id
     bool lent = false;
     // decomposed domains: the global ids of the atoms handed to set_state (caller order, owned atoms and ghosts); they travel
@@ -250,8 +263,11 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!sys.settle_broken, EMDEE_ERR_STATE, "md_step: a rigid molecule had no solution; replace the table or the state");
         EMDEE_REQUIRE(!sys.has_rigid() || !(sys.rigid_stale() || rigid_unchecked), EMDEE_ERR_STATE, "md_step: rigid molecules set for %lld atoms, "
                       "the state holds %d (or does not fit them): set them again or clear them (emdee_md_set_rigid3)", (long long)sys.tables->r_limit, sys.n_owned);
+        EMDEE_REQUIRE(!sys.hbond_broken, EMDEE_ERR_STATE, "md_step: an hbonds cluster had no solution; replace the table or the state");
+        EMDEE_REQUIRE(!sys.has_hbonds() || !(sys.hbonds_stale() || hbonds_unchecked), EMDEE_ERR_STATE, "md_step: hbonds clusters set for %lld atoms, "
+                      "the state holds %d (or does not fit them): set them again or clear them (emdee_md_set_hbonds)", (long long)sys.tables->h_limit, sys.n_owned);
         if (nsteps == 0) return;
-        if (sys.has_rigid()) { step_rigid(nsteps, dt, rebuild_every); return; }   // (coupled or not)
+        if (sys.has_rigid() || sys.has_hbonds()) { step_rigid(nsteps, dt, rebuild_every); return; }   // (coupled or not)
         if (baro.kind != EMDEE_BAROSTAT_OFF) { step_coupled(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
@@ -324,6 +340,8 @@ struct MdImpl : IMd {
     void scale_box(const double mu[3], double vscale) override {
         use_device(sys.ctx);
         require_undivided("scale_box");
+        EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "scale_box: the engine holds an hbonds table (emdee_md_set_hbonds): scaling atom by atom would "
+                      "break its bonds, and the molecular scale is written for three-site molecules; clear the table first");
         EMDEE_REQUIRE(!sys.has_rigid() || molecular, EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
                       "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
@@ -342,6 +360,9 @@ struct MdImpl : IMd {
                       double temperature, uint64_t seed, uint64_t first_step) override {
         use_device(sys.ctx);
         require_undivided("set_barostat");
+        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_hbonds(), EMDEE_ERR_STATE, "set_barostat: the engine holds an hbonds table "
+                      "(emdee_md_set_hbonds): its pressure lacks the clusters' constraint virial, and the molecular sums are written for "
+                      "three-site molecules; clear the table first");
         EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_rigid() || molecular, EMDEE_ERR_STATE, "set_barostat: the engine holds rigid molecules "
                       "(emdee_md_set_rigid3): its pressure lacks the constraint virial, and scaling atom by atom would break their geometry "
                       "(emdee_md_set_molecular_scaling couples to the molecular pressure)");
@@ -392,7 +413,9 @@ struct MdImpl : IMd {
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
     }
-    // emdee_md_step with rigid molecules (emdee_md_set_rigid3): step_coupled's loop shape -- every step closes its own half kick, so
+    // emdee_md_step with rigid molecules (emdee_md_set_rigid3) or an hbonds table (emdee_md_set_hbonds; every stage runs for whichever
+    // tables exist, SETTLE / RATTLE on the molecules and M-SHAKE / RATTLE on the clusters, whose atoms are disjoint):
+    // step_coupled's loop shape -- every step closes its own half kick, so
     // the state after s steps does not depend on how they were dealt to calls -- with the three constraint stages around the
     // unchanged kernels: (a) the constrained atoms' positions are remembered, (c) SETTLE on the drifted records, (e) the bond
     // components of the relative velocities are removed.  Stage (c) re-tests its atoms against the rebuild threshold, so the
@@ -402,20 +425,24 @@ struct MdImpl : IMd {
     // molecular pressure from that step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale,
     // which rebuilds the list and evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.
     void step_rigid(int nsteps, double dt, int rebuild_every) {
-        const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF;
+        const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF, rigid = sys.has_rigid(), hbonds = sys.has_hbonds();
         EMDEE_REQUIRE(!coupled || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
+        EMDEE_REQUIRE(!coupled || !hbonds, EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
-            sys.settle_gather();
+            if (rigid) sys.settle_gather();
+            if (hbonds) sys.hbond_gather();
             sys.kick_drift(0.5 * dt, dt);
-            sys.settle_positions(dt);
+            if (rigid) sys.settle_positions(dt);
+            if (hbonds) sys.hbond_positions(dt);
             since_build++;
             const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
             if (rb) { sys.resort(); since_build = 0; }
             sys.compute_forces(EMDEE_FORCES);
             sys.kick(0.5 * dt);
-            sys.settle_velocities();
+            if (rigid) sys.settle_velocities();
+            if (hbonds) sys.hbond_velocities();
             current_mask = EMDEE_FORCES;
             if (coupled) baro.step++;
             if (event) couple(dt);
@@ -423,6 +450,7 @@ struct MdImpl : IMd {
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
         sys.check_settle();                                  // (one read-back per call)
+        sys.check_hbonds();                                  // (one more with an hbonds table)
     }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
@@ -568,6 +596,8 @@ struct MdImpl : IMd {
     void molecular_pressure_tensor(double out[12]) override {
         use_device(sys.ctx);
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
+        EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "molecular_pressure_tensor: the engine holds an hbonds table (emdee_md_set_hbonds): the "
+                      "molecular sums are written for three-site molecules and would keep the clusters' constraint forces; clear the table first");
         if (!sys.has_rigid()) { pressure_tensor(out); return; }
         EMDEE_REQUIRE(!lent && n_ghost == 0, EMDEE_ERR_STATE, "molecular_pressure_tensor: rigid molecules on an integrator with ghosts or a domain's");
         require_fitting_table("molecular_pressure_tensor");
@@ -600,11 +630,13 @@ struct MdImpl : IMd {
         // ids 0..3: the TimerIds; 4: every fused step launch (interior + boundary halves of a decomposed step together, as
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
-        // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 10, EMDEE_ERR_INVALID, "kernel id out of range");
+        // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
+        // stages of an engine with an hbonds table
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 11, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[11][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
-                                {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1}};
+        const int ids[12][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+                                {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
+                                {T_HBONDS, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -671,6 +703,18 @@ struct MdImpl : IMd {
             sys.reset_settle_error();
             rigid_unchecked = false;
             if (sys.has_rigid()) sys.settle_velocities();
+        }, false);
+    }
+    // emdee_md_set_hbonds: set_rigid3's contract for the star clusters of bonds to hydrogen
+    void set_hbonds(const int32_t *atoms, const double *dist, int32_t n_clusters) override {
+        EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF, EMDEE_ERR_STATE, "set_hbonds: pressure coupling is on (emdee_md_set_barostat): the pressure of "
+                      "an engine with an hbonds table lacks the clusters' constraint virial; switch the coupling off first");
+        install("hbonds clusters", "a decomposed run has none", [&] {
+            sys.own_tables.set_hbonds(atoms, dist, n_clusters, sys.n_owned, sys.stream(),
+                                      [&](const int *a, const double *d, const std::vector<int32_t> &h, int n) { sys.hbond_check_state(a, d, h, n); });
+            sys.reset_hbond_error();
+            hbonds_unchecked = false;
+            if (sys.has_hbonds()) sys.hbond_velocities();
         }, false);
     }
     // emdee_md_set_ewald: all or nothing -- every refusal comes before the setting changes

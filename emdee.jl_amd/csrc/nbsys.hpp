@@ -12,6 +12,7 @@
 #include "ewald.hpp"
 #include "kernels.hpp"
 #include "settle.hpp"
+#include "shake.hpp"
 #include "topology_dev.hpp"
 #include "typed.hpp"
 
@@ -37,8 +38,9 @@ static inline void refuse_experiment_switches() {
 // T_EWALD: the reciprocal-space pass of an Ewald engine (ewald.hpp), which runs inside T_FORCE's launches as well
 // T_SETTLE: the three constraint stages of an engine with rigid molecules (settle.hpp)
 // T_MOLECULAR: the molecular sums and the molecular scale of an engine with rigid molecules (settle.hpp)
+// T_HBONDS: the three constraint stages of an engine with an hbonds table (shake.hpp)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_COUNT = 10 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_COUNT = 11 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -1331,6 +1333,62 @@ struct NbSystem {
         }
         if (words[1] != 0) {
             set_error("%s", topo::rigid3_message(atoms_h, (int64_t)words[1] - 1, "the loaded positions miss a distance of the table by more "
+                      "than 1e-3 (relative): a wrong topology, not rounding").c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+    }
+
+    // ---------------------------------------------------------------- bonds to hydrogen (Topology::set_hbonds, shake.hpp)
+    // The same three stages for the star clusters of the hbonds table: one thread per cluster, no atomics on the state.  The
+    // atoms of the two tables are disjoint (topology.hpp), so the order of the two kernels within a stage cannot matter.
+    DevBuf<double> hbond_x0;                                 // stage (a): 12 doubles per cluster, table order
+    bool has_hbonds() const { return tables->has_hbonds; }
+    bool hbonds_stale() const { return has_hbonds() && (tables->h_limit != n_owned || id_gaps); }
+    // a cluster that moved too far for a solution (flags[23], raised by k_hbond_positions): as settle_broken
+    bool hbond_broken = false;
+    void reset_hbond_error() {
+        hbond_broken = false;
+        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 23, 0, sizeof(int), stream()));
+    }
+    void check_hbonds() {
+        if (!has_hbonds() || !flags.ptr) return;
+        int32_t word = 0;
+        if (!hbond_broken) read_back_words(ctx, stream(), flags.ptr + 23, 1, &word);
+        if (word != 0) {
+            hbond_broken = true;
+            set_error("%s", topo::hbonds_message(tables->h_atoms_h, (int64_t)word - 1, "the step moved its atoms too far for the bonds to be "
+                      "restored (no solution of the SHAKE equations within the iteration cap); the cluster was left as it is: replace the "
+                      "table or the state").c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        EMDEE_REQUIRE(!hbond_broken, EMDEE_ERR_STATE, "an hbonds cluster had no solution (reported before): replace the table or the state");
+    }
+    SettleArgs<real> hbond_args() const { return settle_args(tables->h_atoms.ptr, tables->h_dist.ptr, tables->h_n); }
+    void hbond_gather() {
+        Timed t(this, T_HBONDS);
+        hbond_x0.ensure((size_t)12 * tables->h_n + 1);
+        hipLaunchKernelGGL((k_hbond_gather<real>), dim3(blocks_for(tables->h_n, 256)), dim3(256), 0, stream(), hbond_args(), hbond_x0.ptr);
+    }
+    void hbond_positions(double dt) {
+        Timed t(this, T_HBONDS);
+        const real thr = (real)(0.5 * skin);                 // (kick_drift's threshold)
+        hipLaunchKernelGGL((k_hbond_positions<real>), dim3(blocks_for(tables->h_n, 256)), dim3(256), 0, stream(), hbond_args(),
+                           (const double *)hbond_x0.ptr, dt > 0.0 ? 1.0 / dt : 0.0, (const real *)xb.ptr, thr * thr, flags.ptr + 1, flags.ptr + 23);
+    }
+    void hbond_velocities() {
+        Timed t(this, T_HBONDS);
+        hipLaunchKernelGGL((k_hbond_velocities<real>), dim3(blocks_for(tables->h_n, 256)), dim3(256), 0, stream(), hbond_args());
+    }
+    // a table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the cluster whose atoms
+    // miss a distance by more than 1e-3 relative; one launch, one read-back
+    void hbond_check_state(const int *atoms, const double *dist, const std::vector<int32_t> &atoms_h, int n_clusters) {
+        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 24, 0, sizeof(int), stream()));
+        hipLaunchKernelGGL((k_hbond_check<real>), dim3(blocks_for(n_clusters, 256)), dim3(256), 0, stream(), settle_args(atoms, dist, n_clusters),
+                           flags.ptr + 24);
+        int32_t word = 0;
+        read_back_words(ctx, stream(), flags.ptr + 24, 1, &word);
+        if (word != 0) {
+            set_error("%s", topo::hbonds_message(atoms_h, (int64_t)word - 1, "the loaded positions miss a distance of the table by more "
                       "than 1e-3 (relative): a wrong topology, not rounding").c_str());
             throw Failure{EMDEE_ERR_STATE};
         }

@@ -1,4 +1,4 @@
-// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, charges.  Plain C++17 on
+// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, hbonds clusters, charges.  Plain C++17 on
 // std::vector, no HIP: every function here validates or builds and throws through EMDEE_REQUIRE before it returns anything, so
 // a stand-alone host program can test it (tests/c/topology_host.cpp).  topology_dev.hpp holds the device buffers.
 #pragma once
@@ -200,9 +200,11 @@ inline std::string lost_partner_message(const std::vector<int32_t> (&atoms)[KIND
 
 // ---- rigid three-site molecules (emdee_md_set_rigid3): {apex, a, b} ids and {d_leg, d_base} per molecule
 // The table as a caller gave it: ids in [0, lim), no atom named twice within or across molecules, distances finite and > 0 with
-// d_base < 2 d_leg (a triangle); else refused.
+// d_base < 2 d_leg (a triangle), and no atom that the hbonds table in force names (`hbonds`: its ids, -1 in unused slots; NULL:
+// none in force); else refused.
 template <typename T>
-std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector<double> &geom, int64_t lim) {
+std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector<double> &geom, int64_t lim,
+                                    const std::vector<int32_t> *hbonds = nullptr) {
     const int64_t n = (int64_t)(raw.size() / 3);
     EMDEE_REQUIRE((int64_t)geom.size() == 2 * n, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules but %lld distances", (long long)n, (long long)geom.size());
     EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules (at most (2^31 - 1) / 3)", (long long)n);
@@ -225,6 +227,14 @@ std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector
     for (size_t k = 1; k < named.size(); k++)
         EMDEE_REQUIRE(named[k].first != named[k - 1].first, EMDEE_ERR_INVALID, "set_rigid3: atom %lld is named twice (molecules %lld and %lld)",
                       (long long)named[k].first, (long long)named[k - 1].second, (long long)named[k].second);
+    if (hbonds) {
+        std::vector<int32_t> taken(*hbonds);
+        std::sort(taken.begin(), taken.end());
+        for (const auto &a : named)
+            EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)a.first), EMDEE_ERR_INVALID, "set_rigid3: atom %lld of molecule %lld "
+                          "belongs to a cluster of the hbonds table in force (emdee_md_set_hbonds): an atom is held by one table",
+                          (long long)a.first, (long long)a.second);
+    }
     return std::vector<int32_t>(raw.begin(), raw.end());
 }
 // one byte per id in [0, lim): 1 for the atoms a (checked) table names, 0 for the others -- the one-atom molecules of the
@@ -241,6 +251,74 @@ inline std::string rigid3_message(const std::vector<int32_t> &atoms, int64_t mol
     const bool in = molecule >= 0 && (size_t)(3 * molecule + 2) < atoms.size();
     snprintf(text, sizeof(text), "rigid molecule %lld (atoms %d %d %d): %s", (long long)molecule, in ? atoms[(size_t)3 * molecule] : -1,
              in ? atoms[(size_t)3 * molecule + 1] : -1, in ? atoms[(size_t)3 * molecule + 2] : -1, what);
+    return text;
+}
+
+// ---- bonds to hydrogen (emdee_md_set_hbonds): star clusters {centre, s1, s2, s3} with -1 in the unused trailing slots, and the
+// three centre-satellite distances per cluster
+// The table as a caller gave it: ids in [0, lim), at least one satellite, no id after a -1, no atom named twice within or across
+// clusters, none that the rigid table in force names (`rigid`: its ids; NULL: none in force), the distance of every slot in use
+// finite and > 0; else refused.
+template <typename T>
+std::vector<int32_t> checked_hbonds(const std::vector<T> &raw, const std::vector<double> &dist, int64_t lim,
+                                    const std::vector<int32_t> *rigid = nullptr) {
+    const int64_t n = (int64_t)(raw.size() / 4);
+    EMDEE_REQUIRE((int64_t)dist.size() == 3 * n, EMDEE_ERR_INVALID, "set_hbonds: %lld clusters but %lld distances", (long long)n, (long long)dist.size());
+    EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_hbonds: %lld clusters (at most (2^31 - 1) / 4)", (long long)n);
+    std::vector<std::pair<int64_t, int64_t>> named;           // (id, cluster)
+    named.reserve((size_t)4 * n);
+    std::vector<int32_t> out((size_t)4 * n, -1);
+    for (int64_t k = 0; k < n; k++) {
+        bool ended = false;
+        for (int a = 0; a < 4; a++) {
+            const int64_t g = raw[(size_t)4 * k + a];
+            if (a >= 1 && g == -1) {
+                EMDEE_REQUIRE(a >= 2, EMDEE_ERR_INVALID, "set_hbonds: cluster %lld is empty (its first satellite is -1)", (long long)k);
+                ended = true;
+                continue;
+            }
+            EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_hbonds: cluster %lld names id %lld, outside [0, %lld)", (long long)k,
+                          (long long)g, (long long)lim);
+            EMDEE_REQUIRE(!ended, EMDEE_ERR_INVALID, "set_hbonds: cluster %lld names id %lld after a -1 (unused slots are the trailing ones)",
+                          (long long)k, (long long)g);
+            const double d = dist[(size_t)3 * k + (a >= 1 ? a - 1 : 0)];
+            EMDEE_REQUIRE(a == 0 || (std::isfinite(d) && d > 0.0), EMDEE_ERR_INVALID, "set_hbonds: cluster %lld has a distance that is not "
+                          "finite and > 0 (satellite %d)", (long long)k, a);
+            named.emplace_back(g, k);
+            out[(size_t)4 * k + a] = (int32_t)g;
+        }
+    }
+    std::sort(named.begin(), named.end());
+    for (size_t k = 1; k < named.size(); k++)
+        EMDEE_REQUIRE(named[k].first != named[k - 1].first, EMDEE_ERR_INVALID, "set_hbonds: atom %lld is named twice (clusters %lld and %lld)",
+                      (long long)named[k].first, (long long)named[k - 1].second, (long long)named[k].second);
+    if (rigid) {
+        std::vector<int32_t> taken(*rigid);
+        std::sort(taken.begin(), taken.end());
+        for (const auto &a : named)
+            EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)a.first), EMDEE_ERR_INVALID, "set_hbonds: atom %lld of cluster %lld "
+                          "belongs to a molecule of the rigid table in force (emdee_md_set_rigid3): an atom is held by one table",
+                          (long long)a.first, (long long)a.second);
+    }
+    return out;
+}
+// the distances as the kernels read them: those of the unused slots are 0 (never read as a length)
+inline std::vector<double> hbonds_distances(const std::vector<int32_t> &atoms, const std::vector<double> &dist) {
+    std::vector<double> out(dist);
+    for (size_t k = 0; k < out.size(); k++)
+        if (atoms[4 * (k / 3) + 1 + k % 3] < 0) out[k] = 0.0;
+    return out;
+}
+// the error texts of the device checks (cluster: the number the kernels report, from 0)
+inline std::string hbonds_message(const std::vector<int32_t> &atoms, int64_t cluster, const char *what) {
+    char text[512];
+    const bool in = cluster >= 0 && (size_t)(4 * cluster + 3) < atoms.size();
+    std::string ids;
+    for (int a = 0; a < 4; a++) {
+        const int32_t g = in ? atoms[(size_t)4 * cluster + a] : -1;
+        if (a == 0 || g >= 0) ids += (a ? " " : "") + std::to_string(g);
+    }
+    snprintf(text, sizeof(text), "hbonds cluster %lld (atoms %s): %s", (long long)cluster, ids.c_str(), what);
     return text;
 }
 

@@ -133,7 +133,7 @@ struct Topology {
         EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules (at most (2^31 - 1) / 3)", (long long)n);
         const std::vector<int32_t> raw = fetch(atoms_dev, (size_t)3 * n, s);
         const std::vector<double> geom = fetch(geom_dev, (size_t)2 * n, s);
-        const std::vector<int32_t> h = topo::checked_rigid3(raw, geom, lim);
+        const std::vector<int32_t> h = topo::checked_rigid3(raw, geom, lim, has_hbonds ? &h_atoms_h : nullptr);
         DevBuf<int> na;
         DevBuf<double> ng;
         DevBuf<unsigned char> nm;
@@ -146,6 +146,39 @@ struct Topology {
         r_atoms_h = h;
         r_n = (int)n; r_limit = lim;
         has_rigid = true;
+    }
+
+    // ---- bonds to hydrogen (emdee_md_set_hbonds; shake.hpp): {centre, s1, s2, s3} caller ids (-1: an unused trailing slot) and the
+    // three distances per cluster, undivided engines only
+    DevBuf<int> h_atoms;
+    DevBuf<double> h_dist;
+    std::vector<int32_t> h_atoms_h;                          // the ids as given (the error texts name them; set_rigid3 checks against them)
+    int h_n = 0;                                             // clusters
+    int64_t h_limit = 0;                                     // the atom count the ids were checked against
+    bool has_hbonds = false;
+    // Replaces the table by the n clusters at atoms_dev / dist_dev (device); n = 0 clears it.  check: as set_rigid3's.
+    template <class Check>
+    void set_hbonds(const int32_t *atoms_dev, const double *dist_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && dist_dev)), EMDEE_ERR_INVALID, "set_hbonds: negative count or NULL array");
+        if (n == 0) {
+            has_hbonds = false; h_n = 0; h_atoms_h.clear();
+            return;
+        }
+        EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_hbonds: %lld clusters (at most (2^31 - 1) / 4)", (long long)n);
+        const std::vector<int32_t> raw = fetch(atoms_dev, (size_t)4 * n, s);
+        const std::vector<double> given = fetch(dist_dev, (size_t)3 * n, s);
+        const std::vector<int32_t> h = topo::checked_hbonds(raw, given, lim, has_rigid ? &r_atoms_h : nullptr);
+        const std::vector<double> dist = topo::hbonds_distances(h, given);
+        DevBuf<int> na;
+        DevBuf<double> nd;
+        put(na, h, s); put(nd, dist, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        check(na.ptr, nd.ptr, h, (int)n);
+        // ---- commit
+        h_atoms.swap(na); h_dist.swap(nd);
+        h_atoms_h = h;
+        h_n = (int)n; h_limit = lim;
+        has_hbonds = true;
     }
 
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the

@@ -70,6 +70,7 @@ class BondedTable:
         root = ET.parse(xml_file).getroot()
         self.classes = {t.attrib["name"]: t.attrib.get("class", t.attrib["name"]) for t in root.iter("Type")}
         self.masses = {t.attrib["name"]: float(t.attrib["mass"]) for t in root.iter("Type") if "mass" in t.attrib}
+        self.elements = {t.attrib["name"]: t.attrib["element"] for t in root.iter("Type") if "element" in t.attrib}
         self.bonds, self.angles, self.propers = [], [], []
         for kind, tag, n, out in (("HarmonicBondForce", "Bond", 2, self.bonds), ("HarmonicAngleForce", "Angle", 3, self.angles),
                                   ("PeriodicTorsionForce", "Proper", 4, self.propers)):
@@ -222,6 +223,52 @@ def rigid_triatomics(types, bonds, table, length_unit=1.0, with_dropped=False):
     arr = lambda v, m, dt=np.int64: np.array(v, dtype=dt).reshape(-1, m)
     out = (arr(atoms, 3), arr(geom, 2, np.float64))
     return out + (arr(drop_b, 2), arr(drop_a, 3)) if with_dropped else out
+
+
+def hydrogen_clusters(types, bonds, table, length_unit=1.0, skip=(), with_dropped=False):
+    """The star clusters of bonds to hydrogen (emdee_md_set_hbonds) of a bond graph: every non-hydrogen atom together with the
+    one, two or three hydrogens bonded to it.  Hydrogen is decided by the `element` attribute of the atom's type
+    (table.elements).  skip: atom ids to leave out, centres and hydrogens alike (those of rigid_triatomics, which stay with
+    emdee_md_set_rigid3).  Returns (atoms, dist):
+      atoms (n, 4) int64 {centre, h1, h2, h3}, hydrogens ascending, -1 in the unused trailing slots; dist (n, 3) float64, the
+        r0 of each bond's entry / length_unit, 0 in the unused slots;
+    with_dropped: (atoms, dist, drop_bonds), the last the (m, 2) ids (i < j) of the bonds the constraints replace, as topology()
+    writes them.
+    Raises KeyError for a bond the table has no entry for, ValueError for a hydrogen bonded to two atoms or to another hydrogen,
+    or a centre with more than three hydrogens."""
+    n = len(types)
+    skip = {int(a) for a in np.asarray(skip, dtype=np.int64).ravel()}
+    nb = [set() for _ in range(n)]
+    for i, j in np.asarray(bonds, dtype=np.int64).reshape(-1, 2):
+        nb[i].add(int(j)); nb[j].add(int(i))
+    is_h = [table.elements.get(t) == "H" for t in types]
+    for h in range(n):
+        if is_h[h] and h not in skip and nb[h]:
+            if len(nb[h]) != 1:
+                raise ValueError("hydrogen %d (type %s) is bonded to %d atoms" % (h, types[h], len(nb[h])))
+            if is_h[next(iter(nb[h]))]:
+                raise ValueError("hydrogen %d (type %s) is bonded to another hydrogen" % (h, types[h]))
+    atoms, dist, drop = [], [], []
+    for c in range(n):
+        if is_h[c] or c in skip:
+            continue
+        hs = sorted(h for h in nb[c] if is_h[h] and h not in skip)
+        if not hs:
+            continue
+        if len(hs) > 3:
+            raise ValueError("atom %d (type %s) is bonded to %d hydrogens (a cluster holds at most three)" % (c, types[c], len(hs)))
+        row = []
+        for h in hs:
+            bond = table.bond(types[c], types[h])
+            if bond is None:
+                raise KeyError("no bond parameters for atoms %s (types %s)" % ((c, h), (types[c], types[h])))
+            row.append(bond[0][1] / length_unit)
+            drop.append((min(c, h), max(c, h)))
+        atoms.append([c] + hs + [-1] * (3 - len(hs)))
+        dist.append(row + [0.0] * (3 - len(hs)))
+    arr = lambda v, m, dt=np.int64: np.array(v, dtype=dt).reshape(-1, m)
+    out = (arr(atoms, 4), arr(dist, 3, np.float64))
+    return out + (arr(sorted(drop), 2),) if with_dropped else out
 
 
 def save_checkpoint(path, positions, velocities, step, box_length):

@@ -91,6 +91,14 @@ set_rigid3!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, geom::U
     check(ccall((:emdee_md_set_rigid3, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
                 atoms === nothing ? C_NULL : atoms.ptr, geom === nothing ? C_NULL : geom.ptr, atoms === nothing ? 0 : size(atoms, 2)))
 
+# int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters);
+# Bonds to hydrogen at fixed lengths: atoms a device Int32 matrix (4, n) of caller ids {centre, s1, s2, s3} (0-based, -1 in the
+# unused trailing slots), dist a device Float64 matrix (3, n) of the centre-satellite distances; every later step! holds them
+# (M-SHAKE + RATTLE).  Moves no atom, projects the velocities once; `nothing` clears the table.
+set_hbonds!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, dist::Union{Nothing,HipArray{Float64,2}}=nothing) =
+    check(ccall((:emdee_md_set_hbonds, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
+                atoms === nothing ? C_NULL : atoms.ptr, dist === nothing ? C_NULL : dist.ptr, atoms === nothing ? 0 : size(atoms, 2)))
+
 # Pressure coupling (include/emdee_hip.h; undivided boxes).
 # int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);   -> (lo, len) of the engine's box
 function box(md::VelocityVerlet)

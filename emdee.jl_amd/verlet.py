@@ -58,7 +58,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the constraint stages of an engine with rigid molecules (set_rigid3_)
            "settle": 9,
            # the molecular sums and the molecular scale of an engine with rigid molecules (set_molecular_scaling_)
-           "molecular": 10}
+           "molecular": 10,
+           # the constraint stages of an engine with an hbonds table (set_hbonds_)
+           "hbonds": 11}
 
 
 class VelocityVerlet:
@@ -367,6 +369,24 @@ class VelocityVerlet:
         if a.shape[0] != g.shape[0]:
             raise ValueError("set_rigid3_: %d molecules but %d geometry rows" % (a.shape[0], g.shape[0]))
         _lib.call("emdee_md_set_rigid3", self._handle, C.c_void_p(a.data_ptr()) if a.numel() else None,
+                  C.c_void_p(g.data_ptr()) if g.numel() else None, int(a.shape[0]))
+
+    def set_hbonds_(self, atoms, dist):
+        """Bonds to hydrogen at fixed lengths (include/emdee_hip.h emdee_md_set_hbonds): atoms (n, 4) caller ids {centre, s1, s2,
+        s3} with -1 in the unused trailing slots, dist (n, 3) the centre-satellite distances (those of unused slots are ignored).
+        Every later step_ holds them (M-SHAKE on the positions, RATTLE on the velocities).  Moves no atom; projects the velocities
+        once.  Empty or None clears the table."""
+        a = torch.as_tensor(atoms if atoms is not None else [])
+        g = torch.as_tensor(dist if dist is not None else [], dtype=torch.float64)
+        if a.numel() and (a.dim() != 2 or a.shape[1] != 4):
+            raise ValueError("set_hbonds_: atoms must have shape (n, 4), got %s" % (tuple(a.shape),))
+        if g.numel() and (g.dim() != 2 or g.shape[1] != 3):
+            raise ValueError("set_hbonds_: dist must have shape (n, 3), got %s" % (tuple(g.shape),))
+        a = a.reshape(-1, 4).to(device=self.device, dtype=torch.int32).contiguous()
+        g = g.reshape(-1, 3).to(device=self.device).contiguous()
+        if a.shape[0] != g.shape[0]:
+            raise ValueError("set_hbonds_: %d clusters but %d rows of distances" % (a.shape[0], g.shape[0]))
+        _lib.call("emdee_md_set_hbonds", self._handle, C.c_void_p(a.data_ptr()) if a.numel() else None,
                   C.c_void_p(g.data_ptr()) if g.numel() else None, int(a.shape[0]))
 
     def close(self):

@@ -355,6 +355,46 @@ int32_t emdee_md_set_pme(emdee_md *md, double alpha, const int32_t grid[3], int3
  *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 9. */
 int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double *geom_dev, int32_t n_mol);
 
+/* Bonds to hydrogen held at fixed lengths (SHAKE in matrix form: Kraeutler, van Gunsteren & Huenenberger, J. Comput. Chem. 22,
+ * 501 (2001); RATTLE: Andersen, J. Comput. Phys. 52, 24 (1983); build-defined like the integrator).
+ * n_clusters star clusters: a centre and one, two or three satellites (X-H, XH2, XH3), every satellite at a fixed distance from
+ * the centre; no constraint between satellites.  atoms_dev: 4 n_clusters caller ids {centre, s1, s2, s3}, -1 in the unused
+ * trailing slots; dist_dev: 3 n_clusters doubles, |centre - s_k| (those of unused slots are ignored).  Device arrays, copied.
+ * n_clusters = 0 clears the table.  Water stays with emdee_md_set_rigid3: the two tables may be in force together and name
+ * disjoint atoms.
+ * The contract is that of emdee_md_set_rigid3, point for point.  While a table is in force emdee_md_step takes the closed form
+ * described there, and each of its stages runs for whichever tables exist:
+ *   (a) the clusters' positions x0 are remembered;
+ *   (c) x_c <- x_c + w_c sum_j lambda_j e_j, x_k <- x_k - w_k lambda_k e_k with e_k = x0_c - x0_k, w = 1/m, and the lambda that
+ *       restore the n distances: Newton's method from lambda = 0 on the n coupled equations, each n x n system solved directly,
+ *       to a residual | |r_k|^2 - d_k^2 | <= 4e-15 d_k^2 or 32 iterations (per thread, deterministic); v <- v + (x_constrained -
+ *       x_unconstrained) / dt; the atoms are tested against the skin/2 threshold again and raise the same rebuild word;
+ *   (e) the components of the relative velocities along the bonds are removed: one symmetric n x n solve, applied twice.
+ * One thread per cluster, fp64 on unwrapped differences in both precisions, no atomics on the state: step(40), 8 x step(5) and
+ * 40 x step(1) agree bit for bit, and an engine whose table was cleared steps exactly as one that never had one.
+ *   - Device arrays are copied.  The call moves no atom and CHANGES VELOCITIES: stage (e) is applied once.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: a NULL array with n_clusters > 0, n_clusters < 0, an id
+ *     outside [0, n_owned), an empty cluster (s1 < 0), a -1 followed by an id, an atom named twice (within a cluster or across
+ *     clusters), an atom that the rigid table in force also names (emdee_md_set_rigid3 refuses the mirror case), a distance of
+ *     a used slot that is not finite and > 0.  EMDEE_ERR_STATE naming a cluster, the previous table in force: the loaded
+ *     positions miss a distance by more than 1e-3 relative.  EMDEE_ERR_STATE also before emdee_md_set_state, with ghosts, and
+ *     on an integrator lent by emdee_dd_engine.
+ *   - The table survives an emdee_md_set_state with the same atom count, checked against the new state and the new velocities
+ *     projected; after a state with another count, or one that did not fit, emdee_md_step returns EMDEE_ERR_STATE until the
+ *     table is set again or cleared.
+ *   - A cluster for which stage (c) finds no solution (the iteration cap, a singular Jacobian, a number that is not finite) is
+ *     left as it is; emdee_md_step, which reads one more error word per call, returns EMDEE_ERR_STATE naming it, and the engine
+ *     refuses to step until the table or the state is replaced.
+ *   - The split calls never constrain.  Forces, energies, virials and tensors stay those of the force field.  Masses are
+ *     unrestricted.
+ *   - Pressure: whatever emdee_md_set_molecular_scaling says, an engine with an hbonds table refuses emdee_md_scale_box,
+ *     emdee_md_set_barostat (other than OFF) and emdee_md_molecular_pressure_tensor with EMDEE_ERR_STATE, and this call returns
+ *     EMDEE_ERR_STATE while a barostat is on.  The molecular sums and the molecular scale are written for three-site molecules;
+ *     without the clusters' part the promise that constraint forces drop out of the molecular pressure would be false.
+ *     Extending them to clusters is a follow-up, not part of this call.
+ *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 11. */
+int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -515,7 +555,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * (bin + sort + nbr_build), 3 = verlet_kick, 4 = lj_force_nbr with the velocity-Verlet update fused in
  * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald, emdee_md_set_pme),
  * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3);
- * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling).  Blocking. */
+ * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling);
+ * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds).  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
