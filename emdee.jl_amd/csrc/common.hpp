@@ -286,6 +286,25 @@ static inline void read_back_words(emdee_ctx *ctx, hipStream_t s, const int *dev
     for (int k = 0; k < n2; k++) out2[k] = ((volatile int32_t *)data)[n + k];
 }
 
+// A fault word and its latch: a kernel raises words[index] (the entry + 1 it failed on), the host polls it where its owner
+// decides to (behind a guard of the owner's, with a message of the owner's) and, once it has seen the word raised, refuses
+// until reset.  words: the engine's flag words on the device (NULL before the first state: nothing to clear).
+struct FaultWord {
+    int index;
+    bool latched = false;
+    void reset(int *words, hipStream_t s) {
+        latched = false;
+        if (words) EMDEE_HIP_CHECK(hipMemsetAsync(words + index, 0, sizeof(int), s));
+    }
+    // blocking: the word as it is when the work queued on s so far has run; latches a raised one.  Once latched: 0, and no read-back.
+    int32_t poll(emdee_ctx *ctx, const int *words, hipStream_t s) {
+        int32_t word = 0;
+        if (!latched) read_back_words(ctx, s, words + index, 1, &word);
+        if (word != 0) latched = true;
+        return word;
+    }
+};
+
 // HIP-event pair pool for per-kernel device timing on the context's stream (bench.py's
 // roofline numbers come from here).
 struct KernelTimer {

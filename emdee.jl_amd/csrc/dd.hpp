@@ -1287,7 +1287,7 @@ struct DdImpl : IDd {
     // every rank then sets `broken` and refuses to step, so that no rank enters a step's collectives alone.  The message is the
     // probe's on the rank that holds the domain, `elsewhere` on the others.
     template <class Probe>
-    void agree_or_refuse(bool active, Probe &&probe, bool NbSystem<real>::*broken, const char *elsewhere) {
+    void agree_or_refuse(bool active, Probe &&probe, FaultWord NbSystem<real>::*broken, const char *elsewhere) {
         if (!active) return;
         join_halo();
         std::vector<std::vector<double>> bad;
@@ -1300,19 +1300,19 @@ struct DdImpl : IDd {
         double total = 0.0;
         allreduce_sum(bad, 1, &total);
         if (total > 0.0) {
-            for (auto &pd : dom) pd->sys().*broken = true;
+            for (auto &pd : dom) (pd->sys().*broken).latched = true;
             if (!mine) set_error("%s", elsewhere);
             throw Failure{EMDEE_ERR_STATE};
         }
     }
     // an atom of a domain has an id outside the charge table (NbSystem::check_charges): the charges must be set again
     void check_charges() {
-        agree_or_refuse(tables.has_charges, [](NbSystem<real> &s) { s.ensure_charges(); s.check_charges(); }, &NbSystem<real>::charge_broken,
+        agree_or_refuse(tables.has_charges, [](NbSystem<real> &s) { s.ensure_charges(); s.check_charges(); }, &NbSystem<real>::charge_fault,
                         "an atom of another domain has an id outside the charge table: set the charges again");
     }
     // a domain's bonded term has lost a partner (NbSystem::check_bonded; the message names the term on the rank that holds it)
     void check_bonded() {
-        agree_or_refuse(tables.has_bonded, [](NbSystem<real> &s) { s.check_bonded(); }, &NbSystem<real>::bonded_broken,
+        agree_or_refuse(tables.has_bonded, [](NbSystem<real> &s) { s.check_bonded(); }, &NbSystem<real>::bonded_fault,
                         "a bonded term of another domain has lost a partner: replace the tables or the state");
     }
 
@@ -1386,9 +1386,9 @@ struct DdImpl : IDd {
         EMDEE_REQUIRE(loaded, EMDEE_ERR_STATE, "emdee_dd_step: call emdee_dd_load first");
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0 && rebuild_every >= 0, EMDEE_ERR_INVALID, "emdee_dd_step: negative argument");
         for (auto &pd : dom)
-            EMDEE_REQUIRE(!pd->sys().bonded_broken, EMDEE_ERR_STATE, "emdee_dd_step: a bonded term has lost a partner; replace the tables or the state");
+            EMDEE_REQUIRE(!pd->sys().bonded_fault.latched, EMDEE_ERR_STATE, "emdee_dd_step: a bonded term has lost a partner; replace the tables or the state");
         for (auto &pd : dom)
-            EMDEE_REQUIRE(!pd->sys().charge_broken, EMDEE_ERR_STATE, "emdee_dd_step: an atom has an id outside the charge table; set the charges again");
+            EMDEE_REQUIRE(!pd->sys().charge_fault.latched, EMDEE_ERR_STATE, "emdee_dd_step: an atom has an id outside the charge table; set the charges again");
         if (nsteps == 0) return;
         // Which kernels a domain steps with is ITS business and may change at any rebuild (brick_active: the densest tile of
         // this domain fits LDS or not; an empty domain launches nothing): the batches, their exchanges and the guard words

@@ -196,26 +196,17 @@ struct MdImpl : IMd {
         if (!lent) { sys.reset_bonded_error(); sys.reset_ewald_error(); }   // (a new state: the bonded terms and the struck pairs get another chance; a decomposition resets its own)
         since_build = 0;
         current_mask = 0;
-        // (rigid molecules set for another atom count stay in force, unused, as charges do; for the same count the table is
+        // (a constraint table set for another atom count stays in force, unused, as charges do; for the same count the table is
         // checked against the new state and the velocities are projected again)
-        if (!lent && sys.has_hbonds()) hbonds_unchecked = true;   // (before either check can refuse)
-        if (!lent && sys.has_rigid()) {
-            sys.reset_settle_error();
-            rigid_unchecked = true;
-            if (!sys.rigid_stale() && ng == 0) {
-                sys.settle_check_state(sys.tables->r_atoms.ptr, sys.tables->r_geom.ptr, sys.tables->r_atoms_h, sys.tables->r_n);
-                sys.settle_velocities();
-                rigid_unchecked = false;
-            }
-        }
-        // (an hbonds table: the same rules)
-        if (!lent && sys.has_hbonds()) {
-            sys.reset_hbond_error();
-            hbonds_unchecked = true;
-            if (!sys.hbonds_stale() && ng == 0) {
-                sys.hbond_check_state(sys.tables->h_atoms.ptr, sys.tables->h_dist.ptr, sys.tables->h_atoms_h, sys.tables->h_n);
-                sys.hbond_velocities();
-                hbonds_unchecked = false;
+        for (int k = 0; k < sys.GROUPS; k++) unchecked[k] = unchecked[k] || (!lent && sys.table(sys.groups[k]).present);   // (every table, before a check can refuse)
+        for (int k = 0; k < sys.GROUPS; k++) {
+            auto &g = sys.groups[k];
+            if (lent || !sys.table(g).present) continue;
+            sys.reset_error(g);
+            if (!sys.stale(g) && ng == 0) {
+                sys.check_state(g);
+                sys.velocities(g);
+                unchecked[k] = false;
             }
         }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
@@ -228,10 +219,9 @@ struct MdImpl : IMd {
     }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
-    // rigid molecules whose table has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
-    bool rigid_unchecked = false;
-    // the same for the clusters of an hbonds table
-    bool hbonds_unchecked = false;
+    // per constraint group (NbSystem::groups): its table has not passed the check against the loaded state (another atom count,
+    // ghosts, or a refusal)
+    bool unchecked[NbSystem<real>::GROUPS] = {false, false};
     // an engine of a decomposition (emdee_dd_engine): its pair tables are the decomposition's, keyed by global id
     bool lent = false;
     // decomposed domains: the global ids of the atoms handed to set_state (caller order, owned atoms and ghosts); they travel
@@ -258,17 +248,14 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
         EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "md_step needs n_ghost == 0; decomposed runs drive kick_drift/forces/kick");
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
-        EMDEE_REQUIRE(!sys.bonded_broken, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
-        EMDEE_REQUIRE(!sys.ewald_broken, EMDEE_ERR_STATE, "md_step: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
-        EMDEE_REQUIRE(!sys.settle_broken, EMDEE_ERR_STATE, "md_step: a rigid molecule had no solution; replace the table or the state");
-        EMDEE_REQUIRE(!sys.has_rigid() || !(sys.rigid_stale() || rigid_unchecked), EMDEE_ERR_STATE, "md_step: rigid molecules set for %lld atoms, "
-                      "the state holds %d (or does not fit them): set them again or clear them (emdee_md_set_rigid3)", (long long)sys.tables->r_limit, sys.n_owned);
-        EMDEE_REQUIRE(!sys.hbond_broken, EMDEE_ERR_STATE, "md_step: an hbonds cluster had no solution; replace the table or the state");
-        EMDEE_REQUIRE(!sys.has_hbonds() || !(sys.hbonds_stale() || hbonds_unchecked), EMDEE_ERR_STATE, "md_step: hbonds clusters set for %lld atoms, "
-                      "the state holds %d (or does not fit them): set them again or clear them (emdee_md_set_hbonds)", (long long)sys.tables->h_limit, sys.n_owned);
+        EMDEE_REQUIRE(!sys.bonded_fault.latched, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
+        EMDEE_REQUIRE(!sys.ewald_fault.latched, EMDEE_ERR_STATE, "md_step: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
+        for (int k = 0; k < sys.GROUPS; k++) {
+            EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_step: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
+            require_fitting_table("md_step", k);
+        }
         if (nsteps == 0) return;
-        if (sys.has_rigid() || sys.has_hbonds()) { step_rigid(nsteps, dt, rebuild_every); return; }   // (coupled or not)
-        if (baro.kind != EMDEE_BAROSTAT_OFF) { step_coupled(nsteps, dt, rebuild_every); return; }
+        if (sys.has_rigid() || sys.has_hbonds() || baro.kind != EMDEE_BAROSTAT_OFF) { step_closed(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
@@ -332,10 +319,16 @@ struct MdImpl : IMd {
                       "and the engine holds rigid molecules: switch the coupling off (emdee_md_set_barostat) or clear the table (emdee_md_set_rigid3) first");
         molecular = on == 1;
     }
-    // the conditions emdee_md_step refuses a table on
-    void require_fitting_table(const char *what) const {
-        EMDEE_REQUIRE(!sys.has_rigid() || !(sys.rigid_stale() || rigid_unchecked), EMDEE_ERR_STATE, "%s: rigid molecules set for %lld atoms, the state "
-                      "holds %d (or does not fit them): set them again or clear them (emdee_md_set_rigid3)", what, (long long)sys.tables->r_limit, sys.n_owned);
+    // what the texts of this file call the groups of NbSystem::groups[k], and the entry that sets their table
+    struct GroupText { const char *one, *many, *setter; };
+    static constexpr GroupText GROUP_TEXT[NbSystem<real>::GROUPS] = {{"a rigid molecule", "rigid molecules", "emdee_md_set_rigid3"},
+                                                                     {"an hbonds cluster", "hbonds clusters", "emdee_md_set_hbonds"}};
+    // the conditions emdee_md_step refuses the table of group k on
+    void require_fitting_table(const char *what, int k) const {
+        const auto &g = sys.groups[k];
+        EMDEE_REQUIRE(!sys.table(g).present || !(sys.stale(g) || unchecked[k]), EMDEE_ERR_STATE, "%s: %s set for %lld atoms, the state "
+                      "holds %d (or does not fit them): set them again or clear them (%s)", what, GROUP_TEXT[k].many,
+                      (long long)sys.table(g).limit, sys.n_owned, GROUP_TEXT[k].setter);
     }
     void scale_box(const double mu[3], double vscale) override {
         use_device(sys.ctx);
@@ -345,7 +338,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!sys.has_rigid() || molecular, EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
                       "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
-        require_fitting_table("scale_box");
+        require_fitting_table("scale_box", sys.RIGID);      // (an hbonds table was refused above)
         sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes)
         since_build = 0;
         current_mask = 0;
@@ -389,68 +382,48 @@ struct MdImpl : IMd {
         baro.seed = seed; baro.step = first_step;
         for (int d = 0; d < 3; d++) { baro.p_ref[d] = p_ref[d]; baro.beta[d] = beta[d]; }
     }
-    // emdee_md_step with coupling on.  Every step closes its own half kick (kick + drift, force pass, kick): the state after s
-    // steps then does not depend on how the s steps were dealt to calls -- step(40), 8 x step(5) and 40 x step(1) are the same
-    // sequence of launches, bit for bit -- and no step is ever queued beyond an event on the box the event is about to change.
-    // (The merged kicks and the guarded run-ahead of the uncoupled loop would have to end at every call as well as at every
-    // event, and v + h + h is not v + 2 h in floating point.)  The step that completes an event's interval evaluates the
-    // energies and virials with its forces when the coupling is isotropic: no pass is added for the pressure.
-    void step_coupled(int nsteps, double dt, int rebuild_every) {
-        if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
-        for (int s = 0; s < nsteps; s++) {
-            const bool event = (baro.step + 1) % (unsigned long long)baro.every == 0;
-            sys.kick_drift(0.5 * dt, dt);
-            since_build++;
-            const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
-            if (rb) { sys.resort(); since_build = 0; }
-            const int mask = (event && baro.coupling == EMDEE_COUPLE_ISOTROPIC) ? 7 : EMDEE_FORCES;
-            sys.compute_forces(mask);
-            sys.kick(0.5 * dt);
-            current_mask = mask;
-            baro.step++;
-            if (event) couple(dt);
-        }
-        EMDEE_HIP_CHECK(hipGetLastError());
-        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
-    }
-    // emdee_md_step with rigid molecules (emdee_md_set_rigid3) or an hbonds table (emdee_md_set_hbonds; every stage runs for whichever
-    // tables exist, SETTLE / RATTLE on the molecules and M-SHAKE / RATTLE on the clusters, whose atoms are disjoint):
-    // step_coupled's loop shape -- every step closes its own half kick, so
-    // the state after s steps does not depend on how they were dealt to calls -- with the three constraint stages around the
-    // unchanged kernels: (a) the constrained atoms' positions are remembered, (c) SETTLE on the drifted records, (e) the bond
-    // components of the relative velocities are removed.  Stage (c) re-tests its atoms against the rebuild threshold, so the
-    // displacement word is read after it; a re-sort between (c) and (e) is harmless (the stages find atoms through inv_perm).
-    // The order of a step: (a) gather, (b) kick + drift, (c) SETTLE, [re-sort], (d) force pass and kick, (e) RATTLE; with pressure
-    // coupling on (emdee_md_set_molecular_scaling), after stage (e) of the step that completes an interval, (f) the event: the
-    // molecular pressure from that step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale,
-    // which rebuilds the list and evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.
-    void step_rigid(int nsteps, double dt, int rebuild_every) {
+    // emdee_md_step with coupling on, with rigid molecules (emdee_md_set_rigid3) or with an hbonds table (emdee_md_set_hbonds).  Every
+    // step closes its own half kick (kick + drift, force pass, kick): the state after s steps then does not depend on how the s
+    // steps were dealt to calls -- step(40), 8 x step(5) and 40 x step(1) are the same sequence of launches, bit for bit -- and no
+    // step is ever queued beyond an event on the box the event is about to change.  (The merged kicks and the guarded run-ahead
+    // of the uncoupled loop would have to end at every call as well as at every event, and v + h + h is not v + 2 h in floating
+    // point.)
+    // Around the unchanged kernels, the three constraint stages of every table that exists (NbSystem::groups: SETTLE / RATTLE on
+    // the molecules, then M-SHAKE / RATTLE on the clusters, whose atoms are disjoint): (a) the constrained atoms' positions are
+    // remembered, (c) the distances are restored on the drifted records, (e) the bond components of the relative velocities are
+    // removed.  Stage (c) re-tests its atoms against the rebuild threshold, so the displacement word is read after it; a re-sort
+    // between (c) and (e) is harmless (the stages find atoms through inv_perm).
+    // The order of a step: (a) gather, (b) kick + drift, (c) positions, [re-sort], (d) force pass and kick, (e) velocities; with
+    // pressure coupling on, after the step that completes an interval, (f) the event.  Without a table the event's step evaluates
+    // the energies and virials with its forces when the coupling is isotropic: no pass is added for the pressure.  With rigid
+    // molecules (emdee_md_set_molecular_scaling) the event takes the molecular pressure from that step's forces F(x) and its
+    // stage-(e) velocities (one tensor pass), then the molecular scale, which rebuilds the list and evaluates the forces on the
+    // new box; a fixed rebuild cadence restarts from the event.
+    void step_closed(int nsteps, double dt, int rebuild_every) {
         const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF, rigid = sys.has_rigid(), hbonds = sys.has_hbonds();
-        EMDEE_REQUIRE(!coupled || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
+        EMDEE_REQUIRE(!coupled || !(rigid || hbonds) || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
         EMDEE_REQUIRE(!coupled || !hbonds, EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
+        const bool with_sums = !rigid && !hbonds && baro.coupling == EMDEE_COUPLE_ISOTROPIC;
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
-            if (rigid) sys.settle_gather();
-            if (hbonds) sys.hbond_gather();
+            for (auto &g : sys.groups) if (sys.table(g).present) sys.gather(g);
             sys.kick_drift(0.5 * dt, dt);
-            if (rigid) sys.settle_positions(dt);
-            if (hbonds) sys.hbond_positions(dt);
+            for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, dt);
             since_build++;
             const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
             if (rb) { sys.resort(); since_build = 0; }
-            sys.compute_forces(EMDEE_FORCES);
+            const int mask = (event && with_sums) ? 7 : EMDEE_FORCES;
+            sys.compute_forces(mask);
             sys.kick(0.5 * dt);
-            if (rigid) sys.settle_velocities();
-            if (hbonds) sys.hbond_velocities();
-            current_mask = EMDEE_FORCES;
+            for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
+            current_mask = mask;
             if (coupled) baro.step++;
             if (event) couple(dt);
         }
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
-        sys.check_settle();                                  // (one read-back per call)
-        sys.check_hbonds();                                  // (one more with an hbonds table)
+        for (auto &g : sys.groups) sys.check(g);             // (one read-back per call and table)
     }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
@@ -600,7 +573,7 @@ struct MdImpl : IMd {
                       "molecular sums are written for three-site molecules and would keep the clusters' constraint forces; clear the table first");
         if (!sys.has_rigid()) { pressure_tensor(out); return; }
         EMDEE_REQUIRE(!lent && n_ghost == 0, EMDEE_ERR_STATE, "molecular_pressure_tensor: rigid molecules on an integrator with ghosts or a domain's");
-        require_fitting_table("molecular_pressure_tensor");
+        require_fitting_table("molecular_pressure_tensor", sys.RIGID);   // (an hbonds table was refused above)
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         tensor_pass();
         sys.check_bonded();
@@ -690,32 +663,29 @@ struct MdImpl : IMd {
             if (n == 0) sys.ewald.clear();                   // (no charges, no Ewald sum: the next set_coulomb starts with the reaction field)
         });
     }
-    // emdee_md_set_rigid3: all or nothing -- the candidate table is checked on the host and then against the loaded state before it
-    // replaces the one in force; no atom moves, the velocities are projected once (stage (e)).  The neighbour list and the forces
-    // do not depend on the table: nothing is rebuilt.
+    // emdee_md_set_rigid3, emdee_md_set_hbonds: all or nothing -- the candidate table is checked on the host and then against the
+    // loaded state before it replaces the one in force; no atom moves, the velocities are projected once (stage (e)).  The
+    // neighbour list and the forces do not depend on the table: nothing is rebuilt.  set(check): the Topology setter of group k.
+    template <class Set>
+    void set_groups(int k, const char *what, Set &&set) {
+        auto &g = sys.groups[k];
+        install(what, "a decomposed run has none", [&] {
+            set([&](const int *a, const double *d, const std::vector<int32_t> &h, int n) { sys.check_state(g, a, d, h, n); });
+            sys.reset_error(g);
+            unchecked[k] = false;
+            if (sys.table(g).present) sys.velocities(g);
+        }, false);
+    }
     void set_rigid3(const int32_t *atoms, const double *geom, int32_t n_mol) override {
         EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF || molecular, EMDEE_ERR_STATE, "set_rigid3: pressure coupling is on (emdee_md_set_barostat): the pressure "
                       "of an engine with rigid molecules lacks the constraint virial; switch the coupling off first (or couple to the molecular "
                       "pressure: emdee_md_set_molecular_scaling)");
-        install("rigid molecules", "a decomposed run has none", [&] {
-            sys.own_tables.set_rigid3(atoms, geom, n_mol, sys.n_owned, sys.stream(),
-                                      [&](const int *a, const double *g, const std::vector<int32_t> &h, int n) { sys.settle_check_state(a, g, h, n); });
-            sys.reset_settle_error();
-            rigid_unchecked = false;
-            if (sys.has_rigid()) sys.settle_velocities();
-        }, false);
+        set_groups(sys.RIGID, "rigid molecules", [&](auto &&check) { sys.own_tables.set_rigid3(atoms, geom, n_mol, sys.n_owned, sys.stream(), check); });
     }
-    // emdee_md_set_hbonds: set_rigid3's contract for the star clusters of bonds to hydrogen
     void set_hbonds(const int32_t *atoms, const double *dist, int32_t n_clusters) override {
         EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF, EMDEE_ERR_STATE, "set_hbonds: pressure coupling is on (emdee_md_set_barostat): the pressure of "
                       "an engine with an hbonds table lacks the clusters' constraint virial; switch the coupling off first");
-        install("hbonds clusters", "a decomposed run has none", [&] {
-            sys.own_tables.set_hbonds(atoms, dist, n_clusters, sys.n_owned, sys.stream(),
-                                      [&](const int *a, const double *d, const std::vector<int32_t> &h, int n) { sys.hbond_check_state(a, d, h, n); });
-            sys.reset_hbond_error();
-            hbonds_unchecked = false;
-            if (sys.has_hbonds()) sys.hbond_velocities();
-        }, false);
+        set_groups(sys.HBONDS, "hbonds clusters", [&](auto &&check) { sys.own_tables.set_hbonds(atoms, dist, n_clusters, sys.n_owned, sys.stream(), check); });
     }
     // emdee_md_set_ewald: all or nothing -- every refusal comes before the setting changes
     void set_ewald(double alpha, const int32_t *kmax) override {

@@ -41,6 +41,13 @@ static inline void refuse_experiment_switches() {
 // T_HBONDS: the three constraint stages of an engine with an hbonds table (shake.hpp)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
                T_MOLECULAR = 9, T_HBONDS = 10, T_COUNT = 11 };
+// The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
+// common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
+// W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
+// (k_ewald_struck); W_SETTLE / W_HBONDS, a molecule / a cluster that moved too far for a solution (k_constraint_positions).
+// Words of the table checks (k_constraint_check), cleared and read by every check: W_RIGID_MASS, W_RIGID_DIST; W_HBONDS_DIST.
+enum FlagWord { W_BONDED = 16, W_CHARGES = 17, W_EWALD = 18, W_SETTLE = 20, W_RIGID_MASS = 21, W_RIGID_DIST = 22, W_HBONDS = 23,
+                W_HBONDS_DIST = 24 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -446,9 +453,9 @@ struct NbSystem {
             ScaleBox s{};
             for (int d = 0; d < 3; d++) { s.lo[d] = lo[d]; s.mu[d] = mu[d]; }
             const int scale_vel = vscale != 1.0 ? 1 : 0;
-            if (molecular && tables->r_n > 0) {
+            if (molecular && tables->rigid.n > 0) {
                 Timed t(this, T_MOLECULAR);
-                hipLaunchKernelGGL((k_molecule_scale<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args(), s,
+                hipLaunchKernelGGL((k_molecule_scale<real>), dim3(blocks_for(tables->rigid.n, 256)), dim3(256), 0, stream(), settle_args(), s,
                                    vscale, scale_vel);
             }
             hipLaunchKernelGGL((k_cell_state_scale<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, pitch, rec.ptr,
@@ -1094,25 +1101,19 @@ struct NbSystem {
     bool has_post() const { return has_14() || has_bonded() || has_charges(); }
     // rows the filter visits right after every build: excluded pairs are struck, 1-4 and bonded partners' slots recorded
     bool filters_rows() const { return has_excl() || has_bonded(); }
-    // a bonded term whose partner was missing from the rows (flags[16], raised by k_bonded): the engine refuses to step until
-    // the tables or the state are replaced
-    bool bonded_broken = false;
-    void reset_bonded_error() {
-        bonded_broken = false;
-        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 16, 0, sizeof(int), stream()));
-    }
+    // a bonded term whose partner was missing from the rows (raised by k_bonded): the engine refuses to step until the tables or
+    // the state are replaced
+    FaultWord bonded_fault{W_BONDED};
+    void reset_bonded_error() { bonded_fault.reset(flags.ptr, stream()); }
     // blocking: EMDEE_ERR_STATE naming the term if k_bonded has met a missing partner since the last reset
     void check_bonded() {
         check_ewald();                                       // (the other term that needs a partner in the rows)
         if (!has_bonded() || !flags.ptr) return;
-        int32_t word = 0;
-        if (!bonded_broken) read_back_words(ctx, stream(), flags.ptr + 16, 1, &word);
-        if (word != 0) {
-            bonded_broken = true;
+        if (const int32_t word = bonded_fault.poll(ctx, flags.ptr, stream())) {
             set_error("%s", topo::lost_partner_message(tables->b_atoms, (int64_t)word - 1).c_str());
             throw Failure{EMDEE_ERR_STATE};
         }
-        EMDEE_REQUIRE(!bonded_broken, EMDEE_ERR_STATE, "a bonded term has lost a partner (reported before): replace the tables or the state");
+        EMDEE_REQUIRE(!bonded_fault.latched, EMDEE_ERR_STATE, "a bonded term has lost a partner (reported before): replace the tables or the state");
     }
     // emdee_nbr_* / emdee_md_set_exclusions, _set_pairs14: replaces one of the engine's own tables (n = 0 clears it), all or nothing
     void set_pair_tables(int n_atoms, const int32_t *pairs_dev, int n_pairs, bool one_four, double scale) {
@@ -1159,7 +1160,7 @@ struct NbSystem {
     // no charges), unchanged in between (ghost identities are fixed between rebuilds).
     DevBuf<real> qp;
     bool q_valid = false;
-    bool charge_broken = false;                              // a key without a charge (flags[17]): the engine refuses to step
+    FaultWord charge_fault{W_CHARGES};                       // a key without a charge: the engine refuses to step
     bool has_charges() const { return tables->has_charges; }
     // an undivided engine whose state no longer has the atom count the charges were set for
     bool charges_stale() const { return has_charges() && tables == &own_tables && (tables->q_n != n_owned || id_gaps); }
@@ -1178,26 +1179,23 @@ struct NbSystem {
         if (!has_charges()) return;
         EMDEE_REQUIRE(!charges_stale(), EMDEE_ERR_STATE, "charges set for %lld atoms, the state holds %d: set them again or clear them "
                       "(emdee_md_set_coulomb)", (long long)tables->q_n, n_owned);
-        EMDEE_REQUIRE(!charge_broken, EMDEE_ERR_STATE, "an atom has an id outside the charge table: set the charges again");
+        EMDEE_REQUIRE(!charge_fault.latched, EMDEE_ERR_STATE, "an atom has an id outside the charge table: set the charges again");
         if (q_valid || n_total == 0) return;
         if (tables != &own_tables) EMDEE_REQUIRE(use_tags, EMDEE_ERR_STATE, "charges over global ids: the state carries no tags");
         qp.ensure(std::max<size_t>((size_t)n_total, capacity) + 1);
         hipLaunchKernelGGL((k_fill_charges<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, perm.ptr,
-                           use_tags ? tag.ptr : nullptr, tables->q_tab.ptr, (long long)tables->q_n, qp.ptr, flags.ptr + 17);
+                           use_tags ? tag.ptr : nullptr, tables->q_tab.ptr, (long long)tables->q_n, qp.ptr, flags.ptr + W_CHARGES);
         q_valid = true;
     }
     void reset_charge_error() {
-        charge_broken = false;
         q_valid = false;
-        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 17, 0, sizeof(int), stream()));
+        charge_fault.reset(flags.ptr, stream());
     }
     // blocking: EMDEE_ERR_STATE if a fill has met a key outside the charge table since the last reset
     void check_charges() {
         if (!has_charges() || !flags.ptr) return;
-        int32_t word = 0;
-        if (!charge_broken) read_back_words(ctx, stream(), flags.ptr + 17, 1, &word);
-        if (word != 0) charge_broken = true;
-        EMDEE_REQUIRE(!charge_broken, EMDEE_ERR_STATE, "an atom has an id outside the charge table (emdee_dd_set_coulomb: n_ids too "
+        charge_fault.poll(ctx, flags.ptr, stream());
+        EMDEE_REQUIRE(!charge_fault.latched, EMDEE_ERR_STATE, "an atom has an id outside the charge table (emdee_dd_set_coulomb: n_ids too "
                       "small); set the charges again");
     }
 
@@ -1229,7 +1227,7 @@ struct NbSystem {
         auto kernel = (bitmask & EMDEE_TENSOR) ? k_bonded<real, true> : k_bonded<real, false>;
         hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
                            pair_keys(), bonded_keys(), tables->template bonded_params<real>(), grid, bitmask, frc.ptr, en.ptr,
-                           vir.ptr, vt.ptr, flags.ptr + 16);
+                           vir.ptr, vt.ptr, flags.ptr + W_BONDED);
     }
     // ---------------------------------------------------------------- Ewald summation (emdee_md_set_ewald)
     // With ewald.alpha > 0 a charged engine's pair loops take the erfc-screened terms (the EMDEE_EWALD instances), the row filter
@@ -1238,23 +1236,17 @@ struct NbSystem {
     EwaldRecip<real> ewald;
     DevBuf<int> slotsx;                                      // per entry of the struck CSR of an owned atom: the partner's cell-order slot
     bool has_ewald() const { return ewald.on() && has_charges(); }
-    // a struck pair whose partner was missing from the rows (flags[18], raised by k_ewald_struck): as bonded_broken
-    bool ewald_broken = false;
-    void reset_ewald_error() {
-        ewald_broken = false;
-        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 18, 0, sizeof(int), stream()));
-    }
+    // a struck pair whose partner was missing from the rows (raised by k_ewald_struck): as bonded_fault
+    FaultWord ewald_fault{W_EWALD};
+    void reset_ewald_error() { ewald_fault.reset(flags.ptr, stream()); }
     // blocking: EMDEE_ERR_STATE naming the pair if k_ewald_struck has met a missing partner since the last reset
     void check_ewald() {
         if (!has_ewald() || !has_excl() || !flags.ptr) return;
-        int32_t word = 0;
-        if (!ewald_broken) read_back_words(ctx, stream(), flags.ptr + 18, 1, &word);
-        if (word != 0) {
-            ewald_broken = true;
+        if (const int32_t word = ewald_fault.poll(ctx, flags.ptr, stream())) {
             set_error("%s", topo::lost_pair_message(tables->excl, tables->p14, (int64_t)word - 1).c_str());
             throw Failure{EMDEE_ERR_STATE};
         }
-        EMDEE_REQUIRE(!ewald_broken, EMDEE_ERR_STATE, "Ewald: an excluded or 1-4 pair spans more than rc + skin (reported before): replace the tables or the state");
+        EMDEE_REQUIRE(!ewald_fault.latched, EMDEE_ERR_STATE, "Ewald: an excluded or 1-4 pair spans more than rc + skin (reported before): replace the tables or the state");
     }
     void add_ewald(int bitmask) {
         if (!has_ewald() || n_total == 0) return;
@@ -1266,133 +1258,108 @@ struct NbSystem {
             auto kernel = (bitmask & EMDEE_TENSOR) ? k_ewald_struck<real, true> : k_ewald_struck<real, false>;
             hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
                                pair_keys(), tables->x_start.ptr, grid, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr, charge_args(),
-                               flags.ptr + 18);
+                               flags.ptr + W_EWALD);
         }
         Timed t(this, T_EWALD);
         ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, tables->q_abs, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
     }
-    // ---------------------------------------------------------------- rigid three-site molecules (Topology::set_rigid3, settle.hpp)
-    // The three stages MdImpl::step_rigid puts around the unchanged kick + drift, force pass and kick: one thread per molecule, no
-    // atomics on the state, fp64 on unwrapped differences in both precisions.  Undivided engines only.
-    DevBuf<double> settle_x0;                                // stage (a): 9 doubles per molecule, table order
-    bool has_rigid() const { return tables->has_rigid; }
-    // an engine whose state no longer has the atom count the table was set for: it refuses to step (as with charges)
-    bool rigid_stale() const { return has_rigid() && (tables->r_limit != n_owned || id_gaps); }
-    // a molecule that moved too far for a rigid solution (flags[20], raised by k_settle_positions): as bonded_broken
-    bool settle_broken = false;
-    void reset_settle_error() {
-        settle_broken = false;
-        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 20, 0, sizeof(int), stream()));
+    // ---------------------------------------------------------------- constraint groups (Topology::set_rigid3, set_hbonds)
+    // The three stages MdImpl::step_closed puts around the unchanged kick + drift, force pass and kick, and the check of a table
+    // against a loaded state: one thread per group, no atomics on the state, fp64 on unwrapped differences in both precisions.
+    // Undivided engines only.  One ConstraintGroup per table says what differs -- the table, the policy's kernels (settle.hpp
+    // Triangle: SETTLE / RATTLE on rigid three-site molecules; shake.hpp Star: M-SHAKE / RATTLE on bonds to hydrogen), the timer,
+    // the words and the texts -- and the functions below serve both.  The atoms of the two tables are disjoint (topology.hpp), so
+    // the order of the two kernels within a stage cannot matter.
+    struct ConstraintGroup {
+        Topology::GroupTable Topology::*table;
+        int sites;                                           // x0 holds 3 * sites doubles per group
+        int timer;
+        FaultWord fault;                                     // a group that moved too far for a solution (raised by stage (c)): as bonded_fault
+        int check_word, check_words;                         // the words of the table check
+        std::string (*message)(const std::vector<int32_t> &, int64_t, const char *);
+        const char *no_solution, *reported_before, *check_text[2];
+        void (*k_gather)(ConstraintArgs<real>, double *);
+        void (*k_positions)(ConstraintArgs<real>, const double *, double, const real *, real, int *, int *);
+        void (*k_velocities)(ConstraintArgs<real>);
+        void (*k_check)(ConstraintArgs<real>, int *);
+        DevBuf<double> x0;                                   // stage (a): the sites of every group, table order
+    };
+    template <class G>
+    static ConstraintGroup group_of(Topology::GroupTable Topology::*table, int timer, int fault, int check_word, int check_words,
+                                    std::string (*message)(const std::vector<int32_t> &, int64_t, const char *), const char *no_solution,
+                                    const char *reported_before, const char *check0, const char *check1) {
+        return ConstraintGroup{table, G::SITES, timer, FaultWord{fault}, check_word, check_words, message, no_solution, reported_before,
+                               {check0, check1}, k_constraint_gather<real, G>, k_constraint_positions<real, G>,
+                               k_constraint_velocities<real, G>, k_constraint_check<real, G>, {}};
     }
-    void check_settle() {
-        if (!has_rigid() || !flags.ptr) return;
-        int32_t word = 0;
-        if (!settle_broken) read_back_words(ctx, stream(), flags.ptr + 20, 1, &word);
-        if (word != 0) {
-            settle_broken = true;
-            set_error("%s", topo::rigid3_message(tables->r_atoms_h, (int64_t)word - 1, "the step moved its atoms too far for a rigid "
-                      "solution (a negative radicand in SETTLE); the molecule was left as it is: replace the table or the state").c_str());
+    enum { RIGID = 0, HBONDS = 1, GROUPS = 2 };
+    ConstraintGroup groups[GROUPS] = {
+        group_of<Triangle>(&Topology::rigid, T_SETTLE, W_SETTLE, W_RIGID_MASS, 2, topo::rigid3_message,
+                           "the step moved its atoms too far for a rigid solution (a negative radicand in SETTLE); the molecule was left as it "
+                           "is: replace the table or the state",
+                           "a rigid molecule had no solution (reported before): replace the table or the state",
+                           "the two legs have different masses",
+                           "the loaded positions miss a distance of the table by more than 1e-3 (relative): a wrong topology, not rounding"),
+        group_of<Star>(&Topology::hbonds, T_HBONDS, W_HBONDS, W_HBONDS_DIST, 1, topo::hbonds_message,
+                       "the step moved its atoms too far for the bonds to be restored (no solution of the SHAKE equations within the "
+                       "iteration cap); the cluster was left as it is: replace the table or the state",
+                       "an hbonds cluster had no solution (reported before): replace the table or the state",
+                       "the loaded positions miss a distance of the table by more than 1e-3 (relative): a wrong topology, not rounding",
+                       nullptr)};
+    const Topology::GroupTable &table(const ConstraintGroup &g) const { return tables->*g.table; }
+    bool has_rigid() const { return tables->rigid.present; }
+    bool has_hbonds() const { return tables->hbonds.present; }
+    // an engine whose state no longer has the atom count the table was set for: it refuses to step (as with charges)
+    bool stale(const ConstraintGroup &g) const { return table(g).present && (table(g).limit != n_owned || id_gaps); }
+    void reset_error(ConstraintGroup &g) { g.fault.reset(flags.ptr, stream()); }
+    // blocking, one read-back: EMDEE_ERR_STATE naming the group if stage (c) has met one without a solution since the last reset
+    void check(ConstraintGroup &g) {
+        if (!table(g).present || !flags.ptr) return;
+        if (const int32_t word = g.fault.poll(ctx, flags.ptr, stream())) {
+            set_error("%s", g.message(table(g).atoms_h, (int64_t)word - 1, g.no_solution).c_str());
             throw Failure{EMDEE_ERR_STATE};
         }
-        EMDEE_REQUIRE(!settle_broken, EMDEE_ERR_STATE, "a rigid molecule had no solution (reported before): replace the table or the state");
+        EMDEE_REQUIRE(!g.fault.latched, EMDEE_ERR_STATE, "%s", g.reported_before);
     }
-    SettleArgs<real> settle_args(const int *atoms, const double *geom, int n_mol) const {
-        SettleArgs<real> a{};
-        a.n_mol = n_mol; a.atoms = atoms; a.geom = geom; a.inv_perm = inv_perm.ptr; a.rec = rec.ptr; a.vel = vel.ptr;
+    ConstraintArgs<real> constraint_args(const int *atoms, const double *geom, int n) const {
+        ConstraintArgs<real> a{};
+        a.n = n; a.atoms = atoms; a.geom = geom; a.inv_perm = inv_perm.ptr; a.rec = rec.ptr; a.vel = vel.ptr;
         a.inv_mass = with_mass ? im.ptr : nullptr; a.pitch = pitch;
         a.rel = rel_grid(rel_now, cell_sorted.ptr);
         for (int d = 0; d < 3; d++) { a.box.len[d] = len[d]; a.box.per[d] = per[d]; }
         return a;
     }
-    SettleArgs<real> settle_args() const { return settle_args(tables->r_atoms.ptr, tables->r_geom.ptr, tables->r_n); }
-    void settle_gather() {
-        Timed t(this, T_SETTLE);
-        settle_x0.ensure((size_t)9 * tables->r_n + 1);
-        hipLaunchKernelGGL((k_settle_gather<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args(), settle_x0.ptr);
+    ConstraintArgs<real> constraint_args(const ConstraintGroup &g) const { return constraint_args(table(g).atoms.ptr, table(g).geom.ptr, table(g).n); }
+    ConstraintArgs<real> settle_args() const { return constraint_args(groups[RIGID]); }   // (the molecular sums and the molecular scale)
+    void gather(ConstraintGroup &g) {
+        Timed t(this, g.timer);
+        g.x0.ensure((size_t)3 * g.sites * table(g).n + 1);
+        hipLaunchKernelGGL(g.k_gather, dim3(blocks_for(table(g).n, 256)), dim3(256), 0, stream(), constraint_args(g), g.x0.ptr);
     }
-    void settle_positions(double dt) {
-        Timed t(this, T_SETTLE);
+    void positions(ConstraintGroup &g, double dt) {
+        Timed t(this, g.timer);
         const real thr = (real)(0.5 * skin);                 // (kick_drift's threshold)
-        hipLaunchKernelGGL((k_settle_positions<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args(),
-                           (const double *)settle_x0.ptr, dt > 0.0 ? 1.0 / dt : 0.0, (const real *)xb.ptr, thr * thr, flags.ptr + 1, flags.ptr + 20);
+        hipLaunchKernelGGL(g.k_positions, dim3(blocks_for(table(g).n, 256)), dim3(256), 0, stream(), constraint_args(g), (const double *)g.x0.ptr,
+                           dt > 0.0 ? 1.0 / dt : 0.0, (const real *)xb.ptr, thr * thr, flags.ptr + 1, flags.ptr + g.fault.index);
     }
-    void settle_velocities() {
-        Timed t(this, T_SETTLE);
-        hipLaunchKernelGGL((k_settle_velocities<real>), dim3(blocks_for(tables->r_n, 256)), dim3(256), 0, stream(), settle_args());
+    void velocities(ConstraintGroup &g) {
+        Timed t(this, g.timer);
+        hipLaunchKernelGGL(g.k_velocities, dim3(blocks_for(table(g).n, 256)), dim3(256), 0, stream(), constraint_args(g));
     }
-    // a table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the molecule whose
-    // legs have different masses or whose atoms miss a distance by more than 1e-3 relative; one launch, one read-back
-    void settle_check_state(const int *atoms, const double *geom, const std::vector<int32_t> &atoms_h, int n_mol) {
-        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 21, 0, 2 * sizeof(int), stream()));
-        hipLaunchKernelGGL((k_settle_check<real>), dim3(blocks_for(n_mol, 256)), dim3(256), 0, stream(), settle_args(atoms, geom, n_mol), flags.ptr + 21);
+    // a table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the group that fails
+    // the policy's test (settle.hpp Triangle::check, shake.hpp Star::check); one launch, one read-back
+    void check_state(ConstraintGroup &g, const int *atoms, const double *geom, const std::vector<int32_t> &atoms_h, int n) {
+        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + g.check_word, 0, g.check_words * sizeof(int), stream()));
+        hipLaunchKernelGGL(g.k_check, dim3(blocks_for(n, 256)), dim3(256), 0, stream(), constraint_args(atoms, geom, n), flags.ptr + g.check_word);
         int32_t words[2] = {0, 0};
-        read_back_words(ctx, stream(), flags.ptr + 21, 2, words);
-        if (words[0] != 0) {
-            set_error("%s", topo::rigid3_message(atoms_h, (int64_t)words[0] - 1, "the two legs have different masses").c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
-        if (words[1] != 0) {
-            set_error("%s", topo::rigid3_message(atoms_h, (int64_t)words[1] - 1, "the loaded positions miss a distance of the table by more "
-                      "than 1e-3 (relative): a wrong topology, not rounding").c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
+        read_back_words(ctx, stream(), flags.ptr + g.check_word, g.check_words, words);
+        for (int w = 0; w < g.check_words; w++)
+            if (words[w] != 0) {
+                set_error("%s", g.message(atoms_h, (int64_t)words[w] - 1, g.check_text[w]).c_str());
+                throw Failure{EMDEE_ERR_STATE};
+            }
     }
-
-    // ---------------------------------------------------------------- bonds to hydrogen (Topology::set_hbonds, shake.hpp)
-    // The same three stages for the star clusters of the hbonds table: one thread per cluster, no atomics on the state.  The
-    // atoms of the two tables are disjoint (topology.hpp), so the order of the two kernels within a stage cannot matter.
-    DevBuf<double> hbond_x0;                                 // stage (a): 12 doubles per cluster, table order
-    bool has_hbonds() const { return tables->has_hbonds; }
-    bool hbonds_stale() const { return has_hbonds() && (tables->h_limit != n_owned || id_gaps); }
-    // a cluster that moved too far for a solution (flags[23], raised by k_hbond_positions): as settle_broken
-    bool hbond_broken = false;
-    void reset_hbond_error() {
-        hbond_broken = false;
-        if (flags.ptr) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 23, 0, sizeof(int), stream()));
-    }
-    void check_hbonds() {
-        if (!has_hbonds() || !flags.ptr) return;
-        int32_t word = 0;
-        if (!hbond_broken) read_back_words(ctx, stream(), flags.ptr + 23, 1, &word);
-        if (word != 0) {
-            hbond_broken = true;
-            set_error("%s", topo::hbonds_message(tables->h_atoms_h, (int64_t)word - 1, "the step moved its atoms too far for the bonds to be "
-                      "restored (no solution of the SHAKE equations within the iteration cap); the cluster was left as it is: replace the "
-                      "table or the state").c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
-        EMDEE_REQUIRE(!hbond_broken, EMDEE_ERR_STATE, "an hbonds cluster had no solution (reported before): replace the table or the state");
-    }
-    SettleArgs<real> hbond_args() const { return settle_args(tables->h_atoms.ptr, tables->h_dist.ptr, tables->h_n); }
-    void hbond_gather() {
-        Timed t(this, T_HBONDS);
-        hbond_x0.ensure((size_t)12 * tables->h_n + 1);
-        hipLaunchKernelGGL((k_hbond_gather<real>), dim3(blocks_for(tables->h_n, 256)), dim3(256), 0, stream(), hbond_args(), hbond_x0.ptr);
-    }
-    void hbond_positions(double dt) {
-        Timed t(this, T_HBONDS);
-        const real thr = (real)(0.5 * skin);                 // (kick_drift's threshold)
-        hipLaunchKernelGGL((k_hbond_positions<real>), dim3(blocks_for(tables->h_n, 256)), dim3(256), 0, stream(), hbond_args(),
-                           (const double *)hbond_x0.ptr, dt > 0.0 ? 1.0 / dt : 0.0, (const real *)xb.ptr, thr * thr, flags.ptr + 1, flags.ptr + 23);
-    }
-    void hbond_velocities() {
-        Timed t(this, T_HBONDS);
-        hipLaunchKernelGGL((k_hbond_velocities<real>), dim3(blocks_for(tables->h_n, 256)), dim3(256), 0, stream(), hbond_args());
-    }
-    // a table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the cluster whose atoms
-    // miss a distance by more than 1e-3 relative; one launch, one read-back
-    void hbond_check_state(const int *atoms, const double *dist, const std::vector<int32_t> &atoms_h, int n_clusters) {
-        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 24, 0, sizeof(int), stream()));
-        hipLaunchKernelGGL((k_hbond_check<real>), dim3(blocks_for(n_clusters, 256)), dim3(256), 0, stream(), settle_args(atoms, dist, n_clusters),
-                           flags.ptr + 24);
-        int32_t word = 0;
-        read_back_words(ctx, stream(), flags.ptr + 24, 1, &word);
-        if (word != 0) {
-            set_error("%s", topo::hbonds_message(atoms_h, (int64_t)word - 1, "the loaded positions miss a distance of the table by more "
-                      "than 1e-3 (relative): a wrong topology, not rounding").c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
-    }
+    void check_state(ConstraintGroup &g) { check_state(g, table(g).atoms.ptr, table(g).geom.ptr, table(g).atoms_h, table(g).n); }
 
     void add_post_terms(int bitmask) {
         add_pairs14(bitmask);
@@ -1709,7 +1676,7 @@ struct NbSystem {
     void molecular_tensor_sums(double out[TENSOR_SUMS]) {
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
         if (n_total == 0) return;
-        const int n_mol = has_rigid() ? tables->r_n : 0;
+        const int n_mol = has_rigid() ? tables->rigid.n : 0;
         if (n_mol == 0) { tensor_sums(out); return; }
         int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
         tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);

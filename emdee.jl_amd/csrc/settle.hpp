@@ -1,7 +1,8 @@
 // settle.hpp -- rigid three-site molecules (emdee_md_set_rigid3): the closed-form position stage (SETTLE: Miyamoto & Kollman,
-// J. Comput. Chem. 13, 952 (1992)) and the velocity stage (RATTLE for a triangle: one 3 x 3 linear solve), and the kernels that
-// apply them, one thread per molecule.  The two functions at the top are plain C++ on fixed-size arrays of doubles: a stand-alone
-// host program tests them with the host compiler (tests/c/settle_host.cpp); the kernels below them need HIP.
+// J. Comput. Chem. 13, 952 (1992)) and the velocity stage (RATTLE for a triangle: one 3 x 3 linear solve), the group policy
+// (Triangle) that hands them to the constraint kernels, and those kernels, written here once for every kind of group (shake.hpp
+// adds the Star).  The two functions at the top are plain C++ on fixed-size arrays of doubles: a stand-alone host program tests
+// them with the host compiler (tests/c/settle_host.cpp); the kernels below them need HIP.
 // Sites: 0 = apex, 1 and 2 = the legs a and b, |0 - 1| = |0 - 2| = d_leg, |1 - 2| = d_base; the legs have one mass.
 #pragma once
 
@@ -178,11 +179,12 @@ struct SettleBox {
     double len[3];
     int per[3];
 };
-// The table (Topology, topology_dev.hpp) and where the atoms are: atoms = {apex, a, b} caller ids per molecule, geom = {d_leg,
-// d_base}; an atom's slot comes from inv_perm, so nothing here depends on the sort and a re-sort between two stages is harmless.
+// A constraint table (Topology, topology_dev.hpp) and where the atoms are: n groups, atoms = the caller ids of every group's
+// sites, geom = its distances, both as the group policy lays them out (Triangle below, Star in shake.hpp); an atom's slot comes
+// from inv_perm, so nothing here depends on the sort and a re-sort between two stages is harmless.
 template <typename real>
-struct SettleArgs {
-    int n_mol;
+struct ConstraintArgs {
+    int n;
     const int *atoms;
     const double *geom;
     const int *inv_perm;
@@ -198,7 +200,7 @@ namespace settle_detail {
 // the position a record stands for, in double: fp32 cell-relative records get their cell's origin (no box lengths: a record is
 // continuous between two sorts, wrapped or not)
 template <typename real>
-__device__ __forceinline__ void site(const SettleArgs<real> &a, int p, double (&x)[3]) {
+__device__ __forceinline__ void site(const ConstraintArgs<real> &a, int p, double (&x)[3]) {
     const Rec<real> r = a.rec[p];
     x[0] = (double)r.x; x[1] = (double)r.y; x[2] = (double)r.z;
     if (sizeof(real) == 4 && a.rel.on) {
@@ -208,75 +210,122 @@ __device__ __forceinline__ void site(const SettleArgs<real> &a, int p, double (&
     }
 }
 __device__ __forceinline__ double image(double d, double len, int periodic) { return periodic ? d - len * rint(d / len) : d; }
-// the three sites as the apex at the origin and the minimum images of the legs from it
-__device__ __forceinline__ void unwrap(const SettleBox &b, const double (&s)[3][3], double (&x)[3][3]) {
+// the sites of a group as site 0 at the origin and the minimum images of the others from it
+template <int S>
+__device__ __forceinline__ void unwrap(const SettleBox &b, const double (&s)[S][3], double (&x)[S][3]) {
 #pragma unroll
     for (int d = 0; d < 3; d++) {
         x[0][d] = 0.0;
-        x[1][d] = image(s[1][d] - s[0][d], b.len[d], b.per[d]);
-        x[2][d] = image(s[2][d] - s[0][d], b.len[d], b.per[d]);
+#pragma unroll
+        for (int k = 1; k < S; k++) x[k][d] = image(s[k][d] - s[0][d], b.len[d], b.per[d]);
     }
 }
 template <typename real>
-__device__ __forceinline__ void masses(const SettleArgs<real> &a, int p_apex, int p_leg, double &m_apex, double &m_leg) {
+__device__ __forceinline__ void masses(const ConstraintArgs<real> &a, int p_apex, int p_leg, double &m_apex, double &m_leg) {
     m_apex = a.inv_mass ? 1.0 / (double)a.inv_mass[p_apex] : 1.0;
     m_leg = a.inv_mass ? 1.0 / (double)a.inv_mass[p_leg] : 1.0;
 }
 }  // namespace settle_detail
 
-// stage (a): the positions the molecules have before the step, 9 doubles per molecule in table order
-template <typename real>
-__global__ __launch_bounds__(256) void k_settle_gather(SettleArgs<real> a, double *__restrict__ x0) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
+// ---- the constraint kernels: one thread per group, fp64 on unwrapped differences in both precisions, no atomics on the state.
+// Written once for every kind of group; a group policy G carries what differs between kinds:
+//   SITES, GEOM             sites per group (x0 holds 3 * SITES doubles per group) and doubles of geom per group
+//   slots(a, m, p)          the slots of group m's sites; returns n, the last site in use (a site k > n reads site 0's slot and
+//                           is never written)
+//   positions(a, m, p, n, x0, x1), velocities(a, p, n, x, v)
+//                           the plain-C++ solvers above (and in shake.hpp) with the masses and the geometry as each takes them
+//   check(a, m, p, n, x, words)
+//                           the test of a table entry against the loaded sites x (unwrapped about site 0)
+// Every loop over sites is a compile-time loop over SITES and no array is indexed at run time.
+
+// the rigid triangle: atoms = {apex, a, b}, geom = {d_leg, d_base}; SETTLE and RATTLE take the masses of the apex and of a leg
+struct Triangle {
+    static constexpr int SITES = 3, GEOM = 2;
+    template <typename real>
+    static __device__ __forceinline__ int slots(const ConstraintArgs<real> &a, int m, int (&p)[3]) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < 3; k++) p[k] = a.inv_perm[a.atoms[3 * (size_t)m + k]];
+        return 2;
+    }
+    template <typename real>
+    static __device__ __forceinline__ bool positions(const ConstraintArgs<real> &a, int m, const int (&p)[3], int, const double (&x0)[3][3],
+                                                     double (&x1)[3][3]) {
+        double m_apex, m_leg;
+        settle_detail::masses(a, p[0], p[1], m_apex, m_leg);
+        return settle_positions(x0, x1, m_apex, m_leg, a.geom[2 * (size_t)m], a.geom[2 * (size_t)m + 1]);
+    }
+    template <typename real>
+    static __device__ __forceinline__ void velocities(const ConstraintArgs<real> &a, const int (&p)[3], int, const double (&x)[3][3],
+                                                      double (&v)[3][3]) {
+        double m_apex, m_leg;
+        settle_detail::masses(a, p[0], p[1], m_apex, m_leg);
+        settle_velocities(x, v, m_apex, m_leg);
+    }
+    // words[0] = a molecule + 1 whose legs have different masses, words[1] = a molecule + 1 with a distance more than 1e-3
+    // (relative) off its table entry; the highest such molecule each
+    template <typename real>
+    static __device__ __forceinline__ void check(const ConstraintArgs<real> &a, int m, const int (&p)[3], int, const double (&x)[3][3],
+                                                 int *__restrict__ words) {
+        if (a.inv_mass && a.inv_mass[p[1]] != a.inv_mass[p[2]]) atomicMax(words, m + 1);
+        const double d_leg = a.geom[2 * (size_t)m], d_base = a.geom[2 * (size_t)m + 1];
+        const double l1 = sqrt(x[1][0] * x[1][0] + x[1][1] * x[1][1] + x[1][2] * x[1][2]);
+        const double l2 = sqrt(x[2][0] * x[2][0] + x[2][1] * x[2][1] + x[2][2] * x[2][2]);
+        const double bx = x[1][0] - x[2][0], by = x[1][1] - x[2][1], bz = x[1][2] - x[2][2];
+        const double l3 = sqrt(bx * bx + by * by + bz * bz);
+        if (!(fabs(l1 - d_leg) <= 1e-3 * d_leg) || !(fabs(l2 - d_leg) <= 1e-3 * d_leg) || !(fabs(l3 - d_base) <= 1e-3 * d_base))
+            atomicMax(words + 1, m + 1);
+    }
+};
+
+// stage (a): the positions the groups have before the step, 3 * SITES doubles per group in table order (an unused site: site 0's)
+template <typename real, class G>
+__global__ __launch_bounds__(256) void k_constraint_gather(ConstraintArgs<real> a, double *__restrict__ x0) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n) return;
+    int p[G::SITES];
+    G::slots(a, m, p);
+#pragma unroll
+    for (int k = 0; k < G::SITES; k++) {
         double x[3];
-        settle_detail::site(a, a.inv_perm[a.atoms[3 * (size_t)m + k]], x);
-        x0[9 * (size_t)m + 3 * k] = x[0]; x0[9 * (size_t)m + 3 * k + 1] = x[1]; x0[9 * (size_t)m + 3 * k + 2] = x[2];
+        settle_detail::site(a, p[k], x);
+#pragma unroll
+        for (int d = 0; d < 3; d++) x0[3 * G::SITES * (size_t)m + 3 * k + d] = x[d];
     }
 }
 
-// stage (c): the records of the unconstrained step -> the rigid triangle; v += (x_constrained - x_unconstrained) / dt; the three
-// atoms tested against the rebuild threshold again (k_kick_drift's test, on the corrected record).  A molecule without a
-// solution stays as it is and its number + 1 goes to *err.
-template <typename real>
-__global__ __launch_bounds__(256) void k_settle_positions(SettleArgs<real> a, const double *__restrict__ x0, double inv_dt,
-                                                          const real *__restrict__ xb, real thr2, int *__restrict__ flag,
-                                                          int *__restrict__ err) {
+// stage (c): the records of the unconstrained step -> the group with its distances restored; v += (x_constrained -
+// x_unconstrained) / dt; the group's atoms tested against the rebuild threshold again (k_kick_drift's test, on the corrected
+// record).  A group without a solution stays as it is and its number + 1 goes to *err.
+template <typename real, class G>
+__global__ __launch_bounds__(256) void k_constraint_positions(ConstraintArgs<real> a, const double *__restrict__ x0, double inv_dt,
+                                                              const real *__restrict__ xb, real thr2, int *__restrict__ flag,
+                                                              int *__restrict__ err) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[3];
-    double s0[3][3], xa[3][3], xn[3][3];
+    if (m >= a.n) return;
+    int p[G::SITES];
+    const int n = G::slots(a, m, p);
+    double s0[G::SITES][3], xa[G::SITES][3], xn[G::SITES][3], xs[G::SITES][3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        p[k] = a.inv_perm[a.atoms[3 * (size_t)m + k]];
+    for (int k = 0; k < G::SITES; k++)
 #pragma unroll
-        for (int d = 0; d < 3; d++) s0[k][d] = x0[9 * (size_t)m + 3 * k + d];
-    }
+        for (int d = 0; d < 3; d++) s0[k][d] = x0[3 * G::SITES * (size_t)m + 3 * k + d];
     settle_detail::unwrap(a.box, s0, xa);
     // the unconstrained sites: x0 (unwrapped) + what each record moved since stage (a) (no sort in between: the same frame)
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
+    for (int k = 0; k < G::SITES; k++) {
         double now[3];
         settle_detail::site(a, p[k], now);
 #pragma unroll
-        for (int d = 0; d < 3; d++) xn[k][d] = xa[k][d] + (now[d] - s0[k][d]);
+        for (int d = 0; d < 3; d++) xs[k][d] = xn[k][d] = xa[k][d] + (now[d] - s0[k][d]);
     }
-    double m_apex, m_leg;
-    settle_detail::masses(a, p[0], p[1], m_apex, m_leg);
-    double xs[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int d = 0; d < 3; d++) xs[k][d] = xn[k][d];
-    if (!settle_positions(xa, xs, m_apex, m_leg, a.geom[2 * (size_t)m], a.geom[2 * (size_t)m + 1])) {
-        atomicMax(err, m + 1);                               // (the failure path only; which molecule is named does not depend on the schedule)
+    if (!G::positions(a, m, p, n, xa, xs)) {
+        atomicMax(err, m + 1);                               // (the failure path only; which group is named does not depend on the schedule)
         return;
     }
     bool far = false;
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
+    for (int k = 0; k < G::SITES; k++) {
+        if (k > n) continue;
         const double dx = xs[k][0] - xn[k][0], dy = xs[k][1] - xn[k][1], dz = xs[k][2] - xn[k][2];
         Rec<real> r = a.rec[p[k]];
         r.x = (real)((double)r.x + dx); r.y = (real)((double)r.y + dy); r.z = (real)((double)r.z + dz);
@@ -290,59 +339,49 @@ __global__ __launch_bounds__(256) void k_settle_positions(SettleArgs<real> a, co
     if (far) *flag = 1;
 }
 
-// stage (e): no relative velocity along the three bonds
-template <typename real>
-__global__ __launch_bounds__(256) void k_settle_velocities(SettleArgs<real> a) {
+// stage (e): no relative velocity along any of the group's bonds
+template <typename real, class G>
+__global__ __launch_bounds__(256) void k_constraint_velocities(ConstraintArgs<real> a) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[3];
-    double s[3][3], x[3][3], v[3][3];
+    if (m >= a.n) return;
+    int p[G::SITES];
+    const int n = G::slots(a, m, p);
+    double s[G::SITES][3], x[G::SITES][3], v[G::SITES][3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        p[k] = a.inv_perm[a.atoms[3 * (size_t)m + k]];
+    for (int k = 0; k < G::SITES; k++) {
         settle_detail::site(a, p[k], s[k]);
 #pragma unroll
         for (int d = 0; d < 3; d++) v[k][d] = (double)a.vel[d * a.pitch + p[k]];
     }
     settle_detail::unwrap(a.box, s, x);
-    double m_apex, m_leg;
-    settle_detail::masses(a, p[0], p[1], m_apex, m_leg);
-    settle_velocities(x, v, m_apex, m_leg);
+    G::velocities(a, p, n, x, v);
 #pragma unroll
-    for (int k = 0; k < 3; k++)
+    for (int k = 0; k < G::SITES; k++) {
+        if (k > n) continue;
 #pragma unroll
         for (int d = 0; d < 3; d++) a.vel[d * a.pitch + p[k]] = (real)v[k][d];
+    }
 }
 
-// the check of a table against a loaded state: words[0] = a molecule + 1 whose legs have different masses, words[1] = a molecule
-// + 1 with a distance more than 1e-3 (relative) off its table entry; the highest such molecule each
-template <typename real>
-__global__ __launch_bounds__(256) void k_settle_check(SettleArgs<real> a, int *__restrict__ words) {
+// the check of a table against a loaded state: the policy's words, each the highest group + 1 that fails its test
+template <typename real, class G>
+__global__ __launch_bounds__(256) void k_constraint_check(ConstraintArgs<real> a, int *__restrict__ words) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[3];
-    double s[3][3], x[3][3];
+    if (m >= a.n) return;
+    int p[G::SITES];
+    const int n = G::slots(a, m, p);
+    double s[G::SITES][3], x[G::SITES][3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        p[k] = a.inv_perm[a.atoms[3 * (size_t)m + k]];
-        settle_detail::site(a, p[k], s[k]);
-    }
+    for (int k = 0; k < G::SITES; k++) settle_detail::site(a, p[k], s[k]);
     settle_detail::unwrap(a.box, s, x);
-    if (a.inv_mass && a.inv_mass[p[1]] != a.inv_mass[p[2]]) atomicMax(words, m + 1);
-    const double d_leg = a.geom[2 * (size_t)m], d_base = a.geom[2 * (size_t)m + 1];
-    const double l1 = sqrt(x[1][0] * x[1][0] + x[1][1] * x[1][1] + x[1][2] * x[1][2]);
-    const double l2 = sqrt(x[2][0] * x[2][0] + x[2][1] * x[2][1] + x[2][2] * x[2][2]);
-    const double bx = x[1][0] - x[2][0], by = x[1][1] - x[2][1], bz = x[1][2] - x[2][2];
-    const double l3 = sqrt(bx * bx + by * by + bz * bz);
-    if (!(fabs(l1 - d_leg) <= 1e-3 * d_leg) || !(fabs(l2 - d_leg) <= 1e-3 * d_leg) || !(fabs(l3 - d_base) <= 1e-3 * d_base))
-        atomicMax(words + 1, m + 1);
+    G::check(a, m, p, n, x, words);
 }
 
 // ---- molecular pressure and centre-of-mass scaling: the two kernels (timed under emdee_md_kernel_time index 10) ----------------
 // The sites of molecule m as the molecular definitions take them: s = the records in double (site()), y = the apex record and the
 // minimum images of the legs from it, v the velocities; p the slots.
 template <typename real>
-__device__ __forceinline__ void molecule_load(const SettleArgs<real> &a, int m, int (&p)[3], double (&s)[3][3], double (&y)[3][3],
+__device__ __forceinline__ void molecule_load(const ConstraintArgs<real> &a, int m, int (&p)[3], double (&s)[3][3], double (&y)[3][3],
                                               double (&v)[3][3], double &m_apex, double &m_leg) {
     double x[3][3];
 #pragma unroll
@@ -363,11 +402,11 @@ __device__ __forceinline__ void molecule_load(const SettleArgs<real> &a, int m, 
 // partial[b][0..11] = the sum of molecule_sums over the molecules of block b's stride, k_tensor_partials' shape: fp64, fixed order,
 // no atomics (k_final_sums completes them).  frc: the engine's force planes (the force-field forces of the last force pass).
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_molecule_partials(SettleArgs<real> a, const real *__restrict__ frc, double *__restrict__ partial) {
+__global__ __launch_bounds__(RED_BLOCK) void k_molecule_partials(ConstraintArgs<real> a, const real *__restrict__ frc, double *__restrict__ partial) {
     __shared__ double sh[RED_BLOCK / WAVE];
     double sum[TENSOR_SUMS];
     for (int q = 0; q < TENSOR_SUMS; q++) sum[q] = 0.0;
-    for (int m = blockIdx.x * RED_BLOCK + threadIdx.x; m < a.n_mol; m += gridDim.x * RED_BLOCK) {
+    for (int m = blockIdx.x * RED_BLOCK + threadIdx.x; m < a.n; m += gridDim.x * RED_BLOCK) {
         int p[3];
         double s[3][3], y[3][3], v[3][3], f[3][3], m_apex, m_leg, t[TENSOR_SUMS];
         molecule_load(a, m, p, s, y, v, m_apex, m_leg);
@@ -386,13 +425,13 @@ __global__ __launch_bounds__(RED_BLOCK) void k_molecule_partials(SettleArgs<real
 
 // The molecular scale, one thread per molecule: every site's record moves by (mu - 1) (C_k - lo), C_k = Y + (r_k - y_k) the image
 // of the centre of mass that goes with the record (r_k - y_k: whole box lengths, so the stored image counts stay valid); the
-// shift is added to the record in its own frame in double and rounded once, as k_settle_positions adds its corrections.
+// shift is added to the record in its own frame in double and rounded once, as k_constraint_positions adds its corrections.
 // scale_vel: v_k += (velocity_scale - 1) V; 0 leaves the velocity planes untouched, bit for bit.  k_cell_state_scale, given the
 // membership bytes, leaves these atoms alone.
 template <typename real>
-__global__ __launch_bounds__(256) void k_molecule_scale(SettleArgs<real> a, ScaleBox sb, double velocity_scale, int scale_vel) {
+__global__ __launch_bounds__(256) void k_molecule_scale(ConstraintArgs<real> a, ScaleBox sb, double velocity_scale, int scale_vel) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
+    if (m >= a.n) return;
     int p[3];
     double s[3][3], y[3][3], v[3][3], m_apex, m_leg, shift[3], dv[3];
     molecule_load(a, m, p, s, y, v, m_apex, m_leg);

@@ -4,7 +4,7 @@
 // Newton's method on the n coupled equations, the n x n system solved directly; the velocity stage is RATTLE (Andersen, J.
 // Comput. Phys. 52, 24 (1983)): one symmetric linear solve.  The two functions at the top are plain C++ on fixed-size arrays of
 // doubles, as the top of settle.hpp is: a stand-alone host program tests them with the host compiler (tests/c/shake_host.cpp);
-// the kernels below them need HIP.
+// the group policy below them (Star: how settle.hpp's constraint kernels take a cluster) needs HIP.
 // Sites: 0 = the centre, 1..3 = the satellites; w: the inverse masses; n: how many satellites are in use (1..3).  Both functions
 // are written for three satellites with compile-time loops: a slot k >= n becomes an identity row with a zero right-hand side,
 // a zero bond vector and w = 0, so nothing is indexed at run time (a run-time index put a struct in scratch once).
@@ -133,147 +133,57 @@ EMDEE_HD void shake_velocities(const double (&x)[4][3], double (&v)[4][3], const
 
 namespace emdee {
 
-// The kernels take settle.hpp's SettleArgs: n_mol = the clusters, atoms = {centre, s1, s2, s3} caller ids per cluster with -1 in
-// the unused trailing slots, geom = the three distances.  One thread per cluster, fp64 on unwrapped differences in both
-// precisions, no atomics on the state.
-namespace shake_detail {
-// the slots of cluster m's atoms (an unused site gets the centre's slot: never written, read for nothing) and the satellites in use
-template <typename real>
-__device__ __forceinline__ int slots(const SettleArgs<real> &a, int m, int (&p)[4]) {
-    const int4 id = *reinterpret_cast<const int4 *>(a.atoms + 4 * (size_t)m);
-    p[0] = a.inv_perm[id.x];
-    p[1] = a.inv_perm[id.y];
-    p[2] = id.z >= 0 ? a.inv_perm[id.z] : p[0];
-    p[3] = id.w >= 0 ? a.inv_perm[id.w] : p[0];
-    return 1 + (id.z >= 0 ? 1 : 0) + (id.w >= 0 ? 1 : 0);
-}
-// the sites as the centre at the origin and the minimum images of the satellites from it
-__device__ __forceinline__ void unwrap(const SettleBox &b, const double (&s)[4][3], double (&x)[4][3]) {
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        x[0][d] = 0.0;
-#pragma unroll
-        for (int k = 1; k < 4; k++) x[k][d] = settle_detail::image(s[k][d] - s[0][d], b.len[d], b.per[d]);
+// the star cluster as a group policy of settle.hpp's constraint kernels: atoms = {centre, s1, s2, s3} caller ids per cluster with
+// -1 in the unused trailing slots, geom = the three distances; M-SHAKE and RATTLE take the inverse masses of the four sites
+struct Star {
+    static constexpr int SITES = 4, GEOM = 3;
+    // the slots of cluster m's atoms (an unused site gets the centre's slot: never written, read for nothing) and the satellites in use
+    template <typename real>
+    static __device__ __forceinline__ int slots(const ConstraintArgs<real> &a, int m, int (&p)[4]) {
+        const int4 id = *reinterpret_cast<const int4 *>(a.atoms + 4 * (size_t)m);
+        p[0] = a.inv_perm[id.x];
+        p[1] = a.inv_perm[id.y];
+        p[2] = id.z >= 0 ? a.inv_perm[id.z] : p[0];
+        p[3] = id.w >= 0 ? a.inv_perm[id.w] : p[0];
+        return 1 + (id.z >= 0 ? 1 : 0) + (id.w >= 0 ? 1 : 0);
     }
-}
-template <typename real>
-__device__ __forceinline__ void inverse_masses(const SettleArgs<real> &a, const int (&p)[4], double (&w)[4]) {
+    template <typename real>
+    static __device__ __forceinline__ void inverse_masses(const ConstraintArgs<real> &a, const int (&p)[4], double (&w)[4]) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) w[k] = a.inv_mass ? (double)a.inv_mass[p[k]] : 1.0;
-}
-}  // namespace shake_detail
-
-// stage (a): the positions the clusters have before the step, 12 doubles per cluster in table order (an unused site: the centre's)
-template <typename real>
-__global__ __launch_bounds__(256) void k_hbond_gather(SettleArgs<real> a, double *__restrict__ x0) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[4];
-    shake_detail::slots(a, m, p);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        double x[3];
-        settle_detail::site(a, p[k], x);
-        x0[12 * (size_t)m + 3 * k] = x[0]; x0[12 * (size_t)m + 3 * k + 1] = x[1]; x0[12 * (size_t)m + 3 * k + 2] = x[2];
+        for (int k = 0; k < 4; k++) w[k] = a.inv_mass ? (double)a.inv_mass[p[k]] : 1.0;
     }
-}
-
-// stage (c): the records of the unconstrained step -> every satellite at its distance; v += (x_constrained - x_unconstrained) /
-// dt; the cluster's atoms tested against the rebuild threshold again, as k_settle_positions tests its own.  A cluster without a
-// solution stays as it is and its number + 1 goes to *err.
-template <typename real>
-__global__ __launch_bounds__(256) void k_hbond_positions(SettleArgs<real> a, const double *__restrict__ x0, double inv_dt,
-                                                         const real *__restrict__ xb, real thr2, int *__restrict__ flag,
-                                                         int *__restrict__ err) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[4];
-    const int n = shake_detail::slots(a, m, p);
-    double s0[4][3], xa[4][3], xn[4][3], xs[4][3], w[4], dist[3];
+    template <typename real>
+    static __device__ __forceinline__ bool positions(const ConstraintArgs<real> &a, int m, const int (&p)[4], int n, const double (&x0)[4][3],
+                                                     double (&x1)[4][3]) {
+        double w[4], dist[3];
+        inverse_masses(a, p, w);
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int d = 0; d < 3; d++) s0[k][d] = x0[12 * (size_t)m + 3 * k + d];
-    shake_detail::unwrap(a.box, s0, xa);
-    // the unconstrained sites: x0 (unwrapped) + what each record moved since stage (a) (no sort in between: the same frame)
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        double now[3];
-        settle_detail::site(a, p[k], now);
-#pragma unroll
-        for (int d = 0; d < 3; d++) xs[k][d] = xn[k][d] = xa[k][d] + (now[d] - s0[k][d]);
+        for (int k = 0; k < 3; k++) dist[k] = a.geom[3 * (size_t)m + k];
+        return shake_positions(x0, x1, w, dist, n);
     }
-    shake_detail::inverse_masses(a, p, w);
-#pragma unroll
-    for (int k = 0; k < 3; k++) dist[k] = a.geom[3 * (size_t)m + k];
-    if (!shake_positions(xa, xs, w, dist, n)) {
-        atomicMax(err, m + 1);                               // (the failure path only; which cluster is named does not depend on the schedule)
-        return;
+    template <typename real>
+    static __device__ __forceinline__ void velocities(const ConstraintArgs<real> &a, const int (&p)[4], int n, const double (&x)[4][3],
+                                                      double (&v)[4][3]) {
+        double w[4];
+        inverse_masses(a, p, w);
+        shake_velocities(x, v, w, n);
     }
-    bool far = false;
+    // *word = a cluster + 1 with a distance more than 1e-3 (relative) off its table entry (the highest such cluster): a wrong
+    // topology, not rounding
+    template <typename real>
+    static __device__ __forceinline__ void check(const ConstraintArgs<real> &a, int m, const int (&)[4], int n, const double (&x)[4][3],
+                                                 int *__restrict__ word) {
+        bool off = false;
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (k > n) continue;
-        const double dx = xs[k][0] - xn[k][0], dy = xs[k][1] - xn[k][1], dz = xs[k][2] - xn[k][2];
-        Rec<real> r = a.rec[p[k]];
-        r.x = (real)((double)r.x + dx); r.y = (real)((double)r.y + dy); r.z = (real)((double)r.z + dz);
-        a.rec[p[k]] = r;
-        a.vel[p[k]] = (real)((double)a.vel[p[k]] + dx * inv_dt);
-        a.vel[a.pitch + p[k]] = (real)((double)a.vel[a.pitch + p[k]] + dy * inv_dt);
-        a.vel[2 * a.pitch + p[k]] = (real)((double)a.vel[2 * a.pitch + p[k]] + dz * inv_dt);
-        const real ux = r.x - xb[p[k]], uy = r.y - xb[a.pitch + p[k]], uz = r.z - xb[2 * a.pitch + p[k]];
-        far = far || ux * ux + uy * uy + uz * uz > thr2;
+        for (int k = 1; k < 4; k++) {
+            if (k > n) continue;
+            const double d = a.geom[3 * (size_t)m + k - 1];
+            const double l = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
+            off = off || !(fabs(l - d) <= 1e-3 * d);
+        }
+        if (off) atomicMax(word, m + 1);
     }
-    if (far) *flag = 1;
-}
-
-// stage (e): no relative velocity along any of the cluster's bonds
-template <typename real>
-__global__ __launch_bounds__(256) void k_hbond_velocities(SettleArgs<real> a) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[4];
-    const int n = shake_detail::slots(a, m, p);
-    double s[4][3], x[4][3], v[4][3], w[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        settle_detail::site(a, p[k], s[k]);
-#pragma unroll
-        for (int d = 0; d < 3; d++) v[k][d] = (double)a.vel[d * a.pitch + p[k]];
-    }
-    shake_detail::unwrap(a.box, s, x);
-    shake_detail::inverse_masses(a, p, w);
-    shake_velocities(x, v, w, n);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (k > n) continue;
-#pragma unroll
-        for (int d = 0; d < 3; d++) a.vel[d * a.pitch + p[k]] = (real)v[k][d];
-    }
-}
-
-// the check of a table against a loaded state: *word = a cluster + 1 with a distance more than 1e-3 (relative) off its table
-// entry (the highest such cluster): a wrong topology, not rounding
-template <typename real>
-__global__ __launch_bounds__(256) void k_hbond_check(SettleArgs<real> a, int *__restrict__ word) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mol) return;
-    int p[4];
-    const int n = shake_detail::slots(a, m, p);
-    double s[4][3], x[4][3];
-#pragma unroll
-    for (int k = 0; k < 4; k++) settle_detail::site(a, p[k], s[k]);
-    shake_detail::unwrap(a.box, s, x);
-    bool off = false;
-#pragma unroll
-    for (int k = 1; k < 4; k++) {
-        if (k > n) continue;
-        const double d = a.geom[3 * (size_t)m + k - 1];
-        const double l = sqrt(x[k][0] * x[k][0] + x[k][1] * x[k][1] + x[k][2] * x[k][2]);
-        off = off || !(fabs(l - d) <= 1e-3 * d);
-    }
-    if (off) atomicMax(word, m + 1);
-}
+};
 
 }  // namespace emdee
 #endif

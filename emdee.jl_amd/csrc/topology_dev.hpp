@@ -112,73 +112,64 @@ struct Topology {
         has_bonded = !t.terms.empty();
     }
 
-    // ---- rigid three-site molecules (emdee_md_set_rigid3; settle.hpp): {apex, a, b} caller ids and {d_leg, d_base} per molecule,
-    // undivided engines only
-    DevBuf<int> r_atoms;
-    DevBuf<double> r_geom;
-    DevBuf<unsigned char> r_member;                          // one byte per id below r_limit: named by the table (topo::rigid3_members)
-    std::vector<int32_t> r_atoms_h;                          // the ids as given (the error texts name them)
-    int r_n = 0;                                             // molecules
-    int64_t r_limit = 0;                                     // the atom count the ids were checked against
-    bool has_rigid = false;
-    // Replaces the table by the n molecules at atoms_dev / geom_dev (device); n = 0 clears it.  check(atoms, geom, n): the
-    // engine's test of the uploaded candidate against its state; it throws to refuse, and the table in force stays.
-    template <class Check>
-    void set_rigid3(const int32_t *atoms_dev, const double *geom_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
-        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && geom_dev)), EMDEE_ERR_INVALID, "set_rigid3: negative count or NULL array");
+    // ---- the constraint tables, undivided engines only: rigid three-site molecules (emdee_md_set_rigid3; settle.hpp), {apex, a, b}
+    // caller ids and {d_leg, d_base} per molecule, and bonds to hydrogen (emdee_md_set_hbonds; shake.hpp), {centre, s1, s2, s3}
+    // caller ids (-1: an unused trailing slot) and the three distances per cluster.  An atom is held by one table.
+    struct GroupTable {
+        DevBuf<int> atoms;
+        DevBuf<double> geom;
+        std::vector<int32_t> atoms_h;                        // the ids as given (the error texts name them; the other table's setter checks against them)
+        int n = 0;                                           // groups
+        int64_t limit = 0;                                   // the atom count the ids were checked against
+        bool present = false;
+    };
+    GroupTable rigid, hbonds;
+    DevBuf<unsigned char> r_member;                          // one byte per id below rigid.limit: named by the table (topo::rigid3_members)
+    // Replaces table t by the n groups at atoms_dev / geom_dev (device; `sites` ids and `ngeom` doubles per group); n = 0 clears
+    // it.  host(ids, geom): the host check of the fetched arrays, which it leaves as the kernels read them and may follow with
+    // uploads of its own; it throws to refuse.  check(atoms, geom, ids, n): the engine's test of the uploaded candidate against
+    // its state; it throws to refuse as well, and the table in force stays.  Returns whether a table was committed.
+    template <class Host, class Check>
+    bool set_groups(GroupTable &t, const char *name, const char *noun, int sites, int ngeom, const int32_t *atoms_dev, const double *geom_dev,
+                    int64_t n, int64_t lim, hipStream_t s, Host &&host, Check &&check) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && geom_dev)), EMDEE_ERR_INVALID, "%s: negative count or NULL array", name);
         if (n == 0) {
-            has_rigid = false; r_n = 0; r_atoms_h.clear();
-            return;
+            t.present = false; t.n = 0; t.atoms_h.clear();
+            return false;
         }
-        EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules (at most (2^31 - 1) / 3)", (long long)n);
-        const std::vector<int32_t> raw = fetch(atoms_dev, (size_t)3 * n, s);
-        const std::vector<double> geom = fetch(geom_dev, (size_t)2 * n, s);
-        const std::vector<int32_t> h = topo::checked_rigid3(raw, geom, lim, has_hbonds ? &h_atoms_h : nullptr);
+        EMDEE_REQUIRE(n <= INT32_MAX / sites, EMDEE_ERR_INVALID, "%s: %lld %s (at most (2^31 - 1) / %d)", name, (long long)n, noun, sites);
+        std::vector<int32_t> ids = fetch(atoms_dev, (size_t)sites * n, s);
+        std::vector<double> geom = fetch(geom_dev, (size_t)ngeom * n, s);
+        host(ids, geom);
         DevBuf<int> na;
         DevBuf<double> ng;
-        DevBuf<unsigned char> nm;
-        const std::vector<uint8_t> member = topo::rigid3_members(h, lim);
-        put(na, h, s); put(ng, geom, s); put(nm, member, s);
+        put(na, ids, s); put(ng, geom, s);
         EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        check(na.ptr, ng.ptr, h, (int)n);
+        check(na.ptr, ng.ptr, ids, (int)n);
         // ---- commit
-        r_atoms.swap(na); r_geom.swap(ng); r_member.swap(nm);
-        r_atoms_h = h;
-        r_n = (int)n; r_limit = lim;
-        has_rigid = true;
+        t.atoms.swap(na); t.geom.swap(ng);
+        t.atoms_h = ids;
+        t.n = (int)n; t.limit = lim;
+        t.present = true;
+        return true;
     }
-
-    // ---- bonds to hydrogen (emdee_md_set_hbonds; shake.hpp): {centre, s1, s2, s3} caller ids (-1: an unused trailing slot) and the
-    // three distances per cluster, undivided engines only
-    DevBuf<int> h_atoms;
-    DevBuf<double> h_dist;
-    std::vector<int32_t> h_atoms_h;                          // the ids as given (the error texts name them; set_rigid3 checks against them)
-    int h_n = 0;                                             // clusters
-    int64_t h_limit = 0;                                     // the atom count the ids were checked against
-    bool has_hbonds = false;
-    // Replaces the table by the n clusters at atoms_dev / dist_dev (device); n = 0 clears it.  check: as set_rigid3's.
+    template <class Check>
+    void set_rigid3(const int32_t *atoms_dev, const double *geom_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
+        DevBuf<unsigned char> nm;
+        std::vector<uint8_t> member;                         // (outlives the upload)
+        const bool set = set_groups(rigid, "set_rigid3", "molecules", 3, 2, atoms_dev, geom_dev, n, lim, s, [&](std::vector<int32_t> &ids, std::vector<double> &geom) {
+            ids = topo::checked_rigid3(ids, geom, lim, hbonds.present ? &hbonds.atoms_h : nullptr);
+            member = topo::rigid3_members(ids, lim);
+            put(nm, member, s);
+        }, check);
+        if (set) r_member.swap(nm);
+    }
     template <class Check>
     void set_hbonds(const int32_t *atoms_dev, const double *dist_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
-        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && dist_dev)), EMDEE_ERR_INVALID, "set_hbonds: negative count or NULL array");
-        if (n == 0) {
-            has_hbonds = false; h_n = 0; h_atoms_h.clear();
-            return;
-        }
-        EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_hbonds: %lld clusters (at most (2^31 - 1) / 4)", (long long)n);
-        const std::vector<int32_t> raw = fetch(atoms_dev, (size_t)4 * n, s);
-        const std::vector<double> given = fetch(dist_dev, (size_t)3 * n, s);
-        const std::vector<int32_t> h = topo::checked_hbonds(raw, given, lim, has_rigid ? &r_atoms_h : nullptr);
-        const std::vector<double> dist = topo::hbonds_distances(h, given);
-        DevBuf<int> na;
-        DevBuf<double> nd;
-        put(na, h, s); put(nd, dist, s);
-        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
-        check(na.ptr, nd.ptr, h, (int)n);
-        // ---- commit
-        h_atoms.swap(na); h_dist.swap(nd);
-        h_atoms_h = h;
-        h_n = (int)n; h_limit = lim;
-        has_hbonds = true;
+        set_groups(hbonds, "set_hbonds", "clusters", 4, 3, atoms_dev, dist_dev, n, lim, s, [&](std::vector<int32_t> &ids, std::vector<double> &dist) {
+            ids = topo::checked_hbonds(ids, dist, lim, rigid.present ? &rigid.atoms_h : nullptr);
+            dist = topo::hbonds_distances(ids, dist);
+        }, check);
     }
 
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the

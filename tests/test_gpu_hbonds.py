@@ -180,6 +180,18 @@ def test_kernel_time_index_11_is_zero_without_a_table(emdee, dev):
     md.close()
 
 
+def test_every_stage_runs_once_per_table_and_step_under_its_own_timer(emdee, dev):
+    # Both tables in force: stages (a), (c), (e) of every step run once for the molecules (index 9) and once for the clusters
+    # (index 11), and nothing is booked on the molecular sums (index 10).
+    md = _engine(emdee, dev, hr.mixed_box(), rigid=True)
+    md.profile_(True)
+    md.step_(5, DT)
+    assert md.kernel_time("settle")[1] == 3 * 5
+    assert md.kernel_time("hbonds")[1] == 3 * 5
+    assert md.kernel_time("molecular") == (0.0, 0)
+    md.close()
+
+
 def test_clearing_the_table_restores_the_unconstrained_trajectory(emdee, dev):
     # The pairs within a cluster are excluded and nothing else holds it together: 20 unconstrained steps are harmless.
     # Installing the table projects the velocities, so the twin that never had one starts from the state the install left.
