@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/emdee_hip.h"
@@ -121,6 +122,26 @@ static inline int32_t guarded(F &&body) {
         return EMDEE_ERR_INVALID;
     }
 }
+
+// ---- run-time value -> compile-time constant, for the launch sites that choose a kernel instance (as with_brick_variant does
+// for the brick variant, nbsys.hpp): f gets a std::integral_constant, and is instantiated for the listed values ONLY -- the
+// list at a call site is the set of instances that site can launch.
+template <class F>
+static inline void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the last entry of the list runs for every mask that is not in it
+template <int... Ms>
+struct Masks {};
+template <int First, int... Rest, class F>
+static inline void with_mask(Masks<First, Rest...>, int mask, F &&f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, First>{});
+    else if (mask == First) f(std::integral_constant<int, First>{});
+    else with_mask(Masks<Rest...>{}, mask, f);
+}
+using AllMasks = Masks<1, 2, 3, 4, 5, 6, TENSOR_PASS, 7>;   // the default brick variant and the direct kernels
+using LoopMasks = Masks<1, TENSOR_PASS, 7>;                 // what the MD loop uses: the other variants, the charged and Ewald twins
 
 }  // namespace emdee
 

@@ -1370,8 +1370,10 @@ struct DdImpl : IDd {
             if (!d.words_clear) EMDEE_HIP_CHECK(hipMemsetAsync(d.words.ptr, 0, DD_WORDS * sizeof(int), d.stream()));
             d.words_clear = false;
             if (d.sys().n_total > 0) {
-                const bool tiled = d.sys().brick_active && !(d.md->current_mask & EMDEE_FORCES) &&
-                                   d.sys().fused_step(dt, dt, 0, nullptr, d.V(0), false, false);
+                Pass<real> step = Pass<real>::step(dt, dt);
+                step.trigger = d.V(0);
+                step.carry_ghosts = false;
+                const bool tiled = d.sys().brick_active && !(d.md->current_mask & EMDEE_FORCES) && d.sys().fused_step(step);
                 if (!tiled) {
                     if (!(d.md->current_mask & EMDEE_FORCES)) d.md->forces(EMDEE_FORCES, 0);
                     d.sys().kick_drift(dt, dt, d.V(0));
@@ -1436,16 +1438,20 @@ struct DdImpl : IDd {
                     if (pd->sys().brick_active && !pd->sys().has_post()) pd->sys().prepare_noise(dt);   // (thermostat only) before the pack: both halves read it
                 with_halo(j, j, [&](Domain<real> &d, int phase) {
                     if (d.sys().n_total == 0) return;                     // nothing to move; its words stay clear
+                    // interior bricks look at my own request only (their neighbours are all mine); boundary bricks and the split
+                    // form at the OR of everybody's
+                    Pass<real> step = Pass<real>::step(dt, dt, phase);
+                    if (rebuild_every == 0) step.guard = (phase == 1) ? d.V(j) : d.G(j);
+                    step.trigger = d.V(j + 1);
+                    step.carry_ghosts = false;
+                    step.noise_ready = true;
                     if (d.sys().brick_active && !d.sys().has_post()) {
-                        // interior bricks look at my own request only (their neighbours are all mine); boundary bricks
-                        // at the OR of everybody's
-                        const int *guard = (phase == 1) ? d.V(j) : d.G(j);
-                        const bool launched = d.sys().fused_step(dt, dt, phase, rebuild_every > 0 ? nullptr : guard, d.V(j + 1), false, true);
+                        const bool launched = d.sys().fused_step(step);
                         EMDEE_REQUIRE(launched, EMDEE_ERR_STATE, "emdee_dd_step: domain %d could not launch its step kernel", d.geo.rank);
                     } else if (phase != 1) {
                         // tiles too large for LDS (dense slab, long cutoff): the direct kernels, whole domain behind the halo,
                         // under the same words.  A domain with a 1-4 table too: force pass, 1-4 terms, kick + drift
-                        d.sys().guarded_split_step(dt, dt, rebuild_every > 0 ? nullptr : d.G(j), d.V(j + 1));
+                        d.sys().guarded_split_step(step);
                     }
                 });
             }

@@ -222,18 +222,11 @@ struct EwaldRecip {
     void run(hipStream_t s, int n, size_t pitch, const AtomView<real> &atoms, const double lo[3], const double len[3], const real *q,
              double q_sum, double q_abs, int bitmask, real *frc, real *en, real *vir, real *vt) {
         if (!on() || n == 0) return;
+        const bool all = bitmask != EMDEE_FORCES;
         if (pme.on()) {
-            const bool all = bitmask != EMDEE_FORCES;
             part.ensure((size_t)(all ? 10 : 3) * pitch);
             pme.run(s, n, pitch, atoms, lo, len, alpha, q, q_abs, all, part.ptr);
-            const double self_c = alpha / std::sqrt(M_PI);
-            const double V = len[0] * len[1] * len[2], e_bg = -M_PI * q_sum * q_sum / (2.0 * V * alpha * alpha) / (double)n;
-            if (all)
-                hipLaunchKernelGGL((k_ewald_add<real, true>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, 1, part.ptr, q, self_c, e_bg,
-                                   bitmask, frc, en, vir, vt);
-            else
-                hipLaunchKernelGGL((k_ewald_add<real, false>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, 1, part.ptr, q, self_c, e_bg,
-                                   bitmask, frc, en, vir, vt);
+            add(s, n, pitch, 1, len, q, q_sum, bitmask, frc, en, vir, vt);
             return;
         }
         const int nk = (int)(nvec.size() / 3);
@@ -268,21 +261,25 @@ struct EwaldRecip {
         int nsplit = std::min(std::min(EW_MAX_SPLIT, (1024 + ablocks - 1) / ablocks), std::max(1, nk / 256));
         const int klen = (nk + nsplit - 1) / nsplit;
         nsplit = (nk + klen - 1) / klen;
-        const bool all = bitmask != EMDEE_FORCES;
         part.ensure((size_t)nsplit * (all ? 10 : 3) * pitch);
+        with_bool(all, [&](auto a) {
+            hipLaunchKernelGGL((k_ewald_atoms<decltype(a)::value>), dim3(ablocks, nsplit), dim3(EW_BLOCK), 0, s, n, pitch, nk, klen, ktab.ptr, S.ptr,
+                               ph.ptr, ax.off[1], ax.off[2], part.ptr);
+        });
+        add(s, n, pitch, nsplit, len, q, q_sum, bitmask, frc, en, vir, vt);
+    }
+
+  private:
+    // the tail the mesh and the direct sum share: the partials of nsplit ranges of wave vectors (the mesh: one), the self term
+    // and the background, added to the outputs
+    void add(hipStream_t s, int n, size_t pitch, int nsplit, const double len[3], const real *q, double q_sum, int bitmask, real *frc,
+             real *en, real *vir, real *vt) {
         const double self_c = alpha / std::sqrt(M_PI);
         const double V = len[0] * len[1] * len[2], e_bg = -M_PI * q_sum * q_sum / (2.0 * V * alpha * alpha) / (double)n;
-        if (all) {
-            hipLaunchKernelGGL((k_ewald_atoms<true>), dim3(ablocks, nsplit), dim3(EW_BLOCK), 0, s, n, pitch, nk, klen, ktab.ptr, S.ptr,
-                               ph.ptr, ax.off[1], ax.off[2], part.ptr);
-            hipLaunchKernelGGL((k_ewald_add<real, true>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, nsplit, part.ptr, q,
+        with_bool(bitmask != EMDEE_FORCES, [&](auto all) {
+            hipLaunchKernelGGL((k_ewald_add<real, decltype(all)::value>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, nsplit, part.ptr, q,
                                self_c, e_bg, bitmask, frc, en, vir, vt);
-        } else {
-            hipLaunchKernelGGL((k_ewald_atoms<false>), dim3(ablocks, nsplit), dim3(EW_BLOCK), 0, s, n, pitch, nk, klen, ktab.ptr, S.ptr,
-                               ph.ptr, ax.off[1], ax.off[2], part.ptr);
-            hipLaunchKernelGGL((k_ewald_add<real, false>), dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pitch, nsplit, part.ptr, q,
-                               self_c, e_bg, bitmask, frc, en, vir, vt);
-        }
+        });
     }
 };
 

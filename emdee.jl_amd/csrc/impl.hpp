@@ -79,49 +79,40 @@ struct NbrImpl : INbr {
 
     void compute(void *forces, void *energies, void *virials, const void *positions, double L, const emdee_lj_model &model,
                  const emdee_lj_atom *atoms, int bitmask) override {
-        use_device(sys.ctx);
         EMDEE_REQUIRE(bitmask >= 0 && bitmask <= 7, EMDEE_ERR_INVALID, "bitmask must be a combination of FORCES|ENERGIES|VIRIALS");
         EMDEE_REQUIRE(!(bitmask & EMDEE_FORCES) || forces || N == 0, EMDEE_ERR_INVALID, "forces selected but NULL");
         EMDEE_REQUIRE(!(bitmask & EMDEE_ENERGIES) || energies || N == 0, EMDEE_ERR_INVALID, "energies selected but NULL");
         EMDEE_REQUIRE(!(bitmask & EMDEE_VIRIALS) || virials || N == 0, EMDEE_ERR_INVALID, "virials selected but NULL");
-        EMDEE_REQUIRE(L > 0, EMDEE_ERR_INVALID, "L must be positive");
-        if (N == 0 || bitmask == 0) return;
-        EMDEE_REQUIRE(positions && atoms, EMDEE_ERR_INVALID, "positions/atoms are NULL");
-        const real *pos = (const real *)positions;
-        prepare(pos, L, model, atoms);
-        real *uf = (bitmask & EMDEE_FORCES) ? (real *)forces : nullptr, *ue = (bitmask & EMDEE_ENERGIES) ? (real *)energies : nullptr,
-             *uw = (bitmask & EMDEE_VIRIALS) ? (real *)virials : nullptr;
-        if (sys.brick_active) {
-            // the tiled kernels write the caller's arrays themselves (owner lane, caller index from perm)
-            sys.out_f = uf; sys.out_e = ue; sys.out_w = uw;
-            sys.ref_pos = pos;
-            sys.compute_forces(bitmask);
-            sys.ref_pos = nullptr;
-            sys.out_f = sys.out_e = sys.out_w = nullptr;
-        } else {
-            sys.compute_forces(bitmask);
-            sys.unsort(nullptr, nullptr, uf, ue, uw);
-        }
-        EMDEE_HIP_CHECK(hipGetLastError());
+        Pass<real> out = Pass<real>::force(bitmask);
+        if (bitmask & EMDEE_FORCES) out.f = (real *)forces;
+        if (bitmask & EMDEE_ENERGIES) out.e = (real *)energies;
+        if (bitmask & EMDEE_VIRIALS) out.w = (real *)virials;
+        run(out, positions, L, model, atoms);
     }
     // emdee_compute_virial_tensor: the per-atom virial tensors (6 x N, caller order) of the same pairs compute() sums
     void compute_tensor(void *tensor, const void *positions, double L, const emdee_lj_model &model, const emdee_lj_atom *atoms) override {
-        use_device(sys.ctx);
         EMDEE_REQUIRE(tensor || N == 0, EMDEE_ERR_INVALID, "tensor is NULL");
+        Pass<real> out = Pass<real>::force(TENSOR_PASS);
+        out.vt = (real *)tensor;
+        run(out, positions, L, model, atoms);
+    }
+    // one pass into the caller-order arrays of `out`: the tiled kernels write them themselves (owner lane, caller index from
+    // perm), staging the tiles of the Float32 reference arithmetic from the caller's positions; the direct kernels write the
+    // engine's arrays, which are then copied out
+    void run(const Pass<real> &out, const void *positions, double L, const emdee_lj_model &model, const emdee_lj_atom *atoms) {
+        use_device(sys.ctx);
         EMDEE_REQUIRE(L > 0, EMDEE_ERR_INVALID, "L must be positive");
-        if (N == 0) return;
+        if (N == 0 || out.mask == 0) return;
         EMDEE_REQUIRE(positions && atoms, EMDEE_ERR_INVALID, "positions/atoms are NULL");
-        const real *pos = (const real *)positions;
-        prepare(pos, L, model, atoms);
+        prepare((const real *)positions, L, model, atoms);
         if (sys.brick_active) {
-            sys.out_vt = (real *)tensor;
-            sys.ref_pos = pos;
-            sys.compute_forces(TENSOR_PASS);
-            sys.ref_pos = nullptr;
-            sys.out_vt = nullptr;
+            Pass<real> p = out;
+            p.pos = (const real *)positions;
+            sys.compute_forces(p);
         } else {
-            sys.compute_forces(TENSOR_PASS);
-            sys.unsort_tensor((real *)tensor);
+            sys.compute_forces(out.mask);
+            if (out.vt) sys.unsort_tensor(out.vt);
+            else sys.unsort(nullptr, nullptr, out.f, out.e, out.w);
         }
         EMDEE_HIP_CHECK(hipGetLastError());
     }
@@ -268,7 +259,7 @@ struct MdImpl : IMd {
             bool stale = sys.read_rebuild_flag();
             while (s < nsteps) {
                 if (stale) { sys.resort(); since_build = 0; }
-                const int ran = sys.fused_steps_run_ahead(dt, dt, nsteps - s, &stale);
+                const int ran = sys.fused_steps_run_ahead(Pass<real>::step(dt, dt), nsteps - s, &stale);
                 if (ran == 0) break;                          // direct kernels: one step at a time below
                 s += ran; since_build += ran;
             }
@@ -285,7 +276,7 @@ struct MdImpl : IMd {
             if (rb) { sys.resort(); since_build = 0; }
             if (s == nsteps) {
                 sys.compute_forces(EMDEE_FORCES);
-            } else if (!sys.fused_step(dt, dt, 0)) {
+            } else if (!sys.fused_step(Pass<real>::step(dt, dt))) {
                 sys.compute_forces(EMDEE_FORCES);
                 sys.kick_drift(dt, dt);
             }
@@ -488,7 +479,7 @@ struct MdImpl : IMd {
     }
     void forces(int bitmask, int phase = 0) override {
         use_device(sys.ctx);
-        sys.compute_forces(bitmask, phase);
+        sys.compute_forces(Pass<real>::force(bitmask, phase));
         current_mask = phase == 1 ? 0 : bitmask;
         EMDEE_HIP_CHECK(hipGetLastError());
     }
@@ -498,7 +489,7 @@ struct MdImpl : IMd {
     }
     bool fused_step(double dt, double kick, int phase) override {
         use_device(sys.ctx);
-        const bool ok = sys.fused_step(kick * dt, dt, phase);
+        const bool ok = sys.fused_step(Pass<real>::step(kick * dt, dt, phase));
         if (ok) { since_build += (phase != 1) ? 1 : 0; current_mask = 0; }
         EMDEE_HIP_CHECK(hipGetLastError());
         return ok;
@@ -544,7 +535,7 @@ struct MdImpl : IMd {
     // the tensor pass, unless the tensors are current: energies, virials and tensors; the forces stay as they are
     void tensor_pass() {
         if (current_mask & EMDEE_TENSOR) return;
-        sys.compute_forces(TENSOR_PASS, 0);
+        sys.compute_forces(TENSOR_PASS);
         current_mask |= TENSOR_PASS;
         EMDEE_HIP_CHECK(hipGetLastError());
     }
@@ -687,33 +678,29 @@ struct MdImpl : IMd {
                       "an engine with an hbonds table lacks the clusters' constraint virial; switch the coupling off first");
         set_groups(sys.HBONDS, "hbonds clusters", [&](auto &&check) { sys.own_tables.set_hbonds(atoms, dist, n_clusters, sys.n_owned, sys.stream(), check); });
     }
-    // emdee_md_set_ewald: all or nothing -- every refusal comes before the setting changes
-    void set_ewald(double alpha, const int32_t *kmax) override {
-        EMDEE_REQUIRE(alpha == 0.0 || (std::isfinite(alpha) && alpha > 0.0), EMDEE_ERR_INVALID, "set_ewald: alpha must be finite and >= 0");
-        if (alpha > 0.0) topo::check_ewald(alpha, kmax, std::sqrt(sys.model_d.rc2));
-        require_undivided("set_ewald");
-        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "set_ewald: no state loaded (call emdee_md_set_state first)");
-        EMDEE_REQUIRE(sys.has_charges() && !sys.charges_stale(), EMDEE_ERR_STATE, "set_ewald: the engine has no charges for its state (call emdee_md_set_coulomb first)");
-        EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "set_ewald: the box must be periodic in all three dimensions");
-        install("Ewald summation", "a decomposed run has none", [&] {
-            if (alpha > 0.0) sys.ewald.set(alpha, kmax); else sys.ewald.clear();
+    // emdee_md_set_ewald, emdee_md_set_pme: all or nothing -- every refusal comes before the setting changes.  check(): the host
+    // test of the setting; set(): EwaldRecip's setter (the mesh takes the place of the direct sum)
+    template <class Check, class Set>
+    void set_recip(const char *entry, const char *what, double alpha, Check &&check, Set &&set) {
+        EMDEE_REQUIRE(alpha == 0.0 || (std::isfinite(alpha) && alpha > 0.0), EMDEE_ERR_INVALID, "%s: alpha must be finite and >= 0", entry);
+        if (alpha > 0.0) check();
+        require_undivided(entry);
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "%s: no state loaded (call emdee_md_set_state first)", entry);
+        EMDEE_REQUIRE(sys.has_charges() && !sys.charges_stale(), EMDEE_ERR_STATE, "%s: the engine has no charges for its state (call emdee_md_set_coulomb first)", entry);
+        EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "%s: the box must be periodic in all three dimensions", entry);
+        install(what, "a decomposed run has none", [&] {
+            if (alpha > 0.0) set(); else sys.ewald.clear();
             sys.reset_ewald_error();
         });
         sys.check_ewald();
     }
-    // emdee_md_set_pme: as set_ewald, with the mesh in the place of the direct sum
+    void set_ewald(double alpha, const int32_t *kmax) override {
+        set_recip("set_ewald", "Ewald summation", alpha, [&] { topo::check_ewald(alpha, kmax, std::sqrt(sys.model_d.rc2)); },
+                  [&] { sys.ewald.set(alpha, kmax); });
+    }
     void set_pme(double alpha, const int32_t *grid, int32_t order) override {
-        EMDEE_REQUIRE(alpha == 0.0 || (std::isfinite(alpha) && alpha > 0.0), EMDEE_ERR_INVALID, "set_pme: alpha must be finite and >= 0");
-        if (alpha > 0.0) topo::check_pme(alpha, grid, order, std::sqrt(sys.model_d.rc2));
-        require_undivided("set_pme");
-        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "set_pme: no state loaded (call emdee_md_set_state first)");
-        EMDEE_REQUIRE(sys.has_charges() && !sys.charges_stale(), EMDEE_ERR_STATE, "set_pme: the engine has no charges for its state (call emdee_md_set_coulomb first)");
-        EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "set_pme: the box must be periodic in all three dimensions");
-        install("particle-mesh Ewald summation", "a decomposed run has none", [&] {
-            if (alpha > 0.0) sys.ewald.set_pme(alpha, grid, order); else sys.ewald.clear();
-            sys.reset_ewald_error();
-        });
-        sys.check_ewald();
+        set_recip("set_pme", "particle-mesh Ewald summation", alpha, [&] { topo::check_pme(alpha, grid, order, std::sqrt(sys.model_d.rc2)); },
+                  [&] { sys.ewald.set_pme(alpha, grid, order); });
     }
     void langevin_normals(uint64_t seed, uint64_t step, const int64_t *ids, int n, double *out) override {
         use_device(sys.ctx);
@@ -752,12 +739,10 @@ void Factory<real>::tiles(emdee_ctx *ctx, void *f, void *e, void *w, const void 
                   "a selected output is NULL");
     LJModel<real> m = make_model<real>(model);
     const int nt = (N + TILE - 1) / TILE;
-    if (mode == EMDEE_LITERAL)
-        hipLaunchKernelGGL((k_tiles<real, EMDEE_LITERAL>), dim3(nt), dim3(TILE_BLOCK), 0, ctx->stream, N, (const real *)pos,
-                           (real)L, atoms, m, bitmask, (real *)f, (real *)e, (real *)w);
-    else
-        hipLaunchKernelGGL((k_tiles<real, EMDEE_CUTOFF>), dim3(nt), dim3(TILE_BLOCK), 0, ctx->stream, N, (const real *)pos,
-                           (real)L, atoms, m, bitmask, (real *)f, (real *)e, (real *)w);
+    with_bool(mode == EMDEE_LITERAL, [&](auto literal) {
+        hipLaunchKernelGGL((k_tiles<real, decltype(literal)::value ? EMDEE_LITERAL : EMDEE_CUTOFF>), dim3(nt), dim3(TILE_BLOCK), 0, ctx->stream, N,
+                           (const real *)pos, (real)L, atoms, m, bitmask, (real *)f, (real *)e, (real *)w);
+    });
     EMDEE_HIP_CHECK(hipGetLastError());
 }
 
@@ -770,12 +755,10 @@ void Factory<real>::naive(emdee_ctx *ctx, void *f, void *e, void *w, const void 
     if (N == 0) return;
     EMDEE_REQUIRE(pos && atoms && f && e && w, EMDEE_ERR_INVALID, "naive: NULL array");
     LJModel<real> m = make_model<real>(model);
-    if (mode == EMDEE_LITERAL)
-        hipLaunchKernelGGL((k_naive<real, EMDEE_LITERAL>), dim3(blocks_for(N, 64)), dim3(64), 0, ctx->stream, N,
-                           (const real *)pos, (real)L, atoms, m, (real *)f, (real *)e, (real *)w);
-    else
-        hipLaunchKernelGGL((k_naive<real, EMDEE_CUTOFF>), dim3(blocks_for(N, 64)), dim3(64), 0, ctx->stream, N,
-                           (const real *)pos, (real)L, atoms, m, (real *)f, (real *)e, (real *)w);
+    with_bool(mode == EMDEE_LITERAL, [&](auto literal) {
+        hipLaunchKernelGGL((k_naive<real, decltype(literal)::value ? EMDEE_LITERAL : EMDEE_CUTOFF>), dim3(blocks_for(N, 64)), dim3(64), 0, ctx->stream,
+                           N, (const real *)pos, (real)L, atoms, m, (real *)f, (real *)e, (real *)w);
+    });
     EMDEE_HIP_CHECK(hipGetLastError());
 }
 

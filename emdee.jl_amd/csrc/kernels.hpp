@@ -661,25 +661,9 @@ __global__ void k_gather_sorted(int n, size_t pitch, GridP<real> g, const int *_
     cell_sorted[p] = cell_of[o] / nt;
 }
 
-// Operator path: same list, new caller positions -> refresh the records in place, each atom in the
-// periodic image nearest to where it was at build time (the caller may have wrapped or shifted it).
-template <typename real>
-__global__ void k_refresh_positions(int n, size_t pitch, GridP<real> g, const int *__restrict__ perm,
-                                    const real *__restrict__ pos, const emdee_lj_atom *__restrict__ atoms,
-                                    const real *__restrict__ xb, Rec<real> *__restrict__ rec, float *__restrict__ te) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    int i = perm[p];
-    emdee_lj_atom a = atoms[i];
-    const real bx = xb[p], by = xb[pitch + p], bz = xb[2 * pitch + p];
-    const real x = bx + min_image(pos[3 * (size_t)i] - bx, g.plen[0], g.pinv[0]);
-    const real y = by + min_image(pos[3 * (size_t)i + 1] - by, g.plen[1], g.pinv[1]);
-    const real z = bz + min_image(pos[3 * (size_t)i + 2] - bz, g.plen[2], g.pinv[2]);
-    store_rec<real>(rec, te, p, x, y, z, a.half_sigma, a.twice_sqrt_eps);
-}
-
-// Operator path, one pass per call: refresh the records (as k_refresh_positions), raise flags[1] if an atom has moved
-// more than sqrt(thr2) since the build (the caller then rebuilds and this refresh is discarded) and flags[5] if the
+// Operator path, one pass per call: same list, new caller positions -> refresh the records in place, each atom in the
+// periodic image nearest to where it was at build time (the caller may have wrapped or shifted it); raise flags[1] if an atom
+// has moved more than sqrt(thr2) since the build (the caller then rebuilds and this refresh is discarded) and flags[5] if the
 // LJAtom array is not one value repeated (which selects between the single-species and the general kernels).
 template <typename real>
 __global__ void k_refresh_check(int n, size_t pitch, GridP<real> g, const int *__restrict__ perm, const real *__restrict__ pos,
@@ -706,20 +690,6 @@ __global__ void k_refresh_check(int n, size_t pitch, GridP<real> g, const int *_
     // the first LJAtom itself rides along (flags[14], [15]): the host needs it for the single-species constants, and one
     // posted read-back of the words is cheaper than two copies and a synchronisation
     if (p == 0) { flags[14] = __float_as_int(first.half_sigma); flags[15] = __float_as_int(first.twice_sqrt_eps); }
-}
-
-// Operator path: has any atom moved more than sqrt(thr2) (minimum image) since the build?
-template <typename real>
-__global__ void k_check_displacement(int n, const int *__restrict__ inv_perm, const real *__restrict__ pos,
-                                     const real *__restrict__ xb, size_t pitch, GridP<real> g, real thr2,
-                                     int *__restrict__ flag) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int p = inv_perm[i];
-    real dx = min_image(pos[3 * (size_t)i] - xb[p], g.plen[0], g.pinv[0]);
-    real dy = min_image(pos[3 * (size_t)i + 1] - xb[pitch + p], g.plen[1], g.pinv[1]);
-    real dz = min_image(pos[3 * (size_t)i + 2] - xb[2 * pitch + p], g.plen[2], g.pinv[2]);
-    if (dx * dx + dy * dy + dz * dz > thr2) *flag = 1;
 }
 
 // ------------------------------------------------------------------------------------ neighbour build

@@ -114,6 +114,28 @@ static inline void allow_big_lds(K kernel, size_t bytes) {
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
+// What one force pass or one fused step is asked to do.  The defaults are a plain force pass over every brick into the engine's
+// own arrays; a launch that is neither (build, tables, filter, export, stats) takes a default one.
+template <typename real>
+struct Pass {
+    int mask = EMDEE_FORCES;
+    int phase = 0;                        // 0: every brick; 1 / 2: the interior / the boundary bricks (the two halves of a decomposed step)
+    double c = 0.0, dt = 0.0;             // a step: v += c f/m, x += dt v
+    const int *guard = nullptr;           // a step (device words, see NbSystem::fused_step): does nothing but raise *trigger when *guard is set,
+    int *trigger = nullptr;               // ... and raises *trigger when an atom has moved skin/2 since the last build (NULL: flags[1])
+    // operator path, tiled kernels only: the outputs go straight to these caller-order arrays (vt: the tensor pass's 6 x N array)
+    real *f = nullptr, *e = nullptr, *w = nullptr, *vt = nullptr;
+    const real *pos = nullptr;            // ... and the caller's positions, which the tiles of the Float32 reference arithmetic are staged from
+    // fused_step: copy the ghosts' current coordinates into the buffer that becomes current (callers that unpack fresh ghosts
+    // before every force evaluation, as emdee_dd_step does, do not need it); the caller has already queued prepare_noise(dt) for
+    // this step (it must precede work on another stream)
+    bool carry_ghosts = true, noise_ready = false;
+
+    bool to_caller() const { return f || e || w || vt; }
+    static Pass force(int mask, int phase = 0) { Pass p; p.mask = mask; p.phase = phase; return p; }
+    static Pass step(double c, double dt, int phase = 0) { Pass p; p.c = c; p.dt = dt; p.phase = phase; return p; }
+};
+
 template <typename real>
 struct NbSystem {
     emdee_ctx *ctx = nullptr;
@@ -556,7 +578,7 @@ struct NbSystem {
     }
 
     // ---------------------------------------------------------------- brick plumbing
-    BrickArgs<real> brick_args(int phase = 0) {
+    BrickArgs<real> brick_args(const Pass<real> &p = {}) {
         BrickArgs<real> a{};
         a.n = n_total; a.n_owned = n_owned; a.any_ghosts = has_ghosts ? 1 : 0;
         a.rec = rec.ptr; a.te = te.ptr; a.perm = perm.ptr; a.start = start();
@@ -564,9 +586,9 @@ struct NbSystem {
         a.nbr = nbr16.ptr; a.stride = stride; a.cnt = cnt.ptr; a.flags = flags.ptr;
         a.rlist2 = (real)(rlist * rlist); a.margin = build_margin; a.model = model; a.pitch = pitch;
         a.frc = frc.ptr; a.en = en.ptr; a.vir = vir.ptr; a.stats = stats.ptr;
-        a.phase = phase;   // only force launches are phased; build and stats always cover every brick
+        a.phase = p.phase;
         a.vel = vel.ptr; a.vel_next = vel2.ptr; a.xb = xb.ptr; a.inv_mass = with_mass ? im.ptr : nullptr; a.rec_next = rec2.ptr;
-        a.kick_c = (real)step_c; a.dt = (real)step_dt;
+        a.kick_c = (real)p.c; a.dt = (real)p.dt;
         a.uni_sigma2 = (real)uni_sigma2; a.uni_e4 = (real)uni_e4;
         a.uni = make_uni<real>(model, (real)uni_sigma, (real)uni_e4);
         a.idx_shift = idx_shift;
@@ -587,14 +609,14 @@ struct NbSystem {
         }
         a.rel = rel_now ? 1 : 0;
         for (int d = 0; d < 3; d++) { a.rcw[d] = rel_cw[d]; a.rlo[d] = rel_lo[d]; }
-        a.refmath = (sizeof(real) == 4 && refmath && ref_pos != nullptr) ? 1 : 0;
-        a.user_pos = ref_pos;
+        a.refmath = ref_tiles(p) ? 1 : 0;
+        a.user_pos = p.pos;
         a.thr2 = (real)(0.25 * skin * skin);
-        a.trigger = step_trigger ? step_trigger : flags.ptr + 1;
-        a.guard = step_guard;
+        a.trigger = p.trigger ? p.trigger : flags.ptr + 1;
+        a.guard = p.guard;
         a.btab = btab_valid ? btab.ptr : nullptr;
-        a.user_f = out_f; a.user_e = out_e; a.user_w = out_w;
-        a.vt = vt.ptr; a.user_vt = out_vt;
+        a.user_f = p.f; a.user_e = p.e; a.user_w = p.w;
+        a.vt = vt.ptr; a.user_vt = p.vt;
         a.noise = lgv_on ? noise.ptr : nullptr; a.lgv_c1 = lgv_on ? (real)lgv_c1 : (real)1;
         a.chg = charge_args();
         return a;
@@ -613,35 +635,40 @@ struct NbSystem {
     }
     template <class V>
     static constexpr int typed_min_stride() { return (typed_prefetch_blocks(V::G, V::THREADS, V::Shape::NOC) + 1) * EPL * V::G; }
+    // only force and step launches are phased: the stats launch takes a default Pass and covers every brick
+    template <class V, class K>
+    void launch_bricks(K kernel, size_t lds, const Pass<real> &p) {
+        allow_big_lds(kernel, lds);
+        const int blocks = (p.phase == 1 ? bgrid.ib_per_xcd : p.phase == 2 ? bgrid.bb_per_xcd : bgrid.per_xcd) * NXCD;
+        if (blocks == 0) return;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::THREADS), lds, stream(), brick_args(p));
+    }
     template <class V, int MODE, int BM>
-    void launch_typed_kernel() {
+    void launch_typed_kernel(const Pass<real> &p) {
         if constexpr (typed_variant<V>()) {
             constexpr int M = (MODE == BRICK_STATS) ? 0 : ((MODE == BRICK_STEP || BM == 1) ? 1 : BM == TENSOR_PASS ? TENSOR_PASS : 7);
-            auto kernel = k_typed<real, typename V::Shape, V::THREADS, V::G, MODE, M>;
-            const size_t lds = typed_force_lds_bytes<real, typename V::Shape, V::THREADS>(own_cap);
-            allow_big_lds(kernel, lds);
-            const int phase = (MODE == BRICK_FORCE || MODE == BRICK_STEP) ? force_phase : 0;
-            const int blocks = (phase == 1 ? bgrid.ib_per_xcd : phase == 2 ? bgrid.bb_per_xcd : bgrid.per_xcd) * NXCD;
-            if (blocks == 0) return;
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::THREADS), lds, stream(), brick_args(phase));
+            launch_bricks<V>(k_typed<real, typename V::Shape, V::THREADS, V::G, MODE, M>,
+                             typed_force_lds_bytes<real, typename V::Shape, V::THREADS>(own_cap), p);
         }
     }
 
     // variants a general-species box reaches (0, and 8 for long rows) carry the charged force instances
     template <class V>
     static constexpr bool charged_variant() { return std::is_same<V, BrickVariant<0>>::value || std::is_same<V, BrickVariant<8>>::value; }
+    // the Float32 reference arithmetic of an operator call: general-species tiles staged from the caller's positions
+    bool ref_tiles(const Pass<real> &p) const { return sizeof(real) == 4 && refmath && p.pos != nullptr; }
     template <class V, int MODE, int BM>
-    void launch_brick_kernel() {
-        if (typed_active) { launch_typed_kernel<V, MODE, BM>(); return; }
+    void launch_brick_kernel(const Pass<real> &p) {
+        if (typed_active) { launch_typed_kernel<V, MODE, BM>(p); return; }
         // charged engines: the general-species kernels with the reaction-field terms, whatever their LJ parameters
         if constexpr (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)) {
             if (has_charges()) {
                 if constexpr (charged_variant<V>()) {
                     if (has_ewald()) {
                         // (variant 0 only, see make_plan: the fp64 erfc does not fit the 128 registers of a 1024-thread workgroup)
-                        if constexpr (std::is_same<V, BrickVariant<0>>::value) launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED | EMDEE_EWALD, false>();
+                        if constexpr (std::is_same<V, BrickVariant<0>>::value) launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED | EMDEE_EWALD, false>(p);
                         else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "Ewald engine on brick variant %d", variant);
-                    } else launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED, false>();
+                    } else launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED, false>(p);
                 } else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "charged engine on brick variant %d", variant);
                 return;
             }
@@ -649,44 +676,26 @@ struct NbSystem {
         // single-species fast path for the kernels of the MD loop (default variant only)
         if constexpr (std::is_same<V, BrickVariant<0>>::value && (MODE == BRICK_STEP || (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)))) {
             // (the fp64 variant keeps coordinate planes only in LDS and needs the tile to fit their fixed pitch)
-            if (uniform_atoms && tile_cap <= SOA_SLOTS && idx_shift == PLANE_SHIFT && !(MODE == BRICK_FORCE && sizeof(real) == 4 && refmath && ref_pos != nullptr)) {
-                launch_brick_kernel_impl<V, MODE, BM, true>();
+            if (uniform_atoms && tile_cap <= SOA_SLOTS && idx_shift == PLANE_SHIFT && !(MODE == BRICK_FORCE && ref_tiles(p))) {
+                launch_brick_kernel_impl<V, MODE, BM, true>(p);
                 return;
             }
         }
-        launch_brick_kernel_impl<V, MODE, BM, false>();
+        launch_brick_kernel_impl<V, MODE, BM, false>(p);
     }
 
     template <class V, int MODE, int BM, bool UNI>
-    void launch_brick_kernel_impl() {
-        auto kernel = k_brick<real, typename V::Shape, V::THREADS, V::G, MODE, BM, UNI>;
-        const size_t lds = (UNI && MODE != BRICK_STATS) ? brick_force_lds_bytes_soa<real, typename V::Shape, V::THREADS>(own_cap)
-                                                        : lds_bytes;
-        allow_big_lds(kernel, lds);
-        const int phase = (MODE == BRICK_FORCE || MODE == BRICK_STEP) ? force_phase : 0;
-        const int blocks = (phase == 1 ? bgrid.ib_per_xcd : phase == 2 ? bgrid.bb_per_xcd : bgrid.per_xcd) * NXCD;
-        if (blocks == 0) return;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::THREADS), lds, stream(), brick_args(phase));
+    void launch_brick_kernel_impl(const Pass<real> &p) {
+        launch_bricks<V>(k_brick<real, typename V::Shape, V::THREADS, V::G, MODE, BM, UNI>,
+                         (UNI && MODE != BRICK_STATS) ? brick_force_lds_bytes_soa<real, typename V::Shape, V::THREADS>(own_cap) : lds_bytes, p);
     }
 
+    // the default variant has an instance for every mask; the tuning variants carry only the two masks the MD loop uses, and the
+    // tensor pass
     template <class V>
-    void launch_brick_force(int bitmask) {
-        if constexpr (std::is_same<V, BrickVariant<0>>::value) {
-            switch (bitmask) {
-                case 1: launch_brick_kernel<V, BRICK_FORCE, 1>(); return;
-                case 2: launch_brick_kernel<V, BRICK_FORCE, 2>(); return;
-                case 3: launch_brick_kernel<V, BRICK_FORCE, 3>(); return;
-                case 4: launch_brick_kernel<V, BRICK_FORCE, 4>(); return;
-                case 5: launch_brick_kernel<V, BRICK_FORCE, 5>(); return;
-                case 6: launch_brick_kernel<V, BRICK_FORCE, 6>(); return;
-                case TENSOR_PASS: launch_brick_kernel<V, BRICK_FORCE, TENSOR_PASS>(); return;
-                default: launch_brick_kernel<V, BRICK_FORCE, 7>(); return;
-            }
-        }
-        // tuning variants carry only the two masks the MD loop uses, and the tensor pass
-        if (bitmask == 1) launch_brick_kernel<V, BRICK_FORCE, 1>();
-        else if (bitmask == TENSOR_PASS) launch_brick_kernel<V, BRICK_FORCE, TENSOR_PASS>();
-        else launch_brick_kernel<V, BRICK_FORCE, 7>();
+    void launch_brick_force(const Pass<real> &p) {
+        using List = std::conditional_t<std::is_same<V, BrickVariant<0>>::value, AllMasks, LoopMasks>;
+        with_mask(List{}, p.mask, [&](auto m) { launch_brick_kernel<V, BRICK_FORCE, decltype(m)::value>(p); });
     }
 
     // brick decomposition + LDS tile capacity for the current cell populations; false if a tile cannot fit in LDS (then
@@ -962,6 +971,7 @@ struct NbSystem {
         }
         // (a state with a capacity hint -- decomposed domains -- sizes the list for it: no reallocation while atoms come and go)
         const size_t rows = std::max<size_t>((size_t)std::max(n, 1), cap_hint ? capacity : 0);
+        auto replan = [&] { kept = false; plan_valid = false; btab_valid = false; make_plan(); };
         for (int attempt = 0; attempt < 6; attempt++) {
             EMDEE_REQUIRE((double)n * stride < 1.7e10, EMDEE_ERR_OVERFLOW, "neighbour list would exceed 64 GiB");
             if (in_edit && !brick_active) { edit_abort = true; return; }   // (the direct kernels count atoms on the host: the caller reloads)
@@ -1043,10 +1053,7 @@ struct NbSystem {
             }
             if (kept && (!plan_holds(ctx->host_flags + 6) || ctx->host_flags[2] != 0)) {
                 // the populations outgrew the kept plan (the kernels skipped the bricks concerned): plan afresh and build again
-                kept = false;
-                plan_valid = false;
-                btab_valid = false;
-                make_plan();
+                replan();
                 continue;
             }
             if (brick_active && ctx->host_flags[4] != 0) {
@@ -1054,8 +1061,7 @@ struct NbSystem {
                 // 3-cell run is what picked the field): should they ever, the list is NOT taken -- this state goes on with 32-bit fields.
                 EMDEE_REQUIRE(!field16_blocked, EMDEE_ERR_OVERFLOW, "neighbour build: a lane's share of a tile row (%d) overflows its hit field", ctx->host_flags[4]);
                 field16_blocked = true;
-                kept = false; plan_valid = false; btab_valid = false;
-                make_plan();
+                replan();
                 continue;
             }
             EMDEE_REQUIRE(ctx->host_flags[2] == 0, EMDEE_ERR_OVERFLOW, "LDS tile overflow (%d records > %d)",
@@ -1072,10 +1078,7 @@ struct NbSystem {
             if (brick_active && typed_active && !build_fits_lds()) {
                 // rows longer than the typed build's LDS row buffers can take: this state goes on with the general-species kernels
                 typed_blocked = true;
-                plan_valid = false;
-                btab_valid = false;
-                kept = false;
-                make_plan();
+                replan();
                 continue;
             }
             if (brick_active && !build_fits_lds()) { brick_active = false; idx_shift = 0; btab_valid = false; plan_valid = false; }
@@ -1199,35 +1202,32 @@ struct NbSystem {
                       "small); set the charges again");
     }
 
-    // after a force pass: the scaled 1-4 terms on top
-    void add_pairs14(int bitmask) {
+    // after a force pass: the scaled 1-4 terms on top (the _q twins of a charged engine take the charges as one more argument)
+    void add_pairs14(const Pass<real> &p) {
         if (!has_14() || n_total == 0) return;
         check_tables("1-4 table");
-        const bool user = brick_active && (out_f || out_e || out_w || out_vt);
-        if (has_charges()) {
-            auto kq = has_ewald() ? ((bitmask & EMDEE_TENSOR) ? k_pairs14_q<real, true, true> : k_pairs14_q<real, false, true>)
-                                  : ((bitmask & EMDEE_TENSOR) ? k_pairs14_q<real, true> : k_pairs14_q<real, false>);
-            hipLaunchKernelGGL(kq, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
-                               pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
-                               user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
-                               user ? out_vt : (real *)nullptr, charge_args());
-            return;
-        }
-        auto kernel = (bitmask & EMDEE_TENSOR) ? k_pairs14<real, true> : k_pairs14<real, false>;
-        hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
-                           pair_keys(), grid, model, (real)tables->scale14, bitmask, frc.ptr, en.ptr, vir.ptr,
-                           user ? out_f : (real *)nullptr, user ? out_e : (real *)nullptr, user ? out_w : (real *)nullptr, vt.ptr,
-                           user ? out_vt : (real *)nullptr);
+        auto launch = [&](auto kernel, auto... extra) {
+            hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
+                               pair_keys(), grid, model, (real)tables->scale14, p.mask, frc.ptr, en.ptr, vir.ptr, p.f, p.e, p.w, vt.ptr, p.vt,
+                               extra...);
+        };
+        const bool tensor = p.mask & EMDEE_TENSOR;
+        if (has_charges())
+            with_bool(has_ewald(), [&](auto ew) {
+                with_bool(tensor, [&](auto t) { launch(k_pairs14_q<real, decltype(t)::value, decltype(ew)::value>, charge_args()); });
+            });
+        else with_bool(tensor, [&](auto t) { launch(k_pairs14<real, decltype(t)::value>); });
     }
 
     // after a force pass: the bonded terms on top (k_bonded; not on the operator path, which has no bonded tables)
-    void add_bonded(int bitmask) {
+    void add_bonded(const Pass<real> &p) {
         if (!has_bonded() || n_total == 0) return;
         check_tables("bonded tables");
-        auto kernel = (bitmask & EMDEE_TENSOR) ? k_bonded<real, true> : k_bonded<real, false>;
-        hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
-                           pair_keys(), bonded_keys(), tables->template bonded_params<real>(), grid, bitmask, frc.ptr, en.ptr,
-                           vir.ptr, vt.ptr, flags.ptr + W_BONDED);
+        with_bool(p.mask & EMDEE_TENSOR, [&](auto tensor) {
+            hipLaunchKernelGGL((k_bonded<real, decltype(tensor)::value>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned,
+                               pitch, view(), perm.ptr, pair_keys(), bonded_keys(), tables->template bonded_params<real>(), grid, p.mask, frc.ptr,
+                               en.ptr, vir.ptr, vt.ptr, flags.ptr + W_BONDED);
+        });
     }
     // ---------------------------------------------------------------- Ewald summation (emdee_md_set_ewald)
     // With ewald.alpha > 0 a charged engine's pair loops take the erfc-screened terms (the EMDEE_EWALD instances), the row filter
@@ -1248,20 +1248,21 @@ struct NbSystem {
         }
         EMDEE_REQUIRE(!ewald_fault.latched, EMDEE_ERR_STATE, "Ewald: an excluded or 1-4 pair spans more than rc + skin (reported before): replace the tables or the state");
     }
-    void add_ewald(int bitmask) {
+    void add_ewald(const Pass<real> &p) {
         if (!has_ewald() || n_total == 0) return;
         EMDEE_REQUIRE(!has_ghosts && n_total == n_owned && tables == &own_tables, EMDEE_ERR_STATE,
                       "Ewald summation on an engine with ghosts or a domain's engine: switch it off (emdee_md_set_ewald) or load a state without ghosts");
-        EMDEE_REQUIRE(!(brick_active && (out_f || out_e || out_w || out_vt)), EMDEE_ERR_STATE, "Ewald summation is not on the operator path");
+        EMDEE_REQUIRE(!p.to_caller(), EMDEE_ERR_STATE, "Ewald summation is not on the operator path");
         if (has_excl()) {
             check_tables("exclusion table");
-            auto kernel = (bitmask & EMDEE_TENSOR) ? k_ewald_struck<real, true> : k_ewald_struck<real, false>;
-            hipLaunchKernelGGL(kernel, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, view(), perm.ptr,
-                               pair_keys(), tables->x_start.ptr, grid, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr, charge_args(),
-                               flags.ptr + W_EWALD);
+            with_bool(p.mask & EMDEE_TENSOR, [&](auto tensor) {
+                hipLaunchKernelGGL((k_ewald_struck<real, decltype(tensor)::value>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total,
+                                   n_owned, pitch, view(), perm.ptr, pair_keys(), tables->x_start.ptr, grid, p.mask, frc.ptr, en.ptr, vir.ptr,
+                                   vt.ptr, charge_args(), flags.ptr + W_EWALD);
+            });
         }
         Timed t(this, T_EWALD);
-        ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, tables->q_abs, bitmask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
+        ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, tables->q_abs, p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
     }
     // ---------------------------------------------------------------- constraint groups (Topology::set_rigid3, set_hbonds)
     // The three stages MdImpl::step_closed puts around the unchanged kick + drift, force pass and kick, and the check of a table
@@ -1361,40 +1362,30 @@ struct NbSystem {
     }
     void check_state(ConstraintGroup &g) { check_state(g, table(g).atoms.ptr, table(g).geom.ptr, table(g).atoms_h, table(g).n); }
 
-    void add_post_terms(int bitmask) {
-        add_pairs14(bitmask);
-        add_bonded(bitmask);
-        add_ewald(bitmask);
+    void add_post_terms(const Pass<real> &p) {
+        add_pairs14(p);
+        add_bonded(p);
+        add_ewald(p);
     }
 
     // ---------------------------------------------------------------- forces
-    const int *direct_guard = nullptr;    // guarded_split_step: the direct kernels of a queued step look at this word first
+    // (p.guard: the direct kernels of a queued step, guarded_split_step, look at this word first; the _q twins of a charged engine
+    // take the charges as one more argument)
     template <int BM>
-    void launch_direct_force() {
+    void launch_direct_force(const Pass<real> &p) {
         const int n = n_total;
-        int nblocks = (n + FORCE_ATOMS - 1) / FORCE_ATOMS;
-        int per_xcd = (nblocks + NXCD - 1) / NXCD;
+        const int nblocks = (n + FORCE_ATOMS - 1) / FORCE_ATOMS, per_xcd = (nblocks + NXCD - 1) / NXCD;
+        auto launch = [&](auto kernel, auto... extra) {
+            hipLaunchKernelGGL(kernel, dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned, per_xcd, view(), perm.ptr, nbr.ptr,
+                               stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr, vir.ptr, p.guard, vt.ptr, extra...);
+        };
         if constexpr (BM == 1 || BM == 7 || BM == TENSOR_PASS) {
-          if (has_ewald()) {
-            hipLaunchKernelGGL((k_lj_force_nbr_q<real, BM | EMDEE_EWALD>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
-                               per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
-                               vir.ptr, direct_guard, vt.ptr, charge_args());
-            return;
-          }
-          if (has_charges()) {
-            hipLaunchKernelGGL((k_lj_force_nbr_q<real, BM>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
-                               per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
-                               vir.ptr, direct_guard, vt.ptr, charge_args());
-            return;
-          }
+            if (has_ewald()) return launch(k_lj_force_nbr_q<real, BM | EMDEE_EWALD>, charge_args());
+            if (has_charges()) return launch(k_lj_force_nbr_q<real, BM>, charge_args());
         }
-        hipLaunchKernelGGL((k_lj_force_nbr<real, BM>), dim3(per_xcd * NXCD), dim3(FORCE_BLOCK), 0, stream(), n, n_owned,
-                           per_xcd, view(), perm.ptr, nbr.ptr, stride, cnt.ptr, grid, model, pitch, frc.ptr, en.ptr,
-                           vir.ptr, direct_guard, vt.ptr);
+        launch(k_lj_force_nbr<real, BM>);
     }
 
-    int force_phase = 0;
-    double step_c = 0.0, step_dt = 0.0;
     bool uniform_atoms = false;            // every atom has the same LJAtom (checked when a state is loaded)
     double uni_sigma2 = 0.0, uni_e4 = 0.0, uni_sigma = 1.0;
     // neighbour entries = tile slot << idx_shift; single-species boxes store byte offsets into the coordinate planes
@@ -1490,28 +1481,19 @@ struct NbSystem {
 
     // One inner velocity-Verlet step as a single kernel: f(x_k), v += c f/m, x_{k+1} = x_k + dt v written to
     // the other position buffer.  False if the brick kernels are not in use (caller runs the split kernels).
-    // guard / trigger (device words, optional): the launch does nothing but raise *trigger when *guard is set, and
-    // raises *trigger when an atom it moved is now skin/2 away from its position at the last build (default: flags[1]).
-    // carry_ghosts: copy the ghosts' current coordinates into the buffer that becomes current (callers that unpack
-    // fresh ghosts before every force evaluation, as emdee_dd_step does, do not need it).
-    // noise_ready: the caller has already queued prepare_noise(dt) for this step (it must precede work on another stream).
-    bool fused_step(double c, double dt, int phase = 0, const int *guard = nullptr, int *trigger = nullptr,
-                    bool carry_ghosts = true, bool noise_ready = false) {
+    // What the step obeys -- guard and trigger words, the halves of a decomposed step, ghosts, noise -- is in the Pass.
+    bool fused_step(const Pass<real> &p) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         if (!brick_active || n_total == 0) return false;
         if (has_post()) return false;                          // (the scaled 1-4 and bonded terms are added behind a force pass: the split kernels)
-        if (phase != 2 && !noise_ready) prepare_noise(dt);   // phases 1 and 2 are the two halves of one step
+        if (p.phase != 2 && !p.noise_ready) prepare_noise(p.dt);   // phases 1 and 2 are the two halves of one step
         {
-            Timed t(this, phase == 2 ? T_STEP_BOUNDARY : T_STEP);
-            step_c = c; step_dt = dt;
-            force_phase = phase;
-            step_guard = guard; step_trigger = trigger;
-            with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(); });
-            step_guard = nullptr; step_trigger = nullptr;
+            Timed t(this, p.phase == 2 ? T_STEP_BOUNDARY : T_STEP);
+            with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(p); });
         }
-        if (phase != 1 && lgv_on) lgv_step++;
-        if (phase != 1) {
-            if (carry_ghosts && has_ghosts)
+        if (p.phase != 1 && lgv_on) lgv_step++;
+        if (p.phase != 1) {
+            if (p.carry_ghosts && has_ghosts)
                 hipLaunchKernelGGL((k_copy_ghost_records<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(),
                                    n_total, n_owned, perm.ptr, rec.ptr, rec2.ptr);
             swap_step_buffers();
@@ -1527,26 +1509,23 @@ struct NbSystem {
     // (>= 1; 0 if the brick kernels are not in use); *stale says whether the last of them asked for a rebuild.
     static constexpr int RUN_AHEAD = 4;
     int run_ahead = RUN_AHEAD;            // EMDEE_RUN_AHEAD=1: one step per round trip (profiling: no no-op launches)
-    int *step_trigger = nullptr;
-    const int *step_guard = nullptr;
-    int fused_steps_run_ahead(double c, double dt, int want, bool *stale) {
+    int fused_steps_run_ahead(Pass<real> p, int want, bool *stale) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         *stale = false;
         if (!brick_active || n_total == 0 || has_ghosts || has_post()) return 0;
         const int B = std::max(1, std::min(want, run_ahead));
         int *words = flags.ptr + 9;                          // flags[9 .. 9 + RUN_AHEAD)
         EMDEE_HIP_CHECK(hipMemsetAsync(words, 0, B * sizeof(int), stream()));
-        step_c = c; step_dt = dt; force_phase = 0;
+        p.phase = 0;
         for (int i = 0; i < B; i++) {
-            prepare_noise(dt);
+            prepare_noise(p.dt);
             if (lgv_on) lgv_step++;
             Timed t(this, T_STEP);
-            step_trigger = words + i;
-            step_guard = i ? words + i - 1 : nullptr;
-            with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(); });
+            p.trigger = words + i;
+            p.guard = i ? words + i - 1 : nullptr;
+            with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(p); });
             swap_step_buffers();
         }
-        step_trigger = nullptr; step_guard = nullptr;
         read_back_words(ctx, stream(), words, B, ctx->host_flags + 9);
         int ran = B;
         for (int i = 0; i < B; i++)
@@ -1557,45 +1536,34 @@ struct NbSystem {
         return ran;
     }
 
-    // operator path: outputs of the next compute_forces go straight to these caller-order arrays (tiled kernels only)
-    real *out_f = nullptr, *out_e = nullptr, *out_w = nullptr;
-    real *out_vt = nullptr;               // ... and the tensor pass's 6 x N array
     // per-atom virial tensors of the last tensor pass (TENSOR_PASS): six planes of pitch slots, allocated on first use
     DevBuf<real> vt;
     // fp32 operator path: pair geometry in the reference's own Float32 arithmetic (scaled positions, minimum image per
     // pair; brick.hpp BrickArgs::refmath) -- what keeps compute_nonbonded! within the reference's 1e-4 of its CPU loop
     bool refmath = false;
-    const real *ref_pos = nullptr;        // the caller's positions of the current operator call (refmath tiles are staged from them)
 
-    void compute_forces(int bitmask, int phase = 0) {
+    void compute_forces(const Pass<real> &request) {
+        Pass<real> p = request;
         EMDEE_REQUIRE(has_list, EMDEE_ERR_STATE, "no neighbour list");
-        EMDEE_REQUIRE((bitmask >= 0 && bitmask <= 7) || bitmask == TENSOR_PASS, EMDEE_ERR_INVALID, "bitmask must be a combination of 1|2|4");
-        if (n_total == 0 || bitmask == 0) return;
+        EMDEE_REQUIRE((p.mask >= 0 && p.mask <= 7) || p.mask == TENSOR_PASS, EMDEE_ERR_INVALID, "bitmask must be a combination of 1|2|4");
+        EMDEE_REQUIRE(brick_active || !p.to_caller(), EMDEE_ERR_STATE, "only the tiled kernels write caller-order outputs");
+        if (n_total == 0 || p.mask == 0) return;
         ensure_charges();
         // charged engines have instances for forces, all outputs and the tensor pass: a narrower request runs all outputs (and the
         // terms behind the force pass follow the kernel's outputs)
-        if (has_charges() && bitmask != EMDEE_FORCES && bitmask != TENSOR_PASS) bitmask = 7;
-        if (bitmask & EMDEE_TENSOR) vt.ensure(6 * pitch);
-        if (!brick_active && phase == 1) return;   // the direct kernels have no brick phases: all work in phase 2
+        if (has_charges() && p.mask != EMDEE_FORCES && p.mask != TENSOR_PASS) p.mask = 7;
+        if (p.mask & EMDEE_TENSOR) vt.ensure(6 * pitch);
+        if (!brick_active && p.phase == 1) return;   // the direct kernels have no brick phases: all work in phase 2
         Timed t(this, T_FORCE);
-        force_phase = brick_active ? phase : 0;
         if (brick_active) {
-            with_brick_variant(variant, [&](auto v) { launch_brick_force<decltype(v)>(bitmask); });
-            if (phase != 1) add_post_terms(bitmask);         // (once per force pass: behind its last half)
+            with_brick_variant(variant, [&](auto v) { launch_brick_force<decltype(v)>(p); });
+            if (p.phase != 1) add_post_terms(p);             // (once per force pass: behind its last half)
             return;
         }
-        switch (bitmask) {
-            case 1: launch_direct_force<1>(); break;
-            case 2: launch_direct_force<2>(); break;
-            case 3: launch_direct_force<3>(); break;
-            case 4: launch_direct_force<4>(); break;
-            case 5: launch_direct_force<5>(); break;
-            case 6: launch_direct_force<6>(); break;
-            case TENSOR_PASS: launch_direct_force<TENSOR_PASS>(); break;
-            default: launch_direct_force<7>(); break;
-        }
-        add_post_terms(bitmask);
+        with_mask(AllMasks{}, p.mask, [&](auto m) { launch_direct_force<decltype(m)::value>(p); });
+        add_post_terms(p);
     }
+    void compute_forces(int bitmask) { compute_forces(Pass<real>::force(bitmask)); }
 
     // ---------------------------------------------------------------- integrator
     void kick_drift(double c, double dt, int *trigger = nullptr, const int *guard = nullptr) {
@@ -1616,14 +1584,14 @@ struct NbSystem {
     // Keeps a decomposed run's message sequence independent of which kernels a domain uses (emdee_dd_step).  Also the form of a
     // tiled domain with a 1-4 table (force pass, 1-4 terms, kick + drift): its force pass ignores the guard and leaves forces
     // at unmoved positions -- the rebuild the raised word brings evaluates them afresh.
-    void guarded_split_step(double c, double dt, const int *guard, int *trigger) {
+    void guarded_split_step(const Pass<real> &p) {
         EMDEE_REQUIRE(has_list && sorted && with_vel, EMDEE_ERR_STATE, "no state loaded");
         EMDEE_REQUIRE(!brick_active || has_post(), EMDEE_ERR_STATE, "guarded_split_step is the direct kernels' form of fused_step");
         if (n_total == 0) return;
-        direct_guard = guard;
-        compute_forces(EMDEE_FORCES, 0);
-        direct_guard = nullptr;
-        kick_drift(c, dt, trigger, guard);
+        Pass<real> f = Pass<real>::force(EMDEE_FORCES);
+        f.guard = p.guard;
+        compute_forces(f);
+        kick_drift(p.c, p.dt, p.trigger, p.guard);
     }
 
     void kick(double c) {
@@ -1634,7 +1602,7 @@ struct NbSystem {
                            perm.ptr, vel.ptr, frc.ptr, with_mass ? im.ptr : nullptr, (real)c);
     }
 
-    // blocking read of the rebuild trigger raised by kick_drift / check_user_displacement
+    // blocking read of the rebuild trigger raised by kick_drift and the step kernels
     bool read_rebuild_flag() {
         read_back_words(ctx, stream(), flags.ptr + 1, 1, ctx->host_flags + 1);
         return ctx->host_flags[1] != 0;
@@ -1657,15 +1625,20 @@ struct NbSystem {
     // out[0..5] = sum of the owned atoms' virial tensors (the last tensor pass), out[6..11] = kinetic tensor sum m v^a v^b;
     // (xx, yy, zz, xy, xz, yz), fp64, blocking
     DevBuf<double> tpartial;
-    void tensor_sums(double out[TENSOR_SUMS]) {
-        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
-        if (n_total == 0) return;
-        int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+    // queues the atomic sums; they land behind the partials, where a second total has room next to them
+    double *queue_tensor_sums() {
+        const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
         tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);
         double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
         hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
                            vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
         hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot);
+        return tot;
+    }
+    void tensor_sums(double out[TENSOR_SUMS]) {
+        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
+        if (n_total == 0) return;
+        const double *tot = queue_tensor_sums();
         EMDEE_HIP_CHECK(hipMemcpyAsync(out, tot, TENSOR_SUMS * sizeof(double), hipMemcpyDeviceToHost, stream()));
         EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
     }
@@ -1678,15 +1651,10 @@ struct NbSystem {
         if (n_total == 0) return;
         const int n_mol = has_rigid() ? tables->rigid.n : 0;
         if (n_mol == 0) { tensor_sums(out); return; }
-        int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-        tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);
-        double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
-        hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
-                           vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
-        hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot);
+        double *tot = queue_tensor_sums();
+        const int nb = std::min((int)blocks_for(n_mol, RED_BLOCK), RED_MAX_BLOCKS);
         {
             Timed t(this, T_MOLECULAR);
-            nb = std::min((int)blocks_for(n_mol, RED_BLOCK), RED_MAX_BLOCKS);
             hipLaunchKernelGGL((k_molecule_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), settle_args(), (const real *)frc.ptr,
                                tpartial.ptr);
         }
@@ -1708,7 +1676,7 @@ struct NbSystem {
         if (has_list && n_total > 0) {
             EMDEE_HIP_CHECK(hipMemsetAsync(stats.ptr, 0, 3 * sizeof(unsigned long long), stream()));
             if (brick_active) {
-                with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STATS, 0>(); });
+                with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STATS, 0>(Pass<real>{}); });
             } else {
                 int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
                 hipLaunchKernelGGL((k_list_stats<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, view(), nbr.ptr,
@@ -1768,16 +1736,6 @@ struct NbSystem {
                            rel_grid(rel_now, cell_sorted.ptr));
     }
 
-    // operator path: does the cached list still cover these caller positions?
-    bool user_positions_moved(const real *pos) {
-        if (n_total == 0) return false;
-        real thr = (real)(0.5 * skin);
-        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 1, 0, sizeof(int), stream()));
-        hipLaunchKernelGGL((k_check_displacement<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total,
-                           inv_perm.ptr, pos, xb.ptr, pitch, grid, thr * thr, flags.ptr + 1);
-        return read_rebuild_flag();
-    }
-
     // operator path, list kept: refresh + displacement test + species test in one pass and one read-back.
     // Returns true if the list no longer covers the positions (the caller reloads).
     bool refresh_and_check(const real *pos, const emdee_lj_atom *atoms) {
@@ -1798,12 +1756,6 @@ struct NbSystem {
             set_uniform_constants(first);
         }
         return ctx->host_flags[1] != 0;
-    }
-
-    void refresh_user(const real *pos, const emdee_lj_atom *atoms) {
-        if (n_total == 0) return;
-        hipLaunchKernelGGL((k_refresh_positions<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total,
-                           pitch, grid, perm.ptr, pos, atoms, xb.ptr, rec.ptr, te.ptr);
     }
 };
 

@@ -278,12 +278,10 @@ struct PmeRecip {
             while (((size_t)1 << il) < stride[d]) il++;       // (inner = the stride of the axis)
             const size_t nlines = total / K, lines = FFT_TILE / K;
             const dim3 blocks((unsigned)((nlines + lines - 1) / lines));
-            if (d == 2)
-                hipLaunchKernelGGL((k_pme_fft<INVERSE, true>), blocks, dim3(PME_BLOCK), 0, s, K, lg, nlines, stride[d], il, outer[d],
-                                   tw.ptr + (size_t)d * 128, mesh);
-            else
-                hipLaunchKernelGGL((k_pme_fft<INVERSE, false>), blocks, dim3(PME_BLOCK), 0, s, K, lg, nlines, stride[d], il, outer[d],
-                                   tw.ptr + (size_t)d * 128, mesh);
+            with_bool(d == 2, [&](auto contiguous) {
+                hipLaunchKernelGGL((k_pme_fft<INVERSE, decltype(contiguous)::value>), blocks, dim3(PME_BLOCK), 0, s, K, lg, nlines, stride[d], il,
+                                   outer[d], tw.ptr + (size_t)d * 128, mesh);
+            });
         }
     }
 
