@@ -130,6 +130,9 @@ struct Pass {
     // before every force evaluation, as emdee_dd_step does, do not need it); the caller has already queued prepare_noise(dt) for
     // this step (it must precede work on another stream)
     bool carry_ghosts = true, noise_ready = false;
+    // a force pass whose kernel instance writes more outputs than `mask` selects (NbSystem::runs_all_outputs): the engine's planes of
+    // the outputs left out are not to be touched, the kernel writes those to the spare planes
+    bool spare_unselected = false;
 
     bool to_caller() const { return f || e || w || vt; }
     static Pass force(int mask, int phase = 0) { Pass p; p.mask = mask; p.phase = phase; return p; }
@@ -586,6 +589,11 @@ struct NbSystem {
         a.nbr = nbr16.ptr; a.stride = stride; a.cnt = cnt.ptr; a.flags = flags.ptr;
         a.rlist2 = (real)(rlist * rlist); a.margin = build_margin; a.model = model; a.pitch = pitch;
         a.frc = frc.ptr; a.en = en.ptr; a.vir = vir.ptr; a.stats = stats.ptr;
+        if (p.spare_unselected) {
+            if (!(p.mask & EMDEE_FORCES)) a.frc = spare.ptr;
+            if (!(p.mask & EMDEE_ENERGIES)) a.en = spare.ptr + 3 * pitch;
+            if (!(p.mask & EMDEE_VIRIALS)) a.vir = spare.ptr + 4 * pitch;
+        }
         a.phase = p.phase;
         a.vel = vel.ptr; a.vel_next = vel2.ptr; a.xb = xb.ptr; a.inv_mass = with_mass ? im.ptr : nullptr; a.rec_next = rec2.ptr;
         a.kick_c = (real)p.c; a.dt = (real)p.dt;
@@ -692,6 +700,9 @@ struct NbSystem {
 
     // the default variant has an instance for every mask; the tuning variants carry only the two masks the MD loop uses, and the
     // tensor pass
+    // (a narrower request on those, and on the typed kernels, runs the all-outputs instance: runs_all_outputs)
+    bool runs_all_outputs(int mask) const { return brick_active && mask >= 2 && mask <= 6 && (typed_active || variant != 0); }
+    DevBuf<real> spare;                                      // three force planes, energies, virials: what such a pass is not asked for
     template <class V>
     void launch_brick_force(const Pass<real> &p) {
         using List = std::conditional_t<std::is_same<V, BrickVariant<0>>::value, AllMasks, LoopMasks>;
@@ -770,8 +781,8 @@ struct NbSystem {
             }
             plan_span3 = max_span3 + max_span3 / 16 + 2;
             if (std::getenv("EMDEE_DEBUG_PLAN"))
-                std::fprintf(stderr, "emdee plan: bricks %d x %d x %d, tile_cap %d (max %d), own_cap %d (max %d), max 3-cell span %d, x sub-bins %d K %d\n", bgrid.nb[0],
-                             bgrid.nb[1], bgrid.nb[2], tile_cap, max_tile, own_cap, max_own, max_span3, nsub, sub_k());
+                std::fprintf(stderr, "emdee plan: bricks %d x %d x %d, tile_cap %d (max %d), own_cap %d (max %d), max 3-cell span %d, x sub-bins %d K %d, variant %d\n", bgrid.nb[0],
+                             bgrid.nb[1], bgrid.nb[2], tile_cap, max_tile, own_cap, max_own, max_span3, nsub, sub_k(), variant);
             build_alg = (!field16_blocked && (V::GB == 8 || V::GB == 16) && plan_span3 <= BUILD2_FIELD * V::GB) ? 3 : 1;
             // crowded tile rows (long cutoffs): the same build with one 32-bit hit field per row
             if (build_alg == 1 && (V::GB == 8 || V::GB == 16) && plan_span3 <= 32 * V::GB) build_alg = 5;
@@ -843,7 +854,10 @@ struct NbSystem {
         }
         // the build kernel's LDS (fp32 tile + tables + one row buffer per lane group) must fit as well: very dense or
         // very inhomogeneous boxes with a long cutoff fall back to the direct (global-gather) kernels
-        if (brick_active && !build_fits_lds()) brick_active = false;
+        if (brick_active && !build_fits_lds()) {
+            brick_active = false;
+            if (std::getenv("EMDEE_DEBUG_PLAN")) std::fprintf(stderr, "emdee plan: the build kernel's tile does not fit LDS: direct kernels\n");
+        }
         idx_shift = (brick_active && variant == 0 && uniform_atoms && !has_charges() && tile_cap <= SOA_SLOTS) ? PLANE_SHIFT : 0;
         // two species: the typed kernels (typed.hpp), if the tile fits their coordinate planes, no three cells of a tile row hold
         // more atoms of one species than the 16-bit hit fields of their build take, and both kernels fit LDS
@@ -1554,6 +1568,12 @@ struct NbSystem {
         if (has_charges() && p.mask != EMDEE_FORCES && p.mask != TENSOR_PASS) p.mask = 7;
         if (p.mask & EMDEE_TENSOR) vt.ensure(6 * pitch);
         if (!brick_active && p.phase == 1) return;   // the direct kernels have no brick phases: all work in phase 2
+        // an all-outputs instance behind a narrower request into the engine's own arrays: the planes the request leaves out stay as
+        // they are (include/emdee_hip.h, emdee_md_forces), and the terms behind the pass switch on the request
+        if (runs_all_outputs(p.mask) && !p.to_caller()) {
+            spare.ensure(5 * pitch);
+            p.spare_unselected = true;
+        }
         Timed t(this, T_FORCE);
         if (brick_active) {
             with_brick_variant(variant, [&](auto v) { launch_brick_force<decltype(v)>(p); });

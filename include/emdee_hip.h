@@ -464,7 +464,9 @@ int32_t emdee_md_kick_drift(emdee_md *md, double dt, double kick);
  * ghost cell (can run while the halo exchange is in flight); phase 2: the remaining bricks.
  * A charged engine (emdee_md_set_coulomb) has kernels for EMDEE_FORCES and for all three outputs only: a narrower request
  * (2 .. 6) evaluates all three, so the force plane is rewritten too, with the all-outputs kernel's rounding (an uncharged
- * engine leaves it alone). */
+ * engine leaves it alone: every plane the bitmask leaves out keeps its bits, on every kernel family -- where the all-outputs
+ * kernel serves a narrower request, the 1024-thread brick variant and the two-species kernels, its other outputs go to spare
+ * planes). */
 int32_t emdee_md_forces(emdee_md *md, int32_t bitmask, int32_t phase);
 int32_t emdee_md_kick(emdee_md *md, double dt);              /* v += (dt/2m) f */
 /* One inner step as a single kernel: f = F(x), v += kick (dt/m) f, x += dt v, with the new positions

@@ -71,14 +71,15 @@ def _scales(i, j, N, excl, p14, s14):
 
 
 def nonbonded(pos, lo, lengths, periodic, rc, rs, atoms, excl=None, p14=None, lj14scale=1.0, rows=None,
-              charges=None, coulomb_k=1.0, eps_rf=np.inf, coulomb14scale=1.0, lj=True):
+              charges=None, coulomb_k=1.0, eps_rf=np.inf, coulomb14scale=1.0, lj=True, oracle=None):
     """dict(f (N, 3), e (N,), w (N,), t (N, 6)) of the pair terms.  rows: sampled mode -- only these atoms' entries are
     filled (whole: every partner of theirs is visited), the others stay zero.  charges: adds the reaction field; lj=False
-    leaves the Lennard-Jones part out (the Coulomb part alone)."""
+    leaves the Lennard-Jones part out (the Coulomb part alone).  oracle: on a cubic periodic box the candidate pairs come from
+    the oracle's cell list in place of the N^2 table (virial_tensor_ref.pairs_in_range); the terms are summed here all the same."""
     pos = np.asarray(pos, dtype=np.float64)
     N = pos.shape[0]
     check_inside(pos, lo, lengths, periodic)
-    i, j, d = vt.pairs_in_range(pos, lengths, periodic, rc, rows=rows, margin=0.0)
+    i, j, d = vt.pairs_in_range(pos, lengths, periodic, rc, oracle=oracle, rows=rows, margin=0.0)
     r2 = np.einsum("ij,ij->i", d, d)
     E, W = np.zeros(r2.shape[0]), np.zeros(r2.shape[0])
     if lj:
