@@ -24,6 +24,11 @@ class LJModelC(C.Structure):          # emdee_lj_model
     _fields_ = [("rc2", C.c_double), ("rs2", C.c_double), ("inv_delta2", C.c_double)]
 
 
+class MinimizeResultC(C.Structure):   # emdee_minimize_result
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("rebuilds", C.c_int32), ("reserved", C.c_int32),
+                ("energy0", C.c_double), ("energy", C.c_double), ("g_max", C.c_double), ("dt", C.c_double)]
+
+
 class LJAtomC(C.Structure):           # emdee_lj_atom == Julia LJAtom (src/lennard_jones.jl:15-18)
     _fields_ = [("half_sigma", C.c_float), ("twice_sqrt_eps", C.c_float)]
 
@@ -79,6 +84,7 @@ SIGNATURES = {
     "emdee_md_set_state": [_p, _i32, _i32, _p, _p, _p, _p],
     "emdee_md_get_state": [_p, _p, _p, _p, _p, _p],
     "emdee_md_step": [_p, _i32, _dbl, _i32],
+    "emdee_md_minimize": [_p, _i32, _dbl, _dbl, _dbl, _dbl, C.POINTER(MinimizeResultC)],
     "emdee_md_kick_drift": [_p, _dbl, _dbl],
     "emdee_md_forces": [_p, _i32, _i32],
     "emdee_md_kick": [_p, _dbl],

@@ -371,6 +371,10 @@ int32_t emdee_md_get_state(emdee_md *md, void *positions_dev, void *velocities_d
 int32_t emdee_md_step(emdee_md *md, int32_t nsteps, double dt, int32_t rebuild_every) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->step(nsteps, dt, rebuild_every); });
 }
+int32_t emdee_md_minimize(emdee_md *md, int32_t max_iter, double f_tol, double dt_start, double dt_max, double max_step,
+                          emdee_minimize_result *out) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->minimize(max_iter, f_tol, dt_start, dt_max, max_step, out); });
+}
 int32_t emdee_md_kick_drift(emdee_md *md, double dt, double kick) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->kick_drift(dt, kick); });
 }

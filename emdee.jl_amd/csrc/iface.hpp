@@ -31,6 +31,7 @@ struct IMd {
                            const void *inv_mass) = 0;
     virtual void get_state(void *pos, void *vel, void *frc, void *en, void *vir) = 0;
     virtual void step(int nsteps, double dt, int rebuild_every) = 0;
+    virtual void minimize(int max_iter, double f_tol, double dt_start, double dt_max, double max_step, emdee_minimize_result *out) = 0;
     virtual void kick_drift(double dt, double kick) = 0;
     virtual void forces(int bitmask, int phase) = 0;
     virtual void kick(double dt) = 0;

@@ -471,6 +471,82 @@ struct MdImpl : IMd {
             throw Failure{EMDEE_ERR_STATE};
         }
     }
+    // emdee_md_minimize (include/emdee_hip.h): FIRE around the stages of step_closed.  Iteration 0 is the evaluation at
+    // the entry positions (force pass unless forces and energies are current, G, the reduction, the stop test); every later one is a
+    // closed step with the capped time step, then G, the reduction, the stop test and the update of minimize.hpp.  The thermostat
+    // is left out of the kick + drift for the length of the call and comes back as it was; the box never changes.
+    void minimize(int max_iter, double f_tol, double dt_start, double dt_max, double max_step, emdee_minimize_result *out) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(max_iter >= 0, EMDEE_ERR_INVALID, "md_minimize: max_iter = %d is negative", max_iter);
+        EMDEE_REQUIRE(std::isfinite(f_tol) && f_tol >= 0.0, EMDEE_ERR_INVALID, "md_minimize: f_tol must be finite and >= 0");
+        EMDEE_REQUIRE(std::isfinite(dt_start) && std::isfinite(dt_max) && dt_start > 0.0 && dt_start <= dt_max, EMDEE_ERR_INVALID,
+                      "md_minimize: need 0 < dt_start <= dt_max, both finite");
+        EMDEE_REQUIRE(std::isfinite(max_step) && max_step > 0.0, EMDEE_ERR_INVALID, "md_minimize: max_step must be finite and > 0");
+        require_undivided("md_minimize");
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md_minimize: no state loaded (call emdee_md_set_state first)");
+        EMDEE_REQUIRE(!sys.bonded_fault.latched, EMDEE_ERR_STATE, "md_minimize: a bonded term has lost a partner; replace the tables or the state");
+        EMDEE_REQUIRE(!sys.ewald_fault.latched, EMDEE_ERR_STATE, "md_minimize: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
+        for (int k = 0; k < sys.GROUPS; k++) {
+            EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_minimize: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
+            require_fitting_table("md_minimize", k);
+        }
+        sys.ensure_charges();                                // (charges set for another atom count: refused, as a step is)
+        struct Unthermostatted {                             // (kick_drift applies the thermostat that is on, and counts its steps)
+            NbSystem<real> &s;
+            bool on;
+            explicit Unthermostatted(NbSystem<real> &sys_) : s(sys_), on(sys_.lgv_on) { s.lgv_on = false; }
+            ~Unthermostatted() { s.lgv_on = on; }
+        } unthermostatted(sys);
+        const int mask = EMDEE_FORCES | EMDEE_ENERGIES;
+        const bool tables = sys.has_rigid() || sys.has_hbonds();
+        emdee_minimize_result res{};
+        FireState fire = fire_start(dt_start, dt_max);
+        double r[FIRE_WORDS + 1];
+        sys.zero_velocities();
+        if ((current_mask & mask) != mask) { sys.compute_forces(mask); current_mask = mask; }
+        const real *G = sys.constrained_force();
+        sys.fire_sums(G, r);
+        res.energy0 = r[FIRE_WORDS];
+        double vmax = 0.0;                                   // the largest speed now: zero at entry and after a reset
+        for (;;) {
+            // (a sum that is not a number never counts as converged: the maxima alone would drop it)
+            res.g_max = std::sqrt(r[3]);
+            res.energy = r[FIRE_WORDS];
+            if (res.g_max <= f_tol && std::isfinite(r[2])) { res.converged = 1; break; }
+            if (res.iterations >= max_iter) break;
+            const double t = fire_cap(fire.dt, vmax, std::sqrt(r[5]), max_step);
+            for (auto &g : sys.groups) if (sys.table(g).present) sys.gather(g);
+            sys.kick_drift(0.5 * t, t);
+            for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, t);
+            since_build++;
+            if (sys.read_rebuild_flag()) { sys.resort(); since_build = 0; res.rebuilds++; }
+            sys.compute_forces(mask);
+            sys.kick(0.5 * t);
+            for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
+            current_mask = mask;
+            res.iterations++;
+            G = sys.constrained_force();
+            sys.fire_sums(G, r);
+            if (std::sqrt(r[3]) <= f_tol && std::isfinite(r[2])) continue;   // (converged: no update; the test above ends the call)
+            const double alpha = fire.alpha;
+            if (fire_update(fire, r[0])) {
+                // v <- (1 - alpha) v + alpha |v| G / |G|, tangent again through stage (e); no speed now exceeds the bound below
+                const double c_g = alpha * std::sqrt(r[1] / r[2]);
+                sys.fire_mix(G, 1.0 - alpha, c_g);
+                if (tables) for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
+                vmax = (1.0 - alpha) * std::sqrt(r[4]) + c_g * std::sqrt(r[3]);
+            } else {
+                sys.zero_velocities();
+                vmax = 0.0;
+            }
+        }
+        sys.zero_velocities();
+        res.dt = fire.dt;
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
+        for (auto &g : sys.groups) sys.check(g);             // (one read-back per call and table)
+        if (out) *out = res;
+    }
     void kick_drift(double dt, double kick) override {
         use_device(sys.ctx);
         sys.kick_drift(kick * dt, dt);
@@ -595,12 +671,12 @@ struct MdImpl : IMd {
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
         // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
-        // stages of an engine with an hbonds table
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 11, EMDEE_ERR_INVALID, "kernel id out of range");
+        // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 12, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[12][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[13][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {

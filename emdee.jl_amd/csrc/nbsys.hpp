@@ -11,6 +11,7 @@
 #include "brick.hpp"
 #include "ewald.hpp"
 #include "kernels.hpp"
+#include "minimize.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
 #include "topology_dev.hpp"
@@ -39,8 +40,9 @@ static inline void refuse_experiment_switches() {
 // T_SETTLE: the three constraint stages of an engine with rigid molecules (settle.hpp)
 // T_MOLECULAR: the molecular sums and the molecular scale of an engine with rigid molecules (settle.hpp)
 // T_HBONDS: the three constraint stages of an engine with an hbonds table (shake.hpp)
+// T_MINIMIZE: what emdee_md_minimize adds to the stages of a closed step (minimize.hpp): the constrained force, the reduction, the mixing
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_COUNT = 11 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_COUNT = 12 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -1626,6 +1628,62 @@ struct NbSystem {
     bool read_rebuild_flag() {
         read_back_words(ctx, stream(), flags.ptr + 1, 1, ctx->host_flags + 1);
         return ctx->host_flags[1] != 0;
+    }
+
+    // ---------------------------------------------------------------- energy minimisation (minimize.hpp; MdImpl::minimize drives these)
+    DevBuf<real> gplane;                                     // a = w F, then the constrained force G (three planes, cell order)
+    DevBuf<double> fire_partial;
+    void zero_velocities() {
+        if (n_total == 0) return;
+        Timed t(this, T_MINIMIZE);
+        EMDEE_HIP_CHECK(hipMemsetAsync(vel.ptr, 0, 3 * pitch * sizeof(real), stream()));
+    }
+    // G: the force-field forces of the last pass with the constraint components removed.  Without a table the force planes
+    // themselves.  With tables a = w F goes through the velocity stage of every table that exists (ConstraintArgs::vel, the current
+    // positions): what that stage does to a velocity is what a constraint force does to an acceleration.
+    const real *constrained_force() {
+        if (n_total == 0 || !(has_rigid() || has_hbonds())) return frc.ptr;
+        Timed t(this, T_MINIMIZE);
+        gplane.ensure(3 * pitch);
+        const real *w = with_mass ? im.ptr : nullptr;
+        hipLaunchKernelGGL((k_fire_weight<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                           (const real *)frc.ptr, w, gplane.ptr, 0);
+        for (auto &g : groups) {
+            if (!table(g).present) continue;
+            ConstraintArgs<real> a = constraint_args(g);
+            a.vel = gplane.ptr;
+            hipLaunchKernelGGL(g.k_velocities, dim3(blocks_for(table(g).n, 256)), dim3(256), 0, stream(), a);
+        }
+        hipLaunchKernelGGL((k_fire_weight<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                           (const real *)frc.ptr, w, gplane.ptr, 1);
+        return gplane.ptr;
+    }
+    // out[0..5] = sum G . v, sum v . v, sum G . G, max |G_i|^2, max |v_i|^2, max |w_i F_i|^2, out[6] = the potential energy of the
+    // last pass (energy_sums' kernels, so that it is the number emdee_md_energies gives); one copy, blocking
+    void fire_sums(const real *g, double out[FIRE_WORDS + 1]) {
+        for (int q = 0; q <= FIRE_WORDS; q++) out[q] = 0.0;
+        if (n_total == 0) return;
+        const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+        fire_partial.ensure((size_t)FIRE_WORDS * RED_MAX_BLOCKS + FIRE_WORDS + 1);
+        double *tot = fire_partial.ptr + (size_t)FIRE_WORDS * RED_MAX_BLOCKS;
+        const real *w = with_mass ? im.ptr : nullptr;
+        {
+            Timed t(this, T_MINIMIZE);
+            hipLaunchKernelGGL((k_energy_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                               (const real *)en.ptr, (const real *)nullptr, (const real *)nullptr, (const real *)frc.ptr, w, (real)0, partial.ptr);
+            hipLaunchKernelGGL(k_final_sum3, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)partial.ptr, sums.ptr);
+            hipLaunchKernelGGL((k_fire_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr, g,
+                               (const real *)frc.ptr, (const real *)vel.ptr, w, fire_partial.ptr);
+            hipLaunchKernelGGL(k_fire_final, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)fire_partial.ptr, (const double *)sums.ptr, tot);
+        }
+        EMDEE_HIP_CHECK(hipMemcpyAsync(out, tot, (FIRE_WORDS + 1) * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+    }
+    void fire_mix(const real *g, double c_v, double c_g) {
+        if (n_total == 0) return;
+        Timed t(this, T_MINIMIZE);
+        hipLaunchKernelGGL((k_fire_mix<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                           vel.ptr, g, (real)c_v, (real)c_g);
     }
 
     // ---------------------------------------------------------------- observables

@@ -99,6 +99,27 @@ set_hbonds!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, dist::U
     check(ccall((:emdee_md_set_hbonds, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
                 atoms === nothing ? C_NULL : atoms.ptr, dist === nothing ? C_NULL : dist.ptr, atoms === nothing ? 0 : size(atoms, 2)))
 
+# int32_t emdee_md_minimize(emdee_md *md, int32_t max_iter, double f_tol, double dt_start, double dt_max, double max_step,
+#                           emdee_minimize_result *out);
+# Energy minimisation by FIRE around the constrained step: at most max_iter iterations, until no atom's constrained force exceeds
+# f_tol.  OVERWRITES the velocities with zeros.  Returns the emdee_minimize_result.
+struct MinimizeResult
+    iterations::Int32
+    converged::Int32
+    rebuilds::Int32
+    reserved::Int32
+    energy0::Float64
+    energy::Float64
+    g_max::Float64
+    dt::Float64
+end
+function minimize!(md::VelocityVerlet, max_iter, f_tol; dt_start=0.001, dt_max=0.01, max_step=0.1)
+    out = Ref(MinimizeResult(0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0))
+    check(ccall((:emdee_md_minimize, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Float64, Float64, Ref{MinimizeResult}), md.handle,
+                Int32(max_iter), Float64(f_tol), Float64(dt_start), Float64(dt_max), Float64(max_step), out))
+    return out[]
+end
+
 # Pressure coupling (include/emdee_hip.h; undivided boxes).
 # int32_t emdee_md_get_box(emdee_md *md, double lo[3], double len[3]);   -> (lo, len) of the engine's box
 function box(md::VelocityVerlet)

@@ -60,7 +60,21 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the molecular sums and the molecular scale of an engine with rigid molecules (set_molecular_scaling_)
            "molecular": 10,
            # the constraint stages of an engine with an hbonds table (set_hbonds_)
-           "hbonds": 11}
+           "hbonds": 11,
+           # what minimize_ adds to the stages of its steps: the constrained force, the reduction, the mixing
+           "minimize": 12}
+
+
+class MinimizeResult:
+    """emdee_minimize_result as attributes: iterations, converged (bool), rebuilds, energy0, energy, g_max, dt"""
+
+    def __init__(self, c):
+        self.iterations, self.converged, self.rebuilds = int(c.iterations), bool(c.converged), int(c.rebuilds)
+        self.energy0, self.energy, self.g_max, self.dt = float(c.energy0), float(c.energy), float(c.g_max), float(c.dt)
+
+    def __repr__(self):
+        return ("MinimizeResult(iterations=%d, converged=%s, rebuilds=%d, energy0=%r, energy=%r, g_max=%r, dt=%r)"
+                % (self.iterations, self.converged, self.rebuilds, self.energy0, self.energy, self.g_max, self.dt))
 
 
 class VelocityVerlet:
@@ -112,6 +126,16 @@ class VelocityVerlet:
         finally:
             if self._coupled:
                 self.box()                                  # (the coupling events of the call have changed the lengths)
+
+    def minimize_(self, max_iter, f_tol, dt_start=0.001, dt_max=0.01, max_step=0.1):
+        """Energy minimisation by FIRE around the constrained step (include/emdee_hip.h emdee_md_minimize): at most max_iter
+        iterations, until no atom's constrained force exceeds f_tol.  dt_start, dt_max: FIRE's first and largest time step;
+        max_step: the farthest an atom may drift in one iteration.  OVERWRITES the velocities with zeros.  Returns a
+        MinimizeResult."""
+        res = _lib.MinimizeResultC()
+        _lib.call("emdee_md_minimize", self._handle, int(max_iter), float(f_tol), float(dt_start), float(dt_max), float(max_step),
+                  C.byref(res))
+        return MinimizeResult(res)
 
     # -- split step (domain-decomposed driver: kick_drift_ -> halo exchange -> forces_ -> kick_)
     def kick_drift_(self, dt, kick=0.5):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A small box of rigid three-site water on one MI355X: SPC/E geometry and charges, reaction-field electrostatics, the Langevin
 thermostat at 300 K and a time step of 2 fs, which the rigid molecules (emdee_md_set_rigid3: SETTLE + RATTLE) make possible.
-Prints the largest bond-length deviation and the temperature as it runs.  An NPT leg follows: stochastic cell rescaling
+The lattice start is relaxed by emdee_md_minimize first.  Prints the largest bond-length deviation and the temperature as it runs.  An NPT leg follows: stochastic cell rescaling
 (C-rescale) at 1 bar with the Langevin thermostat, coupled to the molecular pressure and scaling the box by molecular centres of
 mass (emdee_md_set_molecular_scaling), which keeps the molecules rigid; it prints the box side and P_mol as well.
 
@@ -63,7 +63,13 @@ md = E.VelocityVerlet(E.cu(pos, dev), E.cu(vel, dev), L, E.LennardJonesModel(RC,
 md.set_exclusions_(np.concatenate([mol[:, [0, 1]], mol[:, [0, 2]], mol[:, [1, 2]]]))
 md.set_coulomb_(np.tile([-0.8476, 0.4238, 0.4238], n_mol), E.COULOMB_K_KJ_NM, eps_rf=78.0)
 md.set_rigid3_(mol, np.tile([R_OH, D_HH], (n_mol, 1)))
-md.set_langevin_(gamma=5.0, temperature=KB * T, seed=2026)       # 1/ps; the lattice start relaxes under it
+md.set_langevin_(gamma=5.0, temperature=KB * T, seed=2026)       # 1/ps
+# the lattice start has molecules at random orientations next to each other: relax it before the first 2 fs step
+# (emdee_md_minimize: FIRE around the constrained step; it leaves the velocities at zero, so they are loaded again)
+res = md.minimize_(500, 500.0, dt_start=0.0002, dt_max=0.002, max_step=0.01)
+print("minimised: %d iterations, converged = %s, E_pot %.1f -> %.1f kJ/mol, largest constrained force %.1f kJ/mol/nm"
+      % (res.iterations, res.converged, res.energy0, res.energy, res.g_max))
+md.set_state_(md.state(velocities=False, forces=False)["positions"], E.cu(vel, dev), E.cu(atoms, dev), E.cu(1.0 / mass, dev))
 
 
 def report(step, npt=False):

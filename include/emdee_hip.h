@@ -395,6 +395,50 @@ int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double
  *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 11. */
 int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters);
 
+/* Energy minimisation on the device: FIRE (Bitzek, Koskinen, Gaehler, Moseler & Gumbsch, Phys. Rev. Lett. 97, 170201 (2006);
+ * build-defined like the integrator), for free atoms, rigid molecules (emdee_md_set_rigid3) and hbonds clusters
+ * (emdee_md_set_hbonds) alike: what prepares a box with close contacts for emdee_md_step.
+ * FIRE integrates the equations of motion with the engine's masses and steers the velocities towards the force.  With F the
+ * force-field force, w = 1/m, the paper's constants N_min = 5, f_inc = 1.1, f_dec = 0.5, alpha_0 = 0.1, f_alpha = 0.99 and the
+ * scalars dt = dt_start, alpha = alpha_0, n_pos = 0, iteration 0 evaluates F (with the energies), G and the sums below at the
+ * entry positions; every later iteration is
+ *   1. the step cap: t = the largest value <= dt with t v_max + t^2 a_max / 2 <= max_step, v_max and a_max bounding |v_i| and
+ *      |w_i F_i| over the atoms now, so that no atom's unconstrained drift exceeds max_step (overlapping starts are safe);
+ *   2. one closed step of emdee_md_step with t -- stages (a) to (e) of emdee_md_set_rigid3 for whichever tables exist around kick +
+ *      drift, the displacement-triggered re-sort, the force pass (forces and energies) and the kick;
+ *   3. G, the force with the constraint components removed: F itself without a table; with tables w F is handed to stage (e) in
+ *      place of the velocities, and G = (the result) / w;
+ *   4. one fp64 reduction in a fixed order: P = sum G . v, sum v . v, sum G . G, the largest |G_i|, |v_i| and |w_i F_i|; one
+ *      read-back carries them and the potential energy;
+ *   5. the stop test: g_max = max |G_i| <= f_tol ends the call, converged;
+ *   6. the update: P > 0: v <- (1 - alpha) v + alpha sqrt(sum v . v / sum G . G) G, stage (e) once more with tables, and if
+ *      ++n_pos > N_min, dt <- min(f_inc dt, dt_max) and alpha <- f_alpha alpha; P <= 0: v <- 0, dt <- f_dec dt, alpha <- alpha_0,
+ *      n_pos <- 0.
+ * max_iter bounds the iterations after iteration 0 (max_iter = 0 evaluates and reports).  out may be NULL.
+ *   - Undivided engines only: EMDEE_ERR_STATE on an integrator lent by emdee_dd_engine, on one with ghosts and before
+ *     emdee_md_set_state; the refusals of emdee_md_step for a latched fault, a table or charges that do not fit the state apply.
+ *   - EMDEE_ERR_INVALID before anything is written unless max_iter >= 0, f_tol >= 0, 0 < dt_start <= dt_max, max_step > 0, all finite.
+ *   - Velocities are OVERWRITTEN: zeroed at entry, zero at return.  Thermostat and barostat settings are neither applied nor
+ *     changed, the box is untouched.  Every call starts FIRE afresh: two identical calls from identical states agree bit for bit.
+ *   - Positions, forces and energies at return belong together: the result's energy is that of the returned positions, and
+ *     emdee_md_step follows without emdee_md_set_state.  The virials are not evaluated: emdee_md_energies and an emdee_md_get_state
+ *     of energies or virials run their pass over all outputs first, as after emdee_md_step.
+ *   - A constraint group without a solution ends the call as it ends emdee_md_step: EMDEE_ERR_STATE naming the group.
+ *   - Charges, Ewald and PME, bonded tables, exclusions and 1-4 pairs are part of the force pass and work as in emdee_md_step.
+ *   - One blocking read-back per iteration (beside the rebuild word's): the scalars live on the host.  The device time of what the
+ *     call adds to the stages of its steps (G, the reduction, the mixing) is emdee_md_kernel_time index 12. */
+typedef struct {
+    int32_t iterations;     /* force evaluations after the first */
+    int32_t converged;      /* 1: g_max <= f_tol */
+    int32_t rebuilds;       /* neighbour rebuilds during the call */
+    int32_t reserved;
+    double  energy0, energy;/* potential energy before / after */
+    double  g_max;          /* largest |G_i| at the returned positions */
+    double  dt;             /* FIRE's time step at return */
+} emdee_minimize_result;
+int32_t emdee_md_minimize(emdee_md *md, int32_t max_iter, double f_tol, double dt_start, double dt_max, double max_step,
+                          emdee_minimize_result *out);
+
 /* compute_nonbonded!(forces, energies, virials, positions, L, tiles, model, atoms, Val(bitmask))
  * -- src/nonbonded.jl:109-120 -- O(N) neighbour-list path, EMDEE_CUTOFF semantics.
  * Outputs not selected by bitmask may be NULL and are left untouched; selected outputs are
@@ -558,7 +602,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald, emdee_md_set_pme),
  * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3);
  * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling);
- * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds).  Blocking. */
+ * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds); 12 = what emdee_md_minimize adds to the
+ * stages of its steps (the constrained force, the reduction, the mixing).  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
