@@ -43,33 +43,8 @@ enum BrickMode { BRICK_FORCE = 1, BRICK_STATS = 2, BRICK_STEP = 3 };
 // a loop the compiler must leave as written (no unrolling, no interleaving of trips behind run-time alias checks)
 #define EMDEE_PLAIN_LOOP _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
 
-constexpr int EPL = 8;   // neighbour entries per lane per 16-byte load
-// entries the force kernels read of every row without looking at its length: the NPF prefetched blocks of 8 G entries
-// and the one after them (rows are sentinel-padded, so the row stride must hold them)
-// (1024-thread workgroups with 4 lanes per atom are the long-row variant -- rc = 3.5 sigma: 184 entries -- and prefetch five
-// 32-entry blocks: with two, every further block of a row is a dependent global load that four wavefronts per SIMD cannot hide)
-constexpr int brick_prefetch_blocks(int G, int THREADS) { return (EPL * G) >= 128 ? 1 : ((G == 4 && THREADS >= 1024) ? 5 : 2); }
-constexpr int brick_min_stride(int G, int THREADS) { return (brick_prefetch_blocks(G, THREADS) + 1) * EPL * G; }
-
-template <int BX_, int BY_, int BZ_>
-struct BrickShape {
-    static constexpr int BX = BX_, BY = BY_, BZ = BZ_;
-    static constexpr int TX = BX + 2, TY = BY + 2, TZ = BZ + 2;
-    static constexpr int NTC = TX * TY * TZ;   // tile cells
-    static constexpr int NOC = BX * BY * BZ;   // own cells
-};
-
-struct BrickGrid {
-    int nb[3];         // bricks per dimension
-    int nbricks;
-    int per_xcd;       // ceil(nbricks / 8): XCD-contiguous remap of block ids
-    // interior sub-box (bricks whose tile holds no ghost cell): phase-1 launches enumerate only these,
-    // so that every XCD gets an equal share of them
-    int ib_lo[3], ib_n[3];
-    int ib_count, ib_per_xcd;
-    // boundary bricks = the rest, enumerated densely as z-slabs, then y-slabs, then x-slabs (phase 2)
-    int bb_z, bb_y, bb_count, bb_per_xcd;   // bb_z = #bricks in the z-slabs, bb_y = # in the y-slabs
-};
+// (EPL, the prefetch depths, BrickShape and BrickGrid: plan.hpp)
+static_assert(sizeof(Rec<double>) == rec_bytes<double>() && sizeof(Rec<float>) == rec_bytes<float>(), "plan.hpp sizes the tiles with these");
 
 // k-th index of [0, nb) outside the interval [lo, lo + n)
 __host__ __device__ __forceinline__ int outside_interval(int k, int lo, int n) { return k < lo ? k : k + n; }
@@ -186,7 +161,7 @@ __device__ __forceinline__ double rel_tile(double v, float) { return v; }   // (
 
 // ---- LDS tables shared by the build and force kernels ------------------------------------------
 template <class Shape, int THREADS>
-struct BrickTables {
+struct BrickTables : BrickTableSizes<Shape, THREADS> {   // (fixed_ints, bytes, image_ints, row_ints: plan.hpp)
     static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NWAVES = THREADS / WAVE;
     int *off;      // [NTC+1] tile-local first slot of each tile cell
     int *gbeg;     // [NTC]   global (cell-order) first slot of each tile cell
@@ -194,11 +169,6 @@ struct BrickTables {
     int *own;      // [NOC+1] prefix of own-cell populations
     int *wtot;     // [NWAVES]
     int2 *oinfo;   // [own_cap] per own atom {cell-order slot p, (row length or flag) << 16 | tile slot}
-    __host__ __device__ static constexpr size_t fixed_ints() { return (NTC + 4) + NTC + NTC + (NOC + 4) + ((NWAVES + 1) & ~1); }
-    __host__ __device__ static size_t bytes(int own_cap) { return ((fixed_ints() + 2 * (size_t)own_cap) * 4 + 15) & ~(size_t)15; }
-    // off | gbeg | shift | own are contiguous: that image (+ tile_n, n_own) is what k_brick_tables stores per brick
-    __host__ __device__ static constexpr int image_ints() { return (NTC + 4) + NTC + NTC + (NOC + 4); }
-    __host__ __device__ static constexpr int row_ints() { return (image_ints() + 2 + 3) & ~3; }
     __device__ __forceinline__ void carve(unsigned char *base) {
         off = reinterpret_cast<int *>(base);
         gbeg = off + (NTC + 4);
@@ -208,38 +178,8 @@ struct BrickTables {
         oinfo = reinterpret_cast<int2 *>(wtot + ((NWAVES + 1) & ~1));
     }
 };
+// (SOA_SLOTS, soa_pitch and the bytes of dynamic LDS of the force and build kernels: plan.hpp)
 
-// Single-species fp64 force kernels keep only the three coordinate planes in LDS (24 B per record instead of the
-// 32-byte HBM record): with a fixed plane pitch the three reads of a neighbour share one address register and differ
-// in the instruction's immediate offset, and three workgroups fit a CU where the 32-byte tile allows two.
-constexpr int SOA_SLOTS = 2048;                      // records a coordinate-plane tile can hold
-// Plane pitch in records.  fp64: one record more than a power of two, so that the x and y reads of a neighbour cannot be
-// merged into one ds_read2st64_b64 (8 LDS-array cycles per wavefront, MI355X_MICROARCH.md LDS table) and stay two
-// ds_read_b64 (2 cycles each) off one address register with immediate offsets.
-template <typename real>
-constexpr int soa_pitch() { return SOA_SLOTS + (sizeof(real) == 8 ? 1 : 0); }
-template <typename real, class Shape, int THREADS>
-static inline size_t brick_force_lds_bytes_soa(int own_cap) {
-    return (((size_t)3 * soa_pitch<real>() * sizeof(real) + 15) & ~(size_t)15) + BrickTables<Shape, THREADS>::bytes(own_cap);
-}
-
-// bytes of dynamic LDS: force tile = HBM records (+ te plane for fp32) (+ charge plane: charged instances); build tile = float4
-template <typename real>
-__host__ __device__ inline size_t brick_charge_lds_bytes(int tile_cap) { return ((size_t)tile_cap * sizeof(real) + 15) & ~(size_t)15; }
-template <typename real, class Shape, int THREADS>
-static inline size_t brick_force_lds_bytes(int tile_cap, int own_cap, bool charged = false) {
-    size_t tile_bytes = (size_t)tile_cap * sizeof(Rec<real>);
-    size_t te_bytes = sizeof(real) == 4 ? (((size_t)tile_cap * 4 + 15) & ~(size_t)15) : 0;
-    return tile_bytes + te_bytes + (charged ? brick_charge_lds_bytes<real>(tile_cap) : 0) + BrickTables<Shape, THREADS>::bytes(own_cap);
-}
-template <class Shape, int THREADS>
-static inline size_t brick_build_lds_bytes(int tile_cap, int own_cap, int stride, int G, int nsub = 1) {
-    // + one row buffer (stride uint16) per G-lane group
-    // + the candidate rows of every own cell ({first slot, span} of its 9 tile rows, and one all-zero set for ghosts)
-    // (one packed word per row; nsub > 1: one set of rows per own cell AND sub-bin)
-    return (size_t)tile_cap * 16 + BrickTables<Shape, THREADS>::bytes(own_cap) + (size_t)(THREADS / G) * stride * 2 +
-           (((size_t)(Shape::NOC * nsub + 1) * 9 * 4 + 15) & ~(size_t)15);
-}
 // atoms of a tile cell in sub-bins below s, from its packed boundaries (s <= 0: none, s >= 4: the whole cell)
 __device__ __forceinline__ int sub_below(int packed, int s, int population) {
     return s <= 0 ? 0 : (s >= 4 ? population : ((packed >> (10 * (s - 1))) & 1023));
@@ -502,7 +442,7 @@ constexpr int OWN_REGS = 2;   // own atoms per thread whose table entry is fetch
 // the hits are compacted once per atom, from the bit fields, after a prefix sum over the lanes of the group.  Rows
 // come out ordered lane by lane, i.e. still along the tile rows, so neighbouring entries keep pointing at
 // neighbouring tile slots.  ALG 13 / 15 deal the candidates to the lanes round-robin instead.
-constexpr int BUILD2_FIELD = 16;                      // bits per tile row in a lane's bit field
+// (BUILD2_FIELD, the bits per tile row in a lane's bit field: plan.hpp)
 
 // G = lanes that share one atom HERE; GL = lanes per atom of the force kernels, which fixes the lane-major row
 // layout (row_position<GL>) -- the two need not agree.

@@ -702,7 +702,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "%s: set them on a loaded integrator without ghosts (call emdee_md_set_state first)", what);
         set();
         if (!relist) { EMDEE_HIP_CHECK(hipGetLastError()); return; }
-        sys.has_list = false; sys.plan_valid = false;        // (the rows in use follow the old tables; charged and uncharged engines take different kernels and LDS plans)
+        sys.has_list = false; sys.plan = {};                 // (the rows in use follow the old tables; charged and uncharged engines take different kernels and LDS plans)
         sys.resort();                                        // the list, rows and slots for the new tables (a two-species box leaves the typed kernels)
         since_build = 0;
         sys.compute_forces(EMDEE_FORCES);

@@ -785,7 +785,6 @@ __global__ __launch_bounds__(NBR_BLOCK) void k_nbr_build(int n, int n_owned, Ato
 // atoms: neighbouring atoms gather the same records.
 constexpr int FORCE_BLOCK = 256;
 constexpr int FORCE_ATOMS = 64;
-constexpr int NXCD = 8;
 
 // (the body of k_lj_force_nbr and of its charged twin k_lj_force_nbr_q: CHG adds the reaction-field terms, lj_pair.hpp rf_pair)
 template <typename real, int BITMASK, bool CHG, bool EWD = false>

@@ -12,6 +12,7 @@
 #include "ewald.hpp"
 #include "kernels.hpp"
 #include "minimize.hpp"
+#include "plan.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
 #include "topology_dev.hpp"
@@ -83,32 +84,7 @@ struct Scanner {
     }
 };
 
-// ---- brick kernel variants (shape, workgroup size, lanes per atom); variant 0 is the default ----
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
-template <int V>
-struct BrickVariant;
-// G = lanes per atom in the force kernels (and the row layout), GB = lanes per atom in the build kernel
-template <> struct BrickVariant<0> { using Shape = BrickShape<4, 2, 2>; static constexpr int THREADS = 512, G = 4, GB = 8; };
-// (7: the 1024-thread workgroup of variant 8 with FOUR lanes per atom: long rows, e.g. the rc = 3.5 sigma mixture -- 184 entries
-// are 46 pair steps per lane -- amortise a round's fixed work over 16 atoms per wavefront instead of 8)
-template <> struct BrickVariant<7> { using Shape = BrickShape<4, 2, 2>; static constexpr int THREADS = 1024, G = 4, GB = 8; };
-template <> struct BrickVariant<8> { using Shape = BrickShape<4, 2, 2>; static constexpr int THREADS = 1024, G = 8, GB = G; };
-// (9, round 5: two-species boxes with long rows on bricks of 2 x 2 x 2 cells -- a tile of 64 cells, ~2850 records at rc = 3.5 sigma,
-// fits TWO 512-thread workgroups on a CU where variant 7's 96-cell tile leaves room for one of 1024: while one workgroup stages
-// its tile or is being replaced, the other computes)
-template <> struct BrickVariant<9> { using Shape = BrickShape<2, 2, 2>; static constexpr int THREADS = 512, G = 4, GB = 8; };
-
-template <class F>
-static inline void with_brick_variant(int v, F &&f) {
-    switch (v) {
-        case 7: f(BrickVariant<7>{}); break;
-        case 8: f(BrickVariant<8>{}); break;
-        case 9: f(BrickVariant<9>{}); break;
-        default: f(BrickVariant<0>{}); break;
-    }
-}
-
+// (the brick kernel variants, LDS_LIMIT and with_brick_variant: plan.hpp)
 template <typename K>
 static inline void allow_big_lds(K kernel, size_t bytes) {
     if (bytes > 48 * 1024)
@@ -155,20 +131,23 @@ struct NbSystem {
     size_t pitch = 0;
     bool with_vel = false, with_mass = false;
     bool sorted = false, has_list = false;
+    // the list's rows: entries per row, and whether they already include the typed rows' segment padding (both outlive a plan)
     int stride = 0;
+    bool typed_stride = false;
     int64_t builds = 0;
     bool profiling = false;
     KernelTimer timers[T_COUNT];
 
     // path selection
     int path = PATH_BRICK;
-    int variant = 0;
-    BrickGrid bgrid{};
-    int tile_cap = 0, own_cap = 0, row_block = 1;
-    int build_alg = 1;                    // k_brick_build ALG (3 / 5 = two-phase, 16- / 32-bit hit fields; 1 when a tile row is too crowded for both)
-    bool field16_blocked = false;         // a 16-bit hit field overflowed under a plan that should have ruled it out: 32-bit fields until the next load
-    size_t lds_bytes = 0, lds_build_bytes = 0;
-    float build_margin = 0.f;
+    // which kernels the state runs on (plan.hpp): chosen by choose_plan at a load, kept from rebuild to rebuild while it holds
+    // (build_list), dropped -- plan = {} -- by whatever changes the facts it was chosen for
+    BrickPlan plan;
+    const bool &brick_active = plan.active;   // (read-only: the brick kernels are in use, not the direct ones)
+    struct PlanBlocks {                   // what this state has ruled out until the next load
+        bool field16 = false;             // a 16-bit hit field overflowed under a plan that should have ruled it out: 32-bit fields
+        bool typed = false;               // its rows outgrew the typed build
+    } blocked;
 
     DevBuf<Rec<real>> rec, rec2;
     DevBuf<float> te, te2;
@@ -268,7 +247,7 @@ struct NbSystem {
     void set_box(const double lo_[3], const double len_[3], const int per_[3]) {
         bool same = true;
         for (int d = 0; d < 3; d++) same = same && lo[d] == lo_[d] && len[d] == len_[d] && per[d] == (per_[d] ? 1 : 0);
-        if (!same) sorted = has_list = plan_valid = false;
+        if (!same) { sorted = has_list = false; plan = {}; }
         for (int d = 0; d < 3; d++) {
             lo[d] = lo_[d]; len[d] = len_[d]; per[d] = per_[d] ? 1 : 0;
             EMDEE_REQUIRE(len[d] > 0.0 && std::isfinite(len[d]), EMDEE_ERR_INVALID, "box length must be positive");
@@ -279,7 +258,7 @@ struct NbSystem {
         EMDEE_REQUIRE(m.rc2 > 0 && m.rs2 >= 0 && m.rs2 < m.rc2 && std::isfinite(m.inv_delta2), EMDEE_ERR_INVALID,
                       "LennardJonesModel needs 0 <= switch < cutoff (Q10: switch == cutoff gives 1/0)");
         EMDEE_REQUIRE(skin_ >= 0.0, EMDEE_ERR_INVALID, "skin must be >= 0");
-        if (m.rc2 != model_d.rc2 || skin_ != skin) has_list = sorted = plan_valid = false;
+        if (m.rc2 != model_d.rc2 || skin_ != skin) { has_list = sorted = false; plan = {}; }
         model_d = m;
         model = make_model<real>(m);
         skin = skin_;
@@ -364,16 +343,8 @@ struct NbSystem {
                            tmp2.ptr, order.ptr, keep ? count.ptr + nbins : nullptr, tagkey != nullptr ? 1 : 0);
         // (the first slot of every cell, cstart[], is written by the gather kernel that follows)
     }
-    // K: how many quarters of a neighbour cell lie beyond r_list whatever the atom's position in its own quarter: the
-    // quarters < s + K of the left cell are at least (1 + (K - 1) / 4) cell widths away.  0 for a cell a little wider than
-    // r_list; -1 (one more quarter on either side) when the cell is r_list to within the margin that covers the rounding
-    // of M t in the box's own precision (t carries ~2 ulp of 1, M t as many ulp of M: 16 M eps is 8e-5 for the fp32 10^7-atom
-    // box, whose cells are 8.6e-4 wider than r_list)
-    int sub_k() const {
-        const double cx = len[0] / std::max(1, grid.M[0]);
-        const double margin = 16.0 * grid.M[0] * (sizeof(real) == 4 ? 6.0e-8 : 1.2e-16) + 1e-9;
-        return std::max(-1, (int)std::floor(4.0 * (1.0 - rlist * (1.0 + margin) / cx)));
-    }
+    // K of the x sub-bins (plan.hpp plan_sub_k)
+    int sub_k() const { return plan_sub_k((int)sizeof(real), len[0], grid.M[0], rlist); }
     // sub-bins only where the round-robin two-phase build can use them: the tiled path of an untyped box
     void choose_subbins() {
         nsub = (subbins_enabled && path == PATH_BRICK && nt == 1 && n_total > 0) ? 4 : 1;
@@ -548,7 +519,7 @@ struct NbSystem {
         struct Leave { bool &f; ~Leave() { f = false; } } leave{in_edit};
         // (an engine on the direct kernels, or without atoms so far: they count atoms on the host -- the re-sorted state is
         // complete, the caller reads the counts and loads the engine from it)
-        if (path == PATH_BRICK && plan_valid && edit_saved.n_total > 0) build_list();
+        if (path == PATH_BRICK && plan.active && edit_saved.n_total > 0) build_list();
         else edit_abort = true;
         if (edit_abort && !edit_extra_read && extra.n > 0) read_back_words(ctx, stream(), extra.dev, extra.n, extra.host);
         return !edit_abort;
@@ -567,7 +538,7 @@ struct NbSystem {
         n_total = edit_saved.n_total; n_owned = edit_saved.n_owned; id_space = edit_saved.id_space;
         id_gaps = edit_saved.id_gaps; has_ghosts = edit_saved.has_ghosts;
         cmap_valid = false;
-        has_list = false; plan_valid = false; btab_valid = false;   // (inv_perm, xb, the cell tables and the list are the discarded sort's)
+        has_list = false; plan = {}; btab_valid = false;   // (inv_perm, xb, the cell tables and the list are the discarded sort's)
     }
     // rank of every id in use among the ids in use (NULL: the ids have no gaps)
     const int *ids_map() {
@@ -587,9 +558,9 @@ struct NbSystem {
         BrickArgs<real> a{};
         a.n = n_total; a.n_owned = n_owned; a.any_ghosts = has_ghosts ? 1 : 0;
         a.rec = rec.ptr; a.te = te.ptr; a.perm = perm.ptr; a.start = start();
-        a.g = grid; a.bg = bgrid; a.tile_cap = tile_cap; a.own_cap = own_cap;
+        a.g = grid; a.bg = plan.grid; a.tile_cap = plan.tile_cap; a.own_cap = plan.own_cap;
         a.nbr = nbr16.ptr; a.stride = stride; a.cnt = cnt.ptr; a.flags = flags.ptr;
-        a.rlist2 = (real)(rlist * rlist); a.margin = build_margin; a.model = model; a.pitch = pitch;
+        a.rlist2 = (real)(rlist * rlist); a.margin = plan.build_margin; a.model = model; a.pitch = pitch;
         a.frc = frc.ptr; a.en = en.ptr; a.vir = vir.ptr; a.stats = stats.ptr;
         if (p.spare_unselected) {
             if (!(p.mask & EMDEE_FORCES)) a.frc = spare.ptr;
@@ -601,7 +572,7 @@ struct NbSystem {
         a.kick_c = (real)p.c; a.dt = (real)p.dt;
         a.uni_sigma2 = (real)uni_sigma2; a.uni_e4 = (real)uni_e4;
         a.uni = make_uni<real>(model, (real)uni_sigma, (real)uni_e4);
-        a.idx_shift = idx_shift;
+        a.idx_shift = plan.idx_shift;
         a.tstart = tstart(); a.tdig = nt > 1 ? tsub : 1;
         a.nsub = nsub; a.fstart = tstart(); a.bsub = nsub > 1 ? bsub.ptr : nullptr;
         a.sub_k = sub_k();
@@ -636,57 +607,45 @@ struct NbSystem {
         const unsigned lo = (unsigned)(species.key[k] & 0xffffffffull), hi = (unsigned)(species.key[k] >> 32);
         memcpy(&hs, &lo, 4); memcpy(&te, &hi, 4);
     }
-    // typed boxes (typed.hpp): variants 0 and 7 (4 lanes per atom, 512 / 1024 threads) carry the two-species kernels; masks other
-    // than FORCES run the all-outputs kernel
-    bool typed_active = false;
-    template <class V>
-    static constexpr bool typed_variant() {
-        return std::is_same<V, BrickVariant<0>>::value || std::is_same<V, BrickVariant<7>>::value || std::is_same<V, BrickVariant<9>>::value;
-    }
-    template <class V>
-    static constexpr int typed_min_stride() { return (typed_prefetch_blocks(V::G, V::THREADS, V::Shape::NOC) + 1) * EPL * V::G; }
     // only force and step launches are phased: the stats launch takes a default Pass and covers every brick
     template <class V, class K>
     void launch_bricks(K kernel, size_t lds, const Pass<real> &p) {
         allow_big_lds(kernel, lds);
-        const int blocks = (p.phase == 1 ? bgrid.ib_per_xcd : p.phase == 2 ? bgrid.bb_per_xcd : bgrid.per_xcd) * NXCD;
+        const int blocks = (p.phase == 1 ? plan.grid.ib_per_xcd : p.phase == 2 ? plan.grid.bb_per_xcd : plan.grid.per_xcd) * NXCD;
         if (blocks == 0) return;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::THREADS), lds, stream(), brick_args(p));
     }
+    // typed boxes (typed.hpp): masks other than FORCES run the all-outputs kernel
     template <class V, int MODE, int BM>
     void launch_typed_kernel(const Pass<real> &p) {
         if constexpr (typed_variant<V>()) {
             constexpr int M = (MODE == BRICK_STATS) ? 0 : ((MODE == BRICK_STEP || BM == 1) ? 1 : BM == TENSOR_PASS ? TENSOR_PASS : 7);
-            launch_bricks<V>(k_typed<real, typename V::Shape, V::THREADS, V::G, MODE, M>,
-                             typed_force_lds_bytes<real, typename V::Shape, V::THREADS>(own_cap), p);
+            launch_bricks<V>(k_typed<real, typename V::Shape, V::THREADS, V::G, MODE, M>, plan.lds_force, p);
         }
     }
 
-    // variants a general-species box reaches (0, and 8 for long rows) carry the charged force instances
-    template <class V>
-    static constexpr bool charged_variant() { return std::is_same<V, BrickVariant<0>>::value || std::is_same<V, BrickVariant<8>>::value; }
     // the Float32 reference arithmetic of an operator call: general-species tiles staged from the caller's positions
     bool ref_tiles(const Pass<real> &p) const { return sizeof(real) == 4 && refmath && p.pos != nullptr; }
     template <class V, int MODE, int BM>
     void launch_brick_kernel(const Pass<real> &p) {
-        if (typed_active) { launch_typed_kernel<V, MODE, BM>(p); return; }
+        if (plan.typed) { launch_typed_kernel<V, MODE, BM>(p); return; }
         // charged engines: the general-species kernels with the reaction-field terms, whatever their LJ parameters
         if constexpr (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)) {
             if (has_charges()) {
                 if constexpr (charged_variant<V>()) {
                     if (has_ewald()) {
-                        // (variant 0 only, see make_plan: the fp64 erfc does not fit the 128 registers of a 1024-thread workgroup)
+                        // (variant 0 only, see choose_plan: the fp64 erfc does not fit the 128 registers of a 1024-thread workgroup)
                         if constexpr (std::is_same<V, BrickVariant<0>>::value) launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED | EMDEE_EWALD, false>(p);
-                        else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "Ewald engine on brick variant %d", variant);
+                        else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "Ewald engine on brick variant %d", plan.variant);
                     } else launch_brick_kernel_impl<V, MODE, BM | EMDEE_CHARGED, false>(p);
-                } else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "charged engine on brick variant %d", variant);
+                } else EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "charged engine on brick variant %d", plan.variant);
                 return;
             }
         }
         // single-species fast path for the kernels of the MD loop (default variant only)
         if constexpr (std::is_same<V, BrickVariant<0>>::value && (MODE == BRICK_STEP || (MODE == BRICK_FORCE && (BM == 1 || BM == 7 || BM == TENSOR_PASS)))) {
             // (the fp64 variant keeps coordinate planes only in LDS and needs the tile to fit their fixed pitch)
-            if (uniform_atoms && tile_cap <= SOA_SLOTS && idx_shift == PLANE_SHIFT && !(MODE == BRICK_FORCE && ref_tiles(p))) {
+            if (uniform_atoms && plan.tile_cap <= SOA_SLOTS && plan.idx_shift == PLANE_SHIFT && !(MODE == BRICK_FORCE && ref_tiles(p))) {
                 launch_brick_kernel_impl<V, MODE, BM, true>(p);
                 return;
             }
@@ -697,13 +656,13 @@ struct NbSystem {
     template <class V, int MODE, int BM, bool UNI>
     void launch_brick_kernel_impl(const Pass<real> &p) {
         launch_bricks<V>(k_brick<real, typename V::Shape, V::THREADS, V::G, MODE, BM, UNI>,
-                         (UNI && MODE != BRICK_STATS) ? brick_force_lds_bytes_soa<real, typename V::Shape, V::THREADS>(own_cap) : lds_bytes, p);
+                         (UNI && MODE != BRICK_STATS) ? brick_force_lds_bytes_soa<real, typename V::Shape, V::THREADS>(plan.own_cap) : plan.lds_force, p);
     }
 
     // the default variant has an instance for every mask; the tuning variants carry only the two masks the MD loop uses, and the
     // tensor pass
     // (a narrower request on those, and on the typed kernels, runs the all-outputs instance: runs_all_outputs)
-    bool runs_all_outputs(int mask) const { return brick_active && mask >= 2 && mask <= 6 && (typed_active || variant != 0); }
+    bool runs_all_outputs(int mask) const { return plan.active && mask >= 2 && mask <= 6 && (plan.typed || plan.variant != 0); }
     DevBuf<real> spare;                                      // three force planes, energies, virials: what such a pass is not asked for
     template <class V>
     void launch_brick_force(const Pass<real> &p) {
@@ -711,249 +670,73 @@ struct NbSystem {
         with_mask(List{}, p.mask, [&](auto m) { launch_brick_kernel<V, BRICK_FORCE, decltype(m)::value>(p); });
     }
 
-    // brick decomposition + LDS tile capacity for the current cell populations; false if a tile cannot fit in LDS (then
-    // the direct kernels are used).  Three parts: the brick grid (geometry only), the population maxima (one small kernel,
-    // results in flags[6..8]), and the sizes derived from them on the host.
-    void plan_geometry() {
-        with_brick_variant(variant, [&](auto v) {
-            using V = decltype(v);
-            using S = typename V::Shape;
-            bgrid.nb[0] = (grid.M[0] + S::BX - 1) / S::BX;
-            bgrid.nb[1] = (grid.M[1] + S::BY - 1) / S::BY;
-            bgrid.nb[2] = (grid.M[2] + S::BZ - 1) / S::BZ;
-            bgrid.nbricks = bgrid.nb[0] * bgrid.nb[1] * bgrid.nb[2];
-            bgrid.per_xcd = (bgrid.nbricks + NXCD - 1) / NXCD;
-            // interior bricks: along an open dimension, those whose tile (brick +- 1 cell) stays clear of
-            // the outermost cell layers, where the ghosts of a decomposed run live
-            const int B[3] = {S::BX, S::BY, S::BZ};
-            bgrid.ib_count = 1;
-            for (int d = 0; d < 3; d++) {
-                int lo_b = 0, n_b = bgrid.nb[d];
-                if (!grid.per[d]) {
-                    lo_b = 1;
-                    int hi_b = 1;
-                    while (hi_b < bgrid.nb[d] && (hi_b + 1) * B[d] < grid.M[d] - 1) hi_b++;
-                    n_b = std::max(0, hi_b - lo_b);
-                }
-                bgrid.ib_lo[d] = lo_b; bgrid.ib_n[d] = n_b;
-                bgrid.ib_count *= n_b;
-            }
-            bgrid.ib_per_xcd = (bgrid.ib_count + NXCD - 1) / NXCD;
-            bgrid.bb_z = (bgrid.nb[2] - bgrid.ib_n[2]) * bgrid.nb[0] * bgrid.nb[1];
-            bgrid.bb_y = bgrid.ib_n[2] * (bgrid.nb[1] - bgrid.ib_n[1]) * bgrid.nb[0];
-            bgrid.bb_count = bgrid.nbricks - bgrid.ib_count;
-            bgrid.bb_per_xcd = (bgrid.bb_count + NXCD - 1) / NXCD;
-            row_block = EPL * V::G;
-        });
+    // ---------------------------------------------------------------- the plan (plan.hpp)
+    // what choose_plan and plan_kept decide from: the grid, the counts, the flags of the state and the switches of the environment
+    PlanFacts plan_facts() const {
+        PlanFacts f;
+        f.real_bytes = (int)sizeof(real);
+        for (int d = 0; d < 3; d++) { f.M[d] = grid.M[d]; f.per[d] = grid.per[d]; f.len[d] = len[d]; }
+        f.rlist = rlist;
+        f.n = n_total; f.n_plan = edit_n_plan; f.in_edit = in_edit;
+        f.nt = nt; f.nsub = nsub;
+        f.uniform = uniform_atoms; f.charged = has_charges(); f.ewald = has_ewald(); f.filters_rows = filters_rows();
+        f.brick_path = path == PATH_BRICK;
+        f.stride = stride; f.typed_stride = typed_stride;
+        f.field16_blocked = blocked.field16; f.typed_blocked = blocked.typed;
+        f.typed_all = std::getenv("EMDEE_TYPED_ALL") != nullptr;
+        const char *tb = std::getenv("EMDEE_TYPED_BRICKS");
+        f.typed_bricks7 = tb != nullptr && std::atoi(tb) == 7;
+        f.debug = std::getenv("EMDEE_DEBUG_PLAN") != nullptr;
+        return f;
     }
     // flags[6] = largest tile, flags[7] = most own atoms of a brick, flags[8] = most atoms in three consecutive cells of a tile row
     // (with_build_words: the build's own words flags[0..5) are cleared by the same launch -- the first attempt of build_list)
-    void launch_tile_max(bool with_build_words = false) {
-        with_brick_variant(variant, [&](auto v) {
-            using S = typename decltype(v)::Shape;
-            if (with_build_words) Zeros().add(flags.ptr, 9).run(stream());
-            else Zeros().add(flags.ptr + 6, 3).run(stream());
-            hipLaunchKernelGGL((k_brick_tile_max<S>), dim3(blocks_for(bgrid.nbricks, 256)), dim3(256), 0, stream(), bgrid,
-                               grid.M[0], grid.M[1], grid.M[2], grid.per[0], grid.per[1], grid.per[2], start(),
-                               flags.ptr + 6);
-        });
+    template <class S>
+    void launch_tile_max(const BrickGrid &bg, bool with_build_words = false) {
+        if (with_build_words) Zeros().add(flags.ptr, 9).run(stream());
+        else Zeros().add(flags.ptr + 6, 3).run(stream());
+        hipLaunchKernelGGL((k_brick_tile_max<S>), dim3(blocks_for(bg.nbricks, 256)), dim3(256), 0, stream(), bg, grid.M[0], grid.M[1], grid.M[2],
+                           grid.per[0], grid.per[1], grid.per[2], start(), flags.ptr + 6);
     }
-    // A plan is kept from one rebuild to the next (the populations barely change): capacities carry a few percent of
-    // headroom, and the maxima of the NEW populations are checked after the build, together with its overflow words.
-    static int with_headroom(int v) { return (v + v / 32 + 8 + 15) / 16 * 16; }
-    bool plan_sizes(int max_tile, int max_own, int max_span3) {
-        bool ok = true;
-        with_brick_variant(variant, [&](auto v) {
-            using V = decltype(v);
-            using S = typename V::Shape;
-            tile_cap = std::max(64, with_headroom(max_tile + 1));   // + 1: the sentinel record
-            // (the single-species kernels keep coordinate planes of SOA_SLOTS records: do not let the headroom alone push a tile past them)
-            if (max_tile + 1 <= SOA_SLOTS) tile_cap = std::min(tile_cap, SOA_SLOTS);
-            own_cap = std::max(64, with_headroom(max_own));
-            {   // ... nor cost a workgroup per CU in the build or force kernels: give headroom back 16 records at a time
-                const int exact = std::max(64, (max_tile + 1 + 15) / 16 * 16), st = stride > 0 ? stride : 128;
-                // (a CU holds three workgroups only up to ~50,000 B each, not 160 KB / 3: measured in round 2 by padding the launch)
-                constexpr size_t USABLE = 150000;
-                auto per_cu = [&](int tc) {
-                    const size_t b = brick_build_lds_bytes<S, V::THREADS>(tc, own_cap, st, V::GB, nsub),
-                                 f = brick_force_lds_bytes<real, S, V::THREADS>(tc, own_cap, has_charges());
-                    return (int)(USABLE / std::max<size_t>(b, 1)) * 16 + (int)(USABLE / std::max<size_t>(f, 1));
-                };
-                while (tile_cap > exact && per_cu(tile_cap) < per_cu(exact)) tile_cap -= 16;
+    // The populations choose_plan asks for: one small kernel and one blocking read-back each (plans are rare).  The maxima of a
+    // brick shape are measured once per choose_plan call -- the cell populations cannot change inside it.
+    struct DeviceMeasure {
+        NbSystem &s;
+        bool have[2] = {false, false};
+        std::array<int, 3> memo[2];
+        template <class S>
+        std::array<int, 3> maxima(S) {
+            const int k = S::NOC == 8 ? 1 : 0;               // (the two brick shapes of plan.hpp)
+            if (!have[k]) {
+                s.template launch_tile_max<S>(brick_grid<S>(s.grid.M, s.grid.per));
+                read_back_words(s.ctx, s.stream(), s.flags.ptr + 6, 3, s.ctx->host_flags + 6);
+                memo[k] = {s.ctx->host_flags[6], s.ctx->host_flags[7], s.ctx->host_flags[8]};
+                have[k] = true;
             }
-            plan_span3 = max_span3 + max_span3 / 16 + 2;
-            if (std::getenv("EMDEE_DEBUG_PLAN"))
-                std::fprintf(stderr, "emdee plan: bricks %d x %d x %d, tile_cap %d (max %d), own_cap %d (max %d), max 3-cell span %d, x sub-bins %d K %d, variant %d\n", bgrid.nb[0],
-                             bgrid.nb[1], bgrid.nb[2], tile_cap, max_tile, own_cap, max_own, max_span3, nsub, sub_k(), variant);
-            build_alg = (!field16_blocked && (V::GB == 8 || V::GB == 16) && plan_span3 <= BUILD2_FIELD * V::GB) ? 3 : 1;
-            // crowded tile rows (long cutoffs): the same build with one 32-bit hit field per row
-            if (build_alg == 1 && (V::GB == 8 || V::GB == 16) && plan_span3 <= 32 * V::GB) build_alg = 5;
-            if (build_alg == 1) plan_span3 = 1 << 30;               // the ballot build has no limit
-            else plan_span3 = (build_alg == 5 ? 32 : BUILD2_FIELD) * V::GB;   // what the chosen build can take
-            lds_bytes = brick_force_lds_bytes<real, S, V::THREADS>(tile_cap, own_cap, has_charges());
-            ok = lds_bytes <= LDS_LIMIT && tile_cap < 65536;
-            // fp32 pre-test of the build kernel (fp64 boxes): brick-relative coordinates are below
-            // cmax, so each is off by <= cmax 2^-24 after rounding; with |d| <= r_list per component the
-            // error of d^2 is below 4 sqrt(3) r_list cmax 2^-24 + 4 r_list^2 2^-23.  Band = 4 x that bound.
-            build_margin = 0.f;
-            if (sizeof(real) == 8) {
-                double cmax = 0.0;
-                const int B[3] = {S::BX, S::BY, S::BZ};
-                for (int d = 0; d < 3; d++) cmax = std::max(cmax, (B[d] + 2) * len[d] / grid.M[d]);
-                const double bound = 4.0 * 1.7320508 * rlist * cmax * std::ldexp(1.0, -24) + 4.0 * rlist * rlist * std::ldexp(1.0, -23);
-                build_margin = (float)(4.0 * bound);
-            }
-        });
-        return ok;
+            return memo[k];
+        }
+        template <class S>
+        int typed_span(S) {
+            const BrickGrid bg = brick_grid<S>(s.grid.M, s.grid.per);
+            EMDEE_HIP_CHECK(hipMemsetAsync(s.flags.ptr + 8, 0, sizeof(int), s.stream()));
+            hipLaunchKernelGGL((k_typed_span_max<S>), dim3(blocks_for(bg.nbricks, 256)), dim3(256), 0, s.stream(), bg, s.grid.M[0], s.grid.M[1],
+                               s.grid.M[2], s.grid.per[0], s.grid.per[1], s.grid.per[2], s.tstart(), s.flags.ptr + 8, s.tsub);
+            EMDEE_HIP_CHECK(hipMemcpyAsync(s.ctx->host_flags + 8, s.flags.ptr + 8, sizeof(int), hipMemcpyDeviceToHost, s.stream()));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(s.stream()));
+            return s.ctx->host_flags[8];
+        }
+    };
+    // full planning with blocking read-backs: the plan, the row stride it asks for, and its lines under EMDEE_DEBUG_PLAN
+    void replan() {
+        std::string text;
+        plan = choose_plan(plan_facts(), DeviceMeasure{*this}, text);
+        if (!text.empty()) std::fputs(text.c_str(), stderr);
+        stride = plan.stride;
+        typed_stride = plan.typed_stride;
+        btab_valid = false;
     }
-    int plan_span3 = 0;                   // most atoms in three consecutive cells of a tile row the chosen build kernel can take
-    // do the maxima of the current populations (flags[6..8], read back) fit the plan in use?
-    bool plan_holds(const int32_t *maxima) const {
-        return maxima[0] + 1 <= tile_cap && maxima[1] <= own_cap && maxima[2] <= plan_span3;
-    }
-    // first plan of a state (or one that no longer holds): blocking read-back of the maxima
-    bool plan_bricks() {
-        plan_geometry();
-        launch_tile_max();
-        read_back_words(ctx, stream(), flags.ptr + 6, 3, ctx->host_flags + 6);
-        for (int k = 0; k < 3; k++) plan_maxima[k] = ctx->host_flags[6 + k];
-        return plan_sizes(plan_maxima[0], plan_maxima[1], plan_maxima[2]);
-    }
-    int plan_maxima[3] = {0, 0, 0};
 
     // ---------------------------------------------------------------- neighbour list
-    bool brick_active = false;
-
-    bool build_fits_lds() {
-        bool ok = true;
-        with_brick_variant(variant, [&](auto v) {
-            using V = decltype(v);
-            ok = brick_build_lds_bytes<typename V::Shape, V::THREADS>(tile_cap, own_cap, stride, V::GB, nsub) <= LDS_LIMIT;
-            if (typed_active) ok = typed_build_lds_bytes<typename V::Shape, V::THREADS>(tile_cap, own_cap, stride, V::GB, V::G) <= LDS_LIMIT;
-        });
-        return ok;
-    }
-
-    // full planning with a blocking read-back: variant, capacities, build kernel, stride rounding, index encoding
-    bool plan_valid = false;
-    int plan_M[3] = {0, 0, 0}, plan_n = 0;
-    void make_plan() {
-        const int n = n_total;
-        variant = 0;
-        brick_active = (path == PATH_BRICK) && n > 0 && plan_bricks();
-        // A tile too large for two workgroups of the default variant per CU (long cutoffs, dense boxes: rc = 3.5
-        // sigma needs 135 KB) would leave 2 waves per SIMD: take the same bricks with 1024-thread workgroups
-        // (measured on the rc = 3.5 mixture: 116 -> 154 steps/s).
-        // (Ewald engines stay on variant 0, one workgroup per CU if need be: under the 128-register budget of 1024 threads the
-        // erfc of their pair loop would spill to scratch memory)
-        if (brick_active && lds_bytes > LDS_LIMIT / 2 && !has_ewald()) {
-            variant = 8;
-            if (!plan_bricks()) { variant = 0; plan_bricks(); }
-        }
-        if (brick_active) {
-            stride = (stride + row_block - 1) / row_block * row_block;   // whole lane-major blocks
-            with_brick_variant(variant, [&](auto v) { stride = std::max(stride, brick_min_stride(decltype(v)::G, decltype(v)::THREADS)); });
-        }
-        // the build kernel's LDS (fp32 tile + tables + one row buffer per lane group) must fit as well: very dense or
-        // very inhomogeneous boxes with a long cutoff fall back to the direct (global-gather) kernels
-        if (brick_active && !build_fits_lds()) {
-            brick_active = false;
-            if (std::getenv("EMDEE_DEBUG_PLAN")) std::fprintf(stderr, "emdee plan: the build kernel's tile does not fit LDS: direct kernels\n");
-        }
-        idx_shift = (brick_active && variant == 0 && uniform_atoms && !has_charges() && tile_cap <= SOA_SLOTS) ? PLANE_SHIFT : 0;
-        // two species: the typed kernels (typed.hpp), if the tile fits their coordinate planes, no three cells of a tile row hold
-        // more atoms of one species than the 16-bit hit fields of their build take, and both kernels fit LDS
-        typed_active = false;
-        if (brick_active && nt == 2 && !typed_blocked && !filters_rows() && !has_charges()) {
-            // (where the general-species kernels take 1024 threads with 8 lanes per atom -- long cutoffs -- the typed ones take
-            // 1024 threads with 4: rows are two block-aligned segments, and blocks of 32 entries pad them half as much as blocks of 64)
-            // Measured (profiles/README.md, round 3): at rc = 3.5 sigma 190.7 -> 218.0 steps/s in fp64 and 233.8 -> 324.2 in fp32; at
-            // rc = 2.5 (variant 0, rows of ~37 entries per species) the 18 short candidate rows cost the build more than the
-            // pair loop gains, 453.9 -> 419.1: short-row boxes keep the general-species kernels (EMDEE_TYPED_ALL=1 overrides)
-            // Long rows (the general kernels chose 1024-thread workgroups): first the small bricks of variant 9, two 512-thread
-            // workgroups per CU -- if its tile and both kernels fit half a CU's LDS --, then variant 7 (EMDEE_TYPED_BRICKS=7: the
-            // A/B baseline).  Short rows: variant 0, on request only.
-            const int keep = variant;
-            int cands[2] = {-1, -1};
-            if (variant == 8) {
-                const char *tb = std::getenv("EMDEE_TYPED_BRICKS");
-                const bool only7 = tb != nullptr && std::atoi(tb) == 7;
-                cands[0] = only7 ? 7 : 9;
-                cands[1] = only7 ? -1 : 7;
-            } else if (variant == 7 || variant == 9 || (variant == 0 && std::getenv("EMDEE_TYPED_ALL") != nullptr)) {
-                cands[0] = variant;
-            }
-            const int keep_maxima[3] = {plan_maxima[0], plan_maxima[1], plan_maxima[2]};
-            for (int ci = 0; ci < 2 && !typed_active; ci++) {
-                const int cand = cands[ci];
-                if (cand < 0) continue;
-                variant = cand;
-                bool same_shape = false;
-                with_brick_variant(keep, [&](auto kv) {
-                    with_brick_variant(cand, [&](auto cv) { same_shape = std::is_same<typename decltype(kv)::Shape, typename decltype(cv)::Shape>::value; });
-                });
-                if (same_shape) {
-                    for (int k = 0; k < 3; k++) plan_maxima[k] = keep_maxima[k];   // (a candidate of another shape left its own)
-                    plan_geometry();
-                    plan_sizes(keep_maxima[0], keep_maxima[1], keep_maxima[2]);
-                }
-                else plan_bricks();                                  // another brick shape: its own population maxima (a read-back; plans are rare)
-                with_brick_variant(variant, [&](auto v) {
-                    using V = decltype(v);
-                    if constexpr (typed_variant<V>()) {
-                        using S = typename V::Shape;
-                        // (the planes hold typed_slots records: do not let the headroom alone push a tile past them)
-                        if (plan_maxima[0] + 1 <= typed_slots<S, V::THREADS>()) tile_cap = std::min(tile_cap, typed_slots<S, V::THREADS>());
-                        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + 8, 0, sizeof(int), stream()));
-                        hipLaunchKernelGGL((k_typed_span_max<S>), dim3(blocks_for(bgrid.nbricks, 256)), dim3(256), 0, stream(), bgrid,
-                                           grid.M[0], grid.M[1], grid.M[2], grid.per[0], grid.per[1], grid.per[2], tstart(), flags.ptr + 8, tsub);
-                        EMDEE_HIP_CHECK(hipMemcpyAsync(ctx->host_flags + 8, flags.ptr + 8, sizeof(int), hipMemcpyDeviceToHost, stream()));
-                        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
-                        const int span = ctx->host_flags[8];
-                        int st = stride;
-                        if (!typed_stride) {
-                            st = std::max(stride, typed_min_stride<V>()) + row_block;   // + the padding between the two segments
-                            st = (st + row_block - 1) / row_block * row_block;
-                        }
-                        const size_t lds_f = typed_force_lds_bytes<real, S, V::THREADS>(own_cap),
-                                     lds_b = typed_build_lds_bytes<S, V::THREADS>(tile_cap, own_cap, st, V::GB, V::G);
-                        // (variant 9 exists to put two workgroups on a CU: it is taken only where both kernels leave room for that)
-                        const size_t room = cand == 9 ? LDS_LIMIT / 2 - 128 : LDS_LIMIT;   // (- the kernels' static LDS)
-                        const bool ok = tile_cap <= typed_slots<S, V::THREADS>() && span <= 16 * V::GB && lds_f <= room && lds_b <= room;
-                        if (std::getenv("EMDEE_DEBUG_PLAN"))
-                            std::fprintf(stderr, "emdee plan: two species, variant %d: tile_cap %d (max %d), own_cap %d, longest 3-cell span of one species %d, stride %d, LDS force %zu build %zu: typed kernels %s\n",
-                                         cand, tile_cap, plan_maxima[0], own_cap, span, st, lds_f, lds_b, ok ? "on" : "off");
-                        if (ok) {
-                            typed_active = true;
-                            stride = st;
-                            typed_stride = true;
-                            idx_shift = PLANE_SHIFT;
-                        }
-                    }
-                });
-            }
-            if (!typed_active && variant != keep) {
-                variant = keep;
-                plan_bricks();
-            }
-        }
-        if (!typed_active) typed_stride = false;
-        if (has_charges() && std::getenv("EMDEE_DEBUG_PLAN"))
-            std::fprintf(stderr, "emdee plan: charged engine, %s, variant %d, LDS force %zu\n", brick_active ? "brick kernels" : "direct kernels",
-                         variant, lds_bytes);
-        plan_valid = brick_active;
-        plan_uniform = uniform_atoms;
-        plan_charged = has_charges();
-        plan_nt = nt;
-        plan_n = in_edit ? edit_n_plan : n;
-        for (int d = 0; d < 3; d++) plan_M[d] = grid.M[d];
-    }
-    bool plan_uniform = false;
-    bool plan_charged = false;
-    int plan_nt = 1;
-    bool typed_blocked = false;           // this state's rows outgrew the typed build (until the next load)
-    bool typed_stride = false;            // the stride already includes the typed rows' segment padding
-
     void build_list() {
         const int n = n_total;
         if (stride == 0) {
@@ -967,56 +750,45 @@ struct NbSystem {
         }
         btab_valid = false;
         // The plan of the previous build of this state (variant, capacities, build kernel) is kept when the cell grid is the
-        // same: the populations barely change between rebuilds, the capacities carry headroom, and the maxima of the new
-        // populations come back with the build's overflow words -- ONE blocking read-back per rebuild instead of two.
-        // (inside resort_edit n is an upper bound: the plan is compared with the number of atoms before the edit)
-        const int np = in_edit ? edit_n_plan : n;
-        bool kept = plan_valid && path == PATH_BRICK && n > 0 && plan_M[0] == grid.M[0] &&
-                    plan_M[1] == grid.M[1] && plan_M[2] == grid.M[2] && plan_n <= np + np / 8 && np <= plan_n + plan_n / 8 &&
-                    plan_uniform == uniform_atoms && plan_nt == nt && plan_charged == has_charges();
-        if (kept) {
-            plan_geometry();
-            // (taking the maxima from k_brick_tables instead, which has every brick's tables in LDS anyway, was measured and
-            // lost: one workgroup per brick means one look at -- or atomic on -- three hot words per brick, 2.84 -> 2.95 ms per
-            // rebuild even with a device-scope look before the atomic, 4.50 ms without; k_brick_tile_max reduces 64 bricks per
-            // wavefront first)
-            launch_tile_max(true);
-            brick_active = true;
-        } else {
-            make_plan();
-        }
+        // same (plan_kept): the maxima of the new populations come back with the build's overflow words -- ONE blocking
+        // read-back per rebuild instead of two.
+        // (taking the maxima from k_brick_tables instead, which has every brick's tables in LDS anyway, was measured and
+        // lost: one workgroup per brick means one look at -- or atomic on -- three hot words per brick, 2.84 -> 2.95 ms per
+        // rebuild even with a device-scope look before the atomic, 4.50 ms without; k_brick_tile_max reduces 64 bricks per
+        // wavefront first)
+        bool kept = plan_kept(plan, plan_facts());
+        if (kept) with_brick_variant(plan.variant, [&](auto v) { launch_tile_max<typename decltype(v)::Shape>(plan.grid, true); });
+        else replan();
         // (a state with a capacity hint -- decomposed domains -- sizes the list for it: no reallocation while atoms come and go)
         const size_t rows = std::max<size_t>((size_t)std::max(n, 1), cap_hint ? capacity : 0);
-        auto replan = [&] { kept = false; plan_valid = false; btab_valid = false; make_plan(); };
         for (int attempt = 0; attempt < 6; attempt++) {
             EMDEE_REQUIRE((double)n * stride < 1.7e10, EMDEE_ERR_OVERFLOW, "neighbour list would exceed 64 GiB");
-            if (in_edit && !brick_active) { edit_abort = true; return; }   // (the direct kernels count atoms on the host: the caller reloads)
+            if (in_edit && !plan.active) { edit_abort = true; return; }   // (the direct kernels count atoms on the host: the caller reloads)
             if (!(kept && attempt == 0)) Zeros().add(flags.ptr, 5).run(stream());   // (a kept plan cleared them with the maxima)
-            if (brick_active) {
+            if (plan.active) {
                 nbr16.ensure(rows * stride);
-                with_brick_variant(variant, [&](auto v) {
+                with_brick_variant(plan.variant, [&](auto v) {
                     using V = decltype(v);
                     if constexpr (typed_variant<V>()) {
-                        if (typed_active) {   // two species: species-major tables and the two-segment build (typed.hpp)
+                        if (plan.typed) {   // two species: species-major tables and the two-segment build (typed.hpp)
                             constexpr int TT = 256;
                             using BT = TypedTables<typename V::Shape, TT>;
                             static_assert(BT::row_ints() == TypedTables<typename V::Shape, V::THREADS>::row_ints(), "table row layout");
-                            btab.ensure((size_t)bgrid.nbricks * BT::row_ints());
+                            btab.ensure((size_t)plan.grid.nbricks * BT::row_ints());
                             BrickArgs<real> ta = brick_args();
                             ta.btab = btab.ptr;
                             if (tsub > 1) {                          // the x-quarter boundaries of every brick's (species, tile cell) blocks
-                                bsub.ensure((size_t)bgrid.nbricks * BT::NTT + 4);
+                                bsub.ensure((size_t)plan.grid.nbricks * BT::NTT + 4);
                                 ta.nsub = tsub; ta.bsub = bsub.ptr;
                             }
-                            hipLaunchKernelGGL((k_typed_tables<real, typename V::Shape, TT>), dim3(bgrid.per_xcd * NXCD), dim3(TT),
+                            hipLaunchKernelGGL((k_typed_tables<real, typename V::Shape, TT>), dim3(plan.grid.per_xcd * NXCD), dim3(TT),
                                                BT::bytes(0), stream(), ta);
                             btab_valid = true;
                             auto kernel = k_typed_build<real, typename V::Shape, V::THREADS, V::GB, V::G>;
-                            lds_build_bytes = typed_build_lds_bytes<typename V::Shape, V::THREADS>(tile_cap, own_cap, stride, V::GB, V::G);
-                            allow_big_lds(kernel, lds_build_bytes);
+                            allow_big_lds(kernel, plan.lds_build);
                             BrickArgs<real> ba = brick_args();
                             ba.nsub = ta.nsub; ba.bsub = ta.bsub;
-                            hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), lds_build_bytes, stream(), ba);
+                            hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), plan.lds_build, stream(), ba);
                             return;
                         }
                     }
@@ -1026,30 +798,29 @@ struct NbSystem {
                         constexpr int TT = V::Shape::NTC <= 128 ? 128 : 256;
                         using BT = BrickTables<typename V::Shape, TT>;
                         static_assert(BT::row_ints() == BrickTables<typename V::Shape, V::THREADS>::row_ints(), "table row layout");
-                        btab.ensure((size_t)bgrid.nbricks * BT::row_ints());
+                        btab.ensure((size_t)plan.grid.nbricks * BT::row_ints());
                         btab_valid = false;
                         BrickArgs<real> ta = brick_args();
                         ta.btab = btab.ptr;
                         ta.stats = nullptr;
-                        if (nsub > 1) { bsub.ensure((size_t)bgrid.nbricks * V::Shape::NTC + 4); ta.bsub = bsub.ptr; }
-                        hipLaunchKernelGGL((k_brick_tables<real, typename V::Shape, TT>), dim3(bgrid.per_xcd * NXCD), dim3(TT),
+                        if (nsub > 1) { bsub.ensure((size_t)plan.grid.nbricks * V::Shape::NTC + 4); ta.bsub = bsub.ptr; }
+                        hipLaunchKernelGGL((k_brick_tables<real, typename V::Shape, TT>), dim3(plan.grid.per_xcd * NXCD), dim3(TT),
                                            BT::bytes(0), stream(), ta);
                         btab_valid = true;
                     }
                     auto kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 1, V::G>;
                     if constexpr (V::GB == 8 || V::GB == 16) {
-                        if (build_alg == 3) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 3, V::G>;
-                        if (build_alg == 5) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 5, V::G>;
+                        if (plan.build_alg == 3) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 3, V::G>;
+                        if (plan.build_alg == 5) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 5, V::G>;
                         // round-robin candidates (brick.hpp): when the force kernels read plane values or 16-byte records with 4 lanes per atom
                         if constexpr (V::G == 4) {
-                            const bool strided_ok = sizeof(real) == 4 || idx_shift != 0;
-                            if (build_alg == 3 && strided_ok) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 13, V::G>;
-                            if (build_alg == 5 && strided_ok) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 15, V::G>;
+                            const bool strided_ok = sizeof(real) == 4 || plan.idx_shift != 0;
+                            if (plan.build_alg == 3 && strided_ok) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 13, V::G>;
+                            if (plan.build_alg == 5 && strided_ok) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 15, V::G>;
                         }
                     }
-                    lds_build_bytes = brick_build_lds_bytes<typename V::Shape, V::THREADS>(tile_cap, own_cap, stride, V::GB, nsub);
-                    allow_big_lds(kernel, lds_build_bytes);
-                    hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), lds_build_bytes, stream(),
+                    allow_big_lds(kernel, plan.lds_build);
+                    hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), plan.lds_build, stream(),
                                        brick_args());
                 });
             } else {
@@ -1067,21 +838,23 @@ struct NbSystem {
             } else {
                 read_back_words(ctx, stream(), flags.ptr, 9, ctx->host_flags);
             }
-            if (kept && (!plan_holds(ctx->host_flags + 6) || ctx->host_flags[2] != 0)) {
+            if (kept && (!plan_holds(plan, ctx->host_flags + 6) || ctx->host_flags[2] != 0)) {
                 // the populations outgrew the kept plan (the kernels skipped the bricks concerned): plan afresh and build again
+                kept = false;
                 replan();
                 continue;
             }
-            if (brick_active && ctx->host_flags[4] != 0) {
+            if (plan.active && ctx->host_flags[4] != 0) {
                 // A lane's share of a tile row did not fit its 16-bit hit field.  The builds cannot overflow it (the plan's widest
                 // 3-cell run is what picked the field): should they ever, the list is NOT taken -- this state goes on with 32-bit fields.
-                EMDEE_REQUIRE(!field16_blocked, EMDEE_ERR_OVERFLOW, "neighbour build: a lane's share of a tile row (%d) overflows its hit field", ctx->host_flags[4]);
-                field16_blocked = true;
+                EMDEE_REQUIRE(!blocked.field16, EMDEE_ERR_OVERFLOW, "neighbour build: a lane's share of a tile row (%d) overflows its hit field", ctx->host_flags[4]);
+                blocked.field16 = true;
+                kept = false;
                 replan();
                 continue;
             }
             EMDEE_REQUIRE(ctx->host_flags[2] == 0, EMDEE_ERR_OVERFLOW, "LDS tile overflow (%d records > %d)",
-                          ctx->host_flags[2], tile_cap);
+                          ctx->host_flags[2], plan.tile_cap);
             int needed = ctx->host_flags[0];
             if (needed <= stride) {
                 builds++;
@@ -1089,15 +862,18 @@ struct NbSystem {
                 apply_exclusions();
                 return;
             }
-            stride = (needed + needed / 8 + 15) / 16 * 16;   // grow and rebuild
-            if (brick_active) stride = (stride + row_block - 1) / row_block * row_block;
-            if (brick_active && typed_active && !build_fits_lds()) {
-                // rows longer than the typed build's LDS row buffers can take: this state goes on with the general-species kernels
-                typed_blocked = true;
+            // grow and rebuild (after_build): rows longer than the typed build's LDS row buffers can take send this state on
+            // with the general-species kernels, rows longer than theirs to the direct kernels
+            bool block_typed = false;
+            plan = after_build(plan, nsub, needed, block_typed);
+            stride = plan.stride;
+            if (block_typed) {
+                blocked.typed = true;
+                kept = false;
                 replan();
                 continue;
             }
-            if (brick_active && !build_fits_lds()) { brick_active = false; idx_shift = 0; btab_valid = false; plan_valid = false; }
+            if (!plan.active) btab_valid = false;
         }
         EMDEE_REQUIRE(false, EMDEE_ERR_OVERFLOW, "neighbour capacity kept overflowing");
     }
@@ -1137,7 +913,7 @@ struct NbSystem {
     // emdee_nbr_* / emdee_md_set_exclusions, _set_pairs14: replaces one of the engine's own tables (n = 0 clears it), all or nothing
     void set_pair_tables(int n_atoms, const int32_t *pairs_dev, int n_pairs, bool one_four, double scale) {
         own_tables.set(pairs_dev, n_pairs, one_four, scale, n_atoms, stream());
-        has_list = false; plan_valid = false;                // (the rows in use were filtered with the old tables; typed rows are not filtered)
+        has_list = false; plan = {};                         // (the rows in use were filtered with the old tables; typed rows are not filtered)
     }
     PairKeys pair_keys() const {
         return PairKeys{use_tags ? tag.ptr : nullptr, tables->rows, tables->p_start.ptr, tables->p_idx.ptr, has_14() ? slots14.ptr : nullptr,
@@ -1160,12 +936,12 @@ struct NbSystem {
         if (has_bonded()) slotsb.ensure(tables->nb + 1);
         if (has_ewald() && has_excl()) slotsx.ensure(tables->nx + 1);
         if (brick_active) {
-            EMDEE_REQUIRE(!typed_active, EMDEE_ERR_STATE, "exclusions: typed rows are not filtered");
-            with_brick_variant(variant, [&](auto v) {
+            EMDEE_REQUIRE(!plan.typed, EMDEE_ERR_STATE, "exclusions: typed rows are not filtered");
+            with_brick_variant(plan.variant, [&](auto v) {
                 using V = decltype(v);
                 auto kernel = k_brick_filter<real, typename V::Shape, V::THREADS, V::G>;
                 using BT = BrickTables<typename V::Shape, V::THREADS>;
-                hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(),
+                hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(),
                                    tables->x_start.ptr, tables->x_idx.ptr, pair_keys(), bonded_keys());
             });
         } else {
@@ -1404,9 +1180,8 @@ struct NbSystem {
 
     bool uniform_atoms = false;            // every atom has the same LJAtom (checked when a state is loaded)
     double uni_sigma2 = 0.0, uni_e4 = 0.0, uni_sigma = 1.0;
-    // neighbour entries = tile slot << idx_shift; single-species boxes store byte offsets into the coordinate planes
+    // neighbour entries = tile slot << plan.idx_shift; single-species boxes store byte offsets into the coordinate planes
     static constexpr int PLANE_SHIFT = sizeof(real) == 8 ? 3 : 2;
-    int idx_shift = 0;
 
     // Are all LJAtom records identical?  (One small kernel + an 8-byte read-back per load.)
     // uniform_known: -1 = look at the atoms at every load; 0 / 1 = the caller vouches that the species set is mixed /
@@ -1417,8 +1192,7 @@ struct NbSystem {
     void detect_uniform_atoms(const emdee_lj_atom *atoms) {
         nt = 1;
         species.n = 1;
-        typed_blocked = false;
-        field16_blocked = false;
+        blocked = {};
         if (uniform_known >= 0 && n_total > 0) {
             uniform_atoms = uniform_known == 1;
             // (decomposed runs: the two species every domain agreed on at the first load, emdee_dd_load)
@@ -1505,7 +1279,7 @@ struct NbSystem {
         if (p.phase != 2 && !p.noise_ready) prepare_noise(p.dt);   // phases 1 and 2 are the two halves of one step
         {
             Timed t(this, p.phase == 2 ? T_STEP_BOUNDARY : T_STEP);
-            with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(p); });
+            with_brick_variant(plan.variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(p); });
         }
         if (p.phase != 1 && lgv_on) lgv_step++;
         if (p.phase != 1) {
@@ -1539,7 +1313,7 @@ struct NbSystem {
             Timed t(this, T_STEP);
             p.trigger = words + i;
             p.guard = i ? words + i - 1 : nullptr;
-            with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(p); });
+            with_brick_variant(plan.variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STEP, 1>(p); });
             swap_step_buffers();
         }
         read_back_words(ctx, stream(), words, B, ctx->host_flags + 9);
@@ -1578,7 +1352,7 @@ struct NbSystem {
         }
         Timed t(this, T_FORCE);
         if (brick_active) {
-            with_brick_variant(variant, [&](auto v) { launch_brick_force<decltype(v)>(p); });
+            with_brick_variant(plan.variant, [&](auto v) { launch_brick_force<decltype(v)>(p); });
             if (p.phase != 1) add_post_terms(p);             // (once per force pass: behind its last half)
             return;
         }
@@ -1754,7 +1528,7 @@ struct NbSystem {
         if (has_list && n_total > 0) {
             EMDEE_HIP_CHECK(hipMemsetAsync(stats.ptr, 0, 3 * sizeof(unsigned long long), stream()));
             if (brick_active) {
-                with_brick_variant(variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STATS, 0>(Pass<real>{}); });
+                with_brick_variant(plan.variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STATS, 0>(Pass<real>{}); });
             } else {
                 int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
                 hipLaunchKernelGGL((k_list_stats<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, view(), nbr.ptr,
@@ -1775,21 +1549,21 @@ struct NbSystem {
         if (n_total == 0) return;
         const int *map = ids_map();
         if (brick_active) {
-            with_brick_variant(variant, [&](auto v) {
+            with_brick_variant(plan.variant, [&](auto v) {
                 using V = decltype(v);
                 if constexpr (typed_variant<V>()) {
-                    if (typed_active) {
+                    if (plan.typed) {
                         auto tk = k_typed_export<real, typename V::Shape, V::THREADS, V::G>;
                         using TTab = TypedTables<typename V::Shape, V::THREADS>;
                         const size_t tlds = TTab::bytes(0);
-                        hipLaunchKernelGGL(tk, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), tlds, stream(), brick_args(), counts, out, capacity, map);
+                        hipLaunchKernelGGL(tk, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), tlds, stream(), brick_args(), counts, out, capacity, map);
                         return;
                     }
                 }
                 auto kernel = k_brick_export<real, typename V::Shape, V::THREADS, V::G>;
                 using BT = BrickTables<typename V::Shape, V::THREADS>;
                 const size_t lds = BT::bytes(0);
-                hipLaunchKernelGGL(kernel, dim3(bgrid.per_xcd * NXCD), dim3(V::THREADS), lds, stream(), brick_args(), counts, out,
+                hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), lds, stream(), brick_args(), counts, out,
                                    capacity, map);
             });
         } else {

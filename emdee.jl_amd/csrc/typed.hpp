@@ -24,27 +24,9 @@
 
 namespace emdee {
 
-constexpr int TNT = 2;   // species of a typed box
-
-// planes of a typed tile: records per plane (compile time: the three reads of a neighbour share one address register).
-// 512-thread workgroups keep the single-species pitch (three workgroups per CU); 1024-thread ones -- long cutoffs: the
-// rc = 3.5 sigma tile holds ~4400 records -- take one workgroup per CU and 4608 records.
-// (round 5: bricks of 2 x 2 x 2 cells -- 64 tile cells, 2916 records at rc = 3.5 sigma and rho* = 0.8 before the melt's fluctuations; 3104 slots are what half a
-// CU's LDS holds in fp64 next to the tables -- in 512-thread workgroups, TWO per CU:
-// with one 1024-thread workgroup per CU the vector units idled 30 % of the kernel -- nothing computes while a tile is staged
-// or a workgroup is replaced, profiles/r05/valu_f64_mix_rc3.5.txt)
+// (TNT, typed_slots, typed_pitch, the prefetch depth, typed_seg_cap and the bytes of dynamic LDS of both kernels: plan.hpp)
 template <class Shape, int THREADS>
-constexpr int typed_slots() { return THREADS >= 1024 ? 4608 : (Shape::NOC == 8 ? 3104 : SOA_SLOTS); }
-template <typename real, class Shape, int THREADS>
-constexpr int typed_pitch() { return typed_slots<Shape, THREADS>() + (sizeof(real) == 8 ? 1 : 0); }
-// index blocks of a row (= of its species-0 segment) fetched one atom ahead: two of 32 entries where rows are short, four where
-// the workgroup is a long-row one (rc = 3.5 sigma: ~92 neighbours per species; NOC = own cells of the brick shape)
-constexpr int typed_prefetch_blocks(int G, int THREADS, int NOC = 16) { return (EPL * G) >= 128 ? 1 : ((G == 4 && (THREADS >= 1024 || NOC == 8)) ? 4 : 2); }
-// entries the build's LDS row buffer holds per atom: ONE segment (the two species are emitted and flushed one after the other)
-constexpr int typed_seg_cap(int stride, int GL) { return ((stride / 2) + EPL * GL - 1) / (EPL * GL) * (EPL * GL); }
-
-template <class Shape, int THREADS>
-struct TypedTables {
+struct TypedTables : TypedTableSizes<Shape, THREADS> {
     static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NTT = TNT * NTC, NOT = TNT * NOC, NWAVES = THREADS / WAVE;
     int *off;      // [NTT+1] tile-local first slot of (species, tile cell), species-major
     int *gbeg;     // [NTT]   global (cell-order) first slot of that block
@@ -53,11 +35,6 @@ struct TypedTables {
     int *wtot;     // [NWAVES]
     int2 *oinfo;   // [own_cap] per own atom (filled by the kernel)
     int *ocnt;     // [own_cap] ... and its row lengths n0 | n1 << 16 (force kernels)
-    __host__ __device__ static constexpr size_t fixed_ints() { return (NTT + 4) + NTT + NTC + (NOT + 4) + ((NWAVES + 1) & ~1); }
-    __host__ __device__ static size_t bytes(int own_cap) { return ((fixed_ints() + 3 * (size_t)own_cap) * 4 + 15) & ~(size_t)15; }
-    // off | gbeg | shift | own are contiguous: that image (+ tile_n, n_own) is what k_typed_tables stores per brick
-    __host__ __device__ static constexpr int image_ints() { return (NTT + 4) + NTT + NTC + (NOT + 4); }
-    __host__ __device__ static constexpr int row_ints() { return (image_ints() + 2 + 3) & ~3; }
     __device__ __forceinline__ void carve(unsigned char *base) {
         off = reinterpret_cast<int *>(base);
         gbeg = off + (NTT + 4);
@@ -68,16 +45,6 @@ struct TypedTables {
     }
     __device__ __forceinline__ void carve_counts(int own_cap) { ocnt = reinterpret_cast<int *>(oinfo + own_cap); }
 };
-
-template <typename real, class Shape, int THREADS>
-static inline size_t typed_force_lds_bytes(int own_cap) {
-    return (((size_t)3 * typed_pitch<real, Shape, THREADS>() * sizeof(real) + 15) & ~(size_t)15) + TypedTables<Shape, THREADS>::bytes(own_cap) + 256;   // (+ the four pair-constant records)
-}
-template <class Shape, int THREADS>
-static inline size_t typed_build_lds_bytes(int tile_cap, int own_cap, int stride, int G, int GL = 4) {
-    return (size_t)tile_cap * 16 + TypedTables<Shape, THREADS>::bytes(own_cap) + (size_t)(THREADS / G) * typed_seg_cap(stride, GL) * 2 +
-           (((size_t)(Shape::NOC * 4 + 1) * 9 * TNT * 4 + 15) & ~(size_t)15);   // (row table: one packed word per (own cell, x quarter, species, row))
-}
 
 // tables of this block's brick; false when the block has nothing to do.  Contains block barriers.
 template <typename real, class Shape, int THREADS, bool COMPUTE = false>

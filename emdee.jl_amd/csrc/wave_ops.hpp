@@ -6,9 +6,9 @@
 
 #include <hip/hip_runtime.h>
 
-namespace emdee {
+#include "plan.hpp"   // WAVE
 
-constexpr int WAVE = 64;
+namespace emdee {
 
 // DPP control words (GFX9 encoding)
 constexpr int DPP_ROW_SHR1 = 0x111;

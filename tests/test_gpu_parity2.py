@@ -751,3 +751,22 @@ def test_exclusions_on_a_single_species_box(emdee, oracle, dev, dtype):
     rows2 = _rows(*md2.neighbor_lists())
     assert all(partner[i] not in rows2[i] for i in range(0, N, 7))
     md.close(); md2.close()
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+@pytest.mark.parametrize("family", ["uniform", "species3", "long_rows", "typed", "typed_all", "direct", "long_rows_charged"])
+def test_plan_lines_match_the_recorded_ones(emdee, dev, capfd, monkeypatch, family, bits):
+    """The `emdee plan:` lines of the family boxes of tests/helpers/mask_cases.py, and of the charged long-row box under the
+    reaction field and under Ewald summation, are byte for byte the ones recorded in tests/golden/plan_lines.json before the
+    planner became a function (tests/test_plan_host.py feeds the same file to choose_plan on the host)."""
+    import json
+
+    from .helpers import plan_cases as pc
+    with open(os.path.join(GOLDEN, "plan_lines.json")) as fh:
+        want = {(c["case"], c["bits"], c["event"]): c for c in json.load(fh)}
+    box, events = pc.run(emdee, dev, family, bits, lambda: capfd.readouterr().err, monkeypatch.setenv)
+    assert events
+    for event, stride, lines in events:
+        rec = want[(family, bits, event)]
+        assert pc.facts(box, family, bits, event, stride) == rec["facts"]
+        assert lines == rec["lines"], (family, bits, event)
