@@ -176,6 +176,7 @@ struct MdImpl : IMd {
         sys.set_box(lo, len, p);
         sys.set_model(model, skin);
         sys.with_vel = true;
+        sys.image_limit = true;                              // (get_state returns the caller's image)
     }
 
     void set_state(int n_owned, int ng, const void *pos, const void *vel, const emdee_lj_atom *atoms,
@@ -241,6 +242,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         EMDEE_REQUIRE(!sys.bonded_fault.latched, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
         EMDEE_REQUIRE(!sys.ewald_fault.latched, EMDEE_ERR_STATE, "md_step: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
+        EMDEE_REQUIRE(!sys.image_fault.latched, EMDEE_ERR_STATE, "md_step: an atom has travelled more than 511 box lengths from the box (reported before); replace the state");
         for (int k = 0; k < sys.GROUPS; k++) {
             EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_step: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
             require_fitting_table("md_step", k);
@@ -252,6 +254,7 @@ struct MdImpl : IMd {
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
         // with a plain force pass and the closing half kick.
         sys.kick_drift(0.5 * dt, dt);
+        current_mask = 0;                                    // (a call that a rebuild ends early leaves no current forces behind)
         int s = 1;
         if (rebuild_every == 0) {
             // displacement-triggered rebuilds: the inner steps are queued a few at a time (one read-back per
@@ -400,6 +403,7 @@ struct MdImpl : IMd {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
             for (auto &g : sys.groups) if (sys.table(g).present) sys.gather(g);
             sys.kick_drift(0.5 * dt, dt);
+            current_mask = 0;                                // (as in step(): until the force pass of this step)
             for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, dt);
             since_build++;
             const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
@@ -486,6 +490,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md_minimize: no state loaded (call emdee_md_set_state first)");
         EMDEE_REQUIRE(!sys.bonded_fault.latched, EMDEE_ERR_STATE, "md_minimize: a bonded term has lost a partner; replace the tables or the state");
         EMDEE_REQUIRE(!sys.ewald_fault.latched, EMDEE_ERR_STATE, "md_minimize: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
+        EMDEE_REQUIRE(!sys.image_fault.latched, EMDEE_ERR_STATE, "md_minimize: an atom has travelled more than 511 box lengths from the box (reported before); replace the state");
         for (int k = 0; k < sys.GROUPS; k++) {
             EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_minimize: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
             require_fitting_table("md_minimize", k);

@@ -523,10 +523,20 @@ __device__ __forceinline__ void rec_params(const Rec<float> *rec, const float *t
 // Cell-ordered records hold the image of each atom INSIDE the primary box along periodic
 // dimensions (the LDS-tiled kernels add explicit +-L shifts and never apply a minimum image);
 // the number of box lengths removed is kept per atom so caller-order copies return the
-// caller's unwrapped coordinates.  Packed 3 x 10 bits, biased by 512.
+// caller's unwrapped coordinates.  Packed 3 x 10 bits, biased by 512: a count lies in [-512, 511] (img_bound).
 constexpr int IMG_BIAS = 512;
 __device__ __forceinline__ int img_pack(int kx, int ky, int kz) {
     return (kx + IMG_BIAS) | ((ky + IMG_BIAS) << 10) | ((kz + IMG_BIAS) << 20);
+}
+// A count that has left the field must not carry into its neighbours': it is clamped (that atom's unwrapped image is lost, every
+// other atom's stays right) and, where the engine hands positions back (fault != NULL), reported: the first atom to find
+// fault[0] clear leaves its id + 1 there, the axis in fault[1] and the count in fault[2].  The word stays raised until the host
+// clears it (NbSystem::image_fault), so a later rebuild does not overwrite the report.
+__device__ __forceinline__ void img_bound(int &kx, int &ky, int &kz, int atom, int *__restrict__ fault) {
+    if ((((unsigned)kx + IMG_BIAS) | ((unsigned)ky + IMG_BIAS) | ((unsigned)kz + IMG_BIAS)) < 2u * IMG_BIAS) return;
+    const bool bx = kx < -IMG_BIAS || kx >= IMG_BIAS, by = ky < -IMG_BIAS || ky >= IMG_BIAS;
+    if (fault && atomicCAS(fault, 0, atom + 1) == 0) { fault[1] = bx ? 0 : by ? 1 : 2; fault[2] = bx ? kx : by ? ky : kz; }
+    kx = min(max(kx, -IMG_BIAS), IMG_BIAS - 1); ky = min(max(ky, -IMG_BIAS), IMG_BIAS - 1); kz = min(max(kz, -IMG_BIAS), IMG_BIAS - 1);
 }
 __device__ __forceinline__ void img_unpack(int v, int &kx, int &ky, int &kz) {
     kx = (v & 1023) - IMG_BIAS; ky = ((v >> 10) & 1023) - IMG_BIAS; kz = ((v >> 20) & 1023) - IMG_BIAS;
@@ -558,7 +568,8 @@ __global__ void k_gather_user(int n, int n_owned, size_t pitch, GridP<real> g, c
                               int *__restrict__ perm, int *__restrict__ inv_perm, int *__restrict__ cell_sorted,
                               int *__restrict__ img, int nt = 1, const long long *__restrict__ tag_in = nullptr,
                               long long *__restrict__ tag_out = nullptr, int ncell = 0, int *__restrict__ cstart = nullptr,
-                              const int *__restrict__ tstart = nullptr, RelGrid rel_out = RelGrid{}) {
+                              const int *__restrict__ tstart = nullptr, RelGrid rel_out = RelGrid{},
+                              int *__restrict__ img_fault = nullptr) {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     // (typed boxes and x sub-bins: the first slot of every CELL from the per-(cell, digit) starts -- rides here instead of
     // being a launch of its own)
@@ -570,17 +581,19 @@ __global__ void k_gather_user(int n, int n_owned, size_t pitch, GridP<real> g, c
     const int kx = wrap_into_box(x, g.lo[0], g.len[0], g.per[0]);
     const int ky = wrap_into_box(y, g.lo[1], g.len[1], g.per[1]);
     const int kz = wrap_into_box(z, g.lo[2], g.len[2], g.per[2]);
-    img[p] = img_pack(kx, ky, kz);
+    int jx = kx, jy = ky, jz = kz;
     emdee_lj_atom a = atoms[i];
     if (sizeof(real) == 4 && rel_out.on) {                   // cell-relative records (RelGrid)
         double ox, oy, oz;
         rel_out.origin(cell_of[i] / nt, ox, oy, oz);
         double rx = (double)x - ox, ry = (double)y - oy, rz = (double)z - oz;
-        int jx = kx + rel_nearest_image(rx, (double)g.len[0], g.per[0]), jy = ky + rel_nearest_image(ry, (double)g.len[1], g.per[1]),
-            jz = kz + rel_nearest_image(rz, (double)g.len[2], g.per[2]);
-        img[p] = img_pack(jx, jy, jz);
+        jx += rel_nearest_image(rx, (double)g.len[0], g.per[0]);
+        jy += rel_nearest_image(ry, (double)g.len[1], g.per[1]);
+        jz += rel_nearest_image(rz, (double)g.len[2], g.per[2]);
         x = (real)rx; y = (real)ry; z = (real)rz;
     }
+    img_bound(jx, jy, jz, i, img_fault);
+    img[p] = img_pack(jx, jy, jz);
     store_rec<real>(rec, te, p, x, y, z, a.half_sigma, a.twice_sqrt_eps);
     xb[p] = x; xb[pitch + p] = y; xb[2 * pitch + p] = z;
     bool owned = i < n_owned;
@@ -609,7 +622,8 @@ __global__ void k_gather_sorted(int n, size_t pitch, GridP<real> g, const int *_
                                 int *__restrict__ img, int nt = 1, const long long *__restrict__ tag_in = nullptr,
                                 long long *__restrict__ tag_out = nullptr, const int *__restrict__ n_dev = nullptr,
                                 int *__restrict__ n_out = nullptr, int ncell = 0, int *__restrict__ cstart = nullptr,
-                                const int *__restrict__ tstart = nullptr, RelGrid rel_in = RelGrid{}, RelGrid rel_out = RelGrid{}) {
+                                const int *__restrict__ tstart = nullptr, RelGrid rel_in = RelGrid{}, RelGrid rel_out = RelGrid{},
+                                int *__restrict__ img_fault = nullptr) {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (cstart) for (int c = p; c <= ncell; c += gridDim.x * blockDim.x) cstart[c] = tstart[(size_t)c * nt];
     if (EDIT) {
@@ -647,6 +661,8 @@ __global__ void k_gather_sorted(int n, size_t pitch, GridP<real> g, const int *_
         ky += wrap_into_box(r.y, g.lo[1], g.len[1], g.per[1]);
         kz += wrap_into_box(r.z, g.lo[2], g.len[2], g.per[2]);
     }
+    int i = EDIT ? o : perm_in[o];
+    img_bound(kx, ky, kz, i, img_fault);
     img[p] = img_pack(kx, ky, kz);
     store_rec<real>(rec, te, p, r.x, r.y, r.z, hs, tev);
     xb[p] = r.x; xb[pitch + p] = r.y; xb[2 * pitch + p] = r.z;
@@ -655,7 +671,6 @@ __global__ void k_gather_sorted(int n, size_t pitch, GridP<real> g, const int *_
     }
     if (im_out) im_out[p] = im_in[o];
     if (tag_out) tag_out[p] = tag_in[o];
-    int i = EDIT ? o : perm_in[o];
     perm[p] = i;
     inv_perm[i] = p;
     cell_sorted[p] = cell_of[o] / nt;

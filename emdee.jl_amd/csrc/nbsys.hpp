@@ -49,8 +49,10 @@ enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP 
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
 // (k_ewald_struck); W_SETTLE / W_HBONDS, a molecule / a cluster that moved too far for a solution (k_constraint_positions).
 // Words of the table checks (k_constraint_check), cleared and read by every check: W_RIGID_MASS, W_RIGID_DIST; W_HBONDS_DIST.
+// W_IMAGE, three words: an atom (id + 1) whose periodic image count left its 10-bit field, the axis and the count (kernels.hpp
+// img_bound, raised by the two gathers); they ride the read-back every build makes.
 enum FlagWord { W_BONDED = 16, W_CHARGES = 17, W_EWALD = 18, W_SETTLE = 20, W_RIGID_MASS = 21, W_RIGID_DIST = 22, W_HBONDS = 23,
-                W_HBONDS_DIST = 24 };
+                W_HBONDS_DIST = 24, W_IMAGE = 25 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -378,6 +380,7 @@ struct NbSystem {
         lgv_ids = nullptr;                                   // caller-order array of the previous state
         use_tags = tags_user != nullptr;
         reserve(n_own + n_ghost, velocities != nullptr || with_vel, inv_mass != nullptr);
+        if (image_limit) image_fault.reset(flags.ptr, stream());   // (a new state: its counts start from the caller's positions)
         detect_uniform_atoms(atoms);
         configure_grid();
         const int n = n_total;
@@ -390,7 +393,8 @@ struct NbSystem {
                                grid, order.ptr, cell_of.ptr, pos, atoms, velocities, inv_mass, rec.ptr, te.ptr, xb.ptr,
                                with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, perm.ptr, inv_perm.ptr,
                                cell_sorted.ptr, img.ptr, digits(), use_tags ? tags_user : nullptr, use_tags ? tag.ptr : nullptr,
-                               (int)ncell, digits() > 1 ? cstart.ptr : nullptr, count.ptr, rel_grid_next(rel_next, nullptr));
+                               (int)ncell, digits() > 1 ? cstart.ptr : nullptr, count.ptr, rel_grid_next(rel_next, nullptr),
+                               image_word());
         rel_commit(rel_next);
         q_valid = false;
         // ghosts are never written by the step kernel: both position buffers carry their records (LJAtom fields)
@@ -400,7 +404,21 @@ struct NbSystem {
                                perm.ptr, rec.ptr, rec2.ptr);
         sorted = true;
         build_list();
+        if (image_limit && image_words[0] != 0) {            // (the state's positions could not be handed back: no state)
+            sorted = false; has_list = false;
+            image_fault.reset(flags.ptr, stream());
+            EMDEE_REQUIRE(false, EMDEE_ERR_INVALID, "set_state: atom %d lies %d box lengths from the box along axis %d: the image count "
+                          "kept per atom holds -512 .. 511 (positions up to 500 box lengths away are always accepted)",
+                          image_words[0] - 1, image_words[2], image_words[1]);
+        }
     }
+    // An engine that hands positions back in the caller's image (emdee_md_get_state) keeps a count per atom and axis that must stay
+    // in its field (kernels.hpp img_bound).  The gathers raise flags[W_IMAGE ..]; the words come back with every build's read-back
+    // (image_words), a load refuses on them and a rebuild latches image_fault: the engine refuses to step until the state is replaced.
+    bool image_limit = false;
+    FaultWord image_fault{W_IMAGE};
+    int32_t image_words[3] = {0, 0, 0};
+    int *image_word() const { return image_limit ? flags.ptr + W_IMAGE : nullptr; }
 
     // re-bin / re-sort the current state (MD rebuild)
     void resort() {
@@ -421,10 +439,16 @@ struct NbSystem {
                                with_vel ? vel2.ptr : nullptr, with_mass ? im2.ptr : nullptr, perm2.ptr, inv_perm.ptr,
                                cell_sorted2.ptr, img2.ptr, digits(), tk, use_tags ? tag2.ptr : nullptr, (const int *)nullptr,
                                (int *)nullptr, (int)ncell, digits() > 1 ? cstart.ptr : nullptr, count.ptr, rel_in,
-                               rel_grid_next(rel_next, nullptr));
+                               rel_grid_next(rel_next, nullptr), image_word());
         swap_sorted_buffers();
         rel_commit(rel_next);
         build_list();
+        if (image_limit && image_words[0] != 0 && !image_fault.latched) {
+            image_fault.latched = true;
+            EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "rebuild: atom %d has travelled %d box lengths from the box along axis %d: the image "
+                          "count kept per atom holds -512 .. 511; its unwrapped position is lost (every other atom's is intact): replace "
+                          "the state", image_words[0] - 1, image_words[2], image_words[1]);
+        }
     }
     // emdee_md_scale_box: can the box take the factors mu?  (checked before anything is written)
     void check_scaled_box(const double mu[3], double vscale) const {
@@ -836,7 +860,8 @@ struct NbSystem {
                 read_back_words(ctx, stream(), flags.ptr, 9, ctx->host_flags, edit_extra.dev, edit_extra.n, edit_extra.host);
                 edit_extra_read = true;
             } else {
-                read_back_words(ctx, stream(), flags.ptr, 9, ctx->host_flags);
+                // (an engine that keeps counts for its caller: the three words of image_fault ride along)
+                read_back_words(ctx, stream(), flags.ptr, 9, ctx->host_flags, flags.ptr + W_IMAGE, image_limit ? 3 : 0, image_words);
             }
             if (kept && (!plan_holds(plan, ctx->host_flags + 6) || ctx->host_flags[2] != 0)) {
                 // the populations outgrew the kept plan (the kernels skipped the bricks concerned): plan afresh and build again

@@ -484,12 +484,27 @@ int32_t emdee_md_create(emdee_ctx *ctx, const double lo[3], const double len[3],
 int32_t emdee_md_destroy(emdee_md *md);
 /* (Re)load the state, in caller order.  velocities_dev has 3 n_owned reals; inv_mass_dev
  * (n_owned reals) may be NULL for m = 1 (LJAtom has no mass, src/lennard_jones.jl:15-18).
- * Bins, sorts, builds the neighbour list and evaluates the forces. */
+ * Bins, sorts, builds the neighbour list and evaluates the forces.
+ * Positions may lie outside the box: on a periodic axis the engine works on the image inside [lo, lo+len) and keeps, per atom
+ * and axis, the number of box lengths it removed (10 bits: -512 .. 511), so that emdee_md_get_state answers in the caller's
+ * image.  Positions up to 500 box lengths from the box are always accepted.  An atom whose count would leave the field is
+ * refused: EMDEE_ERR_INVALID naming the atom, the axis and the count, and the engine then holds no state (as before the first
+ * emdee_md_set_state) until a valid one is loaded.  Between 500 box lengths and that refusal the outcome is unspecified (the
+ * count of a Float32 engine includes the step to the image next to the atom's cell).  Open axes keep no count.
+ * The counts grow as atoms travel: when a rebuild inside emdee_md_step would push one out of the field, that atom's count
+ * stays at the limit (no other atom's position is affected), the call whose read-back sees it returns EMDEE_ERR_STATE naming
+ * the atom, and emdee_md_step and emdee_md_minimize refuse until the state is replaced.  That call ends inside a step (positions
+ * drifted, velocities half kicked, the forces of that step not evaluated): positions of every other atom read afterwards are
+ * right, velocities are not those of a completed step, and the force plane is the step before's (a read of energies or virials
+ * evaluates all three afresh, as does the next emdee_md_step after a new state). */
 int32_t emdee_md_set_state(emdee_md *md, int32_t n_owned, int32_t n_ghost, const void *positions_dev,
                            const void *velocities_dev, const emdee_lj_atom *atoms_dev,
                            const void *inv_mass_dev);
 /* Copy the state back in caller order; any pointer may be NULL. positions: n_owned+n_ghost
- * atoms; velocities/forces/energies/virials: n_owned atoms. */
+ * atoms; velocities/forces/energies/virials: n_owned atoms.
+ * Positions come back unwrapped, in the image the caller loaded plus what the atom has travelled since: exact to the engine's
+ * rounding for atoms up to 500 box lengths from the box on a periodic axis (the limit of the image counts, see
+ * emdee_md_set_state). */
 int32_t emdee_md_get_state(emdee_md *md, void *positions_dev, void *velocities_dev, void *forces_dev,
                            void *energies_dev, void *virials_dev);
 /* nsteps whole steps (n_ghost must be 0: a decomposed run drives the split calls below).
