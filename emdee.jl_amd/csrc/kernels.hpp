@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "bonded.hpp"
 #include "common.hpp"
 #include "lj_pair.hpp"
 #include "wave_ops.hpp"
@@ -1456,69 +1457,8 @@ __global__ void k_fill_charges(int n, const int *__restrict__ perm, const long l
 // symmetrised tensor sum_a x_a (x) F_a.  A partner missing from the rows (farther than rc + skin at the build) leaves the term
 // out and writes its number + 1 to *err (read by the host: NbSystem::check_bonded).
 // prm: 3 values per term entry -- bond {k, r0, 0}, angle {k, theta0, 0}, torsion {k, n, phase}.
-template <typename real>
-__device__ __forceinline__ void cross3(const real a[3], const real b[3], real c[3]) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-template <typename real>
-__device__ __forceinline__ real dot3(const real a[3], const real b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// U and the forces F[0 .. nat) of one term at unwrapped positions u[0 .. nat) (kind: 1 bond, 2 angle, 3 torsion)
-template <typename real>
-__device__ __forceinline__ real bonded_term(int kind, const real u[4][3], real p0, real p1, real p2, real F[4][3]) {
-    const real tiny = sizeof(real) == 8 ? (real)1e-300 : (real)1e-37;
-    real U;
-    if (kind == 1) {
-        real d[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) d[c] = u[1][c] - u[0][c];
-        const real r = sqrt(dot3(d, d));
-        const real g = p0 * (r - p1) / max(r, tiny);
-#pragma unroll
-        for (int c = 0; c < 3; c++) { F[1][c] = -g * d[c]; F[0][c] = g * d[c]; F[2][c] = 0; F[3][c] = 0; }
-        U = (real)0.5 * p0 * (r - p1) * (r - p1);
-    } else if (kind == 2) {
-        real a[3], b[3], cr[3], ac[3], bc[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) { a[c] = u[0][c] - u[1][c]; b[c] = u[2][c] - u[1][c]; }
-        cross3(a, b, cr);
-        const real cn = sqrt(dot3(cr, cr));
-        const real th = atan2(cn, dot3(a, b));               // finite at 0 and pi (no acos of a clamped cosine needed)
-        const real dU = p0 * (th - p1);
-        cross3(a, cr, ac);
-        cross3(b, cr, bc);
-        const real gi = -dU / (dot3(a, a) * max(cn, tiny)), gk = dU / (dot3(b, b) * max(cn, tiny));
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            F[0][c] = gi * ac[c]; F[2][c] = gk * bc[c]; F[1][c] = -F[0][c] - F[2][c]; F[3][c] = 0;
-        }
-        U = (real)0.5 * p0 * (th - p1) * (th - p1);
-    } else {
-        real b1[3], b2[3], b3[3], m[3], n[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) { b1[c] = u[1][c] - u[0][c]; b2[c] = u[2][c] - u[1][c]; b3[c] = u[3][c] - u[2][c]; }
-        cross3(b1, b2, m);
-        cross3(b2, b3, n);
-        const real b22 = dot3(b2, b2), b2n = sqrt(b22);
-        const real phi = atan2(b2n * dot3(b1, n), dot3(m, n));   // IUPAC: trans = pi
-        const real arg = p1 * phi - p2;
-        const real dU = -p0 * p1 * sin(arg);
-        const real ci = dU * b2n / max(dot3(m, m), tiny), cl = -dU * b2n / max(dot3(n, n), tiny);   // F_i = ci m, F_l = cl n
-        const real s1 = dot3(b1, b2) / max(b22, tiny), s3 = dot3(b3, b2) / max(b22, tiny);
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            F[0][c] = ci * m[c];
-            F[3][c] = cl * n[c];
-            F[1][c] = -((real)1 + s1) * F[0][c] + s3 * F[3][c];
-            F[2][c] = -F[0][c] - F[3][c] - F[1][c];
-        }
-        U = p0 * ((real)1 + cos(arg));
-    }
-    return U;
-}
-
+// The formula of one term -- bonded_term: U and the forces at unwrapped positions, zero force at singular geometries -- is
+// plain C++ in bonded.hpp, where a host program tests it.
 template <typename real, bool TENSOR = false>
 __global__ __launch_bounds__(256) void k_bonded(int n, int n_owned, size_t pitch, AtomView<real> atoms, const int *__restrict__ perm, PairKeys keys,
                          BondedKeys bk, const real *__restrict__ prm, GridP<real> g, int bitmask, real *__restrict__ frc,

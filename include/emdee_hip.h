@@ -184,6 +184,17 @@ int32_t emdee_md_set_pairs14(emdee_md *md, const int32_t *pairs_dev, int32_t n_p
  * 1/3 or 1/4 of the term's energy, of its virial W = sum_a x_a . F_a (x_a unwrapped; a bond gives -r dU/dr) and of its
  * symmetrised tensor sum_a x_a (x) F_a; the energies, virials, tensors and sums of emdee_md_* / emdee_dd_* include them.
  * Bonded terms do not change the pair set: exclusions and 1-4 pairs stay the caller's tables.
+ * Singular geometries.  Where the direction of a term's force is undefined it gives ZERO FORCE on all its atoms and a FINITE
+ * ENERGY, in both precisions, whatever k is: a bond of length 0 (U = k/2 r0^2), an angle with |a x b| = 0 -- straight or folded,
+ * U = k/2 (theta - theta0)^2 with theta = pi or 0 -- and a torsion with |b1 x b2| = 0, |b2 x b3| = 0 or b2 = 0 (U finite: phi is
+ * undefined).  A chain drawn along a lattice line is such a start, and emdee_md_minimize and emdee_*_step go through it: the
+ * atoms stay on their line until something else moves them off it.  "Zero" is decided on the norm the formula divides by, as it
+ * computes it: below 1e-37 (Float32) or 1e-300 (Float64) the force is zero, from there on the quotient is taken as it always was
+ * (every term with its norms above the threshold keeps its bits).  Near a singular geometry the force is not clipped: its error
+ * grows as u / sin(theta) (u the unit round-off; DESIGN.md has the measured constant), and a torsion's force on an end atom grows
+ * as 1 / sin(theta) itself.  Two limits: a torsion's coefficient k n |b2| / |b1 x b2|^2 must stay inside the format (in Float32
+ * and at k n = 1e6 that is sin(theta) above 1e-16 at unit bond lengths), and the zero force of a straight angle holds for arms
+ * longer than 1e-4 (Float32; 1e-11 in Float64) of the length unit.
  *   - emdee_md_set_bonded: caller ids in [0, N), after emdee_md_set_state, undivided boxes.  emdee_dd_set_bonded: global ids
  *     in [0, 2^31), collective, before emdee_dd_load or between steps (after a load it rebuilds every domain).
  *   - Each call replaces the table of its kind; n_terms = 0 clears it.  All or nothing: EMDEE_ERR_INVALID, the previous tables

@@ -4,7 +4,9 @@ periodic torsions, with the engine's per-atom convention.
 Vectors inside a term are chained minimum images along its bonds (d_ij = mi(r_j - r_i), then d_jk, d_kl), so a term that
 crosses the periodic boundary is unwrapped.  Every atom of a term receives its own force (-grad U) and an equal share (1/2,
 1/3, 1/4) of the term's energy U, of its virial W = sum_a x_a . F_a and of its symmetrised tensor sum_a x_a (x) F_a
-(order xx, yy, zz, xy, xz, yz), x_a being the unwrapped positions."""
+(order xx, yy, zz, xy, xz, yz), x_a being the unwrapped positions.  A term at a geometry where the direction of its force is
+undefined (a bond of length 0, a straight or folded angle, a torsion with a collinear bond pair) has zero force and a finite
+energy: the header's contract."""
 import numpy as np
 
 BOND, ANGLE, TORSION = 1, 2, 3
@@ -52,9 +54,11 @@ def term_forces(kind, u, p):
     if kind == ANGLE:
         a, b = u[0] - u[1], u[2] - u[1]
         c = np.cross(a, b)
-        cn = max(np.linalg.norm(c), 1e-300)
-        th = np.arctan2(np.linalg.norm(c), a @ b)
+        cn = np.linalg.norm(c)
+        th = np.arctan2(cn, a @ b)
         dU = p[0] * (th - p[1])
+        if cn < 1e-300:                                      # straight, folded or a zero arm: no direction, no force
+            return 0.5 * p[0] * (th - p[1]) ** 2, np.zeros((3, 3))
         fi = -dU * np.cross(a, c) / ((a @ a) * cn)
         fk = dU * np.cross(b, c) / ((b @ b) * cn)
         return 0.5 * p[0] * (th - p[1]) ** 2, np.array([fi, -fi - fk, fk])
@@ -63,8 +67,10 @@ def term_forces(kind, u, p):
     b2n = np.linalg.norm(b2)
     phi = np.arctan2(b2n * (b1 @ n), m @ n)
     dU = -p[0] * p[1] * np.sin(p[1] * phi - p[2])
-    gi = -b2n / max(m @ m, 1e-300) * m                   # d phi / d x_i
-    gl = b2n / max(n @ n, 1e-300) * n                    # d phi / d x_l
+    if min(m @ m, n @ n, b2 @ b2) < 1e-300:              # a collinear bond pair or b2 = 0: phi is undefined, no force
+        return p[0] * (1.0 + np.cos(p[1] * phi - p[2])), np.zeros((4, 3))
+    gi = -b2n / (m @ m) * m                              # d phi / d x_i
+    gl = b2n / (n @ n) * n                               # d phi / d x_l
     s1, s3 = (b1 @ b2) / (b2 @ b2), (b3 @ b2) / (b2 @ b2)
     gj = -(1.0 + s1) * gi + s3 * gl
     gk = -gi - gl - gj
