@@ -73,6 +73,7 @@ SIGNATURES = {
     "emdee_md_set_pme": [_p, _dbl, C.POINTER(_i32), _i32],
     "emdee_md_set_rigid3": [_p, _p, _p, _i32],
     "emdee_md_set_hbonds": [_p, _p, _p, _i32],
+    "emdee_md_set_vsites": [_p, _p, _p, _i32],
     "emdee_nbr_list": [_p, _p, _p, _i32],
     "emdee_md_nbr_list": [_p, _p, _p, _i32],
     "emdee_compute_nonbonded": [_p, _p, _p, _p, _p, _dbl, _p, LJModelC, _p, _i32, _i32],

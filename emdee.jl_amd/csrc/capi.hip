@@ -275,6 +275,9 @@ int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double
 int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_hbonds(atoms_dev, dist_dev, n_clusters); });
 }
+int32_t emdee_md_set_vsites(emdee_md *md, const int32_t *atoms_dev, const double *weights_dev, int32_t n_sites) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_vsites(atoms_dev, weights_dev, n_sites); });
+}
 int32_t emdee_md_set_ewald(emdee_md *md, double alpha, const int32_t kmax[3]) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_ewald(alpha, kmax); });
 }

@@ -191,6 +191,7 @@ struct MdImpl : IMd {
         // (a constraint table set for another atom count stays in force, unused, as charges do; for the same count the table is
         // checked against the new state and the velocities are projected again)
         for (int k = 0; k < sys.GROUPS; k++) unchecked[k] = unchecked[k] || (!lent && sys.table(sys.groups[k]).present);   // (every table, before a check can refuse)
+        vs_unchecked = vs_unchecked || (!lent && sys.has_vsites());
         for (int k = 0; k < sys.GROUPS; k++) {
             auto &g = sys.groups[k];
             if (lent || !sys.table(g).present) continue;
@@ -201,10 +202,18 @@ struct MdImpl : IMd {
                 unchecked[k] = false;
             }
         }
+        // (a site table for the same count: checked against the new state, the sites placed on their parents with zero velocity,
+        // and the list rebuilt for where they now are)
+        if (!lent && sys.has_vsites() && !sys.vsites_stale() && ng == 0) {
+            sys.check_vsites(sys.tables->vsites);
+            sys.place_sites(true);
+            sys.resort();
+            vs_unchecked = false;
+        }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
         // cleared -- NbSystem::ensure_charges)
         if (!defer_forces && !sys.charges_stale()) {
-            sys.compute_forces(EMDEE_FORCES);
+            force_pass(EMDEE_FORCES);
             current_mask = EMDEE_FORCES;
         }
         EMDEE_HIP_CHECK(hipGetLastError());
@@ -214,6 +223,22 @@ struct MdImpl : IMd {
     // per constraint group (NbSystem::groups): its table has not passed the check against the loaded state (another atom count,
     // ghosts, or a refusal)
     bool unchecked[NbSystem<real>::GROUPS] = {false, false};
+    // ... and the same for the table of virtual sites (emdee_md_set_vsites)
+    bool vs_unchecked = false;
+    bool sites_in_use() const { return !lent && n_ghost == 0 && sys.vsites_fit() && !vs_unchecked; }
+    // A force pass into the engine's own arrays.  With a site table in force, a pass that writes the force planes is followed by the
+    // spreading of the sites' forces to their parents (vsite.hpp), once; a pass that leaves the planes alone (energies and virials
+    // only, the tensor pass, the interior half of a decomposed step) is not.
+    void force_pass(const Pass<real> &p) {
+        sys.compute_forces(p);
+        if ((p.mask & EMDEE_FORCES) && p.phase != 1 && sites_in_use()) sys.spread_sites();
+    }
+    void force_pass(int bitmask) { force_pass(Pass<real>::force(bitmask)); }
+    void require_fitting_sites(const char *what) const {
+        EMDEE_REQUIRE(!sys.has_vsites() || !(sys.vsites_stale() || vs_unchecked), EMDEE_ERR_STATE, "%s: virtual sites set for %lld atoms, the state "
+                      "holds %d (or does not fit them): set them again or clear them (emdee_md_set_vsites)", what,
+                      (long long)sys.tables->vsites.limit, sys.n_owned);
+    }
     // an engine of a decomposition (emdee_dd_engine): its pair tables are the decomposition's, keyed by global id
     bool lent = false;
     // decomposed domains: the global ids of the atoms handed to set_state (caller order, owned atoms and ghosts); they travel
@@ -247,8 +272,9 @@ struct MdImpl : IMd {
             EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_step: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
             require_fitting_table("md_step", k);
         }
+        require_fitting_sites("md_step");
         if (nsteps == 0) return;
-        if (sys.has_rigid() || sys.has_hbonds() || baro.kind != EMDEE_BAROSTAT_OFF) { step_closed(nsteps, dt, rebuild_every); return; }
+        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || baro.kind != EMDEE_BAROSTAT_OFF) { step_closed(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
@@ -333,11 +359,12 @@ struct MdImpl : IMd {
                       "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
         require_fitting_table("scale_box", sys.RIGID);      // (an hbonds table was refused above)
-        sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes)
+        require_fitting_sites("scale_box");
+        sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes; sites go back on their scaled parents)
         since_build = 0;
         current_mask = 0;
         if (!sys.charges_stale()) {
-            sys.compute_forces(EMDEE_FORCES);
+            force_pass(EMDEE_FORCES);
             current_mask = EMDEE_FORCES;
         }
         EMDEE_HIP_CHECK(hipGetLastError());
@@ -387,6 +414,8 @@ struct MdImpl : IMd {
     // remembered, (c) the distances are restored on the drifted records, (e) the bond components of the relative velocities are
     // removed.  Stage (c) re-tests its atoms against the rebuild threshold, so the displacement word is read after it; a re-sort
     // between (c) and (e) is harmless (the stages find atoms through inv_perm).
+    // Virtual sites (emdee_md_set_vsites) add two stages: (c') the sites are put back on their parents after stage (c) of every table
+    // (they raise the same displacement word), (d') their forces are spread to the parents between the force pass and the kick.
     // The order of a step: (a) gather, (b) kick + drift, (c) positions, [re-sort], (d) force pass and kick, (e) velocities; with
     // pressure coupling on, after the step that completes an interval, (f) the event.  Without a table the event's step evaluates
     // the energies and virials with its forces when the coupling is isotropic: no pass is added for the pressure.  With rigid
@@ -398,6 +427,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!coupled || !(rigid || hbonds) || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
         EMDEE_REQUIRE(!coupled || !hbonds, EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
         const bool with_sums = !rigid && !hbonds && baro.coupling == EMDEE_COUPLE_ISOTROPIC;
+        const bool sites = sites_in_use();
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
@@ -405,11 +435,12 @@ struct MdImpl : IMd {
             sys.kick_drift(0.5 * dt, dt);
             current_mask = 0;                                // (as in step(): until the force pass of this step)
             for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, dt);
+            if (sites) sys.place_sites(false);               // (c'): after every constraint table's stage (c), before the word is read
             since_build++;
             const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
             if (rb) { sys.resort(); since_build = 0; }
             const int mask = (event && with_sums) ? 7 : EMDEE_FORCES;
-            sys.compute_forces(mask);
+            force_pass(mask);                                // ((d'): the sites' forces go to their parents before the closing kick)
             sys.kick(0.5 * dt);
             for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
             current_mask = mask;
@@ -495,6 +526,7 @@ struct MdImpl : IMd {
             EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_minimize: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
             require_fitting_table("md_minimize", k);
         }
+        require_fitting_sites("md_minimize");
         sys.ensure_charges();                                // (charges set for another atom count: refused, as a step is)
         struct Unthermostatted {                             // (kick_drift applies the thermostat that is on, and counts its steps)
             NbSystem<real> &s;
@@ -503,12 +535,12 @@ struct MdImpl : IMd {
             ~Unthermostatted() { s.lgv_on = on; }
         } unthermostatted(sys);
         const int mask = EMDEE_FORCES | EMDEE_ENERGIES;
-        const bool tables = sys.has_rigid() || sys.has_hbonds();
+        const bool tables = sys.has_rigid() || sys.has_hbonds(), sites = sites_in_use();
         emdee_minimize_result res{};
         FireState fire = fire_start(dt_start, dt_max);
         double r[FIRE_WORDS + 1];
         sys.zero_velocities();
-        if ((current_mask & mask) != mask) { sys.compute_forces(mask); current_mask = mask; }
+        if ((current_mask & mask) != mask) { force_pass(mask); current_mask = mask; }
         const real *G = sys.constrained_force();
         sys.fire_sums(G, r);
         res.energy0 = r[FIRE_WORDS];
@@ -523,9 +555,10 @@ struct MdImpl : IMd {
             for (auto &g : sys.groups) if (sys.table(g).present) sys.gather(g);
             sys.kick_drift(0.5 * t, t);
             for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, t);
+            if (sites) sys.place_sites(false);
             since_build++;
             if (sys.read_rebuild_flag()) { sys.resort(); since_build = 0; res.rebuilds++; }
-            sys.compute_forces(mask);
+            force_pass(mask);                                // (the sites' forces are their parents': G of a site is 0)
             sys.kick(0.5 * t);
             for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
             current_mask = mask;
@@ -560,7 +593,7 @@ struct MdImpl : IMd {
     }
     void forces(int bitmask, int phase = 0) override {
         use_device(sys.ctx);
-        sys.compute_forces(Pass<real>::force(bitmask, phase));
+        force_pass(Pass<real>::force(bitmask, phase));
         current_mask = phase == 1 ? 0 : bitmask;
         EMDEE_HIP_CHECK(hipGetLastError());
     }
@@ -676,12 +709,13 @@ struct MdImpl : IMd {
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
         // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
-        // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 12, EMDEE_ERR_INVALID, "kernel id out of range");
+        // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps; 13: placement and
+        // force spreading of an engine with virtual sites
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 13, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[13][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[14][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}, {T_MINIMIZE, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -710,7 +744,7 @@ struct MdImpl : IMd {
         sys.has_list = false; sys.plan = {};                 // (the rows in use follow the old tables; charged and uncharged engines take different kernels and LDS plans)
         sys.resort();                                        // the list, rows and slots for the new tables (a two-species box leaves the typed kernels)
         since_build = 0;
-        sys.compute_forces(EMDEE_FORCES);
+        force_pass(EMDEE_FORCES);
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
     }
@@ -758,6 +792,16 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF, EMDEE_ERR_STATE, "set_hbonds: pressure coupling is on (emdee_md_set_barostat): the pressure of "
                       "an engine with an hbonds table lacks the clusters' constraint virial; switch the coupling off first");
         set_groups(sys.HBONDS, "hbonds clusters", [&](auto &&check) { sys.own_tables.set_hbonds(atoms, dist, n_clusters, sys.n_owned, sys.stream(), check); });
+    }
+    // emdee_md_set_vsites: all or nothing -- the candidate table is checked on the host and then against the loaded masses before it
+    // replaces the one in force.  The sites' velocities become 0, the sites are placed, and the list and the forces follow where they
+    // now are (the relisting install path): on return positions, forces and list belong together.
+    void set_vsites(const int32_t *atoms, const double *weights, int32_t n_sites) override {
+        install("virtual sites", "a decomposed run has none", [&] {
+            sys.own_tables.set_vsites(atoms, weights, n_sites, sys.n_owned, sys.stream(), [&](const Topology::VsiteTable &t) { sys.check_vsites(t); });
+            vs_unchecked = false;
+            if (sys.vsites_fit()) sys.place_sites(true);
+        });
     }
     // emdee_md_set_ewald, emdee_md_set_pme: all or nothing -- every refusal comes before the setting changes.  check(): the host
     // test of the setting; set(): EwaldRecip's setter (the mesh takes the place of the direct sum)

@@ -1568,7 +1568,7 @@ __global__ __launch_bounds__(RED_BLOCK) void k_energy_partials(int n, int n_owne
                 double v = (double)vel[d * pitch + p] + (double)(c * im) * (double)frc[d * pitch + p];
                 k2 += v * v;
             }
-            sk += 0.5 * k2 / (double)im;
+            sk += im != (real)0 ? 0.5 * k2 / (double)im : 0.0;   // (a massless atom, a virtual site: exactly 0)
         }
     }
     double t;
@@ -1603,7 +1603,8 @@ __global__ __launch_bounds__(RED_BLOCK) void k_tensor_partials(int n, int n_owne
         if (perm[p] >= n_owned) continue;
         for (int c = 0; c < 6; c++) s[c] += (double)vt[c * pitch + p];
         if (vel) {
-            const double m = 1.0 / (double)(inv_mass ? inv_mass[p] : (real)1);
+            const real im = inv_mass ? inv_mass[p] : (real)1;
+            const double m = im != (real)0 ? 1.0 / (double)im : 0.0;   // (a massless atom, a virtual site: exactly 0)
             const double vx = (double)vel[p], vy = (double)vel[pitch + p], vz = (double)vel[2 * pitch + p];
             s[6] += m * vx * vx; s[7] += m * vy * vy; s[8] += m * vz * vz;
             s[9] += m * vx * vy; s[10] += m * vx * vz; s[11] += m * vy * vz;

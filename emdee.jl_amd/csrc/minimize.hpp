@@ -78,7 +78,8 @@ __device__ __forceinline__ double block_max(double v, double *sh) {
 }
 
 // mode 0: a = w F on every owned slot (the plane the velocity stages project, ConstraintArgs::vel); mode 1, after the projection:
-// a -> G = a / w where the projection changed a component, F itself where it did not (every atom outside the tables).
+// a -> G = a / w where the projection changed a component, F itself where it did not (every atom outside the tables); 0 for an
+// atom with w = 0 (a virtual site, whose force has gone to its parents).
 template <typename real>
 __global__ __launch_bounds__(256) void k_fire_weight(int n, int n_owned, size_t pitch, const int *__restrict__ perm,
                                                      const real *__restrict__ frc, const real *__restrict__ inv_mass,
@@ -91,6 +92,10 @@ __global__ __launch_bounds__(256) void k_fire_weight(int n, int n_owned, size_t 
     const real ax = w * fx, ay = w * fy, az = w * fz;
     if (mode == 0) {
         a[p] = ax; a[pitch + p] = ay; a[2 * pitch + p] = az;
+        return;
+    }
+    if (w == (real)0) {                                      // (a massless atom, a virtual site: G = 0, no 0 / 0)
+        a[p] = (real)0; a[pitch + p] = (real)0; a[2 * pitch + p] = (real)0;
         return;
     }
     const real bx = a[p], by = a[pitch + p], bz = a[2 * pitch + p];

@@ -17,6 +17,7 @@
 #include "shake.hpp"
 #include "topology_dev.hpp"
 #include "typed.hpp"
+#include "vsite.hpp"
 
 namespace emdee {
 
@@ -42,17 +43,19 @@ static inline void refuse_experiment_switches() {
 // T_MOLECULAR: the molecular sums and the molecular scale of an engine with rigid molecules (settle.hpp)
 // T_HBONDS: the three constraint stages of an engine with an hbonds table (shake.hpp)
 // T_MINIMIZE: what emdee_md_minimize adds to the stages of a closed step (minimize.hpp): the constrained force, the reduction, the mixing
+// T_VSITE: placement and force spreading of an engine with virtual sites (vsite.hpp)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_COUNT = 12 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_COUNT = 13 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
 // (k_ewald_struck); W_SETTLE / W_HBONDS, a molecule / a cluster that moved too far for a solution (k_constraint_positions).
 // Words of the table checks (k_constraint_check), cleared and read by every check: W_RIGID_MASS, W_RIGID_DIST; W_HBONDS_DIST.
+// W_VSITE_MASS, two words of the site table's check (k_vsite_check): a site with a mass, a site with a massless parent.
 // W_IMAGE, three words: an atom (id + 1) whose periodic image count left its 10-bit field, the axis and the count (kernels.hpp
 // img_bound, raised by the two gathers); they ride the read-back every build makes.
 enum FlagWord { W_BONDED = 16, W_CHARGES = 17, W_EWALD = 18, W_SETTLE = 20, W_RIGID_MASS = 21, W_RIGID_DIST = 22, W_HBONDS = 23,
-                W_HBONDS_DIST = 24, W_IMAGE = 25 };
+                W_HBONDS_DIST = 24, W_IMAGE = 25, W_VSITE_MASS = 28 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
@@ -488,6 +491,7 @@ struct NbSystem {
         const double nl[3] = {mu[0] * len[0], mu[1] * len[1], mu[2] * len[2]};
         set_box(lo, nl, per);                                // (a changed box invalidates the sort, the list and the plan ...)
         sorted = true;                                       // ... but the records are this state's: the re-sort reads them
+        if (vsites_fit()) place_sites(false);                // (sites back on their scaled parents, on the new box lengths, before the rebuild)
         resort();
     }
     void swap_sorted_buffers() {
@@ -1178,6 +1182,58 @@ struct NbSystem {
             }
     }
     void check_state(ConstraintGroup &g) { check_state(g, table(g).atoms.ptr, table(g).geom.ptr, table(g).atoms_h, table(g).n); }
+
+    // ---------------------------------------------------------------- virtual interaction sites (Topology::set_vsites; vsite.hpp)
+    // Placement after whatever moves parents (MdImpl::step_closed stage (c'), minimize, scale_box, the set call, a reload) and
+    // spreading after every force pass that writes the engine's own force planes (MdImpl::force_pass): one thread per site or per
+    // distinct parent, fp64 sums in table order, no atomics.  Undivided engines only.
+    bool has_vsites() const { return tables->vsites.present; }
+    bool vsites_stale() const { return has_vsites() && (tables->vsites.limit != n_owned || id_gaps); }
+    // the table can be used on this state: it was set for this atom count and the state carries masses (a site's is 0)
+    bool vsites_fit() const { return has_vsites() && !vsites_stale() && with_mass && !has_ghosts && tables->vsites.n > 0; }
+    VsiteArgs<real> vsite_args(const Topology::VsiteTable &t) const {
+        VsiteArgs<real> a{};
+        a.n = t.n; a.n_parents = t.n_parents; a.atoms = t.atoms.ptr; a.weights = t.geom.ptr;
+        a.parent = t.parent.ptr; a.pstart = t.pstart.ptr; a.esite = t.esite.ptr; a.eweight = t.eweight.ptr;
+        a.c = constraint_args(nullptr, nullptr, 0);
+        return a;
+    }
+    // zero_vel: the sites' velocities become 0 as well (the set call, a reload)
+    void place_sites(bool zero_vel) {
+        const Topology::VsiteTable &t = tables->vsites;
+        Timed tm(this, T_VSITE);
+        const real thr = (real)(0.5 * skin);                 // (kick_drift's threshold)
+        hipLaunchKernelGGL((k_vsite_place<real>), dim3(blocks_for(t.n, 256)), dim3(256), 0, stream(), vsite_args(t), (const real *)xb.ptr, thr * thr,
+                           flags.ptr + 1, zero_vel ? 1 : 0);
+    }
+    // the sites' forces go to their parents and become 0: after a pass that has written the force planes, once
+    void spread_sites() {
+        const Topology::VsiteTable &t = tables->vsites;
+        Timed tm(this, T_VSITE);
+        hipLaunchKernelGGL((k_vsite_spread<real>), dim3(blocks_for(t.n_parents, 256)), dim3(256), 0, stream(), vsite_args(t), frc.ptr);
+        hipLaunchKernelGGL((k_vsite_clear<real>), dim3(blocks_for(t.n, 256)), dim3(256), 0, stream(), vsite_args(t), frc.ptr);
+    }
+    // a site table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the site that has
+    // a mass or a parent without one, or the first site when the state was loaded without masses; one launch, one read-back
+    void check_vsites(const Topology::VsiteTable &t) {
+        if (t.n == 0) return;
+        if (!with_mass) {
+            set_error("%s", topo::vsite_message(t.atoms_h, 0, "the state was loaded without masses (inv_mass NULL: every mass is 1), a site needs "
+                                                               "inv_mass = 0: load the state with masses").c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + W_VSITE_MASS, 0, 2 * sizeof(int), stream()));
+        hipLaunchKernelGGL((k_vsite_check<real>), dim3(blocks_for(t.n, 256)), dim3(256), 0, stream(), vsite_args(t), flags.ptr + W_VSITE_MASS);
+        int32_t words[2] = {0, 0};
+        read_back_words(ctx, stream(), flags.ptr + W_VSITE_MASS, 2, words);
+        const char *const text[2] = {"the site has a mass (inv_mass != 0): a virtual site is loaded with inv_mass = 0",
+                                     "a parent is massless (inv_mass == 0): a site is built on atoms with mass"};
+        for (int w = 0; w < 2; w++)
+            if (words[w] != 0) {
+                set_error("%s", topo::vsite_message(t.atoms_h, (int64_t)words[w] - 1, text[w]).c_str());
+                throw Failure{EMDEE_ERR_STATE};
+            }
+    }
 
     void add_post_terms(const Pass<real> &p) {
         add_pairs14(p);

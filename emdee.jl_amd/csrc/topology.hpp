@@ -198,13 +198,17 @@ inline std::string lost_partner_message(const std::vector<int32_t> (&atoms)[KIND
     return text;
 }
 
+// (defined with the site table below) no atom of a constraint table may be a site of the site table in force
+inline void refuse_constrained_sites(const char *name, const char *noun, int sites_per_group, const std::vector<int32_t> &ids,
+                                     const std::vector<int32_t> *vsites);
+
 // ---- rigid three-site molecules (emdee_md_set_rigid3): {apex, a, b} ids and {d_leg, d_base} per molecule
 // The table as a caller gave it: ids in [0, lim), no atom named twice within or across molecules, distances finite and > 0 with
 // d_base < 2 d_leg (a triangle), and no atom that the hbonds table in force names (`hbonds`: its ids, -1 in unused slots; NULL:
-// none in force); else refused.
+// none in force), and no atom that is a site of the site table in force (`vsites`: its {site, a, b, c} ids; NULL: none); else refused.
 template <typename T>
 std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector<double> &geom, int64_t lim,
-                                    const std::vector<int32_t> *hbonds = nullptr) {
+                                    const std::vector<int32_t> *hbonds = nullptr, const std::vector<int32_t> *vsites = nullptr) {
     const int64_t n = (int64_t)(raw.size() / 3);
     EMDEE_REQUIRE((int64_t)geom.size() == 2 * n, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules but %lld distances", (long long)n, (long long)geom.size());
     EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_rigid3: %lld molecules (at most (2^31 - 1) / 3)", (long long)n);
@@ -235,7 +239,9 @@ std::vector<int32_t> checked_rigid3(const std::vector<T> &raw, const std::vector
                           "belongs to a cluster of the hbonds table in force (emdee_md_set_hbonds): an atom is held by one table",
                           (long long)a.first, (long long)a.second);
     }
-    return std::vector<int32_t>(raw.begin(), raw.end());
+    const std::vector<int32_t> out(raw.begin(), raw.end());
+    refuse_constrained_sites("set_rigid3", "molecule", 3, out, vsites);
+    return out;
 }
 // one byte per id in [0, lim): 1 for the atoms a (checked) table names, 0 for the others -- the one-atom molecules of the
 // molecular scale (emdee_md_set_molecular_scaling), which the atom-by-atom scale kernel still moves
@@ -257,11 +263,11 @@ inline std::string rigid3_message(const std::vector<int32_t> &atoms, int64_t mol
 // ---- bonds to hydrogen (emdee_md_set_hbonds): star clusters {centre, s1, s2, s3} with -1 in the unused trailing slots, and the
 // three centre-satellite distances per cluster
 // The table as a caller gave it: ids in [0, lim), at least one satellite, no id after a -1, no atom named twice within or across
-// clusters, none that the rigid table in force names (`rigid`: its ids; NULL: none in force), the distance of every slot in use
-// finite and > 0; else refused.
+// clusters, none that the rigid table in force names (`rigid`: its ids; NULL: none in force), none that is a site of the site
+// table in force (`vsites`: its {site, a, b, c} ids; NULL: none), the distance of every slot in use finite and > 0; else refused.
 template <typename T>
 std::vector<int32_t> checked_hbonds(const std::vector<T> &raw, const std::vector<double> &dist, int64_t lim,
-                                    const std::vector<int32_t> *rigid = nullptr) {
+                                    const std::vector<int32_t> *rigid = nullptr, const std::vector<int32_t> *vsites = nullptr) {
     const int64_t n = (int64_t)(raw.size() / 4);
     EMDEE_REQUIRE((int64_t)dist.size() == 3 * n, EMDEE_ERR_INVALID, "set_hbonds: %lld clusters but %lld distances", (long long)n, (long long)dist.size());
     EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_hbonds: %lld clusters (at most (2^31 - 1) / 4)", (long long)n);
@@ -300,6 +306,7 @@ std::vector<int32_t> checked_hbonds(const std::vector<T> &raw, const std::vector
                           "belongs to a molecule of the rigid table in force (emdee_md_set_rigid3): an atom is held by one table",
                           (long long)a.first, (long long)a.second);
     }
+    refuse_constrained_sites("set_hbonds", "cluster", 4, out, vsites);
     return out;
 }
 // the distances as the kernels read them: those of the unused slots are 0 (never read as a length)
@@ -319,6 +326,122 @@ inline std::string hbonds_message(const std::vector<int32_t> &atoms, int64_t clu
         if (a == 0 || g >= 0) ids += (a ? " " : "") + std::to_string(g);
     }
     snprintf(text, sizeof(text), "hbonds cluster %lld (atoms %s): %s", (long long)cluster, ids.c_str(), what);
+    return text;
+}
+
+// ---- virtual interaction sites (emdee_md_set_vsites; vsite.hpp): {site, a, b, c} ids per entry, c = -1 for a two-parent site,
+// and the weights {w_b, w_c} (w_c ignored where c = -1)
+// The table as a caller gave it: ids in [0, lim) (c may be -1), no atom named twice within an entry, no atom that is a site in two
+// entries, no site that is a parent of another site, no site that the rigid or the hbonds table in force names (`rigid`, `hbonds`:
+// their ids; NULL: none in force), the weights in use finite; else refused.  Parents may belong to either table.
+template <typename T>
+std::vector<int32_t> checked_vsites(const std::vector<T> &raw, const std::vector<double> &weights, int64_t lim,
+                                    const std::vector<int32_t> *rigid = nullptr, const std::vector<int32_t> *hbonds = nullptr) {
+    const int64_t n = (int64_t)(raw.size() / 4);
+    EMDEE_REQUIRE((int64_t)weights.size() == 2 * n, EMDEE_ERR_INVALID, "set_vsites: %lld sites but %lld weights", (long long)n, (long long)weights.size());
+    EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_vsites: %lld sites (at most (2^31 - 1) / 4)", (long long)n);
+    std::vector<std::pair<int64_t, int64_t>> sites, parents;  // (id, entry)
+    sites.reserve((size_t)n); parents.reserve((size_t)3 * n);
+    for (int64_t k = 0; k < n; k++) {
+        for (int a = 0; a < 4; a++) {
+            const int64_t g = raw[(size_t)4 * k + a];
+            if (a == 3 && g == -1) continue;
+            EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_vsites: site %lld names id %lld, outside [0, %lld)%s", (long long)k,
+                          (long long)g, (long long)lim, a == 3 ? " (c = -1 makes a two-parent site)" : "");
+            for (int b = 0; b < a; b++)
+                EMDEE_REQUIRE(raw[(size_t)4 * k + b] != raw[(size_t)4 * k + a], EMDEE_ERR_INVALID, "set_vsites: site %lld names atom %lld twice",
+                              (long long)k, (long long)g);
+            (a == 0 ? sites : parents).emplace_back(g, k);
+        }
+        const bool three = raw[(size_t)4 * k + 3] != -1;
+        EMDEE_REQUIRE(std::isfinite(weights[(size_t)2 * k]) && (!three || std::isfinite(weights[(size_t)2 * k + 1])), EMDEE_ERR_INVALID,
+                      "set_vsites: site %lld has a weight that is not finite", (long long)k);
+    }
+    std::sort(sites.begin(), sites.end());
+    for (size_t k = 1; k < sites.size(); k++)
+        EMDEE_REQUIRE(sites[k].first != sites[k - 1].first, EMDEE_ERR_INVALID, "set_vsites: atom %lld is the site of two entries (%lld and %lld)",
+                      (long long)sites[k].first, (long long)sites[k - 1].second, (long long)sites[k].second);
+    for (const auto &p : parents) {
+        const auto it = std::lower_bound(sites.begin(), sites.end(), std::make_pair(p.first, (int64_t)-1));
+        EMDEE_REQUIRE(it == sites.end() || it->first != p.first, EMDEE_ERR_INVALID, "set_vsites: atom %lld, the site of entry %lld, is a parent "
+                      "of site %lld (a site is built on atoms with mass)", (long long)p.first, it == sites.end() ? -1LL : (long long)it->second,
+                      (long long)p.second);
+    }
+    const std::vector<int32_t> *const held[2] = {rigid, hbonds};
+    const char *const holder[2] = {"a molecule of the rigid table in force (emdee_md_set_rigid3)", "a cluster of the hbonds table in force (emdee_md_set_hbonds)"};
+    for (int t = 0; t < 2; t++) {
+        if (!held[t]) continue;
+        std::vector<int32_t> taken(*held[t]);
+        std::sort(taken.begin(), taken.end());
+        for (const auto &s : sites)
+            EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)s.first), EMDEE_ERR_INVALID, "set_vsites: atom %lld, the site of "
+                          "entry %lld, belongs to %s: a site is massless and follows its parents, it cannot be constrained", (long long)s.first,
+                          (long long)s.second, holder[t]);
+    }
+    return std::vector<int32_t>(raw.begin(), raw.end());
+}
+// the weights as the kernels read them: w_c of a two-parent site is 0 (never a number that is not finite)
+inline std::vector<double> vsite_weights(const std::vector<int32_t> &atoms, const std::vector<double> &weights) {
+    std::vector<double> out(weights);
+    for (size_t k = 0; 4 * k + 3 < atoms.size(); k++)
+        if (atoms[4 * k + 3] < 0) out[2 * k + 1] = 0.0;
+    return out;
+}
+// the mirror refusal of the two constraint builders: no atom of a (checked) rigid or hbonds table may be a site of the site table
+// in force (`vsites`: its {site, a, b, c} ids; NULL: none in force).  Parents may be constrained: that is the point of a site.
+inline void refuse_constrained_sites(const char *name, const char *noun, int sites_per_group, const std::vector<int32_t> &ids,
+                                     const std::vector<int32_t> *vsites) {
+    if (!vsites) return;
+    std::vector<int32_t> taken;
+    for (size_t k = 0; k + 3 < vsites->size(); k += 4) taken.push_back((*vsites)[k]);
+    std::sort(taken.begin(), taken.end());
+    for (size_t k = 0; k < ids.size(); k++)
+        EMDEE_REQUIRE(ids[k] < 0 || !std::binary_search(taken.begin(), taken.end(), ids[k]), EMDEE_ERR_INVALID, "%s: atom %d of %s %lld is a "
+                      "virtual site of the table in force (emdee_md_set_vsites): a site is massless and follows its parents, it cannot be "
+                      "constrained", name, ids[k], noun, (long long)(k / (size_t)sites_per_group));
+}
+// The parent list of a (checked) table with the weights of vsite_weights: the distinct parents in ascending id order, and per
+// parent its (entry, weight) pairs in table order -- weight 1 - w_b - w_c for a, w_b for b, w_c for c.  One thread per parent sums
+// its pairs in that order (vsite.hpp k_vsite_spread): no floating-point atomics, the same bits in every run.
+struct VsiteParents {
+    std::vector<int32_t> parent, start, site;
+    std::vector<double> weight;
+};
+inline VsiteParents build_vsite_parents(const std::vector<int32_t> &atoms, const std::vector<double> &weights) {
+    VsiteParents t;
+    const size_t n = atoms.size() / 4;
+    for (size_t k = 0; k < n; k++)
+        for (int a = 1; a < 4; a++)
+            if (atoms[4 * k + a] >= 0) t.parent.push_back(atoms[4 * k + a]);
+    std::sort(t.parent.begin(), t.parent.end());
+    t.parent.erase(std::unique(t.parent.begin(), t.parent.end()), t.parent.end());
+    const auto row = [&](int32_t g) { return (size_t)(std::lower_bound(t.parent.begin(), t.parent.end(), g) - t.parent.begin()); };
+    t.start.assign(t.parent.size() + 1, 0);
+    for (size_t k = 0; k < n; k++)
+        for (int a = 1; a < 4; a++)
+            if (atoms[4 * k + a] >= 0) t.start[row(atoms[4 * k + a]) + 1]++;
+    for (size_t q = 0; q < t.parent.size(); q++) t.start[q + 1] += t.start[q];
+    t.site.assign((size_t)t.start[t.parent.size()], 0);
+    t.weight.assign((size_t)t.start[t.parent.size()], 0.0);
+    std::vector<int32_t> fill(t.start.begin(), t.start.end() - 1);
+    for (size_t k = 0; k < n; k++) {
+        const double w_b = weights[2 * k], w_c = weights[2 * k + 1];
+        const double w[4] = {0.0, 1.0 - w_b - w_c, w_b, w_c};
+        for (int a = 1; a < 4; a++) {
+            if (atoms[4 * k + a] < 0) continue;
+            const int32_t e = fill[row(atoms[4 * k + a])]++;
+            t.site[(size_t)e] = (int32_t)k;
+            t.weight[(size_t)e] = w[a];
+        }
+    }
+    return t;
+}
+// the error texts of the device check (entry: the number the kernel reports, from 0)
+inline std::string vsite_message(const std::vector<int32_t> &atoms, int64_t entry, const char *what) {
+    char text[512];
+    const bool in = entry >= 0 && (size_t)(4 * entry + 3) < atoms.size();
+    snprintf(text, sizeof(text), "virtual site %lld (atoms %d %d %d %d): %s", (long long)entry, in ? atoms[(size_t)4 * entry] : -1,
+             in ? atoms[(size_t)4 * entry + 1] : -1, in ? atoms[(size_t)4 * entry + 2] : -1, in ? atoms[(size_t)4 * entry + 3] : -1, what);
     return text;
 }
 

@@ -158,7 +158,7 @@ struct Topology {
         DevBuf<unsigned char> nm;
         std::vector<uint8_t> member;                         // (outlives the upload)
         const bool set = set_groups(rigid, "set_rigid3", "molecules", 3, 2, atoms_dev, geom_dev, n, lim, s, [&](std::vector<int32_t> &ids, std::vector<double> &geom) {
-            ids = topo::checked_rigid3(ids, geom, lim, hbonds.present ? &hbonds.atoms_h : nullptr);
+            ids = topo::checked_rigid3(ids, geom, lim, hbonds.present ? &hbonds.atoms_h : nullptr, vsites.present ? &vsites.atoms_h : nullptr);
             member = topo::rigid3_members(ids, lim);
             put(nm, member, s);
         }, check);
@@ -167,9 +167,44 @@ struct Topology {
     template <class Check>
     void set_hbonds(const int32_t *atoms_dev, const double *dist_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
         set_groups(hbonds, "set_hbonds", "clusters", 4, 3, atoms_dev, dist_dev, n, lim, s, [&](std::vector<int32_t> &ids, std::vector<double> &dist) {
-            ids = topo::checked_hbonds(ids, dist, lim, rigid.present ? &rigid.atoms_h : nullptr);
+            ids = topo::checked_hbonds(ids, dist, lim, rigid.present ? &rigid.atoms_h : nullptr, vsites.present ? &vsites.atoms_h : nullptr);
             dist = topo::hbonds_distances(ids, dist);
         }, check);
+    }
+
+    // ---- virtual interaction sites (emdee_md_set_vsites; vsite.hpp), undivided engines only: {site, a, b, c} caller ids (c = -1: a
+    // two-parent site) and {w_b, w_c} per entry as `sites` (GroupTable: atoms, geom), and the parent list of topo::VsiteParents
+    struct VsiteTable : GroupTable {
+        DevBuf<int> parent, pstart, esite;
+        DevBuf<double> eweight;
+        int n_parents = 0;
+    };
+    VsiteTable vsites;
+    // Replaces the table by the n entries at atoms_dev / weights_dev (device); n = 0 clears it.  check(table): the engine's test
+    // of the uploaded candidate against its state; it throws to refuse, and the table in force stays.
+    template <class Check>
+    void set_vsites(const int32_t *atoms_dev, const double *weights_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && weights_dev)), EMDEE_ERR_INVALID, "set_vsites: negative count or NULL array");
+        if (n == 0) {
+            vsites.present = false; vsites.n = 0; vsites.n_parents = 0; vsites.atoms_h.clear();
+            return;
+        }
+        EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_vsites: %lld sites (at most (2^31 - 1) / 4)", (long long)n);
+        VsiteTable t;
+        t.atoms_h = topo::checked_vsites(fetch(atoms_dev, (size_t)4 * n, s), fetch(weights_dev, (size_t)2 * n, s), lim,
+                                         rigid.present ? &rigid.atoms_h : nullptr, hbonds.present ? &hbonds.atoms_h : nullptr);
+        const std::vector<double> w = topo::vsite_weights(t.atoms_h, fetch(weights_dev, (size_t)2 * n, s));
+        const topo::VsiteParents par = topo::build_vsite_parents(t.atoms_h, w);
+        put(t.atoms, t.atoms_h, s); put(t.geom, w, s);
+        put(t.parent, par.parent, s); put(t.pstart, par.start, s); put(t.esite, par.site, s); put(t.eweight, par.weight, s);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        t.n = (int)n; t.n_parents = (int)par.parent.size(); t.limit = lim; t.present = true;
+        check(t);
+        // ---- commit
+        vsites.atoms.swap(t.atoms); vsites.geom.swap(t.geom); vsites.parent.swap(t.parent); vsites.pstart.swap(t.pstart);
+        vsites.esite.swap(t.esite); vsites.eweight.swap(t.eweight);
+        vsites.atoms_h = t.atoms_h;
+        vsites.n = t.n; vsites.n_parents = t.n_parents; vsites.limit = lim; vsites.present = true;
     }
 
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the

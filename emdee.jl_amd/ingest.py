@@ -225,6 +225,24 @@ def rigid_triatomics(types, bonds, table, length_unit=1.0, with_dropped=False):
     return out + (arr(drop_b, 2), arr(drop_a, 3)) if with_dropped else out
 
 
+def bisector_sites(sites, molecules, d_leg, d_base, d_om):
+    """The site table (emdee_md_set_vsites) of a fourth site on the bisector of rigid three-site molecules, at d_om from the apex
+    towards the legs: sites (n,) the ids of the massless sites, molecules (n, 3) ids {apex, a, b} (rigid_triatomics' first result),
+    d_leg, d_base the molecules' distances (scalars or (n,)).  With h = sqrt(d_leg^2 - d_base^2 / 4) the height of the triangle,
+    the site apex + w (a - apex) + w (b - apex) lies 2 w h from the apex: w_b = w_c = d_om / (2 h).
+    Returns (atoms (n, 4) int32 {site, apex, a, b}, weights (n, 2) float64)."""
+    mol = np.asarray(molecules, dtype=np.int64).reshape(-1, 3)
+    site = np.asarray(sites, dtype=np.int64).reshape(-1)
+    if site.shape[0] != mol.shape[0]:
+        raise ValueError("bisector_sites: %d sites but %d molecules" % (site.shape[0], mol.shape[0]))
+    d_leg, d_base, d_om = (np.broadcast_to(np.asarray(v, dtype=np.float64), site.shape) for v in (d_leg, d_base, d_om))
+    h2 = d_leg ** 2 - 0.25 * d_base ** 2
+    if (h2 <= 0.0).any():
+        raise ValueError("bisector_sites: d_base >= 2 d_leg is no triangle")
+    w = d_om / (2.0 * np.sqrt(h2))
+    return np.concatenate([site[:, None], mol], axis=1).astype(np.int32), np.stack([w, w], axis=1)
+
+
 def hydrogen_clusters(types, bonds, table, length_unit=1.0, skip=(), with_dropped=False):
     """The star clusters of bonds to hydrogen (emdee_md_set_hbonds) of a bond graph: every non-hydrogen atom together with the
     one, two or three hydrogens bonded to it.  Hydrogen is decided by the `element` attribute of the atom's type

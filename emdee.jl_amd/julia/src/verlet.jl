@@ -99,6 +99,14 @@ set_hbonds!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, dist::U
     check(ccall((:emdee_md_set_hbonds, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
                 atoms === nothing ? C_NULL : atoms.ptr, dist === nothing ? C_NULL : dist.ptr, atoms === nothing ? 0 : size(atoms, 2)))
 
+# int32_t emdee_md_set_vsites(emdee_md *md, const int32_t *atoms_dev, const double *weights_dev, int32_t n_sites);
+# Virtual interaction sites (the fourth site of TIP4P-family water and OPC): atoms a device Int32 matrix (4, n) of caller ids
+# {site, a, b, c} (0-based, c = -1 for a two-parent site), weights a device Float64 matrix (2, n) of {w_b, w_c}; the sites are
+# loaded with inv_mass = 0.  Zeroes the sites' velocities, places them, rebuilds the list and the forces; `nothing` clears the table.
+set_vsites!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, weights::Union{Nothing,HipArray{Float64,2}}=nothing) =
+    check(ccall((:emdee_md_set_vsites, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
+                atoms === nothing ? C_NULL : atoms.ptr, weights === nothing ? C_NULL : weights.ptr, atoms === nothing ? 0 : size(atoms, 2)))
+
 # int32_t emdee_md_minimize(emdee_md *md, int32_t max_iter, double f_tol, double dt_start, double dt_max, double max_step,
 #                           emdee_minimize_result *out);
 # Energy minimisation by FIRE around the constrained step: at most max_iter iterations, until no atom's constrained force exceeds

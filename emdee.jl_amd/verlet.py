@@ -62,7 +62,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the constraint stages of an engine with an hbonds table (set_hbonds_)
            "hbonds": 11,
            # what minimize_ adds to the stages of its steps: the constrained force, the reduction, the mixing
-           "minimize": 12}
+           "minimize": 12,
+           # placement and force spreading of an engine with virtual sites (set_vsites_)
+           "vsites": 13}
 
 
 class MinimizeResult:
@@ -412,6 +414,24 @@ class VelocityVerlet:
             raise ValueError("set_hbonds_: %d clusters but %d rows of distances" % (a.shape[0], g.shape[0]))
         _lib.call("emdee_md_set_hbonds", self._handle, C.c_void_p(a.data_ptr()) if a.numel() else None,
                   C.c_void_p(g.data_ptr()) if g.numel() else None, int(a.shape[0]))
+
+    def set_vsites_(self, atoms, weights):
+        """Virtual interaction sites (include/emdee_hip.h emdee_md_set_vsites): atoms (n, 4) caller ids {site, a, b, c} with c = -1
+        for a two-parent site, weights (n, 2) {w_b, w_c}; x_site = x_a + w_b (x_b - x_a) + w_c (x_c - x_a).  The sites are loaded
+        with inv_mass = 0.  Zeroes the sites' velocities, places them, rebuilds the list and evaluates the forces; every later
+        step_ and minimize_ keeps them on their parents and hands their forces to the parents.  Empty or None clears the table."""
+        a = torch.as_tensor(atoms if atoms is not None else [])
+        w = torch.as_tensor(weights if weights is not None else [], dtype=torch.float64)
+        if a.numel() and (a.dim() != 2 or a.shape[1] != 4):
+            raise ValueError("set_vsites_: atoms must have shape (n, 4), got %s" % (tuple(a.shape),))
+        if w.numel() and (w.dim() != 2 or w.shape[1] != 2):
+            raise ValueError("set_vsites_: weights must have shape (n, 2), got %s" % (tuple(w.shape),))
+        a = a.reshape(-1, 4).to(device=self.device, dtype=torch.int32).contiguous()
+        w = w.reshape(-1, 2).to(device=self.device).contiguous()
+        if a.shape[0] != w.shape[0]:
+            raise ValueError("set_vsites_: %d sites but %d rows of weights" % (a.shape[0], w.shape[0]))
+        _lib.call("emdee_md_set_vsites", self._handle, C.c_void_p(a.data_ptr()) if a.numel() else None,
+                  C.c_void_p(w.data_ptr()) if w.numel() else None, int(a.shape[0]))
 
     def close(self):
         if self._handle is not None:

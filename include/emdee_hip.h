@@ -406,6 +406,51 @@ int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double
  *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 11. */
 int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters);
 
+/* Virtual interaction sites: massless particles that carry interactions (a charge, LJ parameters) and sit at a fixed linear
+ * combination of two or three atoms with mass -- the fourth site of TIP4P/2005, TIP4P-Ew, TIP4P/Ice and OPC, GROMACS' site types 2
+ * and 3 (build-defined like the integrator).
+ * atoms_dev: 4 n_sites caller ids {site, a, b, c}, c = -1 for a two-parent site; weights_dev: 2 n_sites doubles {w_b, w_c} (w_c is
+ * ignored when c = -1).  Device arrays, copied.  n_sites = 0 clears the table.
+ *   Placement:  x_site = x_a + w_b mi(x_b - x_a) + w_c mi(x_c - x_a), mi the minimum image, in fp64 in both precisions (a Float32
+ *               engine's cell-relative records get their origins added in double); the site's record moves to the image of the
+ *               result nearest to where it was.  A bisector site at d_OM from the apex of a triangle (d_leg, d_base) has
+ *               w_b = w_c = d_OM / (2 sqrt(d_leg^2 - d_base^2 / 4)).
+ *   Spreading:  after a force pass, f_a += (1 - w_b - w_c) f_site, f_b += w_b f_site, f_c += w_c f_site, then f_site = 0.  One
+ *               thread per distinct parent sums its shares in table order, in fp64: no floating-point atomics, runs stay bit
+ *               for bit reproducible.  Several sites may share parents.
+ * Out-of-plane sites (TIP5P's lone pairs, a cross product of the legs) are not covered: a follow-up.
+ * Placement is linear, so sum_k x_k (x) (w_k f_site) = x_site (x) f_site on unwrapped coordinates: the box sums of energies,
+ * virials and tensors are those of the force field and are not touched.  The PER-ATOM energies, virials and tensors keep the
+ * site's half of its pair terms on the site; only the forces move to the parents.
+ *   - Sites are massless: the caller loads them with inv_mass = 0, and kick, drift and Langevin noise then leave them alone; the
+ *     kinetic energy and the kinetic tensor count them as exactly 0.  One device check, one read-back: EMDEE_ERR_STATE naming the
+ *     site, the previous table in force, for a site with inv_mass != 0, a parent with inv_mass == 0, or a state loaded without
+ *     masses.
+ *   - On success the call zeroes the sites' velocities, places the sites, rebuilds the neighbour list and evaluates the forces
+ *     (spread): on return positions, forces and list belong together.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: a NULL array with n_sites > 0, n_sites < 0, an id outside
+ *     [0, n_owned), a or b negative, an atom named twice within an entry, an atom that is a site in two entries, a site that is a
+ *     parent of another site, a site that the rigid or hbonds table in force names (emdee_md_set_rigid3 and emdee_md_set_hbonds
+ *     refuse the mirror case: an atom that is a site; PARENTS may be in either table), a weight in use that is not finite.
+ *     EMDEE_ERR_STATE also before emdee_md_set_state, with ghosts, and on an integrator lent by emdee_dd_engine.
+ *   - The table survives an emdee_md_set_state with the same atom count: it is checked again (EMDEE_ERR_STATE from
+ *     emdee_md_set_state if it does not fit), the sites are placed, their velocities zeroed and the list rebuilt.  After a state
+ *     with another count, or one that did not fit, emdee_md_step and emdee_md_minimize return EMDEE_ERR_STATE until the table is
+ *     set again or cleared.
+ *   - While a table is in force emdee_md_step takes the closed form of emdee_md_set_rigid3 with two more stages: (c') after stage
+ *     (c) of every constraint table the sites are placed (they are tested against the skin/2 threshold and raise the same rebuild
+ *     word), (d') between the force pass and the closing kick the forces are spread.  emdee_md_minimize does the same; G of a
+ *     site is 0.  Every force pass that writes the engine's force planes spreads once (emdee_md_set_state, emdee_md_forces,
+ *     emdee_md_scale_box, emdee_md_get_state or emdee_md_energies evaluating all outputs); the tensor pass leaves the planes alone
+ *     and does not.
+ *   - emdee_md_scale_box, atom by atom or molecular, puts the sites back on their scaled parents before its rebuild: with
+ *     emdee_md_set_molecular_scaling a site moves rigidly with its water, the molecular sums need nothing (the site is massless
+ *     and carries no force after spreading), and pressure coupling works for four-site rigid water.
+ *   - The split calls (emdee_md_kick_drift, _kick, _fused_step) never place sites, as they never constrain; there is no emdee_dd_*
+ *     counterpart.
+ *   - The device time of placement and spreading is emdee_md_kernel_time index 13. */
+int32_t emdee_md_set_vsites(emdee_md *md, const int32_t *atoms_dev, const double *weights_dev, int32_t n_sites);
+
 /* Energy minimisation on the device: FIRE (Bitzek, Koskinen, Gaehler, Moseler & Gumbsch, Phys. Rev. Lett. 97, 170201 (2006);
  * build-defined like the integrator), for free atoms, rigid molecules (emdee_md_set_rigid3) and hbonds clusters
  * (emdee_md_set_hbonds) alike: what prepares a box with close contacts for emdee_md_step.
@@ -629,7 +674,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3);
  * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling);
  * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds); 12 = what emdee_md_minimize adds to the
- * stages of its steps (the constrained force, the reduction, the mixing).  Blocking. */
+ * stages of its steps (the constrained force, the reduction, the mixing); 13 = placement and force spreading of an engine with
+ * virtual sites (emdee_md_set_vsites).  Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
