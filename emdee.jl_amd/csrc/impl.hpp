@@ -188,27 +188,23 @@ struct MdImpl : IMd {
         if (!lent) { sys.reset_bonded_error(); sys.reset_ewald_error(); }   // (a new state: the bonded terms and the struck pairs get another chance; a decomposition resets its own)
         since_build = 0;
         current_mask = 0;
-        // (a constraint table set for another atom count stays in force, unused, as charges do; for the same count the table is
-        // checked against the new state and the velocities are projected again)
-        for (int k = 0; k < sys.GROUPS; k++) unchecked[k] = unchecked[k] || (!lent && sys.table(sys.groups[k]).present);   // (every table, before a check can refuse)
-        vs_unchecked = vs_unchecked || (!lent && sys.has_vsites());
-        for (int k = 0; k < sys.GROUPS; k++) {
-            auto &g = sys.groups[k];
-            if (lent || !sys.table(g).present) continue;
-            sys.reset_error(g);
-            if (!sys.stale(g) && ng == 0) {
-                sys.check_state(g);
-                sys.velocities(g);
-                unchecked[k] = false;
+        // (an attached table set for another atom count stays in force, unused, as charges do; for the same count it is checked
+        // against the new state, the constraint tables first: their velocities are projected again; then the site table: the sites
+        // are placed on their parents with zero velocity and the list is rebuilt for where they now are)
+        for (int k = 0; k < TABLES; k++) unchecked[k] = unchecked[k] || (!lent && attached(k).present);   // (every table, before a check can refuse)
+        for (int k = 0; k < TABLES; k++) {
+            if (lent || !attached(k).present) continue;
+            if (k != VSITES) sys.reset_error(sys.groups[k]);
+            if (sys.stale(attached(k)) || ng != 0) continue;
+            if (k != VSITES) {
+                sys.check_state(sys.groups[k]);
+                sys.velocities(sys.groups[k]);
+            } else {
+                sys.check_vsites(sys.tables->vsites);
+                sys.place_sites(true);
+                sys.resort();
             }
-        }
-        // (a site table for the same count: checked against the new state, the sites placed on their parents with zero velocity,
-        // and the list rebuilt for where they now are)
-        if (!lent && sys.has_vsites() && !sys.vsites_stale() && ng == 0) {
-            sys.check_vsites(sys.tables->vsites);
-            sys.place_sites(true);
-            sys.resort();
-            vs_unchecked = false;
+            unchecked[k] = false;
         }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
         // cleared -- NbSystem::ensure_charges)
@@ -220,12 +216,40 @@ struct MdImpl : IMd {
     }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
-    // per constraint group (NbSystem::groups): its table has not passed the check against the loaded state (another atom count,
-    // ghosts, or a refusal)
-    bool unchecked[NbSystem<real>::GROUPS] = {false, false};
-    // ... and the same for the table of virtual sites (emdee_md_set_vsites)
-    bool vs_unchecked = false;
-    bool sites_in_use() const { return !lent && n_ghost == 0 && sys.vsites_fit() && !vs_unchecked; }
+    // The attached tables: one per constraint group (NbSystem::groups, same index), then the table of virtual sites
+    // (emdee_md_set_vsites).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
+    // texts; what is done with one stays per kind.
+    enum { VSITES = NbSystem<real>::GROUPS, TABLES };
+    const Topology::GroupTable &attached(int k) const { return k == VSITES ? sys.tables->vsites : sys.table(sys.groups[k]); }
+    // what the texts of this file call the entries of table k, and the call that sets it
+    struct GroupText { const char *one, *many, *setter; };
+    static constexpr GroupText GROUP_TEXT[TABLES] = {{"a rigid molecule", "rigid molecules", "emdee_md_set_rigid3"},
+                                                     {"an hbonds cluster", "hbonds clusters", "emdee_md_set_hbonds"},
+                                                     {"a virtual site", "virtual sites", "emdee_md_set_vsites"}};
+    // table k has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
+    bool unchecked[TABLES] = {false, false, false};
+    // the conditions emdee_md_step refuses table k on
+    void require_fitting(const char *what, int k) const {
+        const Topology::GroupTable &t = attached(k);
+        EMDEE_REQUIRE(!t.present || !(sys.stale(t) || unchecked[k]), EMDEE_ERR_STATE, "%s: %s set for %lld atoms, the state "
+                      "holds %d (or does not fit them): set them again or clear them (%s)", what, GROUP_TEXT[k].many,
+                      (long long)t.limit, sys.n_owned, GROUP_TEXT[k].setter);
+    }
+    // what emdee_md_step and emdee_md_minimize refuse alike: a fault reported before and not yet answered by new tables or a new
+    // state, and a table that does not fit the state
+    void require_ready(const char *what) const {
+        const struct { const FaultWord &fault; const char *text; } reported[] = {
+            {sys.bonded_fault, "a bonded term has lost a partner; replace the tables or the state"},
+            {sys.ewald_fault, "an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state"},
+            {sys.image_fault, "an atom has travelled more than 511 box lengths from the box (reported before); replace the state"}};
+        for (const auto &r : reported) EMDEE_REQUIRE(!r.fault.latched, EMDEE_ERR_STATE, "%s: %s", what, r.text);
+        for (int k = 0; k < TABLES; k++) {
+            if (k != VSITES)
+                EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "%s: %s had no solution; replace the table or the state", what, GROUP_TEXT[k].one);
+            require_fitting(what, k);
+        }
+    }
+    bool sites_in_use() const { return !lent && n_ghost == 0 && sys.vsites_fit() && !unchecked[VSITES]; }
     // A force pass into the engine's own arrays.  With a site table in force, a pass that writes the force planes is followed by the
     // spreading of the sites' forces to their parents (vsite.hpp), once; a pass that leaves the planes alone (energies and virials
     // only, the tensor pass, the interior half of a decomposed step) is not.
@@ -234,11 +258,6 @@ struct MdImpl : IMd {
         if ((p.mask & EMDEE_FORCES) && p.phase != 1 && sites_in_use()) sys.spread_sites();
     }
     void force_pass(int bitmask) { force_pass(Pass<real>::force(bitmask)); }
-    void require_fitting_sites(const char *what) const {
-        EMDEE_REQUIRE(!sys.has_vsites() || !(sys.vsites_stale() || vs_unchecked), EMDEE_ERR_STATE, "%s: virtual sites set for %lld atoms, the state "
-                      "holds %d (or does not fit them): set them again or clear them (emdee_md_set_vsites)", what,
-                      (long long)sys.tables->vsites.limit, sys.n_owned);
-    }
     // an engine of a decomposition (emdee_dd_engine): its pair tables are the decomposition's, keyed by global id
     bool lent = false;
     // decomposed domains: the global ids of the atoms handed to set_state (caller order, owned atoms and ghosts); they travel
@@ -265,14 +284,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
         EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "md_step needs n_ghost == 0; decomposed runs drive kick_drift/forces/kick");
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
-        EMDEE_REQUIRE(!sys.bonded_fault.latched, EMDEE_ERR_STATE, "md_step: a bonded term has lost a partner; replace the tables or the state");
-        EMDEE_REQUIRE(!sys.ewald_fault.latched, EMDEE_ERR_STATE, "md_step: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
-        EMDEE_REQUIRE(!sys.image_fault.latched, EMDEE_ERR_STATE, "md_step: an atom has travelled more than 511 box lengths from the box (reported before); replace the state");
-        for (int k = 0; k < sys.GROUPS; k++) {
-            EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_step: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
-            require_fitting_table("md_step", k);
-        }
-        require_fitting_sites("md_step");
+        require_ready("md_step");
         if (nsteps == 0) return;
         if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || baro.kind != EMDEE_BAROSTAT_OFF) { step_closed(nsteps, dt, rebuild_every); return; }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
@@ -339,17 +351,6 @@ struct MdImpl : IMd {
                       "and the engine holds rigid molecules: switch the coupling off (emdee_md_set_barostat) or clear the table (emdee_md_set_rigid3) first");
         molecular = on == 1;
     }
-    // what the texts of this file call the groups of NbSystem::groups[k], and the entry that sets their table
-    struct GroupText { const char *one, *many, *setter; };
-    static constexpr GroupText GROUP_TEXT[NbSystem<real>::GROUPS] = {{"a rigid molecule", "rigid molecules", "emdee_md_set_rigid3"},
-                                                                     {"an hbonds cluster", "hbonds clusters", "emdee_md_set_hbonds"}};
-    // the conditions emdee_md_step refuses the table of group k on
-    void require_fitting_table(const char *what, int k) const {
-        const auto &g = sys.groups[k];
-        EMDEE_REQUIRE(!sys.table(g).present || !(sys.stale(g) || unchecked[k]), EMDEE_ERR_STATE, "%s: %s set for %lld atoms, the state "
-                      "holds %d (or does not fit them): set them again or clear them (%s)", what, GROUP_TEXT[k].many,
-                      (long long)sys.table(g).limit, sys.n_owned, GROUP_TEXT[k].setter);
-    }
     void scale_box(const double mu[3], double vscale) override {
         use_device(sys.ctx);
         require_undivided("scale_box");
@@ -358,8 +359,8 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!sys.has_rigid() || molecular, EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
                       "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
-        require_fitting_table("scale_box", sys.RIGID);      // (an hbonds table was refused above)
-        require_fitting_sites("scale_box");
+        require_fitting("scale_box", sys.RIGID);            // (an hbonds table was refused above)
+        require_fitting("scale_box", VSITES);
         sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes; sites go back on their scaled parents)
         since_build = 0;
         current_mask = 0;
@@ -403,12 +404,12 @@ struct MdImpl : IMd {
         baro.seed = seed; baro.step = first_step;
         for (int d = 0; d < 3; d++) { baro.p_ref[d] = p_ref[d]; baro.beta[d] = beta[d]; }
     }
-    // emdee_md_step with coupling on, with rigid molecules (emdee_md_set_rigid3) or with an hbonds table (emdee_md_set_hbonds).  Every
-    // step closes its own half kick (kick + drift, force pass, kick): the state after s steps then does not depend on how the s
-    // steps were dealt to calls -- step(40), 8 x step(5) and 40 x step(1) are the same sequence of launches, bit for bit -- and no
-    // step is ever queued beyond an event on the box the event is about to change.  (The merged kicks and the guarded run-ahead
-    // of the uncoupled loop would have to end at every call as well as at every event, and v + h + h is not v + 2 h in floating
-    // point.)
+    // One closed step: the one place the sequence of stages lives, for emdee_md_step with a table or a barostat (step_closed) and
+    // for emdee_md_minimize.  It closes its own half kick (kick + drift, force pass, kick): the state after s steps then does not
+    // depend on how the s steps were dealt to calls -- step(40), 8 x step(5) and 40 x step(1) are the same sequence of launches,
+    // bit for bit -- and no step is ever queued beyond an event on the box the event is about to change.  (The merged kicks and
+    // the guarded run-ahead of the uncoupled loop would have to end at every call as well as at every event, and v + h + h is
+    // not v + 2 h in floating point.)
     // Around the unchanged kernels, the three constraint stages of every table that exists (NbSystem::groups: SETTLE / RATTLE on
     // the molecules, then M-SHAKE / RATTLE on the clusters, whose atoms are disjoint): (a) the constrained atoms' positions are
     // remembered, (c) the distances are restored on the drifted records, (e) the bond components of the relative velocities are
@@ -416,40 +417,49 @@ struct MdImpl : IMd {
     // between (c) and (e) is harmless (the stages find atoms through inv_perm).
     // Virtual sites (emdee_md_set_vsites) add two stages: (c') the sites are put back on their parents after stage (c) of every table
     // (they raise the same displacement word), (d') their forces are spread to the parents between the force pass and the kick.
-    // The order of a step: (a) gather, (b) kick + drift, (c) positions, [re-sort], (d) force pass and kick, (e) velocities; with
-    // pressure coupling on, after the step that completes an interval, (f) the event.  Without a table the event's step evaluates
-    // the energies and virials with its forces when the coupling is isotropic: no pass is added for the pressure.  With rigid
-    // molecules (emdee_md_set_molecular_scaling) the event takes the molecular pressure from that step's forces F(x) and its
-    // stage-(e) velocities (one tensor pass), then the molecular scale, which rebuilds the list and evaluates the forces on the
-    // new box; a fixed rebuild cadence restarts from the event.
+    // The order: (a) gather, (b) kick + drift, (c) positions, (c') place sites, [re-sort], (d) force pass, (d') spread, kick,
+    // (e) velocities.  mask: the outputs of the force pass; rebuild_every: the cadence of the re-sort, 0 for the displacement
+    // word.  Returns whether it re-sorted.
+    bool closed_step(double dt, int mask, int rebuild_every) {
+        sys.for_each_table([&](auto &g) { sys.gather(g); });
+        sys.kick_drift(0.5 * dt, dt);
+        current_mask = 0;                                    // (as in step(): until the force pass of this step)
+        sys.for_each_table([&](auto &g) { sys.positions(g, dt); });
+        if (sites_in_use()) sys.place_sites(false);          // (c'): after every constraint table's stage (c), before the word is read
+        since_build++;
+        const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
+        if (rb) { sys.resort(); since_build = 0; }
+        force_pass(mask);                                    // ((d'): the sites' forces go to their parents before the closing kick)
+        sys.kick(0.5 * dt);
+        sys.for_each_table([&](auto &g) { sys.velocities(g); });
+        current_mask = mask;
+        return rb;
+    }
+    // what a call that ran closed steps ends with: the faults its kernels may have raised
+    void check_closed_steps() {
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
+        for (auto &g : sys.groups) sys.check(g);             // (one read-back per call and table)
+    }
+    // emdee_md_step with coupling on, with rigid molecules (emdee_md_set_rigid3), an hbonds table (emdee_md_set_hbonds) or virtual
+    // sites: closed steps and, with pressure coupling on, after the step that completes an interval, (f) the event.  Without a
+    // table the event's step evaluates the energies and virials with its forces when the coupling is isotropic: no pass is added
+    // for the pressure.  With rigid molecules (emdee_md_set_molecular_scaling) the event takes the molecular pressure from that
+    // step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale, which rebuilds the list and
+    // evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.
     void step_closed(int nsteps, double dt, int rebuild_every) {
         const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF, rigid = sys.has_rigid(), hbonds = sys.has_hbonds();
         EMDEE_REQUIRE(!coupled || !(rigid || hbonds) || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
         EMDEE_REQUIRE(!coupled || !hbonds, EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
         const bool with_sums = !rigid && !hbonds && baro.coupling == EMDEE_COUPLE_ISOTROPIC;
-        const bool sites = sites_in_use();
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
-            for (auto &g : sys.groups) if (sys.table(g).present) sys.gather(g);
-            sys.kick_drift(0.5 * dt, dt);
-            current_mask = 0;                                // (as in step(): until the force pass of this step)
-            for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, dt);
-            if (sites) sys.place_sites(false);               // (c'): after every constraint table's stage (c), before the word is read
-            since_build++;
-            const bool rb = rebuild_every > 0 ? since_build >= rebuild_every : sys.read_rebuild_flag();
-            if (rb) { sys.resort(); since_build = 0; }
-            const int mask = (event && with_sums) ? 7 : EMDEE_FORCES;
-            force_pass(mask);                                // ((d'): the sites' forces go to their parents before the closing kick)
-            sys.kick(0.5 * dt);
-            for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
-            current_mask = mask;
+            closed_step(dt, (event && with_sums) ? 7 : EMDEE_FORCES, rebuild_every);
             if (coupled) baro.step++;
             if (event) couple(dt);
         }
-        EMDEE_HIP_CHECK(hipGetLastError());
-        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
-        for (auto &g : sys.groups) sys.check(g);             // (one read-back per call and table)
+        check_closed_steps();
     }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
@@ -506,7 +516,7 @@ struct MdImpl : IMd {
             throw Failure{EMDEE_ERR_STATE};
         }
     }
-    // emdee_md_minimize (include/emdee_hip.h): FIRE around the stages of step_closed.  Iteration 0 is the evaluation at
+    // emdee_md_minimize (include/emdee_hip.h): FIRE around closed_step.  Iteration 0 is the evaluation at
     // the entry positions (force pass unless forces and energies are current, G, the reduction, the stop test); every later one is a
     // closed step with the capped time step, then G, the reduction, the stop test and the update of minimize.hpp.  The thermostat
     // is left out of the kick + drift for the length of the call and comes back as it was; the box never changes.
@@ -519,14 +529,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(std::isfinite(max_step) && max_step > 0.0, EMDEE_ERR_INVALID, "md_minimize: max_step must be finite and > 0");
         require_undivided("md_minimize");
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md_minimize: no state loaded (call emdee_md_set_state first)");
-        EMDEE_REQUIRE(!sys.bonded_fault.latched, EMDEE_ERR_STATE, "md_minimize: a bonded term has lost a partner; replace the tables or the state");
-        EMDEE_REQUIRE(!sys.ewald_fault.latched, EMDEE_ERR_STATE, "md_minimize: an excluded or 1-4 pair of an Ewald engine spans more than rc + skin; replace the tables or the state");
-        EMDEE_REQUIRE(!sys.image_fault.latched, EMDEE_ERR_STATE, "md_minimize: an atom has travelled more than 511 box lengths from the box (reported before); replace the state");
-        for (int k = 0; k < sys.GROUPS; k++) {
-            EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "md_minimize: %s had no solution; replace the table or the state", GROUP_TEXT[k].one);
-            require_fitting_table("md_minimize", k);
-        }
-        require_fitting_sites("md_minimize");
+        require_ready("md_minimize");
         sys.ensure_charges();                                // (charges set for another atom count: refused, as a step is)
         struct Unthermostatted {                             // (kick_drift applies the thermostat that is on, and counts its steps)
             NbSystem<real> &s;
@@ -535,7 +538,6 @@ struct MdImpl : IMd {
             ~Unthermostatted() { s.lgv_on = on; }
         } unthermostatted(sys);
         const int mask = EMDEE_FORCES | EMDEE_ENERGIES;
-        const bool tables = sys.has_rigid() || sys.has_hbonds(), sites = sites_in_use();
         emdee_minimize_result res{};
         FireState fire = fire_start(dt_start, dt_max);
         double r[FIRE_WORDS + 1];
@@ -552,16 +554,7 @@ struct MdImpl : IMd {
             if (res.g_max <= f_tol && std::isfinite(r[2])) { res.converged = 1; break; }
             if (res.iterations >= max_iter) break;
             const double t = fire_cap(fire.dt, vmax, std::sqrt(r[5]), max_step);
-            for (auto &g : sys.groups) if (sys.table(g).present) sys.gather(g);
-            sys.kick_drift(0.5 * t, t);
-            for (auto &g : sys.groups) if (sys.table(g).present) sys.positions(g, t);
-            if (sites) sys.place_sites(false);
-            since_build++;
-            if (sys.read_rebuild_flag()) { sys.resort(); since_build = 0; res.rebuilds++; }
-            force_pass(mask);                                // (the sites' forces are their parents': G of a site is 0)
-            sys.kick(0.5 * t);
-            for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
-            current_mask = mask;
+            if (closed_step(t, mask, 0)) res.rebuilds++;     // (the sites' forces are their parents': G of a site is 0)
             res.iterations++;
             G = sys.constrained_force();
             sys.fire_sums(G, r);
@@ -571,7 +564,7 @@ struct MdImpl : IMd {
                 // v <- (1 - alpha) v + alpha |v| G / |G|, tangent again through stage (e); no speed now exceeds the bound below
                 const double c_g = alpha * std::sqrt(r[1] / r[2]);
                 sys.fire_mix(G, 1.0 - alpha, c_g);
-                if (tables) for (auto &g : sys.groups) if (sys.table(g).present) sys.velocities(g);
+                sys.for_each_table([&](auto &g) { sys.velocities(g); });
                 vmax = (1.0 - alpha) * std::sqrt(r[4]) + c_g * std::sqrt(r[3]);
             } else {
                 sys.zero_velocities();
@@ -580,9 +573,7 @@ struct MdImpl : IMd {
         }
         sys.zero_velocities();
         res.dt = fire.dt;
-        EMDEE_HIP_CHECK(hipGetLastError());
-        sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
-        for (auto &g : sys.groups) sys.check(g);             // (one read-back per call and table)
+        check_closed_steps();
         if (out) *out = res;
     }
     void kick_drift(double dt, double kick) override {
@@ -678,7 +669,7 @@ struct MdImpl : IMd {
                       "molecular sums are written for three-site molecules and would keep the clusters' constraint forces; clear the table first");
         if (!sys.has_rigid()) { pressure_tensor(out); return; }
         EMDEE_REQUIRE(!lent && n_ghost == 0, EMDEE_ERR_STATE, "molecular_pressure_tensor: rigid molecules on an integrator with ghosts or a domain's");
-        require_fitting_table("molecular_pressure_tensor", sys.RIGID);   // (an hbonds table was refused above)
+        require_fitting("molecular_pressure_tensor", sys.RIGID);   // (an hbonds table was refused above)
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         tensor_pass();
         sys.check_bonded();
@@ -799,7 +790,7 @@ struct MdImpl : IMd {
     void set_vsites(const int32_t *atoms, const double *weights, int32_t n_sites) override {
         install("virtual sites", "a decomposed run has none", [&] {
             sys.own_tables.set_vsites(atoms, weights, n_sites, sys.n_owned, sys.stream(), [&](const Topology::VsiteTable &t) { sys.check_vsites(t); });
-            vs_unchecked = false;
+            unchecked[VSITES] = false;
             if (sys.vsites_fit()) sys.place_sites(true);
         });
     }

@@ -1,5 +1,5 @@
 // minimize.hpp -- energy minimisation on the device (emdee_md_minimize): FIRE (Bitzek, Koskinen, Gaehler, Moseler & Gumbsch,
-// Phys. Rev. Lett. 97, 170201 (2006)) around the closed velocity-Verlet step of MdImpl::step_closed, with the engine's masses and
+// Phys. Rev. Lett. 97, 170201 (2006)) around the closed velocity-Verlet step of MdImpl::closed_step, with the engine's masses and
 // whatever constraint tables are in force.  The two update rules at the top are plain C++ on doubles, as the tops of settle.hpp
 // and shake.hpp are: a stand-alone host program tests them with the host compiler (tests/c/fire_host.cpp); the kernels below them
 // need HIP.  DESIGN.md 4d has the algorithm; MdImpl::minimize (impl.hpp) drives it.

@@ -929,15 +929,36 @@ struct NbSystem {
     // the state are replaced
     FaultWord bonded_fault{W_BONDED};
     void reset_bonded_error() { bonded_fault.reset(flags.ptr, stream()); }
+    // The shape of check_bonded, check_ewald and check(g).  Blocking, one read-back unless the fault is latched already:
+    // EMDEE_ERR_STATE with message(entry) if the word has been raised since the last reset, with `reported_before` from then on.
+    template <class Message>
+    void throw_on_fault(FaultWord &fault, Message &&message, const char *reported_before) {
+        if (const int32_t word = fault.poll(ctx, flags.ptr, stream())) {
+            set_error("%s", message((int64_t)word - 1).c_str());
+            throw Failure{EMDEE_ERR_STATE};
+        }
+        EMDEE_REQUIRE(!fault.latched, EMDEE_ERR_STATE, "%s", reported_before);
+    }
+    // The shape of check_state and check_vsites.  The n <= 2 words from flags[first] on are cleared, launch(words) queues the
+    // kernel that raises them, one read-back: EMDEE_ERR_STATE with message(w, entry) for the first word w that names an entry.
+    template <class Launch, class Message>
+    void throw_on_check_words(int first, int n, Launch &&launch, Message &&message) {
+        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + first, 0, n * sizeof(int), stream()));
+        launch(flags.ptr + first);
+        int32_t words[2] = {0, 0};
+        read_back_words(ctx, stream(), flags.ptr + first, n, words);
+        for (int w = 0; w < n; w++)
+            if (words[w] != 0) {
+                set_error("%s", message(w, (int64_t)words[w] - 1).c_str());
+                throw Failure{EMDEE_ERR_STATE};
+            }
+    }
     // blocking: EMDEE_ERR_STATE naming the term if k_bonded has met a missing partner since the last reset
     void check_bonded() {
         check_ewald();                                       // (the other term that needs a partner in the rows)
         if (!has_bonded() || !flags.ptr) return;
-        if (const int32_t word = bonded_fault.poll(ctx, flags.ptr, stream())) {
-            set_error("%s", topo::lost_partner_message(tables->b_atoms, (int64_t)word - 1).c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
-        EMDEE_REQUIRE(!bonded_fault.latched, EMDEE_ERR_STATE, "a bonded term has lost a partner (reported before): replace the tables or the state");
+        throw_on_fault(bonded_fault, [&](int64_t term) { return topo::lost_partner_message(tables->b_atoms, term); },
+                       "a bonded term has lost a partner (reported before): replace the tables or the state");
     }
     // emdee_nbr_* / emdee_md_set_exclusions, _set_pairs14: replaces one of the engine's own tables (n = 0 clears it), all or nothing
     void set_pair_tables(int n_atoms, const int32_t *pairs_dev, int n_pairs, bool one_four, double scale) {
@@ -1063,11 +1084,8 @@ struct NbSystem {
     // blocking: EMDEE_ERR_STATE naming the pair if k_ewald_struck has met a missing partner since the last reset
     void check_ewald() {
         if (!has_ewald() || !has_excl() || !flags.ptr) return;
-        if (const int32_t word = ewald_fault.poll(ctx, flags.ptr, stream())) {
-            set_error("%s", topo::lost_pair_message(tables->excl, tables->p14, (int64_t)word - 1).c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
-        EMDEE_REQUIRE(!ewald_fault.latched, EMDEE_ERR_STATE, "Ewald: an excluded or 1-4 pair spans more than rc + skin (reported before): replace the tables or the state");
+        throw_on_fault(ewald_fault, [&](int64_t pair) { return topo::lost_pair_message(tables->excl, tables->p14, pair); },
+                       "Ewald: an excluded or 1-4 pair spans more than rc + skin (reported before): replace the tables or the state");
     }
     void add_ewald(const Pass<real> &p) {
         if (!has_ewald() || n_total == 0) return;
@@ -1086,7 +1104,7 @@ struct NbSystem {
         ewald.run(stream(), n_total, pitch, view(), lo, len, qp.ptr, tables->q_sum, tables->q_abs, p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
     }
     // ---------------------------------------------------------------- constraint groups (Topology::set_rigid3, set_hbonds)
-    // The three stages MdImpl::step_closed puts around the unchanged kick + drift, force pass and kick, and the check of a table
+    // The three stages MdImpl::closed_step puts around the unchanged kick + drift, force pass and kick, and the check of a table
     // against a loaded state: one thread per group, no atomics on the state, fp64 on unwrapped differences in both precisions.
     // Undivided engines only.  One ConstraintGroup per table says what differs -- the table, the policy's kernels (settle.hpp
     // Triangle: SETTLE / RATTLE on rigid three-site molecules; shake.hpp Star: M-SHAKE / RATTLE on bonds to hydrogen), the timer,
@@ -1131,17 +1149,16 @@ struct NbSystem {
     const Topology::GroupTable &table(const ConstraintGroup &g) const { return tables->*g.table; }
     bool has_rigid() const { return tables->rigid.present; }
     bool has_hbonds() const { return tables->hbonds.present; }
-    // an engine whose state no longer has the atom count the table was set for: it refuses to step (as with charges)
-    bool stale(const ConstraintGroup &g) const { return table(g).present && (table(g).limit != n_owned || id_gaps); }
+    template <class F>
+    void for_each_table(F &&f) { for (auto &g : groups) if (table(g).present) f(g); }   // (every table that exists, in the order of groups[])
+    // an engine whose state no longer has the atom count an attached table -- a constraint table or the site table -- was set for:
+    // it refuses to step (as with charges)
+    bool stale(const Topology::GroupTable &t) const { return t.present && (t.limit != n_owned || id_gaps); }
     void reset_error(ConstraintGroup &g) { g.fault.reset(flags.ptr, stream()); }
     // blocking, one read-back: EMDEE_ERR_STATE naming the group if stage (c) has met one without a solution since the last reset
     void check(ConstraintGroup &g) {
         if (!table(g).present || !flags.ptr) return;
-        if (const int32_t word = g.fault.poll(ctx, flags.ptr, stream())) {
-            set_error("%s", g.message(table(g).atoms_h, (int64_t)word - 1, g.no_solution).c_str());
-            throw Failure{EMDEE_ERR_STATE};
-        }
-        EMDEE_REQUIRE(!g.fault.latched, EMDEE_ERR_STATE, "%s", g.reported_before);
+        throw_on_fault(g.fault, [&](int64_t group) { return g.message(table(g).atoms_h, group, g.no_solution); }, g.reported_before);
     }
     ConstraintArgs<real> constraint_args(const int *atoms, const double *geom, int n) const {
         ConstraintArgs<real> a{};
@@ -1171,26 +1188,19 @@ struct NbSystem {
     // a table (in force, or a candidate not yet committed) against the loaded state: EMDEE_ERR_STATE naming the group that fails
     // the policy's test (settle.hpp Triangle::check, shake.hpp Star::check); one launch, one read-back
     void check_state(ConstraintGroup &g, const int *atoms, const double *geom, const std::vector<int32_t> &atoms_h, int n) {
-        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + g.check_word, 0, g.check_words * sizeof(int), stream()));
-        hipLaunchKernelGGL(g.k_check, dim3(blocks_for(n, 256)), dim3(256), 0, stream(), constraint_args(atoms, geom, n), flags.ptr + g.check_word);
-        int32_t words[2] = {0, 0};
-        read_back_words(ctx, stream(), flags.ptr + g.check_word, g.check_words, words);
-        for (int w = 0; w < g.check_words; w++)
-            if (words[w] != 0) {
-                set_error("%s", g.message(atoms_h, (int64_t)words[w] - 1, g.check_text[w]).c_str());
-                throw Failure{EMDEE_ERR_STATE};
-            }
+        throw_on_check_words(g.check_word, g.check_words, [&](int *words) {
+            hipLaunchKernelGGL(g.k_check, dim3(blocks_for(n, 256)), dim3(256), 0, stream(), constraint_args(atoms, geom, n), words);
+        }, [&](int w, int64_t group) { return g.message(atoms_h, group, g.check_text[w]); });
     }
     void check_state(ConstraintGroup &g) { check_state(g, table(g).atoms.ptr, table(g).geom.ptr, table(g).atoms_h, table(g).n); }
 
     // ---------------------------------------------------------------- virtual interaction sites (Topology::set_vsites; vsite.hpp)
-    // Placement after whatever moves parents (MdImpl::step_closed stage (c'), minimize, scale_box, the set call, a reload) and
+    // Placement after whatever moves parents (MdImpl::closed_step stage (c'), scale_box, the set call, a reload) and
     // spreading after every force pass that writes the engine's own force planes (MdImpl::force_pass): one thread per site or per
     // distinct parent, fp64 sums in table order, no atomics.  Undivided engines only.
     bool has_vsites() const { return tables->vsites.present; }
-    bool vsites_stale() const { return has_vsites() && (tables->vsites.limit != n_owned || id_gaps); }
     // the table can be used on this state: it was set for this atom count and the state carries masses (a site's is 0)
-    bool vsites_fit() const { return has_vsites() && !vsites_stale() && with_mass && !has_ghosts && tables->vsites.n > 0; }
+    bool vsites_fit() const { return has_vsites() && !stale(tables->vsites) && with_mass && !has_ghosts && tables->vsites.n > 0; }
     VsiteArgs<real> vsite_args(const Topology::VsiteTable &t) const {
         VsiteArgs<real> a{};
         a.n = t.n; a.n_parents = t.n_parents; a.atoms = t.atoms.ptr; a.weights = t.geom.ptr;
@@ -1222,17 +1232,11 @@ struct NbSystem {
                                                                "inv_mass = 0: load the state with masses").c_str());
             throw Failure{EMDEE_ERR_STATE};
         }
-        EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr + W_VSITE_MASS, 0, 2 * sizeof(int), stream()));
-        hipLaunchKernelGGL((k_vsite_check<real>), dim3(blocks_for(t.n, 256)), dim3(256), 0, stream(), vsite_args(t), flags.ptr + W_VSITE_MASS);
-        int32_t words[2] = {0, 0};
-        read_back_words(ctx, stream(), flags.ptr + W_VSITE_MASS, 2, words);
         const char *const text[2] = {"the site has a mass (inv_mass != 0): a virtual site is loaded with inv_mass = 0",
                                      "a parent is massless (inv_mass == 0): a site is built on atoms with mass"};
-        for (int w = 0; w < 2; w++)
-            if (words[w] != 0) {
-                set_error("%s", topo::vsite_message(t.atoms_h, (int64_t)words[w] - 1, text[w]).c_str());
-                throw Failure{EMDEE_ERR_STATE};
-            }
+        throw_on_check_words(W_VSITE_MASS, 2, [&](int *words) {
+            hipLaunchKernelGGL((k_vsite_check<real>), dim3(blocks_for(t.n, 256)), dim3(256), 0, stream(), vsite_args(t), words);
+        }, [&](int w, int64_t site) { return topo::vsite_message(t.atoms_h, site, text[w]); });
     }
 
     void add_post_terms(const Pass<real> &p) {
@@ -1503,12 +1507,11 @@ struct NbSystem {
         const real *w = with_mass ? im.ptr : nullptr;
         hipLaunchKernelGGL((k_fire_weight<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, perm.ptr,
                            (const real *)frc.ptr, w, gplane.ptr, 0);
-        for (auto &g : groups) {
-            if (!table(g).present) continue;
+        for_each_table([&](ConstraintGroup &g) {
             ConstraintArgs<real> a = constraint_args(g);
             a.vel = gplane.ptr;
             hipLaunchKernelGGL(g.k_velocities, dim3(blocks_for(table(g).n, 256)), dim3(256), 0, stream(), a);
-        }
+        });
         hipLaunchKernelGGL((k_fire_weight<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, perm.ptr,
                            (const real *)frc.ptr, w, gplane.ptr, 1);
         return gplane.ptr;
@@ -1531,8 +1534,7 @@ struct NbSystem {
                                (const real *)frc.ptr, (const real *)vel.ptr, w, fire_partial.ptr);
             hipLaunchKernelGGL(k_fire_final, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)fire_partial.ptr, (const double *)sums.ptr, tot);
         }
-        EMDEE_HIP_CHECK(hipMemcpyAsync(out, tot, (FIRE_WORDS + 1) * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+        read_back_doubles(out, tot, FIRE_WORDS + 1);
     }
     void fire_mix(const real *g, double c_v, double c_g) {
         if (n_total == 0) return;
@@ -1542,6 +1544,11 @@ struct NbSystem {
     }
 
     // ---------------------------------------------------------------- observables
+    // blocking: n doubles of the device on the host, behind everything queued on the stream so far
+    void read_back_doubles(double *dst, const double *src, int n) {
+        EMDEE_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+    }
     // out[0] = sum e, out[1] = kinetic energy (velocities advanced by a pending c f/m), out[2] = sum w
     void energy_sums(double pending_c, double out[3]) {
         out[0] = out[1] = out[2] = 0.0;
@@ -1551,8 +1558,7 @@ struct NbSystem {
                            perm.ptr, en.ptr, vir.ptr, with_vel ? vel.ptr : nullptr, frc.ptr,
                            with_mass ? im.ptr : nullptr, (real)pending_c, partial.ptr);
         hipLaunchKernelGGL(k_final_sum3, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, partial.ptr, sums.ptr);
-        EMDEE_HIP_CHECK(hipMemcpyAsync(out, sums.ptr, 3 * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+        read_back_doubles(out, sums.ptr, 3);
     }
 
     // out[0..5] = sum of the owned atoms' virial tensors (the last tensor pass), out[6..11] = kinetic tensor sum m v^a v^b;
@@ -1571,9 +1577,7 @@ struct NbSystem {
     void tensor_sums(double out[TENSOR_SUMS]) {
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
         if (n_total == 0) return;
-        const double *tot = queue_tensor_sums();
-        EMDEE_HIP_CHECK(hipMemcpyAsync(out, tot, TENSOR_SUMS * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+        read_back_doubles(out, queue_tensor_sums(), TENSOR_SUMS);
     }
     // out[0..5] = W_mol, out[6..11] = K_mol (include/emdee_hip.h: emdee_md_molecular_pressure_tensor): the atomic sums above minus
     // what the atoms of the rigid molecules carry about their centres of mass (k_molecule_partials over the table, with the
@@ -1593,8 +1597,7 @@ struct NbSystem {
         }
         hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot + TENSOR_SUMS);
         double both[2 * TENSOR_SUMS];
-        EMDEE_HIP_CHECK(hipMemcpyAsync(both, tot, 2 * TENSOR_SUMS * sizeof(double), hipMemcpyDeviceToHost, stream()));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(stream()));
+        read_back_doubles(both, tot, 2 * TENSOR_SUMS);
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = both[q] - both[TENSOR_SUMS + q];
     }
     // caller-order copy of the last tensor pass's per-atom tensors (owned atoms, 6 x n_owned)
