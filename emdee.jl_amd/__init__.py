@@ -23,6 +23,7 @@ from .nonbonded import (ENERGIES, FORCES, VIRIALS, WAVESIZE, AllPairsTiles,     
 from .verlet import COULOMB_K_KJ_NM, HARMONIC_ANGLE, HARMONIC_BOND, PERIODIC_TORSION, VelocityVerlet  # noqa: E402
 from .verlet import (BAROSTAT_BERENDSEN, BAROSTAT_CRESCALE, BAROSTAT_OFF, COUPLE_ANISOTROPIC,     # noqa: E402
                      COUPLE_ISOTROPIC, COUPLE_SEMIISOTROPIC)
+from .verlet import THERMOSTAT_NOSE_HOOVER, THERMOSTAT_OFF, THERMOSTAT_VRESCALE                  # noqa: E402
 from . import synthetic                                                         # noqa: E402
 from . import domain                                                            # noqa: E402
 from . import ingest                                                            # noqa: E402
@@ -37,4 +38,4 @@ __all__ = ["LennardJonesModel", "LennardJonesAtom", "LJAtom", "lennard_jones_ato
            "EmDeeError", "LITERAL", "CUTOFF", "WAVESIZE", "domain", "ingest", "dd", "DomainDecomposition",
            "HARMONIC_BOND", "HARMONIC_ANGLE", "PERIODIC_TORSION", "COULOMB_K_KJ_NM",
            "BAROSTAT_OFF", "BAROSTAT_BERENDSEN", "BAROSTAT_CRESCALE", "COUPLE_ISOTROPIC", "COUPLE_SEMIISOTROPIC",
-           "COUPLE_ANISOTROPIC"]
+           "COUPLE_ANISOTROPIC", "THERMOSTAT_OFF", "THERMOSTAT_VRESCALE", "THERMOSTAT_NOSE_HOOVER"]

@@ -109,6 +109,10 @@ SIGNATURES = {
     "emdee_md_get_box": [_p, _d3, _d3],
     "emdee_md_scale_box": [_p, _d3, _dbl],
     "emdee_md_set_barostat": [_p, _i32, _i32, _d3, _d3, _dbl, _i32, _dbl, C.c_uint64, C.c_uint64],
+    "emdee_md_set_thermostat": [_p, _i32, _dbl, _dbl, _i32, _i64, _i32, C.c_uint64, C.c_uint64],
+    "emdee_md_thermostat_state": [_p, _d3],
+    "emdee_md_set_thermostat_state": [_p, _d3],
+    "emdee_md_thermostat_draws": [_p, C.c_uint64, C.c_uint64, _i64, _d3],
     "emdee_dd_unique_id": [_p],
     "emdee_dd_rccl_selftest": [_p, _i32],
     "emdee_dd_describe": [_d3, _i3, _dbl, _i32, C.POINTER(_i32), _p, _p, _p, C.POINTER(_i32), _p, _d3, _d3, _i3],

@@ -477,6 +477,19 @@ int32_t emdee_md_set_barostat(emdee_md *md, int32_t kind, int32_t coupling, cons
         md->impl->set_barostat(kind, coupling, p_ref, compressibility, tau_p, every, temperature, seed, first_step);
     });
 }
+int32_t emdee_md_set_thermostat(emdee_md *md, int32_t kind, double temperature, double tau_t, int32_t every, int64_t n_dof,
+                                int32_t chain, uint64_t seed, uint64_t first_step) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_thermostat(kind, temperature, tau_t, every, n_dof, chain, seed, first_step); });
+}
+int32_t emdee_md_thermostat_state(emdee_md *md, double out[EMDEE_THERMOSTAT_WORDS]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "thermostat_state: out"); md->impl->thermostat_state(out); });
+}
+int32_t emdee_md_set_thermostat_state(emdee_md *md, const double in[EMDEE_THERMOSTAT_WORDS]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(in, "set_thermostat_state: in"); md->impl->set_thermostat_state(in); });
+}
+int32_t emdee_md_thermostat_draws(emdee_md *md, uint64_t seed, uint64_t step, int64_t n_dof, double out[2]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "thermostat_draws: out"); md->impl->thermostat_draws(seed, step, n_dof, out); });
+}
 
 // ---------------------------------------------------------------- domain decomposition
 int32_t emdee_dd_unique_id(uint8_t out[128]) {

@@ -66,6 +66,11 @@ struct IMd {
     virtual void scale_box(const double mu[3], double velocity_scale) = 0;
     virtual void set_barostat(int32_t kind, int32_t coupling, const double *p_ref, const double *compressibility, double tau_p,
                               int32_t every, double temperature, uint64_t seed, uint64_t first_step) = 0;
+    virtual void set_thermostat(int32_t kind, double temperature, double tau_t, int32_t every, int64_t n_dof, int32_t chain,
+                                uint64_t seed, uint64_t first_step) = 0;
+    virtual void thermostat_state(double *out) = 0;
+    virtual void set_thermostat_state(const double *in) = 0;
+    virtual void thermostat_draws(uint64_t seed, uint64_t step, int64_t n_dof, double *out) = 0;
 };
 
 // spatial domain decomposition (emdee_dd_*): the domains of the decomposition that live in this process

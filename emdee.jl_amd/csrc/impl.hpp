@@ -286,7 +286,10 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         require_ready("md_step");
         if (nsteps == 0) return;
-        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || baro.kind != EMDEE_BAROSTAT_OFF) { step_closed(nsteps, dt, rebuild_every); return; }
+        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || baro.kind != EMDEE_BAROSTAT_OFF || thermo.kind != EMDEE_THERMOSTAT_OFF) {
+            step_closed(nsteps, dt, rebuild_every);
+            return;
+        }
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         // x_1 = x_0 + dt (v_0 + dt/2 f_0); then every inner step is ONE kernel (force + full kick + drift:
         // the closing half kick of step s rides on the opening half kick of step s+1); the last step ends
@@ -447,19 +450,95 @@ struct MdImpl : IMd {
     // for the pressure.  With rigid molecules (emdee_md_set_molecular_scaling) the event takes the molecular pressure from that
     // step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale, which rebuilds the list and
     // evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.
+    // A global thermostat (emdee_md_set_thermostat) sends the call here as well: after the step that completes one of its
+    // intervals, (e') K, the scalar update and v <- alpha v, before (f).  It lives here and not in closed_step, so that
+    // emdee_md_minimize runs without it.
     void step_closed(int nsteps, double dt, int rebuild_every) {
         const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF, rigid = sys.has_rigid(), hbonds = sys.has_hbonds();
         EMDEE_REQUIRE(!coupled || !(rigid || hbonds) || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
         EMDEE_REQUIRE(!coupled || !hbonds, EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
         const bool with_sums = !rigid && !hbonds && baro.coupling == EMDEE_COUPLE_ISOTROPIC;
+        const bool thermostatted = thermo.kind != EMDEE_THERMOSTAT_OFF;
+        const long long n_dof = thermostatted ? degrees_of_freedom() : 0;
+        EMDEE_REQUIRE(!thermostatted || n_dof >= 3, EMDEE_ERR_STATE, "md_step: the thermostat (emdee_md_set_thermostat) finds %lld degrees of "
+                      "freedom in the state and its tables; it needs at least 3", n_dof);
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
             closed_step(dt, (event && with_sums) ? 7 : EMDEE_FORCES, rebuild_every);
+            if (thermostatted && ++thermo.step % (unsigned long long)thermo.every == 0) thermostat_event(dt, n_dof);
             if (coupled) baro.step++;
             if (event) couple(dt);
         }
         check_closed_steps();
+    }
+    // ---- global thermostats (include/emdee_hip.h: emdee_md_set_thermostat; thermostat.hpp)
+    struct Thermostat {
+        int kind = EMDEE_THERMOSTAT_OFF, every = 1, chain = 3;
+        double temperature = 0.0, tau_t = 1.0;
+        long long n_dof = 0;                                 // 0: the library's own count
+        unsigned long long seed = 0, step = 0;               // step: how many steps have been taken, counted from first_step
+    } thermo;
+    // the count a thermostat works with: the one given, or 3 (n_owned - n_sites) - 3 n_rigid - n_satellites - 3 from the tables in force
+    long long degrees_of_freedom() const {
+        if (thermo.n_dof > 0) return thermo.n_dof;
+        const Topology &t = *sys.tables;
+        long long n = 3LL * ((long long)sys.n_owned - (t.vsites.present ? t.vsites.n : 0)) - 3;
+        if (t.rigid.present) n -= 3LL * t.rigid.n;
+        if (t.hbonds.present)
+            for (size_t k = 0; k < t.hbonds.atoms_h.size(); k++) n -= (k % 4 != 0 && t.hbonds.atoms_h[k] >= 0) ? 1 : 0;
+        return n;
+    }
+    // stage (e') of an event step: after stage (e) of the closed step, before the barostat's event (f).  One application over
+    // Delta = every dt; three launches on the engine's stream (NbSystem::thermostat_event), nothing read back.
+    void thermostat_event(double dt, long long n_dof) {
+        ThermostatParams p{};
+        p.kind = thermo.kind; p.chain = thermo.chain; p.kT = thermo.temperature; p.tau = thermo.tau_t;
+        p.Delta = (double)thermo.every * dt; p.n_dof = (double)n_dof; p.seed = thermo.seed; p.step = thermo.step;
+        sys.thermostat_event(p);
+    }
+    void set_thermostat(int32_t kind, double temperature, double tau_t, int32_t every, int64_t n_dof, int32_t chain, uint64_t seed,
+                        uint64_t first_step) override {
+        use_device(sys.ctx);
+        require_undivided("set_thermostat");
+        EMDEE_REQUIRE(kind >= EMDEE_THERMOSTAT_OFF && kind <= EMDEE_THERMOSTAT_NOSE_HOOVER, EMDEE_ERR_INVALID, "set_thermostat: unknown kind %d", kind);
+        if (kind == EMDEE_THERMOSTAT_OFF) { thermo.kind = EMDEE_THERMOSTAT_OFF; return; }
+        EMDEE_REQUIRE(std::isfinite(temperature) && temperature > 0.0, EMDEE_ERR_INVALID, "set_thermostat: temperature must be finite and > 0");
+        EMDEE_REQUIRE(std::isfinite(tau_t) && tau_t > 0.0, EMDEE_ERR_INVALID, "set_thermostat: tau_t must be finite and > 0");
+        EMDEE_REQUIRE(every >= 1, EMDEE_ERR_INVALID, "set_thermostat: every = %d must be >= 1", every);
+        EMDEE_REQUIRE(n_dof >= 0, EMDEE_ERR_INVALID, "set_thermostat: n_dof = %lld is negative (0: the library's own count)", (long long)n_dof);
+        EMDEE_REQUIRE(kind != EMDEE_THERMOSTAT_NOSE_HOOVER || (chain >= 1 && chain <= TH_CHAIN_MAX), EMDEE_ERR_INVALID,
+                      "set_thermostat: chain = %d is outside 1...%d", chain, TH_CHAIN_MAX);
+        EMDEE_REQUIRE(!sys.lgv_on, EMDEE_ERR_STATE, "set_thermostat: the Langevin thermostat is on (emdee_md_set_langevin with gamma > 0): switch it off first");
+        double *w = sys.thermostat_words();
+        EMDEE_HIP_CHECK(hipMemsetAsync(w, 0, TH_WORDS * sizeof(double), sys.stream()));
+        // ---- commit
+        thermo.kind = kind; thermo.every = every; thermo.chain = kind == EMDEE_THERMOSTAT_NOSE_HOOVER ? chain : 0;
+        thermo.temperature = temperature; thermo.tau_t = tau_t; thermo.n_dof = n_dof; thermo.seed = seed; thermo.step = first_step;
+    }
+    // blocking: the twenty words; word 0 is the count the next step would use while a thermostat is on and a state is loaded
+    void thermostat_state(double *out) override {
+        use_device(sys.ctx);
+        sys.read_back_doubles(out, sys.thermostat_words(), TH_WORDS);
+        if (thermo.kind != EMDEE_THERMOSTAT_OFF && (thermo.n_dof > 0 || sys.sorted)) out[TH_NDOF] = (double)degrees_of_freedom();
+    }
+    void set_thermostat_state(const double *in) override {
+        use_device(sys.ctx);
+        require_undivided("set_thermostat_state");
+        for (int k = TH_ETH; k < TH_WORDS; k++)
+            EMDEE_REQUIRE(std::isfinite(in[k]), EMDEE_ERR_INVALID, "set_thermostat_state: word %d is not finite", k);
+        double *w = sys.thermostat_words();
+        EMDEE_HIP_CHECK(hipMemcpyAsync(w + TH_ETH, in + TH_ETH, (TH_WORDS - TH_ETH) * sizeof(double), hipMemcpyHostToDevice, sys.stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));  // (the caller's array is its own again on return)
+    }
+    void thermostat_draws(uint64_t seed, uint64_t step, int64_t n_dof, double *out) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(n_dof >= 1, EMDEE_ERR_INVALID, "thermostat_draws: n_dof = %lld must be >= 1", (long long)n_dof);
+        double *part = sys.thermostat_words() + TH_WORDS;    // (scratch of the events, which the stream orders)
+        hipLaunchKernelGGL(k_thermostat_draws, dim3(1), dim3(64), 0, sys.stream(), (unsigned long long)seed, (unsigned long long)step,
+                           (long long)n_dof, part);
+        EMDEE_HIP_CHECK(hipGetLastError());
+        sys.read_back_doubles(out, part, 2);
     }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
@@ -701,12 +780,12 @@ struct MdImpl : IMd {
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
         // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
         // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps; 13: placement and
-        // force spreading of an engine with virtual sites
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 13, EMDEE_ERR_INVALID, "kernel id out of range");
+        // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 14, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[14][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[15][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -719,6 +798,8 @@ struct MdImpl : IMd {
         if (launches) *launches = n;
     }
     void set_langevin(double gamma, double temperature, uint64_t seed, uint64_t first_step) override {
+        EMDEE_REQUIRE(!(gamma > 0.0) || thermo.kind == EMDEE_THERMOSTAT_OFF, EMDEE_ERR_STATE, "set_langevin: a global thermostat is on "
+                      "(emdee_md_set_thermostat): switch it off first");
         sys.set_langevin(gamma, temperature, seed, first_step, sys.lgv_ids);
     }
     void set_langevin_ids(const int64_t *ids) override { sys.lgv_ids = reinterpret_cast<const long long *>(ids); }

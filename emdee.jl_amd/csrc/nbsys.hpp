@@ -15,6 +15,7 @@
 #include "plan.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
+#include "thermostat.hpp"
 #include "topology_dev.hpp"
 #include "typed.hpp"
 #include "vsite.hpp"
@@ -44,8 +45,9 @@ static inline void refuse_experiment_switches() {
 // T_HBONDS: the three constraint stages of an engine with an hbonds table (shake.hpp)
 // T_MINIMIZE: what emdee_md_minimize adds to the stages of a closed step (minimize.hpp): the constrained force, the reduction, the mixing
 // T_VSITE: placement and force spreading of an engine with virtual sites (vsite.hpp)
+// T_THERMOSTAT: the three launches of a global thermostat's event (thermostat.hpp)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_COUNT = 13 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_COUNT = 14 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -1541,6 +1543,34 @@ struct NbSystem {
         Timed t(this, T_MINIMIZE);
         hipLaunchKernelGGL((k_fire_mix<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch, perm.ptr,
                            vel.ptr, g, (real)c_v, (real)c_g);
+    }
+
+    // ---------------------------------------------------------------- global thermostats (thermostat.hpp; MdImpl::step_closed drives these)
+    // th_words[0..19]: the state words of emdee_md_thermostat_state, on the device; behind them the blocks' partial sums
+    DevBuf<double> th_words;
+    double *thermostat_words() {
+        if (th_words.ensure((size_t)TH_WORDS + RED_MAX_BLOCKS)) EMDEE_HIP_CHECK(hipMemsetAsync(th_words.ptr, 0, TH_WORDS * sizeof(double), stream()));
+        return th_words.ptr;
+    }
+    // stage (e') of an event: K, the scalar update, v <- alpha v; three launches on the stream, nothing read back
+    void thermostat_event(const ThermostatParams &p) {
+        if (n_total == 0) return;
+        double *w = thermostat_words(), *part = w + TH_WORDS;
+        const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+        {
+            Timed t(this, T_THERMOSTAT);
+            hipLaunchKernelGGL((k_kinetic_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                               (const real *)vel.ptr, with_mass ? (const real *)im.ptr : nullptr, part);
+        }
+        {
+            Timed t(this, T_THERMOSTAT);
+            hipLaunchKernelGGL(k_thermostat_update, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)part, p, w);
+        }
+        {
+            Timed t(this, T_THERMOSTAT);
+            hipLaunchKernelGGL((k_scale_velocities<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch,
+                               perm.ptr, vel.ptr, (const double *)w);
+        }
     }
 
     // ---------------------------------------------------------------- observables

@@ -2,6 +2,7 @@
 # (SURVEY.md 8a row a16).  API in EmDee's style: a constructor and `!` mutators.
 export VelocityVerlet, step!, energies, set_langevin!, set_langevin_ids!, virial_tensor!, pressure_tensor
 export box, scale_box!, set_barostat!
+export set_thermostat!, thermostat_state, set_thermostat_state!, thermostat_draws
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -155,6 +156,44 @@ set_barostat!(md::VelocityVerlet, kind, p_ref, compressibility, tau_p, every; co
                 Int32(kind), Int32(coupling), Float64[p_ref[1], p_ref[2], p_ref[3]],
                 Float64[compressibility[1], compressibility[2], compressibility[3]], Float64(tau_p), Int32(every),
                 Float64(temperature), UInt64(seed), UInt64(first_step)))
+
+# Global thermostats (include/emdee_hip.h; undivided boxes).
+# int32_t emdee_md_set_thermostat(emdee_md *md, int32_t kind, double temperature, double tau_t, int32_t every, int64_t n_dof,
+#                                 int32_t chain, uint64_t seed, uint64_t first_step);
+# kind: THERMOSTAT_OFF, THERMOSTAT_VRESCALE or THERMOSTAT_NOSE_HOOVER (chain: its length, 1...8); temperature: kT in energy units;
+# every: steps between events; n_dof: the degrees of freedom, 0 for the library's own count from the tables in force.
+const THERMOSTAT_OFF, THERMOSTAT_VRESCALE, THERMOSTAT_NOSE_HOOVER = Int32(0), Int32(1), Int32(2)
+const THERMOSTAT_WORDS = 20
+set_thermostat!(md::VelocityVerlet, kind, temperature=1.0, tau_t=1.0; every=1, n_dof=0, chain=3, seed=0, first_step=0) =
+    check(ccall((:emdee_md_set_thermostat, libemdee_hip), Int32,
+                (Ptr{Cvoid}, Int32, Float64, Float64, Int32, Int64, Int32, UInt64, UInt64), md.handle,
+                Int32(kind), Float64(temperature), Float64(tau_t), Int32(every), Int64(n_dof), Int32(chain), UInt64(seed),
+                UInt64(first_step)))
+
+# int32_t emdee_md_thermostat_state(emdee_md *md, double out[EMDEE_THERMOSTAT_WORDS]);
+# -> n_dof in use, K as the last event saw it, that event's alpha, E_th (U + K + E_th is conserved), xi (8), v_xi (8)
+function thermostat_state(md::VelocityVerlet)
+    w = zeros(Float64, THERMOSTAT_WORDS)
+    check(ccall((:emdee_md_thermostat_state, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, w))
+    return (n_dof=Int(w[1]), kinetic=w[2], alpha=w[3], energy=w[4], xi=w[5:12], v_xi=w[13:20])
+end
+
+# int32_t emdee_md_set_thermostat_state(emdee_md *md, const double in[EMDEE_THERMOSTAT_WORDS]);
+# writes energy, xi and v_xi of a thermostat_state; a restart is set_thermostat!(...; first_step = steps done), then this
+function set_thermostat_state!(md::VelocityVerlet, state)
+    w = vcat(zeros(Float64, 3), Float64(state.energy), Float64.(state.xi), Float64.(state.v_xi))
+    length(w) == THERMOSTAT_WORDS || throw(DimensionMismatch("xi and v_xi take 8 numbers each"))
+    check(ccall((:emdee_md_set_thermostat_state, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, w))
+end
+
+# int32_t emdee_md_thermostat_draws(emdee_md *md, uint64_t seed, uint64_t step, int64_t n_dof, double out[2]);
+# v-rescale's generator on its own: (R1, S) of the event that completes step `step`
+function thermostat_draws(md::VelocityVerlet, seed, step, n_dof)
+    out = zeros(Float64, 2)
+    check(ccall((:emdee_md_thermostat_draws, libemdee_hip), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Ptr{Float64}), md.handle,
+                UInt64(seed), UInt64(step), Int64(n_dof), out))
+    return (out[1], out[2])
+end
 
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);
 # Atom ids keying the thermostat's noise (device Int64 vector in caller order); `nothing` = the caller index.

@@ -21,6 +21,12 @@ COUPLE_ISOTROPIC, COUPLE_SEMIISOTROPIC, COUPLE_ANISOTROPIC = 0, 1, 2
 _COUPLINGS = {"isotropic": COUPLE_ISOTROPIC, "semiisotropic": COUPLE_SEMIISOTROPIC, "anisotropic": COUPLE_ANISOTROPIC}
 _BAROSTATS = {"off": BAROSTAT_OFF, "berendsen": BAROSTAT_BERENDSEN, "c-rescale": BAROSTAT_CRESCALE, "crescale": BAROSTAT_CRESCALE}
 
+# global thermostats (include/emdee_hip.h: emdee_md_set_thermostat)
+THERMOSTAT_OFF, THERMOSTAT_VRESCALE, THERMOSTAT_NOSE_HOOVER = 0, 1, 2
+THERMOSTAT_WORDS, THERMOSTAT_CHAIN_MAX = 20, 8
+_THERMOSTATS = {"off": THERMOSTAT_OFF, "v-rescale": THERMOSTAT_VRESCALE, "vrescale": THERMOSTAT_VRESCALE,
+                "nose-hoover": THERMOSTAT_NOSE_HOOVER, "nosehoover": THERMOSTAT_NOSE_HOOVER}
+
 
 def _three(v):
     """a scalar or three numbers as three floats"""
@@ -64,7 +70,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # what minimize_ adds to the stages of its steps: the constrained force, the reduction, the mixing
            "minimize": 12,
            # placement and force spreading of an engine with virtual sites (set_vsites_)
-           "vsites": 13}
+           "vsites": 13,
+           # the three launches of every event of a global thermostat (set_thermostat_)
+           "thermostat": 14}
 
 
 class MinimizeResult:
@@ -328,6 +336,43 @@ class VelocityVerlet:
                   (C.c_double * 3)(*_three(compressibility)), float(tau_p), int(every),
                   0.0 if temperature is None else float(temperature), int(seed) & (2 ** 64 - 1), int(first_step))
         self._coupled = k != BAROSTAT_OFF
+
+    # -- global thermostats (include/emdee_hip.h: emdee_md_set_thermostat; undivided boxes)
+    def set_thermostat_(self, kind, temperature=1.0, tau_t=1.0, every=1, n_dof=0, chain=3, seed=0, first_step=0):
+        """A global thermostat in every later step_: kind THERMOSTAT_VRESCALE / THERMOSTAT_NOSE_HOOVER (or "v-rescale" /
+        "nose-hoover"), THERMOSTAT_OFF (or None, "off") switches it off.  temperature: kT in energy units; tau_t: the relaxation
+        time; every: steps between events; n_dof: the degrees of freedom, 0 for the library's own count from the tables in force;
+        chain: the length of the Nose-Hoover chain (1...8); seed, first_step: v-rescale's noise and the numbering of the steps."""
+        if kind is None:
+            kind = THERMOSTAT_OFF
+        k = _THERMOSTATS[kind.lower().replace("_", "-")] if isinstance(kind, str) else int(kind)
+        _lib.call("emdee_md_set_thermostat", self._handle, k, float(temperature), float(tau_t), int(every), int(n_dof), int(chain),
+                  int(seed) & (2 ** 64 - 1), int(first_step))
+
+    def thermostat_state(self):
+        """The thermostat's state words as a dict (blocking): n_dof in use, kinetic (K as the last event saw it, before its
+        scaling), alpha (that event's factor), energy (E_th: U + K + E_th is the conserved quantity), xi and v_xi (8 each; unused
+        chain slots are 0)."""
+        w = (C.c_double * THERMOSTAT_WORDS)()
+        _lib.call("emdee_md_thermostat_state", self._handle, w)
+        w = list(w)
+        return dict(n_dof=int(w[0]), kinetic=w[1], alpha=w[2], energy=w[3], xi=w[4:12], v_xi=w[12:20])
+
+    def set_thermostat_state_(self, state):
+        """Writes energy, xi and v_xi of a dict from thermostat_state() (the words a restart carries over; the others are the
+        library's).  A restart: set_thermostat_(..., first_step=steps done), then this."""
+        xi, v_xi = [float(t) for t in state["xi"]], [float(t) for t in state["v_xi"]]
+        if len(xi) != THERMOSTAT_CHAIN_MAX or len(v_xi) != THERMOSTAT_CHAIN_MAX:
+            raise ValueError("set_thermostat_state_: xi and v_xi take %d numbers each" % THERMOSTAT_CHAIN_MAX)
+        w = [0.0, 0.0, 0.0, float(state["energy"])] + xi + v_xi
+        _lib.call("emdee_md_set_thermostat_state", self._handle, (C.c_double * THERMOSTAT_WORDS)(*w))
+
+    def thermostat_draws(self, seed, step, n_dof):
+        """v-rescale's generator on its own: (R1, S) of the event that completes step `step` -- R1 ~ N(0,1), S chi-squared with
+        n_dof - 1 degrees of freedom (blocking)."""
+        out = (C.c_double * 2)()
+        _lib.call("emdee_md_thermostat_draws", self._handle, int(seed) & (2 ** 64 - 1), int(step), int(n_dof), out)
+        return out[0], out[1]
 
     def set_molecular_scaling_(self, on=True):
         """Molecular scaling (include/emdee_hip.h emdee_md_set_molecular_scaling): with it on, an engine with rigid molecules

@@ -675,7 +675,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling);
  * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds); 12 = what emdee_md_minimize adds to the
  * stages of its steps (the constrained force, the reduction, the mixing); 13 = placement and force spreading of an engine with
- * virtual sites (emdee_md_set_vsites).  Blocking. */
+ * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat).
+ * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
 
@@ -755,6 +756,56 @@ int32_t emdee_md_scale_box(emdee_md *md, const double mu[3], double velocity_sca
 int32_t emdee_md_set_barostat(emdee_md *md, int32_t kind, int32_t coupling, const double p_ref[3],
                               const double compressibility[3], double tau_p, int32_t every, double temperature,
                               uint64_t seed, uint64_t first_step);
+
+/* Global thermostats (build-defined like the integrator: the reference has none).  Where the Langevin thermostat gives every
+ * atom friction and noise of its own, these reduce the kinetic energy K = sum m v^2 / 2 of the owned atoms, update a few scalars
+ * and multiply every velocity by one factor alpha, which leaves hydrodynamics alone and keeps the RATTLE conditions (linear and
+ * homogeneous in v): they compose with every table of the engine.
+ *
+ * emdee_md_set_thermostat switches one on for every later emdee_md_step of this integrator (kind = EMDEE_THERMOSTAT_OFF: off,
+ * the other arguments are then not looked at, and the engine behaves as if the call had never been made, bit for bit).
+ *   temperature: kT in energy units, as emdee_md_set_langevin takes it; tau_t: the relaxation time; every >= 1: the steps between
+ *   events; chain: the chain length M in 1...8 (kind NOSE_HOOVER only); seed, first_step: v-rescale's noise and the numbering of
+ *   the steps, as for the barostat; n_dof > 0: the degrees of freedom, taken as given; n_dof == 0: the library's own count,
+ *   evaluated at every emdee_md_step from the tables then in force,
+ *     3 (n_owned - n_sites) - 3 n_rigid_molecules - (satellites of the hbonds table) - 3,
+ *   which must be at least 3 (else emdee_md_step returns EMDEE_ERR_STATE).
+ * With a thermostat on, emdee_md_step closes the half kick of every step, as with a barostat: the states after s steps do not
+ * depend on how the steps were dealt to calls, bit for bit.  After the step that brings the count s to a multiple of `every`
+ * (after the velocity stage of the constraints, before the barostat's event), with Delta = every dt:
+ *   v-rescale (EMDEE_THERMOSTAT_VRESCALE; Bussi, Donadio & Parrinello, J. Chem. Phys. 126, 014101 (2007)):
+ *     c = exp(-Delta / tau_t), Kbar = n_dof kT / 2, R1 ~ N(0,1), S ~ chi-squared with n_dof - 1 degrees of freedom,
+ *     alpha^2 = c + (1 - c) (S + R1^2) Kbar / (n_dof K) + 2 R1 sqrt(c (1 - c) Kbar / (n_dof K)),  alpha = +sqrt(alpha^2)
+ *     (alpha = 1 for K = 0);  E_th -= (alpha^2 - 1) K.
+ *     {R1, S} are a pure function of (seed, s, n_dof): emdee_md_thermostat_draws returns them (the generator of the Langevin
+ *     noise at ids -2, -3, ...; S = 2 Gamma((n_dof - 1) / 2) by Marsaglia & Tsang with at most 64 attempts).
+ *   Nose-Hoover chain (EMDEE_THERMOSTAT_NOSE_HOOVER; Martyna, Tuckerman, Tobias & Klein, Mol. Phys. 87, 1117 (1996)):
+ *     Q_1 = n_dof kT tau_t^2, Q_k = kT tau_t^2; the MTK factorisation without Suzuki-Yoshida weights, two passes of Delta / 2
+ *     (DESIGN.md 4f has the lines); alpha is the product of the passes' factors exp(-(Delta / 2) v_1);
+ *     E_th = sum Q_k v_k^2 / 2 + n_dof kT xi_1 + kT sum_{k > 1} xi_k.
+ *   then v <- alpha v on every owned atom (fp64 product in both precisions).  U + K + E_th is the conserved quantity.
+ * One application over Delta per event instead of Delta / 2 before and after the step: the sequence of states is the symmetric
+ * integrator's, seen half a thermostat operation later.  An event is three launches on the engine's stream and no read-back;
+ * their device time is emdee_md_kernel_time index 14.  emdee_md_minimize leaves the thermostat out and its state untouched.
+ *
+ * emdee_md_thermostat_state (blocking): out[0] = n_dof in use, [1] = K as the last event saw it, before its scaling, [2] = that
+ * event's alpha, [3] = E_th, [4..11] = xi_k, [12..19] = v_xi_k (unused chain slots 0).  emdee_md_set_thermostat zeroes words
+ * 1-19; emdee_md_set_thermostat_state writes words 3-19.  A restart is emdee_md_set_thermostat with first_step = the steps done,
+ * then emdee_md_set_thermostat_state with the words read before.
+ *   - All or nothing: EMDEE_ERR_INVALID, the previous setting in force, for an unknown kind, a temperature or tau_t that is not
+ *     finite or <= 0, every < 1, n_dof < 0, chain outside 1...8 with kind NOSE_HOOVER, a NULL array.
+ *   - EMDEE_ERR_STATE on an integrator lent by emdee_dd_engine and on one with ghosts; for a kind other than OFF while the
+ *     Langevin thermostat is on (gamma > 0), and from emdee_md_set_langevin with gamma > 0 while a global thermostat is on.
+ * Scope: undivided boxes; no emdee_dd_* counterpart. */
+#define EMDEE_THERMOSTAT_OFF          0
+#define EMDEE_THERMOSTAT_VRESCALE     1     /* stochastic velocity rescaling, Bussi, Donadio & Parrinello 2007 */
+#define EMDEE_THERMOSTAT_NOSE_HOOVER  2     /* Nose-Hoover chain, Martyna, Tuckerman, Tobias & Klein 1996 */
+#define EMDEE_THERMOSTAT_WORDS        20
+int32_t emdee_md_set_thermostat(emdee_md *md, int32_t kind, double temperature, double tau_t, int32_t every, int64_t n_dof,
+                                int32_t chain, uint64_t seed, uint64_t first_step);
+int32_t emdee_md_thermostat_state(emdee_md *md, double out[EMDEE_THERMOSTAT_WORDS]);
+int32_t emdee_md_set_thermostat_state(emdee_md *md, const double in[EMDEE_THERMOSTAT_WORDS]);
+int32_t emdee_md_thermostat_draws(emdee_md *md, uint64_t seed, uint64_t step, int64_t n_dof, double out[2]);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
