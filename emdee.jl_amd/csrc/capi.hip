@@ -490,6 +490,18 @@ int32_t emdee_md_set_thermostat_state(emdee_md *md, const double in[EMDEE_THERMO
 int32_t emdee_md_thermostat_draws(emdee_md *md, uint64_t seed, uint64_t step, int64_t n_dof, double out[2]) {
     return guarded([&] { REQUIRE_PTR(md, "md"); REQUIRE_PTR(out, "thermostat_draws: out"); md->impl->thermostat_draws(seed, step, n_dof, out); });
 }
+int32_t emdee_md_set_rdf(emdee_md *md, double r_max, int32_t n_bins, int32_t n_groups, const int32_t *group_dev, const int32_t *molecule_dev) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_rdf(r_max, n_bins, n_groups, group_dev, molecule_dev); });
+}
+int32_t emdee_md_rdf_sample(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->rdf_sample(); });
+}
+int32_t emdee_md_rdf_read(emdee_md *md, int64_t *counts, int64_t group_sizes[8], int64_t *frames, double *inv_volume_sum) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->rdf_read(counts, group_sizes, frames, inv_volume_sum); });
+}
+int32_t emdee_md_rdf_reset(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->rdf_reset(); });
+}
 
 // ---------------------------------------------------------------- domain decomposition
 int32_t emdee_dd_unique_id(uint8_t out[128]) {

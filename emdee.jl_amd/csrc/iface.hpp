@@ -71,6 +71,10 @@ struct IMd {
     virtual void thermostat_state(double *out) = 0;
     virtual void set_thermostat_state(const double *in) = 0;
     virtual void thermostat_draws(uint64_t seed, uint64_t step, int64_t n_dof, double *out) = 0;
+    virtual void set_rdf(double r_max, int32_t n_bins, int32_t n_groups, const int32_t *group_dev, const int32_t *molecule_dev) = 0;
+    virtual void rdf_sample() = 0;
+    virtual void rdf_read(int64_t *counts, int64_t *group_sizes, int64_t *frames, double *inv_volume_sum) = 0;
+    virtual void rdf_reset() = 0;
 };
 
 // spatial domain decomposition (emdee_dd_*): the domains of the decomposition that live in this process

@@ -540,6 +540,101 @@ struct MdImpl : IMd {
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.read_back_doubles(out, part, 2);
     }
+    // ---- radial distribution functions (include/emdee_hip.h: emdee_md_set_rdf; rdf.hpp)
+    struct RdfTable {
+        bool present = false, grouped = false, with_mol = false;
+        int n_atoms = 0, n_bins = 0, n_groups = 0;
+        double r_max = 0.0, inv_dr = 0.0;
+        int64_t sizes[RDF_MAX_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int64_t frames = 0;
+        double inv_volume_sum = 0.0;
+        int n_counters() const { return rdf_n_pairs(n_groups) * n_bins; }
+    } rdf;
+    double shortest_side() const { return std::min(sys.len[0], std::min(sys.len[1], sys.len[2])); }
+    void zero_rdf() {
+        if (rdf.present) EMDEE_HIP_CHECK(hipMemsetAsync(sys.rdf_counts.ptr, 0, (size_t)rdf.n_counters() * sizeof(unsigned long long), sys.stream()));
+        rdf.frames = 0;
+        rdf.inv_volume_sum = 0.0;
+    }
+    // all or nothing: every refusal comes before the table in force changes; blocking (the two arrays are checked on the host)
+    void set_rdf(double r_max, int32_t n_bins, int32_t n_groups, const int32_t *group_dev, const int32_t *molecule_dev) override {
+        use_device(sys.ctx);
+        if (n_bins == 0) { rdf = RdfTable{}; return; }
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "set_rdf: this integrator is a domain's, lent by emdee_dd_engine: it sees a part of the box only");
+        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "set_rdf: an integrator with ghosts (its box is a domain of a larger one)");
+        EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "set_rdf: the box has an open axis; the minimum image needs three periodic ones");
+        EMDEE_REQUIRE(sys.sorted && !sys.id_gaps, EMDEE_ERR_STATE, "set_rdf: no state loaded (call emdee_md_set_state first)");
+        EMDEE_REQUIRE(n_groups >= 1 && n_groups <= RDF_MAX_GROUPS, EMDEE_ERR_INVALID, "set_rdf: n_groups = %d is outside 1...%d", n_groups, RDF_MAX_GROUPS);
+        EMDEE_REQUIRE(n_bins >= 1, EMDEE_ERR_INVALID, "set_rdf: n_bins = %d must be >= 1 (0 clears the table)", n_bins);
+        EMDEE_REQUIRE((long long)rdf_n_pairs(n_groups) * n_bins <= RDF_MAX_COUNTERS, EMDEE_ERR_INVALID, "set_rdf: %d histograms of %d bins are %lld "
+                      "counters, above the limit of %d (a workgroup's histogram in LDS)", rdf_n_pairs(n_groups), n_bins,
+                      (long long)rdf_n_pairs(n_groups) * n_bins, RDF_MAX_COUNTERS);
+        EMDEE_REQUIRE(std::isfinite(r_max) && r_max > 0.0, EMDEE_ERR_INVALID, "set_rdf: r_max must be finite and > 0");
+        EMDEE_REQUIRE(r_max <= 0.5 * shortest_side(), EMDEE_ERR_INVALID, "set_rdf: r_max = %g exceeds half the shortest box side %g (minimum image)",
+                      r_max, shortest_side());
+        EMDEE_REQUIRE(group_dev || n_groups == 1, EMDEE_ERR_INVALID, "set_rdf: groups is NULL with n_groups = %d (NULL puts every atom in group 0)", n_groups);
+        const int n = sys.n_owned;
+        RdfTable t;
+        t.present = true; t.grouped = group_dev != nullptr; t.with_mol = molecule_dev != nullptr;
+        t.n_atoms = n; t.n_bins = n_bins; t.n_groups = n_groups; t.r_max = r_max; t.inv_dr = (double)n_bins / r_max;
+        std::vector<int32_t> host((size_t)n);
+        auto fetch = [&](const int32_t *dev) {
+            if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(host.data(), dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sys.stream()));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        };
+        if (t.grouped) {
+            fetch(group_dev);
+            for (int i = 0; i < n; i++) {
+                EMDEE_REQUIRE(host[i] >= -1 && host[i] < n_groups, EMDEE_ERR_INVALID, "set_rdf: the group %d of atom %d is outside -1...%d", host[i], i, n_groups - 1);
+                if (host[i] >= 0) t.sizes[host[i]]++;
+            }
+        } else {
+            t.sizes[0] = n;
+        }
+        if (t.with_mol) {
+            fetch(molecule_dev);
+            for (int i = 0; i < n; i++)
+                EMDEE_REQUIRE(host[i] >= -1, EMDEE_ERR_INVALID, "set_rdf: the molecule %d of atom %d is below -1 (-1: none)", host[i], i);
+        }
+        // ---- commit
+        sys.rdf_group.ensure((size_t)n + 1); sys.rdf_mol.ensure((size_t)n + 1);
+        sys.rdf_counts.ensure((size_t)t.n_counters());
+        if (t.grouped && n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(sys.rdf_group.ptr, group_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, sys.stream()));
+        if (t.with_mol && n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(sys.rdf_mol.ptr, molecule_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, sys.stream()));
+        rdf = t;
+        zero_rdf();
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));   // (the caller's arrays are its own again on return)
+    }
+    // one frame: queued on the stream, nothing read back; the engine's state, list and counters are not touched
+    void rdf_sample() override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_sample: no table is set (call emdee_md_set_rdf first)");
+        EMDEE_REQUIRE(sys.sorted && rdf.n_atoms == sys.n_owned && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "rdf_sample: the table was set for %d atoms, "
+                      "the state holds %d: set it again (emdee_md_set_rdf)", rdf.n_atoms, sys.n_owned);
+        EMDEE_REQUIRE(rdf.r_max <= 0.5 * shortest_side(), EMDEE_ERR_STATE, "rdf_sample: the box has shrunk: r_max = %g now exceeds half the shortest "
+                      "side %g; set the table again with a smaller r_max", rdf.r_max, shortest_side());
+        sys.rdf_sample(rdf_plan(sys.len, rdf.r_max, sys.n_owned), rdf.grouped, rdf.with_mol, rdf.r_max, rdf.inv_dr, rdf.n_bins, rdf.n_groups);
+        EMDEE_HIP_CHECK(hipGetLastError());
+        rdf.frames++;
+        rdf.inv_volume_sum += 1.0 / (sys.len[0] * sys.len[1] * sys.len[2]);
+    }
+    // blocking; any pointer may be NULL
+    void rdf_read(int64_t *counts, int64_t *group_sizes, int64_t *frames, double *inv_volume_sum) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_read: no table is set (call emdee_md_set_rdf first)");
+        if (counts) {
+            EMDEE_HIP_CHECK(hipMemcpyAsync(counts, sys.rdf_counts.ptr, (size_t)rdf.n_counters() * sizeof(int64_t), hipMemcpyDeviceToHost, sys.stream()));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        }
+        if (group_sizes) for (int a = 0; a < RDF_MAX_GROUPS; a++) group_sizes[a] = rdf.sizes[a];
+        if (frames) *frames = rdf.frames;
+        if (inv_volume_sum) *inv_volume_sum = rdf.inv_volume_sum;
+    }
+    void rdf_reset() override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_reset: no table is set (call emdee_md_set_rdf first)");
+        zero_rdf();
+    }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
     void couple(double dt) {
@@ -780,12 +875,13 @@ struct MdImpl : IMd {
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
         // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
         // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps; 13: placement and
-        // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 14, EMDEE_ERR_INVALID, "kernel id out of range");
+        // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat; 15: the four
+        // stages of every sample of the radial distribution functions (emdee_md_rdf_sample)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 15, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[15][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[16][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {

@@ -13,6 +13,7 @@
 #include "kernels.hpp"
 #include "minimize.hpp"
 #include "plan.hpp"
+#include "rdf.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
 #include "thermostat.hpp"
@@ -46,8 +47,9 @@ static inline void refuse_experiment_switches() {
 // T_MINIMIZE: what emdee_md_minimize adds to the stages of a closed step (minimize.hpp): the constrained force, the reduction, the mixing
 // T_VSITE: placement and force spreading of an engine with virtual sites (vsite.hpp)
 // T_THERMOSTAT: the three launches of a global thermostat's event (thermostat.hpp)
+// T_RDF: the four stages of a sample of the radial distribution functions (rdf.hpp): count, scan, fill, pair loop
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_COUNT = 14 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_COUNT = 15 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -1570,6 +1572,53 @@ struct NbSystem {
             Timed t(this, T_THERMOSTAT);
             hipLaunchKernelGGL((k_scale_velocities<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, pitch,
                                perm.ptr, vel.ptr, (const double *)w);
+        }
+    }
+
+    // ---------------------------------------------------------------- radial distribution functions (rdf.hpp; MdImpl::set_rdf / rdf_sample drive these)
+    // The table's copies of the caller's group and molecule arrays (caller order), the sample's own binning and the u64 histogram.
+    // A sample reads the records, perm and the cells the Float32 records are relative to; it writes nothing of the engine's.
+    DevBuf<int> rdf_group, rdf_mol, rdf_cell_of, rdf_count, rdf_fill;
+    DevBuf<RdfAtom> rdf_atoms;
+    DevBuf<unsigned long long> rdf_counts;
+    Scanner rdf_scanner;
+    // one frame into rdf_counts[0 .. n_counters): four timed stages on the stream, nothing read back
+    void rdf_sample(const RdfPlan &plan, bool grouped, bool with_mol, double r_max, double inv_dr, int n_bins, int n_groups) {
+        if (n_total == 0) return;
+        const int n = n_total, ncell = (int)rdf_plan_cells(plan), n_counters = rdf_n_pairs(n_groups) * n_bins;
+        RdfGrid g{};
+        for (int d = 0; d < 3; d++) {
+            g.lo[d] = lo[d]; g.len[d] = len[d]; g.inv_len[d] = 1.0 / len[d];
+            g.M[d] = plan.M[d]; g.wrap[d] = plan.wrap[d];
+        }
+        g.nd = plan.nd;
+        rdf_cell_of.ensure((size_t)n + 1); rdf_atoms.ensure((size_t)n + 1);
+        rdf_count.ensure((size_t)ncell + 2); rdf_fill.ensure((size_t)ncell + 2);
+        const RelGrid rel = rel_grid(rel_now, cell_sorted.ptr);
+        const int *grp = grouped ? rdf_group.ptr : nullptr, *mol = with_mol ? rdf_mol.ptr : nullptr;
+        {
+            Timed t(this, T_RDF);
+            EMDEE_HIP_CHECK(hipMemsetAsync(rdf_count.ptr, 0, ((size_t)ncell + 1) * sizeof(int), stream()));
+            EMDEE_HIP_CHECK(hipMemsetAsync(rdf_fill.ptr, 0, (size_t)ncell * sizeof(int), stream()));
+            hipLaunchKernelGGL((k_rdf_count<real>), dim3(blocks_for(n, 256)), dim3(256), 0, stream(), n, n_owned, (const Rec<real> *)rec.ptr, rel,
+                               (const int *)perm.ptr, grp, g, rdf_cell_of.ptr, rdf_count.ptr);
+        }
+        {
+            Timed t(this, T_RDF);
+            rdf_scanner.run(rdf_count.ptr, (size_t)ncell + 1, stream());   // count[] becomes the first slot of every cell
+        }
+        {
+            Timed t(this, T_RDF);
+            hipLaunchKernelGGL((k_rdf_fill<real>), dim3(blocks_for(n, 256)), dim3(256), 0, stream(), n, (const Rec<real> *)rec.ptr, rel,
+                               (const int *)perm.ptr, grp, mol, (const int *)rdf_cell_of.ptr, (const int *)rdf_count.ptr, rdf_fill.ptr,
+                               rdf_atoms.ptr);
+        }
+        {
+            Timed t(this, T_RDF);
+            const int blocks = std::max(1, std::min(ncell, 8 * std::max(ctx->cu_count, 32)));
+            hipLaunchKernelGGL(k_rdf_pairs, dim3(blocks), dim3(RDF_BLOCK), (size_t)n_counters * sizeof(unsigned int), stream(), g, ncell,
+                               (const int *)rdf_count.ptr, (const RdfAtom *)rdf_atoms.ptr, r_max * r_max * RDF_R2_MARGIN, inv_dr, n_bins,
+                               n_groups, n_counters, rdf_counts.ptr);
         }
     }
 

@@ -3,6 +3,7 @@
 export VelocityVerlet, step!, energies, set_langevin!, set_langevin_ids!, virial_tensor!, pressure_tensor
 export box, scale_box!, set_barostat!
 export set_thermostat!, thermostat_state, set_thermostat_state!, thermostat_draws
+export set_rdf!, rdf_sample!, rdf_reset!, rdf_read
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -193,6 +194,40 @@ function thermostat_draws(md::VelocityVerlet, seed, step, n_dof)
     check(ccall((:emdee_md_thermostat_draws, libemdee_hip), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Ptr{Float64}), md.handle,
                 UInt64(seed), UInt64(step), Int64(n_dof), out))
     return (out[1], out[2])
+end
+
+# Radial distribution functions (include/emdee_hip.h; undivided boxes, periodic in all three dimensions).
+# int32_t emdee_md_set_rdf(emdee_md *md, double r_max, int32_t n_bins, int32_t n_groups, const int32_t *group_dev,
+#                          const int32_t *molecule_dev);
+# groups, molecules: device Int32 vectors in caller order, or `nothing` (every atom in group 0 / no molecules); a group of -1
+# leaves the atom out, pairs with equal molecule entries >= 0 are skipped.  n_bins = 0 clears the table.
+const RDF_MAX_GROUPS = 8
+function set_rdf!(md::VelocityVerlet, r_max, n_bins; n_groups=1, groups::Union{Nothing,HipArray{Int32,1}}=nothing,
+                  molecules::Union{Nothing,HipArray{Int32,1}}=nothing)
+    check(ccall((:emdee_md_set_rdf, libemdee_hip), Int32, (Ptr{Cvoid}, Float64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}), md.handle,
+                Float64(r_max), Int32(n_bins), Int32(n_groups), groups === nothing ? C_NULL : groups.ptr,
+                molecules === nothing ? C_NULL : molecules.ptr))
+end
+
+# int32_t emdee_md_rdf_sample(emdee_md *md);
+# adds the current positions as one frame: queued on the stream, nothing read back, the run untouched
+rdf_sample!(md::VelocityVerlet) = check(ccall((:emdee_md_rdf_sample, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_rdf_reset(emdee_md *md);
+rdf_reset!(md::VelocityVerlet) = check(ccall((:emdee_md_rdf_reset, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_rdf_read(emdee_md *md, int64_t *counts, int64_t group_sizes[8], int64_t *frames, double *inv_volume_sum);
+# blocking -> (counts (n_bins x n_pairs: column s = slot a n_groups - a (a - 1) / 2 + (b - a) of the pair a <= b), group sizes,
+# frames, sum of 1 / V); g_ab = counts / (P_ab (4 pi / 3) (r_{k+1}^3 - r_k^3) inv_volume_sum), P_ab = N_a N_b or N_a (N_a - 1) / 2
+function rdf_read(md::VelocityVerlet, n_bins, n_groups)
+    n_pairs = n_groups * (n_groups + 1) ÷ 2
+    counts = zeros(Int64, n_bins, n_pairs)
+    sizes = zeros(Int64, RDF_MAX_GROUPS)
+    frames = Ref{Int64}(0)
+    inv_volume_sum = Ref{Float64}(0.0)
+    check(ccall((:emdee_md_rdf_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}), md.handle,
+                counts, sizes, frames, inv_volume_sum))
+    return (counts=counts, group_sizes=sizes[1:n_groups], frames=frames[], inv_volume_sum=inv_volume_sum[])
 end
 
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);

@@ -72,7 +72,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # placement and force spreading of an engine with virtual sites (set_vsites_)
            "vsites": 13,
            # the three launches of every event of a global thermostat (set_thermostat_)
-           "thermostat": 14}
+           "thermostat": 14,
+           # the four stages of every sample of the radial distribution functions (rdf_sample_)
+           "rdf": 15}
 
 
 class MinimizeResult:
@@ -373,6 +375,64 @@ class VelocityVerlet:
         out = (C.c_double * 2)()
         _lib.call("emdee_md_thermostat_draws", self._handle, int(seed) & (2 ** 64 - 1), int(step), int(n_dof), out)
         return out[0], out[1]
+
+    # -- radial distribution functions (include/emdee_hip.h: emdee_md_set_rdf; undivided periodic boxes)
+    _rdf = None                                            # (r_max, n_bins, n_groups) of the table in force
+
+    def set_rdf_(self, r_max, n_bins, groups=None, molecules=None, n_groups=None):
+        """The table of the pair histograms rdf_sample_() fills: n_bins bins up to r_max (at most half the shortest box side).
+        groups: None (every atom in one group) or one integer per owned atom, -1 to leave the atom out; there is one histogram
+        per unordered pair of groups (n_groups: how many groups there are, 1...8; None: the largest entry of groups + 1).
+        molecules: None, or one integer per owned atom; pairs with equal entries >= 0 are skipped.  n_bins = 0 clears the
+        table.  Zeroes the accumulators."""
+        as_i32 = lambda v: torch.as_tensor(v).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        g = as_i32(groups) if groups is not None else None
+        m = as_i32(molecules) if molecules is not None else None
+        for name, t in (("groups", g), ("molecules", m)):
+            if t is not None and t.shape[0] != self.n_owned:
+                raise ValueError("set_rdf_: %s holds %d entries, the state %d owned atoms" % (name, t.shape[0], self.n_owned))
+        if n_groups is None:
+            n_groups = 1 if g is None or g.numel() == 0 else max(int(g.max().item()) + 1, 1)
+        n_groups = int(n_groups)
+        _lib.call("emdee_md_set_rdf", self._handle, float(r_max), int(n_bins), n_groups,
+                  C.c_void_p(g.data_ptr()) if g is not None else None, C.c_void_p(m.data_ptr()) if m is not None else None)
+        self._rdf = (float(r_max), int(n_bins), n_groups) if int(n_bins) != 0 else None
+
+    def rdf_sample_(self):
+        """Adds the current positions to the histograms as one frame: queued on the stream, nothing read back, the run untouched."""
+        _lib.call("emdee_md_rdf_sample", self._handle)
+
+    def rdf_reset_(self):
+        """Zeroes the counts, the frame count and the sum of 1 / V."""
+        _lib.call("emdee_md_rdf_reset", self._handle)
+
+    def rdf(self):
+        """The accumulated histograms and what follows from them, as a dict (blocking): r (bin centres), edges, pairs (the
+        (a, b) of every histogram, a <= b, in slot order), counts ((n_pairs, n_bins) int64 numpy), group_sizes, frames,
+        inv_volume_sum, g ((n_pairs, n_bins): counts / (P_ab shell inv_volume_sum), P_ab = N_a N_b or N_a (N_a - 1) / 2; pairs
+        skipped as intramolecular stay in P_ab) and coordination (the running number of b around a: cumulative counts, times 2
+        for a == b, over N_a frames)."""
+        import numpy as np
+        if self._rdf is None:
+            raise ValueError("rdf: no table is set (set_rdf_)")
+        r_max, n_bins, n_groups = self._rdf
+        pairs = [(a, b) for a in range(n_groups) for b in range(a, n_groups)]
+        counts = np.zeros((len(pairs), n_bins), dtype=np.int64)
+        sizes, frames, ivs = (C.c_int64 * 8)(), C.c_int64(), C.c_double()
+        _lib.call("emdee_md_rdf_read", self._handle, counts.ctypes.data_as(C.c_void_p), sizes, C.byref(frames), C.byref(ivs))
+        sizes = [int(s) for s in sizes][:n_groups]
+        edges = r_max * np.arange(n_bins + 1, dtype=np.float64) / n_bins
+        shell = 4.0 * np.pi / 3.0 * (edges[1:] ** 3 - edges[:-1] ** 3)
+        g, coordination = np.zeros(counts.shape), np.zeros(counts.shape)
+        for s, (a, b) in enumerate(pairs):
+            P = 0.5 * sizes[a] * (sizes[a] - 1) if a == b else float(sizes[a]) * sizes[b]
+            ideal = P * shell * ivs.value
+            if P > 0 and ivs.value > 0.0:
+                g[s] = counts[s] / ideal
+            if sizes[a] > 0 and frames.value > 0:
+                coordination[s] = (2.0 if a == b else 1.0) * np.cumsum(counts[s]) / (float(sizes[a]) * frames.value)
+        return dict(r=0.5 * (edges[1:] + edges[:-1]), edges=edges, pairs=pairs, counts=counts, group_sizes=sizes,
+                    frames=int(frames.value), inv_volume_sum=float(ivs.value), g=g, coordination=coordination)
 
     def set_molecular_scaling_(self, on=True):
         """Molecular scaling (include/emdee_hip.h emdee_md_set_molecular_scaling): with it on, an engine with rigid molecules

@@ -675,7 +675,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling);
  * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds); 12 = what emdee_md_minimize adds to the
  * stages of its steps (the constrained force, the reduction, the mixing); 13 = placement and force spreading of an engine with
- * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat).
+ * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat);
+ * 15 = the four stages of every sample of the radial distribution functions (emdee_md_rdf_sample).
  * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
@@ -806,6 +807,47 @@ int32_t emdee_md_set_thermostat(emdee_md *md, int32_t kind, double temperature, 
 int32_t emdee_md_thermostat_state(emdee_md *md, double out[EMDEE_THERMOSTAT_WORDS]);
 int32_t emdee_md_set_thermostat_state(emdee_md *md, const double in[EMDEE_THERMOSTAT_WORDS]);
 int32_t emdee_md_thermostat_draws(emdee_md *md, uint64_t seed, uint64_t step, int64_t n_dof, double out[2]);
+
+/* Radial distribution functions (build-defined: the reference has no structural analysis).  The engine histograms the pair
+ * distances of its current positions on the device, so that g(r) of a liquid -- g_OO, g_OH and g_HH of water -- costs no copy of
+ * the positions to the host and no O(N^2) loop there.
+ *
+ * emdee_md_set_rdf(r_max, n_bins, n_groups, group_dev, molecule_dev) sets the table (blocking; n_bins = 0 clears it):
+ *   n_groups in 1...8.  group_dev: n_owned int32 in caller order on the device, each in -1...n_groups-1; -1 leaves the atom out;
+ *   NULL with n_groups == 1 puts every atom in group 0.  molecule_dev: NULL, or n_owned int32; a pair whose two entries are equal
+ *   and >= 0 is intramolecular and is skipped; -1: the atom has no molecule.  Both arrays are copied, the group sizes are counted.
+ *   One histogram per unordered pair of groups a <= b, in slot s(a, b) = a n_groups - a (a - 1) / 2 + (b - a); bin k of it is
+ *   counts[s n_bins + k], a 64-bit integer on the device.  n_bins >= 1 and n_pairs n_bins <= 8192 (a workgroup keeps a private
+ *   histogram in 32 KB of LDS); r_max finite, > 0 and at most half the shortest box side.  Setting a table zeroes the accumulators.
+ *   - All or nothing: EMDEE_ERR_INVALID, the previous table in force, for arguments outside these limits; for a group or molecule
+ *     value out of range the text names the first offending atom.
+ *   - EMDEE_ERR_STATE, each with its own text: before emdee_md_set_state, on an integrator lent by emdee_dd_engine, on one with
+ *     ghosts, on a box with an open axis.
+ *
+ * emdee_md_rdf_sample adds the current positions as one frame: work queued on the engine's stream, nothing read back.  Every
+ * unordered pair {i, j} of grouped atoms that do not share a molecule is counted exactly once: its minimum-image distance r in
+ * fp64 from the engine's records as doubles (a Float32 engine: the cell-relative record plus the origin of its cell), bin
+ * (int)(r inv_dr) with inv_dr = n_bins / r_max formed once in double, dropped when the bin is n_bins or more.  The sums are
+ * integers: the counts are exact and bitwise reproducible.  The host adds 1 to frames and 1 / V of the current box to
+ * inv_volume_sum.  The sample bins the atoms on a grid of its own, made from the positions as they are: it does not read the
+ * neighbour list and is exact whatever the list's age.  It does not touch the engine: no re-sort, no rebuild, no force pass; an
+ * engine that samples and one that does not stay bit for bit equal.  Its device time is emdee_md_kernel_time index 15.
+ *   - EMDEE_ERR_STATE, the accumulators untouched: no table is set; the table was set for another atom count; a barostat has
+ *     shrunk the box so that r_max exceeds half the shortest side.
+ * Sampling on a cadence inside emdee_md_step is not offered: emdee_md_step ends with a read-back anyway, so step(n) followed by
+ * a sample costs nothing more.
+ *
+ * emdee_md_rdf_read (blocking; any pointer may be NULL): the n_pairs n_bins counts, the eight group sizes, frames and
+ * inv_volume_sum.  emdee_md_rdf_reset zeroes the counts, frames and inv_volume_sum.  From them, with r_k = r_max k / n_bins,
+ *   g_ab(k) = counts / (P_ab (4 pi / 3) (r_{k+1}^3 - r_k^3) inv_volume_sum),  P_ab = N_a N_b (a != b),  P_aa = N_a (N_a - 1) / 2,
+ * and the running coordination number of b around a is the cumulative sum of the counts, times 2 for a == b, over N_a frames.
+ * The pairs skipped as intramolecular are not taken out of P_ab, as is usual.
+ * Scope: undivided boxes, periodic in all three dimensions; no emdee_dd_* counterpart. */
+int32_t emdee_md_set_rdf(emdee_md *md, double r_max, int32_t n_bins, int32_t n_groups, const int32_t *group_dev,
+                         const int32_t *molecule_dev);
+int32_t emdee_md_rdf_sample(emdee_md *md);
+int32_t emdee_md_rdf_read(emdee_md *md, int64_t *counts, int64_t group_sizes[8], int64_t *frames, double *inv_volume_sum);
+int32_t emdee_md_rdf_reset(emdee_md *md);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
