@@ -502,6 +502,18 @@ int32_t emdee_md_rdf_read(emdee_md *md, int64_t *counts, int64_t group_sizes[8],
 int32_t emdee_md_rdf_reset(emdee_md *md) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->rdf_reset(); });
 }
+int32_t emdee_md_set_msd(emdee_md *md, int32_t what, int32_t n_groups, const int32_t *group_dev, int32_t n_lags, int32_t origin_every) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_msd(what, n_groups, group_dev, n_lags, origin_every); });
+}
+int32_t emdee_md_msd_sample(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->msd_sample(); });
+}
+int32_t emdee_md_msd_read(emdee_md *md, double *sums, int64_t *origins, int64_t group_sizes[8], int64_t *samples) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->msd_read(sums, origins, group_sizes, samples); });
+}
+int32_t emdee_md_msd_reset(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->msd_reset(); });
+}
 
 // ---------------------------------------------------------------- domain decomposition
 int32_t emdee_dd_unique_id(uint8_t out[128]) {

@@ -75,6 +75,10 @@ struct IMd {
     virtual void rdf_sample() = 0;
     virtual void rdf_read(int64_t *counts, int64_t *group_sizes, int64_t *frames, double *inv_volume_sum) = 0;
     virtual void rdf_reset() = 0;
+    virtual void set_msd(int32_t what, int32_t n_groups, const int32_t *group_dev, int32_t n_lags, int32_t origin_every) = 0;
+    virtual void msd_sample() = 0;
+    virtual void msd_read(double *sums, int64_t *origins, int64_t *group_sizes, int64_t *samples) = 0;
+    virtual void msd_reset() = 0;
 };
 
 // spatial domain decomposition (emdee_dd_*): the domains of the decomposition that live in this process

@@ -184,6 +184,7 @@ struct MdImpl : IMd {
         use_device(sys.ctx);
         EMDEE_REQUIRE(vel || n_owned == 0, EMDEE_ERR_INVALID, "velocities are NULL");
         n_ghost = ng;
+        state_serial++;                                      // (before anything can throw: a state half replaced is another state too)
         sys.load_user(n_owned, ng, (const real *)pos, (const real *)vel, atoms, (const real *)inv_mass, tags_user);
         if (!lent) { sys.reset_bonded_error(); sys.reset_ewald_error(); }   // (a new state: the bonded terms and the struck pairs get another chance; a decomposition resets its own)
         since_build = 0;
@@ -635,6 +636,109 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_reset: no table is set (call emdee_md_set_rdf first)");
         zero_rdf();
     }
+    // ---- mean-squared displacement and velocity autocorrelation (include/emdee_hip.h: emdee_md_set_msd; msd.hpp)
+    struct MsdTable {
+        bool present = false;
+        int what = 0, n_atoms = 0, n_groups = 0, n_lags = 0, origin_every = 1, n_origins = 0, n_grouped = 0, n_chunks = 0;
+        int64_t sizes[MSD_MAX_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int64_t samples = 0;                                 // s of the next sample
+        std::vector<int64_t> origins;                        // per lag: the origins that have contributed
+        double len[3] = {0, 0, 0};                           // the box at the last set or reset
+        uint64_t serial = 0;                                 // ... and the state serial
+        size_t snapshot() const { return (size_t)n_grouped * (((what & MSD_POSITIONS) ? 3 : 0) + ((what & MSD_VELOCITIES) ? 3 : 0)); }
+        size_t n_sums() const { return (size_t)n_lags * n_groups * MSD_WORDS; }
+    } msd;
+    uint64_t state_serial = 0;                               // counts emdee_md_set_state: a snapshot of one state is no origin for another
+    void zero_msd() {
+        if (msd.present) EMDEE_HIP_CHECK(hipMemsetAsync(sys.msd.sums.ptr, 0, msd.n_sums() * sizeof(double), sys.stream()));
+        msd.samples = 0;
+        msd.origins.assign((size_t)msd.n_lags, 0);
+        for (int d = 0; d < 3; d++) msd.len[d] = sys.len[d];
+        msd.serial = state_serial;
+    }
+    // all or nothing: every refusal, a failed allocation included, comes before the table in force changes; blocking
+    void set_msd(int32_t what, int32_t n_groups, const int32_t *group_dev, int32_t n_lags, int32_t origin_every) override {
+        use_device(sys.ctx);
+        if (n_lags == 0) { msd = MsdTable{}; return; }
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "set_msd: this integrator is a domain's, lent by emdee_dd_engine: it sees a part of the box only");
+        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "set_msd: an integrator with ghosts (its box is a domain of a larger one)");
+        EMDEE_REQUIRE(sys.sorted && !sys.id_gaps, EMDEE_ERR_STATE, "set_msd: no state loaded (call emdee_md_set_state first)");
+        EMDEE_REQUIRE(what >= 1 && what <= (MSD_POSITIONS | MSD_VELOCITIES), EMDEE_ERR_INVALID, "set_msd: what = %d is not a non-empty mask of "
+                      "EMDEE_MSD | EMDEE_VACF", what);
+        EMDEE_REQUIRE(n_groups >= 1 && n_groups <= MSD_MAX_GROUPS, EMDEE_ERR_INVALID, "set_msd: n_groups = %d is outside 1...%d", n_groups, MSD_MAX_GROUPS);
+        EMDEE_REQUIRE(n_lags >= 1 && n_lags <= MSD_MAX_LAGS, EMDEE_ERR_INVALID, "set_msd: n_lags = %d is outside 1...%d (0 clears the table)", n_lags, MSD_MAX_LAGS);
+        EMDEE_REQUIRE(origin_every >= 1, EMDEE_ERR_INVALID, "set_msd: origin_every = %d must be >= 1", origin_every);
+        EMDEE_REQUIRE(msd_n_origins(n_lags, origin_every) <= MSD_MAX_ORIGINS, EMDEE_ERR_INVALID, "set_msd: %d lags with an origin every %d samples "
+                      "are %d origins in the ring, above the limit of %d", n_lags, origin_every, msd_n_origins(n_lags, origin_every), MSD_MAX_ORIGINS);
+        EMDEE_REQUIRE(group_dev || n_groups == 1, EMDEE_ERR_INVALID, "set_msd: groups is NULL with n_groups = %d (NULL puts every atom in group 0)", n_groups);
+        const int n = sys.n_owned;
+        std::vector<int32_t> host((size_t)n);
+        if (group_dev) {
+            if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(host.data(), group_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sys.stream()));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+            for (int i = 0; i < n; i++)
+                EMDEE_REQUIRE(host[i] >= -1 && host[i] < n_groups, EMDEE_ERR_INVALID, "set_msd: the group %d of atom %d is outside -1...%d", host[i], i, n_groups - 1);
+        }
+        const MsdLayout lay = msd_layout(group_dev ? host.data() : nullptr, n, n_groups);
+        MsdTable t;
+        t.present = true; t.what = what; t.n_atoms = n; t.n_groups = n_groups; t.n_lags = n_lags; t.origin_every = origin_every;
+        t.n_origins = msd_n_origins(n_lags, origin_every); t.n_grouped = lay.n_grouped; t.n_chunks = (int)lay.chunks.size();
+        for (int g = 0; g < MSD_MAX_GROUPS; g++) t.sizes[g] = lay.sizes[g];
+        // (buffers of their own: a failed allocation throws here and leaves the table in force and its ring as they are)
+        typename NbSystem<real>::MsdDev dev;
+        dev.pos_of.ensure((size_t)n + 1); dev.chunk_of_group.ensure(MSD_MAX_GROUPS + 1); dev.chunks.ensure(lay.chunks.size() + 1);
+        dev.ring.ensure((size_t)(t.n_origins + 1) * t.snapshot() + 1);
+        dev.partial.ensure((size_t)t.n_origins * lay.chunks.size() * MSD_WORDS + 1);
+        dev.sums.ensure(t.n_sums());
+        if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(dev.pos_of.ptr, lay.pos_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, sys.stream()));
+        EMDEE_HIP_CHECK(hipMemcpyAsync(dev.chunk_of_group.ptr, lay.chunk_of_group, sizeof(lay.chunk_of_group), hipMemcpyHostToDevice, sys.stream()));
+        if (!lay.chunks.empty())
+            EMDEE_HIP_CHECK(hipMemcpyAsync(dev.chunks.ptr, lay.chunks.data(), lay.chunks.size() * sizeof(MsdChunk), hipMemcpyHostToDevice, sys.stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));   // (the host arrays of this call are done with; the old ring is idle)
+        // ---- commit
+        sys.msd.swap(dev);
+        msd = t;
+        zero_msd();
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+    }
+    // one sample: queued on the stream, nothing read back; the engine's state, list and counters are not touched.  A refusal
+    // changes nothing.
+    void msd_sample() override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_sample: no table is set (call emdee_md_set_msd first)");
+        EMDEE_REQUIRE(sys.sorted && msd.n_atoms == sys.n_owned && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "msd_sample: the table was set for %d atoms, "
+                      "the state holds %d: set it again (emdee_md_set_msd)", msd.n_atoms, sys.n_owned);
+        EMDEE_REQUIRE(msd.serial == state_serial, EMDEE_ERR_STATE, "msd_sample: the state has been replaced (emdee_md_set_state) since the origins "
+                      "were taken: a displacement between two states means nothing; start again with emdee_md_msd_reset");
+        EMDEE_REQUIRE(msd.len[0] == sys.len[0] && msd.len[1] == sys.len[1] && msd.len[2] == sys.len[2], EMDEE_ERR_STATE, "msd_sample: the box has been "
+                      "rescaled (emdee_md_scale_box or a barostat) since the origins were taken: unwrapped coordinates across a rescaled box "
+                      "are not a displacement; start again with emdee_md_msd_reset");
+        MsdArgs a{};
+        a.what = msd.what; a.n_grouped = msd.n_grouped; a.n_chunks = msd.n_chunks; a.n_groups = msd.n_groups; a.n_lags = msd.n_lags;
+        a.origin_every = msd.origin_every; a.s = msd.samples; a.snapshot = msd.snapshot();
+        const MsdSchedule q = msd_schedule(msd.samples, msd.n_lags, msd.origin_every);
+        sys.msd_sample(a, q.is_origin ? q.slot : -1, msd.n_origins);
+        EMDEE_HIP_CHECK(hipGetLastError());
+        for (const MsdLive &l : q.live) msd.origins[(size_t)l.lag]++;
+        msd.samples++;
+    }
+    // blocking; any pointer may be NULL
+    void msd_read(double *sums, int64_t *origins, int64_t *group_sizes, int64_t *samples) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_read: no table is set (call emdee_md_set_msd first)");
+        if (sums) {
+            EMDEE_HIP_CHECK(hipMemcpyAsync(sums, sys.msd.sums.ptr, msd.n_sums() * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        }
+        if (origins) for (int l = 0; l < msd.n_lags; l++) origins[l] = msd.origins[(size_t)l];
+        if (group_sizes) for (int g = 0; g < MSD_MAX_GROUPS; g++) group_sizes[g] = msd.sizes[g];
+        if (samples) *samples = msd.samples;
+    }
+    void msd_reset() override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_reset: no table is set (call emdee_md_set_msd first)");
+        zero_msd();
+    }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
     void couple(double dt) {
@@ -876,12 +980,13 @@ struct MdImpl : IMd {
         // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
         // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps; 13: placement and
         // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat; 15: the four
-        // stages of every sample of the radial distribution functions (emdee_md_rdf_sample)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 15, EMDEE_ERR_INVALID, "kernel id out of range");
+        // stages of every sample of the radial distribution functions (emdee_md_rdf_sample); 16: the three launches of every sample
+        // of the displacement and velocity correlations (emdee_md_msd_sample)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 16, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[16][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[17][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {

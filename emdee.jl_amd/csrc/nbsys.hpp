@@ -12,6 +12,7 @@
 #include "ewald.hpp"
 #include "kernels.hpp"
 #include "minimize.hpp"
+#include "msd.hpp"
 #include "plan.hpp"
 #include "rdf.hpp"
 #include "settle.hpp"
@@ -48,8 +49,9 @@ static inline void refuse_experiment_switches() {
 // T_VSITE: placement and force spreading of an engine with virtual sites (vsite.hpp)
 // T_THERMOSTAT: the three launches of a global thermostat's event (thermostat.hpp)
 // T_RDF: the four stages of a sample of the radial distribution functions (rdf.hpp): count, scan, fill, pair loop
+// T_MSD: the three launches of a sample of the displacement and velocity correlations (msd.hpp): gather, accumulate, finish
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_COUNT = 15 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_COUNT = 16 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -1619,6 +1621,46 @@ struct NbSystem {
             hipLaunchKernelGGL(k_rdf_pairs, dim3(blocks), dim3(RDF_BLOCK), (size_t)n_counters * sizeof(unsigned int), stream(), g, ncell,
                                (const int *)rdf_count.ptr, (const RdfAtom *)rdf_atoms.ptr, r_max * r_max * RDF_R2_MARGIN, inv_dr, n_bins,
                                n_groups, n_counters, rdf_counts.ptr);
+        }
+    }
+
+    // ---------------------------------------------------------------- mean-squared displacement and velocity autocorrelation (msd.hpp; MdImpl::set_msd / msd_sample drive these)
+    // The table order (pos_of, caller ids -> entries), its chunks, the ring of snapshots (n_origins + 1 of them, the last one the
+    // scratch snapshot), the chunk partials of one sample and the sums.  A sample reads the records, the image counts, perm, the
+    // velocities and the cells the Float32 records are relative to; it writes nothing of the engine's.
+    struct MsdDev {
+        DevBuf<int> pos_of, chunk_of_group;
+        DevBuf<MsdChunk> chunks;
+        DevBuf<double> ring, partial, sums;
+        void swap(MsdDev &o) {
+            pos_of.swap(o.pos_of); chunk_of_group.swap(o.chunk_of_group); chunks.swap(o.chunks);
+            ring.swap(o.ring); partial.swap(o.partial); sums.swap(o.sums);
+        }
+    } msd;
+    // sample a.s: the snapshot into ring slot `slot` (an origin) or into the scratch snapshot (slot < 0), then every live origin
+    // against it; three timed launches on the stream, nothing read back
+    void msd_sample(const MsdArgs &a, int slot, int n_origins) {
+        if (n_total == 0 || a.n_grouped == 0) return;
+        double *cur = msd.ring.ptr + (size_t)(slot >= 0 ? slot : n_origins) * a.snapshot;
+        const int n_live = msd_live_count(a.s, a.n_lags, a.origin_every);
+        {
+            Timed t(this, T_MSD);
+            hipLaunchKernelGGL((k_msd_gather<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, grid,
+                               (const int *)img.ptr, (const int *)perm.ptr, (const Rec<real> *)rec.ptr, rel_grid(rel_now, cell_sorted.ptr),
+                               (const real *)vel.ptr, pitch, (const int *)msd.pos_of.ptr, a.what, a.n_grouped, cur);
+        }
+        if (n_live == 0) return;
+        {
+            Timed t(this, T_MSD);
+            const bool pos = a.what & MSD_POSITIONS, vel_too = a.what & MSD_VELOCITIES;
+            auto kernel = pos ? (vel_too ? k_msd_accumulate<true, true> : k_msd_accumulate<true, false>) : k_msd_accumulate<false, true>;
+            hipLaunchKernelGGL(kernel, dim3(a.n_chunks), dim3(MSD_BLOCK), 0, stream(), a, (const MsdChunk *)msd.chunks.ptr, (const double *)cur,
+                               (const double *)msd.ring.ptr, msd.partial.ptr);
+        }
+        {
+            Timed t(this, T_MSD);
+            hipLaunchKernelGGL(k_msd_finish, dim3(n_live, a.n_groups), dim3(RED_BLOCK), 0, stream(), a, (const int *)msd.chunk_of_group.ptr,
+                               (const double *)msd.partial.ptr, msd.sums.ptr);
         }
     }
 

@@ -4,6 +4,7 @@ export VelocityVerlet, step!, energies, set_langevin!, set_langevin_ids!, virial
 export box, scale_box!, set_barostat!
 export set_thermostat!, thermostat_state, set_thermostat_state!, thermostat_draws
 export set_rdf!, rdf_sample!, rdf_reset!, rdf_read
+export set_msd!, msd_sample!, msd_reset!, msd_read
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -228,6 +229,40 @@ function rdf_read(md::VelocityVerlet, n_bins, n_groups)
     check(ccall((:emdee_md_rdf_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}), md.handle,
                 counts, sizes, frames, inv_volume_sum))
     return (counts=counts, group_sizes=sizes[1:n_groups], frames=frames[], inv_volume_sum=inv_volume_sum[])
+end
+
+# Mean-squared displacement and velocity autocorrelation (include/emdee_hip.h; undivided boxes).
+# int32_t emdee_md_set_msd(emdee_md *md, int32_t what, int32_t n_groups, const int32_t *group_dev, int32_t n_lags,
+#                          int32_t origin_every);
+# what: EMDEE_MSD | EMDEE_VACF.  groups: a device Int32 vector in caller order, or `nothing` (every atom in group 0); a group of -1
+# leaves the atom out.  n_lags in 1...4096, at most 64 origins within them; n_lags = 0 clears the table.
+const EMDEE_MSD = 1
+const EMDEE_VACF = 2
+const EMDEE_MSD_WORDS = 7
+function set_msd!(md::VelocityVerlet, n_lags; origin_every=1, n_groups=1, groups::Union{Nothing,HipArray{Int32,1}}=nothing,
+                  what=EMDEE_MSD | EMDEE_VACF)
+    check(ccall((:emdee_md_set_msd, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int32, Int32), md.handle,
+                Int32(what), Int32(n_groups), groups === nothing ? C_NULL : groups.ptr, Int32(n_lags), Int32(origin_every)))
+end
+
+# int32_t emdee_md_msd_sample(emdee_md *md);
+# the current state as the next sample: queued on the stream, nothing read back, the run untouched
+msd_sample!(md::VelocityVerlet) = check(ccall((:emdee_md_msd_sample, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_msd_reset(emdee_md *md);
+msd_reset!(md::VelocityVerlet) = check(ccall((:emdee_md_msd_reset, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_msd_read(emdee_md *md, double *sums, int64_t *origins, int64_t group_sizes[8], int64_t *samples);
+# blocking -> (sums (7 x n_groups x n_lags: word w of group g at lag l is sums[w + 1, g + 1, l + 1]), origins per lag, group sizes,
+# samples); MSD(l) = (w0 + w1 + w2) / (origins N_g), drift-free: minus (w3 + w4 + w5) / N_g first; VACF(l) = w6 / (origins N_g)
+function msd_read(md::VelocityVerlet, n_lags, n_groups)
+    sums = zeros(Float64, EMDEE_MSD_WORDS, n_groups, n_lags)
+    origins = zeros(Int64, n_lags)
+    sizes = zeros(Int64, RDF_MAX_GROUPS)
+    samples = Ref{Int64}(0)
+    check(ccall((:emdee_md_msd_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), md.handle,
+                sums, origins, sizes, samples))
+    return (sums=sums, origins=origins, group_sizes=sizes[1:n_groups], samples=samples[])
 end
 
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);

@@ -27,6 +27,9 @@ THERMOSTAT_WORDS, THERMOSTAT_CHAIN_MAX = 20, 8
 _THERMOSTATS = {"off": THERMOSTAT_OFF, "v-rescale": THERMOSTAT_VRESCALE, "vrescale": THERMOSTAT_VRESCALE,
                 "nose-hoover": THERMOSTAT_NOSE_HOOVER, "nosehoover": THERMOSTAT_NOSE_HOOVER}
 
+# mean-squared displacement and velocity autocorrelation (include/emdee_hip.h: emdee_md_set_msd)
+MSD, VACF, MSD_WORDS = 1, 2, 7
+
 
 def _three(v):
     """a scalar or three numbers as three floats"""
@@ -74,7 +77,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the three launches of every event of a global thermostat (set_thermostat_)
            "thermostat": 14,
            # the four stages of every sample of the radial distribution functions (rdf_sample_)
-           "rdf": 15}
+           "rdf": 15,
+           # the three launches of every sample of the displacement and velocity correlations (msd_sample_)
+           "msd": 16}
 
 
 class MinimizeResult:
@@ -433,6 +438,60 @@ class VelocityVerlet:
                 coordination[s] = (2.0 if a == b else 1.0) * np.cumsum(counts[s]) / (float(sizes[a]) * frames.value)
         return dict(r=0.5 * (edges[1:] + edges[:-1]), edges=edges, pairs=pairs, counts=counts, group_sizes=sizes,
                     frames=int(frames.value), inv_volume_sum=float(ivs.value), g=g, coordination=coordination)
+
+    # -- mean-squared displacement and velocity autocorrelation (include/emdee_hip.h: emdee_md_set_msd; undivided boxes)
+    _msd = None                                            # (n_lags, n_groups) of the table in force
+
+    def set_msd_(self, n_lags, origin_every=1, groups=None, n_groups=None, msd=True, vacf=True):
+        """The table msd_sample_() fills: lags 0 ... n_lags - 1 (in samples), every origin_every-th sample an origin (at most 64
+        origins within n_lags).  groups: None (every atom in one group) or one integer per owned atom, -1 to leave the atom out
+        (n_groups: how many groups there are, 1...8; None: the largest entry of groups + 1).  msd / vacf: which of the two to
+        keep (positions and velocities are stored only for the one that needs them).  n_lags = 0 clears the table.  Zeroes the
+        sums and restarts the sample counter."""
+        g = torch.as_tensor(groups).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous() if groups is not None else None
+        if g is not None and g.shape[0] != self.n_owned:
+            raise ValueError("set_msd_: groups holds %d entries, the state %d owned atoms" % (g.shape[0], self.n_owned))
+        if n_groups is None:
+            n_groups = 1 if g is None or g.numel() == 0 else max(int(g.max().item()) + 1, 1)
+        n_groups = int(n_groups)
+        what = (MSD if msd else 0) | (VACF if vacf else 0)
+        _lib.call("emdee_md_set_msd", self._handle, what, n_groups, C.c_void_p(g.data_ptr()) if g is not None else None,
+                  int(n_lags), int(origin_every))
+        self._msd = (int(n_lags), n_groups) if int(n_lags) != 0 else None
+
+    def msd_sample_(self):
+        """Takes the current state as the next sample: an origin when its number is a multiple of origin_every, and correlated
+        with every origin within n_lags.  Queued on the stream, nothing read back, the run untouched."""
+        _lib.call("emdee_md_msd_sample", self._handle)
+
+    def msd_reset_(self):
+        """Zeroes the sums, restarts the sample counter at 0 and takes the current box and state as the ones the origins belong to."""
+        _lib.call("emdee_md_msd_reset", self._handle)
+
+    def msd(self):
+        """The accumulated sums and what follows from them, as a dict (blocking): lags (0 ... n_lags - 1, in samples), origins
+        (per lag: how many origins have contributed), group_sizes, samples, sums ((n_lags, n_groups, 7) float64 numpy: the raw
+        words of emdee_md_msd_read), msd ((n_lags, n_groups, 4): per axis and total, sums / (origins N_g)), msd_drift_free
+        ((n_lags, n_groups): the total with the group's mean displacement taken out, per origin) and vacf ((n_lags, n_groups):
+        <v(s) . v(0)> per atom).  NaN where origins N_g == 0."""
+        import numpy as np
+        if self._msd is None:
+            raise ValueError("msd: no table is set (set_msd_)")
+        n_lags, n_groups = self._msd
+        sums = np.zeros((n_lags, n_groups, MSD_WORDS), dtype=np.float64)
+        origins = np.zeros(n_lags, dtype=np.int64)
+        sizes, samples = (C.c_int64 * 8)(), C.c_int64()
+        _lib.call("emdee_md_msd_read", self._handle, sums.ctypes.data_as(C.c_void_p), origins.ctypes.data_as(C.c_void_p), sizes, C.byref(samples))
+        sizes = np.array([int(s) for s in sizes][:n_groups], dtype=np.int64)
+        count = origins[:, None].astype(np.float64) * sizes[None, :].astype(np.float64)
+        ng = sizes[None, :].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            per_axis = np.where(count[..., None] > 0, sums[..., 0:3] / count[..., None], np.nan)
+            total = np.where(count > 0, sums[..., 0:3].sum(axis=2) / count, np.nan)
+            drift_free = np.where(count > 0, (sums[..., 0:3].sum(axis=2) - sums[..., 3:6].sum(axis=2) / ng) / count, np.nan)
+            vacf = np.where(count > 0, sums[..., 6] / count, np.nan)
+        return dict(lags=np.arange(n_lags), origins=origins, group_sizes=[int(s) for s in sizes], samples=int(samples.value), sums=sums,
+                    msd=np.concatenate([per_axis, total[..., None]], axis=2), msd_drift_free=drift_free, vacf=vacf)
 
     def set_molecular_scaling_(self, on=True):
         """Molecular scaling (include/emdee_hip.h emdee_md_set_molecular_scaling): with it on, an engine with rigid molecules

@@ -676,7 +676,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds); 12 = what emdee_md_minimize adds to the
  * stages of its steps (the constrained force, the reduction, the mixing); 13 = placement and force spreading of an engine with
  * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat);
- * 15 = the four stages of every sample of the radial distribution functions (emdee_md_rdf_sample).
+ * 15 = the four stages of every sample of the radial distribution functions (emdee_md_rdf_sample);
+ * 16 = the three launches of every sample of the displacement and velocity correlations (emdee_md_msd_sample).
  * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
@@ -848,6 +849,56 @@ int32_t emdee_md_set_rdf(emdee_md *md, double r_max, int32_t n_bins, int32_t n_g
 int32_t emdee_md_rdf_sample(emdee_md *md);
 int32_t emdee_md_rdf_read(emdee_md *md, int64_t *counts, int64_t group_sizes[8], int64_t *frames, double *inv_volume_sum);
 int32_t emdee_md_rdf_reset(emdee_md *md);
+
+/* Mean-squared displacement and velocity autocorrelation (build-defined: the reference has no analysis of the dynamics).  The
+ * engine keeps a ring of snapshots of the grouped atoms -- unwrapped coordinates and velocities, as doubles -- in device memory and
+ * correlates every sample with the origins still within reach, so that a diffusion coefficient (the Einstein slope of the MSD, the
+ * Green-Kubo integral of the VACF) costs no copy of the state to the host and no bookkeeping of time origins there.
+ *
+ * emdee_md_set_msd(what, n_groups, group_dev, n_lags, origin_every) sets the table (blocking; n_lags = 0 clears it):
+ *   what: a non-empty mask of EMDEE_MSD | EMDEE_VACF.  Without EMDEE_MSD no positions are stored and words 0-5 stay exactly 0;
+ *   without EMDEE_VACF no velocities are stored and word 6 stays exactly 0.
+ *   n_groups in 1...8.  group_dev: n_owned int32 in caller order on the device, each in -1...n_groups-1; -1 leaves the atom out;
+ *   NULL with n_groups == 1 puts every atom in group 0.  The array is copied, the group sizes are counted; an empty group is legal.
+ *   n_lags in 1...4096, origin_every >= 1; the ring holds n_origins = ceil(n_lags / origin_every) <= 64 snapshots and one more as
+ *   scratch: (n_origins + 1) n_grouped 24 bytes (one of the two) or 48 bytes (both) of device memory.  Setting a table zeroes the sums.
+ *   - All or nothing: EMDEE_ERR_INVALID, the previous table in force, for arguments outside these limits; for a group value out of
+ *     range the text names the first offending atom.  A failed allocation (EMDEE_ERR_ALLOC) leaves the previous table in force too.
+ *   - EMDEE_ERR_STATE, each with its own text: before emdee_md_set_state, on an integrator lent by emdee_dd_engine, on one with
+ *     ghosts.  Open axes are fine: their image count is 0.
+ *
+ * emdee_md_msd_sample takes the current state as sample s = 0, 1, ... (counted from the last set or reset; what the interval
+ * between two samples is, is the caller's: step(n); msd_sample()).  When s % origin_every == 0, sample s becomes an origin in ring
+ * slot (s / origin_every) % n_origins.  Then, for every origin o taken at s_o <= s with lag l = s - s_o < n_lags (the one just
+ * written included, l = 0) and every group g, with d_i = x_i(s) - x_i(s_o) on the unwrapped coordinates emdee_md_get_state returns,
+ * seven words are added to sums[(l n_groups + g) 7 + w]:
+ *   w = 0, 1, 2: sum_i d_ix^2, d_iy^2, d_iz^2;   w = 3, 4, 5: (sum_i d_ix)^2, (sum_i d_iy)^2, (sum_i d_iz)^2, the group's drift, squared
+ *   per origin;   w = 6: sum_i v_i(s) . v_i(s_o).
+ * With origins[l] the number of origins that have contributed to lag l: MSD(l) = (w0 + w1 + w2) / (origins N_g), the drift-free
+ * MSD = (w0 + w1 + w2 - (w3 + w4 + w5) / N_g) / (origins N_g), VACF(l) = w6 / (origins N_g).  fp64 throughout in both precisions:
+ * an fp64 engine's snapshot is bit for bit what emdee_md_get_state returns; a Float32 engine's is the record plus the origin of
+ * its cell plus the box lengths removed, in double, unrounded.  Sums in a fixed order that depends on the table alone (chunks of
+ * 1024 atoms of one group, never the device's CU count), no floating-point atomics: bitwise reproducible.  The work is queued on the
+ * engine's stream, nothing is read back, and it writes only buffers of its own: an engine that samples and one that does not stay
+ * bit for bit equal.  Its device time is emdee_md_kernel_time index 16.
+ *   - EMDEE_ERR_STATE, nothing changed: no table is set; the table was set for another number of owned atoms; emdee_md_set_state
+ *     has replaced the state since the last set or reset; the box lengths differ from those at the last set or reset
+ *     (emdee_md_scale_box, a barostat): unwrapped coordinates across a rescaled box are not a displacement -- emdee_md_msd_reset
+ *     starts again.
+ * Sampling on a cadence inside emdee_md_step is not offered, as for the radial distribution functions.
+ *
+ * emdee_md_msd_read (blocking; any pointer may be NULL): the n_lags n_groups EMDEE_MSD_WORDS sums, origins[n_lags] and samples
+ * (both kept on the host, functions of s alone) and the eight group sizes.  emdee_md_msd_reset zeroes the sums and origins,
+ * restarts s at 0 and records the current box and state.
+ * Scope: undivided boxes; no emdee_dd_* counterpart. */
+#define EMDEE_MSD        1
+#define EMDEE_VACF       2
+#define EMDEE_MSD_WORDS  7
+int32_t emdee_md_set_msd(emdee_md *md, int32_t what, int32_t n_groups, const int32_t *group_dev, int32_t n_lags,
+                         int32_t origin_every);
+int32_t emdee_md_msd_sample(emdee_md *md);
+int32_t emdee_md_msd_read(emdee_md *md, double *sums, int64_t *origins, int64_t group_sizes[8], int64_t *samples);
+int32_t emdee_md_msd_reset(emdee_md *md);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
