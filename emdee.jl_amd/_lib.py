@@ -121,6 +121,10 @@ SIGNATURES = {
     "emdee_md_msd_sample": [_p],
     "emdee_md_msd_read": [_p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "emdee_md_msd_reset": [_p],
+    "emdee_md_set_gk": [_p, _i32, _i32],
+    "emdee_md_gk_sample": [_p],
+    "emdee_md_gk_read": [_p, _p, _p, _p, C.POINTER(_i64)],
+    "emdee_md_gk_reset": [_p],
     "emdee_dd_unique_id": [_p],
     "emdee_dd_rccl_selftest": [_p, _i32],
     "emdee_dd_describe": [_d3, _i3, _dbl, _i32, C.POINTER(_i32), _p, _p, _p, C.POINTER(_i32), _p, _d3, _d3, _i3],

@@ -514,6 +514,18 @@ int32_t emdee_md_msd_read(emdee_md *md, double *sums, int64_t *origins, int64_t 
 int32_t emdee_md_msd_reset(emdee_md *md) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->msd_reset(); });
 }
+int32_t emdee_md_set_gk(emdee_md *md, int32_t what, int32_t n_lags) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_gk(what, n_lags); });
+}
+int32_t emdee_md_gk_sample(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->gk_sample(); });
+}
+int32_t emdee_md_gk_read(emdee_md *md, double *sums, double totals[9], double last[9], int64_t *samples) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->gk_read(sums, totals, last, samples); });
+}
+int32_t emdee_md_gk_reset(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->gk_reset(); });
+}
 
 // ---------------------------------------------------------------- domain decomposition
 int32_t emdee_dd_unique_id(uint8_t out[128]) {

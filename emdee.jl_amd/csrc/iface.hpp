@@ -79,6 +79,10 @@ struct IMd {
     virtual void msd_sample() = 0;
     virtual void msd_read(double *sums, int64_t *origins, int64_t *group_sizes, int64_t *samples) = 0;
     virtual void msd_reset() = 0;
+    virtual void set_gk(int32_t what, int32_t n_lags) = 0;
+    virtual void gk_sample() = 0;
+    virtual void gk_read(double *sums, double *totals, double *last, int64_t *samples) = 0;
+    virtual void gk_reset() = 0;
 };
 
 // spatial domain decomposition (emdee_dd_*): the domains of the decomposition that live in this process

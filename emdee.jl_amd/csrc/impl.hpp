@@ -739,6 +739,110 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_reset: no table is set (call emdee_md_set_msd first)");
         zero_msd();
     }
+    // ---- Green-Kubo observables: the stress and heat-flux autocorrelations (include/emdee_hip.h: emdee_md_set_gk; gk.hpp)
+    struct GkTable {
+        bool present = false;
+        int what = 0, n_atoms = 0, n_lags = 0;
+        int64_t samples = 0;                                 // s of the next sample
+        double len[3] = {0, 0, 0};                           // the box at the last set or reset: S and J are extensive, one V per run
+        uint64_t serial = 0;                                 // ... and the state serial
+    } gk;
+    void zero_gk() {
+        if (gk.present) {
+            EMDEE_HIP_CHECK(hipMemsetAsync(sys.gk.ring.ptr, 0, (size_t)gk.n_lags * GK_WORDS * sizeof(double), sys.stream()));
+            EMDEE_HIP_CHECK(hipMemsetAsync(sys.gk.acc.ptr, 0, sys.gk_acc_words(gk.n_lags) * sizeof(double), sys.stream()));
+        }
+        gk.samples = 0;
+        for (int d = 0; d < 3; d++) gk.len[d] = sys.len[d];
+        gk.serial = state_serial;
+    }
+    // what the engine must be for a table with this mask, at set and again at every sample (a table may be attached later)
+    void require_gk(const char *fn, int what) const {
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s: this integrator is a domain's, lent by emdee_dd_engine: it sees a part of the box only", fn);
+        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "%s: an integrator with ghosts (its box is a domain of a larger one)", fn);
+        EMDEE_REQUIRE(sys.sorted && !sys.id_gaps, EMDEE_ERR_STATE, "%s: no state loaded (call emdee_md_set_state first)", fn);
+        EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "%s: the engine holds an hbonds table (emdee_md_set_hbonds): neither the atomic nor the "
+                      "molecular stress holds the clusters' constraint virial; clear the table first", fn);
+        if (!(what & GK_HEAT)) return;
+        // (the per-atom energies and tensors are the half-pair split of the neighbour rows' terms only)
+        const bool pme = sys.has_ewald() && sys.ewald.pme.on();
+        const struct { bool on; const char *text; } other[] = {
+            {sys.has_excl(), "excluded pairs (emdee_md_set_exclusions)"},
+            {sys.has_14(), "scaled 1-4 pairs (emdee_md_set_pairs14)"},
+            {sys.has_bonded(), "bonded terms (emdee_md_set_bonded)"},
+            {sys.has_rigid(), "rigid molecules (emdee_md_set_rigid3)"},
+            {sys.has_vsites(), "virtual sites (emdee_md_set_vsites)"},
+            {pme, "particle-mesh Ewald (emdee_md_set_pme)"},
+            {sys.has_ewald() && !pme, "Ewald summation (emdee_md_set_ewald)"}};
+        std::string all;                                     // (every table in the way, so that one refusal says what to clear)
+        for (const auto &o : other)
+            if (o.on) all += (all.empty() ? "" : ", ") + std::string(o.text);
+        EMDEE_REQUIRE(all.empty(), EMDEE_ERR_STATE, "%s: EMDEE_GK_HEAT on an engine with %s: the heat flux is written for forces that are all "
+                      "pair terms of the neighbour rows, whose per-atom tensors are the half-pair split", fn, all.c_str());
+    }
+    // all or nothing: every refusal, a failed allocation included, comes before the table in force changes; blocking
+    void set_gk(int32_t what, int32_t n_lags) override {
+        use_device(sys.ctx);
+        if (n_lags == 0) { gk = GkTable{}; return; }
+        EMDEE_REQUIRE(what >= 1 && what <= (GK_STRESS | GK_HEAT), EMDEE_ERR_INVALID, "set_gk: what = %d is not a non-empty mask of "
+                      "EMDEE_GK_STRESS | EMDEE_GK_HEAT", what);
+        EMDEE_REQUIRE(n_lags >= 1 && n_lags <= GK_MAX_LAGS, EMDEE_ERR_INVALID, "set_gk: n_lags = %d is outside 1...%d (0 clears the table)", n_lags, GK_MAX_LAGS);
+        require_gk("set_gk", what);
+        // (buffers of their own: a failed allocation throws here and leaves the table in force and its sums as they are)
+        typename NbSystem<real>::GkDev dev;
+        dev.ring.ensure((size_t)n_lags * GK_WORDS);
+        dev.acc.ensure(sys.gk_acc_words(n_lags));
+        dev.heat.ensure((size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS + GK_HEAT_WORDS);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));   // (the old ring is idle)
+        // ---- commit
+        sys.gk.swap(dev);
+        gk = GkTable{};
+        gk.present = true; gk.what = what; gk.n_atoms = sys.n_owned; gk.n_lags = n_lags;
+        zero_gk();
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+    }
+    // one sample: the forces (a rigid engine) and the tensor pass if they are not current, as the pressure entries evaluate them, then
+    // the sample's own launches; queued on the stream, nothing read back.  A refusal changes nothing.
+    void gk_sample() override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(gk.present, EMDEE_ERR_STATE, "gk_sample: no table is set (call emdee_md_set_gk first)");
+        require_gk("gk_sample", gk.what);
+        EMDEE_REQUIRE(gk.n_atoms == sys.n_owned, EMDEE_ERR_STATE, "gk_sample: the table was set for %d atoms, the state holds %d: set it again "
+                      "(emdee_md_set_gk)", gk.n_atoms, sys.n_owned);
+        EMDEE_REQUIRE(gk.serial == state_serial, EMDEE_ERR_STATE, "gk_sample: the state has been replaced (emdee_md_set_state) since the first "
+                      "sample: a correlation between two states means nothing; start again with emdee_md_gk_reset");
+        EMDEE_REQUIRE(gk.len[0] == sys.len[0] && gk.len[1] == sys.len[1] && gk.len[2] == sys.len[2], EMDEE_ERR_STATE, "gk_sample: the box has been "
+                      "rescaled (emdee_md_scale_box or a barostat) since the first sample: the stress and the heat flux are extensive and the "
+                      "Green-Kubo prefactor assumes one volume; start again with emdee_md_gk_reset");
+        EMDEE_REQUIRE(!sys.charges_stale(), EMDEE_ERR_STATE, "gk_sample: charges set for %lld atoms, the state holds %d: set them again or clear "
+                      "them (emdee_md_set_coulomb)", (long long)sys.tables->q_n, sys.n_owned);
+        const bool molecular = sys.has_rigid() && sys.tables->rigid.n > 0;
+        if (sys.has_rigid()) {
+            require_fitting("gk_sample", sys.RIGID);
+            if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
+        }
+        tensor_pass();
+        sys.gk_sample(gk.what, gk.n_lags, gk.samples, molecular);
+        EMDEE_HIP_CHECK(hipGetLastError());
+        gk.samples++;
+    }
+    // blocking; any pointer may be NULL.  The deferred fault word of the bonded terms is checked here, not in the sample.
+    void gk_read(double *sums, double *totals, double *last, int64_t *samples) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(gk.present, EMDEE_ERR_STATE, "gk_read: no table is set (call emdee_md_set_gk first)");
+        sys.check_bonded();
+        const size_t n = (size_t)gk.n_lags * GK_WORDS;
+        if (sums) EMDEE_HIP_CHECK(hipMemcpyAsync(sums, sys.gk.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        if (totals) EMDEE_HIP_CHECK(hipMemcpyAsync(totals, sys.gk.acc.ptr + n, GK_WORDS * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        if (last) EMDEE_HIP_CHECK(hipMemcpyAsync(last, sys.gk.acc.ptr + n + GK_WORDS, GK_WORDS * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        if (samples) *samples = gk.samples;
+    }
+    void gk_reset() override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(gk.present, EMDEE_ERR_STATE, "gk_reset: no table is set (call emdee_md_set_gk first)");
+        zero_gk();
+    }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
     void couple(double dt) {
@@ -981,12 +1085,13 @@ struct MdImpl : IMd {
         // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps; 13: placement and
         // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat; 15: the four
         // stages of every sample of the radial distribution functions (emdee_md_rdf_sample); 16: the three launches of every sample
-        // of the displacement and velocity correlations (emdee_md_msd_sample)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 16, EMDEE_ERR_INVALID, "kernel id out of range");
+        // of the displacement and velocity correlations (emdee_md_msd_sample); 17: the launches every sample of the Green-Kubo
+        // observables adds to the tensor pass (emdee_md_gk_sample)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 17, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[17][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[18][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}, {T_GK, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {

@@ -10,6 +10,7 @@
 
 #include "brick.hpp"
 #include "ewald.hpp"
+#include "gk.hpp"
 #include "kernels.hpp"
 #include "minimize.hpp"
 #include "msd.hpp"
@@ -50,8 +51,9 @@ static inline void refuse_experiment_switches() {
 // T_THERMOSTAT: the three launches of a global thermostat's event (thermostat.hpp)
 // T_RDF: the four stages of a sample of the radial distribution functions (rdf.hpp): count, scan, fill, pair loop
 // T_MSD: the three launches of a sample of the displacement and velocity correlations (msd.hpp): gather, accumulate, finish
+// T_GK: the launches a sample of the Green-Kubo observables adds to the tensor pass (gk.hpp): the box sums, the heat sums, push, correlate
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_COUNT = 16 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_GK = 16, T_COUNT = 17 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -1685,14 +1687,24 @@ struct NbSystem {
     // out[0..5] = sum of the owned atoms' virial tensors (the last tensor pass), out[6..11] = kinetic tensor sum m v^a v^b;
     // (xx, yy, zz, xy, xz, yz), fp64, blocking
     DevBuf<double> tpartial;
-    // queues the atomic sums; they land behind the partials, where a second total has room next to them
-    double *queue_tensor_sums() {
+    // a launch, timed under `timer` when that is a TimerId and not -1
+    template <class Launch>
+    void timed_if(int timer, Launch &&launch) {
+        if (timer < 0) { launch(); return; }
+        Timed t(this, timer);
+        launch();
+    }
+    // queues the atomic sums; they land behind the partials, where a second total has room next to them.  timer >= 0: each of the
+    // two launches is timed under it (a sample of the Green-Kubo observables counts them as its own)
+    double *queue_tensor_sums(int timer = -1) {
         const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
         tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);
         double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
-        hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
-                           vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
-        hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot);
+        timed_if(timer, [&] {
+            hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
+                               vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
+        });
+        timed_if(timer, [&] { hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot); });
         return tot;
     }
     void tensor_sums(double out[TENSOR_SUMS]) {
@@ -1703,24 +1715,75 @@ struct NbSystem {
     // out[0..5] = W_mol, out[6..11] = K_mol (include/emdee_hip.h: emdee_md_molecular_pressure_tensor): the atomic sums above minus
     // what the atoms of the rigid molecules carry about their centres of mass (k_molecule_partials over the table, with the
     // current force planes).  The partial sums of the two passes share their buffer (the stream orders them), the two totals lie
-    // side by side and come back in one copy; the subtraction is the host's.  Blocking.
-    void molecular_tensor_sums(double out[TENSOR_SUMS]) {
-        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
-        if (n_total == 0) return;
-        const int n_mol = has_rigid() ? tables->rigid.n : 0;
-        if (n_mol == 0) { tensor_sums(out); return; }
-        double *tot = queue_tensor_sums();
+    // side by side.  The queueing half: both[0..11] the atomic sums, both[12..23] the molecules'; the difference both[q] -
+    // both[12 + q] is the reader's (n_total > 0 and a rigid table with molecules in it are the caller's to check).
+    double *queue_molecular_tensor_sums(int timer = -1) {
+        const int n_mol = tables->rigid.n;
+        double *tot = queue_tensor_sums(timer);
         const int nb = std::min((int)blocks_for(n_mol, RED_BLOCK), RED_MAX_BLOCKS);
         {
             Timed t(this, T_MOLECULAR);
             hipLaunchKernelGGL((k_molecule_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), settle_args(), (const real *)frc.ptr,
                                tpartial.ptr);
         }
-        hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot + TENSOR_SUMS);
+        timed_if(timer, [&] {
+            hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot + TENSOR_SUMS);
+        });
+        return tot;
+    }
+    // the read-back half: one copy of both totals, the subtraction on the host.  Blocking.
+    void molecular_tensor_sums(double out[TENSOR_SUMS]) {
+        for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
+        if (n_total == 0) return;
+        const int n_mol = has_rigid() ? tables->rigid.n : 0;
+        if (n_mol == 0) { tensor_sums(out); return; }
         double both[2 * TENSOR_SUMS];
-        read_back_doubles(both, tot, 2 * TENSOR_SUMS);
+        read_back_doubles(both, queue_molecular_tensor_sums(), 2 * TENSOR_SUMS);
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = both[q] - both[TENSOR_SUMS + q];
     }
+
+    // ---------------------------------------------------------------- Green-Kubo observables (gk.hpp; MdImpl::set_gk / gk_sample drive these)
+    // The ring of samples (n_lags x 9), the lag sums with the totals and the last sample behind them (acc), the block partials and
+    // the three totals of the heat flux.  A sample reads the outputs of the tensor pass, perm, the velocities and the masses; it
+    // writes these buffers and the scratch of the box sums (tpartial), nothing else of the engine's.
+    struct GkDev {
+        DevBuf<double> ring, acc, heat;
+        void swap(GkDev &o) { ring.swap(o.ring); acc.swap(o.acc); heat.swap(o.heat); }
+    } gk;
+    static size_t gk_acc_words(int n_lags) { return (size_t)n_lags * GK_WORDS + 2 * GK_WORDS; }
+    // sample s of a table with n_lags lags: queued on the stream, nothing read back.  Behind a current tensor pass (and, with
+    // `molecular`, current forces).  GK_STRESS: the box sums of the pressure entry (two launches, a third with `molecular`, whose
+    // molecule pass is T_MOLECULAR's); GK_HEAT: the heat partials and their finish (two); then the push and the correlator (two).
+    void gk_sample(int what, int n_lags, long long s, bool molecular) {
+        const double *box = nullptr, *heat = nullptr;
+        if ((what & GK_STRESS) && n_total > 0) box = molecular ? queue_molecular_tensor_sums(T_GK) : queue_tensor_sums(T_GK);
+        if ((what & GK_HEAT) && n_total > 0) {
+            const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+            double *tot = gk.heat.ptr + (size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS;
+            {
+                Timed t(this, T_GK);
+                hipLaunchKernelGGL((k_gk_heat_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch,
+                                   (const int *)perm.ptr, (const real *)en.ptr, (const real *)vt.ptr, (const real *)vel.ptr,
+                                   with_mass ? (const real *)im.ptr : nullptr, gk.heat.ptr);
+            }
+            {
+                Timed t(this, T_GK);
+                hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, GK_HEAT_WORDS, (const double *)gk.heat.ptr, tot);
+            }
+            heat = tot;
+        }
+        GkArgs a{};
+        a.what = what; a.n_lags = n_lags; a.molecular = molecular ? 1 : 0; a.s = s; a.ring = gk.ring.ptr; a.acc = gk.acc.ptr;
+        {
+            Timed t(this, T_GK);
+            hipLaunchKernelGGL(k_gk_push, dim3(1), dim3(WAVE), 0, stream(), a, box, heat);
+        }
+        {
+            Timed t(this, T_GK);
+            hipLaunchKernelGGL(k_gk_correlate, dim3(blocks_for(gk_live_lags(s, n_lags), GK_BLOCK)), dim3(GK_BLOCK), 0, stream(), a);
+        }
+    }
+
     // caller-order copy of the last tensor pass's per-atom tensors (owned atoms, 6 x n_owned)
     void unsort_tensor(real *out) {
         if (n_total == 0) return;

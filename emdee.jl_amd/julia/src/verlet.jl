@@ -5,6 +5,7 @@ export box, scale_box!, set_barostat!
 export set_thermostat!, thermostat_state, set_thermostat_state!, thermostat_draws
 export set_rdf!, rdf_sample!, rdf_reset!, rdf_read
 export set_msd!, msd_sample!, msd_reset!, msd_read
+export set_gk!, gk_sample!, gk_reset!, gk_read
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -263,6 +264,36 @@ function msd_read(md::VelocityVerlet, n_lags, n_groups)
     check(ccall((:emdee_md_msd_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), md.handle,
                 sums, origins, sizes, samples))
     return (sums=sums, origins=origins, group_sizes=sizes[1:n_groups], samples=samples[])
+end
+
+# Green-Kubo observables: the autocorrelations of the stress and of the heat flux (include/emdee_hip.h; undivided engines).
+# int32_t emdee_md_set_gk(emdee_md *md, int32_t what, int32_t n_lags);
+# what: EMDEE_GK_STRESS | EMDEE_GK_HEAT.  n_lags in 1...65536; n_lags = 0 clears the table.
+const EMDEE_GK_STRESS = 1
+const EMDEE_GK_HEAT = 2
+const EMDEE_GK_WORDS = 9
+function set_gk!(md::VelocityVerlet, n_lags; what=EMDEE_GK_STRESS | EMDEE_GK_HEAT)
+    check(ccall((:emdee_md_set_gk, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Int32), md.handle, Int32(what), Int32(n_lags)))
+end
+
+# int32_t emdee_md_gk_sample(emdee_md *md);
+# the current state as the next sample: queued on the stream, nothing read back, the run untouched
+gk_sample!(md::VelocityVerlet) = check(ccall((:emdee_md_gk_sample, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_gk_reset(emdee_md *md);
+gk_reset!(md::VelocityVerlet) = check(ccall((:emdee_md_gk_reset, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_gk_read(emdee_md *md, double *sums, double totals[9], double last[9], int64_t *samples);
+# blocking -> (sums (9 x n_lags: word w at lag l is sums[w + 1, l + 1], behind it max(0, samples - l) products), totals, last, samples);
+# words 0-4: the traceless stress components, 5: p V, 6-8: the heat flux
+function gk_read(md::VelocityVerlet, n_lags)
+    sums = zeros(Float64, EMDEE_GK_WORDS, n_lags)
+    totals = zeros(Float64, EMDEE_GK_WORDS)
+    last = zeros(Float64, EMDEE_GK_WORDS)
+    samples = Ref{Int64}(0)
+    check(ccall((:emdee_md_gk_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}), md.handle,
+                sums, totals, last, samples))
+    return (sums=sums, totals=totals, last=last, samples=samples[])
 end
 
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);

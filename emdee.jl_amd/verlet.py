@@ -29,6 +29,8 @@ _THERMOSTATS = {"off": THERMOSTAT_OFF, "v-rescale": THERMOSTAT_VRESCALE, "vresca
 
 # mean-squared displacement and velocity autocorrelation (include/emdee_hip.h: emdee_md_set_msd)
 MSD, VACF, MSD_WORDS = 1, 2, 7
+# Green-Kubo observables (include/emdee_hip.h: emdee_md_set_gk)
+GK_STRESS, GK_HEAT, GK_WORDS = 1, 2, 9
 
 
 def _three(v):
@@ -79,7 +81,10 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the four stages of every sample of the radial distribution functions (rdf_sample_)
            "rdf": 15,
            # the three launches of every sample of the displacement and velocity correlations (msd_sample_)
-           "msd": 16}
+           "msd": 16,
+           # the launches every sample of the Green-Kubo observables adds to the tensor pass (gk_sample_): 4 per mask bit alone
+           # (5 for the stress of an engine with rigid molecules), 6 with both
+           "green_kubo": 17}
 
 
 class MinimizeResult:
@@ -492,6 +497,68 @@ class VelocityVerlet:
             vacf = np.where(count > 0, sums[..., 6] / count, np.nan)
         return dict(lags=np.arange(n_lags), origins=origins, group_sizes=[int(s) for s in sizes], samples=int(samples.value), sums=sums,
                     msd=np.concatenate([per_axis, total[..., None]], axis=2), msd_drift_free=drift_free, vacf=vacf)
+
+    # -- Green-Kubo observables: stress and heat-flux autocorrelations (include/emdee_hip.h: emdee_md_set_gk; undivided engines)
+    _gk = None                                             # n_lags of the table in force
+
+    def set_green_kubo_(self, n_lags, stress=True, heat=True):
+        """The table gk_sample_() fills: lags 0 ... n_lags - 1 (in samples, at most 65536), every sample an origin.  stress:
+        words 0-4, the five independent traceless components of S = K + W (the molecular stress with set_rigid3_ in force), and
+        word 5, trace(S) / 3 = p V; heat: words 6-8, the heat flux J = sum (k + e) v + sum W . v, for engines whose forces are
+        all pair terms of the neighbour rows (Lennard-Jones, reaction-field charges).  n_lags = 0 clears the table.  Zeroes the
+        sums and restarts the sample counter."""
+        what = (GK_STRESS if stress else 0) | (GK_HEAT if heat else 0)
+        _lib.call("emdee_md_set_gk", self._handle, what, int(n_lags))
+        self._gk = int(n_lags) if int(n_lags) != 0 else None
+
+    def gk_sample_(self):
+        """Takes the current state as the next sample: its nine words go to the ring and are correlated with every sample
+        within n_lags.  Queued on the stream, nothing read back, the run untouched."""
+        _lib.call("emdee_md_gk_sample", self._handle)
+
+    def gk_reset_(self):
+        """Zeroes the sums, the totals and the ring, restarts the sample counter at 0 and takes the current box and state as
+        the ones the run belongs to."""
+        _lib.call("emdee_md_gk_reset", self._handle)
+
+    def green_kubo(self, dt_sample=None, temperature=None):
+        """The accumulated sums and what follows from them, as a dict (blocking): lags (0 ... n_lags - 1, in samples), counts
+        (per lag: the products behind it, max(0, samples - lag)), sums ((n_lags, 9) float64 numpy: the raw words of
+        emdee_md_gk_read), totals (9), last (9: the most recent sample), samples; stress_acf (the mean of words 0-4 over
+        counts: <P_ab(0) P_ab(t)> V^2 averaged over the five independent traceless components), pressure_acf (word 5 over
+        counts minus (totals[5] / samples)^2: the fluctuation of p V; the mean is taken over all samples and not over the
+        counts[l] pairs of lag l, so the estimate is biased by end effects of relative order l / samples), heat_acf (the mean
+        of words 6-8 over counts).  NaN where counts == 0.  With dt_sample (the time between two samples) and temperature (kT,
+        in energy units) both given, the trapezoid running integrals eta = int stress_acf / (V kT) and
+        lambda_ = int heat_acf / (V kT^2), V the current box."""
+        import numpy as np
+        if self._gk is None:
+            raise ValueError("green_kubo: no table is set (set_green_kubo_)")
+        n_lags = self._gk
+        sums = np.zeros((n_lags, GK_WORDS), dtype=np.float64)
+        totals, last, samples = np.zeros(GK_WORDS), np.zeros(GK_WORDS), C.c_int64()
+        _lib.call("emdee_md_gk_read", self._handle, sums.ctypes.data_as(C.c_void_p), totals.ctypes.data_as(C.c_void_p),
+                  last.ctypes.data_as(C.c_void_p), C.byref(samples))
+        n = int(samples.value)
+        lags = np.arange(n_lags)
+        counts = np.maximum(n - lags, 0).astype(np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = np.where(counts[:, None] > 0, sums / counts[:, None].astype(np.float64), np.nan)
+            stress_acf = mean[:, 0:5].mean(axis=1)
+            pressure_acf = mean[:, 5] - (totals[5] / n) ** 2 if n > 0 else np.full(n_lags, np.nan)
+            heat_acf = mean[:, 6:9].mean(axis=1)
+        out = dict(lags=lags, counts=counts, sums=sums, totals=totals, last=last, samples=n, stress_acf=stress_acf,
+                   pressure_acf=pressure_acf, heat_acf=heat_acf)
+        if dt_sample is not None and temperature is not None:
+            _, ln = self.box()
+            volume, kt = ln[0] * ln[1] * ln[2], float(temperature)
+
+            def running(acf):
+                steps = 0.5 * (acf[1:] + acf[:-1]) * float(dt_sample)
+                return np.concatenate([[0.0], np.cumsum(steps)])
+            out["eta"] = running(stress_acf) / (volume * kt)
+            out["lambda_"] = running(heat_acf) / (volume * kt * kt)
+        return out
 
     def set_molecular_scaling_(self, on=True):
         """Molecular scaling (include/emdee_hip.h emdee_md_set_molecular_scaling): with it on, an engine with rigid molecules

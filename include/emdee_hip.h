@@ -677,7 +677,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * stages of its steps (the constrained force, the reduction, the mixing); 13 = placement and force spreading of an engine with
  * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat);
  * 15 = the four stages of every sample of the radial distribution functions (emdee_md_rdf_sample);
- * 16 = the three launches of every sample of the displacement and velocity correlations (emdee_md_msd_sample).
+ * 16 = the three launches of every sample of the displacement and velocity correlations (emdee_md_msd_sample);
+ * 17 = the launches every sample of the Green-Kubo observables adds to the tensor pass (emdee_md_gk_sample).
  * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
@@ -899,6 +900,67 @@ int32_t emdee_md_set_msd(emdee_md *md, int32_t what, int32_t n_groups, const int
 int32_t emdee_md_msd_sample(emdee_md *md);
 int32_t emdee_md_msd_read(emdee_md *md, double *sums, int64_t *origins, int64_t group_sizes[8], int64_t *samples);
 int32_t emdee_md_msd_reset(emdee_md *md);
+
+/* Green-Kubo observables: the autocorrelations of the stress and of the heat flux (build-defined: the reference has no analysis of
+ * the dynamics).  The shear viscosity eta = V / (kT) int <P_ab(0) P_ab(t)> dt and the thermal conductivity
+ * lambda = 1 / (V kT^2) int <J_a(0) J_a(t)> dt need 10^5 - 10^6 samples of the box stress and of the heat flux; the engine holds
+ * everything both are made of -- the per-atom energies and virial tensors of the tensor pass, the full-step velocities, the
+ * fixed-order box sums -- so a sample costs no read-back: nine fp64 words go to a ring on the device and a correlator adds their
+ * products with the earlier samples to the lag sums.
+ *
+ * One sample = EMDEE_GK_WORDS = 9 words A_0 ... A_8, all energies (pressure x volume; no volume enters the sums):
+ *   EMDEE_GK_STRESS, words 0-5: with S_ab = K_ab + W_ab from the twelve sums of emdee_md_pressure_tensor -- the same numbers from the
+ *   same kernels, not read back -- A_0 = S_xy, A_1 = S_xz, A_2 = S_yz, A_3 = (S_xx - S_yy) / 2, A_4 = (S_yy - S_zz) / 2 (the five
+ *   independent traceless components, for eta) and A_5 = (S_xx + S_yy + S_zz) / 3 = p V (for the bulk viscosity).  On an engine with
+ *   a rigid table in force (emdee_md_set_rigid3) the twelve numbers of emdee_md_molecular_pressure_tensor take their place: the
+ *   atomic tensor lacks the constraint virial, the molecular one is the valid stress.
+ *   EMDEE_GK_HEAT, words 6-8: J = sum_i (k_i + e_i) v_i + sum_i W_i . v_i over the owned atoms, k_i = m_i v_i^2 / 2 (exactly 0 for
+ *   inv_mass = 0), e_i and W_i the per-atom energy and symmetric virial tensor of the tensor pass (emdee_md_virial_tensor), v_i the
+ *   velocities emdee_md_energies takes.  For pair forces this is the usual sum e_i v_i + 1/2 sum_{i != j} r_ij (f_ij . v_i).  The
+ *   partial-enthalpy correction a mixture's thermal conductivity needs is not applied: J is the energy flux, which is the heat
+ *   flux of a one-component fluid only.
+ *   A mask bit that is off leaves its words exactly 0 and runs none of its kernels.
+ *
+ * emdee_md_set_gk(what, n_lags) sets the table (blocking; n_lags = 0 clears it): what is a non-empty mask of EMDEE_GK_STRESS |
+ * EMDEE_GK_HEAT, n_lags in 1...65536.  The ring is n_lags x 9 doubles; setting a table zeroes the sums.
+ *   - All or nothing, the previous table and its sums in force: EMDEE_ERR_INVALID for a mask outside 1...3 or n_lags outside
+ *     0...65536; EMDEE_ERR_ALLOC for a failed allocation.
+ *   - EMDEE_ERR_STATE, each with its own text: before emdee_md_set_state; on an integrator lent by emdee_dd_engine; on one with
+ *     ghosts; with an hbonds table in force (emdee_md_set_hbonds), for any mask: neither stress holds the clusters' constraint virial.
+ *   - EMDEE_ERR_STATE for EMDEE_GK_HEAT on an engine whose forces are not all pair terms of the neighbour rows -- exclusions, 1-4
+ *     pairs, bonded terms, rigid molecules, virtual sites, Ewald summation or PME; the text names the setter of every one in the
+ *     way.  Their per-atom
+ *     tensors are not the half-pair split J is written for.  Lennard-Jones with or without reaction-field charges is accepted.
+ *
+ * emdee_md_gk_sample takes the current state as sample s = 0, 1, ... (counted from the last set or reset; what the interval between
+ * two samples is, is the caller's: step(n); gk_sample()).  The forces (a rigid engine) and the tensor pass are evaluated first if
+ * they are not current, as the pressure entries evaluate them.  A(s) goes to ring slot s % n_lags -- every sample is an origin --,
+ * A_w(s) is added to totals[w], and for every lag l = 0 ... min(s, n_lags - 1) the product A_w(s) A_w(s - l) is added to
+ * sums[l 9 + w].  The number of products behind lag l is max(0, samples - l).  Queued on the engine's stream, nothing read back; it
+ * writes buffers of its own and the outputs of the tensor pass only: an engine that samples and one that does not stay bit for bit
+ * equal.  Bitwise reproducible: the heat reduction has the shape of the box sums (a grid that depends on the atom count alone,
+ * never on the device's CU count), one thread per lag owns its nine sums, no floating-point atomics.  The deferred fault word of
+ * the bonded terms is checked in emdee_md_gk_read, not here.
+ * Device time: emdee_md_kernel_time index 17 covers the launches a sample adds, not the tensor pass (index 0 counts that):
+ * EMDEE_GK_STRESS alone 4 (the two of the box sums, the push, the correlator; 5 with a rigid table, whose molecule pass is index
+ * 10's), EMDEE_GK_HEAT alone 4 (the heat partials, their finish, the push, the correlator), both 6.
+ *   - EMDEE_ERR_STATE, nothing changed: no table is set; the conditions of emdee_md_set_gk no longer hold (a table attached
+ *     since); the table was set for another number of owned atoms; and, until emdee_md_gk_reset: emdee_md_set_state has replaced
+ *     the state since the last set or reset; the box lengths differ from those at the last set or reset (emdee_md_scale_box, a
+ *     barostat): S and J are extensive and the Green-Kubo prefactor assumes one V.
+ * Sampling on a cadence inside emdee_md_step is not offered, as for the radial distribution functions.
+ *
+ * emdee_md_gk_read (blocking; any pointer may be NULL): the n_lags x 9 sums, the nine totals, the most recent A (zeros before the
+ * first sample) and samples.  emdee_md_gk_reset zeroes the sums, the totals and the ring, restarts s at 0 and records the current
+ * box and state.
+ * Scope: undivided engines; no emdee_dd_* counterpart.  No cross-correlations between words; the sums are not restartable. */
+#define EMDEE_GK_STRESS  1
+#define EMDEE_GK_HEAT    2
+#define EMDEE_GK_WORDS   9
+int32_t emdee_md_set_gk(emdee_md *md, int32_t what, int32_t n_lags);
+int32_t emdee_md_gk_sample(emdee_md *md);
+int32_t emdee_md_gk_read(emdee_md *md, double *sums, double totals[9], double last[9], int64_t *samples);
+int32_t emdee_md_gk_reset(emdee_md *md);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
