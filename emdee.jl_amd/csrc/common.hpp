@@ -173,6 +173,8 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }   // (what this held is freed with o)
     ~DevBuf() { release(); }
     void release() {
         if (ptr) (void)hipFree(ptr);

@@ -541,30 +541,54 @@ struct MdImpl : IMd {
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.read_back_doubles(out, part, 2);
     }
-    // ---- radial distribution functions (include/emdee_hip.h: emdee_md_set_rdf; rdf.hpp)
-    struct RdfTable {
-        bool present = false, grouped = false, with_mol = false;
-        int n_atoms = 0, n_bins = 0, n_groups = 0;
-        double r_max = 0.0, inv_dr = 0.0;
-        int64_t sizes[RDF_MAX_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int64_t frames = 0;
-        double inv_volume_sum = 0.0;
-        int n_counters() const { return rdf_n_pairs(n_groups) * n_bins; }
-    } rdf;
-    double shortest_side() const { return std::min(sys.len[0], std::min(sys.len[1], sys.len[2])); }
-    void zero_rdf() {
-        if (rdf.present) EMDEE_HIP_CHECK(hipMemsetAsync(sys.rdf_counts.ptr, 0, (size_t)rdf.n_counters() * sizeof(unsigned long long), sys.stream()));
-        rdf.frames = 0;
-        rdf.inv_volume_sum = 0.0;
+    // ---- the observables (include/emdee_hip.h: emdee_md_set_rdf, emdee_md_set_msd, emdee_md_set_gk).  A table is one
+    // record, host fields and device buffers together, and the refusals the three share are formed once (observables.hpp).  Every
+    // setter is all or nothing and blocking: it builds a candidate record and queues its uploads, every refusal -- a failed
+    // allocation included -- comes before the table in force changes, and install() swaps the candidate in whole.  Clearing puts
+    // an empty record in.  A sample is queued on the stream, nothing read back; the engine's state, list and counters are not
+    // touched, and a refusal changes nothing.  A read is blocking, and any of its pointers may be NULL.
+    RdfRecord rdf;
+    MsdRecord msd;
+    GkRecord gk;
+    uint64_t state_serial = 0;                               // counts emdee_md_set_state: a snapshot of one state is no origin for another
+    ObsEngine obs_engine() const {
+        return ObsEngine{lent, sys.has_ghosts, sys.sorted, sys.id_gaps, sys.n_owned, n_ghost, {sys.len[0], sys.len[1], sys.len[2]}, state_serial};
     }
-    // all or nothing: every refusal comes before the table in force changes; blocking (the two arrays are checked on the host)
+    double shortest_side() const { return std::min(sys.len[0], std::min(sys.len[1], sys.len[2])); }
+    // behind the candidate's uploads (the caller's arrays and this call's are their own again, the table in force is idle)
+    template <class Record>
+    void install(Record &in_force, Record &candidate) {
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        in_force = std::move(candidate);
+        in_force.zero(sys.stream(), obs_engine());
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+    }
+    template <class Record>
+    void reset(ObsKind kind, Record &t) {
+        use_device(sys.ctx);
+        obs_require_present(kind, "reset", t);
+        t.zero(sys.stream(), obs_engine());
+    }
+    // a caller's array of one entry per owned atom, on the host
+    std::vector<int32_t> fetched(const int32_t *dev) {
+        std::vector<int32_t> host((size_t)sys.n_owned);
+        if (!host.empty()) EMDEE_HIP_CHECK(hipMemcpyAsync(host.data(), dev, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, sys.stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        return host;
+    }
+    // ... a setter's group array, checked; empty where the caller gave none
+    std::vector<int32_t> fetched_groups(ObsKind kind, const int32_t *dev, int n_groups) {
+        EMDEE_REQUIRE(dev || n_groups == 1, EMDEE_ERR_INVALID, "%s: groups is NULL with n_groups = %d (NULL puts every atom in group 0)", OBS_TEXT[kind].set, n_groups);
+        std::vector<int32_t> host = dev ? fetched(dev) : std::vector<int32_t>();
+        obs_check_groups(kind, host.data(), (int)host.size(), n_groups);
+        return host;
+    }
+    // ---- radial distribution functions (rdf.hpp)
     void set_rdf(double r_max, int32_t n_bins, int32_t n_groups, const int32_t *group_dev, const int32_t *molecule_dev) override {
         use_device(sys.ctx);
-        if (n_bins == 0) { rdf = RdfTable{}; return; }
-        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "set_rdf: this integrator is a domain's, lent by emdee_dd_engine: it sees a part of the box only");
-        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "set_rdf: an integrator with ghosts (its box is a domain of a larger one)");
+        if (n_bins == 0) { rdf = RdfRecord{}; return; }
+        obs_require_whole_box("set_rdf", obs_engine());
         EMDEE_REQUIRE(sys.per[0] && sys.per[1] && sys.per[2], EMDEE_ERR_STATE, "set_rdf: the box has an open axis; the minimum image needs three periodic ones");
-        EMDEE_REQUIRE(sys.sorted && !sys.id_gaps, EMDEE_ERR_STATE, "set_rdf: no state loaded (call emdee_md_set_state first)");
         EMDEE_REQUIRE(n_groups >= 1 && n_groups <= RDF_MAX_GROUPS, EMDEE_ERR_INVALID, "set_rdf: n_groups = %d is outside 1...%d", n_groups, RDF_MAX_GROUPS);
         EMDEE_REQUIRE(n_bins >= 1, EMDEE_ERR_INVALID, "set_rdf: n_bins = %d must be >= 1 (0 clears the table)", n_bins);
         EMDEE_REQUIRE((long long)rdf_n_pairs(n_groups) * n_bins <= RDF_MAX_COUNTERS, EMDEE_ERR_INVALID, "set_rdf: %d histograms of %d bins are %lld "
@@ -573,96 +597,52 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(std::isfinite(r_max) && r_max > 0.0, EMDEE_ERR_INVALID, "set_rdf: r_max must be finite and > 0");
         EMDEE_REQUIRE(r_max <= 0.5 * shortest_side(), EMDEE_ERR_INVALID, "set_rdf: r_max = %g exceeds half the shortest box side %g (minimum image)",
                       r_max, shortest_side());
-        EMDEE_REQUIRE(group_dev || n_groups == 1, EMDEE_ERR_INVALID, "set_rdf: groups is NULL with n_groups = %d (NULL puts every atom in group 0)", n_groups);
         const int n = sys.n_owned;
-        RdfTable t;
+        RdfRecord t;
         t.present = true; t.grouped = group_dev != nullptr; t.with_mol = molecule_dev != nullptr;
         t.n_atoms = n; t.n_bins = n_bins; t.n_groups = n_groups; t.r_max = r_max; t.inv_dr = (double)n_bins / r_max;
-        std::vector<int32_t> host((size_t)n);
-        auto fetch = [&](const int32_t *dev) {
-            if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(host.data(), dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sys.stream()));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
-        };
-        if (t.grouped) {
-            fetch(group_dev);
-            for (int i = 0; i < n; i++) {
-                EMDEE_REQUIRE(host[i] >= -1 && host[i] < n_groups, EMDEE_ERR_INVALID, "set_rdf: the group %d of atom %d is outside -1...%d", host[i], i, n_groups - 1);
-                if (host[i] >= 0) t.sizes[host[i]]++;
-            }
-        } else {
-            t.sizes[0] = n;
-        }
+        t.sizes[0] = t.grouped ? 0 : n;
+        for (int32_t g : fetched_groups(OBS_RDF, group_dev, n_groups))
+            if (g >= 0) t.sizes[g]++;
         if (t.with_mol) {
-            fetch(molecule_dev);
+            const std::vector<int32_t> host = fetched(molecule_dev);
             for (int i = 0; i < n; i++)
                 EMDEE_REQUIRE(host[i] >= -1, EMDEE_ERR_INVALID, "set_rdf: the molecule %d of atom %d is below -1 (-1: none)", host[i], i);
         }
-        // ---- commit
-        sys.rdf_group.ensure((size_t)n + 1); sys.rdf_mol.ensure((size_t)n + 1);
-        sys.rdf_counts.ensure((size_t)t.n_counters());
-        if (t.grouped && n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(sys.rdf_group.ptr, group_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, sys.stream()));
-        if (t.with_mol && n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(sys.rdf_mol.ptr, molecule_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, sys.stream()));
-        rdf = t;
-        zero_rdf();
-        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));   // (the caller's arrays are its own again on return)
+        t.group.ensure((size_t)n + 1); t.mol.ensure((size_t)n + 1);
+        t.counts.ensure((size_t)t.n_counters());
+        if (t.grouped && n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(t.group.ptr, group_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, sys.stream()));
+        if (t.with_mol && n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(t.mol.ptr, molecule_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, sys.stream()));
+        install(rdf, t);
     }
-    // one frame: queued on the stream, nothing read back; the engine's state, list and counters are not touched
     void rdf_sample() override {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_sample: no table is set (call emdee_md_set_rdf first)");
-        EMDEE_REQUIRE(sys.sorted && rdf.n_atoms == sys.n_owned && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "rdf_sample: the table was set for %d atoms, "
-                      "the state holds %d: set it again (emdee_md_set_rdf)", rdf.n_atoms, sys.n_owned);
+        obs_require_present(OBS_RDF, "sample", rdf);
+        obs_require_fit(OBS_RDF, rdf, obs_engine());
         EMDEE_REQUIRE(rdf.r_max <= 0.5 * shortest_side(), EMDEE_ERR_STATE, "rdf_sample: the box has shrunk: r_max = %g now exceeds half the shortest "
                       "side %g; set the table again with a smaller r_max", rdf.r_max, shortest_side());
-        sys.rdf_sample(rdf_plan(sys.len, rdf.r_max, sys.n_owned), rdf.grouped, rdf.with_mol, rdf.r_max, rdf.inv_dr, rdf.n_bins, rdf.n_groups);
+        sys.rdf_sample(rdf_plan(sys.len, rdf.r_max, sys.n_owned), rdf);
         EMDEE_HIP_CHECK(hipGetLastError());
-        rdf.frames++;
+        rdf.samples++;
         rdf.inv_volume_sum += 1.0 / (sys.len[0] * sys.len[1] * sys.len[2]);
     }
-    // blocking; any pointer may be NULL
     void rdf_read(int64_t *counts, int64_t *group_sizes, int64_t *frames, double *inv_volume_sum) override {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_read: no table is set (call emdee_md_set_rdf first)");
+        obs_require_present(OBS_RDF, "read", rdf);
         if (counts) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(counts, sys.rdf_counts.ptr, (size_t)rdf.n_counters() * sizeof(int64_t), hipMemcpyDeviceToHost, sys.stream()));
+            EMDEE_HIP_CHECK(hipMemcpyAsync(counts, rdf.counts.ptr, (size_t)rdf.n_counters() * sizeof(int64_t), hipMemcpyDeviceToHost, sys.stream()));
             EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
         }
         if (group_sizes) for (int a = 0; a < RDF_MAX_GROUPS; a++) group_sizes[a] = rdf.sizes[a];
-        if (frames) *frames = rdf.frames;
+        if (frames) *frames = rdf.samples;
         if (inv_volume_sum) *inv_volume_sum = rdf.inv_volume_sum;
     }
-    void rdf_reset() override {
-        use_device(sys.ctx);
-        EMDEE_REQUIRE(rdf.present, EMDEE_ERR_STATE, "rdf_reset: no table is set (call emdee_md_set_rdf first)");
-        zero_rdf();
-    }
-    // ---- mean-squared displacement and velocity autocorrelation (include/emdee_hip.h: emdee_md_set_msd; msd.hpp)
-    struct MsdTable {
-        bool present = false;
-        int what = 0, n_atoms = 0, n_groups = 0, n_lags = 0, origin_every = 1, n_origins = 0, n_grouped = 0, n_chunks = 0;
-        int64_t sizes[MSD_MAX_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int64_t samples = 0;                                 // s of the next sample
-        std::vector<int64_t> origins;                        // per lag: the origins that have contributed
-        double len[3] = {0, 0, 0};                           // the box at the last set or reset
-        uint64_t serial = 0;                                 // ... and the state serial
-        size_t snapshot() const { return (size_t)n_grouped * (((what & MSD_POSITIONS) ? 3 : 0) + ((what & MSD_VELOCITIES) ? 3 : 0)); }
-        size_t n_sums() const { return (size_t)n_lags * n_groups * MSD_WORDS; }
-    } msd;
-    uint64_t state_serial = 0;                               // counts emdee_md_set_state: a snapshot of one state is no origin for another
-    void zero_msd() {
-        if (msd.present) EMDEE_HIP_CHECK(hipMemsetAsync(sys.msd.sums.ptr, 0, msd.n_sums() * sizeof(double), sys.stream()));
-        msd.samples = 0;
-        msd.origins.assign((size_t)msd.n_lags, 0);
-        for (int d = 0; d < 3; d++) msd.len[d] = sys.len[d];
-        msd.serial = state_serial;
-    }
-    // all or nothing: every refusal, a failed allocation included, comes before the table in force changes; blocking
+    void rdf_reset() override { reset(OBS_RDF, rdf); }
+    // ---- mean-squared displacement and velocity autocorrelation (msd.hpp)
     void set_msd(int32_t what, int32_t n_groups, const int32_t *group_dev, int32_t n_lags, int32_t origin_every) override {
         use_device(sys.ctx);
-        if (n_lags == 0) { msd = MsdTable{}; return; }
-        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "set_msd: this integrator is a domain's, lent by emdee_dd_engine: it sees a part of the box only");
-        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "set_msd: an integrator with ghosts (its box is a domain of a larger one)");
-        EMDEE_REQUIRE(sys.sorted && !sys.id_gaps, EMDEE_ERR_STATE, "set_msd: no state loaded (call emdee_md_set_state first)");
+        if (n_lags == 0) { msd = MsdRecord{}; return; }
+        obs_require_whole_box("set_msd", obs_engine());
         EMDEE_REQUIRE(what >= 1 && what <= (MSD_POSITIONS | MSD_VELOCITIES), EMDEE_ERR_INVALID, "set_msd: what = %d is not a non-empty mask of "
                       "EMDEE_MSD | EMDEE_VACF", what);
         EMDEE_REQUIRE(n_groups >= 1 && n_groups <= MSD_MAX_GROUPS, EMDEE_ERR_INVALID, "set_msd: n_groups = %d is outside 1...%d", n_groups, MSD_MAX_GROUPS);
@@ -670,97 +650,49 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(origin_every >= 1, EMDEE_ERR_INVALID, "set_msd: origin_every = %d must be >= 1", origin_every);
         EMDEE_REQUIRE(msd_n_origins(n_lags, origin_every) <= MSD_MAX_ORIGINS, EMDEE_ERR_INVALID, "set_msd: %d lags with an origin every %d samples "
                       "are %d origins in the ring, above the limit of %d", n_lags, origin_every, msd_n_origins(n_lags, origin_every), MSD_MAX_ORIGINS);
-        EMDEE_REQUIRE(group_dev || n_groups == 1, EMDEE_ERR_INVALID, "set_msd: groups is NULL with n_groups = %d (NULL puts every atom in group 0)", n_groups);
         const int n = sys.n_owned;
-        std::vector<int32_t> host((size_t)n);
-        if (group_dev) {
-            if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(host.data(), group_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, sys.stream()));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
-            for (int i = 0; i < n; i++)
-                EMDEE_REQUIRE(host[i] >= -1 && host[i] < n_groups, EMDEE_ERR_INVALID, "set_msd: the group %d of atom %d is outside -1...%d", host[i], i, n_groups - 1);
-        }
+        const std::vector<int32_t> host = fetched_groups(OBS_MSD, group_dev, n_groups);
         const MsdLayout lay = msd_layout(group_dev ? host.data() : nullptr, n, n_groups);
-        MsdTable t;
+        MsdRecord t;
         t.present = true; t.what = what; t.n_atoms = n; t.n_groups = n_groups; t.n_lags = n_lags; t.origin_every = origin_every;
         t.n_origins = msd_n_origins(n_lags, origin_every); t.n_grouped = lay.n_grouped; t.n_chunks = (int)lay.chunks.size();
         for (int g = 0; g < MSD_MAX_GROUPS; g++) t.sizes[g] = lay.sizes[g];
-        // (buffers of their own: a failed allocation throws here and leaves the table in force and its ring as they are)
-        typename NbSystem<real>::MsdDev dev;
-        dev.pos_of.ensure((size_t)n + 1); dev.chunk_of_group.ensure(MSD_MAX_GROUPS + 1); dev.chunks.ensure(lay.chunks.size() + 1);
-        dev.ring.ensure((size_t)(t.n_origins + 1) * t.snapshot() + 1);
-        dev.partial.ensure((size_t)t.n_origins * lay.chunks.size() * MSD_WORDS + 1);
-        dev.sums.ensure(t.n_sums());
-        if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(dev.pos_of.ptr, lay.pos_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, sys.stream()));
-        EMDEE_HIP_CHECK(hipMemcpyAsync(dev.chunk_of_group.ptr, lay.chunk_of_group, sizeof(lay.chunk_of_group), hipMemcpyHostToDevice, sys.stream()));
+        t.pos_of.ensure((size_t)n + 1); t.chunk_of_group.ensure(MSD_MAX_GROUPS + 1); t.chunks.ensure(lay.chunks.size() + 1);
+        t.ring.ensure((size_t)(t.n_origins + 1) * t.snapshot() + 1);
+        t.partial.ensure((size_t)t.n_origins * lay.chunks.size() * MSD_WORDS + 1);
+        t.sums.ensure(t.n_sums());
+        if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(t.pos_of.ptr, lay.pos_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, sys.stream()));
+        EMDEE_HIP_CHECK(hipMemcpyAsync(t.chunk_of_group.ptr, lay.chunk_of_group, sizeof(lay.chunk_of_group), hipMemcpyHostToDevice, sys.stream()));
         if (!lay.chunks.empty())
-            EMDEE_HIP_CHECK(hipMemcpyAsync(dev.chunks.ptr, lay.chunks.data(), lay.chunks.size() * sizeof(MsdChunk), hipMemcpyHostToDevice, sys.stream()));
-        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));   // (the host arrays of this call are done with; the old ring is idle)
-        // ---- commit
-        sys.msd.swap(dev);
-        msd = t;
-        zero_msd();
-        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+            EMDEE_HIP_CHECK(hipMemcpyAsync(t.chunks.ptr, lay.chunks.data(), lay.chunks.size() * sizeof(MsdChunk), hipMemcpyHostToDevice, sys.stream()));
+        install(msd, t);
     }
-    // one sample: queued on the stream, nothing read back; the engine's state, list and counters are not touched.  A refusal
-    // changes nothing.
     void msd_sample() override {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_sample: no table is set (call emdee_md_set_msd first)");
-        EMDEE_REQUIRE(sys.sorted && msd.n_atoms == sys.n_owned && n_ghost == 0 && !sys.id_gaps, EMDEE_ERR_STATE, "msd_sample: the table was set for %d atoms, "
-                      "the state holds %d: set it again (emdee_md_set_msd)", msd.n_atoms, sys.n_owned);
-        EMDEE_REQUIRE(msd.serial == state_serial, EMDEE_ERR_STATE, "msd_sample: the state has been replaced (emdee_md_set_state) since the origins "
-                      "were taken: a displacement between two states means nothing; start again with emdee_md_msd_reset");
-        EMDEE_REQUIRE(msd.len[0] == sys.len[0] && msd.len[1] == sys.len[1] && msd.len[2] == sys.len[2], EMDEE_ERR_STATE, "msd_sample: the box has been "
-                      "rescaled (emdee_md_scale_box or a barostat) since the origins were taken: unwrapped coordinates across a rescaled box "
-                      "are not a displacement; start again with emdee_md_msd_reset");
+        obs_require_present(OBS_MSD, "sample", msd);
+        obs_require_fit(OBS_MSD, msd, obs_engine());
         MsdArgs a{};
         a.what = msd.what; a.n_grouped = msd.n_grouped; a.n_chunks = msd.n_chunks; a.n_groups = msd.n_groups; a.n_lags = msd.n_lags;
         a.origin_every = msd.origin_every; a.s = msd.samples; a.snapshot = msd.snapshot();
         const MsdSchedule q = msd_schedule(msd.samples, msd.n_lags, msd.origin_every);
-        sys.msd_sample(a, q.is_origin ? q.slot : -1, msd.n_origins);
+        sys.msd_sample(a, q.is_origin ? q.slot : -1, msd);
         EMDEE_HIP_CHECK(hipGetLastError());
         for (const MsdLive &l : q.live) msd.origins[(size_t)l.lag]++;
         msd.samples++;
     }
-    // blocking; any pointer may be NULL
     void msd_read(double *sums, int64_t *origins, int64_t *group_sizes, int64_t *samples) override {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_read: no table is set (call emdee_md_set_msd first)");
-        if (sums) {
-            EMDEE_HIP_CHECK(hipMemcpyAsync(sums, sys.msd.sums.ptr, msd.n_sums() * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
-            EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
-        }
+        obs_require_present(OBS_MSD, "read", msd);
+        if (sums) sys.read_back_doubles(sums, msd.sums.ptr, (int)msd.n_sums());
         if (origins) for (int l = 0; l < msd.n_lags; l++) origins[l] = msd.origins[(size_t)l];
         if (group_sizes) for (int g = 0; g < MSD_MAX_GROUPS; g++) group_sizes[g] = msd.sizes[g];
         if (samples) *samples = msd.samples;
     }
-    void msd_reset() override {
-        use_device(sys.ctx);
-        EMDEE_REQUIRE(msd.present, EMDEE_ERR_STATE, "msd_reset: no table is set (call emdee_md_set_msd first)");
-        zero_msd();
-    }
-    // ---- Green-Kubo observables: the stress and heat-flux autocorrelations (include/emdee_hip.h: emdee_md_set_gk; gk.hpp)
-    struct GkTable {
-        bool present = false;
-        int what = 0, n_atoms = 0, n_lags = 0;
-        int64_t samples = 0;                                 // s of the next sample
-        double len[3] = {0, 0, 0};                           // the box at the last set or reset: S and J are extensive, one V per run
-        uint64_t serial = 0;                                 // ... and the state serial
-    } gk;
-    void zero_gk() {
-        if (gk.present) {
-            EMDEE_HIP_CHECK(hipMemsetAsync(sys.gk.ring.ptr, 0, (size_t)gk.n_lags * GK_WORDS * sizeof(double), sys.stream()));
-            EMDEE_HIP_CHECK(hipMemsetAsync(sys.gk.acc.ptr, 0, sys.gk_acc_words(gk.n_lags) * sizeof(double), sys.stream()));
-        }
-        gk.samples = 0;
-        for (int d = 0; d < 3; d++) gk.len[d] = sys.len[d];
-        gk.serial = state_serial;
-    }
+    void msd_reset() override { reset(OBS_MSD, msd); }
+    // ---- Green-Kubo observables: the stress and heat-flux autocorrelations (gk.hpp)
     // what the engine must be for a table with this mask, at set and again at every sample (a table may be attached later)
     void require_gk(const char *fn, int what) const {
-        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s: this integrator is a domain's, lent by emdee_dd_engine: it sees a part of the box only", fn);
-        EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "%s: an integrator with ghosts (its box is a domain of a larger one)", fn);
-        EMDEE_REQUIRE(sys.sorted && !sys.id_gaps, EMDEE_ERR_STATE, "%s: no state loaded (call emdee_md_set_state first)", fn);
+        obs_require_whole_box(fn, obs_engine());
         EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "%s: the engine holds an hbonds table (emdee_md_set_hbonds): neither the atomic nor the "
                       "molecular stress holds the clusters' constraint virial; clear the table first", fn);
         if (!(what & GK_HEAT)) return;
@@ -780,40 +712,27 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(all.empty(), EMDEE_ERR_STATE, "%s: EMDEE_GK_HEAT on an engine with %s: the heat flux is written for forces that are all "
                       "pair terms of the neighbour rows, whose per-atom tensors are the half-pair split", fn, all.c_str());
     }
-    // all or nothing: every refusal, a failed allocation included, comes before the table in force changes; blocking
     void set_gk(int32_t what, int32_t n_lags) override {
         use_device(sys.ctx);
-        if (n_lags == 0) { gk = GkTable{}; return; }
+        if (n_lags == 0) { gk = GkRecord{}; return; }
         EMDEE_REQUIRE(what >= 1 && what <= (GK_STRESS | GK_HEAT), EMDEE_ERR_INVALID, "set_gk: what = %d is not a non-empty mask of "
                       "EMDEE_GK_STRESS | EMDEE_GK_HEAT", what);
         EMDEE_REQUIRE(n_lags >= 1 && n_lags <= GK_MAX_LAGS, EMDEE_ERR_INVALID, "set_gk: n_lags = %d is outside 1...%d (0 clears the table)", n_lags, GK_MAX_LAGS);
         require_gk("set_gk", what);
-        // (buffers of their own: a failed allocation throws here and leaves the table in force and its sums as they are)
-        typename NbSystem<real>::GkDev dev;
-        dev.ring.ensure((size_t)n_lags * GK_WORDS);
-        dev.acc.ensure(sys.gk_acc_words(n_lags));
-        dev.heat.ensure((size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS + GK_HEAT_WORDS);
-        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));   // (the old ring is idle)
-        // ---- commit
-        sys.gk.swap(dev);
-        gk = GkTable{};
-        gk.present = true; gk.what = what; gk.n_atoms = sys.n_owned; gk.n_lags = n_lags;
-        zero_gk();
-        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        GkRecord t;
+        t.present = true; t.what = what; t.n_atoms = sys.n_owned; t.n_lags = n_lags;
+        t.ring.ensure(t.ring_words());
+        t.acc.ensure(t.acc_words());
+        t.heat.ensure((size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS + GK_HEAT_WORDS);
+        install(gk, t);
     }
     // one sample: the forces (a rigid engine) and the tensor pass if they are not current, as the pressure entries evaluate them, then
-    // the sample's own launches; queued on the stream, nothing read back.  A refusal changes nothing.
+    // the sample's own launches
     void gk_sample() override {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(gk.present, EMDEE_ERR_STATE, "gk_sample: no table is set (call emdee_md_set_gk first)");
+        obs_require_present(OBS_GK, "sample", gk);
         require_gk("gk_sample", gk.what);
-        EMDEE_REQUIRE(gk.n_atoms == sys.n_owned, EMDEE_ERR_STATE, "gk_sample: the table was set for %d atoms, the state holds %d: set it again "
-                      "(emdee_md_set_gk)", gk.n_atoms, sys.n_owned);
-        EMDEE_REQUIRE(gk.serial == state_serial, EMDEE_ERR_STATE, "gk_sample: the state has been replaced (emdee_md_set_state) since the first "
-                      "sample: a correlation between two states means nothing; start again with emdee_md_gk_reset");
-        EMDEE_REQUIRE(gk.len[0] == sys.len[0] && gk.len[1] == sys.len[1] && gk.len[2] == sys.len[2], EMDEE_ERR_STATE, "gk_sample: the box has been "
-                      "rescaled (emdee_md_scale_box or a barostat) since the first sample: the stress and the heat flux are extensive and the "
-                      "Green-Kubo prefactor assumes one volume; start again with emdee_md_gk_reset");
+        obs_require_fit(OBS_GK, gk, obs_engine());
         EMDEE_REQUIRE(!sys.charges_stale(), EMDEE_ERR_STATE, "gk_sample: charges set for %lld atoms, the state holds %d: set them again or clear "
                       "them (emdee_md_set_coulomb)", (long long)sys.tables->q_n, sys.n_owned);
         const bool molecular = sys.has_rigid() && sys.tables->rigid.n > 0;
@@ -822,27 +741,23 @@ struct MdImpl : IMd {
             if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         }
         tensor_pass();
-        sys.gk_sample(gk.what, gk.n_lags, gk.samples, molecular);
+        sys.gk_sample(gk, molecular);
         EMDEE_HIP_CHECK(hipGetLastError());
         gk.samples++;
     }
-    // blocking; any pointer may be NULL.  The deferred fault word of the bonded terms is checked here, not in the sample.
+    // the deferred fault word of the bonded terms is checked here, not in the sample
     void gk_read(double *sums, double *totals, double *last, int64_t *samples) override {
         use_device(sys.ctx);
-        EMDEE_REQUIRE(gk.present, EMDEE_ERR_STATE, "gk_read: no table is set (call emdee_md_set_gk first)");
+        obs_require_present(OBS_GK, "read", gk);
         sys.check_bonded();
-        const size_t n = (size_t)gk.n_lags * GK_WORDS;
-        if (sums) EMDEE_HIP_CHECK(hipMemcpyAsync(sums, sys.gk.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
-        if (totals) EMDEE_HIP_CHECK(hipMemcpyAsync(totals, sys.gk.acc.ptr + n, GK_WORDS * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
-        if (last) EMDEE_HIP_CHECK(hipMemcpyAsync(last, sys.gk.acc.ptr + n + GK_WORDS, GK_WORDS * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        const size_t n = gk.ring_words();
+        if (sums) EMDEE_HIP_CHECK(hipMemcpyAsync(sums, gk.acc.ptr, n * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        if (totals) EMDEE_HIP_CHECK(hipMemcpyAsync(totals, gk.acc.ptr + n, GK_WORDS * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        if (last) EMDEE_HIP_CHECK(hipMemcpyAsync(last, gk.acc.ptr + n + GK_WORDS, GK_WORDS * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
         EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
         if (samples) *samples = gk.samples;
     }
-    void gk_reset() override {
-        use_device(sys.ctx);
-        EMDEE_REQUIRE(gk.present, EMDEE_ERR_STATE, "gk_reset: no table is set (call emdee_md_set_gk first)");
-        zero_gk();
-    }
+    void gk_reset() override { reset(OBS_GK, gk); }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
     void couple(double dt) {

@@ -468,6 +468,37 @@ static __global__ __launch_bounds__(1024) void k_scan_block(int *__restrict__ da
     }
 }
 
+// in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
+struct Scanner {
+    DevBuf<int> scratch;
+    void run(int *data, size_t n, hipStream_t s) {
+        if (n == 0) return;
+        if (n <= (size_t)SCAN_BLOCK_MAX) {
+            hipLaunchKernelGGL(k_scan_block, dim3(1), dim3(1024), 0, s, data, (int)n);
+            return;
+        }
+        size_t total = 0;
+        for (size_t m = n; m > 1;) {
+            m = (m + SCAN_TILE - 1) / SCAN_TILE;
+            total += m;
+            if (m == 1) break;
+        }
+        scratch.ensure(total + 1);
+        level(data, n, scratch.ptr, s);
+    }
+
+  private:
+    void level(int *data, size_t n, int *sums, hipStream_t s) {
+        size_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+        hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, data, data, n,
+                           tiles > 1 ? sums : nullptr);
+        if (tiles > 1) {
+            level(sums, tiles, sums + tiles, s);
+            hipLaunchKernelGGL(k_scan_add, dim3(blocks_for(n, 256)), dim3(256), 0, s, data, n, sums);
+        }
+    }
+};
+
 // Several small zero-fills in ONE launch (a hipMemsetAsync whose size is not a multiple of 16 bytes is two fill kernels,
 // and every launch behind a blocking read-back is a launch latency on the critical path of a rebuild)
 struct ZeroRanges {

@@ -10,12 +10,10 @@
 
 #include "brick.hpp"
 #include "ewald.hpp"
-#include "gk.hpp"
 #include "kernels.hpp"
 #include "minimize.hpp"
-#include "msd.hpp"
+#include "observables.hpp"
 #include "plan.hpp"
-#include "rdf.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
 #include "thermostat.hpp"
@@ -65,37 +63,6 @@ enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP 
 enum FlagWord { W_BONDED = 16, W_CHARGES = 17, W_EWALD = 18, W_SETTLE = 20, W_RIGID_MASS = 21, W_RIGID_DIST = 22, W_HBONDS = 23,
                 W_HBONDS_DIST = 24, W_IMAGE = 25, W_VSITE_MASS = 28 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
-
-// in-place exclusive scan of int32 data[0..n) (n may exceed one tile: recursive tile sums)
-struct Scanner {
-    DevBuf<int> scratch;
-    void run(int *data, size_t n, hipStream_t s) {
-        if (n == 0) return;
-        if (n <= (size_t)SCAN_BLOCK_MAX) {
-            hipLaunchKernelGGL(k_scan_block, dim3(1), dim3(1024), 0, s, data, (int)n);
-            return;
-        }
-        size_t total = 0;
-        for (size_t m = n; m > 1;) {
-            m = (m + SCAN_TILE - 1) / SCAN_TILE;
-            total += m;
-            if (m == 1) break;
-        }
-        scratch.ensure(total + 1);
-        level(data, n, scratch.ptr, s);
-    }
-
-  private:
-    void level(int *data, size_t n, int *sums, hipStream_t s) {
-        size_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-        hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, data, data, n,
-                           tiles > 1 ? sums : nullptr);
-        if (tiles > 1) {
-            level(sums, tiles, sums + tiles, s);
-            hipLaunchKernelGGL(k_scan_add, dim3(blocks_for(n, 256)), dim3(256), 0, s, data, n, sums);
-        }
-    }
-};
 
 // (the brick kernel variants, LDS_LIMIT and with_brick_variant: plan.hpp)
 template <typename K>
@@ -1579,90 +1546,75 @@ struct NbSystem {
         }
     }
 
-    // ---------------------------------------------------------------- radial distribution functions (rdf.hpp; MdImpl::set_rdf / rdf_sample drive these)
-    // The table's copies of the caller's group and molecule arrays (caller order), the sample's own binning and the u64 histogram.
+    // ---------------------------------------------------------------- radial distribution functions (rdf.hpp; the table is MdImpl's RdfRecord, observables.hpp)
     // A sample reads the records, perm and the cells the Float32 records are relative to; it writes nothing of the engine's.
-    DevBuf<int> rdf_group, rdf_mol, rdf_cell_of, rdf_count, rdf_fill;
-    DevBuf<RdfAtom> rdf_atoms;
-    DevBuf<unsigned long long> rdf_counts;
-    Scanner rdf_scanner;
-    // one frame into rdf_counts[0 .. n_counters): four timed stages on the stream, nothing read back
-    void rdf_sample(const RdfPlan &plan, bool grouped, bool with_mol, double r_max, double inv_dr, int n_bins, int n_groups) {
+    // One frame into t.counts[0 .. n_counters): four timed stages on the stream, nothing read back.
+    void rdf_sample(const RdfPlan &plan, RdfRecord &t) {
         if (n_total == 0) return;
-        const int n = n_total, ncell = (int)rdf_plan_cells(plan), n_counters = rdf_n_pairs(n_groups) * n_bins;
+        const int n = n_total, ncell = (int)rdf_plan_cells(plan), n_counters = t.n_counters();
         RdfGrid g{};
         for (int d = 0; d < 3; d++) {
             g.lo[d] = lo[d]; g.len[d] = len[d]; g.inv_len[d] = 1.0 / len[d];
             g.M[d] = plan.M[d]; g.wrap[d] = plan.wrap[d];
         }
         g.nd = plan.nd;
-        rdf_cell_of.ensure((size_t)n + 1); rdf_atoms.ensure((size_t)n + 1);
-        rdf_count.ensure((size_t)ncell + 2); rdf_fill.ensure((size_t)ncell + 2);
+        t.cell_of.ensure((size_t)n + 1); t.atoms.ensure((size_t)n + 1);
+        t.count.ensure((size_t)ncell + 2); t.fill.ensure((size_t)ncell + 2);
         const RelGrid rel = rel_grid(rel_now, cell_sorted.ptr);
-        const int *grp = grouped ? rdf_group.ptr : nullptr, *mol = with_mol ? rdf_mol.ptr : nullptr;
+        const int *grp = t.grouped ? t.group.ptr : nullptr, *mol = t.with_mol ? t.mol.ptr : nullptr;
         {
-            Timed t(this, T_RDF);
-            EMDEE_HIP_CHECK(hipMemsetAsync(rdf_count.ptr, 0, ((size_t)ncell + 1) * sizeof(int), stream()));
-            EMDEE_HIP_CHECK(hipMemsetAsync(rdf_fill.ptr, 0, (size_t)ncell * sizeof(int), stream()));
+            Timed timed(this, T_RDF);
+            EMDEE_HIP_CHECK(hipMemsetAsync(t.count.ptr, 0, ((size_t)ncell + 1) * sizeof(int), stream()));
+            EMDEE_HIP_CHECK(hipMemsetAsync(t.fill.ptr, 0, (size_t)ncell * sizeof(int), stream()));
             hipLaunchKernelGGL((k_rdf_count<real>), dim3(blocks_for(n, 256)), dim3(256), 0, stream(), n, n_owned, (const Rec<real> *)rec.ptr, rel,
-                               (const int *)perm.ptr, grp, g, rdf_cell_of.ptr, rdf_count.ptr);
+                               (const int *)perm.ptr, grp, g, t.cell_of.ptr, t.count.ptr);
         }
         {
-            Timed t(this, T_RDF);
-            rdf_scanner.run(rdf_count.ptr, (size_t)ncell + 1, stream());   // count[] becomes the first slot of every cell
+            Timed timed(this, T_RDF);
+            t.scanner.run(t.count.ptr, (size_t)ncell + 1, stream());   // count[] becomes the first slot of every cell
         }
         {
-            Timed t(this, T_RDF);
+            Timed timed(this, T_RDF);
             hipLaunchKernelGGL((k_rdf_fill<real>), dim3(blocks_for(n, 256)), dim3(256), 0, stream(), n, (const Rec<real> *)rec.ptr, rel,
-                               (const int *)perm.ptr, grp, mol, (const int *)rdf_cell_of.ptr, (const int *)rdf_count.ptr, rdf_fill.ptr,
-                               rdf_atoms.ptr);
+                               (const int *)perm.ptr, grp, mol, (const int *)t.cell_of.ptr, (const int *)t.count.ptr, t.fill.ptr,
+                               t.atoms.ptr);
         }
         {
-            Timed t(this, T_RDF);
+            Timed timed(this, T_RDF);
             const int blocks = std::max(1, std::min(ncell, 8 * std::max(ctx->cu_count, 32)));
             hipLaunchKernelGGL(k_rdf_pairs, dim3(blocks), dim3(RDF_BLOCK), (size_t)n_counters * sizeof(unsigned int), stream(), g, ncell,
-                               (const int *)rdf_count.ptr, (const RdfAtom *)rdf_atoms.ptr, r_max * r_max * RDF_R2_MARGIN, inv_dr, n_bins,
-                               n_groups, n_counters, rdf_counts.ptr);
+                               (const int *)t.count.ptr, (const RdfAtom *)t.atoms.ptr, t.r_max * t.r_max * RDF_R2_MARGIN, t.inv_dr, t.n_bins,
+                               t.n_groups, n_counters, t.counts.ptr);
         }
     }
 
-    // ---------------------------------------------------------------- mean-squared displacement and velocity autocorrelation (msd.hpp; MdImpl::set_msd / msd_sample drive these)
-    // The table order (pos_of, caller ids -> entries), its chunks, the ring of snapshots (n_origins + 1 of them, the last one the
-    // scratch snapshot), the chunk partials of one sample and the sums.  A sample reads the records, the image counts, perm, the
-    // velocities and the cells the Float32 records are relative to; it writes nothing of the engine's.
-    struct MsdDev {
-        DevBuf<int> pos_of, chunk_of_group;
-        DevBuf<MsdChunk> chunks;
-        DevBuf<double> ring, partial, sums;
-        void swap(MsdDev &o) {
-            pos_of.swap(o.pos_of); chunk_of_group.swap(o.chunk_of_group); chunks.swap(o.chunks);
-            ring.swap(o.ring); partial.swap(o.partial); sums.swap(o.sums);
-        }
-    } msd;
+    // ---------------------------------------------------------------- mean-squared displacement and velocity autocorrelation (msd.hpp; the table is MdImpl's MsdRecord, observables.hpp)
+    // A sample reads the records, the image counts, perm, the velocities and the cells the Float32 records are relative to; it
+    // writes nothing of the engine's.
     // sample a.s: the snapshot into ring slot `slot` (an origin) or into the scratch snapshot (slot < 0), then every live origin
     // against it; three timed launches on the stream, nothing read back
-    void msd_sample(const MsdArgs &a, int slot, int n_origins) {
+    void msd_sample(const MsdArgs &a, int slot, MsdRecord &t) {
         if (n_total == 0 || a.n_grouped == 0) return;
-        double *cur = msd.ring.ptr + (size_t)(slot >= 0 ? slot : n_origins) * a.snapshot;
+        double *cur = t.ring.ptr + (size_t)(slot >= 0 ? slot : t.n_origins) * a.snapshot;
         const int n_live = msd_live_count(a.s, a.n_lags, a.origin_every);
         {
-            Timed t(this, T_MSD);
+            Timed timed(this, T_MSD);
             hipLaunchKernelGGL((k_msd_gather<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, grid,
                                (const int *)img.ptr, (const int *)perm.ptr, (const Rec<real> *)rec.ptr, rel_grid(rel_now, cell_sorted.ptr),
-                               (const real *)vel.ptr, pitch, (const int *)msd.pos_of.ptr, a.what, a.n_grouped, cur);
+                               (const real *)vel.ptr, pitch, (const int *)t.pos_of.ptr, a.what, a.n_grouped, cur);
         }
         if (n_live == 0) return;
         {
-            Timed t(this, T_MSD);
+            Timed timed(this, T_MSD);
             const bool pos = a.what & MSD_POSITIONS, vel_too = a.what & MSD_VELOCITIES;
             auto kernel = pos ? (vel_too ? k_msd_accumulate<true, true> : k_msd_accumulate<true, false>) : k_msd_accumulate<false, true>;
-            hipLaunchKernelGGL(kernel, dim3(a.n_chunks), dim3(MSD_BLOCK), 0, stream(), a, (const MsdChunk *)msd.chunks.ptr, (const double *)cur,
-                               (const double *)msd.ring.ptr, msd.partial.ptr);
+            hipLaunchKernelGGL(kernel, dim3(a.n_chunks), dim3(MSD_BLOCK), 0, stream(), a, (const MsdChunk *)t.chunks.ptr, (const double *)cur,
+                               (const double *)t.ring.ptr, t.partial.ptr);
         }
         {
-            Timed t(this, T_MSD);
-            hipLaunchKernelGGL(k_msd_finish, dim3(n_live, a.n_groups), dim3(RED_BLOCK), 0, stream(), a, (const int *)msd.chunk_of_group.ptr,
-                               (const double *)msd.partial.ptr, msd.sums.ptr);
+            Timed timed(this, T_MSD);
+            hipLaunchKernelGGL(k_msd_finish, dim3(n_live, a.n_groups), dim3(RED_BLOCK), 0, stream(), a, (const int *)t.chunk_of_group.ptr,
+                               (const double *)t.partial.ptr, t.sums.ptr);
         }
     }
 
@@ -1742,45 +1694,39 @@ struct NbSystem {
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = both[q] - both[TENSOR_SUMS + q];
     }
 
-    // ---------------------------------------------------------------- Green-Kubo observables (gk.hpp; MdImpl::set_gk / gk_sample drive these)
-    // The ring of samples (n_lags x 9), the lag sums with the totals and the last sample behind them (acc), the block partials and
-    // the three totals of the heat flux.  A sample reads the outputs of the tensor pass, perm, the velocities and the masses; it
-    // writes these buffers and the scratch of the box sums (tpartial), nothing else of the engine's.
-    struct GkDev {
-        DevBuf<double> ring, acc, heat;
-        void swap(GkDev &o) { ring.swap(o.ring); acc.swap(o.acc); heat.swap(o.heat); }
-    } gk;
-    static size_t gk_acc_words(int n_lags) { return (size_t)n_lags * GK_WORDS + 2 * GK_WORDS; }
-    // sample s of a table with n_lags lags: queued on the stream, nothing read back.  Behind a current tensor pass (and, with
+    // ---------------------------------------------------------------- Green-Kubo observables (gk.hpp; the table is MdImpl's GkRecord, observables.hpp)
+    // A sample reads the outputs of the tensor pass, perm, the velocities and the masses; it writes the record's buffers and the
+    // scratch of the box sums (tpartial), nothing else of the engine's.
+    // sample t.samples of the table: queued on the stream, nothing read back.  Behind a current tensor pass (and, with
     // `molecular`, current forces).  GK_STRESS: the box sums of the pressure entry (two launches, a third with `molecular`, whose
     // molecule pass is T_MOLECULAR's); GK_HEAT: the heat partials and their finish (two); then the push and the correlator (two).
-    void gk_sample(int what, int n_lags, long long s, bool molecular) {
+    void gk_sample(GkRecord &t, bool molecular) {
         const double *box = nullptr, *heat = nullptr;
-        if ((what & GK_STRESS) && n_total > 0) box = molecular ? queue_molecular_tensor_sums(T_GK) : queue_tensor_sums(T_GK);
-        if ((what & GK_HEAT) && n_total > 0) {
+        if ((t.what & GK_STRESS) && n_total > 0) box = molecular ? queue_molecular_tensor_sums(T_GK) : queue_tensor_sums(T_GK);
+        if ((t.what & GK_HEAT) && n_total > 0) {
             const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-            double *tot = gk.heat.ptr + (size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS;
+            double *tot = t.heat.ptr + (size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS;
             {
-                Timed t(this, T_GK);
+                Timed timed(this, T_GK);
                 hipLaunchKernelGGL((k_gk_heat_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch,
                                    (const int *)perm.ptr, (const real *)en.ptr, (const real *)vt.ptr, (const real *)vel.ptr,
-                                   with_mass ? (const real *)im.ptr : nullptr, gk.heat.ptr);
+                                   with_mass ? (const real *)im.ptr : nullptr, t.heat.ptr);
             }
             {
-                Timed t(this, T_GK);
-                hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, GK_HEAT_WORDS, (const double *)gk.heat.ptr, tot);
+                Timed timed(this, T_GK);
+                hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, GK_HEAT_WORDS, (const double *)t.heat.ptr, tot);
             }
             heat = tot;
         }
         GkArgs a{};
-        a.what = what; a.n_lags = n_lags; a.molecular = molecular ? 1 : 0; a.s = s; a.ring = gk.ring.ptr; a.acc = gk.acc.ptr;
+        a.what = t.what; a.n_lags = t.n_lags; a.molecular = molecular ? 1 : 0; a.s = t.samples; a.ring = t.ring.ptr; a.acc = t.acc.ptr;
         {
-            Timed t(this, T_GK);
+            Timed timed(this, T_GK);
             hipLaunchKernelGGL(k_gk_push, dim3(1), dim3(WAVE), 0, stream(), a, box, heat);
         }
         {
-            Timed t(this, T_GK);
-            hipLaunchKernelGGL(k_gk_correlate, dim3(blocks_for(gk_live_lags(s, n_lags), GK_BLOCK)), dim3(GK_BLOCK), 0, stream(), a);
+            Timed timed(this, T_GK);
+            hipLaunchKernelGGL(k_gk_correlate, dim3(blocks_for(gk_live_lags(t.samples, t.n_lags), GK_BLOCK)), dim3(GK_BLOCK), 0, stream(), a);
         }
     }
 

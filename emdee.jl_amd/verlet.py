@@ -386,6 +386,18 @@ class VelocityVerlet:
         _lib.call("emdee_md_thermostat_draws", self._handle, int(seed) & (2 ** 64 - 1), int(step), int(n_dof), out)
         return out[0], out[1]
 
+    def _per_atom_i32(self, fn, n_groups, **arrays):
+        """The per-atom integer arrays of a set_rdf_ / set_msd_ call (name=values or name=None, `groups` first) as int32 device
+        tensors of n_owned entries each, and n_groups (None: what groups implies -- its largest entry + 1, at least 1)."""
+        out = [None if v is None else torch.as_tensor(v).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous() for v in arrays.values()]
+        for name, t in zip(arrays, out):
+            if t is not None and t.shape[0] != self.n_owned:
+                raise ValueError("%s: %s holds %d entries, the state %d owned atoms" % (fn, name, t.shape[0], self.n_owned))
+        g = out[0]
+        if n_groups is None:
+            n_groups = 1 if g is None or g.numel() == 0 else max(int(g.max().item()) + 1, 1)
+        return out, int(n_groups)
+
     # -- radial distribution functions (include/emdee_hip.h: emdee_md_set_rdf; undivided periodic boxes)
     _rdf = None                                            # (r_max, n_bins, n_groups) of the table in force
 
@@ -395,15 +407,7 @@ class VelocityVerlet:
         per unordered pair of groups (n_groups: how many groups there are, 1...8; None: the largest entry of groups + 1).
         molecules: None, or one integer per owned atom; pairs with equal entries >= 0 are skipped.  n_bins = 0 clears the
         table.  Zeroes the accumulators."""
-        as_i32 = lambda v: torch.as_tensor(v).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
-        g = as_i32(groups) if groups is not None else None
-        m = as_i32(molecules) if molecules is not None else None
-        for name, t in (("groups", g), ("molecules", m)):
-            if t is not None and t.shape[0] != self.n_owned:
-                raise ValueError("set_rdf_: %s holds %d entries, the state %d owned atoms" % (name, t.shape[0], self.n_owned))
-        if n_groups is None:
-            n_groups = 1 if g is None or g.numel() == 0 else max(int(g.max().item()) + 1, 1)
-        n_groups = int(n_groups)
+        (g, m), n_groups = self._per_atom_i32("set_rdf_", n_groups, groups=groups, molecules=molecules)
         _lib.call("emdee_md_set_rdf", self._handle, float(r_max), int(n_bins), n_groups,
                   C.c_void_p(g.data_ptr()) if g is not None else None, C.c_void_p(m.data_ptr()) if m is not None else None)
         self._rdf = (float(r_max), int(n_bins), n_groups) if int(n_bins) != 0 else None
@@ -453,12 +457,7 @@ class VelocityVerlet:
         (n_groups: how many groups there are, 1...8; None: the largest entry of groups + 1).  msd / vacf: which of the two to
         keep (positions and velocities are stored only for the one that needs them).  n_lags = 0 clears the table.  Zeroes the
         sums and restarts the sample counter."""
-        g = torch.as_tensor(groups).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous() if groups is not None else None
-        if g is not None and g.shape[0] != self.n_owned:
-            raise ValueError("set_msd_: groups holds %d entries, the state %d owned atoms" % (g.shape[0], self.n_owned))
-        if n_groups is None:
-            n_groups = 1 if g is None or g.numel() == 0 else max(int(g.max().item()) + 1, 1)
-        n_groups = int(n_groups)
+        (g,), n_groups = self._per_atom_i32("set_msd_", n_groups, groups=groups)
         what = (MSD if msd else 0) | (VACF if vacf else 0)
         _lib.call("emdee_md_set_msd", self._handle, what, n_groups, C.c_void_p(g.data_ptr()) if g is not None else None,
                   int(n_lags), int(origin_every))
