@@ -447,6 +447,16 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff) {
 int32_t emdee_md_profile(emdee_md *md, int32_t enable) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->profile(enable != 0); });
 }
+int32_t emdee_md_set_restraints(emdee_md *md, const int32_t *atoms_dev, const double *ref_dev, const double *k_dev, const double *flat_dev,
+                                int32_t n) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_restraints(atoms_dev, ref_dev, k_dev, flat_dev, n); });
+}
+int32_t emdee_md_restraint_sums(emdee_md *md, double out[EMDEE_RESTRAINT_WORDS]) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->restraint_sums(out); });
+}
+int32_t emdee_md_get_restraint_refs(emdee_md *md, double *ref_dev) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->get_restraint_refs(ref_dev); });
+}
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->kernel_time(kernel, total_ms, launches); });
 }

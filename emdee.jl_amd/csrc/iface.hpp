@@ -60,6 +60,9 @@ struct IMd {
     virtual void set_rigid3(const int32_t *atoms, const double *geom, int32_t n_mol) = 0;
     virtual void set_hbonds(const int32_t *atoms, const double *dist, int32_t n_clusters) = 0;
     virtual void set_vsites(const int32_t *atoms, const double *weights, int32_t n_sites) = 0;
+    virtual void set_restraints(const int32_t *atoms, const double *ref, const double *k, const double *flat, int32_t n) = 0;
+    virtual void restraint_sums(double *out) = 0;
+    virtual void get_restraint_refs(double *ref_dev) = 0;
     virtual void set_ewald(double alpha, const int32_t *kmax) = 0;
     virtual void set_pme(double alpha, const int32_t *grid, int32_t order) = 0;
     virtual void get_box(double lo[3], double len[3]) = 0;

@@ -195,40 +195,47 @@ struct MdImpl : IMd {
         for (int k = 0; k < TABLES; k++) unchecked[k] = unchecked[k] || (!lent && attached(k).present);   // (every table, before a check can refuse)
         for (int k = 0; k < TABLES; k++) {
             if (lent || !attached(k).present) continue;
-            if (k != VSITES) sys.reset_error(sys.groups[k]);
+            if (k < VSITES) sys.reset_error(sys.groups[k]);
             if (sys.stale(attached(k)) || ng != 0) continue;
-            if (k != VSITES) {
+            if (k < VSITES) {
                 sys.check_state(sys.groups[k]);
                 sys.velocities(sys.groups[k]);
-            } else {
+            } else if (k == VSITES) {
                 sys.check_vsites(sys.tables->vsites);
                 sys.place_sites(true);
                 sys.resort();
-            }
+            }                                                // (a restraint table asks nothing of the state but its atom count: the references are kept)
             unchecked[k] = false;
         }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
         // cleared -- NbSystem::ensure_charges)
-        if (!defer_forces && !sys.charges_stale()) {
+        if (!defer_forces && !sys.charges_stale() && !restraints_unfit()) {
             force_pass(EMDEE_FORCES);
             current_mask = EMDEE_FORCES;
         }
         EMDEE_HIP_CHECK(hipGetLastError());
     }
+    // a restraint table set for another atom count (or met by ghosts): it stays in force, unused, and the force pass waits for it to
+    // be set again or cleared
+    bool restraints_unfit() const { return !lent && sys.has_restraints() && (sys.stale(sys.tables->restraints) || n_ghost != 0); }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
     // The attached tables: one per constraint group (NbSystem::groups, same index), then the table of virtual sites
-    // (emdee_md_set_vsites).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
+    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
     // texts; what is done with one stays per kind.
-    enum { VSITES = NbSystem<real>::GROUPS, TABLES };
-    const Topology::GroupTable &attached(int k) const { return k == VSITES ? sys.tables->vsites : sys.table(sys.groups[k]); }
+    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, TABLES };
+    const Topology::GroupTable &attached(int k) const {
+        if (k == RESTRAINTS) return sys.tables->restraints;
+        return k == VSITES ? sys.tables->vsites : sys.table(sys.groups[k]);
+    }
     // what the texts of this file call the entries of table k, and the call that sets it
     struct GroupText { const char *one, *many, *setter; };
     static constexpr GroupText GROUP_TEXT[TABLES] = {{"a rigid molecule", "rigid molecules", "emdee_md_set_rigid3"},
                                                      {"an hbonds cluster", "hbonds clusters", "emdee_md_set_hbonds"},
-                                                     {"a virtual site", "virtual sites", "emdee_md_set_vsites"}};
+                                                     {"a virtual site", "virtual sites", "emdee_md_set_vsites"},
+                                                     {"a position restraint", "position restraints", "emdee_md_set_restraints"}};
     // table k has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
-    bool unchecked[TABLES] = {false, false, false};
+    bool unchecked[TABLES] = {false, false, false, false};
     // the conditions emdee_md_step refuses table k on
     void require_fitting(const char *what, int k) const {
         const Topology::GroupTable &t = attached(k);
@@ -245,7 +252,7 @@ struct MdImpl : IMd {
             {sys.image_fault, "an atom has travelled more than 511 box lengths from the box (reported before); replace the state"}};
         for (const auto &r : reported) EMDEE_REQUIRE(!r.fault.latched, EMDEE_ERR_STATE, "%s: %s", what, r.text);
         for (int k = 0; k < TABLES; k++) {
-            if (k != VSITES)
+            if (k < VSITES)
                 EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "%s: %s had no solution; replace the table or the state", what, GROUP_TEXT[k].one);
             require_fitting(what, k);
         }
@@ -274,6 +281,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!((frc || en || vir) && sys.charges_stale()), EMDEE_ERR_STATE, "md: charges set for %lld atoms, the state "
                       "holds %d: set them again or clear them (emdee_md_set_coulomb) before reading forces, energies or virials",
                       (long long)sys.tables->q_n, sys.n_owned);
+        if (frc || en || vir) require_fitting("md_get_state (forces, energies or virials)", RESTRAINTS);
         if ((en || vir) && (current_mask & 6) != 6) forces(7, 0);
         sys.ids_map();                                       // (scratch of the engine's own: before the fence)
         FenceOut fence(caller_ctx, sys.stream());
@@ -287,7 +295,9 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         require_ready("md_step");
         if (nsteps == 0) return;
-        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || baro.kind != EMDEE_BAROSTAT_OFF || thermo.kind != EMDEE_THERMOSTAT_OFF) {
+        // (a restraint table: closed steps as well, so that the state after s steps does not depend on how they were dealt to calls)
+        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || sys.has_restraints() || baro.kind != EMDEE_BAROSTAT_OFF ||
+            thermo.kind != EMDEE_THERMOSTAT_OFF) {
             step_closed(nsteps, dt, rebuild_every);
             return;
         }
@@ -365,6 +375,7 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
         require_fitting("scale_box", sys.RIGID);            // (an hbonds table was refused above)
         require_fitting("scale_box", VSITES);
+        require_fitting("scale_box", RESTRAINTS);
         sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes; sites go back on their scaled parents)
         since_build = 0;
         current_mask = 0;
@@ -445,8 +456,8 @@ struct MdImpl : IMd {
         sys.check_bonded();                                  // (one read-back per call, with bonded tables only)
         for (auto &g : sys.groups) sys.check(g);             // (one read-back per call and table)
     }
-    // emdee_md_step with coupling on, with rigid molecules (emdee_md_set_rigid3), an hbonds table (emdee_md_set_hbonds) or virtual
-    // sites: closed steps and, with pressure coupling on, after the step that completes an interval, (f) the event.  Without a
+    // emdee_md_step with coupling on, with rigid molecules (emdee_md_set_rigid3), an hbonds table (emdee_md_set_hbonds), virtual
+    // sites or position restraints (emdee_md_set_restraints): closed steps and, with pressure coupling on, after the step that completes an interval, (f) the event.  Without a
     // table the event's step evaluates the energies and virials with its forces when the coupling is isotropic: no pass is added
     // for the pressure.  With rigid molecules (emdee_md_set_molecular_scaling) the event takes the molecular pressure from that
     // step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale, which rebuilds the list and
@@ -704,6 +715,7 @@ struct MdImpl : IMd {
             {sys.has_bonded(), "bonded terms (emdee_md_set_bonded)"},
             {sys.has_rigid(), "rigid molecules (emdee_md_set_rigid3)"},
             {sys.has_vsites(), "virtual sites (emdee_md_set_vsites)"},
+            {sys.has_restraints(), "position restraints (emdee_md_set_restraints)"},
             {pme, "particle-mesh Ewald (emdee_md_set_pme)"},
             {sys.has_ewald() && !pme, "Ewald summation (emdee_md_set_ewald)"}};
         std::string all;                                     // (every table in the way, so that one refusal says what to clear)
@@ -1001,12 +1013,14 @@ struct MdImpl : IMd {
         // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat; 15: the four
         // stages of every sample of the radial distribution functions (emdee_md_rdf_sample); 16: the three launches of every sample
         // of the displacement and velocity correlations (emdee_md_msd_sample); 17: the launches every sample of the Green-Kubo
-        // observables adds to the tensor pass (emdee_md_gk_sample)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 17, EMDEE_ERR_INVALID, "kernel id out of range");
+        // observables adds to the tensor pass (emdee_md_gk_sample); 18: the launch the position restraints add to every force pass, and
+        // the scaling of their references (emdee_md_set_restraints)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 18, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[18][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[19][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
-                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}, {T_GK, -1}};
+                                {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}, {T_GK, -1},
+                                {T_RESTRAINTS, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -1095,6 +1109,38 @@ struct MdImpl : IMd {
             unchecked[VSITES] = false;
             if (sys.vsites_fit()) sys.place_sites(true);
         });
+    }
+    // emdee_md_set_restraints: all or nothing -- the candidate table is fetched, checked on the host (topo::restraint_table) and uploaded
+    // before anything in force changes, then installed whole.  The neighbour list does not depend on the table; the forces do, and are
+    // evaluated again, so that planes and table belong together on return.
+    void set_restraints(const int32_t *atoms, const double *ref, const double *k, const double *flat, int32_t n) override {
+        install("position restraints", "a decomposed run has none", [&] {
+            EMDEE_REQUIRE(sys.with_vel, EMDEE_ERR_STATE, "set_restraints: the state was loaded without velocities");
+            sys.own_tables.set_restraints(atoms, ref, k, flat, n, sys.n_owned, sys.stream(),
+                                          [&](const int *a, double *r, int m) { sys.capture_restraint_refs(a, r, m); });
+            unchecked[RESTRAINTS] = false;
+        }, false);
+        if (sys.charges_stale()) { current_mask = 0; return; }
+        force_pass(EMDEE_FORCES);
+        current_mask = EMDEE_FORCES;
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    void restraint_sums(double *out) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(out, EMDEE_ERR_INVALID, "restraint_sums: out is NULL");
+        EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "restraint_sums: no state loaded (call emdee_md_set_state first)");
+        require_fitting("restraint_sums", RESTRAINTS);
+        sys.restraint_sums(out);
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    void get_restraint_refs(double *ref_dev) override {
+        use_device(sys.ctx);
+        const Topology::RestraintTable &t = sys.tables->restraints;
+        if (!t.present || t.n == 0) return;
+        EMDEE_REQUIRE(ref_dev, EMDEE_ERR_INVALID, "get_restraint_refs: ref is NULL");
+        require_fitting("get_restraint_refs", RESTRAINTS);
+        FenceOut fence(caller_ctx, sys.stream());
+        EMDEE_HIP_CHECK(hipMemcpyAsync(ref_dev, t.ref.ptr, (size_t)3 * t.n * sizeof(double), hipMemcpyDeviceToDevice, sys.stream()));
     }
     // emdee_md_set_ewald, emdee_md_set_pme: all or nothing -- every refusal comes before the setting changes.  check(): the host
     // test of the setting; set(): EwaldRecip's setter (the mesh takes the place of the direct sum)

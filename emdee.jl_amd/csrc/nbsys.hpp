@@ -14,6 +14,7 @@
 #include "minimize.hpp"
 #include "observables.hpp"
 #include "plan.hpp"
+#include "restraint.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
 #include "thermostat.hpp"
@@ -50,8 +51,10 @@ static inline void refuse_experiment_switches() {
 // T_RDF: the four stages of a sample of the radial distribution functions (rdf.hpp): count, scan, fill, pair loop
 // T_MSD: the three launches of a sample of the displacement and velocity correlations (msd.hpp): gather, accumulate, finish
 // T_GK: the launches a sample of the Green-Kubo observables adds to the tensor pass (gk.hpp): the box sums, the heat sums, push, correlate
+// T_RESTRAINTS: the launch the position restraints add to every force pass, and the scaling of their references (restraint.hpp)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
-               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_GK = 16, T_COUNT = 17 };
+               T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_GK = 16, T_RESTRAINTS = 17,
+               T_COUNT = 18 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -462,6 +465,11 @@ struct NbSystem {
                                vel.ptr, s, (real)vscale, scale_vel, rel_grid(rel_now, cell_sorted.ptr),
                                molecular ? (const unsigned char *)tables->r_member.ptr : (const unsigned char *)nullptr,
                                molecular ? (const int *)perm.ptr : (const int *)nullptr);
+            if (has_restraints() && tables->restraints.n > 0) {   // (the references follow the box: ref <- lo + mu (ref - lo))
+                Timed t(this, T_RESTRAINTS);
+                hipLaunchKernelGGL(k_restraint_scale, dim3(blocks_for(tables->restraints.n, 256)), dim3(256), 0, stream(), tables->restraints.n,
+                                   tables->restraints.ref.ptr, s);
+            }
         }
         const double nl[3] = {mu[0] * len[0], mu[1] * len[1], mu[2] * len[2]};
         set_box(lo, nl, per);                                // (a changed box invalidates the sort, the list and the plan ...)
@@ -897,7 +905,7 @@ struct NbSystem {
     bool has_bonded() const { return tables->has_bonded; }
     // terms added behind a whole force pass (add_post_terms): such a box steps in the split form (force pass, these terms,
     // kick + drift), not the fused one
-    bool has_post() const { return has_14() || has_bonded() || has_charges(); }
+    bool has_post() const { return has_14() || has_bonded() || has_charges() || has_restraints(); }
     // rows the filter visits right after every build: excluded pairs are struck, 1-4 and bonded partners' slots recorded
     bool filters_rows() const { return has_excl() || has_bonded(); }
     // a bonded term whose partner was missing from the rows (raised by k_bonded): the engine refuses to step until the tables or
@@ -1214,10 +1222,62 @@ struct NbSystem {
         }, [&](int w, int64_t site) { return topo::vsite_message(t.atoms_h, site, text[w]); });
     }
 
+    // ---------------------------------------------------------------- position restraints (Topology::set_restraints; restraint.hpp)
+    // One launch behind a force pass, one thread per table entry; each atom owns its whole term.  Undivided engines only.
+    bool has_restraints() const { return tables->restraints.present; }
+    RestraintArgs<real> restraint_args(const int *atoms, int n) const {
+        const Topology::RestraintTable &t = tables->restraints;
+        RestraintArgs<real> a{};
+        a.n = n; a.n_owned = n_owned; a.n_total = n_total;
+        a.atoms = atoms; a.ref = t.ref.ptr; a.k = t.geom.ptr; a.flat = t.flat.ptr;
+        a.inv_perm = inv_perm.ptr; a.img = img.ptr; a.rec = rec.ptr;
+        a.rel = rel_grid(rel_now, cell_sorted.ptr);
+        for (int d = 0; d < 3; d++) a.len[d] = (double)grid.len[d];
+        a.pitch = pitch;
+        return a;
+    }
+    RestraintArgs<real> restraint_args() const { return restraint_args(tables->restraints.atoms.ptr, tables->restraints.n); }
+    // a table set for another atom count stays in force, unused, as charges do: whatever would evaluate it refuses
+    void require_restraints_fit(const char *what) const {
+        const Topology::RestraintTable &t = tables->restraints;
+        EMDEE_REQUIRE(!stale(t) && !has_ghosts && tables == &own_tables, EMDEE_ERR_STATE, "%s: position restraints set for %lld atoms, the state "
+                      "holds %d (or has ghosts): set them again or clear them (emdee_md_set_restraints)", what, (long long)t.limit, n_owned);
+    }
+    void add_restraints(const Pass<real> &p) {
+        if (!has_restraints() || n_total == 0) return;
+        require_restraints_fit("force pass");
+        EMDEE_REQUIRE(!p.to_caller(), EMDEE_ERR_STATE, "position restraints are not on the operator path");
+        if (tables->restraints.n == 0) return;
+        Timed t(this, T_RESTRAINTS);
+        with_bool(p.mask & EMDEE_TENSOR, [&](auto tensor) {
+            hipLaunchKernelGGL((k_restraints<real, decltype(tensor)::value>), dim3(blocks_for(tables->restraints.n, 256)), dim3(256), 0, stream(),
+                               restraint_args(), p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
+        });
+    }
+    // a candidate table's references <- its atoms' current unwrapped coordinates (Topology::set_restraints, ref NULL)
+    void capture_restraint_refs(const int *atoms, double *ref, int n) {
+        hipLaunchKernelGGL((k_restraint_capture<real>), dim3(blocks_for(n, 256)), dim3(256), 0, stream(), restraint_args(atoms, n), ref);
+    }
+    // emdee_md_restraint_sums, blocking: out[0] = sum U, out[1..6] = the sum of the tensors, out[7] = the largest |d|; fp64 in a fixed
+    // order that depends on the number of entries alone
+    DevBuf<double> rpartial;
+    void restraint_sums(double out[RESTRAINT_WORDS]) {
+        for (int q = 0; q < RESTRAINT_WORDS; q++) out[q] = 0.0;
+        if (!has_restraints() || tables->restraints.n == 0) return;
+        require_restraints_fit("restraint_sums");
+        const int nb = std::min((int)blocks_for(tables->restraints.n, RED_BLOCK), RED_MAX_BLOCKS);
+        rpartial.ensure((size_t)RESTRAINT_WORDS * RED_MAX_BLOCKS + RESTRAINT_WORDS);
+        double *tot = rpartial.ptr + (size_t)RESTRAINT_WORDS * RED_MAX_BLOCKS;
+        hipLaunchKernelGGL((k_restraint_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), restraint_args(), rpartial.ptr);
+        hipLaunchKernelGGL(k_restraint_final, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)rpartial.ptr, tot);
+        read_back_doubles(out, tot, RESTRAINT_WORDS);
+    }
+
     void add_post_terms(const Pass<real> &p) {
         add_pairs14(p);
         add_bonded(p);
         add_ewald(p);
+        add_restraints(p);
     }
 
     // ---------------------------------------------------------------- forces

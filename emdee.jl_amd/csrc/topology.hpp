@@ -1,4 +1,5 @@
-// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, hbonds clusters, charges.  Plain C++17 on
+// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, hbonds clusters, virtual sites,
+// position restraints, charges.  Plain C++17 on
 // std::vector, no HIP: every function here validates or builds and throws through EMDEE_REQUIRE before it returns anything, so
 // a stand-alone host program can test it (tests/c/topology_host.cpp).  topology_dev.hpp holds the device buffers.
 #pragma once
@@ -332,11 +333,12 @@ inline std::string hbonds_message(const std::vector<int32_t> &atoms, int64_t clu
 // ---- virtual interaction sites (emdee_md_set_vsites; vsite.hpp): {site, a, b, c} ids per entry, c = -1 for a two-parent site,
 // and the weights {w_b, w_c} (w_c ignored where c = -1)
 // The table as a caller gave it: ids in [0, lim) (c may be -1), no atom named twice within an entry, no atom that is a site in two
-// entries, no site that is a parent of another site, no site that the rigid or the hbonds table in force names (`rigid`, `hbonds`:
-// their ids; NULL: none in force), the weights in use finite; else refused.  Parents may belong to either table.
+// entries, no site that is a parent of another site, no site that the rigid, the hbonds or the restraint table in force names (`rigid`,
+// `hbonds`, `restrained`: their ids; NULL: none in force), the weights in use finite; else refused.  Parents may belong to any table.
 template <typename T>
 std::vector<int32_t> checked_vsites(const std::vector<T> &raw, const std::vector<double> &weights, int64_t lim,
-                                    const std::vector<int32_t> *rigid = nullptr, const std::vector<int32_t> *hbonds = nullptr) {
+                                    const std::vector<int32_t> *rigid = nullptr, const std::vector<int32_t> *hbonds = nullptr,
+                                    const std::vector<int32_t> *restrained = nullptr) {
     const int64_t n = (int64_t)(raw.size() / 4);
     EMDEE_REQUIRE((int64_t)weights.size() == 2 * n, EMDEE_ERR_INVALID, "set_vsites: %lld sites but %lld weights", (long long)n, (long long)weights.size());
     EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_vsites: %lld sites (at most (2^31 - 1) / 4)", (long long)n);
@@ -369,6 +371,14 @@ std::vector<int32_t> checked_vsites(const std::vector<T> &raw, const std::vector
     }
     const std::vector<int32_t> *const held[2] = {rigid, hbonds};
     const char *const holder[2] = {"a molecule of the rigid table in force (emdee_md_set_rigid3)", "a cluster of the hbonds table in force (emdee_md_set_hbonds)"};
+    if (restrained) {                                        // (the mirror of restraint_table's refusal)
+        std::vector<int32_t> taken(*restrained);
+        std::sort(taken.begin(), taken.end());
+        for (const auto &s : sites)
+            EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)s.first), EMDEE_ERR_INVALID, "set_vsites: atom %lld, the site of "
+                          "entry %lld, is named by the restraint table in force (emdee_md_set_restraints): a site is massless and follows its "
+                          "parents, it cannot be restrained", (long long)s.first, (long long)s.second);
+    }
     for (int t = 0; t < 2; t++) {
         if (!held[t]) continue;
         std::vector<int32_t> taken(*held[t]);
@@ -443,6 +453,82 @@ inline std::string vsite_message(const std::vector<int32_t> &atoms, int64_t entr
     snprintf(text, sizeof(text), "virtual site %lld (atoms %d %d %d %d): %s", (long long)entry, in ? atoms[(size_t)4 * entry] : -1,
              in ? atoms[(size_t)4 * entry + 1] : -1, in ? atoms[(size_t)4 * entry + 2] : -1, in ? atoms[(size_t)4 * entry + 3] : -1, what);
     return text;
+}
+
+// ---- position restraints (emdee_md_set_restraints; restraint.hpp): one caller id, three references, three spring constants and one
+// flat-bottom radius per entry
+// The table as the kernels read it, in the caller's order.
+struct RestraintRows {
+    std::vector<int32_t> atoms;
+    std::vector<double> ref, k, flat;
+};
+// The table as a caller gave it: ids in [0, lim), no atom named twice, every constant and radius finite and >= 0, every reference
+// finite, a flat-bottomed entry (r0 > 0) with at least one non-zero constant and all its non-zero constants equal, no entry that is a
+// site of the site table in force (`vsites`: its {site, a, b, c} ids; NULL: none in force); else refused, the text naming the entry.
+// ref empty: the engine fills the references from the atoms' positions; flat empty: every radius is 0.
+template <typename T>
+RestraintRows restraint_table(const std::vector<T> &ids, const std::vector<double> &ref, const std::vector<double> &k,
+                              const std::vector<double> &flat, int64_t lim, const std::vector<int32_t> *vsites = nullptr) {
+    const int64_t n = (int64_t)ids.size();
+    EMDEE_REQUIRE((int64_t)k.size() == 3 * n, EMDEE_ERR_INVALID, "set_restraints: %lld entries but %lld spring constants (three per entry)",
+                  (long long)n, (long long)k.size());
+    EMDEE_REQUIRE(ref.empty() || (int64_t)ref.size() == 3 * n, EMDEE_ERR_INVALID, "set_restraints: %lld entries but %lld reference "
+                  "coordinates (three per entry)", (long long)n, (long long)ref.size());
+    EMDEE_REQUIRE(flat.empty() || (int64_t)flat.size() == n, EMDEE_ERR_INVALID, "set_restraints: %lld entries but %lld flat-bottom radii",
+                  (long long)n, (long long)flat.size());
+    EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_restraints: %lld entries (at most (2^31 - 1) / 3)", (long long)n);
+    std::vector<std::pair<int64_t, int64_t>> named;          // (id, entry)
+    named.reserve((size_t)n);
+    for (int64_t e = 0; e < n; e++) {
+        const int64_t g = ids[(size_t)e];
+        EMDEE_REQUIRE(g >= 0 && g < lim, EMDEE_ERR_INVALID, "set_restraints: entry %lld names id %lld, outside [0, %lld)", (long long)e,
+                      (long long)g, (long long)lim);
+        named.emplace_back(g, e);
+    }
+    std::sort(named.begin(), named.end());
+    for (size_t q = 1; q < named.size(); q++)
+        EMDEE_REQUIRE(named[q].first != named[q - 1].first, EMDEE_ERR_INVALID, "set_restraints: atom %lld is named twice (entries %lld and "
+                      "%lld)", (long long)named[q].first, (long long)named[q - 1].second, (long long)named[q].second);
+    for (int64_t e = 0; e < n; e++) {
+        const double *q = k.data() + 3 * (size_t)e;
+        const double r0 = flat.empty() ? 0.0 : flat[(size_t)e];
+        for (int a = 0; a < 3; a++)
+            EMDEE_REQUIRE(std::isfinite(q[a]) && q[a] >= 0.0, EMDEE_ERR_INVALID, "set_restraints: entry %lld (atom %lld) has a spring constant "
+                          "on axis %d that is not finite and >= 0", (long long)e, (long long)ids[(size_t)e], a);
+        EMDEE_REQUIRE(std::isfinite(r0) && r0 >= 0.0, EMDEE_ERR_INVALID, "set_restraints: entry %lld (atom %lld) has a flat-bottom radius that "
+                      "is not finite and >= 0", (long long)e, (long long)ids[(size_t)e]);
+        if (!ref.empty())
+            for (int a = 0; a < 3; a++)
+                EMDEE_REQUIRE(std::isfinite(ref[3 * (size_t)e + a]), EMDEE_ERR_INVALID, "set_restraints: entry %lld (atom %lld) has a reference "
+                              "on axis %d that is not finite", (long long)e, (long long)ids[(size_t)e], a);
+        if (r0 > 0.0) {
+            double kk = 0.0;
+            for (int a = 0; a < 3; a++)
+                if (q[a] > 0.0) {
+                    EMDEE_REQUIRE(kk == 0.0 || q[a] == kk, EMDEE_ERR_INVALID, "set_restraints: entry %lld (atom %lld) is flat-bottomed (r0 = %g) "
+                                  "with unequal non-zero spring constants %g and %g: the well is a sphere, a cylinder or a slab of one constant",
+                                  (long long)e, (long long)ids[(size_t)e], r0, kk, q[a]);
+                    kk = q[a];
+                }
+            EMDEE_REQUIRE(kk > 0.0, EMDEE_ERR_INVALID, "set_restraints: entry %lld (atom %lld) is flat-bottomed (r0 = %g) with no non-zero "
+                          "spring constant", (long long)e, (long long)ids[(size_t)e], r0);
+        }
+    }
+    if (vsites) {
+        std::vector<int32_t> taken;
+        for (size_t s = 0; s + 3 < vsites->size(); s += 4) taken.push_back((*vsites)[s]);
+        std::sort(taken.begin(), taken.end());
+        for (int64_t e = 0; e < n; e++)
+            EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)ids[(size_t)e]), EMDEE_ERR_STATE, "set_restraints: atom %lld "
+                          "of entry %lld is a virtual site of the table in force (emdee_md_set_vsites): a site is massless and follows its "
+                          "parents, it cannot be restrained", (long long)ids[(size_t)e], (long long)e);
+    }
+    RestraintRows t;
+    t.atoms.assign(ids.begin(), ids.end());
+    t.ref = ref;
+    t.k = k;
+    t.flat = flat.empty() ? std::vector<double>((size_t)n, 0.0) : flat;
+    return t;
 }
 
 // ---- charges and the reaction-field constants

@@ -192,7 +192,8 @@ struct Topology {
         EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_vsites: %lld sites (at most (2^31 - 1) / 4)", (long long)n);
         VsiteTable t;
         t.atoms_h = topo::checked_vsites(fetch(atoms_dev, (size_t)4 * n, s), fetch(weights_dev, (size_t)2 * n, s), lim,
-                                         rigid.present ? &rigid.atoms_h : nullptr, hbonds.present ? &hbonds.atoms_h : nullptr);
+                                         rigid.present ? &rigid.atoms_h : nullptr, hbonds.present ? &hbonds.atoms_h : nullptr,
+                                         restraints.present ? &restraints.atoms_h : nullptr);
         const std::vector<double> w = topo::vsite_weights(t.atoms_h, fetch(weights_dev, (size_t)2 * n, s));
         const topo::VsiteParents par = topo::build_vsite_parents(t.atoms_h, w);
         put(t.atoms, t.atoms_h, s); put(t.geom, w, s);
@@ -205,6 +206,40 @@ struct Topology {
         vsites.esite.swap(t.esite); vsites.eweight.swap(t.eweight);
         vsites.atoms_h = t.atoms_h;
         vsites.n = t.n; vsites.n_parents = t.n_parents; vsites.limit = lim; vsites.present = true;
+    }
+
+    // ---- position restraints (emdee_md_set_restraints; restraint.hpp), undivided engines only: one caller id (GroupTable: atoms), three
+    // spring constants (geom), three references and one flat-bottom radius per entry, in the caller's order.  The references follow the
+    // box (NbSystem::scale_box), so they live on the device alone.
+    struct RestraintTable : GroupTable {
+        DevBuf<double> ref, flat;
+    };
+    RestraintTable restraints;
+    // Replaces the table by the n entries at the device arrays (ref_dev NULL: capture(atoms, ref) fills the uploaded candidate's
+    // references from the state, queued on s; flat_dev NULL: every radius 0); n = 0 clears it.  Every refusal comes before the table
+    // in force changes.
+    template <class Capture>
+    void set_restraints(const int32_t *atoms_dev, const double *ref_dev, const double *k_dev, const double *flat_dev, int64_t n, int64_t lim,
+                        hipStream_t s, Capture &&capture) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || (atoms_dev && k_dev)), EMDEE_ERR_INVALID, "set_restraints: negative count or NULL array (atoms and "
+                      "spring constants are needed with n > 0)");
+        if (n == 0) {
+            restraints.present = false; restraints.n = 0; restraints.atoms_h.clear();
+            return;
+        }
+        EMDEE_REQUIRE(n <= INT32_MAX / 3, EMDEE_ERR_INVALID, "set_restraints: %lld entries (at most (2^31 - 1) / 3)", (long long)n);
+        const topo::RestraintRows rows = topo::restraint_table(fetch(atoms_dev, (size_t)n, s), ref_dev ? fetch(ref_dev, (size_t)3 * n, s) : std::vector<double>(),
+                                                               fetch(k_dev, (size_t)3 * n, s), flat_dev ? fetch(flat_dev, (size_t)n, s) : std::vector<double>(),
+                                                               lim, vsites.present ? &vsites.atoms_h : nullptr);
+        RestraintTable t;
+        put(t.atoms, rows.atoms, s); put(t.geom, rows.k, s); put(t.flat, rows.flat, s);
+        t.ref.ensure((size_t)3 * n + 1);
+        if (ref_dev) put(t.ref, rows.ref, s); else capture((const int *)t.atoms.ptr, t.ref.ptr, (int)n);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        restraints.atoms.swap(t.atoms); restraints.geom.swap(t.geom); restraints.flat.swap(t.flat); restraints.ref.swap(t.ref);
+        restraints.atoms_h = rows.atoms;
+        restraints.n = (int)n; restraints.limit = lim; restraints.present = true;
     }
 
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the

@@ -225,6 +225,20 @@ def rigid_triatomics(types, bonds, table, length_unit=1.0, with_dropped=False):
     return out + (arr(drop_b, 2), arr(drop_a, 3)) if with_dropped else out
 
 
+def heavy_atoms(types, table, skip=()):
+    """The ids (ascending, int64) of the atoms that are not hydrogen and not in `skip`: the usual selection of a position-restraint
+    table (emdee_md_set_restraints), with the waters found by rigid_triatomics passed as skip (any nesting of ids).  An atom is a
+    hydrogen by the element of its type in the force-field file (`table`: a BondedTable), or, where the file names none, by a
+    mass below 1.5."""
+    skipped = set(int(i) for i in np.asarray(skip, dtype=np.int64).reshape(-1))
+
+    def hydrogen(t):
+        if t in table.elements:
+            return table.elements[t].strip().upper() == "H"
+        return t in table.masses and table.masses[t] < 1.5
+    return np.array([i for i, t in enumerate(types) if i not in skipped and not hydrogen(t)], dtype=np.int64)
+
+
 def bisector_sites(sites, molecules, d_leg, d_base, d_om):
     """The site table (emdee_md_set_vsites) of a fourth site on the bisector of rigid three-site molecules, at d_om from the apex
     towards the legs: sites (n,) the ids of the massless sites, molecules (n, 3) ids {apex, a, b} (rigid_triatomics' first result),

@@ -6,6 +6,7 @@ export set_thermostat!, thermostat_state, set_thermostat_state!, thermostat_draw
 export set_rdf!, rdf_sample!, rdf_reset!, rdf_read
 export set_msd!, msd_sample!, msd_reset!, msd_read
 export set_gk!, gk_sample!, gk_reset!, gk_read
+export set_restraints!, restraint_sums, restraint_refs!
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -110,6 +111,32 @@ set_hbonds!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, dist::U
 set_vsites!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,2}}, weights::Union{Nothing,HipArray{Float64,2}}=nothing) =
     check(ccall((:emdee_md_set_vsites, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
                 atoms === nothing ? C_NULL : atoms.ptr, weights === nothing ? C_NULL : weights.ptr, atoms === nothing ? 0 : size(atoms, 2)))
+
+# int32_t emdee_md_set_restraints(emdee_md *md, const int32_t *atoms_dev, const double *ref_dev, const double *k_dev,
+#                                 const double *flat_dev, int32_t n);
+# Position restraints: atoms a device Int32 vector of n caller ids (0-based), k a device Float64 matrix (3, n) of the spring constants
+# per axis, ref a device Float64 matrix (3, n) in the coordinates the state is read back in (unwrapped; `nothing`: every named atom's
+# current position), flat a device Float64 vector of the flat-bottom radii (`nothing`: all zero).  U = 1/2 sum k_a d_a^2, or
+# 1/2 k max(0, rho - r0)^2 with rho over the axes with k_a > 0.  The references follow the box (scale_box!, the barostats).  Evaluates
+# the forces again; atoms = `nothing` clears the table.
+set_restraints!(md::VelocityVerlet, atoms::Union{Nothing,HipArray{Int32,1}}, k::Union{Nothing,HipArray{Float64,2}}=nothing;
+                ref::Union{Nothing,HipArray{Float64,2}}=nothing, flat::Union{Nothing,HipArray{Float64,1}}=nothing) =
+    check(ccall((:emdee_md_set_restraints, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
+                atoms === nothing ? C_NULL : atoms.ptr, ref === nothing ? C_NULL : ref.ptr, k === nothing ? C_NULL : k.ptr,
+                flat === nothing ? C_NULL : flat.ptr, atoms === nothing ? 0 : length(atoms)))
+
+# int32_t emdee_md_restraint_sums(emdee_md *md, double out[EMDEE_RESTRAINT_WORDS]);
+# (blocking) [1] the restraint energy, [2:7] the sum of the restraint tensors (xx, yy, zz, xy, xz, yz), [8] the largest |x - ref|
+function restraint_sums(md::VelocityVerlet)
+    out = zeros(Float64, 8)
+    check(ccall((:emdee_md_restraint_sums, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, out))
+    return out
+end
+
+# int32_t emdee_md_get_restraint_refs(emdee_md *md, double *ref_dev);
+# The references as they now stand (they follow the box), into a device Float64 matrix (3, n), table order.
+restraint_refs!(md::VelocityVerlet, out::HipArray{Float64,2}) =
+    (check(ccall((:emdee_md_get_restraint_refs, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), md.handle, out.ptr)); out)
 
 # int32_t emdee_md_minimize(emdee_md *md, int32_t max_iter, double f_tol, double dt_start, double dt_max, double max_step,
 #                           emdee_minimize_result *out);

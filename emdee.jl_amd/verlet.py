@@ -31,6 +31,7 @@ _THERMOSTATS = {"off": THERMOSTAT_OFF, "v-rescale": THERMOSTAT_VRESCALE, "vresca
 MSD, VACF, MSD_WORDS = 1, 2, 7
 # Green-Kubo observables (include/emdee_hip.h: emdee_md_set_gk)
 GK_STRESS, GK_HEAT, GK_WORDS = 1, 2, 9
+RESTRAINT_WORDS = 8                                        # (EMDEE_RESTRAINT_WORDS)
 
 
 def _three(v):
@@ -84,7 +85,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            "msd": 16,
            # the launches every sample of the Green-Kubo observables adds to the tensor pass (gk_sample_): 4 per mask bit alone
            # (5 for the stress of an engine with rigid molecules), 6 with both
-           "green_kubo": 17}
+           "green_kubo": 17,
+           # the launch the position restraints add to every force pass, and the scaling of their references (set_restraints_)
+           "restraints": 18}
 
 
 class MinimizeResult:
@@ -662,6 +665,54 @@ class VelocityVerlet:
             raise ValueError("set_vsites_: %d sites but %d rows of weights" % (a.shape[0], w.shape[0]))
         _lib.call("emdee_md_set_vsites", self._handle, C.c_void_p(a.data_ptr()) if a.numel() else None,
                   C.c_void_p(w.data_ptr()) if w.numel() else None, int(a.shape[0]))
+
+    # -- position restraints (include/emdee_hip.h: emdee_md_set_restraints; undivided engines)
+    _restraints = 0                                        # entries of the table in force
+
+    def set_restraints_(self, atoms, k, ref=None, flat=None):
+        """Position restraints (include/emdee_hip.h emdee_md_set_restraints): atoms (n,) caller ids; k the spring constants, a
+        scalar, (n,) or (n, 3) per axis; ref (n, 3) in the coordinates state() returns (unwrapped; None: every named atom's current
+        position); flat (n,) the flat-bottom radii r0 (None: all zero -- harmonic).  U = 1/2 sum k_a d_a^2, or 1/2 k max(0, rho -
+        r0)^2 with rho over the axes with k_a > 0.  The references follow the box (scale_box_, the barostats).  Evaluates the forces
+        again.  Empty or None atoms clears the table."""
+        a = torch.as_tensor(atoms if atoms is not None else []).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(a.shape[0])
+        kk = torch.as_tensor(k if k is not None else 0.0, dtype=torch.float64).to(device=self.device)
+        if kk.dim() == 0:
+            kk = kk.reshape(1, 1).expand(n, 3)
+        elif kk.dim() == 1 and kk.shape[0] == n:
+            kk = kk.reshape(n, 1).expand(n, 3)
+        elif kk.dim() != 2 or tuple(kk.shape) != (n, 3):
+            raise ValueError("set_restraints_: k is a scalar, (n,) or (n, 3) for n = %d atoms, got %s" % (n, tuple(kk.shape)))
+        kk = kk.contiguous()
+        r = f = None
+        if ref is not None:
+            r = torch.as_tensor(ref, dtype=torch.float64).to(device=self.device).contiguous()
+            if tuple(r.shape) != (n, 3):
+                raise ValueError("set_restraints_: ref must have shape (%d, 3), got %s" % (n, tuple(r.shape)))
+        if flat is not None:
+            f = torch.as_tensor(flat, dtype=torch.float64).to(device=self.device).contiguous()
+            if tuple(f.shape) != (n,):
+                raise ValueError("set_restraints_: flat must have shape (%d,), got %s" % (n, tuple(f.shape)))
+        _lib.call("emdee_md_set_restraints", self._handle, C.c_void_p(a.data_ptr()) if n else None,
+                  C.c_void_p(r.data_ptr()) if (r is not None and n) else None, C.c_void_p(kk.data_ptr()) if n else None,
+                  C.c_void_p(f.data_ptr()) if (f is not None and n) else None, n)
+        self._restraints = n
+
+    def restraint_sums(self):
+        """(8,) float64 numpy (blocking): [0] the restraint energy, [1:7] the sum of the restraint tensors (xx, yy, zz, xy, xz,
+        yz), [7] the largest |x - ref| over the table.  Zeros without a table."""
+        import numpy as np
+        out = np.zeros(RESTRAINT_WORDS, dtype=np.float64)
+        _lib.call("emdee_md_restraint_sums", self._handle, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def restraint_refs(self):
+        """The references as they now stand (they follow the box): (n, 3) float64 tensor on the device, table order."""
+        out = torch.zeros((self._restraints, 3), dtype=torch.float64, device=self.device)
+        if self._restraints:
+            _lib.call("emdee_md_get_restraint_refs", self._handle, C.c_void_p(out.data_ptr()))
+        return out
 
     def close(self):
         if self._handle is not None:

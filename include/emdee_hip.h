@@ -678,7 +678,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat);
  * 15 = the four stages of every sample of the radial distribution functions (emdee_md_rdf_sample);
  * 16 = the three launches of every sample of the displacement and velocity correlations (emdee_md_msd_sample);
- * 17 = the launches every sample of the Green-Kubo observables adds to the tensor pass (emdee_md_gk_sample).
+ * 17 = the launches every sample of the Green-Kubo observables adds to the tensor pass (emdee_md_gk_sample);
+ * 18 = the launch the position restraints add to every force pass, and the scaling of their references (emdee_md_set_restraints).
  * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
@@ -961,6 +962,57 @@ int32_t emdee_md_set_gk(emdee_md *md, int32_t what, int32_t n_lags);
 int32_t emdee_md_gk_sample(emdee_md *md);
 int32_t emdee_md_gk_read(emdee_md *md, double *sums, double totals[9], double last[9], int64_t *samples);
 int32_t emdee_md_gk_reset(emdee_md *md);
+
+/* ---- position restraints: harmonic and flat-bottomed, scaled with the box (restraint.hpp)
+ * An external field that ties the named atoms to reference points: the stage of an equilibration in which a solute is held near its
+ * starting structure while the solvent relaxes, a slab pinned along one axis, a droplet kept off an open face.  With a table in force
+ * the potential energy and the stress of the engine hold an EXTERNAL FIELD: emdee_md_energies, _pressure_tensor, _virial_tensor,
+ * _get_state, the barostats and the Green-Kubo stress take the term with the rest, momentum is no longer conserved and the pressure
+ * is that of the atoms in the field.
+ * emdee_md_set_restraints (blocking, the device arrays are copied; n = 0 clears the table):
+ *   atoms_dev  n caller ids.
+ *   ref_dev    3 n doubles in the coordinates emdee_md_get_state returns: the caller's image, unwrapped; a reference may lie outside the
+ *              box.  NULL: every named atom's current position (d = 0 exactly, in both precisions).
+ *   k_dev      3 n doubles, the spring constants per axis, each finite and >= 0.
+ *   flat_dev   n doubles, the flat-bottom radius r0 >= 0.  NULL: all zero.
+ * The term of one atom: d = x_unwrapped - ref, formed in fp64 in both precisions from the record and the per-axis image count (a Float32
+ * engine adds its cell origin in double); no minimum image, so an atom that walks through a box face or is re-sorted by a rebuild sees
+ * a continuous force.  r0 = 0: U = 1/2 sum_a k_a d_a^2, f_a = -k_a d_a.  r0 > 0: the non-zero constants of the entry are one value k,
+ * rho is the norm of d over the axes with k_a > 0 (the well is a sphere, a cylinder or a slab), U = 1/2 k max(0, rho - r0)^2, the force
+ * points along the masked d and is exactly 0 inside the well.  The atom owns the whole term: its energy plane gets U, its virial plane
+ * d . f, its tensor the symmetrised d (x) f in the component order of emdee_compute_virial_tensor, its force plane f, each only when the
+ * pass's mask asks for it.  No atomics: bitwise reproducible.
+ * The references follow the box: emdee_md_scale_box and every barostat event map ref <- lo + mu (ref - lo) per axis (GROMACS's
+ * refcoord_scaling = all), so that with atom-by-atom scaling d -> mu d and tr W_restr = -dU_restr/dmu; with molecular scaling the
+ * molecular virial holds the restraint force with the others.
+ * With a table the engine steps in the split form, never the fused one: kick + drift, the force pass with the restraint launch behind
+ * it, kick.  Every step closes its own half kick, as the steps of an engine with constraints, a barostat or a thermostat do, so the
+ * state after s steps does not depend on how the s steps were dealt to calls: step(40), 8 x step(5) and 40 x step(1) agree bit for
+ * bit.  emdee_md_minimize needs nothing new.  An engine without a table is bit for bit and launch for
+ * launch what it was.  On success the forces are evaluated again: planes and table belong together on return.
+ * Degrees of freedom: the library's own count (emdee_md_set_thermostat with n_dof = 0) still subtracts 3 for the centre of mass, which a
+ * restrained system does not conserve; a caller who restrains atoms may pass n_dof explicitly.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: a NULL atoms_dev or k_dev with n > 0; n < 0; an id outside
+ *     [0, n_owned); an atom named twice; a constant or radius that is not finite and >= 0; a reference that is not finite; r0 > 0 with
+ *     unequal non-zero constants, or with no non-zero constant.  The text names the entry.
+ *   - EMDEE_ERR_STATE, the previous table in force: a call before emdee_md_set_state; ghosts; an integrator lent by emdee_dd_engine; an
+ *     entry that is a virtual site of the table in force (and emdee_md_set_vsites refuses a site that this table names); a state loaded
+ *     without velocities.
+ *   - The table survives an emdee_md_set_state with the same atom count, references kept.  After a state with another count
+ *     emdee_md_step, emdee_md_minimize, emdee_md_scale_box and the reads refuse (EMDEE_ERR_STATE) until the table is set again or cleared.
+ *   - The Green-Kubo heat flux (EMDEE_GK_HEAT) is refused with a restraint table, at set and at sample.
+ * emdee_md_restraint_sums (blocking): out[0] = sum U, out[1..6] = the sum of the tensors (xx, yy, zz, xy, xz, yz), out[7] = the largest
+ * |d| (all three axes) over the table; fp64 in a fixed order that depends on n alone.  All zero without a table.
+ * emdee_md_get_restraint_refs: the references as they now stand (after an NPT stage, for a restart), 3 n doubles in table order to
+ * ref_dev, queued on the context's stream; nothing is written without a table.
+ * Device time: emdee_md_kernel_time index 18.
+ * Scope: undivided engines; no emdee_dd_* counterpart.  No restraints on centres of mass, no distance or dihedral restraints, no
+ * time-dependent references. */
+#define EMDEE_RESTRAINT_WORDS 8
+int32_t emdee_md_set_restraints(emdee_md *md, const int32_t *atoms_dev, const double *ref_dev, const double *k_dev,
+                                const double *flat_dev, int32_t n);
+int32_t emdee_md_restraint_sums(emdee_md *md, double out[EMDEE_RESTRAINT_WORDS]);
+int32_t emdee_md_get_restraint_refs(emdee_md *md, double *ref_dev);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
