@@ -1,7 +1,7 @@
 // gk.hpp -- Green-Kubo observables on the device (emdee_md_set_gk, emdee_md_gk_sample): per sample nine fp64 words -- the five
 // independent traceless components of the stress S = K + W, its trace / 3, and the heat flux J -- a ring of them in HBM, and a
 // correlator that adds A_w(s) A_w(s - l) to the lag sums with nothing read back.  The stress words come from the twelve box sums of
-// the pressure entries (k_tensor_partials / k_final_sums, kernels.hpp), the heat flux from one more reduction of their shape over the
+// the pressure entries (TensorSums, kernels.hpp, through reduce.hpp), the heat flux from one more reduction of that shape over the
 // tensor pass's per-atom energies and tensors and the velocities.  The parts with no HIP in them -- the six stress words, an atom's
 // three heat addends, the ring slot and the lag counts -- are plain C++ at the top, as the top of msd.hpp is: a stand-alone host
 // program tests them with the host compiler (tests/c/gk_host.cpp); the kernels below them need HIP.  DESIGN.md 4i has the algorithm;
@@ -63,18 +63,17 @@ EMDEE_HD long long gk_count(long long samples, int lag) { return samples > lag ?
 
 namespace emdee {
 
-// partial[b][0..2] = the heat addends of the owned slots of block b's stride, k_tensor_partials' shape: fp64 in both precisions,
-// fixed order, no atomics (k_final_sums completes them).  en, vt: the per-atom energies and tensors of the last tensor pass; vel: the
-// velocities k_energy_partials takes, no pending kick.
+// The term of the heat flux (reduce.hpp), over the owned slots, fp64 in both precisions: the three heat addends.  en, vt: the per-atom
+// energies and tensors of the last tensor pass; vel: the velocities EnergySums takes, no pending kick.
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_gk_heat_partials(int n, int n_owned, size_t pitch, const int *__restrict__ perm,
-                                                                 const real *__restrict__ en, const real *__restrict__ vt,
-                                                                 const real *__restrict__ vel, const real *__restrict__ inv_mass,
-                                                                 double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double s[GK_HEAT_WORDS] = {0.0, 0.0, 0.0};
-    for (int p = blockIdx.x * RED_BLOCK + threadIdx.x; p < n; p += gridDim.x * RED_BLOCK) {
-        if (perm[p] >= n_owned) continue;
+struct HeatSums {
+    static constexpr int SUMS = GK_HEAT_WORDS, MAXES = 0;
+    int n_owned;
+    size_t pitch;
+    const int *perm;
+    const real *en, *vt, *vel, *inv_mass;
+    __device__ __forceinline__ void operator()(int p, double *s) const {
+        if (perm[p] >= n_owned) return;
         real w[6], v[3];
 #pragma unroll
         for (int c = 0; c < 6; c++) w[c] = vt[c * pitch + p];
@@ -85,12 +84,7 @@ __global__ __launch_bounds__(RED_BLOCK) void k_gk_heat_partials(int n, int n_own
 #pragma unroll
         for (int d = 0; d < GK_HEAT_WORDS; d++) s[d] += term[d];
     }
-#pragma unroll
-    for (int d = 0; d < GK_HEAT_WORDS; d++) {
-        const double t = block_sum(s[d], sh);
-        if (threadIdx.x == 0) partial[GK_HEAT_WORDS * blockIdx.x + d] = t;
-    }
-}
+};
 
 // what a sample needs of the table: the mask, the ring, the sample's number; acc = sums (n_lags x 9), then totals (9), then last (9)
 struct GkArgs {

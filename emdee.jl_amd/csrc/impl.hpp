@@ -546,7 +546,7 @@ struct MdImpl : IMd {
     void thermostat_draws(uint64_t seed, uint64_t step, int64_t n_dof, double *out) override {
         use_device(sys.ctx);
         EMDEE_REQUIRE(n_dof >= 1, EMDEE_ERR_INVALID, "thermostat_draws: n_dof = %lld must be >= 1", (long long)n_dof);
-        double *part = sys.thermostat_words() + TH_WORDS;    // (scratch of the events, which the stream orders)
+        double *part = sys.red_partials();                   // (scratch of the box sums, which the stream orders)
         hipLaunchKernelGGL(k_thermostat_draws, dim3(1), dim3(64), 0, sys.stream(), (unsigned long long)seed, (unsigned long long)step,
                            (long long)n_dof, part);
         EMDEE_HIP_CHECK(hipGetLastError());
@@ -735,7 +735,6 @@ struct MdImpl : IMd {
         t.present = true; t.what = what; t.n_atoms = sys.n_owned; t.n_lags = n_lags;
         t.ring.ensure(t.ring_words());
         t.acc.ensure(t.acc_words());
-        t.heat.ensure((size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS + GK_HEAT_WORDS);
         install(gk, t);
     }
     // one sample: the forces (a rigid engine) and the tensor pass if they are not current, as the pressure entries evaluate them, then

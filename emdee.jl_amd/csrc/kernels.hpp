@@ -20,6 +20,7 @@
 #include "bonded.hpp"
 #include "common.hpp"
 #include "lj_pair.hpp"
+#include "reduce.hpp"
 #include "wave_ops.hpp"
 
 namespace emdee {
@@ -1563,35 +1564,20 @@ __global__ __launch_bounds__(256) void k_bonded(int n, int n_owned, size_t pitch
 }
 
 // ------------------------------------------------------------------------------------ reductions
-// Deterministic two-stage sums in fp64 (mixed precision: fp32 per-atom values, fp64 totals).
-constexpr int RED_BLOCK = 256;
-constexpr int RED_MAX_BLOCKS = 1024;
-
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    if (lane == WAVE - 1) sh[wv] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) for (int w = 0; w < RED_BLOCK / WAVE; w++) t += sh[w];
-    __syncthreads();
-    return t;   // valid in thread 0
-}
-
-// partial[b][0..2] = sum e, kinetic energy (with optional pending half kick c f/m), sum w
+// The two-stage fp64 sums are reduce.hpp's; here the terms of the energy and the tensor entries.
+// [0] = sum e, [1] = kinetic energy (with optional pending half kick c f/m), [2] = sum w
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_energy_partials(int n, int n_owned, size_t pitch,
-                                                                const int *__restrict__ perm,
-                                                                const real *__restrict__ en, const real *__restrict__ vir,
-                                                                const real *__restrict__ vel, const real *__restrict__ frc,
-                                                                const real *__restrict__ inv_mass, real c,
-                                                                double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double se = 0.0, sk = 0.0, sw = 0.0;
-    for (int p = blockIdx.x * RED_BLOCK + threadIdx.x; p < n; p += gridDim.x * RED_BLOCK) {
-        if (perm[p] >= n_owned) continue;
-        if (en) se += (double)en[p];
-        if (vir) sw += (double)vir[p];
+struct EnergySums {
+    static constexpr int SUMS = 3, MAXES = 0;
+    int n_owned;
+    size_t pitch;
+    const int *perm;
+    const real *en, *vir, *vel, *frc, *inv_mass;
+    real c;
+    __device__ __forceinline__ void operator()(int p, double *acc) const {
+        if (perm[p] >= n_owned) return;
+        if (en) acc[0] += (double)en[p];
+        if (vir) acc[2] += (double)vir[p];
         if (vel) {
             const real im = inv_mass ? inv_mass[p] : (real)1;
             double k2 = 0.0;
@@ -1599,39 +1585,23 @@ __global__ __launch_bounds__(RED_BLOCK) void k_energy_partials(int n, int n_owne
                 double v = (double)vel[d * pitch + p] + (double)(c * im) * (double)frc[d * pitch + p];
                 k2 += v * v;
             }
-            sk += im != (real)0 ? 0.5 * k2 / (double)im : 0.0;   // (a massless atom, a virtual site: exactly 0)
+            acc[1] += im != (real)0 ? 0.5 * k2 / (double)im : 0.0;   // (a massless atom, a virtual site: exactly 0)
         }
     }
-    double t;
-    t = block_sum(se, sh); if (threadIdx.x == 0) partial[3 * blockIdx.x] = t;
-    t = block_sum(sk, sh); if (threadIdx.x == 0) partial[3 * blockIdx.x + 1] = t;
-    t = block_sum(sw, sh); if (threadIdx.x == 0) partial[3 * blockIdx.x + 2] = t;
-}
+};
 
-static __global__ __launch_bounds__(RED_BLOCK) void k_final_sum3(int nblocks, const double *__restrict__ partial,
-                                                          double *__restrict__ out) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    for (int q = 0; q < 3; q++) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += RED_BLOCK) s += partial[3 * b + q];
-        double t = block_sum(s, sh);
-        if (threadIdx.x == 0) out[q] = t;
-    }
-}
-
-// Pressure tensor sums: partial[b][0..5] = sum of the owned atoms' virial tensors W_i, [6..11] = kinetic tensor
-// sum m_i v_i^a v_i^b (with the velocities k_energy_partials takes for its kinetic energy, no pending kick), both in the order
-// (xx, yy, zz, xy, xz, yz); fp64, fixed order, no atomics (k_final_sums completes them)
+// Pressure tensor sums: [0..5] = sum of the owned atoms' virial tensors W_i, [6..11] = kinetic tensor sum m_i v_i^a v_i^b (with the
+// velocities EnergySums takes for its kinetic energy, no pending kick), both in the order (xx, yy, zz, xy, xz, yz)
 constexpr int TENSOR_SUMS = 12;
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_tensor_partials(int n, int n_owned, size_t pitch, const int *__restrict__ perm,
-                                                                const real *__restrict__ vt, const real *__restrict__ vel,
-                                                                const real *__restrict__ inv_mass, double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double s[TENSOR_SUMS];
-    for (int q = 0; q < TENSOR_SUMS; q++) s[q] = 0.0;
-    for (int p = blockIdx.x * RED_BLOCK + threadIdx.x; p < n; p += gridDim.x * RED_BLOCK) {
-        if (perm[p] >= n_owned) continue;
+struct TensorSums {
+    static constexpr int SUMS = TENSOR_SUMS, MAXES = 0;
+    int n_owned;
+    size_t pitch;
+    const int *perm;
+    const real *vt, *vel, *inv_mass;
+    __device__ __forceinline__ void operator()(int p, double *s) const {
+        if (perm[p] >= n_owned) return;
         for (int c = 0; c < 6; c++) s[c] += (double)vt[c * pitch + p];
         if (vel) {
             const real im = inv_mass ? inv_mass[p] : (real)1;
@@ -1641,23 +1611,7 @@ __global__ __launch_bounds__(RED_BLOCK) void k_tensor_partials(int n, int n_owne
             s[9] += m * vx * vy; s[10] += m * vx * vz; s[11] += m * vy * vz;
         }
     }
-    for (int q = 0; q < TENSOR_SUMS; q++) {
-        const double t = block_sum(s[q], sh);
-        if (threadIdx.x == 0) partial[TENSOR_SUMS * blockIdx.x + q] = t;
-    }
-}
-
-// out[q] = sum over b of partial[b][q], q < nq (k_final_sum3 for any number of sums)
-static __global__ __launch_bounds__(RED_BLOCK) void k_final_sums(int nblocks, int nq, const double *__restrict__ partial,
-                                                                 double *__restrict__ out) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    for (int q = 0; q < nq; q++) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += RED_BLOCK) s += partial[(size_t)nq * b + q];
-        double t = block_sum(s, sh);
-        if (threadIdx.x == 0) out[q] = t;
-    }
-}
+};
 
 // per-atom tensors in caller order, owned atoms only: out[6 i + c] = vt[c][p] (i: k_unsort's caller index)
 template <typename real>

@@ -55,28 +55,6 @@ namespace emdee {
 // what one reduction brings back: sum G . v, sum v . v, sum G . G, then the largest |G_i|^2, |v_i|^2 and |w_i F_i|^2
 constexpr int FIRE_SUMS = 3, FIRE_MAXIMA = 3, FIRE_WORDS = FIRE_SUMS + FIRE_MAXIMA;
 
-// the largest of a wavefront's values, valid in lane 63: wave_sum_to_lane63's exchange with max in place of +.  A lane without a
-// source reads 0, which no value >= 0 minds.
-__device__ __forceinline__ double wave_max_to_lane63(double v) {
-    v = fmax(v, dpp_mov<DPP_ROW_SHR1, 0xf, 0xf>(v));
-    v = fmax(v, dpp_mov<DPP_ROW_SHR2, 0xf, 0xf>(v));
-    v = fmax(v, dpp_mov<DPP_ROW_SHR4, 0xf, 0xf>(v));
-    v = fmax(v, dpp_mov<DPP_ROW_SHR8, 0xf, 0xf>(v));
-    v = fmax(v, dpp_mov<DPP_ROW_BCAST15, 0xa, 0xf>(v));
-    v = fmax(v, dpp_mov<DPP_ROW_BCAST31, 0xc, 0xf>(v));
-    return v;
-}
-__device__ __forceinline__ double block_max(double v, double *sh) {
-    v = wave_max_to_lane63(v);
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    if (lane == WAVE - 1) sh[wv] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) for (int w = 0; w < RED_BLOCK / WAVE; w++) t = fmax(t, sh[w]);
-    __syncthreads();
-    return t;   // valid in thread 0
-}
-
 // mode 0: a = w F on every owned slot (the plane the velocity stages project, ConstraintArgs::vel); mode 1, after the projection:
 // a -> G = a / w where the projection changed a component, F itself where it did not (every atom outside the tables); 0 for an
 // atom with w = 0 (a virtual site, whose force has gone to its parents).
@@ -104,52 +82,28 @@ __global__ __launch_bounds__(256) void k_fire_weight(int n, int n_owned, size_t 
     a[2 * pitch + p] = bz == az ? fz : bz / w;
 }
 
-// partial[b][0..5] over the owned slots of block b's stride, k_tensor_partials' shape: fp64 in both precisions, fixed order, no
-// atomics (k_fire_final completes them).  g: the G planes, or frc itself on an engine without a table.
+// The term of FIRE's six words (reduce.hpp), over the owned slots, fp64 in both precisions.  g: the G planes, or frc itself on an
+// engine without a table.
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_fire_partials(int n, int n_owned, size_t pitch, const int *__restrict__ perm,
-                                                             const real *__restrict__ g, const real *__restrict__ frc,
-                                                             const real *__restrict__ vel, const real *__restrict__ inv_mass,
-                                                             double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double P = 0.0, vv = 0.0, gg = 0.0, g2 = 0.0, v2 = 0.0, a2 = 0.0;
-    for (int p = blockIdx.x * RED_BLOCK + threadIdx.x; p < n; p += gridDim.x * RED_BLOCK) {
-        if (perm[p] >= n_owned) continue;
+struct FireSums {
+    static constexpr int SUMS = FIRE_SUMS, MAXES = FIRE_MAXIMA;
+    int n_owned;
+    size_t pitch;
+    const int *perm;
+    const real *g, *frc, *vel, *inv_mass;
+    __device__ __forceinline__ void operator()(int p, double *acc) const {
+        if (perm[p] >= n_owned) return;
         const double w = inv_mass ? (double)inv_mass[p] : 1.0;
         const double gx = (double)g[p], gy = (double)g[pitch + p], gz = (double)g[2 * pitch + p];
         const double vx = (double)vel[p], vy = (double)vel[pitch + p], vz = (double)vel[2 * pitch + p];
         const double fx = (double)frc[p], fy = (double)frc[pitch + p], fz = (double)frc[2 * pitch + p];
         const double gi = gx * gx + gy * gy + gz * gz, vi = vx * vx + vy * vy + vz * vz, ai = w * w * (fx * fx + fy * fy + fz * fz);
-        P += gx * vx + gy * vy + gz * vz;
-        vv += vi;
-        gg += gi;
-        g2 = fmax(g2, gi); v2 = fmax(v2, vi); a2 = fmax(a2, ai);
+        acc[0] += gx * vx + gy * vy + gz * vz;
+        acc[1] += vi;
+        acc[2] += gi;
+        acc[3] = fmax(acc[3], gi); acc[4] = fmax(acc[4], vi); acc[5] = fmax(acc[5], ai);
     }
-    double t;
-    t = block_sum(P, sh); if (threadIdx.x == 0) partial[FIRE_WORDS * blockIdx.x] = t;
-    t = block_sum(vv, sh); if (threadIdx.x == 0) partial[FIRE_WORDS * blockIdx.x + 1] = t;
-    t = block_sum(gg, sh); if (threadIdx.x == 0) partial[FIRE_WORDS * blockIdx.x + 2] = t;
-    t = block_max(g2, sh); if (threadIdx.x == 0) partial[FIRE_WORDS * blockIdx.x + 3] = t;
-    t = block_max(v2, sh); if (threadIdx.x == 0) partial[FIRE_WORDS * blockIdx.x + 4] = t;
-    t = block_max(a2, sh); if (threadIdx.x == 0) partial[FIRE_WORDS * blockIdx.x + 5] = t;
-}
-
-// out[0..5] = the three sums and the three maxima over the blocks' partials (k_final_sums' shape); out[6] = *energy, the potential
-// energy k_final_sum3 has just left, so that one copy brings everything back
-static __global__ __launch_bounds__(RED_BLOCK) void k_fire_final(int nblocks, const double *__restrict__ partial,
-                                                                 const double *__restrict__ energy, double *__restrict__ out) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    for (int q = 0; q < FIRE_WORDS; q++) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += RED_BLOCK) {
-            const double t = partial[(size_t)FIRE_WORDS * b + q];
-            s = q < FIRE_SUMS ? s + t : fmax(s, t);
-        }
-        const double t = q < FIRE_SUMS ? block_sum(s, sh) : block_max(s, sh);
-        if (threadIdx.x == 0) out[q] = t;
-    }
-    if (threadIdx.x == 0) out[FIRE_WORDS] = *energy;
-}
+};
 
 // the mixing of step 6: v <- c_v v + c_g G, with c_v = 1 - alpha and c_g = alpha sqrt(vv / gg) from the host
 template <typename real>

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(MSD_BLOCK) void k_msd_accumulate(MsdArgs a, const M
     }
 }
 
-// One workgroup per (live origin j, group g): the group's chunk partials summed in chunk order (k_final_sums' shape), msd_finish,
+// One workgroup per (live origin j, group g): the group's chunk partials summed in chunk order (final_word, reduce.hpp), msd_finish,
 // and thread 0 adds the seven words to sums[lag][g][0..6].  No two workgroups of a sample share a (lag, group), and the samples
 // follow one another on the stream: plain loads and stores, no atomics.
 static __global__ __launch_bounds__(RED_BLOCK) void k_msd_finish(MsdArgs a, const int *__restrict__ chunk_of_group,
@@ -261,11 +261,7 @@ static __global__ __launch_bounds__(RED_BLOCK) void k_msd_finish(MsdArgs a, cons
     const int c0 = chunk_of_group[g], c1 = chunk_of_group[g + 1];
     double total[MSD_WORDS];
 #pragma unroll
-    for (int w = 0; w < MSD_WORDS; w++) {
-        double s = 0.0;
-        for (int c = c0 + (int)threadIdx.x; c < c1; c += RED_BLOCK) s += partial[((size_t)j * a.n_chunks + c) * MSD_WORDS + w];
-        total[w] = block_sum(s, sh);
-    }
+    for (int w = 0; w < MSD_WORDS; w++) total[w] = final_word(c1 - c0, partial + ((size_t)j * a.n_chunks + c0) * MSD_WORDS, MSD_WORDS, w, false, sh);
     if (threadIdx.x == 0) {
         double out[MSD_WORDS];
         msd_finish(total, out);

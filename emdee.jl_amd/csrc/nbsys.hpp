@@ -171,7 +171,6 @@ struct NbSystem {
     DevBuf<unsigned short> nbr16;
     DevBuf<int> btab;                     // per-brick tables of the current list (k_brick_tables)
     bool btab_valid = false;
-    DevBuf<double> partial, sums;
     DevBuf<unsigned long long> stats;
     Scanner scanner;
 
@@ -225,6 +224,48 @@ struct NbSystem {
             if (s->profiling) s->timers[id].end(k, s->stream());
         }
     };
+    // a launch, timed under `timer` when that is a TimerId and not -1
+    template <class Launch>
+    void timed_if(int timer, Launch &&launch) {
+        if (timer < 0) { launch(); return; }
+        Timed t(this, timer);
+        launch();
+    }
+
+    // ---------------------------------------------------------------- box sums (reduce.hpp)
+    // The scratch of every two-stage sum: the blocks' partials, sized for the widest term and shared by all (the stream orders their
+    // users), and behind them the totals in fixed slots, so that totals which one launch or one copy reads together never alias.
+    // The energy sums lie right behind FIRE's six words (fire_sums: one copy of seven), the molecules' tensor sums right behind the
+    // atomic ones (molecular_tensor_sums: one copy of twenty-four; k_gk_push reads those and the heat sums in one launch).
+    enum RedSlot { RED_FIRE = 0, RED_ENERGY = 6, RED_TENSOR = 9, RED_MOLECULE = 21, RED_HEAT = 33, RED_RESTRAINT = 36, RED_TOTALS = 44 };
+    DevBuf<double> red;
+    double *red_partials() {
+        red.ensure((size_t)RED_MAX_WORDS * RED_MAX_BLOCKS + RED_TOTALS);
+        return red.ptr;
+    }
+    // The two stages of `term` over n > 0 elements, queued on the stream, nothing read back: the device address of the totals in
+    // `slot`.  timer >= 0: each launch is timed under it.  The halves are for a caller that times them apart (the molecule pass) or
+    // completes the sum in a kernel of its own (the thermostat): queue_partials returns the number of blocks, which stage 2 takes.
+    template <class Term>
+    int queue_partials(int n, const Term &term, int timer = -1) {
+        const int nb = red_blocks(n);
+        double *partial = red_partials();
+        timed_if(timer, [&] { hipLaunchKernelGGL((k_reduce_partials<Term>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n, term, partial); });
+        return nb;
+    }
+    template <class Term>
+    double *queue_final(int nb, int slot, int timer = -1) {
+        const double *partial = red_partials();
+        double *tot = red.ptr + (size_t)RED_MAX_WORDS * RED_MAX_BLOCKS + slot;
+        timed_if(timer, [&] {
+            hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, Term::SUMS, Term::MAXES, partial, tot);
+        });
+        return tot;
+    }
+    template <class Term>
+    double *queue(int n, const Term &term, int slot, int timer = -1) {
+        return queue_final<Term>(queue_partials(n, term, timer), slot, timer);
+    }
 
     // ---------------------------------------------------------------- geometry
     void set_box(const double lo_[3], const double len_[3], const int per_[3]) {
@@ -297,7 +338,7 @@ struct NbSystem {
         cell_of.ensure(m + 1); cell_sorted.ensure(m + 1); cell_sorted2.ensure(m + 1); order.ensure(m + 1); cnt.ensure(m + 1);
         if (use_tags) { tag.ensure(m + 1); tag2.ensure(m + 1); }
         if (flags.ensure(32)) EMDEE_HIP_CHECK(hipMemsetAsync(flags.ptr, 0, 32 * sizeof(int), stream()));
-        partial.ensure(3 * RED_MAX_BLOCKS); sums.ensure(8); stats.ensure(4);
+        red_partials(); stats.ensure(4);
     }
 
     // ---------------------------------------------------------------- binning
@@ -1260,17 +1301,11 @@ struct NbSystem {
     }
     // emdee_md_restraint_sums, blocking: out[0] = sum U, out[1..6] = the sum of the tensors, out[7] = the largest |d|; fp64 in a fixed
     // order that depends on the number of entries alone
-    DevBuf<double> rpartial;
     void restraint_sums(double out[RESTRAINT_WORDS]) {
         for (int q = 0; q < RESTRAINT_WORDS; q++) out[q] = 0.0;
         if (!has_restraints() || tables->restraints.n == 0) return;
         require_restraints_fit("restraint_sums");
-        const int nb = std::min((int)blocks_for(tables->restraints.n, RED_BLOCK), RED_MAX_BLOCKS);
-        rpartial.ensure((size_t)RESTRAINT_WORDS * RED_MAX_BLOCKS + RESTRAINT_WORDS);
-        double *tot = rpartial.ptr + (size_t)RESTRAINT_WORDS * RED_MAX_BLOCKS;
-        hipLaunchKernelGGL((k_restraint_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), restraint_args(), rpartial.ptr);
-        hipLaunchKernelGGL(k_restraint_final, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)rpartial.ptr, tot);
-        read_back_doubles(out, tot, RESTRAINT_WORDS);
+        read_back_doubles(out, queue(tables->restraints.n, RestraintSums<real>{restraint_args()}, RED_RESTRAINT), RESTRAINT_WORDS);
     }
 
     void add_post_terms(const Pass<real> &p) {
@@ -1526,7 +1561,6 @@ struct NbSystem {
 
     // ---------------------------------------------------------------- energy minimisation (minimize.hpp; MdImpl::minimize drives these)
     DevBuf<real> gplane;                                     // a = w F, then the constrained force G (three planes, cell order)
-    DevBuf<double> fire_partial;
     void zero_velocities() {
         if (n_total == 0) return;
         Timed t(this, T_MINIMIZE);
@@ -1552,22 +1586,18 @@ struct NbSystem {
         return gplane.ptr;
     }
     // out[0..5] = sum G . v, sum v . v, sum G . G, max |G_i|^2, max |v_i|^2, max |w_i F_i|^2, out[6] = the potential energy of the
-    // last pass (energy_sums' kernels, so that it is the number emdee_md_energies gives); one copy, blocking
+    // last pass (energy_sums' term, so that it is the number emdee_md_energies gives), which RED_ENERGY keeps right behind
+    // RED_FIRE's six words; one copy, blocking
     void fire_sums(const real *g, double out[FIRE_WORDS + 1]) {
         for (int q = 0; q <= FIRE_WORDS; q++) out[q] = 0.0;
         if (n_total == 0) return;
-        const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-        fire_partial.ensure((size_t)FIRE_WORDS * RED_MAX_BLOCKS + FIRE_WORDS + 1);
-        double *tot = fire_partial.ptr + (size_t)FIRE_WORDS * RED_MAX_BLOCKS;
+        static_assert(RED_ENERGY == RED_FIRE + FIRE_WORDS, "fire_sums copies the energy sums' first word with FIRE's six");
         const real *w = with_mass ? im.ptr : nullptr;
+        double *tot;
         {
             Timed t(this, T_MINIMIZE);
-            hipLaunchKernelGGL((k_energy_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
-                               (const real *)en.ptr, (const real *)nullptr, (const real *)nullptr, (const real *)frc.ptr, w, (real)0, partial.ptr);
-            hipLaunchKernelGGL(k_final_sum3, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)partial.ptr, sums.ptr);
-            hipLaunchKernelGGL((k_fire_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr, g,
-                               (const real *)frc.ptr, (const real *)vel.ptr, w, fire_partial.ptr);
-            hipLaunchKernelGGL(k_fire_final, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)fire_partial.ptr, (const double *)sums.ptr, tot);
+            queue(n_total, EnergySums<real>{n_owned, pitch, perm.ptr, en.ptr, nullptr, nullptr, frc.ptr, w, (real)0}, RED_ENERGY);
+            tot = queue(n_total, FireSums<real>{n_owned, pitch, perm.ptr, g, frc.ptr, vel.ptr, w}, RED_FIRE);
         }
         read_back_doubles(out, tot, FIRE_WORDS + 1);
     }
@@ -1579,25 +1609,20 @@ struct NbSystem {
     }
 
     // ---------------------------------------------------------------- global thermostats (thermostat.hpp; MdImpl::step_closed drives these)
-    // th_words[0..19]: the state words of emdee_md_thermostat_state, on the device; behind them the blocks' partial sums
+    // th_words[0..19]: the state words of emdee_md_thermostat_state, on the device
     DevBuf<double> th_words;
     double *thermostat_words() {
-        if (th_words.ensure((size_t)TH_WORDS + RED_MAX_BLOCKS)) EMDEE_HIP_CHECK(hipMemsetAsync(th_words.ptr, 0, TH_WORDS * sizeof(double), stream()));
+        if (th_words.ensure(TH_WORDS)) EMDEE_HIP_CHECK(hipMemsetAsync(th_words.ptr, 0, TH_WORDS * sizeof(double), stream()));
         return th_words.ptr;
     }
     // stage (e') of an event: K, the scalar update, v <- alpha v; three launches on the stream, nothing read back
     void thermostat_event(const ThermostatParams &p) {
         if (n_total == 0) return;
-        double *w = thermostat_words(), *part = w + TH_WORDS;
-        const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
+        double *w = thermostat_words();
+        const int nb = queue_partials(n_total, KineticSums<real>{n_owned, pitch, perm.ptr, vel.ptr, with_mass ? im.ptr : nullptr}, T_THERMOSTAT);
         {
             Timed t(this, T_THERMOSTAT);
-            hipLaunchKernelGGL((k_kinetic_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
-                               (const real *)vel.ptr, with_mass ? (const real *)im.ptr : nullptr, part);
-        }
-        {
-            Timed t(this, T_THERMOSTAT);
-            hipLaunchKernelGGL(k_thermostat_update, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)part, p, w);
+            hipLaunchKernelGGL(k_thermostat_update, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, (const double *)red_partials(), p, w);
         }
         {
             Timed t(this, T_THERMOSTAT);
@@ -1688,36 +1713,18 @@ struct NbSystem {
     void energy_sums(double pending_c, double out[3]) {
         out[0] = out[1] = out[2] = 0.0;
         if (n_total == 0) return;
-        int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-        hipLaunchKernelGGL((k_energy_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch,
-                           perm.ptr, en.ptr, vir.ptr, with_vel ? vel.ptr : nullptr, frc.ptr,
-                           with_mass ? im.ptr : nullptr, (real)pending_c, partial.ptr);
-        hipLaunchKernelGGL(k_final_sum3, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, partial.ptr, sums.ptr);
-        read_back_doubles(out, sums.ptr, 3);
+        const EnergySums<real> term{n_owned, pitch, perm.ptr, en.ptr, vir.ptr, with_vel ? vel.ptr : nullptr, frc.ptr,
+                                    with_mass ? im.ptr : nullptr, (real)pending_c};
+        read_back_doubles(out, queue(n_total, term, RED_ENERGY), 3);
     }
 
     // out[0..5] = sum of the owned atoms' virial tensors (the last tensor pass), out[6..11] = kinetic tensor sum m v^a v^b;
     // (xx, yy, zz, xy, xz, yz), fp64, blocking
-    DevBuf<double> tpartial;
-    // a launch, timed under `timer` when that is a TimerId and not -1
-    template <class Launch>
-    void timed_if(int timer, Launch &&launch) {
-        if (timer < 0) { launch(); return; }
-        Timed t(this, timer);
-        launch();
-    }
-    // queues the atomic sums; they land behind the partials, where a second total has room next to them.  timer >= 0: each of the
-    // two launches is timed under it (a sample of the Green-Kubo observables counts them as its own)
+    // queues the atomic sums (RED_TENSOR, where the molecules' total has its slot next to them).  timer >= 0: each of the two
+    // launches is timed under it (a sample of the Green-Kubo observables counts them as its own)
     double *queue_tensor_sums(int timer = -1) {
-        const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-        tpartial.ensure((size_t)TENSOR_SUMS * RED_MAX_BLOCKS + 2 * TENSOR_SUMS);
-        double *tot = tpartial.ptr + (size_t)TENSOR_SUMS * RED_MAX_BLOCKS;
-        timed_if(timer, [&] {
-            hipLaunchKernelGGL((k_tensor_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch, perm.ptr,
-                               vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr, tpartial.ptr);
-        });
-        timed_if(timer, [&] { hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot); });
-        return tot;
+        const TensorSums<real> term{n_owned, pitch, perm.ptr, vt.ptr, with_vel ? vel.ptr : nullptr, with_mass ? im.ptr : nullptr};
+        return queue(n_total, term, RED_TENSOR, timer);
     }
     void tensor_sums(double out[TENSOR_SUMS]) {
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
@@ -1725,22 +1732,16 @@ struct NbSystem {
         read_back_doubles(out, queue_tensor_sums(), TENSOR_SUMS);
     }
     // out[0..5] = W_mol, out[6..11] = K_mol (include/emdee_hip.h: emdee_md_molecular_pressure_tensor): the atomic sums above minus
-    // what the atoms of the rigid molecules carry about their centres of mass (k_molecule_partials over the table, with the
-    // current force planes).  The partial sums of the two passes share their buffer (the stream orders them), the two totals lie
-    // side by side.  The queueing half: both[0..11] the atomic sums, both[12..23] the molecules'; the difference both[q] -
-    // both[12 + q] is the reader's (n_total > 0 and a rigid table with molecules in it are the caller's to check).
+    // what the atoms of the rigid molecules carry about their centres of mass (MoleculeSums over the table, with the current
+    // force planes), the molecule pass under T_MOLECULAR, its final under the caller's timer.  The two totals lie side by side.
+    // The queueing half: both[0..11] the atomic sums, both[12..23] the molecules'; the difference both[q] - both[12 + q] is the
+    // reader's (n_total > 0 and a rigid table with molecules in it are the caller's to check).
     double *queue_molecular_tensor_sums(int timer = -1) {
         const int n_mol = tables->rigid.n;
+        static_assert(RED_MOLECULE == RED_TENSOR + TENSOR_SUMS, "the readers take both totals as one array of twenty-four");
         double *tot = queue_tensor_sums(timer);
-        const int nb = std::min((int)blocks_for(n_mol, RED_BLOCK), RED_MAX_BLOCKS);
-        {
-            Timed t(this, T_MOLECULAR);
-            hipLaunchKernelGGL((k_molecule_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), settle_args(), (const real *)frc.ptr,
-                               tpartial.ptr);
-        }
-        timed_if(timer, [&] {
-            hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, TENSOR_SUMS, tpartial.ptr, tot + TENSOR_SUMS);
-        });
+        const int nb = queue_partials(n_mol, MoleculeSums<real>{settle_args(), frc.ptr}, T_MOLECULAR);
+        queue_final<MoleculeSums<real>>(nb, RED_MOLECULE, timer);
         return tot;
     }
     // the read-back half: one copy of both totals, the subtraction on the host.  Blocking.
@@ -1756,7 +1757,7 @@ struct NbSystem {
 
     // ---------------------------------------------------------------- Green-Kubo observables (gk.hpp; the table is MdImpl's GkRecord, observables.hpp)
     // A sample reads the outputs of the tensor pass, perm, the velocities and the masses; it writes the record's buffers and the
-    // scratch of the box sums (tpartial), nothing else of the engine's.
+    // scratch of the box sums (red), nothing else of the engine's.
     // sample t.samples of the table: queued on the stream, nothing read back.  Behind a current tensor pass (and, with
     // `molecular`, current forces).  GK_STRESS: the box sums of the pressure entry (two launches, a third with `molecular`, whose
     // molecule pass is T_MOLECULAR's); GK_HEAT: the heat partials and their finish (two); then the push and the correlator (two).
@@ -1764,19 +1765,8 @@ struct NbSystem {
         const double *box = nullptr, *heat = nullptr;
         if ((t.what & GK_STRESS) && n_total > 0) box = molecular ? queue_molecular_tensor_sums(T_GK) : queue_tensor_sums(T_GK);
         if ((t.what & GK_HEAT) && n_total > 0) {
-            const int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-            double *tot = t.heat.ptr + (size_t)GK_HEAT_WORDS * RED_MAX_BLOCKS;
-            {
-                Timed timed(this, T_GK);
-                hipLaunchKernelGGL((k_gk_heat_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, n_owned, pitch,
-                                   (const int *)perm.ptr, (const real *)en.ptr, (const real *)vt.ptr, (const real *)vel.ptr,
-                                   with_mass ? (const real *)im.ptr : nullptr, t.heat.ptr);
-            }
-            {
-                Timed timed(this, T_GK);
-                hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(RED_BLOCK), 0, stream(), nb, GK_HEAT_WORDS, (const double *)t.heat.ptr, tot);
-            }
-            heat = tot;
+            const HeatSums<real> term{n_owned, pitch, perm.ptr, en.ptr, vt.ptr, vel.ptr, with_mass ? im.ptr : nullptr};
+            heat = queue(n_total, term, RED_HEAT, T_GK);
         }
         GkArgs a{};
         a.what = t.what; a.n_lags = t.n_lags; a.molecular = molecular ? 1 : 0; a.s = t.samples; a.ring = t.ring.ptr; a.acc = t.acc.ptr;
@@ -1804,8 +1794,7 @@ struct NbSystem {
             if (brick_active) {
                 with_brick_variant(plan.variant, [&](auto v) { launch_brick_kernel<decltype(v), BRICK_STATS, 0>(Pass<real>{}); });
             } else {
-                int nb = std::min((int)blocks_for(n_total, RED_BLOCK), RED_MAX_BLOCKS);
-                hipLaunchKernelGGL((k_list_stats<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n_total, view(), nbr.ptr,
+                hipLaunchKernelGGL((k_list_stats<real>), dim3(red_blocks(n_total)), dim3(RED_BLOCK), 0, stream(), n_total, view(), nbr.ptr,
                                    stride, cnt.ptr, grid, model.rc2, count_pairs ? 1 : 0, stats.ptr);
             }
             EMDEE_HIP_CHECK(hipMemcpyAsync(h, stats.ptr, sizeof(h), hipMemcpyDeviceToHost, stream()));

@@ -111,11 +111,10 @@ struct MsdRecord : ObsTable {
         restart(e);
     }
 };
-// The ring of samples (n_lags x 9), the lag sums with the totals and the last sample behind them (acc), the block partials and
-// the three totals of the heat flux.
+// The ring of samples (n_lags x 9), the lag sums with the totals and the last sample behind them (acc).
 struct GkRecord : ObsTable {
     int what = 0, n_lags = 0;
-    DevBuf<double> ring, acc, heat;
+    DevBuf<double> ring, acc;
     size_t ring_words() const { return (size_t)n_lags * GK_WORDS; }
     size_t acc_words() const { return ring_words() + 2 * GK_WORDS; }
     void zero(hipStream_t s, const ObsEngine &e) {

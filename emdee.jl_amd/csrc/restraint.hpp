@@ -64,7 +64,6 @@ EMDEE_HD double restraint_scale_ref(double ref, double lo, double mu) { return l
 
 #if defined(__HIPCC__)
 #include "kernels.hpp"
-#include "minimize.hpp"                                      // (block_max)
 
 namespace emdee {
 
@@ -151,41 +150,23 @@ static __global__ __launch_bounds__(256) void k_restraint_scale(int n, double *_
     for (int c = 0; c < 3; c++) ref[3 * (size_t)e + c] = restraint_scale_ref(ref[3 * (size_t)e + c], s.lo[c], s.mu[c]);
 }
 
-// partial[b][0..7] over the entries of block b's stride, k_tensor_partials' shape: fp64 in both precisions, fixed order, no atomics
-// (k_restraint_final completes them).  [0] = sum U, [1..6] = sum of the tensors, [7] = the largest |d| (all three axes).  The number of
-// blocks is a function of n alone, so the order of summation is.
+// The term of emdee_md_restraint_sums (reduce.hpp), over the entries of the table, fp64 in both precisions: [0] = sum U, [1..6] = sum of
+// the tensors, [7] = the largest |d| (all three axes).
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_restraint_partials(RestraintArgs<real> a, double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double s[RESTRAINT_WORDS];
-    for (int q = 0; q < RESTRAINT_WORDS; q++) s[q] = 0.0;
-    for (int e = blockIdx.x * RED_BLOCK + threadIdx.x; e < a.n; e += gridDim.x * RED_BLOCK) {
+struct RestraintSums {
+    static constexpr int SUMS = 7, MAXES = 1;
+    static_assert(SUMS + MAXES == RESTRAINT_WORDS, "emdee_md_restraint_sums returns RESTRAINT_WORDS words");
+    RestraintArgs<real> a;
+    __device__ __forceinline__ void operator()(int e, double *s) const {
         const int p = restraint_slot(a, e);
-        if (p < 0) continue;
+        if (p < 0) return;
         double d[3], k[3], r0, f[3], T[6];
         restraint_entry(a, e, p, d, k, r0);
         s[0] += restraint_term<double>(d, k, r0, f, T);
         for (int c = 0; c < 6; c++) s[1 + c] += T[c];
         s[7] = fmax(s[7], sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]));
     }
-    for (int q = 0; q < RESTRAINT_WORDS; q++) {
-        const double t = q < 7 ? block_sum(s[q], sh) : block_max(s[q], sh);
-        if (threadIdx.x == 0) partial[RESTRAINT_WORDS * blockIdx.x + q] = t;
-    }
-}
-// out[0..6] = the sums, out[7] = the maximum over the blocks' partials (k_final_sums' shape)
-static __global__ __launch_bounds__(RED_BLOCK) void k_restraint_final(int nblocks, const double *__restrict__ partial, double *__restrict__ out) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    for (int q = 0; q < RESTRAINT_WORDS; q++) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += RED_BLOCK) {
-            const double t = partial[(size_t)RESTRAINT_WORDS * b + q];
-            s = q < 7 ? s + t : fmax(s, t);
-        }
-        const double t = q < 7 ? block_sum(s, sh) : block_max(s, sh);
-        if (threadIdx.x == 0) out[q] = t;
-    }
-}
+};
 
 }  // namespace emdee
 #endif

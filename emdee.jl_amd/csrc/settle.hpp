@@ -399,14 +399,14 @@ __device__ __forceinline__ void molecule_load(const ConstraintArgs<real> &a, int
     settle_detail::masses(a, p[0], p[1], m_apex, m_leg);
 }
 
-// partial[b][0..11] = the sum of molecule_sums over the molecules of block b's stride, k_tensor_partials' shape: fp64, fixed order,
-// no atomics (k_final_sums completes them).  frc: the engine's force planes (the force-field forces of the last force pass).
+// The term of the molecular sums (reduce.hpp), over the molecules of the table: [0..11] = the sum of molecule_sums.  frc: the engine's
+// force planes (the force-field forces of the last force pass).
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_molecule_partials(ConstraintArgs<real> a, const real *__restrict__ frc, double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double sum[TENSOR_SUMS];
-    for (int q = 0; q < TENSOR_SUMS; q++) sum[q] = 0.0;
-    for (int m = blockIdx.x * RED_BLOCK + threadIdx.x; m < a.n; m += gridDim.x * RED_BLOCK) {
+struct MoleculeSums {
+    static constexpr int SUMS = TENSOR_SUMS, MAXES = 0;
+    ConstraintArgs<real> a;
+    const real *frc;
+    __device__ __forceinline__ void operator()(int m, double *sum) const {
         int p[3];
         double s[3][3], y[3][3], v[3][3], f[3][3], m_apex, m_leg, t[TENSOR_SUMS];
         molecule_load(a, m, p, s, y, v, m_apex, m_leg);
@@ -417,11 +417,7 @@ __global__ __launch_bounds__(RED_BLOCK) void k_molecule_partials(ConstraintArgs<
         molecule_sums(y, v, f, m_apex, m_leg, t);
         for (int q = 0; q < TENSOR_SUMS; q++) sum[q] += t[q];
     }
-    for (int q = 0; q < TENSOR_SUMS; q++) {
-        const double t = block_sum(sum[q], sh);
-        if (threadIdx.x == 0) partial[TENSOR_SUMS * blockIdx.x + q] = t;
-    }
-}
+};
 
 // The molecular scale, one thread per molecule: every site's record moves by (mu - 1) (C_k - lo), C_k = Y + (r_k - y_k) the image
 // of the centre of mass that goes with the record (r_k - y_k: whole box lengths, so the stored image counts stay valid); the

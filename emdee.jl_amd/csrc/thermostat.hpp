@@ -136,34 +136,33 @@ EMDEE_HD double thermostat_update(const ThermostatParams &p, double K, double *w
 
 #if defined(__HIPCC__)
 
+#include "reduce.hpp"
+
 namespace emdee {
 
-// partial[b] = sum of m v^2 / 2 over the owned slots of block b's stride, k_tensor_partials' shape: fp64 in both precisions, fixed
-// order, no atomics (k_thermostat_update completes the sum)
+// The term of an event's K (reduce.hpp), over the owned slots, fp64 in both precisions: the sum of m v^2 / 2 (k_thermostat_update
+// completes it)
 template <typename real>
-__global__ __launch_bounds__(RED_BLOCK) void k_kinetic_partials(int n, int n_owned, size_t pitch, const int *__restrict__ perm,
-                                                                const real *__restrict__ vel, const real *__restrict__ inv_mass,
-                                                                double *__restrict__ partial) {
-    __shared__ double sh[RED_BLOCK / WAVE];
-    double s = 0.0;
-    for (int p = blockIdx.x * RED_BLOCK + threadIdx.x; p < n; p += gridDim.x * RED_BLOCK) {
-        if (perm[p] >= n_owned) continue;
+struct KineticSums {
+    static constexpr int SUMS = 1, MAXES = 0;
+    int n_owned;
+    size_t pitch;
+    const int *perm;
+    const real *vel, *inv_mass;
+    __device__ __forceinline__ void operator()(int p, double *s) const {
+        if (perm[p] >= n_owned) return;
         const real im = inv_mass ? inv_mass[p] : (real)1;
         const double m = im != (real)0 ? 1.0 / (double)im : 0.0;   // (a massless atom, a virtual site: exactly 0)
         const double vx = (double)vel[p], vy = (double)vel[pitch + p], vz = (double)vel[2 * pitch + p];
-        s += 0.5 * m * (vx * vx + vy * vy + vz * vz);
+        s[0] += 0.5 * m * (vx * vx + vy * vy + vz * vz);
     }
-    const double t = block_sum(s, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
+};
 
-// one block: K in k_final_sums' order, then thread 0 runs the scalar update on the state words w[0..19]
+// one block: K as k_reduce_final would leave it, then thread 0 runs the scalar update on the state words w[0..19]
 static __global__ __launch_bounds__(RED_BLOCK) void k_thermostat_update(int nblocks, const double *__restrict__ partial,
                                                                         ThermostatParams p, double *__restrict__ w) {
     __shared__ double sh[RED_BLOCK / WAVE];
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += RED_BLOCK) s += partial[b];
-    const double K = block_sum(s, sh);
+    const double K = final_word(nblocks, partial, 1, 0, false, sh);
     if (threadIdx.x == 0) thermostat_update(p, K, w);
 }
 

@@ -1,6 +1,6 @@
 """Device time of the molecular sums and the molecular scale at the size of examples/rigid_water.py (12^3 = 1728 rigid three-site
-molecules, 5184 atoms, fp64, masses, reaction field, Langevin): emdee_md_kernel_time index 10 (k_molecule_partials once and
-k_molecule_scale once per coupling event) per event, against index 9 (the three constraint stages) per step and the wall time
+molecules, 5184 atoms, fp64, masses, reaction field, Langevin): emdee_md_kernel_time index 10 (the molecule pass of the molecular
+sums once and k_molecule_scale once per coupling event) per event, against index 9 (the three constraint stages) per step and the wall time
 of one rigid step without coupling -- the step of the commit before molecular scaling, whose loop and kernels are unchanged.
 A number for the record, not a gate.
 

@@ -119,7 +119,8 @@ def test_heat_addends_are_the_numpy_formula(gk_host, real):
 # ---------------------------------------------------------------- the kernels
 def test_gk_kernels_are_in_the_report_and_use_no_scratch_memory():
     """`make report` (hipcc -Rpass-analysis=kernel-resource-usage on both kernel translation units, cross-compiled: no GPU needed):
-    the kernels of a sample are there, the heat reduction in both precisions, and keep nothing in scratch"""
+    the kernels of a sample are there, the heat reduction (reduce.hpp's two stages over HeatSums) in both precisions, and keep
+    nothing in scratch"""
     src = os.path.join(ROOT, "emdee.jl_amd", "csrc")
     if shutil.which("/opt/rocm/bin/hipcc") is None and shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
@@ -129,7 +130,7 @@ def test_gk_kernels_are_in_the_report_and_use_no_scratch_memory():
         text = open(os.path.join(src, name)).read()
         for b in re.split(r"remark: Function Name: ", text)[1:]:
             fn = b.split(" ", 1)[0].strip()
-            if "k_gk" not in fn:
+            if "k_gk" not in fn and "HeatSums" not in fn and "k_reduce_final" not in fn:
                 continue
             m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b)
             assert m is not None, fn
@@ -137,6 +138,7 @@ def test_gk_kernels_are_in_the_report_and_use_no_scratch_memory():
             seen.setdefault(name, set()).add(fn)
     for name, real in (("resource_usage_f64.txt", "Id"), ("resource_usage_f32.txt", "If")):
         fns = seen.get(name, set())
-        assert any("k_gk_heat_partials" + real in f for f in fns), (name, sorted(fns))
+        assert any("k_reduce_partialsINS_8HeatSums" + real in f for f in fns), (name, sorted(fns))
+        assert any("k_reduce_final" in f for f in fns), (name, sorted(fns))
         assert any("k_gk_push" in f for f in fns), (name, sorted(fns))
         assert any("k_gk_correlate" in f for f in fns), (name, sorted(fns))

@@ -268,7 +268,8 @@ def test_heavy_atoms_on_the_fixture(emdee):
 # ---------------------------------------------------------------- the kernels
 def test_restraint_kernels_are_in_the_report_and_use_no_scratch_memory():
     """`make report` (hipcc -Rpass-analysis=kernel-resource-usage on both kernel translation units, cross-compiled: no GPU needed):
-    the kernels of the restraints are there in both precisions and keep nothing in scratch"""
+    the kernels of the restraints are there in both precisions -- the sums as reduce.hpp's two stages over RestraintSums -- and keep
+    nothing in scratch"""
     src = os.path.join(ROOT, "emdee.jl_amd", "csrc")
     if shutil.which("/opt/rocm/bin/hipcc") is None and shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
@@ -278,7 +279,7 @@ def test_restraint_kernels_are_in_the_report_and_use_no_scratch_memory():
         text = open(os.path.join(src, name)).read()
         for b in re.split(r"remark: Function Name: ", text)[1:]:
             fn = b.split(" ", 1)[0].strip()
-            if "k_restraint" not in fn:
+            if "k_restraint" not in fn and "RestraintSums" not in fn and "k_reduce_final" not in fn:
                 continue
             m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b)
             assert m is not None, fn
@@ -287,5 +288,5 @@ def test_restraint_kernels_are_in_the_report_and_use_no_scratch_memory():
     for name, real in (("resource_usage_f64.txt", "Id"), ("resource_usage_f32.txt", "If")):
         fns = seen.get(name, set())
         for kernel in ("k_restraints" + real + "Lb0", "k_restraints" + real + "Lb1", "k_restraint_capture" + real,
-                       "k_restraint_partials" + real, "k_restraint_scale", "k_restraint_final"):
+                       "k_reduce_partialsINS_13RestraintSums" + real, "k_restraint_scale", "k_reduce_final"):
             assert any(kernel in f for f in fns), (name, kernel, sorted(fns))
