@@ -24,6 +24,9 @@
 // pairs inside the band are re-tested with the exact fp64 records, so the neighbour set is
 // bit-identical to an all-fp64 build.
 //
+// The brick tables (BrickTables, brick_setup, brick_locate, brick_for_each_slot, k_brick_tables, k_brick_export) are shared
+// with typed.hpp: templates over NT, the species the tables tell apart -- 1 here, one block of slots per tile cell.
+//
 // Reference lines restated: pair function src/lennard_jones.jl:25-42 (lj_pair.hpp);
 // f_ij = W/r2 * r_ij and the half split of E, W per atom src/nonbonded.jl:136-145; the cell
 // grid convention src/cells.jl:82-85.  What replaces what: compute_tile! (src/nonbonded.jl:44-107)
@@ -159,23 +162,31 @@ __device__ __forceinline__ void rel_fill_consts(const BrickArgs<real> &a, int bx
 __device__ __forceinline__ float rel_tile(float v, float c) { return (rintf(v * REL_FX) + c) * REL_IFX; }
 __device__ __forceinline__ double rel_tile(double v, float) { return v; }   // (fp64 states are never cell-relative)
 
-// ---- LDS tables shared by the build and force kernels ------------------------------------------
-template <class Shape, int THREADS>
-struct BrickTables : BrickTableSizes<Shape, THREADS> {   // (fixed_ints, bytes, image_ints, row_ints: plan.hpp)
-    static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NWAVES = THREADS / WAVE;
-    int *off;      // [NTC+1] tile-local first slot of each tile cell
-    int *gbeg;     // [NTC]   global (cell-order) first slot of each tile cell
-    int *shift;    // [NTC]   periodic image: 2 bits per dimension (0:-1, 1:0, 2:+1)
-    int *own;      // [NOC+1] prefix of own-cell populations
+// ---- the brick tables: LDS tables shared by the build and force kernels of this file and of typed.hpp --------
+// NT = species the tables tell apart.  NT = 1: a cell's atoms in any order, one block per tile cell.  NT = TNT: the box is
+// sorted by (cell, species) and the tile is SPECIES-MAJOR -- all tile cells' atoms of species 0, then of species 1; inside
+// one species the cells keep the tile order.  A block is then a (species, tile cell) pair, index t * NTC + tc.
+template <class Shape, int THREADS, int NT = 1>
+struct BrickTables : BrickTableSizes<Shape, THREADS, NT> {   // (fixed_ints, bytes, image_ints, row_ints: plan.hpp)
+    static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NTT = NT * NTC, NOT = NT * NOC, NWAVES = THREADS / WAVE;
+    int *off;      // [NTT+1] tile-local first slot of each block
+    int *gbeg;     // [NTT]   global (cell-order) first slot of each block
+    int *shift;    // [NTC]   per tile cell: periodic image, 2 bits per dimension (0:-1, 1:0, 2:+1); bit 8 + t: the own block of species t holds only ghosts
+    int *own;      // [NOT+1] prefix of the own populations, (species, own cell)
     int *wtot;     // [NWAVES]
-    int2 *oinfo;   // [own_cap] per own atom {cell-order slot p, (row length or flag) << 16 | tile slot}
+    int2 *oinfo;   // [own_cap] per own atom (filled by the kernel; k_brick: {cell-order slot p, (row length or flag) << 16 | tile slot})
+    int *ocnt;     // [own_cap] NT > 1, force kernels: the two segment lengths of its row, n0 | n1 << 16
     __device__ __forceinline__ void carve(unsigned char *base) {
         off = reinterpret_cast<int *>(base);
-        gbeg = off + (NTC + 4);
-        shift = gbeg + NTC;
+        gbeg = off + (NTT + 4);
+        shift = gbeg + NTT;
         own = shift + NTC;
-        wtot = own + (NOC + 4);
+        wtot = own + (NOT + 4);
         oinfo = reinterpret_cast<int2 *>(wtot + ((NWAVES + 1) & ~1));
+    }
+    __device__ __forceinline__ void carve_counts(int own_cap) {
+        static_assert(NT > 1, "only two-segment rows keep their lengths apart from oinfo");
+        ocnt = reinterpret_cast<int *>(oinfo + own_cap);
     }
 };
 // (SOA_SLOTS, soa_pitch and the bytes of dynamic LDS of the force and build kernels: plan.hpp)
@@ -251,21 +262,29 @@ __device__ __forceinline__ bool brick_of_block(const BrickArgs<real> &a, int &bx
     return true;
 }
 
-// Fills the tile-cell and own-cell tables of this block's brick.  Returns false when the block
+// first word of the stored image of brick (bxi, byi, bzi)
+template <class BT, typename real>
+__device__ __forceinline__ int *brick_image(const BrickArgs<real> &a, int bxi, int byi, int bzi) {
+    return a.btab + (size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * BT::row_ints();
+}
+
+// Fills the block and own-cell tables of this block's brick.  Returns false when the block
 // has nothing to do.  Contains block barriers: every thread of the block must call it.
-template <typename real, class Shape, int THREADS, bool COMPUTE = false>
-__device__ __forceinline__ bool brick_setup(const BrickArgs<real> &a, const BrickTables<Shape, THREADS> &T, int &bxi,
+template <typename real, class Shape, int THREADS, int NT = 1, bool COMPUTE = false>
+__device__ __forceinline__ bool brick_setup(const BrickArgs<real> &a, const BrickTables<Shape, THREADS, NT> &T, int &bxi,
                                             int &byi, int &bzi, int &tile_n, int &n_own) {
+    using BT = BrickTables<Shape, THREADS, NT>;
     constexpr int BX = Shape::BX, BY = Shape::BY, BZ = Shape::BZ, TX = Shape::TX, TY = Shape::TY, NTC = Shape::NTC,
-                  NOC = Shape::NOC;
+                  NOC = Shape::NOC, NTT = BT::NTT, NOT = BT::NOT;
+    static_assert(NTT <= THREADS, "brick tables: one thread per block");
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
     const int Mx = a.g.M[0], My = a.g.M[1], Mz = a.g.M[2];
     if (!brick_of_block(a, bxi, byi, bzi)) return false;
     if (!COMPUTE && a.btab != nullptr) {
         // the tables of this brick were computed when the list was built (the cell populations are frozen until the
         // next rebuild): copy the image instead of redoing the scans and the serial own-cell prefix in every launch
-        constexpr int ROW = BrickTables<Shape, THREADS>::row_ints(), IMG = BrickTables<Shape, THREADS>::image_ints();
-        const int *row = a.btab + (size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * ROW;
+        constexpr int ROW = BT::row_ints(), IMG = BT::image_ints();
+        const int *row = brick_image<BT>(a, bxi, byi, bzi);
         for (int i = tid; i < ROW / 4; i += THREADS)
             reinterpret_cast<uint4 *>(T.off)[i] = reinterpret_cast<const uint4 *>(row)[i];
         __syncthreads();
@@ -279,9 +298,11 @@ __device__ __forceinline__ bool brick_setup(const BrickArgs<real> &a, const Bric
         }
         return n_own > 0;
     }
+    // my block: species t, tile cell tc
+    const int t = NT == 1 ? 0 : tid / NTC, tc = NT == 1 ? tid : tid % NTC;
+    const int tx = tc % TX, ty = (tc / TX) % TY, tz = tc / (TX * TY);
     int my_cnt = 0;
-    if (tid < NTC) {
-        const int tx = tid % TX, ty = (tid / TX) % TY, tz = tid / (TX * TY);
+    if (tid < NTT) {
         int gx = bxi * BX - 1 + tx, gy = byi * BY - 1 + ty, gz = bzi * BZ - 1 + tz;
         // own range may be clipped on the high side of a partial brick; halo = own range +- 1
         const int ox1 = min(bxi * BX + BX, Mx), oy1 = min(byi * BY + BY, My), oz1 = min(bzi * BZ + BZ, Mz);
@@ -297,38 +318,45 @@ __device__ __forceinline__ bool brick_setup(const BrickArgs<real> &a, const Bric
         wrap(gx, Mx, a.g.per[0], 0);
         wrap(gy, My, a.g.per[1], 2);
         wrap(gz, Mz, a.g.per[2], 4);
-        int gb = 0;
+        int gb = 0, packed = 0;
         if (valid) {
             const int c = gx + Mx * (gy + My * gz);
-            gb = a.start[c];
-            my_cnt = a.start[c + 1] - gb;
-        }
-        // Decomposed runs: an own cell that holds nothing but ghosts (the outermost cell layers of a cut dimension, all
-        // but a sliver of them) takes no part in the own-atom loops of the build and force kernels -- ghosts own no row,
-        // receive no force and are not integrated, but as own atoms they occupied one lane group each: 16 % of the atoms
-        // of a rank of the 8-GPU 10^7-atom run.  Marked with bit 8 of the cell's shift word (part of the stored image).
-        if (COMPUTE && a.any_ghosts && valid && my_cnt > 0 && tx >= 1 && tx <= BX && ty >= 1 && ty <= BY && tz >= 1 && tz <= BZ) {
-            int owned = 0;
-            for (int k = 0; k < my_cnt; k++) owned |= (a.perm[gb + k] < a.n_owned) ? 1 : 0;
-            if (!owned) sh |= 256;
+            const int *fs = nullptr;   // with x sub-bins: the first slots of the block's four quarters
+            if constexpr (NT == 1) {
+                gb = a.start[c];
+                my_cnt = a.start[c + 1] - gb;
+                if (a.nsub == 4) fs = a.fstart + 4 * (size_t)c;
+            } else {
+                const size_t k = ((size_t)c * NT + t) * a.tdig;
+                gb = a.tstart[k];
+                my_cnt = a.tstart[k + a.tdig] - gb;
+                fs = a.tstart + k;
+            }
+            // the three inner boundaries of the block's sub-bins, relative to its first atom (sub_below)
+            if (COMPUTE && a.bsub != nullptr && fs != nullptr) packed = (fs[1] - gb) | ((fs[2] - gb) << 10) | ((fs[3] - gb) << 20);
         }
         T.gbeg[tid] = gb;
-        T.shift[tid] = sh;
-        if (COMPUTE && a.bsub != nullptr) {
-            int packed = 0;
-            if (valid && a.nsub == 4) {
-                const int *fs = a.fstart + 4 * (size_t)(gx + Mx * (gy + My * gz));
-                packed = (fs[1] - gb) | ((fs[2] - gb) << 10) | ((fs[3] - gb) << 20);
-            }
-            a.bsub[(size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * NTC + tid] = packed;
-        }
+        if (t == 0) T.shift[tc] = sh;
+        if (COMPUTE && a.bsub != nullptr) a.bsub[(size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * NTT + tid] = packed;
     }
-    {   // exclusive scan of my_cnt over the first NTC threads (NTC <= THREADS)
+    // Decomposed runs: an own block that holds nothing but ghosts (the outermost cell layers of a cut dimension, all
+    // but a sliver of them) takes no part in the own-atom loops of the build and force kernels -- ghosts own no row,
+    // receive no force and are not integrated, but as own atoms they occupied one lane group each: 16 % of the atoms
+    // of a rank of the 8-GPU 10^7-atom run.  Marked with bit 8 + species of the cell's shift word (part of the stored
+    // image), set once the plain words are in place.
+    int ghosts_only = 0;
+    if (COMPUTE && a.any_ghosts && tid < NTT && my_cnt > 0 && tx >= 1 && tx <= BX && ty >= 1 && ty <= BY && tz >= 1 && tz <= BZ) {
+        int owned = 0;
+        const int gb = T.gbeg[tid];
+        for (int k = 0; k < my_cnt; k++) owned |= (a.perm[gb + k] < a.n_owned) ? 1 : 0;
+        ghosts_only = owned ? 0 : 1;
+    }
+    {   // exclusive scan of my_cnt over the first NTT threads (NTT <= THREADS)
         int inc = my_cnt;
 #pragma unroll
         for (int off = 1; off < WAVE; off <<= 1) {
-            int t = __shfl_up(inc, off);
-            if (lane >= off) inc += t;
+            int u = __shfl_up(inc, off);
+            if (lane >= off) inc += u;
         }
         if (lane == WAVE - 1) T.wtot[wv] = inc;
         __syncthreads();
@@ -336,25 +364,27 @@ __device__ __forceinline__ bool brick_setup(const BrickArgs<real> &a, const Bric
         for (int w = 0; w < wv; w++) woff += T.wtot[w];
         // tile slots start at 1: slot 0 is the SENTINEL record (parked far outside the box by the force kernel),
         // so an index word that was never loaded (all zero bits) and the padding of a row mean the same thing
-        if (tid < NTC) T.off[tid] = 1 + woff + inc - my_cnt;
-        if (tid == NTC - 1) T.off[NTC] = 1 + woff + inc;
+        if (tid < NTT) T.off[tid] = 1 + woff + inc - my_cnt;
+        if (tid == NTT - 1) T.off[NTT] = 1 + woff + inc;
+        if (ghosts_only) atomicOr(&T.shift[tc], 256 << t);   // (the shift words were stored before the barrier above)
     }
     __syncthreads();
-    tile_n = T.off[NTC];
+    tile_n = T.off[NTT];
     if (tid == 0) {
         int acc = 0;
-        for (int oc = 0; oc < NOC; oc++) {
+        for (int q = 0; q < NOT; q++) {
+            const int qt = q / NOC, oc = q % NOC;
             const int ox = oc % BX, oy = (oc / BX) % BY, oz = oc / (BX * BY);
-            const int tc = (ox + 1) + TX * ((oy + 1) + TY * (oz + 1));
-            T.own[oc] = acc;
+            const int cell = (ox + 1) + TX * ((oy + 1) + TY * (oz + 1)), blk = qt * NTC + cell;
+            T.own[q] = acc;
             // cells past the box edge of a partial brick hold halo images, not atoms of this brick
-            const bool mine = (bxi * BX + ox < Mx) && (byi * BY + oy < My) && (bzi * BZ + oz < Mz) && !(T.shift[tc] & 256);
-            acc += mine ? (T.off[tc + 1] - T.off[tc]) : 0;
+            const bool mine = (bxi * BX + ox < Mx) && (byi * BY + oy < My) && (bzi * BZ + oz < Mz) && !(T.shift[cell] & (256 << qt));
+            acc += mine ? (T.off[blk + 1] - T.off[blk]) : 0;
         }
-        T.own[NOC] = acc;
+        T.own[NOT] = acc;
     }
     __syncthreads();
-    n_own = T.own[NOC];
+    n_own = T.own[NOT];
     if (tile_n > a.tile_cap || n_own > a.own_cap) {   // cannot happen: the host sized both from k_brick_tile_max
         if (tid == 0) atomicMax(&a.flags[2], max(tile_n, n_own));
         return false;
@@ -362,32 +392,47 @@ __device__ __forceinline__ bool brick_setup(const BrickArgs<real> &a, const Bric
     return n_own > 0;
 }
 
-// own atom o -> own cell, tile slot, cell-order slot
-template <class Shape, int THREADS>
-__device__ __forceinline__ int brick_locate(const BrickTables<Shape, THREADS> &T, int o, int &ti, int &p) {
-    int oc = 0;
+// own atom o -> index q of its (species, own cell), tile slot, cell-order slot (and its block)
+template <class Shape, int THREADS, int NT>
+__device__ __forceinline__ int brick_locate(const BrickTables<Shape, THREADS, NT> &T, int o, int &ti, int &p, int *blk_out = nullptr) {
+    constexpr int NOC = Shape::NOC, NTC = Shape::NTC;
+    int q = 0;
 #pragma unroll
-    for (int q = 1; q < Shape::NOC; q++) oc += (T.own[q] <= o) ? 1 : 0;
+    for (int k = 1; k < NT * NOC; k++) q += (T.own[k] <= o) ? 1 : 0;
+    const int t = NT == 1 ? 0 : q / NOC, oc = NT == 1 ? q : q % NOC;
     const int ox = oc % Shape::BX, oy = (oc / Shape::BX) % Shape::BY, oz = oc / (Shape::BX * Shape::BY);
-    const int tc = (ox + 1) + Shape::TX * ((oy + 1) + Shape::TY * (oz + 1));
-    const int kk = o - T.own[oc];
-    ti = T.off[tc] + kk;
-    p = T.gbeg[tc] + kk;
-    return oc;
+    const int blk = t * NTC + (ox + 1) + Shape::TX * ((oy + 1) + Shape::TY * (oz + 1));
+    const int kk = o - T.own[q];
+    ti = T.off[blk] + kk;
+    p = T.gbeg[blk] + kk;
+    if (blk_out) *blk_out = blk;
+    return q;
 }
 
-// Calls f(slot, tile cell) once for every tile slot.  Half-waves take whole tile rows (TX cells,
-// contiguous in the tile and, away from a periodic wrap, in HBM): consecutive lanes touch consecutive
+// the block that holds tile slot sl: off[blk] <= sl < off[blk + 1]
+template <class Shape, int THREADS, int NT>
+__device__ __forceinline__ int brick_block_of_slot(const BrickTables<Shape, THREADS, NT> &T, int sl) {
+    int lo = 0, hi = NT * Shape::NTC;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (T.off[mid] <= sl) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Calls f(slot, block, tx, ty, tz) once for every tile slot.  Half-waves take whole (species, tile row) runs (TX
+// cells, contiguous in the tile and, away from a periodic wrap, in HBM): consecutive lanes touch consecutive
 // records, and a slot's cell is found with TX-1 loop-invariant compares instead of a dependent
-// binary search over all tile cells.
+// binary search over all blocks.
 constexpr int STAGE_LANES = 32;
-template <class Shape, int THREADS, class F>
-__device__ __forceinline__ void brick_for_each_slot(const BrickTables<Shape, THREADS> &T, F &&f) {
-    constexpr int NW = THREADS / STAGE_LANES, NROWS = Shape::TY * Shape::TZ, TX = Shape::TX;
+template <class Shape, int THREADS, int NT, class F>
+__device__ __forceinline__ void brick_for_each_slot(const BrickTables<Shape, THREADS, NT> &T, F &&f) {
+    constexpr int NW = THREADS / STAGE_LANES, NYZ = Shape::TY * Shape::TZ, NROWS = NYZ * NT, TX = Shape::TX;
     const int worker = threadIdx.x / STAGE_LANES, l = threadIdx.x % STAGE_LANES;
     for (int row = worker; row < NROWS; row += NW) {
-        const int c0 = row * TX;
-        const int ty = row % Shape::TY, tz = row / Shape::TY;      // (per row, not per slot: the cell-relative staging indexes by them)
+        const int t = NT == 1 ? 0 : row / NYZ, yz = NT == 1 ? row : row % NYZ;
+        const int c0 = t * Shape::NTC + yz * TX;
+        const int ty = yz % Shape::TY, tz = yz / Shape::TY;      // (per row, not per slot: the cell-relative staging indexes by them)
         int edge[TX + 1];
 #pragma unroll
         for (int c = 0; c <= TX; c++) edge[c] = T.off[c0 + c];
@@ -401,35 +446,20 @@ __device__ __forceinline__ void brick_for_each_slot(const BrickTables<Shape, THR
 }
 
 // Once per rebuild: the tables of every brick, stored as the LDS image the other kernels copy in (brick_setup).
-template <typename real, class Shape, int THREADS>
+template <typename real, class Shape, int THREADS, int NT>
 __global__ __launch_bounds__(THREADS) void k_brick_tables(BrickArgs<real> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    BrickTables<Shape, THREADS> T;
+    using BT = BrickTables<Shape, THREADS, NT>;
+    BT T;
     T.carve(s_dyn);
     const int lb = (blockIdx.x % NXCD) * a.bg.per_xcd + blockIdx.x / NXCD;
     if (lb >= a.bg.nbricks) return;
     int bxi = 0, byi = 0, bzi = 0, tile_n = 0, n_own = 0;
-    brick_setup<real, Shape, THREADS, true>(a, T, bxi, byi, bzi, tile_n, n_own);   // false also for empty bricks: stored too
-    constexpr int ROW = BrickTables<Shape, THREADS>::row_ints(), IMG = BrickTables<Shape, THREADS>::image_ints();
-    int *row = a.btab + (size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * ROW;
+    brick_setup<real, Shape, THREADS, NT, true>(a, T, bxi, byi, bzi, tile_n, n_own);   // false also for empty bricks: stored too
+    constexpr int IMG = BT::image_ints();
+    int *row = brick_image<BT>(a, bxi, byi, bzi);
     for (int i = threadIdx.x; i < IMG; i += THREADS) row[i] = T.off[i];
     if (threadIdx.x == 0) { row[IMG] = tile_n; row[IMG + 1] = n_own; }
-    // The population maxima a kept plan is checked against (NbSystem::plan_holds), as k_brick_tile_max reports them:
-    // flags[6] largest tile, [7] most own atoms, [8] most atoms in three consecutive cells of a tile row.
-    if (a.stats != nullptr) {
-        int span3 = 0;
-        if (threadIdx.x < Shape::NTC && threadIdx.x % Shape::TX + 3 <= Shape::TX) span3 = T.off[threadIdx.x + 3] - T.off[threadIdx.x];
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) span3 = max(span3, __shfl_xor(span3, off));
-        // (same-address atomics serialise in L2 at ~10 ns each and there is one workgroup per brick: look first (a device-scope load: the per-CU cache would
-        // keep showing the zero it saw first), and only the few bricks that raise a maximum pay for an atomic -- without the look this kernel took 1.6 ms instead of 0.04)
-        int *maxima = reinterpret_cast<int *>(a.stats);
-        if ((threadIdx.x & (WAVE - 1)) == 0 && span3 > __hip_atomic_load(&maxima[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&maxima[2], span3);
-        if (threadIdx.x == 0) {
-            if (tile_n - 1 > __hip_atomic_load(&maxima[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&maxima[0], tile_n - 1);
-            if (n_own > __hip_atomic_load(&maxima[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&maxima[1], n_own);
-        }
-    }
 }
 
 constexpr int OWN_REGS = 2;   // own atoms per thread whose table entry is fetched before the tile is staged
@@ -1321,30 +1351,31 @@ __global__ __launch_bounds__(THREADS) void k_brick(BrickArgs<real> a) {
 
 // Debug/verification accessor: the neighbour rows as CALLER ids (tile-local slots decoded through the brick's tables),
 // counts[i] entries at out[i * capacity ...], in list order.  One workgroup per brick, like the force kernels.
-template <typename real, class Shape, int THREADS, int G>
+// NT > 1: a row is two segments (typed.hpp k_typed_build), species-0 neighbours first.
+template <typename real, class Shape, int THREADS, int G, int NT>
 __global__ __launch_bounds__(THREADS) void k_brick_export(BrickArgs<real> a, int *__restrict__ counts, int *__restrict__ out,
                                                           int capacity, const int *__restrict__ cmap = nullptr) {
+    constexpr int BLK = EPL * G;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    BrickTables<Shape, THREADS> T;
+    BrickTables<Shape, THREADS, NT> T;
     T.carve(s_dyn);
     int bxi, byi, bzi, tile_n, n_own;
-    if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
+    if (!brick_setup<real, Shape, THREADS, NT>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
     for (int o = threadIdx.x; o < n_own; o += THREADS) {
         int ti, p;
         brick_locate(T, o, ti, p);
         if (a.perm[p] >= a.n_owned) continue;
         const int i = cmap ? cmap[a.perm[p]] : a.perm[p];
         const int m = a.cnt[p];
-        counts[i] = m;
+        const int n0 = NT == 1 ? m : (m & 0xffff), n1 = NT == 1 ? 0 : (int)((unsigned)m >> 16);
+        const int S1 = (n0 + BLK - 1) / BLK * BLK;        // the second segment starts on a block boundary
+        counts[i] = n0 + n1;
         const unsigned short *row = a.nbr + (size_t)p * a.stride;
-        for (int e = 0; e < m && e < capacity; e++) {
-            const int sl = (int)row[row_position<G>((unsigned)e)] >> a.idx_shift;
-            int lo = 0, hi = Shape::NTC;                  // tile cell with off[tc] <= sl < off[tc + 1]
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (T.off[mid] <= sl) lo = mid; else hi = mid;
-            }
-            const int j = a.perm[T.gbeg[lo] + (sl - T.off[lo])];
+        for (int e = 0; e < n0 + n1 && e < capacity; e++) {
+            const unsigned pos = e < n0 ? row_position<G>((unsigned)e) : (unsigned)S1 + row_position<G>((unsigned)(e - n0));
+            const int sl = (int)row[pos] >> a.idx_shift;
+            const int blk = brick_block_of_slot(T, sl);
+            const int j = a.perm[T.gbeg[blk] + (sl - T.off[blk])];
             out[(size_t)i * capacity + e] = cmap ? cmap[j] : j;
         }
     }
@@ -1365,13 +1396,8 @@ __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, con
     int bxi, byi, bzi, tile_n, n_own;
     if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
     auto slot = [&](unsigned short ent) {                // tile slot -> cell-order slot
-        const int sl = (int)ent >> a.idx_shift;
-        int lo = 0, hi = Shape::NTC;                      // tile cell with off[tc] <= sl < off[tc + 1]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (T.off[mid] <= sl) lo = mid; else hi = mid;
-        }
-        return T.gbeg[lo] + (sl - T.off[lo]);
+        const int sl = (int)ent >> a.idx_shift, tc = brick_block_of_slot(T, sl);
+        return T.gbeg[tc] + (sl - T.off[tc]);
     };
     for (int o = threadIdx.x; o < n_own; o += THREADS) {
         int ti, p;

@@ -667,6 +667,33 @@ struct NbSystem {
         if (blocks == 0) return;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::THREADS), lds, stream(), brick_args(p));
     }
+    // The tables of every brick, once per rebuild; the build and every force launch copy them in (brick.hpp k_brick_tables).
+    // NT = 1 or TNT (species-major tables); sub = 4 when the sort orders a block's atoms by x quarter: the boundaries of every
+    // brick's blocks go to bsub as well.  Returns the arguments the kernel ran with.
+    // (the image depends on the brick shape only: a small workgroup writes it)
+    template <class V, int NT>
+    BrickArgs<real> launch_tables(int sub) {
+        constexpr int TT = (NT > 1 || V::Shape::NTC > 128) ? 256 : 128;
+        using BT = BrickTables<typename V::Shape, TT, NT>;
+        static_assert(BT::row_ints() == BrickTables<typename V::Shape, V::THREADS, NT>::row_ints(), "table row layout");
+        btab.ensure((size_t)plan.grid.nbricks * BT::row_ints());
+        btab_valid = false;
+        BrickArgs<real> ta = brick_args();
+        ta.btab = btab.ptr;
+        if (sub > 1) {
+            bsub.ensure((size_t)plan.grid.nbricks * BT::NTT + 4);
+            ta.nsub = sub; ta.bsub = bsub.ptr;
+        }
+        hipLaunchKernelGGL((k_brick_tables<real, typename V::Shape, TT, NT>), dim3(plan.grid.per_xcd * NXCD), dim3(TT), BT::bytes(0), stream(), ta);
+        btab_valid = true;
+        return ta;
+    }
+    template <class V, int NT>
+    void launch_export(int *counts, int *out, int capacity, const int *map) {
+        auto kernel = k_brick_export<real, typename V::Shape, V::THREADS, V::G, NT>;
+        const size_t lds = BrickTables<typename V::Shape, V::THREADS, NT>::bytes(0);
+        hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), lds, stream(), brick_args(), counts, out, capacity, map);
+    }
     // typed boxes (typed.hpp): masks other than FORCES run the all-outputs kernel
     template <class V, int MODE, int BM>
     void launch_typed_kernel(const Pass<real> &p) {
@@ -823,19 +850,7 @@ struct NbSystem {
                     using V = decltype(v);
                     if constexpr (typed_variant<V>()) {
                         if (plan.typed) {   // two species: species-major tables and the two-segment build (typed.hpp)
-                            constexpr int TT = 256;
-                            using BT = TypedTables<typename V::Shape, TT>;
-                            static_assert(BT::row_ints() == TypedTables<typename V::Shape, V::THREADS>::row_ints(), "table row layout");
-                            btab.ensure((size_t)plan.grid.nbricks * BT::row_ints());
-                            BrickArgs<real> ta = brick_args();
-                            ta.btab = btab.ptr;
-                            if (tsub > 1) {                          // the x-quarter boundaries of every brick's (species, tile cell) blocks
-                                bsub.ensure((size_t)plan.grid.nbricks * BT::NTT + 4);
-                                ta.nsub = tsub; ta.bsub = bsub.ptr;
-                            }
-                            hipLaunchKernelGGL((k_typed_tables<real, typename V::Shape, TT>), dim3(plan.grid.per_xcd * NXCD), dim3(TT),
-                                               BT::bytes(0), stream(), ta);
-                            btab_valid = true;
+                            const BrickArgs<real> ta = launch_tables<V, TNT>(tsub);
                             auto kernel = k_typed_build<real, typename V::Shape, V::THREADS, V::GB, V::G>;
                             allow_big_lds(kernel, plan.lds_build);
                             BrickArgs<real> ba = brick_args();
@@ -844,22 +859,7 @@ struct NbSystem {
                             return;
                         }
                     }
-                    if (!btab_valid) {
-                        // tables of every brick, once per rebuild; the build and every force launch copy them in
-                        // (the image depends on the brick shape only: a small workgroup writes it)
-                        constexpr int TT = V::Shape::NTC <= 128 ? 128 : 256;
-                        using BT = BrickTables<typename V::Shape, TT>;
-                        static_assert(BT::row_ints() == BrickTables<typename V::Shape, V::THREADS>::row_ints(), "table row layout");
-                        btab.ensure((size_t)plan.grid.nbricks * BT::row_ints());
-                        btab_valid = false;
-                        BrickArgs<real> ta = brick_args();
-                        ta.btab = btab.ptr;
-                        ta.stats = nullptr;
-                        if (nsub > 1) { bsub.ensure((size_t)plan.grid.nbricks * V::Shape::NTC + 4); ta.bsub = bsub.ptr; }
-                        hipLaunchKernelGGL((k_brick_tables<real, typename V::Shape, TT>), dim3(plan.grid.per_xcd * NXCD), dim3(TT),
-                                           BT::bytes(0), stream(), ta);
-                        btab_valid = true;
-                    }
+                    if (!btab_valid) launch_tables<V, 1>(nsub);
                     auto kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 1, V::G>;
                     if constexpr (V::GB == 8 || V::GB == 16) {
                         if (plan.build_alg == 3) kernel = k_brick_build<real, typename V::Shape, V::THREADS, V::GB, 3, V::G>;
@@ -1815,19 +1815,9 @@ struct NbSystem {
             with_brick_variant(plan.variant, [&](auto v) {
                 using V = decltype(v);
                 if constexpr (typed_variant<V>()) {
-                    if (plan.typed) {
-                        auto tk = k_typed_export<real, typename V::Shape, V::THREADS, V::G>;
-                        using TTab = TypedTables<typename V::Shape, V::THREADS>;
-                        const size_t tlds = TTab::bytes(0);
-                        hipLaunchKernelGGL(tk, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), tlds, stream(), brick_args(), counts, out, capacity, map);
-                        return;
-                    }
+                    if (plan.typed) return launch_export<V, TNT>(counts, out, capacity, map);
                 }
-                auto kernel = k_brick_export<real, typename V::Shape, V::THREADS, V::G>;
-                using BT = BrickTables<typename V::Shape, V::THREADS>;
-                const size_t lds = BT::bytes(0);
-                hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), lds, stream(), brick_args(), counts, out,
-                                   capacity, map);
+                launch_export<V, 1>(counts, out, capacity, map);
             });
         } else {
             hipLaunchKernelGGL(k_export_rows, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, perm.ptr, nbr.ptr,

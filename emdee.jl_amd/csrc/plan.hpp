@@ -63,22 +63,14 @@ struct BrickGrid {
 };
 
 // ---- sizes of the LDS tables shared by the build and force kernels (brick.hpp BrickTables carves them) ----
-template <class Shape, int THREADS>
+// NT = species the tables tell apart: 1 (brick.hpp, atoms of a cell in any order) or TNT (typed.hpp, species-major blocks)
+template <class Shape, int THREADS, int NT = 1>
 struct BrickTableSizes {
-    static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NWAVES = THREADS / WAVE;
-    EMDEE_PLAN_HD static constexpr size_t fixed_ints() { return (NTC + 4) + NTC + NTC + (NOC + 4) + ((NWAVES + 1) & ~1); }
-    EMDEE_PLAN_HD static size_t bytes(int own_cap) { return ((fixed_ints() + 2 * (size_t)own_cap) * 4 + 15) & ~(size_t)15; }
-    // off | gbeg | shift | own are contiguous: that image (+ tile_n, n_own) is what k_brick_tables stores per brick
-    EMDEE_PLAN_HD static constexpr int image_ints() { return (NTC + 4) + NTC + NTC + (NOC + 4); }
-    EMDEE_PLAN_HD static constexpr int row_ints() { return (image_ints() + 2 + 3) & ~3; }
-};
-// ... and of a two-species box (typed.hpp TypedTables)
-template <class Shape, int THREADS>
-struct TypedTableSizes {
-    static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NTT = TNT * NTC, NOT = TNT * NOC, NWAVES = THREADS / WAVE;
+    static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NTT = NT * NTC, NOT = NT * NOC, NWAVES = THREADS / WAVE;
+    static constexpr int own_words = NT == 1 ? 2 : 3;   // per own atom: oinfo (and the two segment lengths of a typed row)
     EMDEE_PLAN_HD static constexpr size_t fixed_ints() { return (NTT + 4) + NTT + NTC + (NOT + 4) + ((NWAVES + 1) & ~1); }
-    EMDEE_PLAN_HD static size_t bytes(int own_cap) { return ((fixed_ints() + 3 * (size_t)own_cap) * 4 + 15) & ~(size_t)15; }
-    // off | gbeg | shift | own are contiguous: that image (+ tile_n, n_own) is what k_typed_tables stores per brick
+    EMDEE_PLAN_HD static size_t bytes(int own_cap) { return ((fixed_ints() + own_words * (size_t)own_cap) * 4 + 15) & ~(size_t)15; }
+    // off | gbeg | shift | own are contiguous: that image (+ tile_n, n_own) is what k_brick_tables stores per brick
     EMDEE_PLAN_HD static constexpr int image_ints() { return (NTT + 4) + NTT + NTC + (NOT + 4); }
     EMDEE_PLAN_HD static constexpr int row_ints() { return (image_ints() + 2 + 3) & ~3; }
 };
@@ -134,11 +126,11 @@ constexpr int typed_prefetch_blocks(int G, int THREADS, int NOC = 16) { return (
 constexpr int typed_seg_cap(int stride, int GL) { return ((stride / 2) + EPL * GL - 1) / (EPL * GL) * (EPL * GL); }
 template <typename real, class Shape, int THREADS>
 static inline size_t typed_force_lds_bytes(int own_cap) {
-    return (((size_t)3 * typed_pitch<real, Shape, THREADS>() * sizeof(real) + 15) & ~(size_t)15) + TypedTableSizes<Shape, THREADS>::bytes(own_cap) + 256;   // (+ the four pair-constant records)
+    return (((size_t)3 * typed_pitch<real, Shape, THREADS>() * sizeof(real) + 15) & ~(size_t)15) + BrickTableSizes<Shape, THREADS, TNT>::bytes(own_cap) + 256;   // (+ the four pair-constant records)
 }
 template <class Shape, int THREADS>
 static inline size_t typed_build_lds_bytes(int tile_cap, int own_cap, int stride, int G, int GL = 4) {
-    return (size_t)tile_cap * 16 + TypedTableSizes<Shape, THREADS>::bytes(own_cap) + (size_t)(THREADS / G) * typed_seg_cap(stride, GL) * 2 +
+    return (size_t)tile_cap * 16 + BrickTableSizes<Shape, THREADS, TNT>::bytes(own_cap) + (size_t)(THREADS / G) * typed_seg_cap(stride, GL) * 2 +
            (((size_t)(Shape::NOC * 4 + 1) * 9 * TNT * 4 + 15) & ~(size_t)15);   // (row table: one packed word per (own cell, x quarter, species, row))
 }
 

@@ -14,6 +14,9 @@
 // (24 B per record) instead of 32-byte records in LDS.  The candidate rows are half as long as the untyped ones, so
 // the 16-bit-field round-robin build of the single-species boxes (ALG 13 of brick.hpp) applies at rc = 3.5 sigma too.
 //
+// The tables under both kernels are brick.hpp's brick tables with NT = TNT: a block of slots per (species, tile cell), in
+// species-major order, populations from tstart, and a third word per own atom (the two segment lengths of its row).
+//
 // Same arithmetic per pair as the general-species kernels (sigma_ij^2 and 4 eps_ij are formed on the host with the very
 // operations the pair loop used, lj_pair.hpp lj_force_over_r2 / lj_interaction_pair evaluate them): results differ only
 // in the order of summation.  Restates what brick.hpp restates: src/lennard_jones.jl:25-42, src/nonbonded.jl:136-145,
@@ -24,188 +27,8 @@
 
 namespace emdee {
 
-// (TNT, typed_slots, typed_pitch, the prefetch depth, typed_seg_cap and the bytes of dynamic LDS of both kernels: plan.hpp)
-template <class Shape, int THREADS>
-struct TypedTables : TypedTableSizes<Shape, THREADS> {
-    static constexpr int NTC = Shape::NTC, NOC = Shape::NOC, NTT = TNT * NTC, NOT = TNT * NOC, NWAVES = THREADS / WAVE;
-    int *off;      // [NTT+1] tile-local first slot of (species, tile cell), species-major
-    int *gbeg;     // [NTT]   global (cell-order) first slot of that block
-    int *shift;    // [NTC]   periodic image of the tile cell: 2 bits per dimension (0:-1, 1:0, 2:+1)
-    int *own;      // [NOT+1] prefix of the own populations, (species, own cell)
-    int *wtot;     // [NWAVES]
-    int2 *oinfo;   // [own_cap] per own atom (filled by the kernel)
-    int *ocnt;     // [own_cap] ... and its row lengths n0 | n1 << 16 (force kernels)
-    __device__ __forceinline__ void carve(unsigned char *base) {
-        off = reinterpret_cast<int *>(base);
-        gbeg = off + (NTT + 4);
-        shift = gbeg + NTT;
-        own = shift + NTC;
-        wtot = own + (NOT + 4);
-        oinfo = reinterpret_cast<int2 *>(wtot + ((NWAVES + 1) & ~1));
-    }
-    __device__ __forceinline__ void carve_counts(int own_cap) { ocnt = reinterpret_cast<int *>(oinfo + own_cap); }
-};
-
-// tables of this block's brick; false when the block has nothing to do.  Contains block barriers.
-template <typename real, class Shape, int THREADS, bool COMPUTE = false>
-__device__ __forceinline__ bool typed_setup(const BrickArgs<real> &a, const TypedTables<Shape, THREADS> &T, int &bxi, int &byi,
-                                            int &bzi, int &tile_n, int &n_own) {
-    constexpr int BX = Shape::BX, BY = Shape::BY, BZ = Shape::BZ, TX = Shape::TX, TY = Shape::TY, NTC = Shape::NTC, NOC = Shape::NOC;
-    constexpr int NTT = TNT * NTC, NOT = TNT * NOC;
-    static_assert(NTT <= THREADS, "typed tables: one thread per (species, tile cell)");
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    const int Mx = a.g.M[0], My = a.g.M[1], Mz = a.g.M[2];
-    if (!brick_of_block(a, bxi, byi, bzi)) return false;
-    if (!COMPUTE && a.btab != nullptr) {
-        constexpr int ROW = TypedTables<Shape, THREADS>::row_ints(), IMG = TypedTables<Shape, THREADS>::image_ints();
-        const int *row = a.btab + (size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * ROW;
-        for (int i = tid; i < ROW / 4; i += THREADS)
-            reinterpret_cast<uint4 *>(T.off)[i] = reinterpret_cast<const uint4 *>(row)[i];
-        __syncthreads();
-        tile_n = T.off[IMG];
-        n_own = T.off[IMG + 1];
-        if (tile_n > a.tile_cap || n_own > a.own_cap) {   // (a kept plan the populations outgrew: skipped and reported)
-            if (tid == 0) atomicMax(&a.flags[2], max(tile_n, n_own));
-            return false;
-        }
-        return n_own > 0;
-    }
-    int my_cnt = 0;
-    if (tid < NTT) {
-        const int t = tid / NTC, tc = tid % NTC;
-        const int tx = tc % TX, ty = (tc / TX) % TY, tz = tc / (TX * TY);
-        int gx = bxi * BX - 1 + tx, gy = byi * BY - 1 + ty, gz = bzi * BZ - 1 + tz;
-        const int ox1 = min(bxi * BX + BX, Mx), oy1 = min(byi * BY + BY, My), oz1 = min(bzi * BZ + BZ, Mz);
-        bool valid = gx <= ox1 && gy <= oy1 && gz <= oz1;
-        int sh = 1 | (1 << 2) | (1 << 4);
-        auto wrap = [&](int &c, int M, int per, int bit) {
-            if (c < 0) {
-                if (per) { c += M; sh = (sh & ~(3 << bit)) | (0 << bit); } else valid = false;
-            } else if (c >= M) {
-                if (per) { c -= M; sh = (sh & ~(3 << bit)) | (2 << bit); } else valid = false;
-            }
-        };
-        wrap(gx, Mx, a.g.per[0], 0);
-        wrap(gy, My, a.g.per[1], 2);
-        wrap(gz, Mz, a.g.per[2], 4);
-        int gb = 0, packed = 0;
-        if (valid) {
-            const size_t c = ((size_t)(gx + Mx * (gy + My * gz)) * TNT + t) * a.tdig;
-            gb = a.tstart[c];
-            my_cnt = a.tstart[c + a.tdig] - gb;
-            if (COMPUTE && a.bsub != nullptr) {          // x sub-bins: the three inner boundaries of the block (brick.hpp sub_below)
-                const int *fs = a.tstart + c;
-                packed = (fs[1] - gb) | ((fs[2] - gb) << 10) | ((fs[3] - gb) << 20);
-            }
-        }
-        T.gbeg[tid] = gb;
-        if (t == 0) T.shift[tc] = sh;
-        if (COMPUTE && a.bsub != nullptr) a.bsub[(size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * NTT + tid] = packed;
-    }
-    // Decomposed runs: an own (species, cell) block that holds nothing but ghosts takes no part in the own-atom loops (as in
-    // brick.hpp): bit 8 + species of the cell's shift word, set once the plain words are in place
-    int ghosts_only = 0;
-    if (COMPUTE && a.any_ghosts && tid < NTT && my_cnt > 0) {
-        const int tc = tid % NTC, tx = tc % TX, ty = (tc / TX) % TY, tz = tc / (TX * TY);
-        if (tx >= 1 && tx <= BX && ty >= 1 && ty <= BY && tz >= 1 && tz <= BZ) {
-            int owned = 0;
-            const int gb = T.gbeg[tid];
-            for (int k = 0; k < my_cnt; k++) owned |= (a.perm[gb + k] < a.n_owned) ? 1 : 0;
-            ghosts_only = owned ? 0 : 1;
-        }
-    }
-    {   // exclusive scan of my_cnt over the first NTT threads; tile slots start at 1 (slot 0 is the sentinel record)
-        int inc = my_cnt;
-#pragma unroll
-        for (int off = 1; off < WAVE; off <<= 1) {
-            int t = __shfl_up(inc, off);
-            if (lane >= off) inc += t;
-        }
-        if (lane == WAVE - 1) T.wtot[wv] = inc;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wv; w++) woff += T.wtot[w];
-        if (tid < NTT) T.off[tid] = 1 + woff + inc - my_cnt;
-        if (tid == NTT - 1) T.off[NTT] = 1 + woff + inc;
-        if (ghosts_only) atomicOr(&T.shift[tid % NTC], 256 << (tid / NTC));   // (the shift words were stored before the barrier above)
-    }
-    __syncthreads();
-    tile_n = T.off[NTT];
-    if (tid == 0) {
-        int acc = 0;
-        for (int q = 0; q < NOT; q++) {
-            const int t = q / NOC, oc = q % NOC;
-            const int ox = oc % BX, oy = (oc / BX) % BY, oz = oc / (BX * BY);
-            const int tc = t * NTC + (ox + 1) + TX * ((oy + 1) + TY * (oz + 1));
-            T.own[q] = acc;
-            const bool mine = (bxi * BX + ox < Mx) && (byi * BY + oy < My) && (bzi * BZ + oz < Mz) &&
-                              !(T.shift[tc - t * NTC] & (256 << t));
-            acc += mine ? (T.off[tc + 1] - T.off[tc]) : 0;
-        }
-        T.own[NOT] = acc;
-    }
-    __syncthreads();
-    n_own = T.own[NOT];
-    if (tile_n > a.tile_cap || n_own > a.own_cap) {
-        if (tid == 0) atomicMax(&a.flags[2], max(tile_n, n_own));
-        return false;
-    }
-    return n_own > 0;
-}
-
-// own atom o -> (species, own cell) index q, tile slot, cell-order slot
-template <class Shape, int THREADS>
-__device__ __forceinline__ int typed_locate(const TypedTables<Shape, THREADS> &T, int o, int &ti, int &p, int *tc_out = nullptr) {
-    constexpr int NOC = Shape::NOC, NTC = Shape::NTC;
-    int q = 0;
-#pragma unroll
-    for (int k = 1; k < TNT * NOC; k++) q += (T.own[k] <= o) ? 1 : 0;
-    const int t = q / NOC, oc = q % NOC;
-    const int ox = oc % Shape::BX, oy = (oc / Shape::BX) % Shape::BY, oz = oc / (Shape::BX * Shape::BY);
-    const int tc = t * NTC + (ox + 1) + Shape::TX * ((oy + 1) + Shape::TY * (oz + 1));
-    const int kk = o - T.own[q];
-    ti = T.off[tc] + kk;
-    p = T.gbeg[tc] + kk;
-    if (tc_out) *tc_out = tc;
-    return q;
-}
-
-// f(slot, typed tile cell) once for every tile slot; half-waves take whole (species, tile row) runs
-template <class Shape, int THREADS, class F>
-__device__ __forceinline__ void typed_for_each_slot(const TypedTables<Shape, THREADS> &T, F &&f) {
-    constexpr int NW = THREADS / STAGE_LANES, NYZ = Shape::TY * Shape::TZ, NROWS = NYZ * TNT, TX = Shape::TX;
-    const int worker = threadIdx.x / STAGE_LANES, l = threadIdx.x % STAGE_LANES;
-    for (int row = worker; row < NROWS; row += NW) {
-        const int c0 = (row / NYZ) * Shape::NTC + (row % NYZ) * TX;
-        const int ty = (row % NYZ) % Shape::TY, tz = (row % NYZ) / Shape::TY;   // (per row: the cell-relative staging indexes by them)
-        int edge[TX + 1];
-#pragma unroll
-        for (int c = 0; c <= TX; c++) edge[c] = T.off[c0 + c];
-        for (int s = edge[0] + l; s < edge[TX]; s += STAGE_LANES) {
-            int tx = 0;
-#pragma unroll
-            for (int c = 1; c < TX; c++) tx += (edge[c] <= s) ? 1 : 0;
-            f(s, c0 + tx, tx, ty, tz);
-        }
-    }
-}
-
-// once per rebuild: the tables of every brick, stored as the LDS image the other kernels copy in.  With a.stats != NULL
-// also the population maxima of the plan check, per species: [2] = most atoms of ONE species in three consecutive cells.
-template <typename real, class Shape, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_typed_tables(BrickArgs<real> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    TypedTables<Shape, THREADS> T;
-    T.carve(s_dyn);
-    const int lb = (blockIdx.x % NXCD) * a.bg.per_xcd + blockIdx.x / NXCD;
-    if (lb >= a.bg.nbricks) return;
-    int bxi = 0, byi = 0, bzi = 0, tile_n = 0, n_own = 0;
-    typed_setup<real, Shape, THREADS, true>(a, T, bxi, byi, bzi, tile_n, n_own);
-    constexpr int ROW = TypedTables<Shape, THREADS>::row_ints(), IMG = TypedTables<Shape, THREADS>::image_ints();
-    int *row = a.btab + (size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * ROW;
-    for (int i = threadIdx.x; i < IMG; i += THREADS) row[i] = T.off[i];
-    if (threadIdx.x == 0) { row[IMG] = tile_n; row[IMG + 1] = n_own; }
-}
+// (TNT, typed_slots, typed_pitch, the prefetch depth, typed_seg_cap and the bytes of dynamic LDS of both kernels: plan.hpp;
+// the tables, their setup, the slot walk, k_brick_tables and k_brick_export: brick.hpp, with NT = TNT)
 
 // most atoms of one species in three consecutive cells of a tile row, over all bricks (-> out[0]); what the 16-bit hit
 // fields of the typed build can take is 16 G
@@ -260,18 +83,19 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 512 && Shape::NOC != 8 ? 5 : 4
     constexpr bool BAND = sizeof(real) == 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     float4 *tile = reinterpret_cast<float4 *>(s_dyn);   // {x, y, z relative to the brick origin, cell-order slot}
-    TypedTables<Shape, THREADS> T;
+    using TTab = BrickTables<Shape, THREADS, TNT>;
+    TTab T;
     T.carve(s_dyn + (size_t)a.tile_cap * 16);
     int bxi, byi, bzi, tile_n, n_own;
-    if (!typed_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
+    if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     // x sub-bins (round 5; as brick.hpp's builds): a (cell, species) block is sorted by quarter along x, and an atom of quarter s
     // takes the quarters >= s + K of the left cell of a candidate row, the middle cell and the quarters <= s - K of the right
-    // one -- 9 of 12 quarters where cells are just wider than r_list.  The boundaries of the tile's blocks (k_typed_tables
+    // one -- 9 of 12 quarters where cells are just wider than r_list.  The boundaries of the tile's blocks (k_brick_tables
     // wrote them) borrow the row buffers until the row table is in place.
     constexpr int NTT = TNT * NTC;
     const int NSUB = (a.nsub == 4 && a.bsub != nullptr) ? 4 : 1;
-    unsigned char *after = s_dyn + (size_t)a.tile_cap * 16 + TypedTables<Shape, THREADS>::bytes(a.own_cap);
+    unsigned char *after = s_dyn + (size_t)a.tile_cap * 16 + TTab::bytes(a.own_cap);
     int *s_sub = reinterpret_cast<int *>(after);
     if (NSUB > 1) {
         const int *bs = a.bsub + (size_t)(bxi + a.bg.nb[0] * (byi + a.bg.nb[1] * bzi)) * NTT;
@@ -300,11 +124,11 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 512 && Shape::NOC != 8 ? 5 : 4
         own_p[k] = own_ti[k] = 0; own_key[k] = 0; own_q[k] = 0;
         if (o < n_own) {
             int tc;
-            own_q[k] = typed_locate(T, o, own_ti[k], own_p[k], &tc);
+            own_q[k] = brick_locate(T, o, own_ti[k], own_p[k], &tc);
             own_key[k] = (a.perm[own_p[k]] < a.n_owned ? 1 : 0) | (own_sub(tc, own_ti[k]) << 1);
         }
     }
-    typed_for_each_slot(T, [&](int s, int tc, int tx, int ty, int tz) {
+    brick_for_each_slot(T, [&](int s, int tc, int tx, int ty, int tz) {
         const int gp = T.gbeg[tc] + (s - T.off[tc]);
         const int sh = T.shift[tc % NTC];
         const Rec<real> r = a.rec[gp];
@@ -329,7 +153,7 @@ __global__ __launch_bounds__(THREADS, (THREADS <= 512 && Shape::NOC != 8 ? 5 : 4
     }
     for (int o = tid + OWN_REGS * THREADS; o < n_own; o += THREADS) {
         int ti, p, tc;
-        const int q = typed_locate(T, o, ti, p, &tc);
+        const int q = brick_locate(T, o, ti, p, &tc);
         if (EMDEE_BOUND(BS_TYPED_OWN, o, a.own_cap)) T.oinfo[o] = make_int2(p, (q << 20) | (own_sub(tc, ti) << 17) | ((a.perm[p] < a.n_owned ? 1 : 0) << 16) | ti);
     }
     // candidate rows per own cell (and x quarter): for each neighbour species the 9 tile rows of 3 cells around it, packed as
@@ -560,16 +384,17 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
     real *plane = reinterpret_cast<real *>(s_dyn);                          // x | y | z, PITCH records apart
     const unsigned char *plane_b = s_dyn;
     constexpr size_t TILE_BYTES = ((size_t)3 * PITCH * sizeof(real) + 15) & ~(size_t)15;
-    TypedTables<Shape, THREADS> T;
+    using TTab = BrickTables<Shape, THREADS, TNT>;
+    TTab T;
     T.carve(s_dyn + TILE_BYTES);
     struct PairC { real sig2, e4; LJSeg<real> seg; };               // (seg: the force-only launches' folded constants, lj_pair.hpp)
-    PairC *ptab = reinterpret_cast<PairC *>(s_dyn + TILE_BYTES + TypedTables<Shape, THREADS>::bytes(a.own_cap));   // [species_i * 2 + species_j]
+    PairC *ptab = reinterpret_cast<PairC *>(s_dyn + TILE_BYTES + TTab::bytes(a.own_cap));   // [species_i * 2 + species_j]
     if (MODE == BRICK_STEP && a.guard != nullptr && *a.guard != 0) {
         if (threadIdx.x == 0) *a.trigger = 1;                               // a step queued behind a rebuild request: no trace
         return;
     }
     int bxi, byi, bzi, tile_n, n_own;
-    if (!typed_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
+    if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
 
     int own_p[OWN_REGS], own_ti[OWN_REGS], own_m[OWN_REGS], own_q[OWN_REGS];
@@ -578,7 +403,7 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
         const int o = tid + k * THREADS;
         own_p[k] = own_ti[k] = own_m[k] = own_q[k] = 0;
         if (o < n_own) {
-            own_q[k] = typed_locate(T, o, own_ti[k], own_p[k]);
+            own_q[k] = brick_locate(T, o, own_ti[k], own_p[k]);
             own_m[k] = a.cnt[own_p[k]];
         }
     }
@@ -595,7 +420,7 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
         org[1] = (double)a.g.lo[1] + (double)(byi * Shape::BY) * ((double)a.g.len[1] / (double)a.g.M[1]);
         org[2] = (double)a.g.lo[2] + (double)(bzi * Shape::BZ) * ((double)a.g.len[2] / (double)a.g.M[2]);
     }
-    typed_for_each_slot(T, [&](int s, int tc, int tx, int ty, int tz) {
+    brick_for_each_slot(T, [&](int s, int tc, int tx, int ty, int tz) {
         const int gp = T.gbeg[tc] + (s - T.off[tc]);
         const int sh = T.shift[tc % NTC];
         Rec<real> r = a.rec[gp];
@@ -627,7 +452,7 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
     }
     for (int o = tid + OWN_REGS * THREADS; o < n_own; o += THREADS) {
         int ti, p;
-        const int q = typed_locate(T, o, ti, p);
+        const int q = brick_locate(T, o, ti, p);
         if (!EMDEE_BOUND(BS_TYPED_OWN, o, a.own_cap)) continue;
         T.oinfo[o] = make_int2(p | ((q / NOC) << 30), ti);
         T.ocnt[o] = a.cnt[p];
@@ -811,38 +636,6 @@ __global__ __launch_bounds__(THREADS, (Shape::NOC == 8 ? 4 : 1)) void k_typed(Br
             if (se) atomicAdd(&a.stats[0], se);
             if (sm) atomicMax(&a.stats[1], sm);
             if (si) atomicAdd(&a.stats[2], si);
-        }
-    }
-}
-
-// verification accessor: the neighbour rows as CALLER ids, species-0 neighbours first
-template <typename real, class Shape, int THREADS, int G>
-__global__ __launch_bounds__(THREADS) void k_typed_export(BrickArgs<real> a, int *__restrict__ counts, int *__restrict__ out, int capacity,
-                                                          const int *__restrict__ cmap = nullptr) {
-    constexpr int BLK = EPL * G, NTT = TNT * Shape::NTC;
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    TypedTables<Shape, THREADS> T;
-    T.carve(s_dyn);
-    int bxi, byi, bzi, tile_n, n_own;
-    if (!typed_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
-    for (int o = threadIdx.x; o < n_own; o += THREADS) {
-        int ti, p;
-        typed_locate(T, o, ti, p);
-        if (a.perm[p] >= a.n_owned) continue;
-        const int i = cmap ? cmap[a.perm[p]] : a.perm[p];
-        const int m = a.cnt[p], n0 = m & 0xffff, n1 = (int)((unsigned)m >> 16), S1 = (n0 + BLK - 1) / BLK * BLK;
-        counts[i] = n0 + n1;
-        const unsigned short *row = a.nbr + (size_t)p * a.stride;
-        for (int e = 0; e < n0 + n1 && e < capacity; e++) {
-            const unsigned pos = e < n0 ? row_position<G>((unsigned)e) : (unsigned)S1 + row_position<G>((unsigned)(e - n0));
-            const int sl = (int)row[pos] >> a.idx_shift;
-            int lo = 0, hi = NTT;                             // typed tile cell with off[tc] <= sl < off[tc + 1]
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (T.off[mid] <= sl) lo = mid; else hi = mid;
-            }
-            const int j = a.perm[T.gbeg[lo] + (sl - T.off[lo])];
-            out[(size_t)i * capacity + e] = cmap ? cmap[j] : j;
         }
     }
 }
