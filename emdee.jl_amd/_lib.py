@@ -77,6 +77,9 @@ SIGNATURES = {
     "emdee_md_set_restraints": [_p, _p, _p, _p, _p, _i32],
     "emdee_md_restraint_sums": [_p, _p],
     "emdee_md_get_restraint_refs": [_p, _p],
+    "emdee_md_set_pull": [_p, _p, _i32, _p, _p, _i32, _i32, _i32],
+    "emdee_md_pull_read": [_p, _p, _p],
+    "emdee_md_pull_log_read": [_p, _p, _p, _p],
     "emdee_nbr_list": [_p, _p, _p, _i32],
     "emdee_md_nbr_list": [_p, _p, _p, _i32],
     "emdee_compute_nonbonded": [_p, _p, _p, _p, _p, _dbl, _p, LJModelC, _p, _i32, _i32],

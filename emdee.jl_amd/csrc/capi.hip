@@ -457,6 +457,16 @@ int32_t emdee_md_restraint_sums(emdee_md *md, double out[EMDEE_RESTRAINT_WORDS])
 int32_t emdee_md_get_restraint_refs(emdee_md *md, double *ref_dev) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->get_restraint_refs(ref_dev); });
 }
+int32_t emdee_md_set_pull(emdee_md *md, const int32_t *group_dev, int32_t n_groups, const int32_t *coords, const double *params,
+                          int32_t n_coords, int32_t log_every, int32_t log_capacity) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_pull(group_dev, n_groups, coords, params, n_coords, log_every, log_capacity); });
+}
+int32_t emdee_md_pull_read(emdee_md *md, double *coords_out, double *groups_out) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->pull_read(coords_out, groups_out); });
+}
+int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->pull_log_read(log_dev, count, dropped); });
+}
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->kernel_time(kernel, total_ms, launches); });
 }

@@ -63,6 +63,10 @@ struct IMd {
     virtual void set_restraints(const int32_t *atoms, const double *ref, const double *k, const double *flat, int32_t n) = 0;
     virtual void restraint_sums(double *out) = 0;
     virtual void get_restraint_refs(double *ref_dev) = 0;
+    virtual void set_pull(const int32_t *group, int32_t n_groups, const int32_t *coords, const double *params, int32_t n_coords,
+                          int32_t log_every, int32_t log_capacity) = 0;
+    virtual void pull_read(double *coords_out, double *groups_out) = 0;
+    virtual void pull_log_read(double *log_dev, int64_t *count, int64_t *dropped) = 0;
     virtual void set_ewald(double alpha, const int32_t *kmax) = 0;
     virtual void set_pme(double alpha, const int32_t *grid, int32_t order) = 0;
     virtual void get_box(double lo[3], double len[3]) = 0;

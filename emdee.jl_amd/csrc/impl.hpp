@@ -209,7 +209,7 @@ struct MdImpl : IMd {
         }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
         // cleared -- NbSystem::ensure_charges)
-        if (!defer_forces && !sys.charges_stale() && !restraints_unfit()) {
+        if (!defer_forces && !sys.charges_stale() && !restraints_unfit() && !pull_unfit()) {
             force_pass(EMDEE_FORCES);
             current_mask = EMDEE_FORCES;
         }
@@ -218,13 +218,16 @@ struct MdImpl : IMd {
     // a restraint table set for another atom count (or met by ghosts): it stays in force, unused, and the force pass waits for it to
     // be set again or cleared
     bool restraints_unfit() const { return !lent && sys.has_restraints() && (sys.stale(sys.tables->restraints) || n_ghost != 0); }
+    // the same for the pull table (emdee_md_set_pull)
+    bool pull_unfit() const { return !lent && sys.has_pull() && (sys.stale(sys.tables->pull) || n_ghost != 0); }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
     // The attached tables: one per constraint group (NbSystem::groups, same index), then the table of virtual sites
-    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
+    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints), then the pull table (emdee_md_set_pull).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
     // texts; what is done with one stays per kind.
-    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, TABLES };
+    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, PULL, TABLES };
     const Topology::GroupTable &attached(int k) const {
+        if (k == PULL) return sys.tables->pull;
         if (k == RESTRAINTS) return sys.tables->restraints;
         return k == VSITES ? sys.tables->vsites : sys.table(sys.groups[k]);
     }
@@ -233,9 +236,10 @@ struct MdImpl : IMd {
     static constexpr GroupText GROUP_TEXT[TABLES] = {{"a rigid molecule", "rigid molecules", "emdee_md_set_rigid3"},
                                                      {"an hbonds cluster", "hbonds clusters", "emdee_md_set_hbonds"},
                                                      {"a virtual site", "virtual sites", "emdee_md_set_vsites"},
-                                                     {"a position restraint", "position restraints", "emdee_md_set_restraints"}};
+                                                     {"a position restraint", "position restraints", "emdee_md_set_restraints"},
+                                                     {"a pull group", "pull groups", "emdee_md_set_pull"}};
     // table k has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
-    bool unchecked[TABLES] = {false, false, false, false};
+    bool unchecked[TABLES] = {false, false, false, false, false};
     // the conditions emdee_md_step refuses table k on
     void require_fitting(const char *what, int k) const {
         const Topology::GroupTable &t = attached(k);
@@ -282,6 +286,7 @@ struct MdImpl : IMd {
                       "holds %d: set them again or clear them (emdee_md_set_coulomb) before reading forces, energies or virials",
                       (long long)sys.tables->q_n, sys.n_owned);
         if (frc || en || vir) require_fitting("md_get_state (forces, energies or virials)", RESTRAINTS);
+        if (frc || en || vir) require_fitting("md_get_state (forces, energies or virials)", PULL);
         if ((en || vir) && (current_mask & 6) != 6) forces(7, 0);
         sys.ids_map();                                       // (scratch of the engine's own: before the fence)
         FenceOut fence(caller_ctx, sys.stream());
@@ -295,8 +300,8 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         require_ready("md_step");
         if (nsteps == 0) return;
-        // (a restraint table: closed steps as well, so that the state after s steps does not depend on how they were dealt to calls)
-        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || sys.has_restraints() || baro.kind != EMDEE_BAROSTAT_OFF ||
+        // (a restraint or pull table: closed steps as well, so that the state after s steps does not depend on how they were dealt to calls)
+        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || sys.has_restraints() || sys.has_pull() || baro.kind != EMDEE_BAROSTAT_OFF ||
             thermo.kind != EMDEE_THERMOSTAT_OFF) {
             step_closed(nsteps, dt, rebuild_every);
             return;
@@ -376,6 +381,7 @@ struct MdImpl : IMd {
         require_fitting("scale_box", sys.RIGID);            // (an hbonds table was refused above)
         require_fitting("scale_box", VSITES);
         require_fitting("scale_box", RESTRAINTS);
+        require_fitting("scale_box", PULL);                  // (xi0 and r0 do not scale with the box)
         sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes; sites go back on their scaled parents)
         since_build = 0;
         current_mask = 0;
@@ -477,6 +483,7 @@ struct MdImpl : IMd {
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
+            if (sys.has_pull()) sys.own_tables.pull.advance(dt);   // (xi0 <- xi0 + rate dt on the host; the step's force pass closes it: work, log)
             closed_step(dt, (event && with_sums) ? 7 : EMDEE_FORCES, rebuild_every);
             if (thermostatted && ++thermo.step % (unsigned long long)thermo.every == 0) thermostat_event(dt, n_dof);
             if (coupled) baro.step++;
@@ -716,6 +723,7 @@ struct MdImpl : IMd {
             {sys.has_rigid(), "rigid molecules (emdee_md_set_rigid3)"},
             {sys.has_vsites(), "virtual sites (emdee_md_set_vsites)"},
             {sys.has_restraints(), "position restraints (emdee_md_set_restraints)"},
+            {sys.has_pull(), "a centre-of-mass pull (emdee_md_set_pull)"},
             {pme, "particle-mesh Ewald (emdee_md_set_pme)"},
             {sys.has_ewald() && !pme, "Ewald summation (emdee_md_set_ewald)"}};
         std::string all;                                     // (every table in the way, so that one refusal says what to clear)
@@ -1013,13 +1021,14 @@ struct MdImpl : IMd {
         // stages of every sample of the radial distribution functions (emdee_md_rdf_sample); 16: the three launches of every sample
         // of the displacement and velocity correlations (emdee_md_msd_sample); 17: the launches every sample of the Green-Kubo
         // observables adds to the tensor pass (emdee_md_gk_sample); 18: the launch the position restraints add to every force pass, and
-        // the scaling of their references (emdee_md_set_restraints)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 18, EMDEE_ERR_INVALID, "kernel id out of range");
+        // the scaling of their references (emdee_md_set_restraints); 19: the three launches the centre-of-mass pull adds to every force
+        // pass (emdee_md_set_pull)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 19, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[19][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[20][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
                                 {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}, {T_GK, -1},
-                                {T_RESTRAINTS, -1}};
+                                {T_RESTRAINTS, -1}, {T_PULL, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -1140,6 +1149,42 @@ struct MdImpl : IMd {
         require_fitting("get_restraint_refs", RESTRAINTS);
         FenceOut fence(caller_ctx, sys.stream());
         EMDEE_HIP_CHECK(hipMemcpyAsync(ref_dev, t.ref.ptr, (size_t)3 * t.n * sizeof(double), hipMemcpyDeviceToDevice, sys.stream()));
+    }
+    // emdee_md_set_pull: all or nothing -- the group array is fetched, the table checked and built on the host (topo::pull_table) and
+    // uploaded before anything in force changes, then installed whole.  The neighbour list does not depend on the table; the forces do,
+    // and are evaluated again, so that planes, read-back words and table belong together on return.
+    void set_pull(const int32_t *group, int32_t n_groups, const int32_t *coords, const double *params, int32_t n_coords, int32_t log_every,
+                  int32_t log_capacity) override {
+        install("the centre-of-mass pull (emdee_md_set_pull)", "a decomposed run has none", [&] {
+            EMDEE_REQUIRE(sys.with_vel, EMDEE_ERR_STATE, "set_pull: the state was loaded without velocities");
+            sys.own_tables.set_pull(group, n_groups, coords, params, n_coords, log_every, log_capacity, sys.n_owned, sys.stream());
+            unchecked[PULL] = false;
+        }, false);
+        if (sys.charges_stale() || restraints_unfit()) { current_mask = 0; return; }
+        force_pass(EMDEE_FORCES);
+        current_mask = EMDEE_FORCES;
+        EMDEE_HIP_CHECK(hipGetLastError());
+    }
+    // what the last force pass wrote: one copy, no launch
+    void pull_read(double *coords_out, double *groups_out) override {
+        use_device(sys.ctx);
+        Topology::PullTable &t = sys.own_tables.pull;
+        EMDEE_REQUIRE(!lent && t.present, EMDEE_ERR_STATE, "pull_read: no pull table is set (emdee_md_set_pull)");
+        require_fitting("pull_read", PULL);
+        double h[PULL_MAX_COORDS * PULL_WORDS + PULL_MAX_GROUPS * 4];
+        sys.read_back_doubles(h, t.out.ptr, PULL_MAX_COORDS * PULL_WORDS + PULL_MAX_GROUPS * 4);
+        if (coords_out) for (int q = 0; q < t.n * PULL_WORDS; q++) coords_out[q] = h[q];
+        if (groups_out) for (int q = 0; q < t.n_groups * 4; q++) groups_out[q] = h[PULL_MAX_COORDS * PULL_WORDS + q];
+    }
+    void pull_log_read(double *log_dev, int64_t *count, int64_t *dropped) override {
+        use_device(sys.ctx);
+        Topology::PullTable &t = sys.own_tables.pull;
+        EMDEE_REQUIRE(!lent && t.present, EMDEE_ERR_STATE, "pull_log_read: no pull table is set (emdee_md_set_pull)");
+        if (count) *count = t.log_count;
+        if (dropped) *dropped = t.log_dropped;
+        if (!log_dev || t.log_count == 0) return;
+        FenceOut fence(caller_ctx, sys.stream());
+        EMDEE_HIP_CHECK(hipMemcpyAsync(log_dev, t.log.ptr, (size_t)2 * t.log_count * t.n * sizeof(double), hipMemcpyDeviceToDevice, sys.stream()));
     }
     // emdee_md_set_ewald, emdee_md_set_pme: all or nothing -- every refusal comes before the setting changes.  check(): the host
     // test of the setting; set(): EwaldRecip's setter (the mesh takes the place of the direct sum)

@@ -14,6 +14,7 @@
 #include "minimize.hpp"
 #include "observables.hpp"
 #include "plan.hpp"
+#include "pull.hpp"
 #include "restraint.hpp"
 #include "settle.hpp"
 #include "shake.hpp"
@@ -52,9 +53,10 @@ static inline void refuse_experiment_switches() {
 // T_MSD: the three launches of a sample of the displacement and velocity correlations (msd.hpp): gather, accumulate, finish
 // T_GK: the launches a sample of the Green-Kubo observables adds to the tensor pass (gk.hpp): the box sums, the heat sums, push, correlate
 // T_RESTRAINTS: the launch the position restraints add to every force pass, and the scaling of their references (restraint.hpp)
+// T_PULL: the three launches the centre-of-mass pull adds to every force pass (pull.hpp): partial sums, finish, apply
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
                T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_GK = 16, T_RESTRAINTS = 17,
-               T_COUNT = 18 };
+               T_PULL = 18, T_COUNT = 19 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -946,7 +948,7 @@ struct NbSystem {
     bool has_bonded() const { return tables->has_bonded; }
     // terms added behind a whole force pass (add_post_terms): such a box steps in the split form (force pass, these terms,
     // kick + drift), not the fused one
-    bool has_post() const { return has_14() || has_bonded() || has_charges() || has_restraints(); }
+    bool has_post() const { return has_14() || has_bonded() || has_charges() || has_restraints() || has_pull(); }
     // rows the filter visits right after every build: excluded pairs are struck, 1-4 and bonded partners' slots recorded
     bool filters_rows() const { return has_excl() || has_bonded(); }
     // a bonded term whose partner was missing from the rows (raised by k_bonded): the engine refuses to step until the tables or
@@ -1308,11 +1310,44 @@ struct NbSystem {
         read_back_doubles(out, queue(tables->restraints.n, RestraintSums<real>{restraint_args()}, RED_RESTRAINT), RESTRAINT_WORDS);
     }
 
+    // ---------------------------------------------------------------- the centre-of-mass pull (Topology::set_pull; pull.hpp)
+    // Three launches behind a force pass: the chunks' partial sums, the one block that finishes the bookkeeping, one thread per grouped
+    // atom.  The pass that follows PullTable::advance closes a step: the work words advance and the log takes its entry.  Undivided
+    // engines only.
+    bool has_pull() const { return tables->pull.present; }
+    void require_pull_fit(const char *what) const {
+        const Topology::PullTable &t = tables->pull;
+        EMDEE_REQUIRE(!stale(t) && !has_ghosts && tables == &own_tables, EMDEE_ERR_STATE, "%s: the pull table was set for %lld atoms, the state "
+                      "holds %d (or has ghosts): set it again or clear it (emdee_md_set_pull)", what, (long long)t.limit, n_owned);
+    }
+    void add_pull(const Pass<real> &p) {
+        if (!has_pull() || n_total == 0) return;
+        require_pull_fit("force pass");
+        EMDEE_REQUIRE(!p.to_caller(), EMDEE_ERR_STATE, "the centre-of-mass pull (emdee_md_set_pull) is not on the operator path");
+        Topology::PullTable &t = own_tables.pull;
+        ComPullArgs a{};
+        a.n_groups = t.n_groups; a.n_coords = t.n; a.closing = t.closing ? 1 : 0; a.log_slot = t.log_slot; a.dt = t.closing_dt;
+        for (int g = 0; g <= PULL_MAX_GROUPS; g++) a.chunk_of_group[g] = t.chunk_of_group[g];
+        for (int c = 0; c < PULL_MAX_COORDS; c++) { a.xi0[c] = t.xi0[c]; a.coord[c] = t.coord[c]; }
+        t.closing = false; t.log_slot = -1;
+        const RestraintArgs<real> ra = restraint_args(t.atoms.ptr, t.n_grouped);
+        const real *w = with_mass ? im.ptr : nullptr;
+        Timed timed(this, T_PULL);
+        hipLaunchKernelGGL((k_pull_partials<real>), dim3(t.n_chunks), dim3(MSD_BLOCK), 0, stream(), ra, w, (const MsdChunk *)t.chunks.ptr, t.partial.ptr);
+        hipLaunchKernelGGL(k_pull_finish, dim3(1), dim3(RED_BLOCK), 0, stream(), a, (const double *)t.partial.ptr, t.out.ptr, t.groups_out(),
+                           t.group_words.ptr, t.log.ptr);
+        with_bool(p.mask & EMDEE_TENSOR, [&](auto tensor) {
+            hipLaunchKernelGGL((k_pull_apply<real, decltype(tensor)::value>), dim3(blocks_for(t.n_grouped, 256)), dim3(256), 0, stream(), ra, w,
+                               (const int *)t.group_of.ptr, (const double *)t.group_words.ptr, p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr);
+        });
+    }
+
     void add_post_terms(const Pass<real> &p) {
         add_pairs14(p);
         add_bonded(p);
         add_ewald(p);
         add_restraints(p);
+        add_pull(p);
     }
 
     // ---------------------------------------------------------------- forces

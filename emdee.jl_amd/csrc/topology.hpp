@@ -1,5 +1,5 @@
 // topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, hbonds clusters, virtual sites,
-// position restraints, charges.  Plain C++17 on
+// position restraints, the centre-of-mass pull, charges.  Plain C++17 on
 // std::vector, no HIP: every function here validates or builds and throws through EMDEE_REQUIRE before it returns anything, so
 // a stand-alone host program can test it (tests/c/topology_host.cpp).  topology_dev.hpp holds the device buffers.
 #pragma once
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "error.hpp"
+#include "pull.hpp"
 
 namespace emdee {
 namespace topo {
@@ -334,11 +335,12 @@ inline std::string hbonds_message(const std::vector<int32_t> &atoms, int64_t clu
 // and the weights {w_b, w_c} (w_c ignored where c = -1)
 // The table as a caller gave it: ids in [0, lim) (c may be -1), no atom named twice within an entry, no atom that is a site in two
 // entries, no site that is a parent of another site, no site that the rigid, the hbonds or the restraint table in force names (`rigid`,
-// `hbonds`, `restrained`: their ids; NULL: none in force), the weights in use finite; else refused.  Parents may belong to any table.
+// `hbonds`, `restrained`: their ids; NULL: none in force), no site in a group of the pull table in force (`pulled`: the grouped ids), the
+// weights in use finite; else refused.  Parents may belong to any table.
 template <typename T>
 std::vector<int32_t> checked_vsites(const std::vector<T> &raw, const std::vector<double> &weights, int64_t lim,
                                     const std::vector<int32_t> *rigid = nullptr, const std::vector<int32_t> *hbonds = nullptr,
-                                    const std::vector<int32_t> *restrained = nullptr) {
+                                    const std::vector<int32_t> *restrained = nullptr, const std::vector<int32_t> *pulled = nullptr) {
     const int64_t n = (int64_t)(raw.size() / 4);
     EMDEE_REQUIRE((int64_t)weights.size() == 2 * n, EMDEE_ERR_INVALID, "set_vsites: %lld sites but %lld weights", (long long)n, (long long)weights.size());
     EMDEE_REQUIRE(n <= INT32_MAX / 4, EMDEE_ERR_INVALID, "set_vsites: %lld sites (at most (2^31 - 1) / 4)", (long long)n);
@@ -378,6 +380,14 @@ std::vector<int32_t> checked_vsites(const std::vector<T> &raw, const std::vector
             EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)s.first), EMDEE_ERR_INVALID, "set_vsites: atom %lld, the site of "
                           "entry %lld, is named by the restraint table in force (emdee_md_set_restraints): a site is massless and follows its "
                           "parents, it cannot be restrained", (long long)s.first, (long long)s.second);
+    }
+    if (pulled) {                                            // (the mirror of pull_table's refusal)
+        std::vector<int32_t> taken(*pulled);
+        std::sort(taken.begin(), taken.end());
+        for (const auto &s : sites)
+            EMDEE_REQUIRE(!std::binary_search(taken.begin(), taken.end(), (int32_t)s.first), EMDEE_ERR_INVALID, "set_vsites: atom %lld, the site of "
+                          "entry %lld, is in a group of the pull table in force (emdee_md_set_pull): a site is massless, a centre of mass "
+                          "cannot hold it", (long long)s.first, (long long)s.second);
     }
     for (int t = 0; t < 2; t++) {
         if (!held[t]) continue;
@@ -528,6 +538,97 @@ RestraintRows restraint_table(const std::vector<T> &ids, const std::vector<doubl
     t.ref = ref;
     t.k = k;
     t.flat = flat.empty() ? std::vector<double>((size_t)n, 0.0) : flat;
+    return t;
+}
+
+// ---- the centre-of-mass pull (emdee_md_set_pull; pull.hpp): a per-atom group array, and per coordinate five integers {a, b, kind,
+// geometry, mask} and six doubles {k or F, r0, rate, nx, ny, nz}
+// The table as the kernels read it: the grouped ids in the table order of group_layout.hpp with the group of every entry, the chunks,
+// the coordinates (the direction vectors normalised) and the starting references.
+struct PullRows {
+    std::vector<int32_t> ids, group_of;
+    MsdLayout lay;
+    PullCoord coord[PULL_MAX_COORDS] = {};
+    double r0[PULL_MAX_COORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int n_groups = 0, n_coords = 0;
+};
+// The table as a caller gave it: n_groups and n_coords in 1 ... 8, every group id in -1 ... n_groups - 1, every group non-empty, every
+// coordinate between two different groups of the table, a known kind and geometry, a mask in 1 ... 7 for the distance geometry, a
+// finite non-zero vector for the direction geometry, finite parameters, k >= 0 for an umbrella, rate = 0 for a constant force, no
+// grouped atom that is a site of the site table in force (`vsites`: its {site, a, b, c} ids; NULL: none in force); else refused, the
+// text naming the entry and the offending value.
+template <typename T>
+PullRows pull_table(const std::vector<T> &group, int64_t n_groups, const std::vector<int32_t> &coords, const std::vector<double> &params,
+                    int64_t n_coords, const std::vector<int32_t> *vsites = nullptr) {
+    EMDEE_REQUIRE(n_groups >= 1 && n_groups <= PULL_MAX_GROUPS, EMDEE_ERR_INVALID, "set_pull: n_groups = %lld is outside 1...%d", (long long)n_groups,
+                  PULL_MAX_GROUPS);
+    EMDEE_REQUIRE(n_coords >= 1 && n_coords <= PULL_MAX_COORDS, EMDEE_ERR_INVALID, "set_pull: n_coords = %lld is outside 1...%d (0 clears the table)",
+                  (long long)n_coords, PULL_MAX_COORDS);
+    EMDEE_REQUIRE((int64_t)coords.size() == 5 * n_coords && (int64_t)params.size() == 6 * n_coords, EMDEE_ERR_INVALID, "set_pull: %lld coordinates "
+                  "but %lld integers (five per coordinate) and %lld parameters (six per coordinate)", (long long)n_coords, (long long)coords.size(),
+                  (long long)params.size());
+    EMDEE_REQUIRE((int64_t)group.size() <= INT32_MAX, EMDEE_ERR_INVALID, "set_pull: %lld atoms (at most 2^31 - 1)", (long long)group.size());
+    const int n = (int)group.size();
+    std::vector<int> g32((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int64_t g = group[(size_t)i];
+        EMDEE_REQUIRE(g >= -1 && g < n_groups, EMDEE_ERR_INVALID, "set_pull: atom %d has group %lld, outside -1...%lld", i, (long long)g,
+                      (long long)n_groups - 1);
+        g32[(size_t)i] = (int)g;
+    }
+    PullRows t;
+    t.n_groups = (int)n_groups; t.n_coords = (int)n_coords;
+    t.lay = msd_layout(g32.data(), n, (int)n_groups);
+    for (int g = 0; g < (int)n_groups; g++)
+        EMDEE_REQUIRE(t.lay.sizes[g] > 0, EMDEE_ERR_INVALID, "set_pull: group %d is empty (every group in use holds at least one atom)", g);
+    for (int c = 0; c < (int)n_coords; c++) {
+        const int32_t *q = coords.data() + 5 * (size_t)c;
+        const double *p = params.data() + 6 * (size_t)c;
+        EMDEE_REQUIRE(q[0] >= 0 && q[0] < n_groups && q[1] >= 0 && q[1] < n_groups, EMDEE_ERR_INVALID, "set_pull: coordinate %d names groups %d and "
+                      "%d, outside 0...%lld", c, q[0], q[1], (long long)n_groups - 1);
+        EMDEE_REQUIRE(q[0] != q[1], EMDEE_ERR_INVALID, "set_pull: coordinate %d names group %d twice (a coordinate lies between two different groups)",
+                      c, q[0]);
+        EMDEE_REQUIRE(q[2] == PULL_UMBRELLA || q[2] == PULL_CONSTANT_FORCE, EMDEE_ERR_INVALID, "set_pull: coordinate %d has the unknown kind %d "
+                      "(EMDEE_PULL_UMBRELLA or EMDEE_PULL_CONSTANT_FORCE)", c, q[2]);
+        EMDEE_REQUIRE(q[3] == PULL_DISTANCE || q[3] == PULL_DIRECTION, EMDEE_ERR_INVALID, "set_pull: coordinate %d has the unknown geometry %d "
+                      "(EMDEE_PULL_DISTANCE or EMDEE_PULL_DIRECTION)", c, q[3]);
+        for (int w = 0; w < 3; w++)
+            EMDEE_REQUIRE(std::isfinite(p[w]), EMDEE_ERR_INVALID, "set_pull: coordinate %d has the parameter %s = %g, which is not finite", c,
+                          w == 0 ? "k (or F)" : w == 1 ? "r0" : "rate", p[w]);
+        EMDEE_REQUIRE(q[2] != PULL_UMBRELLA || p[0] >= 0.0, EMDEE_ERR_INVALID, "set_pull: coordinate %d is an umbrella with k = %g < 0", c, p[0]);
+        EMDEE_REQUIRE(q[2] != PULL_CONSTANT_FORCE || p[2] == 0.0, EMDEE_ERR_INVALID, "set_pull: coordinate %d is a constant force with rate = %g "
+                      "(a constant force has no reference to move: rate must be 0)", c, p[2]);
+        PullCoord &pc = t.coord[c];
+        pc.a = q[0]; pc.b = q[1]; pc.kind = q[2]; pc.geometry = q[3]; pc.mask = 0;
+        pc.k = p[0]; pc.rate = p[2];
+        pc.n[0] = pc.n[1] = pc.n[2] = 0.0;
+        if (q[3] == PULL_DISTANCE) {
+            EMDEE_REQUIRE(q[4] >= 1 && q[4] <= 7, EMDEE_ERR_INVALID, "set_pull: coordinate %d has the axis mask %d, outside 1...7 (bit a keeps axis a; "
+                          "a distance needs at least one)", c, q[4]);
+            pc.mask = q[4];
+        } else {
+            const double norm = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5]);
+            EMDEE_REQUIRE(std::isfinite(norm) && norm > 0.0, EMDEE_ERR_INVALID, "set_pull: coordinate %d has the direction (%g, %g, %g), which is "
+                          "zero or not finite", c, p[3], p[4], p[5]);
+            for (int a = 0; a < 3; a++) pc.n[a] = p[3 + a] / norm;
+        }
+        t.r0[c] = p[1];
+    }
+    t.ids.assign((size_t)t.lay.n_grouped, 0);
+    t.group_of.assign((size_t)t.lay.n_grouped, 0);
+    for (int i = 0; i < n; i++)
+        if (t.lay.pos_of[(size_t)i] >= 0) {
+            t.ids[(size_t)t.lay.pos_of[(size_t)i]] = i;
+            t.group_of[(size_t)t.lay.pos_of[(size_t)i]] = g32[(size_t)i];
+        }
+    if (vsites) {
+        for (size_t s = 0; s + 3 < vsites->size(); s += 4) {
+            const int32_t site = (*vsites)[s];
+            EMDEE_REQUIRE(site < 0 || site >= n || g32[(size_t)site] < 0, EMDEE_ERR_STATE, "set_pull: atom %d of group %d is a virtual site of the "
+                          "table in force (emdee_md_set_vsites): a site is massless, a centre of mass cannot hold it", site,
+                          (site >= 0 && site < n) ? g32[(size_t)site] : -1);
+        }
+    }
     return t;
 }
 

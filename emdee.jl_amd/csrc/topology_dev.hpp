@@ -193,7 +193,7 @@ struct Topology {
         VsiteTable t;
         t.atoms_h = topo::checked_vsites(fetch(atoms_dev, (size_t)4 * n, s), fetch(weights_dev, (size_t)2 * n, s), lim,
                                          rigid.present ? &rigid.atoms_h : nullptr, hbonds.present ? &hbonds.atoms_h : nullptr,
-                                         restraints.present ? &restraints.atoms_h : nullptr);
+                                         restraints.present ? &restraints.atoms_h : nullptr, pull.present ? &pull.atoms_h : nullptr);
         const std::vector<double> w = topo::vsite_weights(t.atoms_h, fetch(weights_dev, (size_t)2 * n, s));
         const topo::VsiteParents par = topo::build_vsite_parents(t.atoms_h, w);
         put(t.atoms, t.atoms_h, s); put(t.geom, w, s);
@@ -240,6 +240,79 @@ struct Topology {
         restraints.atoms.swap(t.atoms); restraints.geom.swap(t.geom); restraints.flat.swap(t.flat); restraints.ref.swap(t.ref);
         restraints.atoms_h = rows.atoms;
         restraints.n = (int)n; restraints.limit = lim; restraints.present = true;
+    }
+
+    // ---- the centre-of-mass pull (emdee_md_set_pull; pull.hpp), undivided engines only: the grouped caller ids in table order
+    // (GroupTable: atoms; n: the coordinates), the group of every entry, the chunks, and the scratch and outputs of the three launches.
+    // The host owns the coordinates, the moving references xi0, the count of completed steps and the log's bookkeeping.
+    struct PullTable : GroupTable {
+        DevBuf<int> group_of;
+        DevBuf<MsdChunk> chunks;
+        DevBuf<double> partial, out, group_words, log;       // out: n_coords x PULL_WORDS, then n_groups x 4 (one copy reads both)
+        PullCoord coord[PULL_MAX_COORDS] = {};
+        double xi0[PULL_MAX_COORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int chunk_of_group[PULL_MAX_GROUPS + 1] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        int n_groups = 0, n_grouped = 0, n_chunks = 0;
+        int log_every = 0, log_capacity = 0;
+        long long steps = 0, log_count = 0, log_dropped = 0; // completed steps since the set; entries written; samples dropped
+        // what the next force pass closes (set by advance(), taken by NbSystem::add_pull)
+        bool closing = false;
+        double closing_dt = 0.0;
+        int log_slot = -1;
+        double *groups_out() { return out.ptr + (size_t)PULL_MAX_COORDS * PULL_WORDS; }
+        // one more completed step of length dt: xi0 advances on the host, the next force pass closes the step
+        void advance(double dt) {
+            for (int c = 0; c < n; c++) xi0[c] = pull_advance(xi0[c], coord[c].rate, dt);
+            steps++;
+            closing = true; closing_dt = dt; log_slot = -1;
+            if (log_capacity > 0 && log_every > 0 && steps % log_every == 0) {
+                if (log_count < log_capacity) log_slot = (int)log_count++; else log_dropped++;
+            }
+        }
+    };
+    PullTable pull;
+    // Replaces the table by the one the host arrays describe (group_dev: device, `lim` ids); n_coords = 0 clears it.  Every refusal
+    // comes before the table in force changes.
+    void set_pull(const int32_t *group_dev, int32_t n_groups, const int32_t *coords, const double *params, int32_t n_coords, int32_t log_every,
+                  int32_t log_capacity, int64_t lim, hipStream_t s) {
+        EMDEE_REQUIRE(n_coords >= 0, EMDEE_ERR_INVALID, "set_pull: n_coords = %d is outside 1...%d (0 clears the table)", n_coords, PULL_MAX_COORDS);
+        if (n_coords == 0) {
+            pull.present = false; pull.n = 0; pull.atoms_h.clear();
+            return;
+        }
+        EMDEE_REQUIRE(n_coords <= PULL_MAX_COORDS, EMDEE_ERR_INVALID, "set_pull: n_coords = %d is outside 1...%d (0 clears the table)", n_coords, PULL_MAX_COORDS);
+        EMDEE_REQUIRE(group_dev && coords && params, EMDEE_ERR_INVALID, "set_pull: NULL array (group, coords and params are needed with n_coords > 0)");
+        EMDEE_REQUIRE(log_capacity >= 0 && log_every >= 0 && (log_capacity == 0 || log_every >= 1), EMDEE_ERR_INVALID, "set_pull: log_every = %d and "
+                      "log_capacity = %d: a log (capacity > 0) needs log_every >= 1, and neither is negative", log_every, log_capacity);
+        EMDEE_REQUIRE((int64_t)log_capacity * n_coords <= INT32_MAX / 2, EMDEE_ERR_INVALID, "set_pull: log_capacity = %d with %d coordinates is more "
+                      "than 2^30 words", log_capacity, n_coords);
+        const topo::PullRows rows = topo::pull_table(fetch(group_dev, (size_t)lim, s), n_groups,
+                                                     std::vector<int32_t>(coords, coords + 5 * (size_t)n_coords),
+                                                     std::vector<double>(params, params + 6 * (size_t)n_coords), n_coords,
+                                                     vsites.present ? &vsites.atoms_h : nullptr);
+        PullTable t;
+        put(t.atoms, rows.ids, s); put(t.group_of, rows.group_of, s);
+        t.chunks.ensure(rows.lay.chunks.size() + 1);
+        EMDEE_HIP_CHECK(hipMemcpyAsync(t.chunks.ptr, rows.lay.chunks.data(), rows.lay.chunks.size() * sizeof(MsdChunk), hipMemcpyHostToDevice, s));
+        t.partial.ensure(4 * rows.lay.chunks.size() + 1);
+        t.out.ensure((size_t)PULL_MAX_COORDS * PULL_WORDS + (size_t)PULL_MAX_GROUPS * 4);
+        t.group_words.ensure((size_t)PULL_MAX_GROUPS * PULL_GROUP_WORDS);
+        t.log.ensure((size_t)2 * log_capacity * n_coords + 1);
+        EMDEE_HIP_CHECK(hipMemsetAsync(t.out.ptr, 0, ((size_t)PULL_MAX_COORDS * PULL_WORDS + (size_t)PULL_MAX_GROUPS * 4) * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipMemsetAsync(t.group_words.ptr, 0, (size_t)PULL_MAX_GROUPS * PULL_GROUP_WORDS * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipMemsetAsync(t.log.ptr, 0, ((size_t)2 * log_capacity * n_coords + 1) * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        pull.atoms.swap(t.atoms); pull.group_of.swap(t.group_of); pull.chunks.swap(t.chunks); pull.partial.swap(t.partial);
+        pull.out.swap(t.out); pull.group_words.swap(t.group_words); pull.log.swap(t.log);
+        pull.atoms_h = rows.ids;
+        for (int c = 0; c < PULL_MAX_COORDS; c++) { pull.coord[c] = rows.coord[c]; pull.xi0[c] = rows.r0[c]; }
+        for (int g = 0; g <= PULL_MAX_GROUPS; g++) pull.chunk_of_group[g] = rows.lay.chunk_of_group[g];
+        pull.n_groups = rows.n_groups; pull.n_grouped = rows.lay.n_grouped; pull.n_chunks = (int)rows.lay.chunks.size();
+        pull.log_every = log_every; pull.log_capacity = log_capacity;
+        pull.steps = 0; pull.log_count = 0; pull.log_dropped = 0;
+        pull.closing = false; pull.closing_dt = 0.0; pull.log_slot = -1;
+        pull.n = n_coords; pull.limit = lim; pull.present = true;
     }
 
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the

@@ -7,6 +7,7 @@ export set_rdf!, rdf_sample!, rdf_reset!, rdf_read
 export set_msd!, msd_sample!, msd_reset!, msd_read
 export set_gk!, gk_sample!, gk_reset!, gk_read
 export set_restraints!, restraint_sums, restraint_refs!
+export set_pull!, pull_read, pull_log_read!
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -137,6 +138,35 @@ end
 # The references as they now stand (they follow the box), into a device Float64 matrix (3, n), table order.
 restraint_refs!(md::VelocityVerlet, out::HipArray{Float64,2}) =
     (check(ccall((:emdee_md_get_restraint_refs, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), md.handle, out.ptr)); out)
+
+# int32_t emdee_md_set_pull(emdee_md *md, const int32_t *group_dev, int32_t n_groups, const int32_t *coords, const double *params,
+#                           int32_t n_coords, int32_t log_every, int32_t log_capacity);
+# Centre-of-mass pulling: group a device Int32 vector of n_owned entries in -1 ... n_groups - 1; coords a HOST Int32 matrix (5, n_coords)
+# of {a, b, kind, geometry, mask} (groups 0-based; kind 1 umbrella, 2 constant force; geometry 1 distance, 2 direction; mask bits 1..7);
+# params a HOST Float64 matrix (6, n_coords) of {k or F, r0, rate, nx, ny, nz}.  U = 1/2 k (xi - xi0)^2 with xi0 = r0 + rate t, or -F xi.
+# xi0 and r0 do not scale with the box.  Evaluates the forces again; coords = `nothing` clears the table.
+function set_pull!(md::VelocityVerlet, group::Union{Nothing,HipArray{Int32,1}}, n_groups::Integer,
+                   coords::Union{Nothing,Matrix{Int32}}, params::Union{Nothing,Matrix{Float64}}; log_every::Integer=0, log_capacity::Integer=0)
+    check(ccall((:emdee_md_set_pull, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Int32, Int32), md.handle,
+                group === nothing ? C_NULL : group.ptr, n_groups, coords === nothing ? C_NULL : coords, params === nothing ? C_NULL : params,
+                coords === nothing ? 0 : size(coords, 2), log_every, log_capacity))
+end
+
+# int32_t emdee_md_pull_read(emdee_md *md, double *coords_out, double *groups_out);
+# (blocking, one copy) what the last force pass wrote: (8, n_coords) {xi, xi0, f, U, work, Dx, Dy, Dz} and (4, n_groups) {X, Y, Z, M}
+function pull_read(md::VelocityVerlet, n_coords::Integer, n_groups::Integer)
+    c, g = zeros(Float64, 8, n_coords), zeros(Float64, 4, n_groups)
+    check(ccall((:emdee_md_pull_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), md.handle, c, g))
+    return c, g
+end
+
+# int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
+# The log so far into a device Float64 array (2, n_coords, capacity) of {xi, f}; returns (count, dropped).
+function pull_log_read!(md::VelocityVerlet, out::HipArray{Float64,3})
+    count, dropped = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:emdee_md_pull_log_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), md.handle, out.ptr, count, dropped))
+    return count[], dropped[]
+end
 
 # int32_t emdee_md_minimize(emdee_md *md, int32_t max_iter, double f_tol, double dt_start, double dt_max, double max_step,
 #                           emdee_minimize_result *out);

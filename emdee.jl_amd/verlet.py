@@ -32,6 +32,10 @@ MSD, VACF, MSD_WORDS = 1, 2, 7
 # Green-Kubo observables (include/emdee_hip.h: emdee_md_set_gk)
 GK_STRESS, GK_HEAT, GK_WORDS = 1, 2, 9
 RESTRAINT_WORDS = 8                                        # (EMDEE_RESTRAINT_WORDS)
+# the centre-of-mass pull (include/emdee_hip.h: emdee_md_set_pull)
+PULL_WORDS, PULL_UMBRELLA, PULL_CONSTANT_FORCE, PULL_DISTANCE, PULL_DIRECTION = 8, 1, 2, 1, 2
+_PULL_KINDS = {"umbrella": PULL_UMBRELLA, "constant-force": PULL_CONSTANT_FORCE, "constant_force": PULL_CONSTANT_FORCE}
+_PULL_GEOMETRIES = {"distance": PULL_DISTANCE, "direction": PULL_DIRECTION}
 
 
 def _three(v):
@@ -87,7 +91,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # (5 for the stress of an engine with rigid molecules), 6 with both
            "green_kubo": 17,
            # the launch the position restraints add to every force pass, and the scaling of their references (set_restraints_)
-           "restraints": 18}
+           "restraints": 18,
+           # the three launches the centre-of-mass pull adds to every force pass (set_pull_): partial sums, finish, apply
+           "pull": 19}
 
 
 class MinimizeResult:
@@ -713,6 +719,65 @@ class VelocityVerlet:
         if self._restraints:
             _lib.call("emdee_md_get_restraint_refs", self._handle, C.c_void_p(out.data_ptr()))
         return out
+
+    # -- centre-of-mass pulling between atom groups (include/emdee_hip.h: emdee_md_set_pull; undivided engines)
+    _pull = None                                           # (n_coords, n_groups, log_capacity) of the table in force
+
+    def set_pull_(self, group, coords, params=None, n_groups=None, log_every=0, log_capacity=0):
+        """A bias between the centres of mass of atom groups (include/emdee_hip.h emdee_md_set_pull).  group: one integer per owned
+        atom, -1 to leave the atom out (n_groups: how many groups, 1...8; None: the largest entry + 1).  coords: a list of dicts, one
+        per coordinate, with a, b (groups), kind ("umbrella" or "constant-force"), geometry ("distance" or "direction"), k (the spring
+        constant, or the force F of a constant force), r0, rate, and mask (distance: bit a keeps axis a, default 7) or n (direction:
+        a vector, normalised by the library); or, with params, the raw tables: coords (n, 5) integers {a, b, kind, geometry, mask} and
+        params (n, 6) floats {k or F, r0, rate, nx, ny, nz}.  log_every, log_capacity: the on-device log of (xi, f), one entry every
+        log_every completed steps (capacity 0: none).  Evaluates the forces again.  Empty or None coords clears the table."""
+        import numpy as np
+        if params is None:
+            rows_i, rows_d = [], []
+            for c in (coords or []):
+                kind, geom = c.get("kind", "umbrella"), c.get("geometry", "distance")
+                n = [float(t) for t in c.get("n", (0.0, 0.0, 0.0))]
+                rows_i.append([int(c["a"]), int(c["b"]), _PULL_KINDS.get(kind, kind), _PULL_GEOMETRIES.get(geom, geom), int(c.get("mask", 7))])
+                rows_d.append([float(c.get("k", c.get("F", 0.0))), float(c.get("r0", 0.0)), float(c.get("rate", 0.0))] + n)
+            ci, cd = np.array(rows_i, dtype=np.int32).reshape(-1, 5), np.array(rows_d, dtype=np.float64).reshape(-1, 6)
+        else:
+            ci = np.ascontiguousarray(np.asarray(coords, dtype=np.int32).reshape(-1, 5))
+            cd = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1, 6))
+            if ci.shape[0] != cd.shape[0]:
+                raise ValueError("set_pull_: %d rows of coords but %d rows of params" % (ci.shape[0], cd.shape[0]))
+        nc = int(ci.shape[0])
+        if nc == 0:
+            _lib.call("emdee_md_set_pull", self._handle, None, 0, None, None, 0, 0, 0)
+            self._pull = None
+            return
+        (g,), n_groups = self._per_atom_i32("set_pull_", n_groups, group=group)
+        _lib.call("emdee_md_set_pull", self._handle, C.c_void_p(g.data_ptr()) if g is not None else None, n_groups,
+                  ci.ctypes.data_as(C.c_void_p), cd.ctypes.data_as(C.c_void_p), nc, int(log_every), int(log_capacity))
+        self._pull = (nc, n_groups, int(log_capacity))
+
+    def pull(self):
+        """What the last force pass wrote (blocking, one copy, no launch), as a dict of float64 numpy arrays: xi, xi0, f, U, work
+        (n_coords,), D (n_coords, 3), centres (n_groups, 3) and masses (n_groups,)."""
+        import numpy as np
+        if self._pull is None:
+            raise RuntimeError("pull: no pull table is set (set_pull_)")
+        nc, ng, _ = self._pull
+        c, g = np.zeros((nc, PULL_WORDS), dtype=np.float64), np.zeros((ng, 4), dtype=np.float64)
+        _lib.call("emdee_md_pull_read", self._handle, c.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p))
+        return dict(xi=c[:, 0].copy(), xi0=c[:, 1].copy(), f=c[:, 2].copy(), U=c[:, 3].copy(), work=c[:, 4].copy(), D=c[:, 5:8].copy(),
+                    centres=g[:, :3].copy(), masses=g[:, 3].copy())
+
+    def pull_log(self):
+        """The on-device log so far (blocking), as a dict: xi and f, float64 numpy (count, n_coords), entry j taken at the pass that
+        closed step (j + 1) log_every since the set; count; dropped, the samples that found the log full."""
+        if self._pull is None:
+            raise RuntimeError("pull_log: no pull table is set (set_pull_)")
+        nc, _, cap = self._pull
+        buf = torch.zeros((max(cap, 1), nc, 2), dtype=torch.float64, device=self.device)
+        count, dropped = C.c_int64(), C.c_int64()
+        _lib.call("emdee_md_pull_log_read", self._handle, C.c_void_p(buf.data_ptr()), C.byref(count), C.byref(dropped))
+        h = buf[:count.value].cpu().numpy()
+        return dict(xi=h[:, :, 0].copy(), f=h[:, :, 1].copy(), count=int(count.value), dropped=int(dropped.value))
 
     def close(self):
         if self._handle is not None:

@@ -679,7 +679,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * 15 = the four stages of every sample of the radial distribution functions (emdee_md_rdf_sample);
  * 16 = the three launches of every sample of the displacement and velocity correlations (emdee_md_msd_sample);
  * 17 = the launches every sample of the Green-Kubo observables adds to the tensor pass (emdee_md_gk_sample);
- * 18 = the launch the position restraints add to every force pass, and the scaling of their references (emdee_md_set_restraints).
+ * 18 = the launch the position restraints add to every force pass, and the scaling of their references (emdee_md_set_restraints);
+ * 19 = the three launches the centre-of-mass pull adds to every force pass (emdee_md_set_pull).
  * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
@@ -1013,6 +1014,66 @@ int32_t emdee_md_set_restraints(emdee_md *md, const int32_t *atoms_dev, const do
                                 const double *flat_dev, int32_t n);
 int32_t emdee_md_restraint_sums(emdee_md *md, double out[EMDEE_RESTRAINT_WORDS]);
 int32_t emdee_md_get_restraint_refs(emdee_md *md, double *ref_dev);
+
+/* ---- centre-of-mass pulling between atom groups (pull.hpp)
+ * A bias along a collective coordinate: a harmonic (umbrella) or constant force between the centres of mass of two groups of atoms --
+ * umbrella sampling of a potential of mean force, steered MD, pulling a molecule through a slab, holding two solutes at a distance.
+ * As with the restraints, the potential energy and the stress of the engine then hold the bias: emdee_md_energies, the pressure entries,
+ * the molecular sums, the barostats, the Green-Kubo stress and emdee_md_minimize take the term with the rest.
+ * emdee_md_set_pull (blocking; n_coords = 0 clears the table):
+ *   group_dev     n_owned int32 on the device, -1 ... n_groups - 1 by caller id, as emdee_md_set_msd takes them; -1 leaves an atom out.
+ *                 Every group in use is non-empty; the caller loads each group whole (no minimum image is taken anywhere).
+ *   n_groups      1 ... 8.
+ *   coords        HOST, n_coords x 5 int32: {a, b, kind, geometry, mask}.  a != b are groups; kind is EMDEE_PULL_UMBRELLA or
+ *                 EMDEE_PULL_CONSTANT_FORCE; geometry EMDEE_PULL_DISTANCE or EMDEE_PULL_DIRECTION; mask (distance only) keeps axis a
+ *                 where bit a is set, 1 ... 7.
+ *   params        HOST, n_coords x 6 doubles: {k or F, r0, rate, nx, ny, nz}.  n (direction only) is normalised by the library.
+ *   n_coords      1 ... 8.
+ *   log_every, log_capacity   the on-device log (below); log_capacity = 0: none.
+ * The coordinate.  M_g = sum m_i and R_g = sum m_i x_i / M_g over group g, with m_i = 1 / inv_mass (1 where the engine has no masses)
+ * and x_i the UNWRAPPED coordinates emdee_md_get_state returns, formed in fp64 in both precisions from the record, the image count and,
+ * for Float32, the cell origin: a group that diffuses through a box face or is re-sorted by a rebuild feels a continuous force.
+ * D = R_b - R_a.  EMDEE_PULL_DISTANCE: xi = |m o D|, dxi/dD = m o D / xi.  EMDEE_PULL_DIRECTION: xi = n . D, signed, dxi/dD = n.
+ * EMDEE_PULL_UMBRELLA: U = 1/2 k (xi - xi0)^2 with xi0 starting at r0; every completed step of length dt of emdee_md_step advances
+ * xi0 by rate dt -- one fp64 addition per step on the host, so the sequence does not depend on how the steps are dealt to calls
+ * (emdee_md_minimize leaves xi0 alone).  EMDEE_PULL_CONSTANT_FORCE: U = -F xi; rate must be 0.  With f = -dU/dxi the force on group b
+ * is F_b = f dxi/dD, on group a -F_b.  At xi = 0 in the distance geometry the force is zero and U finite; no division happens.
+ * An umbrella coordinate accumulates the work of its moving reference on the device by the RECTANGLE RULE: at the force pass that
+ * closes a step, after xi0 has advanced, work += f rate dt with f at the new xi and xi0.
+ * xi0 and r0 DO NOT SCALE WITH THE BOX: emdee_md_scale_box and the barostats leave them as they are.
+ * Where the term goes.  Everything is mass-weighted, so a group accelerates as one body: atom i of group g gets the force m_i A_g with
+ * A_g the sum over the coordinates that name g of (+-F_c) / M_g; its energy plane gets m_i / M_g 1/2 U_c per coordinate, its virial
+ * and tensor planes m_i / M_g 1/2 sym(D_c (x) F_b,c), each only when the pass's mask asks for it.  The box sums then hold exactly U_c and
+ * sym(D_c (x) F_b,c), and the per-atom values are translation invariant.  Three launches behind every force pass, no atomics, no order
+ * of summation that depends on the device: bitwise reproducible.  An engine with a table steps in closed steps, as a restrained one
+ * does; an engine without one is launch for launch and bit for bit what it was.  On success the forces are evaluated again.
+ * emdee_md_pull_read (blocking, one copy, no launch): what the last force pass wrote.  coords_out: n_coords x EMDEE_PULL_WORDS doubles
+ * {xi, xi0, f, U, work, Dx, Dy, Dz}; groups_out: n_groups x 4 doubles {X, Y, Z, M}.  Either may be NULL.
+ * emdee_md_pull_log_read: the log takes entry j, {xi, f} per coordinate, at the pass that closes step (j + 1) log_every counted from the
+ * set; when it is full, further samples are dropped and counted.  The entries so far go to log_dev (device, capacity x n_coords x 2
+ * doubles, queued on the context's stream; may be NULL), their number to *count, the dropped samples to *dropped.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: n_groups or n_coords outside 1 ... 8; a group id outside
+ *     -1 ... n_groups - 1; an empty group; a = b or a group outside the table; an unknown kind or geometry; a mask of 0 (or above 7) for
+ *     a distance; a zero or non-finite direction; a parameter that is not finite; k < 0; rate != 0 with a constant force; a NULL array;
+ *     a negative log_every or log_capacity, or a log without log_every >= 1.  The text names the entry and the value.
+ *   - EMDEE_ERR_STATE, the previous table in force: a call before emdee_md_set_state; ghosts; an integrator lent by emdee_dd_engine; a
+ *     grouped atom that is a virtual site of the table in force (it has no mass; emdee_md_set_vsites refuses the mirror case); a state
+ *     loaded without velocities.  A force pass on the operator path refuses with a table.
+ *   - The table survives an emdee_md_set_state with the same atom count.  After a state with another count emdee_md_step,
+ *     emdee_md_minimize, emdee_md_scale_box and the reads refuse (EMDEE_ERR_STATE) until the table is set again or cleared.
+ *   - The Green-Kubo heat flux (EMDEE_GK_HEAT) is refused with a pull table, at set and at sample.
+ * Device time: emdee_md_kernel_time index 19.
+ * Scope: undivided engines.  Follow-ups, not here: a fixed point in space as one end of a coordinate; angle and dihedral coordinates;
+ * flat-bottomed biases; decomposed engines. */
+#define EMDEE_PULL_WORDS           8
+#define EMDEE_PULL_UMBRELLA        1
+#define EMDEE_PULL_CONSTANT_FORCE  2
+#define EMDEE_PULL_DISTANCE        1
+#define EMDEE_PULL_DIRECTION       2
+int32_t emdee_md_set_pull(emdee_md *md, const int32_t *group_dev, int32_t n_groups, const int32_t *coords, const double *params,
+                          int32_t n_coords, int32_t log_every, int32_t log_capacity);
+int32_t emdee_md_pull_read(emdee_md *md, double *coords_out, double *groups_out);
+int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
