@@ -1073,9 +1073,10 @@ __global__ void k_cell_state_scale(int n, size_t pitch, Rec<real> *__restrict__ 
     Rec<real> r = rec[p];
     double ox = 0.0, oy = 0.0, oz = 0.0;
     if (sizeof(real) == 4 && rel.on) rel.origin(rel.cell[p], ox, oy, oz);
-    r.x = (real)(s.lo[0] + s.mu[0] * ((double)r.x + ox - s.lo[0]) - ox);
-    r.y = (real)(s.lo[1] + s.mu[1] * ((double)r.y + oy - s.lo[1]) - oy);
-    r.z = (real)(s.lo[2] + s.mu[2] * ((double)r.z + oz - s.lo[2]) - oz);
+    // (a factor of exactly 1 -- an axis the barostat does not couple -- leaves the coordinate its bits: lo + (x - lo) rounds twice)
+    if (s.mu[0] != 1.0) r.x = (real)(s.lo[0] + s.mu[0] * ((double)r.x + ox - s.lo[0]) - ox);
+    if (s.mu[1] != 1.0) r.y = (real)(s.lo[1] + s.mu[1] * ((double)r.y + oy - s.lo[1]) - oy);
+    if (s.mu[2] != 1.0) r.z = (real)(s.lo[2] + s.mu[2] * ((double)r.z + oz - s.lo[2]) - oz);
     rec[p] = r;
     if (scale_vel) {
         vel[p] *= vscale; vel[pitch + p] *= vscale; vel[2 * pitch + p] *= vscale;

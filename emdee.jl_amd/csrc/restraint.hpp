@@ -57,8 +57,9 @@ EMDEE_HD double restraint_term(const double d[3], const double k[3], double r0, 
 }
 
 // ---- the references follow the box (emdee_md_scale_box, every barostat event): ref <- lo + mu (ref - lo) per axis.  An atom scaled
-// the same way keeps d -> mu d.
-EMDEE_HD double restraint_scale_ref(double ref, double lo, double mu) { return lo + mu * (ref - lo); }
+// the same way keeps d -> mu d.  A factor of exactly 1 leaves the reference its bits, as it leaves the atom's coordinate
+// (kernels.hpp k_cell_state_scale).
+EMDEE_HD double restraint_scale_ref(double ref, double lo, double mu) { return mu == 1.0 ? ref : lo + mu * (ref - lo); }
 
 }  // namespace emdee
 

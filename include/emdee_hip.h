@@ -534,7 +534,8 @@ int32_t emdee_compute_nonbonded_naive(emdee_ctx *ctx, void *forces_dev, void *en
  * Atoms 0..n_owned-1 are integrated; atoms n_owned..n_owned+n_ghost-1 are ghosts (images
  * owned by another domain): they act on owned atoms but receive no force and
  * are moved only by emdee_md_unpack_ghosts.  The single-GPU reference-shaped case is
- * lo = 0, len = L, periodic = {1,1,1}, n_ghost = 0. */
+ * lo = 0, len = L, periodic = {1,1,1}, n_ghost = 0.  What an axis with periodic[d] == 0 means for atoms beyond its faces, for the
+ * box scale and for the entries that need three periodic axes: "Open axes" at emdee_md_set_state. */
 int32_t emdee_md_create(emdee_ctx *ctx, const double lo[3], const double len[3], const int32_t periodic[3],
                         emdee_lj_model model, double skin, int32_t precision, emdee_md **out);
 int32_t emdee_md_destroy(emdee_md *md);
@@ -552,7 +553,23 @@ int32_t emdee_md_destroy(emdee_md *md);
  * the atom, and emdee_md_step and emdee_md_minimize refuse until the state is replaced.  That call ends inside a step (positions
  * drifted, velocities half kicked, the forces of that step not evaluated): positions of every other atom read afterwards are
  * right, velocities are not those of a completed step, and the force plane is the step before's (a read of energies or virials
- * evaluates all three afresh, as does the next emdee_md_step after a new state). */
+ * evaluates all three afresh, as does the next emdee_md_step after a new state).
+ *
+ * Open axes (periodic[d] == 0; a slab has one, a droplet three).  The walls lo[d] and lo[d] + len[d] of an open axis are not walls:
+ * they only place the cell grid.  No minimum image is taken along d anywhere -- pair terms, bonded terms, rigid molecules, bonds to
+ * hydrogen, virtual sites, restraints and pull all use the plain difference -- so a molecule may be longer than len[d] / 2 along d.
+ *   - An atom beyond a face, at the load or after steps, is binned into the outermost cell of that side, gets no image count, and
+ *     comes back from emdee_md_get_state where it is (fp64: the bits it was given until it moves).
+ *   - Results are guaranteed for atoms up to D beyond a face, with w the widest cell, w_d = len[d] / floor(len[d] / (cutoff + skin)):
+ *     D = 12 w for a Float64 engine, D = 32 - 6 w length units for a Float32 engine ("Open axes", derives both).  Further
+ *     out the outcome is unspecified, not refused: a Float64 neighbour list may then misjudge a pair within 1e-6 of cutoff + skin, a
+ *     Float32 pair no longer sees the same separation from both of its atoms.  Many atoms far out also crowd the outermost cells.
+ *   - emdee_md_scale_box and the barostats treat an open axis as any other: x_d <- lo_d + mu_d (x_d - lo_d), len_d <- mu_d len_d
+ *     (without the 2 (cutoff + skin) test, which is the minimum image's), and the volume in every pressure is len_0 len_1 len_2,
+ *     the open lengths included -- choose them as the volume the pressure is meant for, or give the axis a compressibility of 0:
+ *     a factor mu_d of exactly 1 leaves len_d and every coordinate along d bit for bit.
+ *   - Refused on a box with an open axis, each EMDEE_ERR_STATE with its own text: emdee_md_set_ewald, emdee_md_set_pme,
+ *     emdee_md_set_rdf.  emdee_dd_create takes a fully periodic global box.  Everything else accepts open axes. */
 int32_t emdee_md_set_state(emdee_md *md, int32_t n_owned, int32_t n_ghost, const void *positions_dev,
                            const void *velocities_dev, const emdee_lj_atom *atoms_dev,
                            const void *inv_mass_dev);

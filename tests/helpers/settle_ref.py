@@ -14,13 +14,13 @@ import numpy as np
 BONDS = ((0, 1, 0), (0, 2, 0), (1, 2, 1))               # (site, site, column of geom)
 
 
-def unwrap(pos, mol, lengths):
-    """pos with the legs of every molecule moved to their minimum image from the apex"""
+def unwrap(pos, mol, lengths, periodic=(1, 1, 1)):
+    """pos with the legs of every molecule moved to their minimum image from the apex (taken on the periodic axes only)"""
     x = np.array(pos, dtype=np.float64)
-    ln = np.asarray(lengths, dtype=np.float64)
+    ln = np.asarray(lengths, dtype=np.float64) * np.asarray(periodic, dtype=bool)
     for k in (1, 2):
         d = x[mol[:, k]] - x[mol[:, 0]]
-        x[mol[:, k]] = x[mol[:, 0]] + d - ln * np.rint(d / ln)
+        x[mol[:, k]] = x[mol[:, 0]] + d - ln * np.rint(d / np.where(ln > 0.0, ln, 1.0))
     return x
 
 

@@ -137,14 +137,15 @@ def bond_velocities(x, v, pairs):
     return np.abs(np.einsum("ij,ij->i", r, dv)) / (np.linalg.norm(r, axis=1) * (np.maximum(speed[i], speed[j]) + 1e-300))
 
 
-def unwrap(pos, pairs, lengths):
-    """pos with the second atom of every pair moved to its minimum image from the first, pairs taken in order (a star's centre
-    comes first in each of its pairs; a triangle's third bond then changes nothing)"""
-    x, ln = np.array(pos, dtype=np.float64), np.asarray(lengths, dtype=np.float64)
+def unwrap(pos, pairs, lengths, periodic=(1, 1, 1)):
+    """pos with the second atom of every pair moved to its minimum image (on the periodic axes only) from the first, pairs taken
+    in order (a star's centre comes first in each of its pairs; a triangle's third bond then changes nothing)"""
+    x, ln = np.array(pos, dtype=np.float64), np.asarray(lengths, dtype=np.float64) * np.asarray(periodic, dtype=bool)
+    div = np.where(ln > 0.0, ln, 1.0)
     for a, b, _ in np.asarray(pairs, dtype=np.float64).reshape(-1, 3):
         a, b = int(a), int(b)
         d = x[b] - x[a]
-        x[b] = x[a] + d - ln * np.rint(d / ln)
+        x[b] = x[a] + d - ln * np.rint(d / div)
     return x
 
 
