@@ -72,6 +72,7 @@ SIGNATURES = {
     "emdee_md_set_ewald": [_p, _dbl, C.POINTER(_i32)],
     "emdee_md_set_pme": [_p, _dbl, C.POINTER(_i32), _i32],
     "emdee_md_set_rigid3": [_p, _p, _p, _i32],
+    "emdee_md_set_molecules": [_p, _p, _i32],
     "emdee_md_set_hbonds": [_p, _p, _p, _i32],
     "emdee_md_set_vsites": [_p, _p, _p, _i32],
     "emdee_md_set_restraints": [_p, _p, _p, _p, _p, _i32],

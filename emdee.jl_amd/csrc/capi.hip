@@ -272,6 +272,9 @@ int32_t emdee_md_set_coulomb(emdee_md *md, const double *charges_dev, int32_t n,
 int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double *geom_dev, int32_t n_mol) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_rigid3(atoms_dev, geom_dev, n_mol); });
 }
+int32_t emdee_md_set_molecules(emdee_md *md, const int32_t *molecule_dev, int32_t n) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_molecules(molecule_dev, n); });
+}
 int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_hbonds(atoms_dev, dist_dev, n_clusters); });
 }

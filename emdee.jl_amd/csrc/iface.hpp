@@ -58,6 +58,7 @@ struct IMd {
     virtual void set_bonded(int32_t kind, const int32_t *atoms, const double *params, int32_t n_terms) = 0;
     virtual void set_coulomb(const double *charges, int32_t n, double coulomb_k, double eps_rf, double coulomb14scale) = 0;
     virtual void set_rigid3(const int32_t *atoms, const double *geom, int32_t n_mol) = 0;
+    virtual void set_molecules(const int32_t *molecule, int32_t n) = 0;
     virtual void set_hbonds(const int32_t *atoms, const double *dist, int32_t n_clusters) = 0;
     virtual void set_vsites(const int32_t *atoms, const double *weights, int32_t n_sites) = 0;
     virtual void set_restraints(const int32_t *atoms, const double *ref, const double *k, const double *flat, int32_t n) = 0;

@@ -204,6 +204,8 @@ struct MdImpl : IMd {
                 sys.check_vsites(sys.tables->vsites);
                 sys.place_sites(true);
                 sys.resort();
+            } else if (k == MOLECULES) {
+                sys.check_molecules(sys.tables->molecules);     // (after the constraint tables: their groups must be whole inside it)
             }                                                // (a restraint table asks nothing of the state but its atom count: the references are kept)
             unchecked[k] = false;
         }
@@ -223,10 +225,11 @@ struct MdImpl : IMd {
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
     // The attached tables: one per constraint group (NbSystem::groups, same index), then the table of virtual sites
-    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints), then the pull table (emdee_md_set_pull).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
+    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints), then the pull table (emdee_md_set_pull), then the molecule table (emdee_md_set_molecules).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
     // texts; what is done with one stays per kind.
-    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, PULL, TABLES };
+    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, PULL, MOLECULES, TABLES };
     const Topology::GroupTable &attached(int k) const {
+        if (k == MOLECULES) return sys.tables->molecules;
         if (k == PULL) return sys.tables->pull;
         if (k == RESTRAINTS) return sys.tables->restraints;
         return k == VSITES ? sys.tables->vsites : sys.table(sys.groups[k]);
@@ -237,9 +240,10 @@ struct MdImpl : IMd {
                                                      {"an hbonds cluster", "hbonds clusters", "emdee_md_set_hbonds"},
                                                      {"a virtual site", "virtual sites", "emdee_md_set_vsites"},
                                                      {"a position restraint", "position restraints", "emdee_md_set_restraints"},
-                                                     {"a pull group", "pull groups", "emdee_md_set_pull"}};
+                                                     {"a pull group", "pull groups", "emdee_md_set_pull"},
+                                                     {"a molecule", "molecules of the molecule table", "emdee_md_set_molecules"}};
     // table k has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
-    bool unchecked[TABLES] = {false, false, false, false, false};
+    bool unchecked[TABLES] = {false, false, false, false, false, false};
     // the conditions emdee_md_step refuses table k on
     void require_fitting(const char *what, int k) const {
         const Topology::GroupTable &t = attached(k);
@@ -361,28 +365,46 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "%s: this integrator is a domain's, lent by emdee_dd_engine (the geometry of a decomposition is fixed at create)", what);
         EMDEE_REQUIRE(n_ghost == 0 && !sys.has_ghosts, EMDEE_ERR_STATE, "%s: an integrator with ghosts (its box is a domain of a larger one)", what);
     }
-    // emdee_md_set_molecular_scaling: an engine with a rigid table scales by molecular centres and couples to the molecular pressure
+    // emdee_md_set_molecular_scaling: an engine with a rigid table or a molecule table scales by molecular centres and couples to the
+    // molecular pressure
     bool molecular = false;
+    // The one predicate for "this engine may be pressure-coupled" (scaled, coupled, asked for its molecular pressure): it holds no
+    // constraint table, or the switch is on and either a molecule table covers the groups (the setters see to that) or the engine is
+    // rigid-only, whose molecules the Triangle kernels take from the rigid table.  on, table: the switch and whether a molecule table
+    // is in force, as they are or as a call is about to leave them.
+    bool couplable(bool on, bool table) const { return (!sys.has_rigid() && !sys.has_hbonds()) || (on && (table || !sys.has_hbonds())); }
+    bool couplable() const { return couplable(molecular, sys.has_molecules()); }
+    // the molecular entries take molecules from a table: the molecule table in force, else the rigid table
+    bool by_molecules() const { return sys.molecule_table() != nullptr || sys.has_rigid(); }
     void set_molecular_scaling(int32_t on) override {
         EMDEE_REQUIRE(on == 0 || on == 1, EMDEE_ERR_INVALID, "set_molecular_scaling: on = %d is neither 0 nor 1", on);
         require_undivided("set_molecular_scaling");
-        EMDEE_REQUIRE(on == 1 || !(baro.kind != EMDEE_BAROSTAT_OFF && sys.has_rigid()), EMDEE_ERR_STATE, "set_molecular_scaling: pressure coupling is on "
-                      "and the engine holds rigid molecules: switch the coupling off (emdee_md_set_barostat) or clear the table (emdee_md_set_rigid3) first");
+        if (baro.kind != EMDEE_BAROSTAT_OFF && !couplable(on == 1, sys.has_molecules())) {
+            EMDEE_REQUIRE(!sys.has_rigid(), EMDEE_ERR_STATE, "set_molecular_scaling: pressure coupling is on "
+                          "and the engine holds rigid molecules: switch the coupling off (emdee_md_set_barostat) or clear the table (emdee_md_set_rigid3) first");
+            EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "set_molecular_scaling: pressure coupling is on and the engine holds an hbonds table: switch the "
+                          "coupling off (emdee_md_set_barostat) or clear the table (emdee_md_set_hbonds) first");
+        }
         molecular = on == 1;
+        sys.molecules_on = molecular;
     }
     void scale_box(const double mu[3], double vscale) override {
         use_device(sys.ctx);
         require_undivided("scale_box");
-        EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "scale_box: the engine holds an hbonds table (emdee_md_set_hbonds): scaling atom by atom would "
-                      "break its bonds, and the molecular scale is written for three-site molecules; clear the table first");
-        EMDEE_REQUIRE(!sys.has_rigid() || molecular, EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
-                      "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
+        if (!couplable()) {
+            EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "scale_box: the engine holds an hbonds table (emdee_md_set_hbonds): scaling atom by atom would "
+                          "break its bonds, and the molecular scale is written for three-site molecules; clear the table first");
+            EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "scale_box: the engine holds rigid molecules (emdee_md_set_rigid3): scaling atom by atom "
+                          "would break their geometry, and its pressure lacks the constraint virial (emdee_md_set_molecular_scaling scales by molecular centres)");
+        }
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "scale_box: no state loaded (call emdee_md_set_state first)");
-        require_fitting("scale_box", sys.RIGID);            // (an hbonds table was refused above)
+        require_fitting("scale_box", sys.RIGID);
+        require_fitting("scale_box", sys.HBONDS);
         require_fitting("scale_box", VSITES);
         require_fitting("scale_box", RESTRAINTS);
         require_fitting("scale_box", PULL);                  // (xi0 and r0 do not scale with the box)
-        sys.scale_box(mu, vscale, sys.has_rigid());          // (validates before it writes; sites go back on their scaled parents)
+        if (molecular) require_fitting("scale_box", MOLECULES);
+        sys.scale_box(mu, vscale, by_molecules());           // (validates before it writes; sites go back on their scaled parents)
         since_build = 0;
         current_mask = 0;
         if (!sys.charges_stale()) {
@@ -396,12 +418,14 @@ struct MdImpl : IMd {
                       double temperature, uint64_t seed, uint64_t first_step) override {
         use_device(sys.ctx);
         require_undivided("set_barostat");
-        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_hbonds(), EMDEE_ERR_STATE, "set_barostat: the engine holds an hbonds table "
-                      "(emdee_md_set_hbonds): its pressure lacks the clusters' constraint virial, and the molecular sums are written for "
-                      "three-site molecules; clear the table first");
-        EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_OFF || !sys.has_rigid() || molecular, EMDEE_ERR_STATE, "set_barostat: the engine holds rigid molecules "
-                      "(emdee_md_set_rigid3): its pressure lacks the constraint virial, and scaling atom by atom would break their geometry "
-                      "(emdee_md_set_molecular_scaling couples to the molecular pressure)");
+        if (kind != EMDEE_BAROSTAT_OFF && !couplable()) {
+            EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "set_barostat: the engine holds an hbonds table "
+                          "(emdee_md_set_hbonds): its pressure lacks the clusters' constraint virial, and the molecular sums are written for "
+                          "three-site molecules; clear the table first");
+            EMDEE_REQUIRE(false, EMDEE_ERR_STATE, "set_barostat: the engine holds rigid molecules "
+                          "(emdee_md_set_rigid3): its pressure lacks the constraint virial, and scaling atom by atom would break their geometry "
+                          "(emdee_md_set_molecular_scaling couples to the molecular pressure)");
+        }
         if (kind == EMDEE_BAROSTAT_OFF) { baro.kind = EMDEE_BAROSTAT_OFF; return; }
         EMDEE_REQUIRE(kind == EMDEE_BAROSTAT_BERENDSEN || kind == EMDEE_BAROSTAT_CRESCALE, EMDEE_ERR_INVALID, "set_barostat: unknown kind %d", kind);
         EMDEE_REQUIRE(coupling >= EMDEE_COUPLE_ISOTROPIC && coupling <= EMDEE_COUPLE_ANISOTROPIC, EMDEE_ERR_INVALID, "set_barostat: unknown coupling %d", coupling);
@@ -467,15 +491,16 @@ struct MdImpl : IMd {
     // table the event's step evaluates the energies and virials with its forces when the coupling is isotropic: no pass is added
     // for the pressure.  With rigid molecules (emdee_md_set_molecular_scaling) the event takes the molecular pressure from that
     // step's forces F(x) and its stage-(e) velocities (one tensor pass), then the molecular scale, which rebuilds the list and
-    // evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.
+    // evaluates the forces on the new box; a fixed rebuild cadence restarts from the event.  A molecule table in force
+    // (emdee_md_set_molecules) couples the same way, hbonds clusters included: its molecules take the place of the rigid table's.
     // A global thermostat (emdee_md_set_thermostat) sends the call here as well: after the step that completes one of its
     // intervals, (e') K, the scalar update and v <- alpha v, before (f).  It lives here and not in closed_step, so that
     // emdee_md_minimize runs without it.
     void step_closed(int nsteps, double dt, int rebuild_every) {
         const bool coupled = baro.kind != EMDEE_BAROSTAT_OFF, rigid = sys.has_rigid(), hbonds = sys.has_hbonds();
         EMDEE_REQUIRE(!coupled || !(rigid || hbonds) || molecular, EMDEE_ERR_STATE, "md_step: pressure coupling with rigid molecules needs emdee_md_set_molecular_scaling");
-        EMDEE_REQUIRE(!coupled || !hbonds, EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
-        const bool with_sums = !rigid && !hbonds && baro.coupling == EMDEE_COUPLE_ISOTROPIC;
+        EMDEE_REQUIRE(!coupled || couplable(), EMDEE_ERR_STATE, "md_step: pressure coupling with an hbonds table (emdee_md_set_hbonds)");
+        const bool with_sums = !by_molecules() && baro.coupling == EMDEE_COUPLE_ISOTROPIC;
         const bool thermostatted = thermo.kind != EMDEE_THERMOSTAT_OFF;
         const long long n_dof = thermostatted ? degrees_of_freedom() : 0;
         EMDEE_REQUIRE(!thermostatted || n_dof >= 3, EMDEE_ERR_STATE, "md_step: the thermostat (emdee_md_set_thermostat) finds %lld degrees of "
@@ -754,8 +779,9 @@ struct MdImpl : IMd {
         obs_require_fit(OBS_GK, gk, obs_engine());
         EMDEE_REQUIRE(!sys.charges_stale(), EMDEE_ERR_STATE, "gk_sample: charges set for %lld atoms, the state holds %d: set them again or clear "
                       "them (emdee_md_set_coulomb)", (long long)sys.tables->q_n, sys.n_owned);
-        const bool molecular = sys.has_rigid() && sys.tables->rigid.n > 0;
-        if (sys.has_rigid()) {
+        const bool molecular = sys.molecular_groups() > 0;
+        if (sys.molecules_on) require_fitting("gk_sample", MOLECULES);
+        if (by_molecules()) {
             require_fitting("gk_sample", sys.RIGID);
             if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         }
@@ -788,7 +814,7 @@ struct MdImpl : IMd {
             EMDEE_HIP_CHECK(hipMemcpyAsync(xi, baro_xi.ptr, 3 * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
         }
         double P[3];
-        if (sys.has_rigid()) {                               // the molecular pressure, always through the tensor path
+        if (by_molecules()) {                                // the molecular pressure, always through the tensor path
             tensor_pass();
             double t[TENSOR_SUMS];
             sys.molecular_tensor_sums(t);
@@ -981,11 +1007,13 @@ struct MdImpl : IMd {
     void molecular_pressure_tensor(double out[12]) override {
         use_device(sys.ctx);
         EMDEE_REQUIRE(sys.sorted, EMDEE_ERR_STATE, "md: no state loaded");
-        EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "molecular_pressure_tensor: the engine holds an hbonds table (emdee_md_set_hbonds): the "
+        EMDEE_REQUIRE(!sys.has_hbonds() || couplable(), EMDEE_ERR_STATE, "molecular_pressure_tensor: the engine holds an hbonds table (emdee_md_set_hbonds): the "
                       "molecular sums are written for three-site molecules and would keep the clusters' constraint forces; clear the table first");
-        if (!sys.has_rigid()) { pressure_tensor(out); return; }
+        if (molecular) require_fitting("molecular_pressure_tensor", MOLECULES);   // (a stale table is refused, not passed over)
+        if (!by_molecules()) { pressure_tensor(out); return; }
         EMDEE_REQUIRE(!lent && n_ghost == 0, EMDEE_ERR_STATE, "molecular_pressure_tensor: rigid molecules on an integrator with ghosts or a domain's");
-        require_fitting("molecular_pressure_tensor", sys.RIGID);   // (an hbonds table was refused above)
+        require_fitting("molecular_pressure_tensor", sys.RIGID);
+        require_fitting("molecular_pressure_tensor", sys.HBONDS);
         if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
         tensor_pass();
         sys.check_bonded();
@@ -1015,7 +1043,7 @@ struct MdImpl : IMd {
         // ids 0..3: the TimerIds; 4: every fused step launch (interior + boundary halves of a decomposed step together, as
         // before they had timers of their own); 5: all but the boundary halves; 6: the boundary halves; 7: the halo of a
         // decomposed step (pack -> exchange -> unpack); 8: the reciprocal-space pass of an Ewald engine (part of 0's launches too);
-        // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale; 11: the constraint
+        // 9: the constraint stages of an engine with rigid molecules; 10: its molecular sums and molecular scale, and those of a molecule table (emdee_md_set_molecules); 11: the constraint
         // stages of an engine with an hbonds table; 12: what emdee_md_minimize adds to the stages of its steps; 13: placement and
         // force spreading of an engine with virtual sites; 14: the three launches of every event of a global thermostat; 15: the four
         // stages of every sample of the radial distribution functions (emdee_md_rdf_sample); 16: the three launches of every sample
@@ -1091,7 +1119,10 @@ struct MdImpl : IMd {
     void set_groups(int k, const char *what, Set &&set) {
         auto &g = sys.groups[k];
         install(what, "a decomposed run has none", [&] {
-            set([&](const int *a, const double *d, const std::vector<int32_t> &h, int n) { sys.check_state(g, a, d, h, n); });
+            set([&](const int *a, const double *d, const std::vector<int32_t> &h, int n) {
+                sys.check_state(g, a, d, h, n);
+                sys.check_groups_whole(a, d, n, g.sites);         // (a molecule table in force: the groups lie whole inside its molecules)
+            });
             sys.reset_error(g);
             unchecked[k] = false;
             if (sys.table(g).present) sys.velocities(g);
@@ -1104,9 +1135,23 @@ struct MdImpl : IMd {
         set_groups(sys.RIGID, "rigid molecules", [&](auto &&check) { sys.own_tables.set_rigid3(atoms, geom, n_mol, sys.n_owned, sys.stream(), check); });
     }
     void set_hbonds(const int32_t *atoms, const double *dist, int32_t n_clusters) override {
-        EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF, EMDEE_ERR_STATE, "set_hbonds: pressure coupling is on (emdee_md_set_barostat): the pressure of "
+        // (with a molecule table in force and the switch on, the engine stays couplable: the builder refuses a cluster the table splits)
+        EMDEE_REQUIRE(baro.kind == EMDEE_BAROSTAT_OFF || n_clusters == 0 || (molecular && sys.has_molecules()), EMDEE_ERR_STATE, "set_hbonds: pressure coupling is on (emdee_md_set_barostat): the pressure of "
                       "an engine with an hbonds table lacks the clusters' constraint virial; switch the coupling off first");
         set_groups(sys.HBONDS, "hbonds clusters", [&](auto &&check) { sys.own_tables.set_hbonds(atoms, dist, n_clusters, sys.n_owned, sys.stream(), check); });
+    }
+    // emdee_md_set_molecules: all or nothing -- the candidate table is fetched, checked and built on the host (topo::molecule_table),
+    // uploaded, and checked against the loaded state (NbSystem::check_molecules) before it replaces the one in force.  No atom moves;
+    // neither the list nor the forces depend on the table.
+    void set_molecules(const int32_t *molecule_dev, int32_t n) override {
+        EMDEE_REQUIRE(n != 0 || baro.kind == EMDEE_BAROSTAT_OFF || couplable(molecular, false), EMDEE_ERR_STATE, "set_molecules: pressure coupling is on "
+                      "(emdee_md_set_barostat) and the engine holds an hbonds table, which couples through the molecule table alone: switch the "
+                      "coupling off or clear the hbonds table (emdee_md_set_hbonds) first");
+        install("the molecule table (emdee_md_set_molecules)", "a decomposed run has none", [&] {
+            EMDEE_REQUIRE(sys.with_vel, EMDEE_ERR_STATE, "set_molecules: the state was loaded without velocities");
+            sys.own_tables.set_molecules(molecule_dev, n, sys.n_owned, sys.stream(), [&](const Topology::MoleculeTable &t) { sys.check_molecules(t); });
+            unchecked[MOLECULES] = false;
+        }, false);
     }
     // emdee_md_set_vsites: all or nothing -- the candidate table is checked on the host and then against the loaded masses before it
     // replaces the one in force.  The sites' velocities become 0, the sites are placed, and the list and the forces follow where they

@@ -12,6 +12,7 @@
 #include "ewald.hpp"
 #include "kernels.hpp"
 #include "minimize.hpp"
+#include "molecule.hpp"
 #include "observables.hpp"
 #include "plan.hpp"
 #include "pull.hpp"
@@ -44,7 +45,7 @@ static inline void refuse_experiment_switches() {
 // reports the two together, 5 and 6 one each); T_HALO: pack -> exchange -> unpack of a decomposed step, on the stream they run on
 // T_EWALD: the reciprocal-space pass of an Ewald engine (ewald.hpp), which runs inside T_FORCE's launches as well
 // T_SETTLE: the three constraint stages of an engine with rigid molecules (settle.hpp)
-// T_MOLECULAR: the molecular sums and the molecular scale of an engine with rigid molecules (settle.hpp)
+// T_MOLECULAR: the molecular sums and the molecular scale of an engine with rigid molecules (settle.hpp) or a molecule table (molecule.hpp)
 // T_HBONDS: the three constraint stages of an engine with an hbonds table (shake.hpp)
 // T_MINIMIZE: what emdee_md_minimize adds to the stages of a closed step (minimize.hpp): the constrained force, the reduction, the mixing
 // T_VSITE: placement and force spreading of an engine with virtual sites (vsite.hpp)
@@ -63,10 +64,11 @@ enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP 
 // (k_ewald_struck); W_SETTLE / W_HBONDS, a molecule / a cluster that moved too far for a solution (k_constraint_positions).
 // Words of the table checks (k_constraint_check), cleared and read by every check: W_RIGID_MASS, W_RIGID_DIST; W_HBONDS_DIST.
 // W_VSITE_MASS, two words of the site table's check (k_vsite_check): a site with a mass, a site with a massless parent.
+// W_MOLECULE_MASS, two words of the molecule table's check (molecule.hpp): a molecule of mass 0, a molecule not loaded whole.
 // W_IMAGE, three words: an atom (id + 1) whose periodic image count left its 10-bit field, the axis and the count (kernels.hpp
 // img_bound, raised by the two gathers); they ride the read-back every build makes.
 enum FlagWord { W_BONDED = 16, W_CHARGES = 17, W_EWALD = 18, W_SETTLE = 20, W_RIGID_MASS = 21, W_RIGID_DIST = 22, W_HBONDS = 23,
-                W_HBONDS_DIST = 24, W_IMAGE = 25, W_VSITE_MASS = 28 };
+                W_HBONDS_DIST = 24, W_IMAGE = 25, W_VSITE_MASS = 28, W_MOLECULE_MASS = 30 };
 enum PathId { PATH_BRICK = 0, PATH_DIRECT = 1 };
 
 // (the brick kernel variants, LDS_LIMIT and with_brick_variant: plan.hpp)
@@ -489,8 +491,9 @@ struct NbSystem {
     // ... then: the sorted state rescaled in place (k_cell_state_scale), the box mu_d len_d, and the re-sort -- new cells, a new
     // plan when the box changed (set_box), the list, the 1-4 and bonded slots, the charge plane at the next force pass.
     // No read-back of its own: mu and vscale are the caller's host values.
-    // molecular (emdee_md_set_molecular_scaling, an engine with a rigid table): the atoms of the table move with their molecules'
-    // centres of mass (k_molecule_scale) and k_cell_state_scale passes them over; every other atom scales as before.  Neither
+    // molecular (emdee_md_set_molecular_scaling, an engine with a rigid table or a molecule table): the atoms of the table move with
+    // their molecules' centres of mass (molecule_table(): k_molecule_centres and k_molecule_shift over the molecule table, else
+    // k_molecule_scale over the triangles) and k_cell_state_scale passes them over; every other atom scales as before.  Neither
     // kernel reads what the other writes.
     void scale_box(const double mu[3], double vscale, bool molecular = false) {
         EMDEE_REQUIRE(sorted && with_vel && !has_ghosts, EMDEE_ERR_STATE, "scale_box: needs a loaded state without ghosts");
@@ -499,14 +502,20 @@ struct NbSystem {
             ScaleBox s{};
             for (int d = 0; d < 3; d++) { s.lo[d] = lo[d]; s.mu[d] = mu[d]; }
             const int scale_vel = vscale != 1.0 ? 1 : 0;
-            if (molecular && tables->rigid.n > 0) {
+            const Topology::MoleculeTable *mt = molecular ? molecule_table() : nullptr;
+            if (mt && mt->n > 0) {
+                queue_molecule_centres(*mt, T_MOLECULAR);
+                Timed t(this, T_MOLECULAR);
+                hipLaunchKernelGGL((k_molecule_shift<real>), dim3(blocks_for(mt->n_entries, 256)), dim3(256), 0, stream(), molecule_args(*mt), s,
+                                   vscale, scale_vel);
+            } else if (molecular && !mt && tables->rigid.n > 0) {
                 Timed t(this, T_MOLECULAR);
                 hipLaunchKernelGGL((k_molecule_scale<real>), dim3(blocks_for(tables->rigid.n, 256)), dim3(256), 0, stream(), settle_args(), s,
                                    vscale, scale_vel);
             }
+            const unsigned char *member = !molecular ? nullptr : mt ? mt->member.ptr : tables->r_member.ptr;
             hipLaunchKernelGGL((k_cell_state_scale<real>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, pitch, rec.ptr,
-                               vel.ptr, s, (real)vscale, scale_vel, rel_grid(rel_now, cell_sorted.ptr),
-                               molecular ? (const unsigned char *)tables->r_member.ptr : (const unsigned char *)nullptr,
+                               vel.ptr, s, (real)vscale, scale_vel, rel_grid(rel_now, cell_sorted.ptr), member,
                                molecular ? (const int *)perm.ptr : (const int *)nullptr);
             if (has_restraints() && tables->restraints.n > 0) {   // (the references follow the box: ref <- lo + mu (ref - lo))
                 Timed t(this, T_RESTRAINTS);
@@ -1220,6 +1229,68 @@ struct NbSystem {
     }
     void check_state(ConstraintGroup &g) { check_state(g, table(g).atoms.ptr, table(g).geom.ptr, table(g).atoms_h, table(g).n); }
 
+    // ---------------------------------------------------------------- whole molecules (Topology::set_molecules; molecule.hpp)
+    // The general path of the molecular sums and the molecular scale.  molecules_on: emdee_md_set_molecular_scaling's switch, as
+    // MdImpl keeps it.  molecule_table() is the ONE place the molecular entries (scale_box, queue_molecular_tensor_sums,
+    // molecular_tensor_sums) choose their path: the molecule table if one is in force, fits the state and the switch is on, else NULL
+    // -- the Triangle kernels over the rigid table.  Undivided engines only.
+    bool molecules_on = false;
+    bool has_molecules() const { return tables->molecules.present; }
+    const Topology::MoleculeTable *molecule_table() const {
+        const Topology::MoleculeTable &t = tables->molecules;
+        return (molecules_on && t.present && !stale(t) && !has_ghosts && tables == &own_tables) ? &t : nullptr;
+    }
+    // the molecules the path in force sums over and scales by (0: the molecular entries are the atomic ones)
+    int molecular_groups() const {
+        if (const Topology::MoleculeTable *mt = molecule_table()) return mt->n;
+        return has_rigid() ? tables->rigid.n : 0;
+    }
+    MoleculeArgs<real> molecule_args(const Topology::MoleculeTable &t) const {
+        MoleculeArgs<real> a{};
+        a.n_mol = t.n; a.n_small = t.n_small; a.start = t.start.ptr; a.entry_mol = t.entry_mol.ptr; a.centres = t.centres.ptr;
+        a.r = restraint_args(t.atoms.ptr, t.n_entries);
+        a.rec = rec.ptr; a.vel = vel.ptr; a.inv_mass = with_mass ? im.ptr : nullptr;
+        return a;
+    }
+    // kernel (1): the centres of every molecule of t, for the kernel the caller queues behind it
+    void queue_molecule_centres(const Topology::MoleculeTable &t, int timer = -1) {
+        const int small_blocks = blocks_for(t.n_small, 256), large_blocks = blocks_for(t.n - t.n_small, 256 / WAVE);
+        timed_if(timer, [&] {
+            hipLaunchKernelGGL((k_molecule_centres<real>), dim3(small_blocks + large_blocks), dim3(256), 0, stream(), molecule_args(t), small_blocks);
+        });
+    }
+    // a molecule table (in force, or a candidate not yet committed) against the loaded state and the constraint tables in force:
+    // EMDEE_ERR_STATE naming the molecule whose mass is 0 or that is not loaded whole; one read-back
+    void check_molecules(const Topology::MoleculeTable &t) {
+        if (t.n == 0) return;
+        const char *const text[2] = {"its total mass is 0: the centre of mass of massless atoms is undefined (give every virtual site the id of its parents)",
+                                     "it is not loaded whole: the unwrapped distance of two atoms of a constraint group inside it misses the table's "
+                                     "distance by more than 1e-3 (relative), as after wrapping a state atom by atom; load every molecule in one piece "
+                                     "(the image the caller loads is the one the centre of mass is formed from)"};
+        throw_on_check_words(W_MOLECULE_MASS, 2, [&](int *words) {
+            queue_molecule_centres(t);
+            hipLaunchKernelGGL(k_molecule_check_mass, dim3(blocks_for(t.n, 256)), dim3(256), 0, stream(), t.n, (const double *)t.centres.ptr, words);
+            const struct { const Topology::GroupTable &g; int sites; } held[2] = {{tables->rigid, 3}, {tables->hbonds, 4}};
+            for (const auto &h : held)
+                if (h.g.present && !stale(h.g) && h.g.n > 0)
+                    hipLaunchKernelGGL((k_molecule_check_whole<real>), dim3(blocks_for(h.g.n, 256)), dim3(256), 0, stream(),
+                                       restraint_args(t.atoms.ptr, t.n_entries), h.g.n, h.sites, (const int *)h.g.atoms.ptr,
+                                       (const double *)h.g.geom.ptr, (const int *)t.mol_of.ptr, words);
+        }, [&](int w, int64_t mol) { return topo::molecule_message(t.rows, mol, text[w]); });
+    }
+    // the same test for a candidate constraint table (emdee_md_set_rigid3, emdee_md_set_hbonds) against the molecule table in force
+    void check_groups_whole(const int *atoms, const double *geom, int n, int sites) {
+        const Topology::MoleculeTable &t = tables->molecules;
+        if (!t.present || stale(t) || t.n == 0 || n == 0) return;
+        throw_on_check_words(W_MOLECULE_MASS, 2, [&](int *words) {
+            hipLaunchKernelGGL((k_molecule_check_whole<real>), dim3(blocks_for(n, 256)), dim3(256), 0, stream(), restraint_args(t.atoms.ptr, t.n_entries),
+                               n, sites, atoms, geom, (const int *)t.mol_of.ptr, words);
+        }, [&](int, int64_t mol) {
+            return topo::molecule_message(t.rows, mol, "it is not loaded whole: the unwrapped distance of two atoms of a constraint group of this call "
+                                                       "misses the table's distance by more than 1e-3 (relative); load every molecule in one piece");
+        });
+    }
+
     // ---------------------------------------------------------------- virtual interaction sites (Topology::set_vsites; vsite.hpp)
     // Placement after whatever moves parents (MdImpl::closed_step stage (c'), scale_box, the set call, a reload) and
     // spreading after every force pass that writes the engine's own force planes (MdImpl::force_pass): one thread per site or per
@@ -1767,24 +1838,34 @@ struct NbSystem {
         read_back_doubles(out, queue_tensor_sums(), TENSOR_SUMS);
     }
     // out[0..5] = W_mol, out[6..11] = K_mol (include/emdee_hip.h: emdee_md_molecular_pressure_tensor): the atomic sums above minus
-    // what the atoms of the rigid molecules carry about their centres of mass (MoleculeSums over the table, with the current
-    // force planes), the molecule pass under T_MOLECULAR, its final under the caller's timer.  The two totals lie side by side.
+    // what the atoms of the molecules carry about their centres of mass, with the current force planes -- MoleculeAtomSums over the
+    // entries of the molecule table behind k_molecule_centres if one is in force (molecule_table()), else MoleculeSums over the rigid
+    // table -- the molecule pass under T_MOLECULAR, its final under the caller's timer.  The two totals lie side by side.
     // The queueing half: both[0..11] the atomic sums, both[12..23] the molecules'; the difference both[q] - both[12 + q] is the
-    // reader's (n_total > 0 and a rigid table with molecules in it are the caller's to check).
+    // reader's (n_total > 0 and molecular_groups() > 0 are the caller's to check).
     double *queue_molecular_tensor_sums(int timer = -1) {
-        const int n_mol = tables->rigid.n;
         static_assert(RED_MOLECULE == RED_TENSOR + TENSOR_SUMS, "the readers take both totals as one array of twenty-four");
         double *tot = queue_tensor_sums(timer);
-        const int nb = queue_partials(n_mol, MoleculeSums<real>{settle_args(), frc.ptr}, T_MOLECULAR);
-        queue_final<MoleculeSums<real>>(nb, RED_MOLECULE, timer);
+        if (const Topology::MoleculeTable *mt = molecule_table()) {
+            queue_molecule_centres(*mt, T_MOLECULAR);
+            const int nb = red_blocks(mt->n_entries);
+            double *partial = red_partials();
+            timed_if(T_MOLECULAR, [&] {
+                hipLaunchKernelGGL((k_molecule_partials<real>), dim3(nb), dim3(RED_BLOCK), 0, stream(), mt->n_entries,
+                                   MoleculeAtomSums<real>{molecule_args(*mt), frc.ptr}, partial);
+            });
+            queue_final<MoleculeAtomSums<real>>(nb, RED_MOLECULE, timer);
+        } else {
+            const int nb = queue_partials(tables->rigid.n, MoleculeSums<real>{settle_args(), frc.ptr}, T_MOLECULAR);
+            queue_final<MoleculeSums<real>>(nb, RED_MOLECULE, timer);
+        }
         return tot;
     }
     // the read-back half: one copy of both totals, the subtraction on the host.  Blocking.
     void molecular_tensor_sums(double out[TENSOR_SUMS]) {
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = 0.0;
         if (n_total == 0) return;
-        const int n_mol = has_rigid() ? tables->rigid.n : 0;
-        if (n_mol == 0) { tensor_sums(out); return; }
+        if (molecular_groups() == 0) { tensor_sums(out); return; }
         double both[2 * TENSOR_SUMS];
         read_back_doubles(both, queue_molecular_tensor_sums(), 2 * TENSOR_SUMS);
         for (int q = 0; q < TENSOR_SUMS; q++) out[q] = both[q] - both[TENSOR_SUMS + q];

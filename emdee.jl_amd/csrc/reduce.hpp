@@ -3,7 +3,7 @@
 // block_sum (block_max) per word into partial[block][word].  Stage 2, final_word: one block, a strided loop over the blocks' partials,
 // then block_sum (block_max) again.  No atomics; the number of blocks is a function of n alone (red_blocks), so the order of summation
 // is, and a total is the same bits on every run.  A Term is a small struct of pointers and scalars -- EnergySums and TensorSums
-// (kernels.hpp), MoleculeSums (settle.hpp), RestraintSums (restraint.hpp), FireSums (minimize.hpp), KineticSums (thermostat.hpp),
+// (kernels.hpp), MoleculeSums (settle.hpp), MoleculeAtomSums (molecule.hpp), RestraintSums (restraint.hpp), FireSums (minimize.hpp), KineticSums (thermostat.hpp),
 // HeatSums (gk.hpp) -- with
 //     static constexpr int SUMS, MAXES;                      // its words: SUMS sums first, then MAXES maxima of values >= 0
 //     __device__ void operator()(int i, double *acc) const;  // element i's terms into acc[0 .. SUMS + MAXES)
@@ -64,12 +64,12 @@ __device__ __forceinline__ double block_max(double v, double *sh) {
     return t;   // valid in thread 0
 }
 
-// stage 1: partial[b][0 .. WORDS) over the elements of block b's stride
+// stage 1: partial[b][0 .. WORDS) over the elements of block b's stride.  The body, for k_reduce_partials and for a stage-1 kernel that
+// a family keeps under its own name (molecule.hpp k_molecule_partials); sh: RED_BLOCK / WAVE doubles of LDS
 template <class Term>
-__global__ __launch_bounds__(RED_BLOCK) void k_reduce_partials(int n, Term term, double *__restrict__ partial) {
+__device__ __forceinline__ void reduce_partials(int n, const Term &term, double *__restrict__ partial, double *sh) {
     constexpr int WORDS = Term::SUMS + Term::MAXES;
     static_assert(WORDS >= 1 && WORDS <= RED_MAX_WORDS, "the scratch of the reductions is sized for RED_MAX_WORDS words");
-    __shared__ double sh[RED_BLOCK / WAVE];
     double acc[WORDS];
     for (int q = 0; q < WORDS; q++) acc[q] = 0.0;
     for (int i = blockIdx.x * RED_BLOCK + threadIdx.x; i < n; i += gridDim.x * RED_BLOCK) term(i, acc);
@@ -77,6 +77,11 @@ __global__ __launch_bounds__(RED_BLOCK) void k_reduce_partials(int n, Term term,
         const double t = q < Term::SUMS ? block_sum(acc[q], sh) : block_max(acc[q], sh);
         if (threadIdx.x == 0) partial[WORDS * blockIdx.x + q] = t;
     }
+}
+template <class Term>
+__global__ __launch_bounds__(RED_BLOCK) void k_reduce_partials(int n, Term term, double *__restrict__ partial) {
+    __shared__ double sh[RED_BLOCK / WAVE];
+    reduce_partials(n, term, partial, sh);
 }
 
 // stage 2, one block: word q of `words` over the blocks' partials, valid in thread 0

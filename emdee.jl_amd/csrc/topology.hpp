@@ -1,5 +1,5 @@
-// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, hbonds clusters, virtual sites,
-// position restraints, the centre-of-mass pull, charges.  Plain C++17 on
+// topology.hpp -- the host side of the topology tables: exclusions and 1-4 pairs, bonded terms, rigid molecules, hbonds clusters, whole
+// molecules, virtual sites, position restraints, the centre-of-mass pull, charges.  Plain C++17 on
 // std::vector, no HIP: every function here validates or builds and throws through EMDEE_REQUIRE before it returns anything, so
 // a stand-alone host program can test it (tests/c/topology_host.cpp).  topology_dev.hpp holds the device buffers.
 #pragma once
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "error.hpp"
+#include "molecule.hpp"
 #include "pull.hpp"
 
 namespace emdee {
@@ -329,6 +330,114 @@ inline std::string hbonds_message(const std::vector<int32_t> &atoms, int64_t clu
     }
     snprintf(text, sizeof(text), "hbonds cluster %lld (atoms %s): %s", (long long)cluster, ids.c_str(), what);
     return text;
+}
+
+// ---- whole molecules (emdee_md_set_molecules; molecule.hpp): one id per atom, >= -1; equal ids >= 0 form one molecule, -1 is a
+// molecule of one.  The table the kernels read holds the molecules of two atoms and more (a molecule of one adds exactly 0 to the
+// molecular sums and scales as a free atom does): small ones (<= MOL_SMALL atoms) first, sorted by size and then by first atom, the
+// large ones behind them by first atom; caller ids ascending within a molecule.  The order depends on the table alone.
+struct MoleculeRows {
+    int n_mol = 0, n_small = 0;
+    std::vector<int32_t> start, atoms, entry_mol;            // the CSR in table order (start: n_mol + 1), the molecule of every entry
+    std::vector<int32_t> mol_of;                             // per caller id: its molecule in table order, -1 for a molecule of one
+    std::vector<int32_t> label;                              // per molecule in table order: the id the caller gave it
+    std::vector<int32_t> compact;                            // per caller id: its molecule in order of first appearance (every atom has one)
+    std::vector<uint8_t> member;                             // per caller id: 1 for the atoms of the table (k_cell_state_scale passes them over)
+};
+// the atoms of a molecule, for the error texts: at most eight ids, then their number
+inline std::string molecule_atoms_text(const MoleculeRows &t, int64_t mol) {
+    if (mol < 0 || mol >= t.n_mol) return "?";
+    std::string ids;
+    const int first = t.start[(size_t)mol], end = t.start[(size_t)mol + 1];
+    for (int e = first; e < end && e < first + 8; e++) ids += (e > first ? " " : "") + std::to_string(t.atoms[(size_t)e]);
+    if (end - first > 8) ids += " ... (" + std::to_string(end - first) + " atoms)";
+    return ids;
+}
+// the error texts of the device checks (molecule: the number the kernels report, in table order)
+inline std::string molecule_message(const MoleculeRows &t, int64_t mol, const char *what) {
+    const bool in = mol >= 0 && mol < t.n_mol;
+    return "molecule " + std::to_string(in ? t.label[(size_t)mol] : -1) + " of the molecule table (atoms " + molecule_atoms_text(t, mol) + "): " + what;
+}
+// Every constraint must lie inside one molecule: refused if a group of `ids` (`sites` per group, -1 in unused slots) has atoms that
+// do not all carry one id >= 0 of `molecule` (one id per caller id).  name: the call that refuses; noun: "rigid molecule" or
+// "hbonds cluster"; setter: the call that set the groups.
+inline void refuse_split_groups(const char *name, const char *noun, const char *setter, int sites, const std::vector<int32_t> &ids,
+                                const std::vector<int32_t> &molecule) {
+    for (size_t g = 0; g < ids.size() / (size_t)sites; g++) {
+        std::string text;
+        int32_t first = -1, m0 = -1;
+        for (int a = 0; a < sites; a++)
+            if (ids[(size_t)sites * g + a] >= 0) text += (text.empty() ? "" : " ") + std::to_string(ids[(size_t)sites * g + a]);
+        for (int a = 0; a < sites; a++) {
+            const int32_t id = ids[(size_t)sites * g + a];
+            if (id < 0 || (size_t)id >= molecule.size()) continue;
+            const int32_t m = molecule[(size_t)id];
+            EMDEE_REQUIRE(m >= 0, EMDEE_ERR_INVALID, "%s: %s %lld (atoms %s, %s) has atom %d in no molecule of the molecule table (id -1, "
+                          "emdee_md_set_molecules): a constraint must lie inside one molecule", name, noun, (long long)g, text.c_str(), setter, id);
+            if (first < 0) { first = id; m0 = m; }
+            EMDEE_REQUIRE(m == m0, EMDEE_ERR_INVALID, "%s: %s %lld (atoms %s, %s) is split by the molecule table (emdee_md_set_molecules): atom "
+                          "%d is in molecule %d, atom %d in molecule %d; a constraint must lie inside one molecule", name, noun, (long long)g,
+                          text.c_str(), setter, first, m0, id, m);
+        }
+    }
+}
+// The table from the ids as a caller gave them (`rigid`, `hbonds`: the ids of the constraint tables in force; NULL: none): ids >= -1,
+// no constraint group split or left at -1; else refused.
+template <typename T>
+MoleculeRows molecule_table(const std::vector<T> &raw, int64_t lim, const std::vector<int32_t> *rigid = nullptr,
+                            const std::vector<int32_t> *hbonds = nullptr) {
+    EMDEE_REQUIRE((int64_t)raw.size() == lim, EMDEE_ERR_INVALID, "set_molecules: %lld ids, the state holds %lld atoms (one id per atom; "
+                  "n = 0 clears the table)", (long long)raw.size(), (long long)lim);
+    const size_t n = raw.size();
+    std::vector<int32_t> given(n);
+    for (size_t i = 0; i < n; i++) {
+        EMDEE_REQUIRE(raw[i] >= -1 && raw[i] <= INT32_MAX, EMDEE_ERR_INVALID, "set_molecules: the molecule %lld of atom %lld is below -1 "
+                      "(-1: a molecule of one)", (long long)raw[i], (long long)i);
+        given[i] = (int32_t)raw[i];
+    }
+    if (rigid) refuse_split_groups("set_molecules", "rigid molecule", "emdee_md_set_rigid3", 3, *rigid, given);
+    if (hbonds) refuse_split_groups("set_molecules", "hbonds cluster", "emdee_md_set_hbonds", 4, *hbonds, given);
+    // compaction in order of first appearance by caller id
+    MoleculeRows t;
+    t.compact.assign(n, -1); t.mol_of.assign(n, -1); t.member.assign(n, 0);
+    std::vector<std::pair<int32_t, int32_t>> seen;            // (given id, atom), sorted: equal ids side by side, atoms ascending
+    for (size_t i = 0; i < n; i++)
+        if (given[i] >= 0) seen.emplace_back(given[i], (int32_t)i);
+    std::sort(seen.begin(), seen.end());
+    struct Mol { int32_t first, size, label; size_t at; };
+    std::vector<Mol> mols;
+    for (size_t k = 0; k < seen.size(); k++) {
+        if (k == 0 || seen[k].first != seen[k - 1].first) mols.push_back(Mol{seen[k].second, 0, seen[k].first, k});
+        mols.back().size++;
+    }
+    for (size_t i = 0; i < n; i++)
+        if (given[i] < 0) mols.push_back(Mol{(int32_t)i, 1, -1, 0});
+    std::sort(mols.begin(), mols.end(), [](const Mol &a, const Mol &b) { return a.first < b.first; });
+    for (size_t c = 0; c < mols.size(); c++) {
+        if (mols[c].label < 0) { t.compact[(size_t)mols[c].first] = (int32_t)c; continue; }
+        for (int32_t k = 0; k < mols[c].size; k++) t.compact[(size_t)seen[mols[c].at + k].second] = (int32_t)c;
+    }
+    // the table order: molecules of one left out, size classes, the small class by size, then by first atom
+    std::vector<Mol> order;
+    for (const Mol &m : mols)
+        if (m.size >= 2) order.push_back(m);
+    std::sort(order.begin(), order.end(), [](const Mol &a, const Mol &b) {
+        const int32_t ka = a.size <= MOL_SMALL ? a.size : MOL_SMALL + 1, kb = b.size <= MOL_SMALL ? b.size : MOL_SMALL + 1;
+        return ka != kb ? ka < kb : a.first < b.first;
+    });
+    t.n_mol = (int)order.size();
+    t.start.push_back(0);
+    for (size_t m = 0; m < order.size(); m++) {
+        if (order[m].size <= MOL_SMALL) t.n_small = (int)m + 1;
+        t.label.push_back(order[m].label);
+        for (int32_t k = 0; k < order[m].size; k++) {
+            const int32_t id = seen[order[m].at + k].second;
+            t.atoms.push_back(id); t.entry_mol.push_back((int32_t)m);
+            t.mol_of[(size_t)id] = (int32_t)m; t.member[(size_t)id] = 1;
+        }
+        t.start.push_back((int32_t)t.atoms.size());
+    }
+    return t;
 }
 
 // ---- virtual interaction sites (emdee_md_set_vsites; vsite.hpp): {site, a, b, c} ids per entry, c = -1 for a two-parent site,

@@ -159,6 +159,8 @@ struct Topology {
         std::vector<uint8_t> member;                         // (outlives the upload)
         const bool set = set_groups(rigid, "set_rigid3", "molecules", 3, 2, atoms_dev, geom_dev, n, lim, s, [&](std::vector<int32_t> &ids, std::vector<double> &geom) {
             ids = topo::checked_rigid3(ids, geom, lim, hbonds.present ? &hbonds.atoms_h : nullptr, vsites.present ? &vsites.atoms_h : nullptr);
+            if (molecules.present && molecules.limit == lim)
+                topo::refuse_split_groups("set_rigid3", "rigid molecule", "this call", 3, ids, molecules.ids_h);
             member = topo::rigid3_members(ids, lim);
             put(nm, member, s);
         }, check);
@@ -168,8 +170,52 @@ struct Topology {
     void set_hbonds(const int32_t *atoms_dev, const double *dist_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
         set_groups(hbonds, "set_hbonds", "clusters", 4, 3, atoms_dev, dist_dev, n, lim, s, [&](std::vector<int32_t> &ids, std::vector<double> &dist) {
             ids = topo::checked_hbonds(ids, dist, lim, rigid.present ? &rigid.atoms_h : nullptr, vsites.present ? &vsites.atoms_h : nullptr);
+            if (molecules.present && molecules.limit == lim)
+                topo::refuse_split_groups("set_hbonds", "hbonds cluster", "this call", 4, ids, molecules.ids_h);
             dist = topo::hbonds_distances(ids, dist);
         }, check);
+    }
+
+    // ---- whole molecules (emdee_md_set_molecules; molecule.hpp), undivided engines only: the CSR of topo::MoleculeRows (GroupTable:
+    // atoms = the entries' caller ids, n = the molecules of two atoms and more), the molecule of every entry and of every caller id, the
+    // membership bytes, and the centres the first kernel writes for the second.
+    struct MoleculeTable : GroupTable {
+        DevBuf<int> start, entry_mol, mol_of;
+        DevBuf<unsigned char> member;
+        DevBuf<double> centres;
+        std::vector<int32_t> ids_h;                          // the ids as given, one per atom (the constraint setters check against them)
+        topo::MoleculeRows rows;                             // the host copy (the error texts name molecules and atoms from it)
+        int n_small = 0, n_entries = 0;
+    };
+    MoleculeTable molecules;
+    // Replaces the table by the one the n ids at molecule_dev (device) describe; n = 0 with NULL clears it.  check(table): the
+    // engine's test of the uploaded candidate against its state; it throws to refuse, and the table in force stays.
+    template <class Check>
+    void set_molecules(const int32_t *molecule_dev, int64_t n, int64_t lim, hipStream_t s, Check &&check) {
+        EMDEE_REQUIRE(n >= 0 && (n == 0 || molecule_dev), EMDEE_ERR_INVALID, "set_molecules: negative count or NULL array with n > 0");
+        if (n == 0) {
+            molecules.present = false; molecules.n = 0; molecules.n_small = 0; molecules.n_entries = 0;
+            molecules.atoms_h.clear(); molecules.ids_h.clear(); molecules.rows = topo::MoleculeRows{};
+            return;
+        }
+        EMDEE_REQUIRE(n == lim, EMDEE_ERR_INVALID, "set_molecules: n = %lld is neither 0 nor the atom count %lld (one id per atom)", (long long)n,
+                      (long long)lim);
+        MoleculeTable t;
+        t.ids_h = fetch(molecule_dev, (size_t)n, s);
+        t.rows = topo::molecule_table(t.ids_h, lim, rigid.present && rigid.limit == lim ? &rigid.atoms_h : nullptr,
+                                      hbonds.present && hbonds.limit == lim ? &hbonds.atoms_h : nullptr);
+        put(t.start, t.rows.start, s); put(t.atoms, t.rows.atoms, s); put(t.entry_mol, t.rows.entry_mol, s);
+        put(t.mol_of, t.rows.mol_of, s); put(t.member, t.rows.member, s);
+        t.centres.ensure((size_t)MOL_CENTRE * t.rows.n_mol + 1);
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        t.atoms_h = t.rows.atoms;
+        t.n = t.rows.n_mol; t.n_small = t.rows.n_small; t.n_entries = (int)t.rows.atoms.size(); t.limit = lim; t.present = true;
+        check(t);
+        // ---- commit
+        molecules.start.swap(t.start); molecules.atoms.swap(t.atoms); molecules.entry_mol.swap(t.entry_mol); molecules.mol_of.swap(t.mol_of);
+        molecules.member.swap(t.member); molecules.centres.swap(t.centres);
+        molecules.atoms_h = t.atoms_h; molecules.ids_h = t.ids_h; molecules.rows = t.rows;
+        molecules.n = t.n; molecules.n_small = t.n_small; molecules.n_entries = t.n_entries; molecules.limit = lim; molecules.present = true;
     }
 
     // ---- virtual interaction sites (emdee_md_set_vsites; vsite.hpp), undivided engines only: {site, a, b, c} caller ids (c = -1: a

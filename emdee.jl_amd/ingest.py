@@ -303,6 +303,34 @@ def hydrogen_clusters(types, bonds, table, length_unit=1.0, skip=(), with_droppe
     return out + (arr(sorted(drop), 2),) if with_dropped else out
 
 
+def molecules(n_atoms, bonds):
+    """The molecule table (emdee_md_set_molecules) of a bond graph: the connected components of `bonds` ((m, 2) ids, the full
+    list, constrained bonds included) as an (n_atoms,) int32 array, one id per atom.  Ids are dense and in order of first
+    appearance by atom id; an atom without a bond is a molecule of one and gets -1.  Union-find with path halving, plain Python."""
+    n_atoms = int(n_atoms)
+    root = list(range(n_atoms))
+
+    def find(a):
+        while root[a] != a:
+            root[a] = root[root[a]]
+            a = root[a]
+        return a
+    for i, j in np.asarray(bonds, dtype=np.int64).reshape(-1, 2):
+        i, j = int(i), int(j)
+        if not (0 <= i < n_atoms and 0 <= j < n_atoms):
+            raise ValueError("molecules: bond (%d, %d) names an atom outside [0, %d)" % (i, j, n_atoms))
+        a, b = find(i), find(j)
+        if a != b:
+            root[max(a, b)] = min(a, b)
+    roots = [find(a) for a in range(n_atoms)]
+    size = np.bincount(np.array(roots, dtype=np.int64), minlength=n_atoms) if n_atoms else np.zeros(0, dtype=np.int64)
+    ids, out = {}, np.full(n_atoms, -1, dtype=np.int32)
+    for a, r in enumerate(roots):
+        if size[r] >= 2:
+            out[a] = ids.setdefault(r, len(ids))
+    return out
+
+
 def save_checkpoint(path, positions, velocities, step, box_length):
     """(x, v, step, L) as a compressed npz; accepts GPU tensors or numpy arrays."""
     to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)

@@ -400,6 +400,14 @@ end
 set_molecular_scaling!(md::VelocityVerlet, on::Bool=true) =
     check(ccall((:emdee_md_set_molecular_scaling, libemdee_hip), Int32, (Ptr{Cvoid}, Int32), md.handle, Int32(on)))
 
+# int32_t emdee_md_set_molecules(emdee_md *md, const int32_t *molecule_dev, int32_t n);
+# The molecule table: a device Int32 vector of one id per atom in caller order, equal ids >= 0 form one molecule, -1 is a molecule
+# of one.  With set_molecular_scaling! on, the molecular pressure, scale_box! and the barostats take whole molecules from it, and an
+# engine with set_hbonds! in force can be pressure-coupled.  Load every molecule whole; `nothing` clears the table.
+set_molecules!(md::VelocityVerlet, molecule::Union{Nothing,HipArray{Int32,1}}) =
+    check(ccall((:emdee_md_set_molecules, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), md.handle,
+                molecule === nothing ? C_NULL : molecule.ptr, molecule === nothing ? 0 : length(molecule)))
+
 # int32_t emdee_md_get_state(emdee_md*, void *positions, void *velocities, void *forces, void *energies, void *virials);
 function state!(md::VelocityVerlet{T}, positions::HipArray{T,2}, velocities::HipArray{T,2}, forces::HipArray{T,2}) where {T}
     check(ccall((:emdee_md_get_state, libemdee_hip), Int32,

@@ -73,7 +73,8 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            "ewald_reciprocal": 8,
            # the constraint stages of an engine with rigid molecules (set_rigid3_)
            "settle": 9,
-           # the molecular sums and the molecular scale of an engine with rigid molecules (set_molecular_scaling_)
+           # the molecular sums and the molecular scale of an engine with rigid molecules (set_molecular_scaling_) or a molecule
+           # table (set_molecules_: the centres, then the entries' pass or the shift)
            "molecular": 10,
            # the constraint stages of an engine with an hbonds table (set_hbonds_)
            "hbonds": 11,
@@ -263,7 +264,8 @@ class VelocityVerlet:
 
     def molecular_tensor_sums(self):
         """The twelve fp64 sums of emdee_md_molecular_pressure_tensor: W_mol (6), K_mol (6) -- tensor_sums() minus what the atoms
-        of the rigid molecules (set_rigid3_) carry about their centres of mass; without a table, tensor_sums() itself (blocking)."""
+        of the rigid molecules (set_rigid3_), or of the molecules of set_molecules_ with set_molecular_scaling_ on, carry about
+        their centres of mass; without a table, tensor_sums() itself (blocking)."""
         out = (C.c_double * 12)()
         _lib.call("emdee_md_molecular_pressure_tensor", self._handle, out)
         return list(out)
@@ -573,6 +575,17 @@ class VelocityVerlet:
         (set_rigid3_) accepts scale_box_ and set_barostat_ -- molecules are translated with their centres of mass, and the
         coupling takes the molecular pressure.  Changes nothing for an engine without a table."""
         _lib.call("emdee_md_set_molecular_scaling", self._handle, int(on))
+
+    def set_molecules_(self, molecule):
+        """The molecule table (include/emdee_hip.h emdee_md_set_molecules): one int32 id per atom in caller order, equal ids >= 0
+        form one molecule, -1 is a molecule of one (ingest.molecules builds the array from a bond list).  With
+        set_molecular_scaling_ on, molecular_tensor_sums, scale_box_ and the barostats take whole molecules from it, and an engine
+        with set_hbonds_ in force can be pressure-coupled.  Load every molecule whole.  None clears the table."""
+        if molecule is None:
+            _lib.call("emdee_md_set_molecules", self._handle, None, 0)
+            return
+        m = torch.as_tensor(molecule).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        _lib.call("emdee_md_set_molecules", self._handle, C.c_void_p(m.data_ptr()) if m.numel() else None, int(m.shape[0]))
 
     # -- exclusions and 1-4 pairs (include/emdee_hip.h; set after the state is loaded, undivided boxes)
     def set_exclusions_(self, pairs):

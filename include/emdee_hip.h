@@ -398,11 +398,13 @@ int32_t emdee_md_set_rigid3(emdee_md *md, const int32_t *atoms_dev, const double
  *     refuses to step until the table or the state is replaced.
  *   - The split calls never constrain.  Forces, energies, virials and tensors stay those of the force field.  Masses are
  *     unrestricted.
- *   - Pressure: whatever emdee_md_set_molecular_scaling says, an engine with an hbonds table refuses emdee_md_scale_box,
- *     emdee_md_set_barostat (other than OFF) and emdee_md_molecular_pressure_tensor with EMDEE_ERR_STATE, and this call returns
- *     EMDEE_ERR_STATE while a barostat is on.  The molecular sums and the molecular scale are written for three-site molecules;
- *     without the clusters' part the promise that constraint forces drop out of the molecular pressure would be false.
- *     Extending them to clusters is a follow-up, not part of this call.
+ *   - Pressure: without a molecule table (emdee_md_set_molecules), whatever emdee_md_set_molecular_scaling says, an engine with
+ *     an hbonds table refuses emdee_md_scale_box, emdee_md_set_barostat (other than OFF) and emdee_md_molecular_pressure_tensor
+ *     with EMDEE_ERR_STATE, and this call returns EMDEE_ERR_STATE while a barostat is on: the molecular sums and the molecular
+ *     scale of the rigid table are written for three-site molecules, and without the clusters' part the promise that constraint
+ *     forces drop out of the molecular pressure would be false.  With a molecule table in force and
+ *     emdee_md_set_molecular_scaling on, all four are accepted: the sums and the scale run over whole molecules, every cluster
+ *     inside one (a cluster that the molecule table in force splits, or leaves at -1, is EMDEE_ERR_INVALID here).
  *   - The device time of stages (a), (c) and (e) is emdee_md_kernel_time index 11. */
 int32_t emdee_md_set_hbonds(emdee_md *md, const int32_t *atoms_dev, const double *dist_dev, int32_t n_clusters);
 
@@ -674,13 +676,54 @@ int32_t emdee_md_pressure_tensor(emdee_md *md, double out[12]);
  *   - the coupling events of an engine with a table take P from the molecular sums, for all three couplings, always through
  *     the tensor path (one tensor pass per event): P_d = (K_mol^dd + W_mol^dd) / V, isotropic P = tr(K_mol + W_mol) / (3 V);
  *     mu and velocity_scale from the formulas of emdee_md_set_barostat, applied with the molecular scale.
+ *   - with a molecule table in force (emdee_md_set_molecules, below) the three entries take their molecules from it, and an
+ *     engine with an hbonds table is accepted by all of them.
  * On an engine without a table the switch changes nothing, bit for bit.  emdee_md_energies and emdee_md_pressure_tensor return
  * atomic values always.  EMDEE_ERR_INVALID for on outside {0, 1}; EMDEE_ERR_STATE on an integrator lent by emdee_dd_engine or
  * with ghosts, and for switching off while a barostat is on and a table is in force (the setting stays).
  * The device time of the molecular sums and the molecular scale is emdee_md_kernel_time index 10.
- * Scope: undivided orthorhombic boxes, the molecules of the rigid table; no emdee_dd_* counterpart. */
+ * Scope: undivided orthorhombic boxes, the molecules of the rigid table or of the molecule table below; no emdee_dd_* counterpart.
+ *
+ * Whole molecules of any size.  The definitions above hold for ANY partition of the atoms into groups, as long as every
+ * constraint lies inside one group: constraint forces are internal to a group and sum to zero, so they drop out of W_mol whatever
+ * the group's size, and tr W_mol is -dU/dln(mu) of the scale that translates each group with its centre of mass.  The natural unit
+ * is the whole molecule (solute, water, lipid, polymer chain): bonded geometry, constraint geometry and rotation then survive a box
+ * scale to rounding.
+ * emdee_md_set_molecules(molecule_dev, n): n = n_owned int32 ids in caller order on the device, each >= -1; equal ids >= 0 form one
+ * molecule (ids need not be dense or ordered), -1 is a molecule of one.  The array is copied; the call blocks.  n = 0 with NULL
+ * clears the table.  While a table is in force AND emdee_md_set_molecular_scaling is on, emdee_md_molecular_pressure_tensor,
+ * emdee_md_scale_box and every barostat event take their molecules from this table instead of the rigid table: the inner sums of
+ * W_mol and K_mol run over all atoms of each molecule; the scale moves every atom of a molecule by (mu - 1) (Y - lo) and adds
+ * (velocity_scale - 1) V to its velocity.  An engine with an hbonds table then accepts emdee_md_scale_box, emdee_md_set_barostat
+ * (Berendsen with all three couplings, C-rescale), emdee_md_molecular_pressure_tensor, and emdee_md_set_hbonds while a barostat is
+ * on.  Without a table, or with the switch off, every entry behaves as before this call existed, texts and bits alike.
+ *   - Centres of mass are formed in fp64 from the UNWRAPPED coordinates (the record plus the image counts kept per atom, as
+ *     restraints and the pull take them), every difference relative to the molecule's first atom: a molecule may be larger than
+ *     half a box, so THE CALLER LOADS EVERY MOLECULE WHOLE (emdee_md_set_pull has the same contract).  A record's shift uses the
+ *     image of Y that goes with it, r' = r + (mu - 1) (Y - k L - lo) with k its image counts: the stored counts stay valid.
+ *   - Three launches per use: the centres (one thread per molecule of up to 8 atoms, one wavefront per larger one), then the
+ *     sums over the table's entries (the two-stage reduction of every box sum) or the shift (one thread per entry).  No atomics; the
+ *     order of every sum depends on the table alone: the same bits in every run.  Molecules of one atom are left out of the table:
+ *     they add exactly 0 and scale as free atoms do.  Timed under emdee_md_kernel_time index 10.
+ *   - A virtual site may carry any id: it is massless and carries no force after spreading, so it adds nothing to the sums; after
+ *     the scale the sites go back on their scaled parents.
+ *   - All or nothing, as emdee_md_set_rigid3: the previous table stays in force on refusal.  EMDEE_ERR_INVALID: n neither 0 nor
+ *     n_owned, NULL with n > 0, an id below -1, a rigid molecule or an hbonds cluster of the tables in force whose atoms do not
+ *     all carry one id >= 0 (the constraint would not be internal to a molecule; emdee_md_set_rigid3 and emdee_md_set_hbonds refuse
+ *     the same group the other way round).  EMDEE_ERR_STATE, from one device check and one read-back: a molecule whose total mass
+ *     is 0; a molecule that is not loaded whole -- for a constraint group inside it the unwrapped distance of two sites is off
+ *     the table's distance by more than 1e-3 (relative), the common mistake of wrapping a state atom by atom.  EMDEE_ERR_STATE
+ *     before emdee_md_set_state, with ghosts, on an integrator lent by emdee_dd_engine; and for clearing the table, or switching
+ *     emdee_md_set_molecular_scaling off, while a barostat is on and an hbonds table is in force.
+ *   - The table survives an emdee_md_set_state with the same atom count and is checked against the new state; after a state with
+ *     another count, or one that did not fit, emdee_md_step returns EMDEE_ERR_STATE until it is set again or cleared.
+ *   - Restraint references, the pull, the minimiser, the thermostats and the count of degrees of freedom do not read the table.
+ *     The Green-Kubo stress of a rigid-only engine takes whichever molecular sums are in force; an hbonds table keeps refusing
+ *     both Green-Kubo masks.  The radial distribution functions keep their own molecule argument.
+ * Scope: undivided orthorhombic boxes; no emdee_dd_* counterpart. */
 int32_t emdee_md_molecular_pressure_tensor(emdee_md *md, double out[12]);
 int32_t emdee_md_set_molecular_scaling(emdee_md *md, int32_t on);
+int32_t emdee_md_set_molecules(emdee_md *md, const int32_t *molecule_dev, int32_t n);
 int32_t emdee_md_nbr_stats(emdee_md *md, int64_t *builds, int64_t *listed, int32_t *max_count,
                            int32_t *capacity);
 int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
@@ -689,7 +732,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * (bin + sort + nbr_build), 3 = verlet_kick, 4 = lj_force_nbr with the velocity-Verlet update fused in
  * (emdee_md_step's inner steps, emdee_md_fused_step); 8 = the reciprocal-space pass of an Ewald engine (emdee_md_set_ewald, emdee_md_set_pme),
  * which index 0 contains as well; 9 = the constraint stages of an engine with rigid molecules (emdee_md_set_rigid3);
- * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling);
+ * 10 = its molecular sums and molecular scale (emdee_md_molecular_pressure_tensor, emdee_md_set_molecular_scaling), and those of a
+ * molecule table (emdee_md_set_molecules);
  * 11 = the constraint stages of an engine with an hbonds table (emdee_md_set_hbonds); 12 = what emdee_md_minimize adds to the
  * stages of its steps (the constrained force, the reduction, the mixing); 13 = placement and force spreading of an engine with
  * virtual sites (emdee_md_set_vsites); 14 = the three launches of every event of a global thermostat (emdee_md_set_thermostat);
