@@ -34,6 +34,7 @@
 #pragma once
 
 #include "kernels.hpp"
+#include "alchemical.hpp"
 
 namespace emdee {
 
@@ -1410,6 +1411,43 @@ __global__ __launch_bounds__(THREADS) void k_brick_filter(BrickArgs<real> a, con
         if (w < 0) continue;
         for (int e = w; e < m; e++) row[row_position<G>((unsigned)e)] = 0;   // the sentinel slot
         a.cnt[p] = w;
+    }
+}
+
+// The alchemical row pass on the brick list (alchemical.hpp, "the row pass"): FILL = false counts every owned atom's cross entries
+// into the scan array; FILL = true, after the scan, strikes them -- the row compacted in place and refilled with the sentinel as
+// k_brick_filter does, the slots to the CSR, the owner to its list.  The entries are decoded as there.
+template <typename real, class Shape, int THREADS, int G, bool FILL>
+__global__ __launch_bounds__(THREADS) void k_brick_alch(BrickArgs<real> a, const int *__restrict__ flag, int *__restrict__ scan,
+                                                        int *__restrict__ xs, AlchOwner *__restrict__ owners) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+    BrickTables<Shape, THREADS> T;
+    T.carve(s_dyn);
+    int bxi, byi, bzi, tile_n, n_own;
+    if (!brick_setup<real, Shape, THREADS>(a, T, bxi, byi, bzi, tile_n, n_own)) return;
+    auto slot = [&](unsigned short ent) {                // tile slot -> cell-order slot
+        const int sl = (int)ent >> a.idx_shift, tc = brick_block_of_slot(T, sl);
+        return T.gbeg[tc] + (sl - T.off[tc]);
+    };
+    for (int o = threadIdx.x; o < n_own; o += THREADS) {
+        int ti, p;
+        brick_locate(T, o, ti, p);
+        if (a.perm[p] >= a.n_owned) continue;
+        const int m = min(a.cnt[p], a.stride);
+        unsigned short *row = a.nbr + (size_t)p * a.stride;
+        const int fi = flag[a.perm[p]];
+        if (!FILL) {
+            const int c = alch_count_row(flag, a.perm, p, m, [&](int e) { return row[row_position<G>((unsigned)e)]; }, slot);
+            alch_put_count(scan, a.n, p, c, fi);
+        } else {
+            const int c = scan[p + 1] - scan[p];
+            if (c == 0) continue;
+            const int w = alch_strike_row(flag, a.perm, p, m, [&](int e) -> unsigned short & { return row[row_position<G>((unsigned)e)]; },
+                                          slot, xs + scan[p]);
+            for (int e = w; e < m; e++) row[row_position<G>((unsigned)e)] = 0;   // the sentinel slot
+            a.cnt[p] = w;
+            alch_put_owner(scan, a.n, p, c, fi, owners);
+        }
     }
 }
 

@@ -470,6 +470,19 @@ int32_t emdee_md_pull_read(emdee_md *md, double *coords_out, double *groups_out)
 int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->pull_log_read(log_dev, count, dropped); });
 }
+int32_t emdee_md_set_alchemical(emdee_md *md, const int32_t *flag_dev, double lambda, double alpha, const double *foreign, int32_t n_foreign,
+                                int32_t log_every, int32_t log_capacity) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_alchemical(flag_dev, lambda, alpha, foreign, n_foreign, log_every, log_capacity); });
+}
+int32_t emdee_md_set_lambda(emdee_md *md, double lambda) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_lambda(lambda); });
+}
+int32_t emdee_md_alchemical_read(emdee_md *md, double *words) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->alchemical_read(words); });
+}
+int32_t emdee_md_alchemical_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->alchemical_log_read(log_dev, count, dropped); });
+}
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->kernel_time(kernel, total_ms, launches); });
 }

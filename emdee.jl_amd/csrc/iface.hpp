@@ -68,6 +68,11 @@ struct IMd {
                           int32_t log_every, int32_t log_capacity) = 0;
     virtual void pull_read(double *coords_out, double *groups_out) = 0;
     virtual void pull_log_read(double *log_dev, int64_t *count, int64_t *dropped) = 0;
+    virtual void set_alchemical(const int32_t *flag, double lambda, double alpha, const double *foreign, int32_t n_foreign, int32_t log_every,
+                                int32_t log_capacity) = 0;
+    virtual void set_lambda(double lambda) = 0;
+    virtual void alchemical_read(double *words) = 0;
+    virtual void alchemical_log_read(double *log_dev, int64_t *count, int64_t *dropped) = 0;
     virtual void set_ewald(double alpha, const int32_t *kmax) = 0;
     virtual void set_pme(double alpha, const int32_t *grid, int32_t order) = 0;
     virtual void get_box(double lo[3], double len[3]) = 0;

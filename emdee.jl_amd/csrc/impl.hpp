@@ -211,7 +211,7 @@ struct MdImpl : IMd {
         }
         // (charges set for another atom count stay in force, unused: the engine refuses to step until they are set again or
         // cleared -- NbSystem::ensure_charges)
-        if (!defer_forces && !sys.charges_stale() && !restraints_unfit() && !pull_unfit()) {
+        if (!defer_forces && !sys.charges_stale() && !restraints_unfit() && !pull_unfit() && !alch_unfit()) {
             force_pass(EMDEE_FORCES);
             current_mask = EMDEE_FORCES;
         }
@@ -222,13 +222,16 @@ struct MdImpl : IMd {
     bool restraints_unfit() const { return !lent && sys.has_restraints() && (sys.stale(sys.tables->restraints) || n_ghost != 0); }
     // the same for the pull table (emdee_md_set_pull)
     bool pull_unfit() const { return !lent && sys.has_pull() && (sys.stale(sys.tables->pull) || n_ghost != 0); }
+    // the same for the alchemical table (emdee_md_set_alchemical)
+    bool alch_unfit() const { return !lent && sys.has_alch() && (sys.stale(sys.tables->alch) || n_ghost != 0); }
     // emdee_dd_step: the rebuild in the middle of a run is followed by a fused step, which evaluates the forces itself
     bool defer_forces = false;
     // The attached tables: one per constraint group (NbSystem::groups, same index), then the table of virtual sites
-    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints), then the pull table (emdee_md_set_pull), then the molecule table (emdee_md_set_molecules).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
+    // (emdee_md_set_vsites), then the table of position restraints (emdee_md_set_restraints), then the pull table (emdee_md_set_pull), then the molecule table (emdee_md_set_molecules), then the alchemical table (emdee_md_set_alchemical).  Only the state of a table is shared -- present, the atom count it was set for, stale, unchecked, the
     // texts; what is done with one stays per kind.
-    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, PULL, MOLECULES, TABLES };
+    enum { VSITES = NbSystem<real>::GROUPS, RESTRAINTS, PULL, MOLECULES, ALCHEMICAL, TABLES };
     const Topology::GroupTable &attached(int k) const {
+        if (k == ALCHEMICAL) return sys.tables->alch;
         if (k == MOLECULES) return sys.tables->molecules;
         if (k == PULL) return sys.tables->pull;
         if (k == RESTRAINTS) return sys.tables->restraints;
@@ -241,9 +244,10 @@ struct MdImpl : IMd {
                                                      {"a virtual site", "virtual sites", "emdee_md_set_vsites"},
                                                      {"a position restraint", "position restraints", "emdee_md_set_restraints"},
                                                      {"a pull group", "pull groups", "emdee_md_set_pull"},
-                                                     {"a molecule", "molecules of the molecule table", "emdee_md_set_molecules"}};
+                                                     {"a molecule", "molecules of the molecule table", "emdee_md_set_molecules"},
+                                                     {"a flagged atom", "the flags of the alchemical table", "emdee_md_set_alchemical"}};
     // table k has not passed the check against the loaded state (another atom count, ghosts, or a refusal)
-    bool unchecked[TABLES] = {false, false, false, false, false, false};
+    bool unchecked[TABLES] = {false, false, false, false, false, false, false};
     // the conditions emdee_md_step refuses table k on
     void require_fitting(const char *what, int k) const {
         const Topology::GroupTable &t = attached(k);
@@ -263,6 +267,13 @@ struct MdImpl : IMd {
             if (k < VSITES)
                 EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "%s: %s had no solution; replace the table or the state", what, GROUP_TEXT[k].one);
             require_fitting(what, k);
+        }
+        // (a Coulomb soft core is not built: on a charged engine the solute's charges are scaled to zero first)
+        if (!lent && sys.has_alch() && sys.has_charges()) {
+            const int64_t i = alch_first_charged(sys.tables->alch.atoms_h, sys.tables->q_h);
+            EMDEE_REQUIRE(i < 0, EMDEE_ERR_STATE, "%s: atom %lld is flagged by the alchemical table (emdee_md_set_alchemical) and carries a charge: "
+                          "the soft core covers the Lennard-Jones coupling only; set the solute's charges to zero (emdee_md_set_coulomb) first", what,
+                          (long long)i);
         }
     }
     bool sites_in_use() const { return !lent && n_ghost == 0 && sys.vsites_fit() && !unchecked[VSITES]; }
@@ -291,6 +302,7 @@ struct MdImpl : IMd {
                       (long long)sys.tables->q_n, sys.n_owned);
         if (frc || en || vir) require_fitting("md_get_state (forces, energies or virials)", RESTRAINTS);
         if (frc || en || vir) require_fitting("md_get_state (forces, energies or virials)", PULL);
+        if (frc || en || vir) require_fitting("md_get_state (forces, energies or virials)", ALCHEMICAL);
         if ((en || vir) && (current_mask & 6) != 6) forces(7, 0);
         sys.ids_map();                                       // (scratch of the engine's own: before the fence)
         FenceOut fence(caller_ctx, sys.stream());
@@ -304,8 +316,9 @@ struct MdImpl : IMd {
         EMDEE_REQUIRE(nsteps >= 0 && dt >= 0, EMDEE_ERR_INVALID, "md_step: negative nsteps or dt");
         require_ready("md_step");
         if (nsteps == 0) return;
-        // (a restraint or pull table: closed steps as well, so that the state after s steps does not depend on how they were dealt to calls)
-        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || sys.has_restraints() || sys.has_pull() || baro.kind != EMDEE_BAROSTAT_OFF ||
+        // (a restraint, pull or alchemical table: closed steps as well, so that the state after s steps does not depend on how they were dealt to calls)
+        if (sys.has_rigid() || sys.has_hbonds() || sys.has_vsites() || sys.has_restraints() || sys.has_pull() || sys.has_alch() ||
+            baro.kind != EMDEE_BAROSTAT_OFF ||
             thermo.kind != EMDEE_THERMOSTAT_OFF) {
             step_closed(nsteps, dt, rebuild_every);
             return;
@@ -403,6 +416,7 @@ struct MdImpl : IMd {
         require_fitting("scale_box", VSITES);
         require_fitting("scale_box", RESTRAINTS);
         require_fitting("scale_box", PULL);                  // (xi0 and r0 do not scale with the box)
+        require_fitting("scale_box", ALCHEMICAL);
         if (molecular) require_fitting("scale_box", MOLECULES);
         sys.scale_box(mu, vscale, by_molecules());           // (validates before it writes; sites go back on their scaled parents)
         since_build = 0;
@@ -509,6 +523,7 @@ struct MdImpl : IMd {
         for (int s = 0; s < nsteps; s++) {
             const bool event = coupled && (baro.step + 1) % (unsigned long long)baro.every == 0;
             if (sys.has_pull()) sys.own_tables.pull.advance(dt);   // (xi0 <- xi0 + rate dt on the host; the step's force pass closes it: work, log)
+            if (sys.has_alch()) sys.own_tables.alch.advance();     // (the step's force pass writes the log entry that is due)
             closed_step(dt, (event && with_sums) ? 7 : EMDEE_FORCES, rebuild_every);
             if (thermostatted && ++thermo.step % (unsigned long long)thermo.every == 0) thermostat_event(dt, n_dof);
             if (coupled) baro.step++;
@@ -749,6 +764,7 @@ struct MdImpl : IMd {
             {sys.has_vsites(), "virtual sites (emdee_md_set_vsites)"},
             {sys.has_restraints(), "position restraints (emdee_md_set_restraints)"},
             {sys.has_pull(), "a centre-of-mass pull (emdee_md_set_pull)"},
+            {sys.has_alch(), "an alchemical table (emdee_md_set_alchemical)"},
             {pme, "particle-mesh Ewald (emdee_md_set_pme)"},
             {sys.has_ewald() && !pme, "Ewald summation (emdee_md_set_ewald)"}};
         std::string all;                                     // (every table in the way, so that one refusal says what to clear)
@@ -1050,13 +1066,14 @@ struct MdImpl : IMd {
         // of the displacement and velocity correlations (emdee_md_msd_sample); 17: the launches every sample of the Green-Kubo
         // observables adds to the tensor pass (emdee_md_gk_sample); 18: the launch the position restraints add to every force pass, and
         // the scaling of their references (emdee_md_set_restraints); 19: the three launches the centre-of-mass pull adds to every force
-        // pass (emdee_md_set_pull)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 19, EMDEE_ERR_INVALID, "kernel id out of range");
+        // pass (emdee_md_set_pull); 20: the row pass of the alchemical table at every rebuild and its launches behind every force pass
+        // (emdee_md_set_alchemical)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 20, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[20][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[21][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
                                 {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}, {T_GK, -1},
-                                {T_RESTRAINTS, -1}, {T_PULL, -1}};
+                                {T_RESTRAINTS, -1}, {T_PULL, -1}, {T_ALCHEMICAL, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {
@@ -1205,7 +1222,7 @@ struct MdImpl : IMd {
             sys.own_tables.set_pull(group, n_groups, coords, params, n_coords, log_every, log_capacity, sys.n_owned, sys.stream());
             unchecked[PULL] = false;
         }, false);
-        if (sys.charges_stale() || restraints_unfit()) { current_mask = 0; return; }
+        if (sys.charges_stale() || restraints_unfit() || alch_unfit()) { current_mask = 0; return; }
         force_pass(EMDEE_FORCES);
         current_mask = EMDEE_FORCES;
         EMDEE_HIP_CHECK(hipGetLastError());
@@ -1230,6 +1247,56 @@ struct MdImpl : IMd {
         if (!log_dev || t.log_count == 0) return;
         FenceOut fence(caller_ctx, sys.stream());
         EMDEE_HIP_CHECK(hipMemcpyAsync(log_dev, t.log.ptr, (size_t)2 * t.log_count * t.n * sizeof(double), hipMemcpyDeviceToDevice, sys.stream()));
+    }
+    // emdee_md_set_alchemical: all or nothing -- the flags are fetched and every check is made on the host (alchemical.hpp) before
+    // anything in force changes, then the table is installed whole.  The rows depend on the table (the cross entries leave them, or
+    // come back at a clear): the list is rebuilt and the forces are evaluated again, as after emdee_md_set_exclusions.
+    void set_alchemical(const int32_t *flag, double lambda, double alpha, const double *foreign, int32_t n_foreign, int32_t log_every,
+                        int32_t log_capacity) override {
+        install("the alchemical table (emdee_md_set_alchemical)", "a decomposed run has none", [&] {
+            EMDEE_REQUIRE(!sys.charges_stale() && !restraints_unfit() && !pull_unfit(), EMDEE_ERR_STATE, "set_alchemical: another table of the engine "
+                          "(charges, restraints or pull) was set for another atom count: set it again or clear it first");
+            sys.own_tables.set_alchemical(flag, lambda, alpha, foreign, n_foreign, log_every, log_capacity, sys.n_owned, sys.stream());
+            unchecked[ALCHEMICAL] = false;
+        });
+    }
+    // a host scalar, handed to the kernels as an argument: no rebuild; the next step or query evaluates the forces anew
+    void set_lambda(double lambda) override {
+        use_device(sys.ctx);
+        Topology::AlchTable &t = sys.own_tables.alch;
+        EMDEE_REQUIRE(!lent && t.present, EMDEE_ERR_STATE, "set_lambda: no alchemical table is set (emdee_md_set_alchemical)");
+        alch_check_lambda("set_lambda", lambda);
+        t.lambda = lambda;
+        current_mask = 0;
+    }
+    // lambda, U_alch, dU/dlambda, the cross virial and the cross pairs inside rc of the current positions (a force pass if lambda or
+    // the state changed since the last), then U_alch at the foreign lambdas (the energies-only launch); blocking, one copy
+    void alchemical_read(double *words) override {
+        use_device(sys.ctx);
+        Topology::AlchTable &t = sys.own_tables.alch;
+        EMDEE_REQUIRE(!lent && t.present, EMDEE_ERR_STATE, "alchemical_read: no alchemical table is set (emdee_md_set_alchemical)");
+        EMDEE_REQUIRE(words, EMDEE_ERR_INVALID, "alchemical_read: words is NULL");
+        require_fitting("alchemical_read", ALCHEMICAL);
+        EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "alchemical_read: the state has ghosts");
+        if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
+        {
+            typename NbSystem<real>::Timed timed(&sys, T_ALCHEMICAL);
+            sys.queue_alch_foreign();
+        }
+        double h[ALCH_WORDS + ALCH_MAX_FOREIGN];
+        sys.read_back_doubles(h, t.out.ptr, ALCH_WORDS + ALCH_MAX_FOREIGN);
+        for (int q = 0; q < ALCH_WORDS + t.n_foreign; q++) words[q] = h[q];
+    }
+    void alchemical_log_read(double *log_dev, int64_t *count, int64_t *dropped) override {
+        use_device(sys.ctx);
+        Topology::AlchTable &t = sys.own_tables.alch;
+        EMDEE_REQUIRE(!lent && t.present, EMDEE_ERR_STATE, "alchemical_log_read: no alchemical table is set (emdee_md_set_alchemical)");
+        if (count) *count = t.log_count;
+        if (dropped) *dropped = t.log_dropped;
+        if (!log_dev || t.log_count == 0) return;
+        FenceOut fence(caller_ctx, sys.stream());
+        EMDEE_HIP_CHECK(hipMemcpyAsync(log_dev, t.log.ptr, (size_t)t.log_count * (2 + t.n_foreign) * sizeof(double), hipMemcpyDeviceToDevice,
+                                       sys.stream()));
     }
     // emdee_md_set_ewald, emdee_md_set_pme: all or nothing -- every refusal comes before the setting changes.  check(): the host
     // test of the setting; set(): EwaldRecip's setter (the mesh takes the place of the direct sum)

@@ -55,9 +55,10 @@ static inline void refuse_experiment_switches() {
 // T_GK: the launches a sample of the Green-Kubo observables adds to the tensor pass (gk.hpp): the box sums, the heat sums, push, correlate
 // T_RESTRAINTS: the launch the position restraints add to every force pass, and the scaling of their references (restraint.hpp)
 // T_PULL: the three launches the centre-of-mass pull adds to every force pass (pull.hpp): partial sums, finish, apply
+// T_ALCHEMICAL: the row pass of the alchemical table at a rebuild and its launches behind a force pass (alchemical.hpp)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
                T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_GK = 16, T_RESTRAINTS = 17,
-               T_PULL = 18, T_COUNT = 19 };
+               T_PULL = 18, T_ALCHEMICAL = 19, T_COUNT = 20 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -241,7 +242,8 @@ struct NbSystem {
     // users), and behind them the totals in fixed slots, so that totals which one launch or one copy reads together never alias.
     // The energy sums lie right behind FIRE's six words (fire_sums: one copy of seven), the molecules' tensor sums right behind the
     // atomic ones (molecular_tensor_sums: one copy of twenty-four; k_gk_push reads those and the heat sums in one launch).
-    enum RedSlot { RED_FIRE = 0, RED_ENERGY = 6, RED_TENSOR = 9, RED_MOLECULE = 21, RED_HEAT = 33, RED_RESTRAINT = 36, RED_TOTALS = 44 };
+    enum RedSlot { RED_FIRE = 0, RED_ENERGY = 6, RED_TENSOR = 9, RED_MOLECULE = 21, RED_HEAT = 33, RED_RESTRAINT = 36, RED_ALCH = 44,
+                   RED_ALCH_FOREIGN = 48, RED_TOTALS = 64 };
     DevBuf<double> red;
     double *red_partials() {
         red.ensure((size_t)RED_MAX_WORDS * RED_MAX_BLOCKS + RED_TOTALS);
@@ -769,7 +771,7 @@ struct NbSystem {
         f.rlist = rlist;
         f.n = n_total; f.n_plan = edit_n_plan; f.in_edit = in_edit;
         f.nt = nt; f.nsub = nsub;
-        f.uniform = uniform_atoms; f.charged = has_charges(); f.ewald = has_ewald(); f.filters_rows = filters_rows();
+        f.uniform = uniform_atoms; f.charged = has_charges(); f.ewald = has_ewald(); f.filters_rows = filters_rows() || has_alch();
         f.brick_path = path == PATH_BRICK;
         f.stride = stride; f.typed_stride = typed_stride;
         f.field16_blocked = blocked.field16; f.typed_blocked = blocked.typed;
@@ -924,6 +926,7 @@ struct NbSystem {
                 builds++;
                 has_list = true;
                 apply_exclusions();
+                apply_alchemical();
                 return;
             }
             // grow and rebuild (after_build): rows longer than the typed build's LDS row buffers can take send this state on
@@ -957,7 +960,7 @@ struct NbSystem {
     bool has_bonded() const { return tables->has_bonded; }
     // terms added behind a whole force pass (add_post_terms): such a box steps in the split form (force pass, these terms,
     // kick + drift), not the fused one
-    bool has_post() const { return has_14() || has_bonded() || has_charges() || has_restraints() || has_pull(); }
+    bool has_post() const { return has_14() || has_bonded() || has_charges() || has_restraints() || has_pull() || has_alch(); }
     // rows the filter visits right after every build: excluded pairs are struck, 1-4 and bonded partners' slots recorded
     bool filters_rows() const { return has_excl() || has_bonded(); }
     // a bonded term whose partner was missing from the rows (raised by k_bonded): the engine refuses to step until the tables or
@@ -1413,12 +1416,134 @@ struct NbSystem {
         });
     }
 
+    // ---------------------------------------------------------------- soft-core alchemical decoupling (Topology::set_alchemical; alchemical.hpp)
+    // Right after every build (and after the exclusion filter, so that an excluded cross pair stays excluded and is never recorded)
+    // the row pass strikes the cross entries of every owned atom's row: count, one exclusive scan (the sort's Scanner), one read-back
+    // of the three totals, fill.  Behind every force pass one launch over the owners the pass listed, then the two stages of the sums
+    // and the launch that leaves the words of a read on the device.  The foreign energies are queued at log events and by the read
+    // only.  Undivided engines only; launched only with a table in force.
+    DevBuf<int> alch_scan, alch_xs;                          // the scan array of the row pass; the CSR of struck slots
+    DevBuf<AlchOwner> alch_owners;
+    DevBuf<double> alch_part, alch_part_f;                   // per owner ALCH_SUMS words; per solute owner ALCH_MAX_FOREIGN energies
+    int alch_n_struck = 0, alch_n_sol = 0, alch_n_env = 0;   // of the list in use
+    bool has_alch() const { return tables->alch.present; }
+    void require_alch_fit(const char *what) const {
+        const Topology::AlchTable &t = tables->alch;
+        EMDEE_REQUIRE(!stale(t) && !has_ghosts && tables == &own_tables, EMDEE_ERR_STATE, "%s: the alchemical table was set for %lld atoms, the "
+                      "state holds %d (or has ghosts): set it again or clear it (emdee_md_set_alchemical)", what, (long long)t.limit, n_owned);
+    }
+    void apply_alchemical() {
+        alch_n_struck = alch_n_sol = alch_n_env = 0;
+        if (!has_alch() || n_total == 0) return;
+        if (stale(tables->alch) || has_ghosts || tables != &own_tables) return;   // (unfit: the force pass refuses; the rows stay whole)
+        const Topology::AlchTable &t = own_tables.alch;
+        Timed timed(this, T_ALCHEMICAL);
+        const size_t n = (size_t)n_total;
+        alch_scan.ensure(3 * n + 4);
+        EMDEE_HIP_CHECK(hipMemsetAsync(alch_scan.ptr, 0, (3 * n + 4) * sizeof(int), stream()));
+        auto rows = [&](auto fill) {
+            constexpr bool FILL = decltype(fill)::value;
+            if (brick_active) {
+                EMDEE_REQUIRE(!plan.typed, EMDEE_ERR_STATE, "alchemical table: typed rows are not filtered");
+                with_brick_variant(plan.variant, [&](auto v) {
+                    using V = decltype(v);
+                    auto kernel = k_brick_alch<real, typename V::Shape, V::THREADS, V::G, FILL>;
+                    using BT = BrickTables<typename V::Shape, V::THREADS>;
+                    hipLaunchKernelGGL(kernel, dim3(plan.grid.per_xcd * NXCD), dim3(V::THREADS), BT::bytes(0), stream(), brick_args(),
+                                       (const int *)t.flag.ptr, alch_scan.ptr, alch_xs.ptr, alch_owners.ptr);
+                });
+            } else if constexpr (FILL) {
+                hipLaunchKernelGGL(k_alch_strike_rows, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, perm.ptr, nbr.ptr,
+                                   stride, cnt.ptr, (const int *)t.flag.ptr, (const int *)alch_scan.ptr, alch_xs.ptr, alch_owners.ptr);
+            } else {
+                hipLaunchKernelGGL(k_alch_count_rows, dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), n_total, n_owned, perm.ptr,
+                                   (const int *)nbr.ptr, stride, (const int *)cnt.ptr, (const int *)t.flag.ptr, alch_scan.ptr);
+            }
+        };
+        rows(std::false_type{});
+        scanner.run(alch_scan.ptr, 3 * n + 1, stream());
+        hipLaunchKernelGGL(k_alch_totals, dim3(1), dim3(64), 0, stream(), alch_scan.ptr, n_total);
+        int32_t tot[3] = {0, 0, 0};
+        read_back_words(ctx, stream(), alch_scan.ptr + 3 * n + 1, 3, tot);
+        alch_n_struck = tot[0]; alch_n_sol = tot[1]; alch_n_env = tot[2];
+        if (alch_n_struck == 0) return;
+        alch_xs.ensure((size_t)alch_n_struck + 1);
+        alch_owners.ensure((size_t)alch_n_sol + alch_n_env + 1);
+        alch_part.ensure((size_t)ALCH_SUMS * ((size_t)alch_n_sol + alch_n_env) + 1);
+        alch_part_f.ensure((size_t)ALCH_MAX_FOREIGN * alch_n_sol + 1);
+        rows(std::true_type{});
+    }
+    // the two stages of one of the table's sums over n owners into `slot` (stage 1 under the family's own name)
+    template <class Term>
+    double *queue_alch_sums(int n, const Term &term, int slot) {
+        const int nb = red_blocks(n);
+        hipLaunchKernelGGL((k_alch_partials<Term>), dim3(nb), dim3(RED_BLOCK), 0, stream(), n, term, red_partials());
+        return queue_final<Term>(nb, slot);
+    }
+    AlchArgs<real> alch_args() const {
+        const Topology::AlchTable &t = own_tables.alch;
+        AlchArgs<real> a{};
+        a.n_sol = alch_n_sol; a.n_env = alch_n_env;
+        a.owners = alch_owners.ptr; a.xs = alch_xs.ptr; a.pitch = pitch;
+        a.lambda = (real)t.lambda; a.alpha = (real)t.alpha;
+        a.sw = AlchModel<real>{model.idl2, model.x0, model.c60};
+        a.rc2 = model.rc2;
+        return a;
+    }
+    // U_alch at the table's foreign lambdas at the current positions, into out[ALCH_WORDS ...): the energies-only instance over the
+    // solute owners and the sums, eight words at a time
+    void queue_alch_foreign() {
+        Topology::AlchTable &t = own_tables.alch;
+        if (t.n_foreign == 0) return;
+        double *dst = t.out.ptr + ALCH_WORDS;
+        if (alch_n_sol == 0) {
+            EMDEE_HIP_CHECK(hipMemsetAsync(dst, 0, ALCH_MAX_FOREIGN * sizeof(double), stream()));
+            return;
+        }
+        AlchForeign<real> f{};
+        f.K = t.n_foreign;
+        for (int k = 0; k < ALCH_MAX_FOREIGN; k++) f.lambda[k] = (real)t.foreign[k];
+        hipLaunchKernelGGL((k_alchemical_foreign<real>), dim3(alch_sol_blocks(alch_n_sol)), dim3(ALCH_BLOCK), 0, stream(), alch_args(), view(), grid,
+                           f, alch_part_f.ptr);
+        for (int first = 0; first < t.n_foreign; first += 8) {
+            const double *tot = queue_alch_sums(alch_n_sol, AlchForeignSums{alch_part_f.ptr, first}, RED_ALCH_FOREIGN + first);
+            EMDEE_HIP_CHECK(hipMemcpyAsync(dst + first, tot, 8 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+        }
+    }
+    void add_alchemical(const Pass<real> &p) {
+        if (!has_alch() || n_total == 0) return;
+        require_alch_fit("force pass");
+        EMDEE_REQUIRE(!p.to_caller(), EMDEE_ERR_STATE, "the alchemical table (emdee_md_set_alchemical) is not on the operator path");
+        Topology::AlchTable &t = own_tables.alch;
+        const int slot = t.log_slot;
+        t.log_slot = -1;
+        Timed timed(this, T_ALCHEMICAL);
+        const int owners = alch_n_sol + alch_n_env;
+        if (owners == 0) {
+            hipLaunchKernelGGL(k_alch_zero_words, dim3(1), dim3(64), 0, stream(), t.lambda, t.out.ptr, ALCH_WORDS);
+        } else {
+            const AlchArgs<real> a = alch_args();
+            with_bool(p.mask & EMDEE_TENSOR, [&](auto tensor) {
+                hipLaunchKernelGGL((k_alchemical<real, decltype(tensor)::value>), dim3(alch_sol_blocks(a.n_sol) + alch_env_blocks(a.n_env)),
+                                   dim3(ALCH_BLOCK), 0, stream(), a, view(), grid, p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr, alch_part.ptr);
+            });
+            const double *tot = queue_alch_sums(owners, AlchSums{alch_part.ptr}, RED_ALCH);
+            hipLaunchKernelGGL(k_alch_finish, dim3(1), dim3(64), 0, stream(), t.lambda, tot, t.out.ptr);
+        }
+        if (slot >= 0) {
+            queue_alch_foreign();
+            hipLaunchKernelGGL(k_alch_log, dim3(1), dim3(64), 0, stream(), (const double *)t.out.ptr, t.n_foreign,
+                               t.log.ptr + (size_t)slot * (2 + t.n_foreign));
+        }
+    }
+
     void add_post_terms(const Pass<real> &p) {
         add_pairs14(p);
         add_bonded(p);
         add_ewald(p);
         add_restraints(p);
         add_pull(p);
+        add_alchemical(p);
     }
 
     // ---------------------------------------------------------------- forces

@@ -3,6 +3,7 @@
 
 #include <cstddef>
 
+#include "alchemical.hpp"
 #include "common.hpp"
 #include "topology.hpp"
 
@@ -374,7 +375,7 @@ struct Topology {
     void set_charges(const double *charges_dev, int64_t n, double K, double eps, double s14, int64_t want, hipStream_t s) {
         EMDEE_REQUIRE(n >= 0 && (n == 0 || charges_dev), EMDEE_ERR_INVALID, "set_coulomb: negative count or NULL array");
         if (n == 0) {                                        // (clearing needs no constants)
-            has_charges = false; q_n = 0;
+            has_charges = false; q_n = 0; q_h.clear();
             return;
         }
         topo::check_coulomb(n, want, K, eps, s14);
@@ -388,7 +389,59 @@ struct Topology {
         // ---- commit
         q_tab.swap(nq);
         q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14; q_sum = sum; q_abs = sum_abs;
+        q_h.swap(h);
         has_charges = true;
+    }
+    std::vector<double> q_h;                                 // the host copy (the alchemical table's readiness check: a flagged atom carries charge 0)
+
+    // ---- soft-core alchemical decoupling (emdee_md_set_alchemical; alchemical.hpp), undivided engines only: the flag of every caller
+    // id on the device (GroupTable: atoms_h the flagged ids, n their count), the words of a read and the log.  The host owns lambda,
+    // alpha, the foreign lambdas, the count of completed steps and the log's bookkeeping; the struck entries of a build are the
+    // engine's (NbSystem::alch_*).
+    struct AlchTable : GroupTable {
+        DevBuf<int> flag;
+        DevBuf<double> out, log;                             // out: ALCH_WORDS, then the foreign energies; log: capacity x (2 + n_foreign)
+        double lambda = 1.0, alpha = 0.0, foreign[ALCH_MAX_FOREIGN] = {};
+        int n_foreign = 0;
+        int log_every = 0, log_capacity = 0;
+        long long steps = 0, log_count = 0, log_dropped = 0; // completed steps since the set; entries written; samples dropped
+        int log_slot = -1;                                   // the entry the next force pass writes (set by advance(), taken by NbSystem::add_alchemical)
+        void advance() {
+            steps++;
+            log_slot = -1;
+            if (log_capacity > 0 && log_every > 0 && steps % log_every == 0) {
+                if (log_count < log_capacity) log_slot = (int)log_count++; else log_dropped++;
+            }
+        }
+    };
+    AlchTable alch;
+    // Replaces the table by the one the arrays describe (flag_dev: device, `lim` ints; foreign: host); flag_dev = NULL clears it.  Every
+    // refusal comes before the table in force changes.
+    void set_alchemical(const int32_t *flag_dev, double lambda, double alpha, const double *foreign, int32_t n_foreign, int32_t log_every,
+                        int32_t log_capacity, int64_t lim, hipStream_t s) {
+        if (!flag_dev) {
+            alch.present = false; alch.n = 0; alch.atoms_h.clear();
+            return;
+        }
+        alch_check_params(lambda, alpha, foreign, n_foreign, log_every, log_capacity);
+        const std::vector<int32_t> raw = fetch(flag_dev, (size_t)lim, s);
+        const std::vector<int32_t> ids = alch_check_flags(raw);
+        AlchTable t;
+        put(t.flag, raw, s);
+        const size_t words = (size_t)ALCH_WORDS + ALCH_MAX_FOREIGN, log_words = (size_t)log_capacity * (2 + n_foreign) + 1;
+        t.out.ensure(words);
+        t.log.ensure(log_words);
+        EMDEE_HIP_CHECK(hipMemsetAsync(t.out.ptr, 0, words * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipMemsetAsync(t.log.ptr, 0, log_words * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        alch.flag.swap(t.flag); alch.out.swap(t.out); alch.log.swap(t.log);
+        alch.atoms_h = ids;
+        alch.lambda = lambda; alch.alpha = alpha; alch.n_foreign = n_foreign;
+        for (int k = 0; k < ALCH_MAX_FOREIGN; k++) alch.foreign[k] = k < n_foreign ? foreign[k] : 0.0;
+        alch.log_every = log_every; alch.log_capacity = log_capacity;
+        alch.steps = 0; alch.log_count = 0; alch.log_dropped = 0; alch.log_slot = -1;
+        alch.n = (int)ids.size(); alch.limit = lim; alch.present = true;
     }
 };
 

@@ -8,6 +8,7 @@ export set_msd!, msd_sample!, msd_reset!, msd_read
 export set_gk!, gk_sample!, gk_reset!, gk_read
 export set_restraints!, restraint_sums, restraint_refs!
 export set_pull!, pull_read, pull_log_read!
+export set_alchemical!, set_lambda!, alchemical_read, alchemical_log_read!
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -165,6 +166,38 @@ end
 function pull_log_read!(md::VelocityVerlet, out::HipArray{Float64,3})
     count, dropped = Ref{Int64}(0), Ref{Int64}(0)
     check(ccall((:emdee_md_pull_log_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), md.handle, out.ptr, count, dropped))
+    return count[], dropped[]
+end
+
+# int32_t emdee_md_set_alchemical(emdee_md *md, const int32_t *flag_dev, double lambda, double alpha, const double *foreign,
+#                                 int32_t n_foreign, int32_t log_every, int32_t log_capacity);
+# Soft-core alchemical decoupling: flag a device Int32 vector of n_owned entries (1 solute, 0 environment); the Lennard-Jones coupling
+# between flagged and unflagged atoms becomes lambda 4 eps (D^-2 - D^-1) g with D = alpha (1 - lambda) + (r / sigma)^6.  foreign: HOST
+# Float64 vector of up to 16 more lambdas for BAR / MBAR.  Rebuilds the list and evaluates the forces again; flag = `nothing` clears.
+function set_alchemical!(md::VelocityVerlet, flag::Union{Nothing,HipArray{Int32,1}}; lambda::Real=1.0, alpha::Real=0.5,
+                         foreign::Vector{Float64}=Float64[], log_every::Integer=0, log_capacity::Integer=0)
+    check(ccall((:emdee_md_set_alchemical, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Int32, Int32, Int32), md.handle,
+                flag === nothing ? C_NULL : flag.ptr, lambda, alpha, isempty(foreign) ? C_NULL : foreign, length(foreign), log_every, log_capacity))
+end
+
+# int32_t emdee_md_set_lambda(emdee_md *md, double lambda);
+# (a host scalar: no rebuild; the next step or query evaluates the forces anew)
+set_lambda!(md::VelocityVerlet, lambda::Real) =
+    check(ccall((:emdee_md_set_lambda, libemdee_hip), Int32, (Ptr{Cvoid}, Float64), md.handle, lambda))
+
+# int32_t emdee_md_alchemical_read(emdee_md *md, double *words);
+# (blocking) {lambda, U_alch, dU/dlambda, the cross virial, the cross pairs inside rc}, then U_alch at the n_foreign foreign lambdas
+function alchemical_read(md::VelocityVerlet, n_foreign::Integer)
+    w = zeros(Float64, 5 + n_foreign)
+    check(ccall((:emdee_md_alchemical_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, w))
+    return w
+end
+
+# int32_t emdee_md_alchemical_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
+# The log so far into a device Float64 array (2 + n_foreign, capacity) of {dU/dlambda, U_alch, foreign ...}; returns (count, dropped).
+function alchemical_log_read!(md::VelocityVerlet, out::HipArray{Float64,2})
+    count, dropped = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:emdee_md_alchemical_log_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), md.handle, out.ptr, count, dropped))
     return count[], dropped[]
 end
 

@@ -36,6 +36,7 @@ RESTRAINT_WORDS = 8                                        # (EMDEE_RESTRAINT_WO
 PULL_WORDS, PULL_UMBRELLA, PULL_CONSTANT_FORCE, PULL_DISTANCE, PULL_DIRECTION = 8, 1, 2, 1, 2
 _PULL_KINDS = {"umbrella": PULL_UMBRELLA, "constant-force": PULL_CONSTANT_FORCE, "constant_force": PULL_CONSTANT_FORCE}
 _PULL_GEOMETRIES = {"distance": PULL_DISTANCE, "direction": PULL_DIRECTION}
+ALCH_WORDS, ALCH_MAX_FOREIGN = 5, 16                       # (EMDEE_ALCH_WORDS, EMDEE_ALCH_MAX_FOREIGN: emdee_md_set_alchemical)
 
 
 def _three(v):
@@ -94,7 +95,9 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the launch the position restraints add to every force pass, and the scaling of their references (set_restraints_)
            "restraints": 18,
            # the three launches the centre-of-mass pull adds to every force pass (set_pull_): partial sums, finish, apply
-           "pull": 19}
+           "pull": 19,
+           # the row pass of the alchemical table at every rebuild and its launches behind every force pass (set_alchemical_)
+           "alchemical": 20}
 
 
 class MinimizeResult:
@@ -791,6 +794,57 @@ class VelocityVerlet:
         _lib.call("emdee_md_pull_log_read", self._handle, C.c_void_p(buf.data_ptr()), C.byref(count), C.byref(dropped))
         h = buf[:count.value].cpu().numpy()
         return dict(xi=h[:, :, 0].copy(), f=h[:, :, 1].copy(), count=int(count.value), dropped=int(dropped.value))
+
+    # -- soft-core alchemical decoupling (include/emdee_hip.h: emdee_md_set_alchemical; undivided engines)
+    _alch = None                                           # (n_foreign, log_capacity) of the table in force
+
+    def set_alchemical_(self, flag, lam=1.0, alpha=0.5, foreign=(), log_every=0, log_capacity=0):
+        """Decouples the Lennard-Jones interaction between the flagged atoms (the solute) and all others along lam through a soft
+        core (include/emdee_hip.h emdee_md_set_alchemical): U = lam 4 eps (D^-2 - D^-1) g with D = alpha (1 - lam) + (r / sigma)^6.
+        flag: one integer per owned atom, 1 for the solute, 0 for the environment.  foreign: up to 16 more lambdas at which U_alch is
+        evaluated for BAR / MBAR (by alchemical() and at log events).  log_every, log_capacity: the on-device log of (dU/dlam,
+        U_alch, foreign energies), one entry every log_every completed steps (capacity 0: none).  Rebuilds the list and evaluates
+        the forces again.  flag = None clears the table."""
+        import numpy as np
+        if flag is None:
+            _lib.call("emdee_md_set_alchemical", self._handle, None, 1.0, 0.0, None, 0, 0, 0)
+            self._alch = None
+            return
+        (f,), _ = self._per_atom_i32("set_alchemical_", 1, flag=flag)
+        fl = np.ascontiguousarray(np.asarray(foreign, dtype=np.float64).reshape(-1))
+        _lib.call("emdee_md_set_alchemical", self._handle, C.c_void_p(f.data_ptr()), float(lam), float(alpha),
+                  fl.ctypes.data_as(C.c_void_p) if fl.size else None, int(fl.size), int(log_every), int(log_capacity))
+        self._alch = (int(fl.size), int(log_capacity))
+
+    def set_lambda_(self, lam):
+        """Moves lambda (a host scalar: no rebuild); the next step_ or query evaluates the forces anew.  For slow growth and lambda
+        schedules."""
+        _lib.call("emdee_md_set_lambda", self._handle, float(lam))
+
+    set_alchemical, set_lambda = set_alchemical_, set_lambda_
+
+    def alchemical(self):
+        """The alchemical words of the current positions (blocking), as a dict: lam, U (U_alch), dUdl, virial (the cross pairs' scalar
+        virial), pairs (the cross pairs inside the cutoff, an int) and foreign, float64 numpy (n_foreign,) of U_alch at the foreign
+        lambdas."""
+        import numpy as np
+        if self._alch is None:
+            raise RuntimeError("alchemical: no alchemical table is set (set_alchemical_)")
+        w = np.zeros(ALCH_WORDS + self._alch[0], dtype=np.float64)
+        _lib.call("emdee_md_alchemical_read", self._handle, w.ctypes.data_as(C.c_void_p))
+        return dict(lam=float(w[0]), U=float(w[1]), dUdl=float(w[2]), virial=float(w[3]), pairs=int(round(w[4])), foreign=w[ALCH_WORDS:].copy())
+
+    def alchemical_log(self):
+        """The on-device log so far (blocking), as a dict: dUdl and U, float64 numpy (count,), foreign (count, n_foreign), entry j
+        taken at the pass that closed step (j + 1) log_every since the set; count; dropped, the samples that found the log full."""
+        if self._alch is None:
+            raise RuntimeError("alchemical_log: no alchemical table is set (set_alchemical_)")
+        nf, cap = self._alch
+        buf = torch.zeros((max(cap, 1), 2 + nf), dtype=torch.float64, device=self.device)
+        count, dropped = C.c_int64(), C.c_int64()
+        _lib.call("emdee_md_alchemical_log_read", self._handle, C.c_void_p(buf.data_ptr()), C.byref(count), C.byref(dropped))
+        h = buf[:count.value].cpu().numpy()
+        return dict(dUdl=h[:, 0].copy(), U=h[:, 1].copy(), foreign=h[:, 2:].copy(), count=int(count.value), dropped=int(dropped.value))
 
     def close(self):
         if self._handle is not None:

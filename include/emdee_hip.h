@@ -741,7 +741,8 @@ int32_t emdee_md_count_pairs(emdee_md *md, int64_t *pairs_in_cutoff);
  * 16 = the three launches of every sample of the displacement and velocity correlations (emdee_md_msd_sample);
  * 17 = the launches every sample of the Green-Kubo observables adds to the tensor pass (emdee_md_gk_sample);
  * 18 = the launch the position restraints add to every force pass, and the scaling of their references (emdee_md_set_restraints);
- * 19 = the three launches the centre-of-mass pull adds to every force pass (emdee_md_set_pull).
+ * 19 = the three launches the centre-of-mass pull adds to every force pass (emdee_md_set_pull);
+ * 20 = the row pass of the alchemical table at every rebuild and its launches behind every force pass (emdee_md_set_alchemical).
  * Blocking. */
 int32_t emdee_md_profile(emdee_md *md, int32_t enable);
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches);
@@ -1135,6 +1136,63 @@ int32_t emdee_md_set_pull(emdee_md *md, const int32_t *group_dev, int32_t n_grou
                           int32_t n_coords, int32_t log_every, int32_t log_capacity);
 int32_t emdee_md_pull_read(emdee_md *md, double *coords_out, double *groups_out);
 int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
+
+/* ---- soft-core alchemical decoupling (alchemical.hpp)
+ * The Lennard-Jones stage of a solvation free energy: the coupling of one group of atoms, the solute, to everything else is turned
+ * off along lambda through a soft core.  (The Coulomb stage needs no call of its own: scale the solute's charges with
+ * emdee_md_set_coulomb.)  Every pair of one flagged and one unflagged atom inside the cutoff interacts by
+ *     u = (r^2 / sigma_ij^2)^3,  D = alpha (1 - lambda) + u,  U(r; lambda) = lambda 4 eps_ij (D^-2 - D^-1) g(r)
+ * -- Beutler et al. 1994 with lambda-power 1 and r-power 6 (GROMACS sc-power = 1, sc-r-power = 6); sigma_ij and 4 eps_ij from the
+ * atoms' own records, g the model's switch, r^2 < rc^2 the test of every pair loop.  Flagged-flagged and unflagged-unflagged pairs
+ * stay in the neighbour rows at full strength: DECOUPLING, NOT ANNIHILATION.  At lambda = 1 the term is the model's pair function, at
+ * lambda = 0 exactly 0; at r = 0 with lambda < 1 and alpha > 0 it is finite and exerts no force; alpha = 0 is plain linear scaling,
+ * which diverges at overlap.
+ * emdee_md_set_alchemical (blocking; flag_dev = NULL clears the table):
+ *   flag_dev      n_owned int32 on the device by caller id: 1 for a solute atom, 0 for the environment; at least one 1.
+ *   lambda        in [0, 1]; emdee_md_set_lambda moves it later.
+ *   alpha         the soft-core parameter, finite and >= 0 (0.5 is the usual choice).
+ *   foreign       HOST, n_foreign doubles in [0, 1]: the lambdas U_alch is also evaluated at for BAR and MBAR; n_foreign 0 ... 16.
+ *   log_every, log_capacity   the on-device log (below); log_capacity = 0: none.
+ * How it runs.  Right after every list build the cross entries leave the rows of the owned atoms (after the exclusion filter: an
+ * excluded cross pair stays excluded) and their slots go to a compact CSR of the build, memory O(struck entries).  Behind every force
+ * pass one launch runs over the atoms that own struck entries -- a wavefront per solute atom, a thread per environment atom, half of a
+ * pair's E and W to the owner, no atomics -- and adds to the force, energy, virial and tensor planes under the pass's mask, so that
+ * emdee_md_minimize, emdee_md_energies, the pressure entries, the molecular sums, the barostats and the Green-Kubo stress see the
+ * term with the rest.  The same pass leaves U_alch, dU/dlambda, the cross pairs' scalar virial and the number of cross pairs inside
+ * rc on the device: fp64 sums in an order that depends on the state alone, bitwise reproducible.  An engine with a table steps in
+ * closed steps, as a restrained or pulled one does; an engine without one is launch for launch and bit for bit what it was.  A
+ * two-species box with a table runs on the general-species kernels.  Setting or clearing the table rebuilds the list and evaluates
+ * the forces again.
+ * emdee_md_set_lambda: lambda in [0, 1], a host scalar handed to the kernels as an argument -- no rebuild; the next step or query
+ * evaluates the forces anew.  For slow growth and lambda schedules.
+ * emdee_md_alchemical_read (blocking): words[0 .. EMDEE_ALCH_WORDS) = {lambda, U_alch, dU/dlambda, the cross virial, the cross pairs
+ * inside rc} of the current positions, then the n_foreign energies U_alch(foreign[k]) at the same positions (one energies-only launch).
+ * emdee_md_alchemical_log_read: the log takes entry j, {dU/dlambda, U_alch, the n_foreign foreign energies}, at the pass that closes
+ * step (j + 1) log_every counted from the set; when it is full, further samples are dropped and counted.  The entries so far go to
+ * log_dev (device, capacity x (2 + n_foreign) doubles, queued on the context's stream; may be NULL), their number to *count, the
+ * dropped samples to *dropped.  The foreign energies are evaluated at log events and by the read only, never in a plain force pass.
+ *   - All or nothing.  EMDEE_ERR_INVALID, the previous table in force: a flag that is neither 0 nor 1; no flagged atom; lambda or a
+ *     foreign lambda outside [0, 1]; alpha negative or not finite; n_foreign outside 0 ... 16 or a NULL array with n_foreign > 0; a
+ *     negative log_every or log_capacity, or a log without log_every >= 1.  The text names the entry and the value.
+ *   - EMDEE_ERR_STATE, the previous table in force: a call before emdee_md_set_state; ghosts; an integrator lent by emdee_dd_engine.
+ *     The reads and emdee_md_set_lambda refuse without a table.  A force pass on the operator path refuses with a table.
+ *   - On a charged engine every flagged atom must carry charge 0 -- a Coulomb soft core is not built: otherwise emdee_md_step and
+ *     emdee_md_minimize refuse (EMDEE_ERR_STATE), naming the first such atom.  With zero charges the reaction field, Ewald and PME
+ *     need nothing.
+ *   - Flagged atoms may be atoms of rigid molecules, of hbonds clusters, or virtual sites: the flag says nothing about constraints.
+ *   - The table survives an emdee_md_set_state with the same atom count.  After a state with another count emdee_md_step,
+ *     emdee_md_minimize, emdee_md_scale_box and the reads refuse (EMDEE_ERR_STATE) until the table is set again or cleared.
+ *   - The Green-Kubo heat flux (EMDEE_GK_HEAT) is refused with an alchemical table, at set and at sample.
+ * Device time: emdee_md_kernel_time index 20 (the row pass at a rebuild and the launches behind a force pass).
+ * Scope: undivided engines.  Follow-ups, not here: a Coulomb soft core; more than one group, each with its own lambda; annihilation
+ * of the solute's internal pairs; decomposed runs. */
+#define EMDEE_ALCH_WORDS           5
+#define EMDEE_ALCH_MAX_FOREIGN     16
+int32_t emdee_md_set_alchemical(emdee_md *md, const int32_t *flag_dev, double lambda, double alpha, const double *foreign,
+                                int32_t n_foreign, int32_t log_every, int32_t log_capacity);
+int32_t emdee_md_set_lambda(emdee_md *md, double lambda);
+int32_t emdee_md_alchemical_read(emdee_md *md, double *words);
+int32_t emdee_md_alchemical_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
