@@ -132,6 +132,10 @@ SIGNATURES = {
     "emdee_md_msd_sample": [_p],
     "emdee_md_msd_read": [_p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "emdee_md_msd_reset": [_p],
+    "emdee_md_set_spatial": [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _i32],
+    "emdee_md_spatial_sample": [_p],
+    "emdee_md_spatial_read": [_p, _p, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_dbl)],
+    "emdee_md_spatial_reset": [_p],
     "emdee_md_set_gk": [_p, _i32, _i32],
     "emdee_md_gk_sample": [_p],
     "emdee_md_gk_read": [_p, _p, _p, _p, C.POINTER(_i64)],

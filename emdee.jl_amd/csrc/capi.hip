@@ -562,6 +562,20 @@ int32_t emdee_md_gk_read(emdee_md *md, double *sums, double totals[9], double la
 int32_t emdee_md_gk_reset(emdee_md *md) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->gk_reset(); });
 }
+int32_t emdee_md_set_spatial(emdee_md *md, int32_t geometry, int32_t what, int32_t n_bins, int32_t n_groups, const int32_t *group_dev,
+                             const double range[2], const double centre[3], int32_t centre_group) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_spatial(geometry, what, n_bins, n_groups, group_dev, range, centre, centre_group); });
+}
+int32_t emdee_md_spatial_sample(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->spatial_sample(); });
+}
+int32_t emdee_md_spatial_read(emdee_md *md, int64_t *counts, double *sums, int64_t outside[8], int64_t group_sizes[8], int64_t *frames,
+                              double *inv_bin_volume_sum) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->spatial_read(counts, sums, outside, group_sizes, frames, inv_bin_volume_sum); });
+}
+int32_t emdee_md_spatial_reset(emdee_md *md) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->spatial_reset(); });
+}
 
 // ---------------------------------------------------------------- domain decomposition
 int32_t emdee_dd_unique_id(uint8_t out[128]) {

@@ -96,6 +96,11 @@ struct IMd {
     virtual void gk_sample() = 0;
     virtual void gk_read(double *sums, double *totals, double *last, int64_t *samples) = 0;
     virtual void gk_reset() = 0;
+    virtual void set_spatial(int32_t geometry, int32_t what, int32_t n_bins, int32_t n_groups, const int32_t *group_dev, const double *range,
+                             const double *centre, int32_t centre_group) = 0;
+    virtual void spatial_sample() = 0;
+    virtual void spatial_read(int64_t *counts, double *sums, int64_t *outside, int64_t *group_sizes, int64_t *frames, double *inv_bin_volume_sum) = 0;
+    virtual void spatial_reset() = 0;
 };
 
 // spatial domain decomposition (emdee_dd_*): the domains of the decomposition that live in this process

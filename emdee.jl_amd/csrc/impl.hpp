@@ -599,7 +599,7 @@ struct MdImpl : IMd {
         EMDEE_HIP_CHECK(hipGetLastError());
         sys.read_back_doubles(out, part, 2);
     }
-    // ---- the observables (include/emdee_hip.h: emdee_md_set_rdf, emdee_md_set_msd, emdee_md_set_gk).  A table is one
+    // ---- the observables (include/emdee_hip.h: emdee_md_set_rdf, emdee_md_set_msd, emdee_md_set_gk, emdee_md_set_spatial).  A table is one
     // record, host fields and device buffers together, and the refusals the three share are formed once (observables.hpp).  Every
     // setter is all or nothing and blocking: it builds a candidate record and queues its uploads, every refusal -- a failed
     // allocation included -- comes before the table in force changes, and install() swaps the candidate in whole.  Clearing puts
@@ -819,6 +819,151 @@ struct MdImpl : IMd {
         if (samples) *samples = gk.samples;
     }
     void gk_reset() override { reset(OBS_GK, gk); }
+    // ---- spatial profiles along an axis and around a centre (spatial.hpp)
+    SpatialRecord spatial;
+    // EMDEE_SPATIAL_STRESS bins the atomic tensors, which lack the constraint virial: at set and again at every sample
+    void require_spatial(const char *fn, int what) const {
+        obs_require_whole_box(fn, obs_engine());
+        if (!(what & SPATIAL_STRESS)) return;
+        EMDEE_REQUIRE(!sys.has_rigid(), EMDEE_ERR_STATE, "%s: EMDEE_SPATIAL_STRESS on an engine with rigid molecules (emdee_md_set_rigid3): the "
+                      "per-atom tensors lack the constraint virial; clear the table first, or profile EMDEE_SPATIAL_DENSITY | EMDEE_SPATIAL_KINETIC", fn);
+        EMDEE_REQUIRE(!sys.has_hbonds(), EMDEE_ERR_STATE, "%s: EMDEE_SPATIAL_STRESS on an engine with an hbonds table (emdee_md_set_hbonds): the "
+                      "per-atom tensors lack the constraint virial; clear the table first, or profile EMDEE_SPATIAL_DENSITY | EMDEE_SPATIAL_KINETIC", fn);
+    }
+    // half the shortest periodic side: what a radial table's r_max may reach (a droplet box has no periodic side and no limit)
+    double radial_limit() const {
+        double h = INFINITY;
+        for (int d = 0; d < 3; d++)
+            if (sys.per[d]) h = std::min(h, 0.5 * sys.len[d]);
+        return h;
+    }
+    void set_spatial(int32_t geometry, int32_t what, int32_t n_bins, int32_t n_groups, const int32_t *group_dev, const double *range,
+                     const double *centre, int32_t centre_group) override {
+        use_device(sys.ctx);
+        if (n_bins == 0) { spatial = SpatialRecord{}; return; }
+        EMDEE_REQUIRE(geometry >= SPATIAL_X && geometry <= SPATIAL_RADIAL, EMDEE_ERR_INVALID, "set_spatial: geometry = %d is none of EMDEE_SPATIAL_X, "
+                      "_Y, _Z, _RADIAL (0...3)", geometry);
+        EMDEE_REQUIRE(what >= 1 && what <= SPATIAL_ALL, EMDEE_ERR_INVALID, "set_spatial: what = %d is not a non-empty mask of "
+                      "EMDEE_SPATIAL_DENSITY | EMDEE_SPATIAL_KINETIC | EMDEE_SPATIAL_STRESS", what);
+        EMDEE_REQUIRE(n_bins >= 1 && n_bins <= SPATIAL_MAX_BINS, EMDEE_ERR_INVALID, "set_spatial: n_bins = %d is outside 1...%d (0 clears the table)",
+                      n_bins, SPATIAL_MAX_BINS);
+        EMDEE_REQUIRE(n_groups >= 1 && n_groups <= SPATIAL_MAX_GROUPS, EMDEE_ERR_INVALID, "set_spatial: n_groups = %d is outside 1...%d", n_groups,
+                      SPATIAL_MAX_GROUPS);
+        EMDEE_REQUIRE(centre_group >= -1 && centre_group < n_groups, EMDEE_ERR_INVALID, "set_spatial: centre_group = %d is outside -1...%d",
+                      centre_group, n_groups - 1);
+        require_spatial("set_spatial", what);
+        SpatialRecord t;
+        if (geometry == SPATIAL_RADIAL) {
+            EMDEE_REQUIRE(range, EMDEE_ERR_INVALID, "set_spatial: the radial geometry needs range = {0, r_max}");
+            EMDEE_REQUIRE(range[0] == 0.0 && std::isfinite(range[1]) && range[1] > 0.0, EMDEE_ERR_INVALID, "set_spatial: the radial range must be "
+                          "{0, r_max} with r_max finite and > 0");
+            EMDEE_REQUIRE(range[1] <= radial_limit(), EMDEE_ERR_INVALID, "set_spatial: r_max = %g exceeds half the shortest periodic side %g "
+                          "(minimum image)", range[1], radial_limit());
+            if (centre_group < 0) {
+                EMDEE_REQUIRE(centre, EMDEE_ERR_INVALID, "set_spatial: the radial geometry needs a centre or a centre_group");
+                EMDEE_REQUIRE(std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]), EMDEE_ERR_INVALID,
+                              "set_spatial: the centre is not finite");
+                for (int d = 0; d < 3; d++) t.centre[d] = centre[d];
+            }
+            t.range[0] = 0.0; t.range[1] = range[1];
+        } else if (sys.per[geometry]) {
+            EMDEE_REQUIRE(!range, EMDEE_ERR_INVALID, "set_spatial: axis %d is periodic: its bins are fractions of the box, range must be NULL", geometry);
+        } else {
+            EMDEE_REQUIRE(range, EMDEE_ERR_INVALID, "set_spatial: axis %d is open: range = {r0, r1} is required", geometry);
+            EMDEE_REQUIRE(std::isfinite(range[0]) && std::isfinite(range[1]) && range[0] < range[1], EMDEE_ERR_INVALID, "set_spatial: the range "
+                          "must be finite with r0 < r1");
+            t.range[0] = range[0]; t.range[1] = range[1];
+        }
+        const int n = sys.n_owned;
+        const std::vector<int32_t> host = fetched_groups(OBS_SPATIAL, group_dev, n_groups);
+        const MsdLayout lay = msd_layout(group_dev ? host.data() : nullptr, n, n_groups);
+        std::vector<int> atoms((size_t)lay.n_grouped + 1, 0);
+        for (int i = 0; i < n; i++)
+            if (lay.pos_of[(size_t)i] >= 0) atoms[(size_t)lay.pos_of[(size_t)i]] = i;
+        t.present = true; t.geometry = geometry; t.what = what; t.n_atoms = n; t.n_bins = n_bins; t.n_groups = n_groups;
+        t.centre_group = geometry == SPATIAL_RADIAL ? centre_group : -1;
+        t.n_grouped = lay.n_grouped; t.n_chunks = (int)lay.chunks.size();
+        for (int g = 0; g < SPATIAL_MAX_GROUPS; g++) t.sizes[g] = lay.sizes[g];
+        for (int g = 0; g <= SPATIAL_MAX_GROUPS; g++) t.chunk_of_group[g] = lay.chunk_of_group[g];
+        const size_t nw = (size_t)spatial_n_words(what), slots = lay.chunks.size() * SPATIAL_CHUNK;
+        t.pos_of.ensure((size_t)n + 1); t.atoms.ensure(atoms.size()); t.chunk_of_group_dev.ensure(SPATIAL_MAX_GROUPS + 1);
+        t.chunks.ensure(lay.chunks.size() + 1); t.key.ensure((size_t)lay.n_grouped + 1); t.planes.ensure(nw * lay.n_grouped + 1);
+        t.sbin.ensure(slots + 1); t.runn.ensure(slots + 1); t.runw.ensure(slots * nw + 1);
+        t.sums.ensure(t.n_sums()); t.counts.ensure(t.n_cells() + SPATIAL_MAX_GROUPS);
+        t.partial.ensure(4 * lay.chunks.size() + 4); t.centre_dev.ensure(4);
+        if (n > 0) EMDEE_HIP_CHECK(hipMemcpyAsync(t.pos_of.ptr, lay.pos_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, sys.stream()));
+        EMDEE_HIP_CHECK(hipMemcpyAsync(t.atoms.ptr, atoms.data(), atoms.size() * sizeof(int), hipMemcpyHostToDevice, sys.stream()));
+        EMDEE_HIP_CHECK(hipMemcpyAsync(t.chunk_of_group_dev.ptr, lay.chunk_of_group, sizeof(lay.chunk_of_group), hipMemcpyHostToDevice, sys.stream()));
+        if (!lay.chunks.empty())
+            EMDEE_HIP_CHECK(hipMemcpyAsync(t.chunks.ptr, lay.chunks.data(), lay.chunks.size() * sizeof(MsdChunk), hipMemcpyHostToDevice, sys.stream()));
+        if (t.centre_group >= 0) {                           // (the group's mass, once: the set is blocking anyway)
+            double c[4] = {0.0, 0.0, 0.0, 0.0};
+            if (sys.n_total > 0) {
+                sys.spatial_centre(t);
+                EMDEE_HIP_CHECK(hipGetLastError());
+                sys.read_back_doubles(c, t.centre_dev.ptr, 4);
+            }
+            EMDEE_REQUIRE(c[3] > 0.0, EMDEE_ERR_INVALID, "set_spatial: the centre group %d has total mass 0: it has no centre of mass", centre_group);
+        }
+        install(spatial, t);
+    }
+    // the geometry of a sample from the box as it is now
+    SpatialGeom spatial_geom() const {
+        SpatialGeom g{};
+        g.geometry = spatial.geometry; g.n_bins = spatial.n_bins;
+        if (spatial.geometry == SPATIAL_RADIAL) {
+            g.cx = spatial.centre[0]; g.cy = spatial.centre[1]; g.cz = spatial.centre[2];
+            for (int d = 0; d < 3; d++) { g.len[d] = sys.per[d] ? sys.len[d] : 0.0; g.inv_len[d] = sys.per[d] ? 1.0 / sys.len[d] : 0.0; }
+            g.r_max = spatial.range[1]; g.inv_dr = (double)spatial.n_bins / spatial.range[1];
+        } else {
+            const int d = spatial.geometry;
+            g.periodic = sys.per[d] ? 1 : 0;
+            g.lo = g.periodic ? sys.lo[d] : spatial.range[0];
+            g.inv_width = (double)spatial.n_bins / (g.periodic ? sys.len[d] : spatial.range[1] - spatial.range[0]);
+        }
+        return g;
+    }
+    // one sample: with EMDEE_SPATIAL_STRESS the tensor pass first if it is not current, as gk_sample; without it no pass of the engine
+    void spatial_sample() override {
+        use_device(sys.ctx);
+        obs_require_present(OBS_SPATIAL, "sample", spatial);
+        require_spatial("spatial_sample", spatial.what);
+        obs_require_fit(OBS_SPATIAL, spatial, obs_engine());
+        const int d = spatial.geometry;
+        if (d == SPATIAL_RADIAL)
+            EMDEE_REQUIRE(spatial.range[1] <= radial_limit(), EMDEE_ERR_STATE, "spatial_sample: the box has shrunk: r_max = %g now exceeds half the "
+                          "shortest periodic side %g; set the table again with a smaller r_max", spatial.range[1], radial_limit());
+        else
+            EMDEE_REQUIRE((sys.per[d] != 0) == (spatial.range[0] == spatial.range[1]), EMDEE_ERR_STATE, "spatial_sample: axis %d has been opened or "
+                          "closed since the table was set: set it again (emdee_md_set_spatial)", d);
+        if (spatial.what & (SPATIAL_DENSITY | SPATIAL_STRESS))
+            EMDEE_REQUIRE(!sys.charges_stale(), EMDEE_ERR_STATE, "spatial_sample: charges set for %lld atoms, the state holds %d: set them again or "
+                          "clear them (emdee_md_set_coulomb)", (long long)sys.tables->q_n, sys.n_owned);
+        if (spatial.what & SPATIAL_STRESS) tensor_pass();
+        sys.spatial_sample(spatial, spatial_geom());
+        EMDEE_HIP_CHECK(hipGetLastError());
+        spatial.samples++;
+        if (d != SPATIAL_RADIAL) {
+            const double area = sys.len[(d + 1) % 3] * sys.len[(d + 2) % 3];
+            const double width = (sys.per[d] ? sys.len[d] : spatial.range[1] - spatial.range[0]) / (double)spatial.n_bins;
+            spatial.inv_bin_volume_sum += 1.0 / (area * width);
+        }
+    }
+    // the deferred fault word of the bonded terms is checked here, not in the sample
+    void spatial_read(int64_t *counts, double *sums, int64_t *outside, int64_t *group_sizes, int64_t *frames, double *inv_bin_volume_sum) override {
+        use_device(sys.ctx);
+        obs_require_present(OBS_SPATIAL, "read", spatial);
+        sys.check_bonded();
+        const size_t nc = spatial.n_cells();
+        if (counts) EMDEE_HIP_CHECK(hipMemcpyAsync(counts, spatial.counts.ptr, nc * sizeof(int64_t), hipMemcpyDeviceToHost, sys.stream()));
+        if (outside) EMDEE_HIP_CHECK(hipMemcpyAsync(outside, spatial.counts.ptr + nc, SPATIAL_MAX_GROUPS * sizeof(int64_t), hipMemcpyDeviceToHost, sys.stream()));
+        if (sums) EMDEE_HIP_CHECK(hipMemcpyAsync(sums, spatial.sums.ptr, spatial.n_sums() * sizeof(double), hipMemcpyDeviceToHost, sys.stream()));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(sys.stream()));
+        if (group_sizes) for (int g = 0; g < SPATIAL_MAX_GROUPS; g++) group_sizes[g] = spatial.sizes[g];
+        if (frames) *frames = spatial.samples;
+        if (inv_bin_volume_sum) *inv_bin_volume_sum = spatial.inv_bin_volume_sum;
+    }
+    void spatial_reset() override { reset(OBS_SPATIAL, spatial); }
     // one coupling event: the pressure of the step just completed from the engine's own fp64 box sums (the event's one
     // read-back), the factors on the host, emdee_md_scale_box
     void couple(double dt) {
@@ -1067,13 +1212,13 @@ struct MdImpl : IMd {
         // observables adds to the tensor pass (emdee_md_gk_sample); 18: the launch the position restraints add to every force pass, and
         // the scaling of their references (emdee_md_set_restraints); 19: the three launches the centre-of-mass pull adds to every force
         // pass (emdee_md_set_pull); 20: the row pass of the alchemical table at every rebuild and its launches behind every force pass
-        // (emdee_md_set_alchemical)
-        EMDEE_REQUIRE(kernel >= 0 && kernel <= 20, EMDEE_ERR_INVALID, "kernel id out of range");
+        // (emdee_md_set_alchemical); 21: the launches of every sample of the spatial profiles (emdee_md_spatial_sample)
+        EMDEE_REQUIRE(kernel >= 0 && kernel <= 21, EMDEE_ERR_INVALID, "kernel id out of range");
         use_device(sys.ctx);
-        const int ids[21][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
+        const int ids[22][2] = {{T_FORCE, -1}, {T_KICK_DRIFT, -1}, {T_REBUILD, -1}, {T_KICK, -1}, {T_STEP, T_STEP_BOUNDARY}, {T_STEP, -1},
                                 {T_STEP_BOUNDARY, -1}, {T_HALO, -1}, {T_EWALD, -1}, {T_SETTLE, -1}, {T_MOLECULAR, -1},
                                 {T_HBONDS, -1}, {T_MINIMIZE, -1}, {T_VSITE, -1}, {T_THERMOSTAT, -1}, {T_RDF, -1}, {T_MSD, -1}, {T_GK, -1},
-                                {T_RESTRAINTS, -1}, {T_PULL, -1}, {T_ALCHEMICAL, -1}};
+                                {T_RESTRAINTS, -1}, {T_PULL, -1}, {T_ALCHEMICAL, -1}, {T_SPATIAL, -1}};
         double ms = 0.0;
         int64_t n = 0;
         for (int q = 0; q < 2; q++) {

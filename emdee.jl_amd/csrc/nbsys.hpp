@@ -56,9 +56,11 @@ static inline void refuse_experiment_switches() {
 // T_RESTRAINTS: the launch the position restraints add to every force pass, and the scaling of their references (restraint.hpp)
 // T_PULL: the three launches the centre-of-mass pull adds to every force pass (pull.hpp): partial sums, finish, apply
 // T_ALCHEMICAL: the row pass of the alchemical table at a rebuild and its launches behind a force pass (alchemical.hpp)
+// T_SPATIAL: the three launches of a sample of the spatial profiles (spatial.hpp): gather, accumulate, finish; two more ahead of them
+// with a centre group (the chunks' partial sums, the centre of mass)
 enum TimerId { T_FORCE = 0, T_KICK_DRIFT = 1, T_REBUILD = 2, T_KICK = 3, T_STEP = 4, T_STEP_BOUNDARY = 5, T_HALO = 6, T_EWALD = 7, T_SETTLE = 8,
                T_MOLECULAR = 9, T_HBONDS = 10, T_MINIMIZE = 11, T_VSITE = 12, T_THERMOSTAT = 13, T_RDF = 14, T_MSD = 15, T_GK = 16, T_RESTRAINTS = 17,
-               T_PULL = 18, T_ALCHEMICAL = 19, T_COUNT = 20 };
+               T_PULL = 18, T_ALCHEMICAL = 19, T_SPATIAL = 20, T_COUNT = 21 };
 // The words of NbSystem::flags above the ones the build, the plan and the step kernels use (flags[0..15]).  Fault words (FaultWord,
 // common.hpp), each the entry + 1 a kernel failed on: W_BONDED, a bonded term whose partner was missing from the rows (k_bonded);
 // W_CHARGES, a key without a charge (k_fill_charges); W_EWALD, a struck pair whose partner was missing from the rows
@@ -2018,6 +2020,64 @@ struct NbSystem {
         {
             Timed timed(this, T_GK);
             hipLaunchKernelGGL(k_gk_correlate, dim3(blocks_for(gk_live_lags(t.samples, t.n_lags), GK_BLOCK)), dim3(GK_BLOCK), 0, stream(), a);
+        }
+    }
+
+    // ---------------------------------------------------------------- spatial profiles (spatial.hpp; the table is MdImpl's SpatialRecord, observables.hpp)
+    // A sample reads the records, the image counts, perm, the velocities, the masses, the charge table and (SPATIAL_STRESS) the outputs
+    // of a current tensor pass; it writes the record's buffers, nothing of the engine's.
+    // the centre of mass of the table's centre group into t.centre_dev (R, then M): two launches, timed under `timer` when >= 0
+    void spatial_centre(SpatialRecord &t, int timer = -1) {
+        const int c0 = t.chunk_of_group[t.centre_group], nc = t.chunk_of_group[t.centre_group + 1] - c0;
+        const RestraintArgs<real> ra = restraint_args(t.atoms.ptr, t.n_grouped);
+        if (nc > 0)
+            timed_if(timer, [&] {
+                hipLaunchKernelGGL((k_spatial_centre_partials<real>), dim3(nc), dim3(SPATIAL_BLOCK), 0, stream(), ra, with_mass ? (const real *)im.ptr : nullptr,
+                                   (const MsdChunk *)t.chunks.ptr + c0, t.partial.ptr);
+            });
+        timed_if(timer, [&] {
+            hipLaunchKernelGGL(k_spatial_centre, dim3(1), dim3(WAVE), 0, stream(), nc, (const double *)t.partial.ptr, t.centre_dev.ptr);
+        });
+    }
+    // one sample with the geometry of the current box: queued on the stream, nothing read back
+    void spatial_sample(SpatialRecord &t, const SpatialGeom &geom) {
+        if (n_total == 0 || t.n_grouped == 0) return;
+        const bool by_group = geom.geometry == SPATIAL_RADIAL && t.centre_group >= 0;
+        if (by_group) spatial_centre(t, T_SPATIAL);
+        SpatialSrc<real> a{};
+        a.n = n_total; a.n_owned = n_owned; a.g = grid; a.img = img.ptr; a.perm = perm.ptr; a.rec = rec.ptr;
+        a.rel = rel_grid(rel_now, cell_sorted.ptr);
+        a.vel = with_vel ? vel.ptr : nullptr; a.inv_mass = with_mass ? im.ptr : nullptr; a.en = en.ptr; a.vt = vt.ptr; a.pitch = pitch;
+        a.q_raw = has_charges() ? tables->q_raw.ptr : nullptr;
+        a.q_n = tables->q_n;
+        auto launch = [&](auto mask) {
+            constexpr int MASK = decltype(mask)::value;
+            {
+                Timed timed(this, T_SPATIAL);
+                hipLaunchKernelGGL((k_spatial_gather<real, MASK>), dim3(blocks_for(n_total, 256)), dim3(256), 0, stream(), a, geom,
+                                   by_group ? (const double *)t.centre_dev.ptr : nullptr, (const int *)t.pos_of.ptr, t.n_grouped, t.key.ptr,
+                                   t.planes.ptr);
+            }
+            {
+                Timed timed(this, T_SPATIAL);
+                hipLaunchKernelGGL((k_spatial_accumulate<MASK>), dim3(t.n_chunks), dim3(SPATIAL_BLOCK), 0, stream(), (const MsdChunk *)t.chunks.ptr,
+                                   (const int *)t.key.ptr, (const double *)t.planes.ptr, (size_t)t.n_grouped, t.sbin.ptr, t.runn.ptr, t.runw.ptr);
+            }
+            {
+                Timed timed(this, T_SPATIAL);
+                hipLaunchKernelGGL((k_spatial_finish<MASK>), dim3(blocks_for((size_t)t.n_bins + 1, SPATIAL_BLOCK), t.n_groups), dim3(SPATIAL_BLOCK),
+                                   0, stream(), t.n_bins, (const int *)t.chunk_of_group_dev.ptr, (const int *)t.sbin.ptr, (const int *)t.runn.ptr,
+                                   (const double *)t.runw.ptr, t.sums.ptr, t.counts.ptr, t.counts.ptr + t.n_cells());
+            }
+        };
+        switch (t.what) {
+            case 1: launch(std::integral_constant<int, 1>{}); break;
+            case 2: launch(std::integral_constant<int, 2>{}); break;
+            case 3: launch(std::integral_constant<int, 3>{}); break;
+            case 4: launch(std::integral_constant<int, 4>{}); break;
+            case 5: launch(std::integral_constant<int, 5>{}); break;
+            case 6: launch(std::integral_constant<int, 6>{}); break;
+            default: launch(std::integral_constant<int, 7>{}); break;
         }
     }
 

@@ -1,7 +1,7 @@
-// observables.hpp -- the tables of the on-device observables (emdee_md_set_rdf, emdee_md_set_msd, emdee_md_set_gk; rdf.hpp, msd.hpp
-// and gk.hpp have the algorithms and the kernels): one record per observable, host fields and device buffers together, and the
-// refusals the three share, each formed once.  MdImpl (impl.hpp) builds a candidate record, checks it and swaps it in whole
-// (MdImpl::install); NbSystem::rdf_sample / msd_sample / gk_sample (nbsys.hpp) queue a sample on the record they are handed.  The
+// observables.hpp -- the tables of the on-device observables (emdee_md_set_rdf, emdee_md_set_msd, emdee_md_set_gk, emdee_md_set_spatial;
+// rdf.hpp, msd.hpp, gk.hpp and spatial.hpp have the algorithms and the kernels): one record per observable, host fields and device buffers together, and the
+// refusals they share, each formed once.  MdImpl (impl.hpp) builds a candidate record, checks it and swaps it in whole
+// (MdImpl::install); NbSystem::rdf_sample / msd_sample / gk_sample / spatial_sample (nbsys.hpp) queue a sample on the record they are handed.  The
 // part with no HIP in it -- the records' base, the texts and the gate -- is plain C++ at the top: a stand-alone host program
 // drives it with the host compiler (tests/c/observables_host.cpp); the records below it own device memory.
 #pragma once
@@ -10,19 +10,21 @@
 #include "gk.hpp"
 #include "msd.hpp"
 #include "rdf.hpp"
+#include "spatial.hpp"
 
 namespace emdee {
 
-enum ObsKind { OBS_RDF = 0, OBS_MSD = 1, OBS_GK = 2 };
+enum ObsKind { OBS_RDF = 0, OBS_MSD = 1, OBS_GK = 2, OBS_SPATIAL = 3 };
 // name: the prefix of the four entries' messages; since / replaced / rescaled: why a sample is refused after emdee_md_set_state or
 // a rescaled box (nullptr: the observable pins neither -- a frame of the radial distribution functions stands alone)
 struct ObsText { const char *name, *set, *setter, *reset, *since, *replaced, *rescaled; };
-constexpr ObsText OBS_TEXT[3] = {
+constexpr ObsText OBS_TEXT[4] = {
     {"rdf", "set_rdf", "emdee_md_set_rdf", "emdee_md_rdf_reset", nullptr, nullptr, nullptr},
     {"msd", "set_msd", "emdee_md_set_msd", "emdee_md_msd_reset", "the origins were taken", "a displacement between two states means nothing",
      "unwrapped coordinates across a rescaled box are not a displacement"},
     {"gk", "set_gk", "emdee_md_set_gk", "emdee_md_gk_reset", "the first sample", "a correlation between two states means nothing",
-     "the stress and the heat flux are extensive and the Green-Kubo prefactor assumes one volume"}};
+     "the stress and the heat flux are extensive and the Green-Kubo prefactor assumes one volume"},
+    {"spatial", "set_spatial", "emdee_md_set_spatial", "emdee_md_spatial_reset", nullptr, nullptr, nullptr}};
 
 // what the refusals ask of the engine (state_serial counts emdee_md_set_state)
 struct ObsEngine {
@@ -120,6 +122,27 @@ struct GkRecord : ObsTable {
     void zero(hipStream_t s, const ObsEngine &e) {
         EMDEE_HIP_CHECK(hipMemsetAsync(ring.ptr, 0, ring_words() * sizeof(double), s));
         EMDEE_HIP_CHECK(hipMemsetAsync(acc.ptr, 0, acc_words() * sizeof(double), s));
+        restart(e);
+    }
+};
+// The table order (pos_of, and atoms: its inverse, one caller id per entry, for the centre group's centre of mass), its chunks, the
+// planes of one sample (the bins, the masked addends), the chunks' runs (sorted bins, lengths, words), the sums and the counts
+// (n_groups n_bins of them, then the eight `outside`).
+struct SpatialRecord : ObsTable {
+    int geometry = 0, what = 0, n_bins = 0, n_groups = 0, centre_group = -1, n_grouped = 0, n_chunks = 0;
+    double range[2] = {0, 0}, centre[3] = {0, 0, 0}, inv_bin_volume_sum = 0.0;
+    int64_t sizes[SPATIAL_MAX_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int chunk_of_group[SPATIAL_MAX_GROUPS + 1] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf<int> pos_of, atoms, chunk_of_group_dev, key, sbin, runn;
+    DevBuf<MsdChunk> chunks;
+    DevBuf<double> planes, runw, sums, partial, centre_dev;
+    DevBuf<unsigned long long> counts;
+    size_t n_cells() const { return (size_t)n_groups * n_bins; }
+    size_t n_sums() const { return n_cells() * SPATIAL_WORDS; }
+    void zero(hipStream_t s, const ObsEngine &e) {
+        EMDEE_HIP_CHECK(hipMemsetAsync(sums.ptr, 0, n_sums() * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipMemsetAsync(counts.ptr, 0, (n_cells() + SPATIAL_MAX_GROUPS) * sizeof(unsigned long long), s));
+        inv_bin_volume_sum = 0.0;
         restart(e);
     }
 };

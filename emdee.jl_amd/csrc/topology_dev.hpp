@@ -365,6 +365,7 @@ struct Topology {
     // ---- charges (emdee_*_set_coulomb): sqrt(K) q per atom key (caller id or global id, as the other tables), and the
     // reaction-field constants.  Every engine keeps a plane of them in its own cell order (NbSystem::qp).
     DevBuf<double> q_tab;
+    DevBuf<double> q_raw;                                    // the charges as the caller gave them (the spatial profiles' sum q)
     int64_t q_n = 0;                                         // keys 0 .. q_n - 1 have a charge
     double coulomb_k = 0.0, eps_rf = INFINITY, scale14c = 1.0;
     double q_sum = 0.0;                                      // sum of sqrt(K) q in key order (the Ewald background term)
@@ -380,6 +381,9 @@ struct Topology {
         }
         topo::check_coulomb(n, want, K, eps, s14);
         std::vector<double> h = fetch(charges_dev, (size_t)n, s);
+        const std::vector<double> raw = h;                  // (its own copy: the upload is queued, h is scaled in place)
+        DevBuf<double> nraw;
+        put(nraw, raw, s);
         topo::scale_charges(h, K);
         double sum = 0.0, sum_abs = 0.0;
         for (double v : h) { sum += v; sum_abs += std::fabs(v); }
@@ -388,6 +392,7 @@ struct Topology {
         EMDEE_HIP_CHECK(hipStreamSynchronize(s));
         // ---- commit
         q_tab.swap(nq);
+        q_raw.swap(nraw);
         q_n = n; coulomb_k = K; eps_rf = eps; scale14c = s14; q_sum = sum; q_abs = sum_abs;
         q_h.swap(h);
         has_charges = true;

@@ -6,6 +6,7 @@ export set_thermostat!, thermostat_state, set_thermostat_state!, thermostat_draw
 export set_rdf!, rdf_sample!, rdf_reset!, rdf_read
 export set_msd!, msd_sample!, msd_reset!, msd_read
 export set_gk!, gk_sample!, gk_reset!, gk_read
+export set_spatial!, spatial_sample!, spatial_reset!, spatial_read
 export set_restraints!, restraint_sums, restraint_refs!
 export set_pull!, pull_read, pull_log_read!
 export set_alchemical!, set_lambda!, alchemical_read, alchemical_log_read!
@@ -384,6 +385,53 @@ function gk_read(md::VelocityVerlet, n_lags)
     check(ccall((:emdee_md_gk_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}), md.handle,
                 sums, totals, last, samples))
     return (sums=sums, totals=totals, last=last, samples=samples[])
+end
+
+# Spatial profiles along an axis and around a centre (include/emdee_hip.h; undivided engines).
+# int32_t emdee_md_set_spatial(emdee_md *md, int32_t geometry, int32_t what, int32_t n_bins, int32_t n_groups,
+#                              const int32_t *group_dev, const double range[2], const double centre[3], int32_t centre_group);
+# geometry: EMDEE_SPATIAL_X, _Y, _Z (range === nothing on a periodic axis, (r0, r1) on an open one) or EMDEE_SPATIAL_RADIAL
+# (range = (0, r_max); centre, or centre_group >= 0: that group's centre of mass, formed on the device at every sample).  what: a
+# mask of EMDEE_SPATIAL_DENSITY | _KINETIC | _STRESS.  groups as set_msd! takes them.  n_bins in 1...4096; n_bins = 0 clears the table.
+const EMDEE_SPATIAL_X = 0
+const EMDEE_SPATIAL_Y = 1
+const EMDEE_SPATIAL_Z = 2
+const EMDEE_SPATIAL_RADIAL = 3
+const EMDEE_SPATIAL_DENSITY = 1
+const EMDEE_SPATIAL_KINETIC = 2
+const EMDEE_SPATIAL_STRESS = 4
+const EMDEE_SPATIAL_WORDS = 10
+function set_spatial!(md::VelocityVerlet, geometry, n_bins; what=EMDEE_SPATIAL_DENSITY | EMDEE_SPATIAL_KINETIC | EMDEE_SPATIAL_STRESS,
+                      n_groups=1, groups::Union{Nothing,HipArray{Int32,1}}=nothing, range=nothing, centre=nothing, centre_group=-1)
+    rng = range === nothing ? C_NULL : Float64[range[1], range[2]]
+    ctr = centre === nothing ? C_NULL : Float64[centre[1], centre[2], centre[3]]
+    check(ccall((:emdee_md_set_spatial, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32),
+                md.handle, Int32(geometry), Int32(what), Int32(n_bins), Int32(n_groups), groups === nothing ? C_NULL : groups.ptr, rng, ctr,
+                Int32(centre_group)))
+end
+
+# int32_t emdee_md_spatial_sample(emdee_md *md);
+# the current state as one more frame: queued on the stream, nothing read back, the run untouched
+spatial_sample!(md::VelocityVerlet) = check(ccall((:emdee_md_spatial_sample, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_spatial_reset(emdee_md *md);
+spatial_reset!(md::VelocityVerlet) = check(ccall((:emdee_md_spatial_reset, libemdee_hip), Int32, (Ptr{Cvoid},), md.handle))
+
+# int32_t emdee_md_spatial_read(emdee_md *md, int64_t *counts, double *sums, int64_t outside[8], int64_t group_sizes[8],
+#                               int64_t *frames, double *inv_bin_volume_sum);
+# blocking -> (counts (n_bins x n_groups), sums (10 x n_bins x n_groups: word w of bin k of group g is sums[w + 1, k + 1, g + 1]),
+# outside, group sizes, frames, inv_bin_volume_sum); P_N = (w6 + w9) / V_bin, P_T = ((w5 - w6) + (w8 - w9)) / (2 V_bin)
+function spatial_read(md::VelocityVerlet, n_bins, n_groups)
+    counts = zeros(Int64, n_bins, n_groups)
+    sums = zeros(Float64, EMDEE_SPATIAL_WORDS, n_bins, n_groups)
+    outside = zeros(Int64, RDF_MAX_GROUPS)
+    sizes = zeros(Int64, RDF_MAX_GROUPS)
+    frames = Ref{Int64}(0)
+    inv_bin_volume_sum = Ref{Float64}(0.0)
+    check(ccall((:emdee_md_spatial_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                md.handle, counts, sums, outside, sizes, frames, inv_bin_volume_sum))
+    return (counts=counts, sums=sums, outside=outside[1:n_groups], group_sizes=sizes[1:n_groups], frames=frames[],
+            inv_bin_volume_sum=inv_bin_volume_sum[])
 end
 
 # int32_t emdee_md_set_langevin_ids(emdee_md *md, const int64_t *ids_dev);

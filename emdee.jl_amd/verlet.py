@@ -31,6 +31,10 @@ _THERMOSTATS = {"off": THERMOSTAT_OFF, "v-rescale": THERMOSTAT_VRESCALE, "vresca
 MSD, VACF, MSD_WORDS = 1, 2, 7
 # Green-Kubo observables (include/emdee_hip.h: emdee_md_set_gk)
 GK_STRESS, GK_HEAT, GK_WORDS = 1, 2, 9
+# spatial profiles (include/emdee_hip.h: emdee_md_set_spatial)
+SPATIAL_X, SPATIAL_Y, SPATIAL_Z, SPATIAL_RADIAL = 0, 1, 2, 3
+SPATIAL_DENSITY, SPATIAL_KINETIC, SPATIAL_STRESS, SPATIAL_WORDS = 1, 2, 4, 10
+_SPATIAL_GEOMETRIES = {"x": SPATIAL_X, "y": SPATIAL_Y, "z": SPATIAL_Z, "radial": SPATIAL_RADIAL}
 RESTRAINT_WORDS = 8                                        # (EMDEE_RESTRAINT_WORDS)
 # the centre-of-mass pull (include/emdee_hip.h: emdee_md_set_pull)
 PULL_WORDS, PULL_UMBRELLA, PULL_CONSTANT_FORCE, PULL_DISTANCE, PULL_DIRECTION = 8, 1, 2, 1, 2
@@ -97,7 +101,45 @@ KERNELS = {"lj_force_nbr": 0, "verlet_kick_drift": 1, "rebuild": 2, "verlet_kick
            # the three launches the centre-of-mass pull adds to every force pass (set_pull_): partial sums, finish, apply
            "pull": 19,
            # the row pass of the alchemical table at every rebuild and its launches behind every force pass (set_alchemical_)
-           "alchemical": 20}
+           "alchemical": 20,
+           # the launches of every sample of the spatial profiles (spatial_sample_): gather, accumulate, finish, and two more ahead
+           # of them with a centre group
+           "spatial": 21}
+
+
+def spatial_profiles(geometry, edges, counts, sums, outside, group_sizes, frames, inv_bin_volume_sum):
+    """What follows from the words of emdee_md_spatial_read, as a dict.  edges: the n_bins + 1 bin edges (positions along the axis,
+    or radii); counts (n_groups, n_bins), sums (n_groups, n_bins, 10).  bin_volume: planar frames / inv_bin_volume_sum (the harmonic
+    mean over the frames' boxes), radial the shells' 4 pi / 3 (r_{k+1}^3 - r_k^3).  Densities and pressures are per frame and per
+    bin volume; velocity = sum m v / sum m; kinetic_energy = sum m v^2 / 2 per atom, kinetic_normal the share of the normal
+    component, kinetic_tangential that of ONE tangential component (no Boltzmann constant is applied: a temperature is twice a
+    component's share, over k_B); p_normal = (w6 + w9) / V, p_tangential = ((w5 - w6) + (w8 - w9)) / (2 V).  Planar geometries
+    add gamma_sum = sum_k (P_N - P_T)_k times the bin width: the sum over every interface crossed.  NaN where nothing was counted."""
+    import numpy as np
+    edges = np.asarray(edges, dtype=np.float64)
+    counts, sums = np.asarray(counts, dtype=np.int64), np.asarray(sums, dtype=np.float64)
+    frames = int(frames)
+    if int(geometry) == SPATIAL_RADIAL:
+        volume = 4.0 * np.pi / 3.0 * (edges[1:] ** 3 - edges[:-1] ** 3)
+    else:
+        volume = np.full(edges.shape[0] - 1, frames / inv_bin_volume_sum if inv_bin_volume_sum > 0.0 else np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per = 1.0 / (frames * volume)[None, :] if frames > 0 else np.full((1, volume.shape[0]), np.nan)
+        n = counts.astype(np.float64)
+        velocity = np.where(sums[..., 0:1] != 0.0, sums[..., 2:5] / sums[..., 0:1], np.nan)
+        kinetic = np.where(n > 0, 0.5 * sums[..., 5] / n, np.nan)
+        kinetic_n = np.where(n > 0, 0.5 * sums[..., 6] / n, np.nan)
+        kinetic_t = np.where(n > 0, 0.25 * (sums[..., 5] - sums[..., 6]) / n, np.nan)
+        p_n = (sums[..., 6] + sums[..., 9]) * per
+        p_t = 0.5 * ((sums[..., 5] - sums[..., 6]) + (sums[..., 8] - sums[..., 9])) * per
+    out = dict(edges=edges, centres=0.5 * (edges[1:] + edges[:-1]), bin_volume=volume, counts=counts, sums=sums,
+               outside=[int(t) for t in outside], group_sizes=[int(t) for t in group_sizes], frames=frames,
+               inv_bin_volume_sum=float(inv_bin_volume_sum), number_density=n * per, mass_density=sums[..., 0] * per,
+               charge_density=sums[..., 1] * per, velocity=velocity, kinetic_energy=kinetic, kinetic_normal=kinetic_n,
+               kinetic_tangential=kinetic_t, energy_density=sums[..., 7] * per, p_normal=p_n, p_tangential=p_t)
+    if int(geometry) != SPATIAL_RADIAL:
+        out["gamma_sum"] = ((p_n - p_t) * (edges[1:] - edges[:-1])[None, :]).sum(axis=1)
+    return out
 
 
 class MinimizeResult:
@@ -510,6 +552,60 @@ class VelocityVerlet:
             vacf = np.where(count > 0, sums[..., 6] / count, np.nan)
         return dict(lags=np.arange(n_lags), origins=origins, group_sizes=[int(s) for s in sizes], samples=int(samples.value), sums=sums,
                     msd=np.concatenate([per_axis, total[..., None]], axis=2), msd_drift_free=drift_free, vacf=vacf)
+
+    # -- spatial profiles along an axis and around a centre (include/emdee_hip.h: emdee_md_set_spatial; undivided engines)
+    _spatial = None                                        # (geometry, n_bins, n_groups, range) of the table in force
+
+    def set_spatial_(self, geometry, n_bins, groups=None, n_groups=None, range=None, centre=None, centre_group=-1, density=True,
+                     kinetic=True, stress=True):
+        """The table spatial_sample_() fills.  geometry: "x", "y", "z" (planar slabs normal to that axis; range=None on a periodic
+        axis, whose bins are fractions of the box, range=(r0, r1) on an open one) or "radial" (shells up to r_max: range=(0, r_max)
+        or range=r_max; the centre is `centre`, or with centre_group >= 0 the centre of mass of that group, formed on the device
+        at every sample).  groups / n_groups as set_msd_ takes them.  density / kinetic / stress: which words to keep (see
+        spatial()).  n_bins = 0 clears the table.  Zeroes the sums."""
+        geometry = _SPATIAL_GEOMETRIES[geometry] if isinstance(geometry, str) else int(geometry)
+        (g,), n_groups = self._per_atom_i32("set_spatial_", n_groups, groups=groups)
+        what = (SPATIAL_DENSITY if density else 0) | (SPATIAL_KINETIC if kinetic else 0) | (SPATIAL_STRESS if stress else 0)
+        if range is not None:
+            try:
+                range = (float(range[0]), float(range[1]))
+            except TypeError:
+                range = (0.0, float(range))
+        rng = (C.c_double * 2)(*range) if range is not None else None
+        ctr = (C.c_double * 3)(*_three(centre)) if centre is not None else None
+        _lib.call("emdee_md_set_spatial", self._handle, geometry, what, int(n_bins), n_groups,
+                  C.c_void_p(g.data_ptr()) if g is not None else None, rng, ctr, int(centre_group))
+        self._spatial = (geometry, int(n_bins), n_groups, range) if int(n_bins) != 0 else None
+
+    def spatial_sample_(self):
+        """Adds the current state to the profiles as one frame: queued on the stream, nothing read back, the run untouched (with
+        stress the tensor pass is evaluated first if it is not current)."""
+        _lib.call("emdee_md_spatial_sample", self._handle)
+
+    def spatial_reset_(self):
+        """Zeroes the counts, the sums, outside, the frame count and the sum of 1 / V_bin."""
+        _lib.call("emdee_md_spatial_reset", self._handle)
+
+    def spatial(self):
+        """The accumulated profiles and what follows from them (spatial_profiles), as a dict (blocking): edges (of the current box
+        on a periodic axis), centres, bin_volume, counts ((n_groups, n_bins) int64), sums ((n_groups, n_bins, 10): the raw words of
+        emdee_md_spatial_read), outside, group_sizes, frames, inv_bin_volume_sum, number_density, mass_density, charge_density,
+        velocity, kinetic_energy, kinetic_normal, kinetic_tangential, energy_density, p_normal, p_tangential and, planar,
+        gamma_sum."""
+        import numpy as np
+        if self._spatial is None:
+            raise ValueError("spatial: no table is set (set_spatial_)")
+        geometry, n_bins, n_groups, rng = self._spatial
+        counts = np.zeros((n_groups, n_bins), dtype=np.int64)
+        sums = np.zeros((n_groups, n_bins, SPATIAL_WORDS), dtype=np.float64)
+        outside, sizes, frames, ivs = (C.c_int64 * 8)(), (C.c_int64 * 8)(), C.c_int64(), C.c_double()
+        _lib.call("emdee_md_spatial_read", self._handle, counts.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p), outside,
+                  sizes, C.byref(frames), C.byref(ivs))
+        if rng is None:
+            lo, ln = self.box()
+            rng = (float(lo[geometry]), float(lo[geometry]) + float(ln[geometry]))
+        edges = rng[0] + (rng[1] - rng[0]) * np.arange(n_bins + 1, dtype=np.float64) / n_bins
+        return spatial_profiles(geometry, edges, counts, sums, list(outside)[:n_groups], list(sizes)[:n_groups], frames.value, ivs.value)
 
     # -- Green-Kubo observables: stress and heat-flux autocorrelations (include/emdee_hip.h: emdee_md_set_gk; undivided engines)
     _gk = None                                             # n_lags of the table in force

@@ -237,6 +237,8 @@ int32_t emdee_md_set_bonded(emdee_md *md, int32_t kind, const int32_t *atoms_dev
  *     tensors (emdee_md_get_state with any of them, _energies, _virial_tensor, _pressure_tensor) until the charges are set
  *     again or cleared; positions and velocities can still be read.
  *   - n = 0 clears the charges (the constants are then not looked at): the engine runs the uncharged kernels again.
+ *   - The engine keeps two fp64 tables of n entries on the device: sqrt(K) q for its kernels, and the charges as given, for the
+ *     charge word of emdee_md_set_spatial (q is not recovered exactly from sqrt(K) q): 16 bytes per atom, one more upload per call.
  *   - All or nothing: EMDEE_ERR_INVALID, the previous charges in force, for a NULL array with n > 0, the wrong n, a non-finite
  *     charge, K not finite or <= 0, eps_rf < 1 or NaN, a non-finite or negative coulomb14scale.
  *   - The 1-4 pairs themselves come from emdee_*_set_pairs14.
@@ -1025,6 +1027,87 @@ int32_t emdee_md_set_gk(emdee_md *md, int32_t what, int32_t n_lags);
 int32_t emdee_md_gk_sample(emdee_md *md);
 int32_t emdee_md_gk_read(emdee_md *md, double *sums, double totals[9], double last[9], int64_t *samples);
 int32_t emdee_md_gk_reset(emdee_md *md);
+
+/* Spatial profiles along an axis and around a centre (build-defined: the reference has no analysis).  What a slab, a droplet or a
+ * box with vacuum in it is run for: the density profile across the interface, the normal and tangential pressure profiles and the
+ * surface tension they integrate to, the temperature, flow and charge profiles, the radial profiles of a droplet.  The engine holds
+ * every addend on the device -- positions and image counts, full-step velocities and inverse masses, the charges, the per-atom
+ * energies and virial tensors of the tensor pass -- so a sample costs no copy of the state: ten fp64 words per (group, bin).
+ *
+ * emdee_md_set_spatial(geometry, what, n_bins, n_groups, group_dev, range, centre, centre_group) sets the table (blocking; n_bins = 0
+ * clears it):
+ *   geometry: EMDEE_SPATIAL_X, _Y, _Z: planar slabs normal to that axis, n = e_d.  On a periodic axis range must be NULL and the bins
+ *   are fractions of the box, bin = floor((x_d - lo_d) n_bins / len_d) wrapped into 0...n_bins-1: they follow the box under a
+ *   barostat.  On an open axis range = {r0, r1} is required, finite, r0 < r1, in absolute coordinates; an atom outside [r0, r1) adds 1
+ *   to outside[group] and nothing else (atoms beyond the faces of an open axis are ordinary atoms here).
+ *   EMDEE_SPATIAL_RADIAL: spherical shells, n = r / |r|, range = {0, r_max}, bin = (int)(r n_bins / r_max), r >= r_max is outside.
+ *   r_max may be at most half the shortest PERIODIC side (a droplet box has none and no limit); distances are minimum-image on the
+ *   periodic axes only.  The centre is centre[3] when centre_group = -1; otherwise the mass-weighted centre of the atoms of that
+ *   group, formed on the device in fp64 at every sample from the unwrapped coordinates -- the group is loaded whole, as for
+ *   emdee_md_set_pull -- with nothing read back; a centre group of total mass 0 is refused.  Its order is fixed so that a host
+ *   can repeat it bit for bit from the coordinates emdee_md_get_state returns: per chunk of 1024 atoms of the group, ascending
+ *   caller id, the products m x, m y, m z (each rounded on its own) and m go through a halving tree (s[i] += s[i + h], h = 512 ... 1,
+ *   zeros beyond the count), the chunks' totals are added in chunk order, and R = (sum m x) / M.
+ *   what: a non-empty mask.  sums[(g n_bins + k) EMDEE_SPATIAL_WORDS + w], all fp64:
+ *     EMDEE_SPATIAL_DENSITY  w = 0: sum m;  1: sum q (0 on an engine without charges)
+ *     EMDEE_SPATIAL_KINETIC  w = 2, 3, 4: sum m v_x, m v_y, m v_z;  5: sum m v^2;  6: sum m (v . n)^2
+ *     EMDEE_SPATIAL_STRESS   w = 7: sum e_i;  8: sum tr W_i;  9: sum n . W_i . n
+ *   m = 1 / (double)inv_mass, exactly 0 for inv_mass = 0 (a virtual site is binned where it sits, with mass 0); v the velocities
+ *   emdee_md_energies takes; e_i and W_i the per-atom energies and tensors behind emdee_md_get_state and emdee_md_virial_tensor.  On
+ *   the centre of the radial geometry n is undefined: words 6 and 9 take a third of words 5 and 8 there.  A bit that is off runs none
+ *   of its loads and leaves its words exactly 0.  counts[g n_bins + k] (64-bit) is always kept.  With V_bin the bin's volume,
+ *     P_N = (w6 + w9) / V_bin,   P_T = ((w5 - w6) + (w8 - w9)) / (2 V_bin).
+ *   The per-atom split of the tensor pass is what is binned (the half-pair split, as the stress/atom profiles of other packages),
+ *   not the Irving-Kirkwood contour.
+ *   n_bins in 1...4096; n_groups and group_dev as emdee_md_set_msd takes them (1...8 groups, -1 leaves an atom out, NULL with one
+ *   group takes every atom).  Setting a table zeroes the sums.
+ *   - All or nothing, the previous table and its sums in force: EMDEE_ERR_INVALID for an argument outside these limits, a range on a
+ *     periodic axis, no range on an open one, a number that is not finite, an r_max beyond half a periodic side, a centre_group outside
+ *     -1...n_groups-1 or of mass 0; EMDEE_ERR_ALLOC for a failed allocation.
+ *   - EMDEE_ERR_STATE, each with its own text: before emdee_md_set_state; on an integrator lent by emdee_dd_engine; on one with
+ *     ghosts; EMDEE_SPATIAL_STRESS with a rigid or an hbonds table in force (emdee_md_set_rigid3, emdee_md_set_hbonds): the atomic
+ *     tensors lack the constraint virial.  DENSITY and KINETIC are accepted there.  Bonded terms, exclusions, Ewald, PME, virtual
+ *     sites, restraints, pull and alchemical tables all pass: the box sums of emdee_md_pressure_tensor are sums of these same planes.
+ *
+ * emdee_md_spatial_sample adds the current state to the sums: queued on the engine's stream, nothing read back.  With
+ * EMDEE_SPATIAL_STRESS the tensor pass is evaluated first if it is not current, as emdee_md_gk_sample does; without it no pass of
+ * the engine runs at all.  It writes buffers of its own and, with STRESS, the outputs of the tensor pass: an engine that samples and
+ * one that does not stay bit for bit equal.  The host adds 1 to frames and, in the planar geometry, 1 / V_bin of the current box to
+ * inv_bin_volume_sum (V_bin = the cross-section times len_d / n_bins, or times (r1 - r0) / n_bins; shell volumes do not depend on
+ * the box: the radial geometry adds nothing).  A frame stands alone: neither a replaced state of the same size nor a rescaled box is
+ * refused.  fp64 arithmetic from the planes as they are, in both precisions: an fp64 engine bins bit for bit the coordinates
+ * emdee_md_get_state returns, a Float32 engine the record plus the origin of its cell plus the box lengths removed, in double,
+ * unrounded.  The bin is one rule shared by host and device, every difference and product a rounding of its own.  Sums in a fixed
+ * order that depends on the table alone (group-major, ascending caller id, chunks of 1024 atoms of one group; never the device's CU
+ * count or the engine's cell order), no atomics: bitwise reproducible -- two engines given the same calls agree in every bit --
+ * and a rebuild of the neighbour list between two samples of one state changes no bit of the counts and of the DENSITY and KINETIC
+ * words.  The STRESS words read e_i and W_i, which the engine re-evaluates after a rebuild in the order of its new rows: those
+ * inputs move in the last bit, and so may words 7-9.
+ * Device time: emdee_md_kernel_time index 21 covers the sample's own launches, not the tensor pass (index 0 counts that): 3 for every
+ * mask and every geometry (gather, accumulate, finish), 5 with a centre group (the chunks' partial sums and the centre of mass ahead
+ * of them); none when no atom is grouped.
+ *   - EMDEE_ERR_STATE, nothing changed: no table is set; the conditions of the set no longer hold (a rigid or hbonds table attached
+ *     since); the table was set for another number of owned atoms; a barostat has put r_max beyond half a periodic side.
+ * Sampling on a cadence inside emdee_md_step is not offered, as for the radial distribution functions.
+ *
+ * emdee_md_spatial_read (blocking; any pointer may be NULL): the n_groups n_bins counts, the n_groups n_bins EMDEE_SPATIAL_WORDS
+ * sums, outside[8], the eight group sizes, frames and inv_bin_volume_sum; it checks the deferred fault word of the bonded terms.
+ * emdee_md_spatial_reset zeroes the counts, the sums, outside, frames and inv_bin_volume_sum.
+ * Scope: undivided engines; no emdee_dd_* counterpart.  No cylindrical shells, no off-diagonal stress profiles. */
+#define EMDEE_SPATIAL_X        0
+#define EMDEE_SPATIAL_Y        1
+#define EMDEE_SPATIAL_Z        2
+#define EMDEE_SPATIAL_RADIAL   3
+#define EMDEE_SPATIAL_DENSITY  1
+#define EMDEE_SPATIAL_KINETIC  2
+#define EMDEE_SPATIAL_STRESS   4
+#define EMDEE_SPATIAL_WORDS    10
+int32_t emdee_md_set_spatial(emdee_md *md, int32_t geometry, int32_t what, int32_t n_bins, int32_t n_groups,
+                             const int32_t *group_dev, const double range[2], const double centre[3], int32_t centre_group);
+int32_t emdee_md_spatial_sample(emdee_md *md);
+int32_t emdee_md_spatial_read(emdee_md *md, int64_t *counts, double *sums, int64_t outside[8], int64_t group_sizes[8],
+                              int64_t *frames, double *inv_bin_volume_sum);
+int32_t emdee_md_spatial_reset(emdee_md *md);
 
 /* ---- position restraints: harmonic and flat-bottomed, scaled with the box (restraint.hpp)
  * An external field that ties the named atoms to reference points: the stage of an equilibration in which a solute is held near its
