@@ -85,6 +85,10 @@ SIGNATURES = {
     "emdee_md_set_lambda": [_p, _dbl],
     "emdee_md_alchemical_read": [_p, _p],
     "emdee_md_alchemical_log_read": [_p, _p, _p, _p],
+    "emdee_md_set_alchemical_coulomb": [_p, _i32, _dbl, _dbl, _p, _i32],
+    "emdee_md_set_lambda_coulomb": [_p, _dbl],
+    "emdee_md_alchemical_coulomb_read": [_p, _p],
+    "emdee_md_alchemical_coulomb_log_read": [_p, _p, _p, _p],
     "emdee_nbr_list": [_p, _p, _p, _i32],
     "emdee_md_nbr_list": [_p, _p, _p, _i32],
     "emdee_compute_nonbonded": [_p, _p, _p, _p, _p, _dbl, _p, LJModelC, _p, _i32, _i32],

@@ -14,6 +14,8 @@
 // C++ at the top, as the top of pull.hpp is: a stand-alone host program tests them with the host compiler
 // (tests/c/alchemical_host.cpp); the kernels below them need HIP.  DESIGN.md 4l has the algorithm; MdImpl::set_alchemical (impl.hpp)
 // installs a table.
+// The Coulomb stage (emdee_md_set_alchemical_coulomb) puts the soft-core charge term of a reaction-field engine on
+// the same entries: alch_coulomb_pair beside alch_pair, the COUL instances of the two kernels, sums, words and a log of its own.
 #pragma once
 
 #include <cmath>
@@ -33,6 +35,8 @@ namespace emdee {
 constexpr int ALCH_WORDS = 5;                                // (EMDEE_ALCH_WORDS) lambda, U_alch, dU/dlambda, the cross virial, the cross pairs inside rc
 constexpr int ALCH_MAX_FOREIGN = 16;                         // (EMDEE_ALCH_MAX_FOREIGN)
 constexpr int ALCH_SUMS = 4;                                 // the words an owner writes: its half of U, dU/dlambda, W and of the pair count
+constexpr int ALCH_COULOMB_WORDS = 4;                        // (EMDEE_ALCH_COULOMB_WORDS) lambda_q, U_q, dU/dlambda_q, the cross Coulomb virial
+constexpr int ALCH_COULOMB_SUMS = 3;                         // the Coulomb words an owner writes: its half of U_q, dU/dlambda_q and W_q
 
 // what the pair function needs of the model (lj_pair.hpp LJModel): x = r2 idl2 - x0, -r g' = c60 x^2 (1 - x)^2 r2
 template <typename real>
@@ -89,6 +93,47 @@ EMDEE_HD void alch_pair_foreign(real r2, const AlchModel<real> &m, real sigma2, 
     }
 }
 
+// ---- the Coulomb stage (emdee_md_set_alchemical_coulomb): the charge term of the same cross pairs on a reaction-field engine, the
+// soft core of Steinbrecher, Joung & Case 2011 (AMBER) on the reaction field of emdee_md_set_coulomb.  qq = K q_i q_j; k and c the
+// reaction field's constants (lj_pair.hpp Charges: k = (eps_rf - 1) / ((2 eps_rf + 1) rc^3), c = 1/rc + k rc^2); beta a squared length:
+//     rho2 = r2 + beta (1 - lambda_q),  phi = 1/rho + k rho2 - c,  wl = 1/rho^3 - 2 k
+//   E       = lambda_q qq phi
+//   wr2     = lambda_q qq wl          the factor of the force d wr2: finite at r = 0, where the force is 0
+//   W       = wr2 r2                  = -r dE/dr
+//   dEdl    = qq (phi + lambda_q (beta / 2) wl)
+// One inverse square root, no sixth root.  At lambda_q = 0 E, W and wr2 are exactly 0 (dEdl is not); at beta (1 - lambda_q) = 0
+// rho2 == r2 bit for bit and the term is lambda_q times the reaction-field pair; at r = 0 with beta (1 - lambda_q) > 0 everything is
+// finite.  The cutoff is the caller's strict test: with beta (1 - lambda_q) > 0 E(rc) is not 0 (phi vanishes at rho = rc, not at
+// r = rc), the jump GROMACS's soft-core reaction field has as well.
+template <typename real>
+struct AlchRf {
+    real k, c;
+};
+template <typename real>
+EMDEE_HD void alch_coulomb_pair(real r2, real qq, const AlchRf<real> &rf, real lambda_q, real beta, real &E_out, real &W_out, real &dEdl_out,
+                                real &wr2_out) {
+    const real rho2 = r2 + beta * ((real)1 - lambda_q);
+    const real ir = (real)1 / std::sqrt(rho2);
+    const real phi = ir + (rf.k * rho2 - rf.c);
+    const real wl = (ir * ir) * ir - (real)2 * rf.k;
+    dEdl_out = qq * (phi + lambda_q * ((real)0.5 * beta) * wl);
+    if (lambda_q > (real)0) {
+        E_out = lambda_q * (qq * phi);
+        wr2_out = lambda_q * (qq * wl);
+        W_out = wr2_out * r2;
+    } else {                                                 // exactly 0, whatever rho is
+        E_out = (real)0; W_out = (real)0; wr2_out = (real)0;
+    }
+}
+// E at K foreign lambda_q values: K calls of the function above, bit for bit
+template <typename real>
+EMDEE_HD void alch_coulomb_pair_foreign(real r2, real qq, const AlchRf<real> &rf, real beta, const real *lambdas_q, int K, real *E_out) {
+    for (int k = 0; k < K; k++) {
+        real W, dEdl, wr2;
+        alch_coulomb_pair(r2, qq, rf, lambdas_q[k], beta, E_out[k], W, dEdl, wr2);
+    }
+}
+
 // ---- the table checks (emdee_md_set_alchemical): every refusal names the offending value
 inline void alch_check_lambda(const char *what, double lambda) {
     EMDEE_REQUIRE(lambda >= 0.0 && lambda <= 1.0, EMDEE_ERR_INVALID, "%s: lambda = %g is outside [0, 1]", what, lambda);
@@ -111,6 +156,22 @@ inline void alch_check_params(double lambda, double alpha, const double *foreign
     EMDEE_REQUIRE(log_capacity * (2 + n_foreign) <= INT32_MAX / 2, EMDEE_ERR_INVALID, "set_alchemical: log_capacity = %lld with %lld foreign "
                   "lambdas is more than 2^30 words", (long long)log_capacity, (long long)n_foreign);
 }
+// the checks of the Coulomb stage (emdee_md_set_alchemical_coulomb): lambda_q and every foreign lambda_q in [0, 1]; beta >= 0 and
+// finite; as many foreign lambda_q as the table has foreign lambdas (the k-th foreign state is the pair of the two)
+inline void alch_check_lambda_q(const char *what, double lambda_q) {
+    EMDEE_REQUIRE(lambda_q >= 0.0 && lambda_q <= 1.0, EMDEE_ERR_INVALID, "%s: lambda_q = %g is outside [0, 1]", what, lambda_q);
+}
+inline void alch_coulomb_check_params(double lambda_q, double beta, const double *foreign_q, int64_t n_foreign, int64_t table_n_foreign) {
+    alch_check_lambda_q("set_alchemical_coulomb", lambda_q);
+    EMDEE_REQUIRE(std::isfinite(beta) && beta >= 0.0, EMDEE_ERR_INVALID, "set_alchemical_coulomb: beta = %g must be finite and >= 0", beta);
+    EMDEE_REQUIRE(n_foreign == table_n_foreign, EMDEE_ERR_INVALID, "set_alchemical_coulomb: n_foreign = %lld, the alchemical table has %lld "
+                  "foreign lambdas (the k-th foreign state is the pair of the two)", (long long)n_foreign, (long long)table_n_foreign);
+    EMDEE_REQUIRE(n_foreign == 0 || foreign_q, EMDEE_ERR_INVALID, "set_alchemical_coulomb: NULL array of foreign lambda_q with n_foreign = %lld",
+                  (long long)n_foreign);
+    for (int64_t k = 0; k < n_foreign; k++)
+        EMDEE_REQUIRE(foreign_q[k] >= 0.0 && foreign_q[k] <= 1.0, EMDEE_ERR_INVALID, "set_alchemical_coulomb: foreign lambda_q %lld = %g is outside "
+                      "[0, 1]", (long long)k, foreign_q[k]);
+}
 // the flag array as a caller gave it: every entry 0 or 1, at least one 1.  Returns the flagged ids, ascending.
 template <typename T>
 std::vector<int32_t> alch_check_flags(const std::vector<T> &flag) {
@@ -125,8 +186,8 @@ std::vector<int32_t> alch_check_flags(const std::vector<T> &flag) {
                   "the table)");
     return ids;
 }
-// a charged engine: the first flagged atom that carries a charge, or -1 (a Coulomb soft core is not built: scale the solute's
-// charges to zero with emdee_md_set_coulomb first)
+// a charged engine: the first flagged atom that carries a charge, or -1 (refused without the Coulomb stage, and with it under Ewald
+// or PME: scale the solute's charges to zero with emdee_md_set_coulomb first)
 inline int64_t alch_first_charged(const std::vector<int32_t> &flagged, const std::vector<double> &charge) {
     for (int32_t i : flagged)
         if (i >= 0 && (size_t)i < charge.size() && charge[(size_t)i] != 0.0) return i;
@@ -237,15 +298,26 @@ constexpr int ALCH_BLOCK = 256;
 EMDEE_HD int alch_sol_blocks(int n_sol) { return (n_sol + ALCH_BLOCK / WAVE - 1) / (ALCH_BLOCK / WAVE); }
 EMDEE_HD int alch_env_blocks(int n_env) { return (n_env + ALCH_BLOCK - 1) / ALCH_BLOCK; }
 
-// what one lane or thread gathers over its entries
+// The Coulomb stage (emdee_md_set_alchemical_coulomb) of the same launch, the COUL instances: q the plane of sqrt(K) q per cell-order
+// slot that the charged force kernels read (lj_pair.hpp Charges), so that qq is one product; lambda_q and beta host scalars as lambda.
+template <typename real>
+struct AlchCoulomb {
+    const real *q;
+    real lambda_q, beta;
+    AlchRf<real> rf;
+};
+// what one lane or thread gathers over its entries (eq, wq, dlq: the Coulomb stage's U_q, W_q and dU/dlambda_q, kept apart from the
+// Lennard-Jones words of a read; unused, and gone, in the instances without the stage)
 template <typename real, bool TENSOR>
 struct AlchAcc {
     real fx = 0, fy = 0, fz = 0, e = 0, w = 0, dl = 0, np = 0;
     real tv[6] = {0, 0, 0, 0, 0, 0};
+    real eq = 0, wq = 0, dlq = 0;
 };
-template <typename real, bool TENSOR>
-__device__ __forceinline__ void alch_entry(const AlchArgs<real> &a, const AtomView<real> &atoms, const GridP<real> &g, real xi, real yi,
-                                           real zi, real hs_i, real te_i, int q, AlchAcc<real, TENSOR> &s) {
+template <typename real, bool TENSOR, bool COUL>
+__device__ __forceinline__ void alch_entry(const AlchArgs<real> &a, const AlchCoulomb<real> &cq, const AtomView<real> &atoms,
+                                           const GridP<real> &g, real xi, real yi, real zi, real hs_i, real te_i, real q_i, int q,
+                                           AlchAcc<real, TENSOR> &s) {
     real xj, yj, zj, hs_j, te_j;
     load_atom(atoms, q, xj, yj, zj, hs_j, te_j);
     const real dx = min_image(xi - xj, g.plen[0], g.pinv[0]);
@@ -256,33 +328,46 @@ __device__ __forceinline__ void alch_entry(const AlchArgs<real> &a, const AtomVi
     const real sigma = hs_i + hs_j;
     real E, W, dEdl, wr2;
     alch_pair(r2, a.sw, sigma * sigma, te_i * te_j, a.lambda, a.alpha, E, W, dEdl, wr2);
-    s.fx += wr2 * dx; s.fy += wr2 * dy; s.fz += wr2 * dz;
     s.e += E; s.w += W; s.dl += dEdl; s.np += (real)1;
+    if (COUL) {                                              // (wr2_lj + wr2_q) d: at lambda_q = 0 wr2_q is exactly 0, the force the uncharged one
+        real Eq, Wq, dEdlq, wr2q;
+        alch_coulomb_pair(r2, q_i * cq.q[q], cq.rf, cq.lambda_q, cq.beta, Eq, Wq, dEdlq, wr2q);
+        s.eq += Eq; s.wq += Wq; s.dlq += dEdlq;
+        wr2 += wr2q;
+    }
+    s.fx += wr2 * dx; s.fy += wr2 * dy; s.fz += wr2 * dz;
     if (TENSOR) {
         const real hx = wr2 * dx, hy = wr2 * dy, hz = wr2 * dz;
         s.tv[0] += hx * dx; s.tv[1] += hy * dy; s.tv[2] += hz * dz;
         s.tv[3] += hx * dy; s.tv[4] += hx * dz; s.tv[5] += hy * dz;
     }
 }
-// Owner o's sums into the planes under the mask, and its half of U, dU/dlambda, W and the pair count into part[o][0..4)
-template <typename real, bool TENSOR>
+// Owner o's sums into the planes under the mask, and its half of U, dU/dlambda, W and the pair count into part[o][0..4); COUL: U_q and
+// W_q go to the planes with the Lennard-Jones words, and the owner's half of U_q, dU/dlambda_q and W_q to part_q[o][0..3)
+template <typename real, bool TENSOR, bool COUL>
 __device__ __forceinline__ void alch_write(const AlchArgs<real> &a, int o, int p, const AlchAcc<real, TENSOR> &s, int bitmask,
                                            real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir, real *__restrict__ vt,
-                                           double *__restrict__ part) {
+                                           double *__restrict__ part, double *__restrict__ part_q) {
     const real h = (real)0.5;
     if (bitmask & EMDEE_FORCES) { frc[p] += s.fx; frc[a.pitch + p] += s.fy; frc[2 * a.pitch + p] += s.fz; }
-    if (bitmask & EMDEE_ENERGIES) en[p] += h * s.e;
-    if (bitmask & EMDEE_VIRIALS) vir[p] += h * s.w;
+    if (bitmask & EMDEE_ENERGIES) en[p] += h * (COUL ? s.e + s.eq : s.e);
+    if (bitmask & EMDEE_VIRIALS) vir[p] += h * (COUL ? s.w + s.wq : s.w);
     if (TENSOR)
         for (int c = 0; c < 6; c++) vt[c * a.pitch + p] += h * s.tv[c];
     double *out = part + (size_t)ALCH_SUMS * o;
     out[0] = 0.5 * (double)s.e; out[1] = 0.5 * (double)s.dl; out[2] = 0.5 * (double)s.w; out[3] = 0.5 * (double)s.np;
+    if (COUL) {
+        double *oq = part_q + (size_t)ALCH_COULOMB_SUMS * o;
+        oq[0] = 0.5 * (double)s.eq; oq[1] = 0.5 * (double)s.dlq; oq[2] = 0.5 * (double)s.wq;
+    }
 }
-// (TENSOR: the tensor pass's instance; the force and the observable passes keep the instance without the six sums, as k_pairs14)
-template <typename real, bool TENSOR>
-__global__ __launch_bounds__(ALCH_BLOCK) void k_alchemical(AlchArgs<real> a, AtomView<real> atoms, GridP<real> g, int bitmask,
-                                                            real *__restrict__ frc, real *__restrict__ en, real *__restrict__ vir,
-                                                            real *__restrict__ vt, double *__restrict__ part) {
+// (TENSOR: the tensor pass's instance; the force and the observable passes keep the instance without the six sums, as k_pairs14.
+// COUL: the Coulomb stage on a charged engine; the instances without it never touch cq or part_q)
+template <typename real, bool TENSOR, bool COUL>
+__global__ __launch_bounds__(ALCH_BLOCK) void k_alchemical(AlchArgs<real> a, AlchCoulomb<real> cq, AtomView<real> atoms, GridP<real> g,
+                                                            int bitmask, real *__restrict__ frc, real *__restrict__ en,
+                                                            real *__restrict__ vir, real *__restrict__ vt, double *__restrict__ part,
+                                                            double *__restrict__ part_q) {
     const int sol_blocks = alch_sol_blocks(a.n_sol);
     AlchAcc<real, TENSOR> s;
     if ((int)blockIdx.x < sol_blocks) {                      // one wavefront per solute owner, lanes over its entries
@@ -291,13 +376,16 @@ __global__ __launch_bounds__(ALCH_BLOCK) void k_alchemical(AlchArgs<real> a, Ato
         const AlchOwner ow = a.owners[o];
         real xi, yi, zi, hs_i, te_i;
         load_atom(atoms, ow.p, xi, yi, zi, hs_i, te_i);
+        const real q_i = COUL ? cq.q[ow.p] : (real)0;
         const int lane = threadIdx.x & (WAVE - 1);
-        for (int k = lane; k < ow.count; k += WAVE) alch_entry<real, TENSOR>(a, atoms, g, xi, yi, zi, hs_i, te_i, a.xs[ow.start + k], s);
+        for (int k = lane; k < ow.count; k += WAVE)
+            alch_entry<real, TENSOR, COUL>(a, cq, atoms, g, xi, yi, zi, hs_i, te_i, q_i, a.xs[ow.start + k], s);
         s.fx = wave_sum_to_lane63(s.fx); s.fy = wave_sum_to_lane63(s.fy); s.fz = wave_sum_to_lane63(s.fz);
         s.e = wave_sum_to_lane63(s.e); s.w = wave_sum_to_lane63(s.w); s.dl = wave_sum_to_lane63(s.dl); s.np = wave_sum_to_lane63(s.np);
         if (TENSOR)
             for (int c = 0; c < 6; c++) s.tv[c] = wave_sum_to_lane63(s.tv[c]);
-        if (lane == WAVE - 1) alch_write<real, TENSOR>(a, o, ow.p, s, bitmask, frc, en, vir, vt, part);
+        if (COUL) { s.eq = wave_sum_to_lane63(s.eq); s.wq = wave_sum_to_lane63(s.wq); s.dlq = wave_sum_to_lane63(s.dlq); }
+        if (lane == WAVE - 1) alch_write<real, TENSOR, COUL>(a, o, ow.p, s, bitmask, frc, en, vir, vt, part, part_q);
         return;
     }
     const int o = a.n_sol + ((int)blockIdx.x - sol_blocks) * ALCH_BLOCK + threadIdx.x;   // one thread per environment owner
@@ -305,49 +393,64 @@ __global__ __launch_bounds__(ALCH_BLOCK) void k_alchemical(AlchArgs<real> a, Ato
     const AlchOwner ow = a.owners[o];
     real xi, yi, zi, hs_i, te_i;
     load_atom(atoms, ow.p, xi, yi, zi, hs_i, te_i);
-    for (int k = 0; k < ow.count; k++) alch_entry<real, TENSOR>(a, atoms, g, xi, yi, zi, hs_i, te_i, a.xs[ow.start + k], s);
-    alch_write<real, TENSOR>(a, o, ow.p, s, bitmask, frc, en, vir, vt, part);
+    const real q_i = COUL ? cq.q[ow.p] : (real)0;
+    for (int k = 0; k < ow.count; k++) alch_entry<real, TENSOR, COUL>(a, cq, atoms, g, xi, yi, zi, hs_i, te_i, q_i, a.xs[ow.start + k], s);
+    alch_write<real, TENSOR, COUL>(a, o, ow.p, s, bitmask, frc, en, vir, vt, part, part_q);
 }
 // The energies-only instance: U_alch at K foreign lambdas at the current positions.  Every cross pair has exactly one solute atom,
 // and every solute atom is owned: the solute owners' wavefronts alone see each pair once, so the whole E goes to part[o][0 .. K).
+// COUL: a second set of accumulators, U_q at the K foreign lambda_q, to part_q[o][0 .. K).
 template <typename real>
 struct AlchForeign {
     int K;
     real lambda[ALCH_MAX_FOREIGN];
+    real lambda_q[ALCH_MAX_FOREIGN];
 };
-template <typename real>
-__global__ __launch_bounds__(ALCH_BLOCK) void k_alchemical_foreign(AlchArgs<real> a, AtomView<real> atoms, GridP<real> g, AlchForeign<real> f,
-                                                                    double *__restrict__ part) {
+template <typename real, bool COUL>
+__global__ __launch_bounds__(ALCH_BLOCK) void k_alchemical_foreign(AlchArgs<real> a, AlchCoulomb<real> cq, AtomView<real> atoms, GridP<real> g,
+                                                                    AlchForeign<real> f, double *__restrict__ part,
+                                                                    double *__restrict__ part_q) {
     const int o = blockIdx.x * (ALCH_BLOCK / WAVE) + threadIdx.x / WAVE;
     if (o >= a.n_sol) return;
     const AlchOwner ow = a.owners[o];
     real xi, yi, zi, hs_i, te_i;
     load_atom(atoms, ow.p, xi, yi, zi, hs_i, te_i);
+    const real q_i = COUL ? cq.q[ow.p] : (real)0;
     const int lane = threadIdx.x & (WAVE - 1);
-    real e[ALCH_MAX_FOREIGN];
+    real e[ALCH_MAX_FOREIGN], eq[ALCH_MAX_FOREIGN];
 #pragma unroll
-    for (int k = 0; k < ALCH_MAX_FOREIGN; k++) e[k] = 0;
+    for (int k = 0; k < ALCH_MAX_FOREIGN; k++) { e[k] = 0; eq[k] = 0; }
     for (int c = lane; c < ow.count; c += WAVE) {
         real xj, yj, zj, hs_j, te_j;
-        load_atom(atoms, a.xs[ow.start + c], xj, yj, zj, hs_j, te_j);
+        const int q = a.xs[ow.start + c];
+        load_atom(atoms, q, xj, yj, zj, hs_j, te_j);
         const real dx = min_image(xi - xj, g.plen[0], g.pinv[0]);
         const real dy = min_image(yi - yj, g.plen[1], g.pinv[1]);
         const real dz = min_image(zi - zj, g.plen[2], g.pinv[2]);
         const real r2 = dx * dx + dy * dy + dz * dz;
         if (!(r2 < a.rc2)) continue;
         const real sigma = hs_i + hs_j;
+        const real qq = COUL ? q_i * cq.q[q] : (real)0;
 #pragma unroll
         for (int k = 0; k < ALCH_MAX_FOREIGN; k++) {
             if (k >= f.K) continue;
             real E, W, dEdl, wr2;
             alch_pair(r2, a.sw, sigma * sigma, te_i * te_j, f.lambda[k], a.alpha, E, W, dEdl, wr2);
             e[k] += E;
+            if (COUL) {
+                alch_coulomb_pair(r2, qq, cq.rf, f.lambda_q[k], cq.beta, E, W, dEdl, wr2);
+                eq[k] += E;
+            }
         }
     }
 #pragma unroll
     for (int k = 0; k < ALCH_MAX_FOREIGN; k++) {
         const real t = wave_sum_to_lane63(e[k]);
         if (lane == WAVE - 1) part[(size_t)ALCH_MAX_FOREIGN * o + k] = (double)t;
+        if (COUL) {
+            const real tq = wave_sum_to_lane63(eq[k]);
+            if (lane == WAVE - 1) part_q[(size_t)ALCH_MAX_FOREIGN * o + k] = (double)tq;
+        }
     }
 }
 
@@ -367,6 +470,23 @@ struct AlchForeignSums {
         for (int w = 0; w < 8; w++) acc[w] += part[(size_t)ALCH_MAX_FOREIGN * o + first + w];
     }
 };
+// the Coulomb stage's sums, in slots of their own: every owner's half of U_q, dU/dlambda_q and W_q; the solute owners' U_q at the
+// foreign lambda_q
+struct AlchCoulombSums {
+    static constexpr int SUMS = ALCH_COULOMB_SUMS, MAXES = 0;
+    const double *part;
+    __device__ void operator()(int o, double *acc) const {
+        for (int w = 0; w < ALCH_COULOMB_SUMS; w++) acc[w] += part[(size_t)ALCH_COULOMB_SUMS * o + w];
+    }
+};
+struct AlchCoulombForeignSums {
+    static constexpr int SUMS = 8, MAXES = 0;
+    const double *part;
+    int first;
+    __device__ void operator()(int o, double *acc) const {
+        for (int w = 0; w < 8; w++) acc[w] += part[(size_t)ALCH_MAX_FOREIGN * o + first + w];
+    }
+};
 // stage 1 of both sums under the family's own name (reduce_partials is the body, as molecule.hpp k_molecule_partials); stage 2 is
 // k_reduce_final
 template <class Term>
@@ -380,6 +500,11 @@ static __global__ void k_alch_finish(double lambda, const double *__restrict__ t
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     out[0] = lambda; out[1] = tot[0]; out[2] = tot[1]; out[3] = tot[2]; out[4] = tot[3];
 }
+// the Coulomb stage's words: out[0 .. ALCH_COULOMB_WORDS) from the three totals
+static __global__ void k_alch_coulomb_finish(double lambda_q, const double *__restrict__ tot, double *__restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    out[0] = lambda_q; out[1] = tot[0]; out[2] = tot[1]; out[3] = tot[2];
+}
 static __global__ void k_alch_zero_words(double lambda, double *__restrict__ out, int n) {
     const int t = threadIdx.x;
     if (t < n) out[t] = t == 0 ? lambda : 0.0;
@@ -389,6 +514,13 @@ static __global__ void k_alch_log(const double *__restrict__ out, int K, double 
     if (t == 0) entry[0] = out[2];
     if (t == 1) entry[1] = out[1];
     if (t >= 2 && t < 2 + K) entry[t] = out[ALCH_WORDS + t - 2];
+}
+// the second log's entry {dU/dlambda_q, U_q, K foreign U_q}, at the same pass as the first log's
+static __global__ void k_alch_coulomb_log(const double *__restrict__ out, int K, double *__restrict__ entry) {
+    const int t = threadIdx.x;
+    if (t == 0) entry[0] = out[2];
+    if (t == 1) entry[1] = out[1];
+    if (t >= 2 && t < 2 + K) entry[t] = out[ALCH_COULOMB_WORDS + t - 2];
 }
 
 }  // namespace emdee

@@ -483,6 +483,18 @@ int32_t emdee_md_alchemical_read(emdee_md *md, double *words) {
 int32_t emdee_md_alchemical_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->alchemical_log_read(log_dev, count, dropped); });
 }
+int32_t emdee_md_set_alchemical_coulomb(emdee_md *md, int32_t enable, double lambda_q, double beta, const double *foreign_q, int32_t n_foreign) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_alchemical_coulomb(enable, lambda_q, beta, foreign_q, n_foreign); });
+}
+int32_t emdee_md_set_lambda_coulomb(emdee_md *md, double lambda_q) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->set_lambda_coulomb(lambda_q); });
+}
+int32_t emdee_md_alchemical_coulomb_read(emdee_md *md, double *words) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->alchemical_coulomb_read(words); });
+}
+int32_t emdee_md_alchemical_coulomb_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped) {
+    return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->alchemical_coulomb_log_read(log_dev, count, dropped); });
+}
 int32_t emdee_md_kernel_time(emdee_md *md, int32_t kernel, double *total_ms, int64_t *launches) {
     return guarded([&] { REQUIRE_PTR(md, "md"); md->impl->kernel_time(kernel, total_ms, launches); });
 }

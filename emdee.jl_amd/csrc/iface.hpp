@@ -73,6 +73,10 @@ struct IMd {
     virtual void set_lambda(double lambda) = 0;
     virtual void alchemical_read(double *words) = 0;
     virtual void alchemical_log_read(double *log_dev, int64_t *count, int64_t *dropped) = 0;
+    virtual void set_alchemical_coulomb(int32_t enable, double lambda_q, double beta, const double *foreign_q, int32_t n_foreign) = 0;
+    virtual void set_lambda_coulomb(double lambda_q) = 0;
+    virtual void alchemical_coulomb_read(double *words) = 0;
+    virtual void alchemical_coulomb_log_read(double *log_dev, int64_t *count, int64_t *dropped) = 0;
     virtual void set_ewald(double alpha, const int32_t *kmax) = 0;
     virtual void set_pme(double alpha, const int32_t *grid, int32_t order) = 0;
     virtual void get_box(double lo[3], double len[3]) = 0;

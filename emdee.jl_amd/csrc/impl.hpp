@@ -268,13 +268,26 @@ struct MdImpl : IMd {
                 EMDEE_REQUIRE(!sys.groups[k].fault.latched, EMDEE_ERR_STATE, "%s: %s had no solution; replace the table or the state", what, GROUP_TEXT[k].one);
             require_fitting(what, k);
         }
-        // (a Coulomb soft core is not built: on a charged engine the solute's charges are scaled to zero first)
+        // (without the Coulomb stage a charged engine's solute carries no charge: its charges are scaled to zero first.  With the stage
+        // (emdee_md_set_alchemical_coulomb) the reaction field's cross pairs carry the charge term; under Ewald or PME they do not)
         if (!lent && sys.has_alch() && sys.has_charges()) {
             const int64_t i = alch_first_charged(sys.tables->alch.atoms_h, sys.tables->q_h);
-            EMDEE_REQUIRE(i < 0, EMDEE_ERR_STATE, "%s: atom %lld is flagged by the alchemical table (emdee_md_set_alchemical) and carries a charge: "
-                          "the soft core covers the Lennard-Jones coupling only; set the solute's charges to zero (emdee_md_set_coulomb) first", what,
-                          (long long)i);
+            if (!sys.has_alch_coulomb())
+                EMDEE_REQUIRE(i < 0, EMDEE_ERR_STATE, "%s: atom %lld is flagged by the alchemical table (emdee_md_set_alchemical) and carries a charge: "
+                              "the soft core covers the Lennard-Jones coupling only; set the solute's charges to zero (emdee_md_set_coulomb) first", what,
+                              (long long)i);
+            else require_no_recip_solute_charge(what, i);
         }
+    }
+    // the Coulomb stage covers the pair terms of the reaction field: a charged flagged atom under Ewald or PME is refused with the stage
+    // on as it is with the stage off (i: alch_first_charged)
+    void require_no_recip_solute_charge(const char *what, int64_t i) const {
+        if (!sys.has_ewald()) return;
+        const bool pme = sys.ewald.pme.on();
+        EMDEE_REQUIRE(i < 0, EMDEE_ERR_STATE, "%s: atom %lld is flagged by the alchemical table and carries a charge: the Coulomb stage "
+                      "(emdee_md_set_alchemical_coulomb) covers the reaction field only, not %s (%s); set the solute's charges to zero "
+                      "(emdee_md_set_coulomb) or switch the reciprocal sum off first", what, (long long)i,
+                      pme ? "particle-mesh Ewald" : "Ewald summation", pme ? "emdee_md_set_pme" : "emdee_md_set_ewald");
     }
     bool sites_in_use() const { return !lent && n_ghost == 0 && sys.vsites_fit() && !unchecked[VSITES]; }
     // A force pass into the engine's own arrays.  With a site table in force, a pass that writes the force planes is followed by the
@@ -1441,6 +1454,60 @@ struct MdImpl : IMd {
         if (!log_dev || t.log_count == 0) return;
         FenceOut fence(caller_ctx, sys.stream());
         EMDEE_HIP_CHECK(hipMemcpyAsync(log_dev, t.log.ptr, (size_t)t.log_count * (2 + t.n_foreign) * sizeof(double), hipMemcpyDeviceToDevice,
+                                       sys.stream()));
+    }
+    // emdee_md_set_alchemical_coulomb: the Coulomb stage of the table in force, all or nothing; the rows and the CSR do not depend on
+    // it, so nothing is rebuilt: the next step or query evaluates the forces anew.  enable = 0 clears the stage.
+    void set_alchemical_coulomb(int32_t enable, double lambda_q, double beta, const double *foreign_q, int32_t n_foreign) override {
+        use_device(sys.ctx);
+        EMDEE_REQUIRE(!lent, EMDEE_ERR_STATE, "set_alchemical_coulomb: a decomposed run has no alchemical table (this integrator is a domain's, "
+                      "lent by emdee_dd_engine)");
+        Topology::AlchTable &t = sys.own_tables.alch;
+        if (enable) {
+            EMDEE_REQUIRE(t.present, EMDEE_ERR_STATE, "set_alchemical_coulomb: no alchemical table is set (emdee_md_set_alchemical)");
+            EMDEE_REQUIRE(sys.has_charges(), EMDEE_ERR_STATE, "set_alchemical_coulomb: the engine has no charges (call emdee_md_set_coulomb first)");
+            EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "set_alchemical_coulomb: the state has %d ghosts; load a state without ghosts", n_ghost);
+            alch_coulomb_check_params(lambda_q, beta, foreign_q, n_foreign, t.n_foreign);
+            require_no_recip_solute_charge("set_alchemical_coulomb", alch_first_charged(t.atoms_h, sys.tables->q_h));
+        }
+        sys.own_tables.set_alchemical_coulomb(enable, lambda_q, beta, foreign_q, n_foreign, sys.stream());
+        current_mask = 0;
+    }
+    void set_lambda_coulomb(double lambda_q) override {
+        use_device(sys.ctx);
+        Topology::AlchTable &t = sys.own_tables.alch;
+        EMDEE_REQUIRE(!lent && t.present && t.coulomb, EMDEE_ERR_STATE, "set_lambda_coulomb: no Coulomb stage is set (emdee_md_set_alchemical_coulomb)");
+        alch_check_lambda_q("set_lambda_coulomb", lambda_q);
+        t.lambda_q = lambda_q;
+        current_mask = 0;
+    }
+    // lambda_q, U_q, dU/dlambda_q and the cross Coulomb virial of the current positions (a force pass if a lambda or the state changed
+    // since the last), then U_q at the foreign lambda_q (the energies-only launch); blocking, one copy
+    void alchemical_coulomb_read(double *words) override {
+        use_device(sys.ctx);
+        Topology::AlchTable &t = sys.own_tables.alch;
+        EMDEE_REQUIRE(!lent && t.present && t.coulomb, EMDEE_ERR_STATE, "alchemical_coulomb_read: no Coulomb stage is set (emdee_md_set_alchemical_coulomb)");
+        EMDEE_REQUIRE(words, EMDEE_ERR_INVALID, "alchemical_coulomb_read: words is NULL");
+        require_fitting("alchemical_coulomb_read", ALCHEMICAL);
+        EMDEE_REQUIRE(n_ghost == 0, EMDEE_ERR_STATE, "alchemical_coulomb_read: the state has ghosts");
+        if (!(current_mask & EMDEE_FORCES)) forces(EMDEE_FORCES, 0);
+        {
+            typename NbSystem<real>::Timed timed(&sys, T_ALCHEMICAL);
+            sys.queue_alch_foreign();
+        }
+        double h[ALCH_COULOMB_WORDS + ALCH_MAX_FOREIGN];
+        sys.read_back_doubles(h, t.out_q.ptr, ALCH_COULOMB_WORDS + ALCH_MAX_FOREIGN);
+        for (int q = 0; q < ALCH_COULOMB_WORDS + t.n_foreign; q++) words[q] = h[q];
+    }
+    void alchemical_coulomb_log_read(double *log_dev, int64_t *count, int64_t *dropped) override {
+        use_device(sys.ctx);
+        Topology::AlchTable &t = sys.own_tables.alch;
+        EMDEE_REQUIRE(!lent && t.present && t.coulomb, EMDEE_ERR_STATE, "alchemical_coulomb_log_read: no Coulomb stage is set (emdee_md_set_alchemical_coulomb)");
+        if (count) *count = t.log_count;
+        if (dropped) *dropped = t.log_dropped;
+        if (!log_dev || t.log_count == 0) return;
+        FenceOut fence(caller_ctx, sys.stream());
+        EMDEE_HIP_CHECK(hipMemcpyAsync(log_dev, t.log_q.ptr, (size_t)t.log_count * (2 + t.n_foreign) * sizeof(double), hipMemcpyDeviceToDevice,
                                        sys.stream()));
     }
     // emdee_md_set_ewald, emdee_md_set_pme: all or nothing -- every refusal comes before the setting changes.  check(): the host

@@ -245,7 +245,7 @@ struct NbSystem {
     // The energy sums lie right behind FIRE's six words (fire_sums: one copy of seven), the molecules' tensor sums right behind the
     // atomic ones (molecular_tensor_sums: one copy of twenty-four; k_gk_push reads those and the heat sums in one launch).
     enum RedSlot { RED_FIRE = 0, RED_ENERGY = 6, RED_TENSOR = 9, RED_MOLECULE = 21, RED_HEAT = 33, RED_RESTRAINT = 36, RED_ALCH = 44,
-                   RED_ALCH_FOREIGN = 48, RED_TOTALS = 64 };
+                   RED_ALCH_FOREIGN = 48, RED_ALCH_COULOMB = 64, RED_ALCH_COULOMB_FOREIGN = 68, RED_TOTALS = 84 };
     DevBuf<double> red;
     double *red_partials() {
         red.ensure((size_t)RED_MAX_WORDS * RED_MAX_BLOCKS + RED_TOTALS);
@@ -1492,24 +1492,53 @@ struct NbSystem {
         a.rc2 = model.rc2;
         return a;
     }
+    // The Coulomb stage (emdee_md_set_alchemical_coulomb) takes part in a pass when it is set and the engine has charges on the
+    // reaction field; set on an engine whose charges were cleared it is inert (the instances without it run, its words read 0), and
+    // under Ewald or PME the solute carries no charge (MdImpl::require_ready), so that every term would be 0.
+    DevBuf<double> alch_part_q, alch_part_fq;                // per owner ALCH_COULOMB_SUMS words; per solute owner ALCH_MAX_FOREIGN U_q
+    DevBuf<double> alch_part_x;                              // scratch for the Lennard-Jones partials of the words-only launch at lambda_q = 0
+    bool has_alch_coulomb() const { return has_alch() && tables->alch.coulomb; }
+    bool alch_coulomb_active() const { return has_alch_coulomb() && has_charges() && !has_ewald(); }
+    AlchCoulomb<real> alch_coulomb_args() const {
+        AlchCoulomb<real> c{};
+        if (!alch_coulomb_active()) return c;
+        const Topology::AlchTable &t = own_tables.alch;
+        const Charges<real> ch = charge_args();
+        c.q = ch.q;
+        c.lambda_q = (real)t.lambda_q; c.beta = (real)t.beta;
+        c.rf = AlchRf<real>{ch.k, ch.c};
+        return c;
+    }
     // U_alch at the table's foreign lambdas at the current positions, into out[ALCH_WORDS ...): the energies-only instance over the
-    // solute owners and the sums, eight words at a time
+    // solute owners and the sums, eight words at a time; with the Coulomb stage U_q at the foreign lambda_q into out_q[ALCH_COULOMB_WORDS ...)
+    // from the same launch
     void queue_alch_foreign() {
         Topology::AlchTable &t = own_tables.alch;
         if (t.n_foreign == 0) return;
         double *dst = t.out.ptr + ALCH_WORDS;
+        double *dst_q = t.coulomb ? t.out_q.ptr + ALCH_COULOMB_WORDS : nullptr;
+        const bool coul = alch_coulomb_active();
+        if (dst_q && (alch_n_sol == 0 || !coul)) EMDEE_HIP_CHECK(hipMemsetAsync(dst_q, 0, ALCH_MAX_FOREIGN * sizeof(double), stream()));
         if (alch_n_sol == 0) {
             EMDEE_HIP_CHECK(hipMemsetAsync(dst, 0, ALCH_MAX_FOREIGN * sizeof(double), stream()));
             return;
         }
         AlchForeign<real> f{};
         f.K = t.n_foreign;
-        for (int k = 0; k < ALCH_MAX_FOREIGN; k++) f.lambda[k] = (real)t.foreign[k];
-        hipLaunchKernelGGL((k_alchemical_foreign<real>), dim3(alch_sol_blocks(alch_n_sol)), dim3(ALCH_BLOCK), 0, stream(), alch_args(), view(), grid,
-                           f, alch_part_f.ptr);
+        for (int k = 0; k < ALCH_MAX_FOREIGN; k++) { f.lambda[k] = (real)t.foreign[k]; f.lambda_q[k] = (real)t.foreign_q[k]; }
+        if (coul) alch_part_fq.ensure((size_t)ALCH_MAX_FOREIGN * alch_n_sol + 1);
+        with_bool(coul, [&](auto cq) {
+            hipLaunchKernelGGL((k_alchemical_foreign<real, decltype(cq)::value>), dim3(alch_sol_blocks(alch_n_sol)), dim3(ALCH_BLOCK), 0, stream(),
+                               alch_args(), alch_coulomb_args(), view(), grid, f, alch_part_f.ptr, alch_part_fq.ptr);
+        });
         for (int first = 0; first < t.n_foreign; first += 8) {
             const double *tot = queue_alch_sums(alch_n_sol, AlchForeignSums{alch_part_f.ptr, first}, RED_ALCH_FOREIGN + first);
             EMDEE_HIP_CHECK(hipMemcpyAsync(dst + first, tot, 8 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
+        }
+        if (!coul) return;
+        for (int first = 0; first < t.n_foreign; first += 8) {
+            const double *tot = queue_alch_sums(alch_n_sol, AlchCoulombForeignSums{alch_part_fq.ptr, first}, RED_ALCH_COULOMB_FOREIGN + first);
+            EMDEE_HIP_CHECK(hipMemcpyAsync(dst_q + first, tot, 8 * sizeof(double), hipMemcpyDeviceToDevice, stream()));
         }
     }
     void add_alchemical(const Pass<real> &p) {
@@ -1521,21 +1550,47 @@ struct NbSystem {
         t.log_slot = -1;
         Timed timed(this, T_ALCHEMICAL);
         const int owners = alch_n_sol + alch_n_env;
+        const bool coul = alch_coulomb_active() && owners > 0;
         if (owners == 0) {
             hipLaunchKernelGGL(k_alch_zero_words, dim3(1), dim3(64), 0, stream(), t.lambda, t.out.ptr, ALCH_WORDS);
         } else {
             const AlchArgs<real> a = alch_args();
+            const dim3 blocks(alch_sol_blocks(a.n_sol) + alch_env_blocks(a.n_env));
+            if (coul) alch_part_q.ensure((size_t)ALCH_COULOMB_SUMS * (size_t)owners + 1);
+            // At lambda_q = 0 U_q, W_q and the force factor are exactly 0, and the planes come from the instance without the stage
+            // itself: adding the zeros inside the Coulomb instance is not enough for equal bits, since the compiler contracts the
+            // Float32 accumulation differently from instance to instance.  dU/dlambda_q is not 0 there: a second launch of the
+            // Coulomb instance under an empty mask writes the stage's partials alone (its Lennard-Jones partials go to scratch).
+            const bool split = coul && t.lambda_q == 0.0;
             with_bool(p.mask & EMDEE_TENSOR, [&](auto tensor) {
-                hipLaunchKernelGGL((k_alchemical<real, decltype(tensor)::value>), dim3(alch_sol_blocks(a.n_sol) + alch_env_blocks(a.n_env)),
-                                   dim3(ALCH_BLOCK), 0, stream(), a, view(), grid, p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr, alch_part.ptr);
+                with_bool(coul && !split, [&](auto cq) {
+                    hipLaunchKernelGGL((k_alchemical<real, decltype(tensor)::value, decltype(cq)::value>), blocks, dim3(ALCH_BLOCK), 0, stream(), a,
+                                       alch_coulomb_args(), view(), grid, p.mask, frc.ptr, en.ptr, vir.ptr, vt.ptr, alch_part.ptr, alch_part_q.ptr);
+                });
             });
+            if (split) {
+                alch_part_x.ensure((size_t)ALCH_SUMS * (size_t)owners + 1);
+                hipLaunchKernelGGL((k_alchemical<real, false, true>), blocks, dim3(ALCH_BLOCK), 0, stream(), a, alch_coulomb_args(), view(), grid, 0,
+                                   frc.ptr, en.ptr, vir.ptr, vt.ptr, alch_part_x.ptr, alch_part_q.ptr);
+            }
             const double *tot = queue_alch_sums(owners, AlchSums{alch_part.ptr}, RED_ALCH);
             hipLaunchKernelGGL(k_alch_finish, dim3(1), dim3(64), 0, stream(), t.lambda, tot, t.out.ptr);
+        }
+        if (t.coulomb) {                                     // the stage's words: the three sums, or 0 where it is inert
+            if (coul) {
+                const double *tot = queue_alch_sums(owners, AlchCoulombSums{alch_part_q.ptr}, RED_ALCH_COULOMB);
+                hipLaunchKernelGGL(k_alch_coulomb_finish, dim3(1), dim3(64), 0, stream(), t.lambda_q, tot, t.out_q.ptr);
+            } else {
+                hipLaunchKernelGGL(k_alch_zero_words, dim3(1), dim3(64), 0, stream(), t.lambda_q, t.out_q.ptr, ALCH_COULOMB_WORDS);
+            }
         }
         if (slot >= 0) {
             queue_alch_foreign();
             hipLaunchKernelGGL(k_alch_log, dim3(1), dim3(64), 0, stream(), (const double *)t.out.ptr, t.n_foreign,
                                t.log.ptr + (size_t)slot * (2 + t.n_foreign));
+            if (t.coulomb)
+                hipLaunchKernelGGL(k_alch_coulomb_log, dim3(1), dim3(64), 0, stream(), (const double *)t.out_q.ptr, t.n_foreign,
+                                   t.log_q.ptr + (size_t)slot * (2 + t.n_foreign));
         }
     }
 

@@ -411,6 +411,11 @@ struct Topology {
         int log_every = 0, log_capacity = 0;
         long long steps = 0, log_count = 0, log_dropped = 0; // completed steps since the set; entries written; samples dropped
         int log_slot = -1;                                   // the entry the next force pass writes (set by advance(), taken by NbSystem::add_alchemical)
+        // the Coulomb stage (emdee_md_set_alchemical_coulomb): off until it is set; its own words and its own log, on the table's
+        // cadence and capacity, entry j at the same pass as entry j of `log`
+        bool coulomb = false;
+        double lambda_q = 1.0, beta = 0.0, foreign_q[ALCH_MAX_FOREIGN] = {};
+        DevBuf<double> out_q, log_q;                         // out_q: ALCH_COULOMB_WORDS, then the foreign U_q; log_q: capacity x (2 + n_foreign)
         void advance() {
             steps++;
             log_slot = -1;
@@ -426,6 +431,7 @@ struct Topology {
                         int32_t log_capacity, int64_t lim, hipStream_t s) {
         if (!flag_dev) {
             alch.present = false; alch.n = 0; alch.atoms_h.clear();
+            alch.coulomb = false;
             return;
         }
         alch_check_params(lambda, alpha, foreign, n_foreign, log_every, log_capacity);
@@ -447,6 +453,30 @@ struct Topology {
         alch.log_every = log_every; alch.log_capacity = log_capacity;
         alch.steps = 0; alch.log_count = 0; alch.log_dropped = 0; alch.log_slot = -1;
         alch.n = (int)ids.size(); alch.limit = lim; alch.present = true;
+        alch.coulomb = false;                                // (a new table starts without the Coulomb stage)
+    }
+    // The Coulomb stage of the table in force (foreign_q: host); enable = 0 clears it, the other arguments unread.  Every refusal comes
+    // before anything changes.  Setting it restarts the table's count of steps and both logs.
+    void set_alchemical_coulomb(int32_t enable, double lambda_q, double beta, const double *foreign_q, int32_t n_foreign, hipStream_t s) {
+        if (!enable) {
+            alch.coulomb = false;
+            return;
+        }
+        alch_coulomb_check_params(lambda_q, beta, foreign_q, n_foreign, alch.n_foreign);
+        const size_t words = (size_t)ALCH_COULOMB_WORDS + ALCH_MAX_FOREIGN, log_words = (size_t)alch.log_capacity * (2 + alch.n_foreign) + 1;
+        DevBuf<double> out_q, log_q;
+        out_q.ensure(words);
+        log_q.ensure(log_words);
+        EMDEE_HIP_CHECK(hipMemsetAsync(out_q.ptr, 0, words * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipMemsetAsync(log_q.ptr, 0, log_words * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipMemsetAsync(alch.log.ptr, 0, log_words * sizeof(double), s));
+        EMDEE_HIP_CHECK(hipStreamSynchronize(s));
+        // ---- commit
+        alch.out_q.swap(out_q); alch.log_q.swap(log_q);
+        alch.lambda_q = lambda_q; alch.beta = beta;
+        for (int k = 0; k < ALCH_MAX_FOREIGN; k++) alch.foreign_q[k] = k < n_foreign ? foreign_q[k] : 0.0;
+        alch.steps = 0; alch.log_count = 0; alch.log_dropped = 0; alch.log_slot = -1;
+        alch.coulomb = true;
     }
 };
 

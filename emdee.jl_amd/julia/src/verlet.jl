@@ -10,6 +10,7 @@ export set_spatial!, spatial_sample!, spatial_reset!, spatial_read
 export set_restraints!, restraint_sums, restraint_refs!
 export set_pull!, pull_read, pull_log_read!
 export set_alchemical!, set_lambda!, alchemical_read, alchemical_log_read!
+export set_alchemical_coulomb!, set_lambda_coulomb!, alchemical_coulomb_read, alchemical_coulomb_log_read!
 
 mutable struct VelocityVerlet{T}
     handle::Ptr{Cvoid}
@@ -199,6 +200,42 @@ end
 function alchemical_log_read!(md::VelocityVerlet, out::HipArray{Float64,2})
     count, dropped = Ref{Int64}(0), Ref{Int64}(0)
     check(ccall((:emdee_md_alchemical_log_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), md.handle, out.ptr, count, dropped))
+    return count[], dropped[]
+end
+
+# int32_t emdee_md_set_alchemical_coulomb(emdee_md *md, int32_t enable, double lambda_q, double beta, const double *foreign_q,
+#                                         int32_t n_foreign);
+# The Coulomb stage of the alchemical table in force, on the reaction field: every cross pair's charge term becomes
+# lambda_q qq (1/rho + k_rf rho^2 - c_rf) with rho^2 = r^2 + beta (1 - lambda_q).  foreign_q: HOST Float64 vector, as long as the table's
+# foreign lambdas.  No rebuild; restarts the table's step count and both logs.  lambda_q = `nothing` clears the stage.
+function set_alchemical_coulomb!(md::VelocityVerlet, lambda_q::Union{Nothing,Real}; beta::Real=0.0, foreign_q::Vector{Float64}=Float64[])
+    if lambda_q === nothing
+        return check(ccall((:emdee_md_set_alchemical_coulomb, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Ptr{Float64}, Int32),
+                           md.handle, 0, 1.0, 0.0, C_NULL, 0))
+    end
+    check(ccall((:emdee_md_set_alchemical_coulomb, libemdee_hip), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Ptr{Float64}, Int32), md.handle, 1,
+                lambda_q, beta, isempty(foreign_q) ? C_NULL : foreign_q, length(foreign_q)))
+end
+
+# int32_t emdee_md_set_lambda_coulomb(emdee_md *md, double lambda_q);
+# (a host scalar: no rebuild; the next step or query evaluates the forces anew)
+set_lambda_coulomb!(md::VelocityVerlet, lambda_q::Real) =
+    check(ccall((:emdee_md_set_lambda_coulomb, libemdee_hip), Int32, (Ptr{Cvoid}, Float64), md.handle, lambda_q))
+
+# int32_t emdee_md_alchemical_coulomb_read(emdee_md *md, double *words);
+# (blocking) {lambda_q, U_q, dU_q/dlambda_q, the cross Coulomb virial}, then U_q at the n_foreign foreign lambda_q
+function alchemical_coulomb_read(md::VelocityVerlet, n_foreign::Integer)
+    w = zeros(Float64, 4 + n_foreign)
+    check(ccall((:emdee_md_alchemical_coulomb_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Float64}), md.handle, w))
+    return w
+end
+
+# int32_t emdee_md_alchemical_coulomb_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
+# The second log so far into a device Float64 array (2 + n_foreign, capacity) of {dU_q/dlambda_q, U_q, foreign ...}; returns (count, dropped).
+function alchemical_coulomb_log_read!(md::VelocityVerlet, out::HipArray{Float64,2})
+    count, dropped = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:emdee_md_alchemical_coulomb_log_read, libemdee_hip), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), md.handle, out.ptr, count,
+                dropped))
     return count[], dropped[]
 end
 

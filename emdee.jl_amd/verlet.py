@@ -41,6 +41,7 @@ PULL_WORDS, PULL_UMBRELLA, PULL_CONSTANT_FORCE, PULL_DISTANCE, PULL_DIRECTION = 
 _PULL_KINDS = {"umbrella": PULL_UMBRELLA, "constant-force": PULL_CONSTANT_FORCE, "constant_force": PULL_CONSTANT_FORCE}
 _PULL_GEOMETRIES = {"distance": PULL_DISTANCE, "direction": PULL_DIRECTION}
 ALCH_WORDS, ALCH_MAX_FOREIGN = 5, 16                       # (EMDEE_ALCH_WORDS, EMDEE_ALCH_MAX_FOREIGN: emdee_md_set_alchemical)
+ALCH_COULOMB_WORDS = 4                                     # (EMDEE_ALCH_COULOMB_WORDS: emdee_md_set_alchemical_coulomb)
 
 
 def _three(v):
@@ -905,12 +906,14 @@ class VelocityVerlet:
         if flag is None:
             _lib.call("emdee_md_set_alchemical", self._handle, None, 1.0, 0.0, None, 0, 0, 0)
             self._alch = None
+            self._alch_q = False
             return
         (f,), _ = self._per_atom_i32("set_alchemical_", 1, flag=flag)
         fl = np.ascontiguousarray(np.asarray(foreign, dtype=np.float64).reshape(-1))
         _lib.call("emdee_md_set_alchemical", self._handle, C.c_void_p(f.data_ptr()), float(lam), float(alpha),
                   fl.ctypes.data_as(C.c_void_p) if fl.size else None, int(fl.size), int(log_every), int(log_capacity))
         self._alch = (int(fl.size), int(log_capacity))
+        self._alch_q = False                               # (a new table starts without the Coulomb stage)
 
     def set_lambda_(self, lam):
         """Moves lambda (a host scalar: no rebuild); the next step_ or query evaluates the forces anew.  For slow growth and lambda
@@ -939,6 +942,53 @@ class VelocityVerlet:
         buf = torch.zeros((max(cap, 1), 2 + nf), dtype=torch.float64, device=self.device)
         count, dropped = C.c_int64(), C.c_int64()
         _lib.call("emdee_md_alchemical_log_read", self._handle, C.c_void_p(buf.data_ptr()), C.byref(count), C.byref(dropped))
+        h = buf[:count.value].cpu().numpy()
+        return dict(dUdl=h[:, 0].copy(), U=h[:, 1].copy(), foreign=h[:, 2:].copy(), count=int(count.value), dropped=int(dropped.value))
+
+    # -- the Coulomb stage of the alchemical table (include/emdee_hip.h: emdee_md_set_alchemical_coulomb; reaction-field engines)
+    _alch_q = False
+
+    def set_alchemical_coulomb_(self, lam_q, beta=0.0, foreign_q=()):
+        """The Coulomb stage of the alchemical table in force, on the reaction field of set_coulomb_ (include/emdee_hip.h
+        emdee_md_set_alchemical_coulomb): every cross pair's charge term becomes U_q = lam_q qq (1/rho + k_rf rho^2 - c_rf) with
+        rho^2 = r^2 + beta (1 - lam_q); the solute's internal pairs keep their charges.  beta: a squared length in the caller's
+        units.  foreign_q: as many lambda_q as the table has foreign lambdas; the k-th foreign state is (foreign[k], foreign_q[k]).
+        Restarts the table's step count and both logs; no rebuild.  lam_q = None clears the stage."""
+        import numpy as np
+        if lam_q is None:
+            _lib.call("emdee_md_set_alchemical_coulomb", self._handle, 0, 1.0, 0.0, None, 0)
+            self._alch_q = False
+            return
+        fq = np.ascontiguousarray(np.asarray(foreign_q, dtype=np.float64).reshape(-1))
+        _lib.call("emdee_md_set_alchemical_coulomb", self._handle, 1, float(lam_q), float(beta),
+                  fq.ctypes.data_as(C.c_void_p) if fq.size else None, int(fq.size))
+        self._alch_q = True
+
+    def set_lambda_coulomb_(self, lam_q):
+        """Moves lambda_q (a host scalar: no rebuild); the next step_ or query evaluates the forces anew."""
+        _lib.call("emdee_md_set_lambda_coulomb", self._handle, float(lam_q))
+
+    set_alchemical_coulomb, set_lambda_coulomb = set_alchemical_coulomb_, set_lambda_coulomb_
+
+    def alchemical_coulomb(self):
+        """The Coulomb stage's words of the current positions (blocking), as a dict: lam_q, U (U_q), dUdl (dU_q/dlam_q), virial (the
+        cross pairs' scalar Coulomb virial) and foreign, float64 numpy (n_foreign,) of U_q at the foreign lambda_q."""
+        import numpy as np
+        if self._alch is None or not self._alch_q:
+            raise RuntimeError("alchemical_coulomb: no Coulomb stage is set (set_alchemical_coulomb_)")
+        w = np.zeros(ALCH_COULOMB_WORDS + self._alch[0], dtype=np.float64)
+        _lib.call("emdee_md_alchemical_coulomb_read", self._handle, w.ctypes.data_as(C.c_void_p))
+        return dict(lam_q=float(w[0]), U=float(w[1]), dUdl=float(w[2]), virial=float(w[3]), foreign=w[ALCH_COULOMB_WORDS:].copy())
+
+    def alchemical_coulomb_log(self):
+        """The Coulomb stage's on-device log so far (blocking), as a dict: dUdl and U, float64 numpy (count,), foreign (count,
+        n_foreign); entry j is taken at the same pass as entry j of alchemical_log(); count; dropped."""
+        if self._alch is None or not self._alch_q:
+            raise RuntimeError("alchemical_coulomb_log: no Coulomb stage is set (set_alchemical_coulomb_)")
+        nf, cap = self._alch
+        buf = torch.zeros((max(cap, 1), 2 + nf), dtype=torch.float64, device=self.device)
+        count, dropped = C.c_int64(), C.c_int64()
+        _lib.call("emdee_md_alchemical_coulomb_log_read", self._handle, C.c_void_p(buf.data_ptr()), C.byref(count), C.byref(dropped))
         h = buf[:count.value].cpu().numpy()
         return dict(dUdl=h[:, 0].copy(), U=h[:, 1].copy(), foreign=h[:, 2:].copy(), count=int(count.value), dropped=int(dropped.value))
 

@@ -1222,8 +1222,8 @@ int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, in
 
 /* ---- soft-core alchemical decoupling (alchemical.hpp)
  * The Lennard-Jones stage of a solvation free energy: the coupling of one group of atoms, the solute, to everything else is turned
- * off along lambda through a soft core.  (The Coulomb stage needs no call of its own: scale the solute's charges with
- * emdee_md_set_coulomb.)  Every pair of one flagged and one unflagged atom inside the cutoff interacts by
+ * off along lambda through a soft core.  (The Coulomb stage of a reaction-field engine is emdee_md_set_alchemical_coulomb, below.)
+ * Every pair of one flagged and one unflagged atom inside the cutoff interacts by
  *     u = (r^2 / sigma_ij^2)^3,  D = alpha (1 - lambda) + u,  U(r; lambda) = lambda 4 eps_ij (D^-2 - D^-1) g(r)
  * -- Beutler et al. 1994 with lambda-power 1 and r-power 6 (GROMACS sc-power = 1, sc-r-power = 6); sigma_ij and 4 eps_ij from the
  * atoms' own records, g the model's switch, r^2 < rc^2 the test of every pair loop.  Flagged-flagged and unflagged-unflagged pairs
@@ -1259,7 +1259,7 @@ int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, in
  *     negative log_every or log_capacity, or a log without log_every >= 1.  The text names the entry and the value.
  *   - EMDEE_ERR_STATE, the previous table in force: a call before emdee_md_set_state; ghosts; an integrator lent by emdee_dd_engine.
  *     The reads and emdee_md_set_lambda refuse without a table.  A force pass on the operator path refuses with a table.
- *   - On a charged engine every flagged atom must carry charge 0 -- a Coulomb soft core is not built: otherwise emdee_md_step and
+ *   - On a charged engine without the Coulomb stage (below) every flagged atom must carry charge 0: otherwise emdee_md_step and
  *     emdee_md_minimize refuse (EMDEE_ERR_STATE), naming the first such atom.  With zero charges the reaction field, Ewald and PME
  *     need nothing.
  *   - Flagged atoms may be atoms of rigid molecules, of hbonds clusters, or virtual sites: the flag says nothing about constraints.
@@ -1267,15 +1267,60 @@ int32_t emdee_md_pull_log_read(emdee_md *md, double *log_dev, int64_t *count, in
  *     emdee_md_minimize, emdee_md_scale_box and the reads refuse (EMDEE_ERR_STATE) until the table is set again or cleared.
  *   - The Green-Kubo heat flux (EMDEE_GK_HEAT) is refused with an alchemical table, at set and at sample.
  * Device time: emdee_md_kernel_time index 20 (the row pass at a rebuild and the launches behind a force pass).
- * Scope: undivided engines.  Follow-ups, not here: a Coulomb soft core; more than one group, each with its own lambda; annihilation
- * of the solute's internal pairs; decomposed runs. */
+ * Scope: undivided engines.  Follow-ups, not here: a Coulomb soft core under Ewald or PME (the solute's and the environment's structure
+ * factors or charge meshes kept apart); more than one group, each with its own lambda; annihilation of the solute's internal pairs;
+ * decomposed runs; a per-pair soft-core length.
+ *
+ * ---- the Coulomb stage (reaction-field engines)
+ * emdee_md_set_alchemical_coulomb turns the charge term of the same cross pairs -- one flagged, one unflagged atom, the entries of the
+ * table's CSR with r^2 < rc^2 -- into AMBER's soft-core Coulomb (Steinbrecher, Joung & Case 2011) on the reaction field of
+ * emdee_md_set_coulomb.  With qq = K q_i q_j and the engine's k_rf and c_rf (k_rf = (eps_rf - 1) / ((2 eps_rf + 1) rc^3),
+ * c_rf = 1 / rc + k_rf rc^2):
+ *     rho2 = r^2 + beta (1 - lambda_q),  phi = 1 / rho + k_rf rho2 - c_rf,  wl = 1 / rho^3 - 2 k_rf
+ *     U_q = lambda_q qq phi,  force = lambda_q qq wl d,  W_q = lambda_q qq wl r^2 = -r dU_q/dr,
+ *     dU_q/dlambda_q = qq (phi + lambda_q (beta / 2) wl)
+ * The solute's internal pairs keep their full charges: DECOUPLING, NOT ANNIHILATION (scaling the solute's charges with
+ * emdee_md_set_coulomb would scale those too, and yields neither dU/dlambda nor foreign energies).  At lambda_q = 0 U_q, W_q and the force
+ * are exactly 0 (dU_q/dlambda_q is not); at beta (1 - lambda_q) = 0 the term is lambda_q times the model's own reaction-field pair; at
+ * r = 0 with beta (1 - lambda_q) > 0 everything is finite and the force is 0.  The cutoff is the strict test r^2 < rc^2 of every pair
+ * loop: for beta (1 - lambda_q) > 0 U_q(rc) is not 0 (phi vanishes at rho = rc), a jump of the energy at the cutoff that GROMACS's
+ * soft-core reaction field has as well.  1-4 and excluded cross pairs are struck before the alchemical pass and keep their treatment.
+ *   enable        0 clears the stage (the other arguments are not looked at); a new emdee_md_set_alchemical, set or clear, clears it too.
+ *   lambda_q      in [0, 1]; emdee_md_set_lambda_coulomb moves it later (a host scalar: no rebuild).
+ *   beta          the soft-core length squared, in the caller's units of length^2, finite and >= 0.
+ *   foreign_q     HOST, n_foreign doubles in [0, 1]; n_foreign must equal the table's: the k-th foreign state is the pair
+ *                 (foreign[k], foreign_q[k]).  May be NULL with n_foreign = 0.
+ * Opt-in: without the call an engine is launch for launch and bit for bit what it was, the refusal of a charged flagged atom included.
+ * With it, and with charges, the launch behind every force pass takes its Coulomb instance: the charge term is formed beside the
+ * Lennard-Jones one on the same entries, (wr2_lj + wr2_q) d goes to the force, U_q and W_q to the energy, virial and tensor planes; the
+ * sums of U_q, dU_q/dlambda_q and W_q stay on the device, fixed order, no atomics, bitwise reproducible.  emdee_md_alchemical_read and
+ * emdee_md_alchemical_log_read keep their layout and meaning: the Lennard-Jones words alone.
+ * emdee_md_alchemical_coulomb_read (blocking): words[0 .. EMDEE_ALCH_COULOMB_WORDS) = {lambda_q, U_q, dU_q/dlambda_q, W_q (the cross
+ * Coulomb virial)} of the current positions, then U_q at the n_foreign foreign_q (the energies-only launch).
+ * emdee_md_alchemical_coulomb_log_read: a second on-device log of {dU_q/dlambda_q, U_q, the n_foreign foreign U_q} per entry, on the
+ * table's own log_every and log_capacity; its entry j is taken at the same pass as entry j of the table's log, and count and dropped
+ * are the same.  Setting the stage restarts the table's step count and both logs.
+ *   - All or nothing; the previous stage stays in force; the text names the value.  EMDEE_ERR_INVALID: lambda_q or a foreign lambda_q
+ *     outside [0, 1] or NaN; beta negative or not finite; n_foreign different from the table's, or a NULL array with n_foreign > 0.
+ *   - EMDEE_ERR_STATE: no alchemical table; no charges (emdee_md_set_coulomb); ghosts; an integrator lent by emdee_dd_engine.  The
+ *     reads and emdee_md_set_lambda_coulomb refuse without the stage.
+ *   - Under emdee_md_set_ewald or emdee_md_set_pme a charged flagged atom is refused (EMDEE_ERR_STATE) with the stage on as with the
+ *     stage off -- at the set and at the readiness check of emdee_md_step and emdee_md_minimize, whichever comes later; the text names
+ *     the atom, this setter and the Ewald or PME setter.  With zero solute charges Ewald and PME keep working.
+ *   - Clearing the charges (emdee_md_set_coulomb with n = 0) leaves the stage set but inert: U_q, dU_q/dlambda_q and W_q read 0. */
 #define EMDEE_ALCH_WORDS           5
 #define EMDEE_ALCH_MAX_FOREIGN     16
+#define EMDEE_ALCH_COULOMB_WORDS   4    /* lambda_q, U_q, dU/dlambda_q, W_q (the cross Coulomb virial) */
 int32_t emdee_md_set_alchemical(emdee_md *md, const int32_t *flag_dev, double lambda, double alpha, const double *foreign,
                                 int32_t n_foreign, int32_t log_every, int32_t log_capacity);
 int32_t emdee_md_set_lambda(emdee_md *md, double lambda);
 int32_t emdee_md_alchemical_read(emdee_md *md, double *words);
 int32_t emdee_md_alchemical_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
+int32_t emdee_md_set_alchemical_coulomb(emdee_md *md, int32_t enable, double lambda_q, double beta, const double *foreign_q,
+                                        int32_t n_foreign);
+int32_t emdee_md_set_lambda_coulomb(emdee_md *md, double lambda_q);
+int32_t emdee_md_alchemical_coulomb_read(emdee_md *md, double *words);
+int32_t emdee_md_alchemical_coulomb_log_read(emdee_md *md, double *log_dev, int64_t *count, int64_t *dropped);
 
 /* ---------------------------------------------------------------- domain decomposition (multi-GPU)
  * Build-defined (the reference is single-GPU; SURVEY.md 8(b) table rows emdee_dd_create / emdee_dd_step, 8(e)).
